@@ -16,13 +16,19 @@ the host cores (pinned to its GPU's NUMA node), keeps it resident and decodes it
 pixels stay where they were decoded.  RCCL carries the barrier that brackets the timed region, the max-over-ranks
 of the elapsed time, the work counters, and the all-reduce of the per-image checksum / decode-count vectors that
 proves every image of the list was decoded exactly once and equal to its single-GPU decode.  Rank 0 prints ONE
-JSON line.  Besides the kernel-only `value` it carries `end_to_end` -- the same images streamed from host memory
-through jda_pipeline (device filter + pre-scan + decode, batches overlapped), host work included.
+JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the roofline of the timed
+launches).  Everything else moves behind --full: the exactly-once proof of the sharding, the parity check against the
+reference, `end_to_end` -- the same images streamed from host memory through jda_pipeline (device filter + pre-scan +
+decode, batches overlapped), host work included --, the short legs over the other BASELINE configurations and the CPU
+baseline.  --dump-outputs DIR writes what the last timed step decoded (dump_outputs).
 """
 import argparse
 import json
 import os
 import sys
+import threading
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -34,24 +40,80 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
 
 
+def _cache_dirs():
+    """Where cached_jpeg looks for a synthetic input, in this order: bench_cache/ and bench_cold/ in the tree, then the user's
+    cache directory (for a tree the benchmark may not write to)."""
+    dirs = [os.path.join(ROOT, "bench_cache"), os.path.join(ROOT, "bench_cold")]
+    base = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    if os.path.isabs(base):
+        dirs.append(os.path.join(base, "jpegdec_amd", "bench_cache"))
+    return dirs
+
+
 def cached_jpeg(width, height, subsampling, seed, quality=85, restart_rows=0):
-    """Synthetic input (jpegdec_amd/synth.py recipe), cached under bench_cache/ so the GPU box does
-    not spend its minutes on Pillow."""
+    """Synthetic input (jpegdec_amd/synth.py recipe), cached so that later runs do not spend their time on making it again: under
+    bench_cache/ where the tree is writable, else in the user's cache directory, else not at all."""
     from jpegdec_amd.synth import synth_jpeg
 
-    d = os.path.join(ROOT, "bench_cache")
-    os.makedirs(d, exist_ok=True)
     name = "synth_%dx%d_%s_q%d_s%d%s.jpg" % (width, height, subsampling.replace(":", ""), quality, seed,
                                              "_rst%d" % restart_rows if restart_rows else "")
-    for dd in (d, os.path.join(ROOT, "bench_cold")):
+    dirs = _cache_dirs()
+    for dd in dirs:
         if os.path.exists(os.path.join(dd, name)):
             return open(os.path.join(dd, name), "rb").read()
-    path = os.path.join(d, name)
     data = synth_jpeg(width, height, subsampling, seed=seed, quality=quality, restart_rows=restart_rows)
-    with open(path + ".tmp%d" % os.getpid(), "wb") as f:
-        f.write(data)
-    os.replace(path + ".tmp%d" % os.getpid(), path)
+    for dd in [dirs[0]] + dirs[2:]:
+        tmp = os.path.join(dd, "%s.tmp%d_%d" % (name, os.getpid(), threading.get_ident()))
+        try:
+            os.makedirs(dd, exist_ok=True)
+            with open(tmp, "wb") as f:
+                f.write(data)
+            os.replace(tmp, os.path.join(dd, name))
+            break
+        except OSError:
+            try:
+                os.remove(tmp)
+            except OSError:
+                pass
     return data
+
+
+def cached_jpegs(specs):
+    """cached_jpeg for a list of (width, height, subsampling, seed, quality, restart_rows): the distinct inputs are made on
+    threads (the recipe's upsampling, noise and encoding run outside the GIL; the bytes do not depend on the thread count), at
+    most 8 at a time -- a 4096x4096 input takes ~1.4 GB while it is made."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from jpegdec_amd.sharding import cpu_quota
+
+    distinct = list(dict.fromkeys(specs))
+    workers = max(1, min(len(distinct), 8, cpu_quota()[0]))
+    with ThreadPoolExecutor(workers) as ex:
+        made = dict(zip(distinct, ex.map(lambda s: cached_jpeg(s[0], s[1], s[2], s[3], quality=s[4], restart_rows=s[5]), distinct)))
+    return [made[s] for s in specs]
+
+
+DUMP_SAMPLES_PER_IMAGE = 1 << 16
+
+
+def dump_outputs(ctx, out_dir, outputs, geo):
+    """--dump-outputs DIR: the pixels the timed path left in HBM after its last step, for comparing two builds output for output.
+    The visible bytes of every image (out_h rows x out_w * bpp bytes) are read back one image at a time and written as
+      pixels_sample.npy    float32 [images, 65536]  the bytes at one fixed, seeded set of positions (the same for every image)
+      byte_histogram.npy   float64 [images, 256]    how often each byte value occurs in the whole image (exact)
+    -- 16 MiB for the 64-image metric batch."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows, row_bytes = geo["out_h"], geo["out_w"] * geo["bpp"]
+    pos = np.random.default_rng(1234).integers(0, rows * row_bytes, size=DUMP_SAMPLES_PER_IMAGE)
+    r, c = pos // row_bytes, pos % row_bytes
+    sample = np.empty((len(outputs), len(pos)), dtype=np.float32)
+    hist = np.empty((len(outputs), 256), dtype=np.float64)
+    for i, (ptr, pitch, _, canvas_h) in enumerate(outputs):
+        img = ctx.to_host(ptr, pitch * canvas_h).reshape(canvas_h, pitch)[:rows, :row_bytes]
+        sample[i] = img[r, c]
+        hist[i] = np.bincount(np.ascontiguousarray(img).reshape(-1), minlength=256)
+    np.save(os.path.join(out_dir, "pixels_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "byte_histogram.npy"), hist)
 
 
 def cpu_baseline(jpegs, pixel_type, cores, detail, model, wall_target=5.0):
@@ -363,7 +425,7 @@ def run_config_legs(J, ctx, threads, only=None):
         try:
             key = (w, h, sub, q, nd)
             if key not in cache:
-                cache[key] = [cached_jpeg(w, h, sub, 1234 + i, quality=q) for i in range(nd)]
+                cache[key] = cached_jpegs([(w, h, sub, 1234 + i, q, 0) for i in range(nd)])
             out[name] = config_leg(J, ctx, name, what, cache[key], n, pt, opt, threads)
         except Exception as e:  # a leg that fails is reported, the headline stands
             out[name] = {"workload": what, "error": "%s: %s" % (type(e).__name__, e)}
@@ -378,7 +440,7 @@ def run_config_legs(J, ctx, threads, only=None):
         try:
             key = (w, h, sub, q, nd)
             if key not in cache:
-                cache[key] = [cached_jpeg(w, h, sub, 1234 + i, quality=q) for i in range(nd)]
+                cache[key] = cached_jpegs([(w, h, sub, 1234 + i, q, 0) for i in range(nd)])
             out[name] = e2e_config_leg(J, ctx, what, cache[key], n, pt, threads)
         except Exception as e:
             out[name] = {"workload": what, "error": "%s: %s" % (type(e).__name__, e)}
@@ -420,6 +482,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-configs", action="store_true", help="skip the short legs over the other BASELINE.json configurations (`configs` in the line; N = 1, metric workload only)")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend for the control collectives (nccl = RCCL)")
     ap.add_argument("--device-module", default="jpegdec_amd", help="module providing the device half (tests: tests.stub_device, to run the N-rank control flow without a GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity check against the reference, the exactly-once proof of the sharding, the end-to-end leg, "
+                         "the config legs, the CPU baseline and the one-image prepare time (each still switched off by its --no-* option); "
+                         "without it a run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step decoded (rank 0's images) as DIR/*.npy (see dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -480,18 +548,20 @@ def run(args, J, out=sys.stdout):
     else:
         width, height, sub = args.width, args.height, args.subsampling
         n_total = args.batch * world
-        n_distinct = args.distinct or min(16, args.batch)      # (the 4096x4096 q85 set is cached under bench_cache/; other shapes are made on first use)
-    jpegs = [cached_jpeg(width, height, sub, 1234 + i, quality=args.quality, restart_rows=args.restart_rows) for i in range(n_distinct)]
+        n_distinct = args.distinct or min(16, args.batch)      # (made on first use and cached: cached_jpeg)
+    jpegs = cached_jpegs([(width, height, sub, 1234 + i, args.quality, args.restart_rows) for i in range(n_distinct)])
     bits_px = 8.0 * sum(len(j) for j in jpegs) / (len(jpegs) * width * height)
     lo, hi = shard_range(n_total, rank, world)
     my_files = [jpegs[i % n_distinct] for i in range(lo, hi)]
     n_mine = hi - lo
 
     # ---- host prepare of the shard on this rank's threads, upload, launch plan
-    t_prep0 = time.perf_counter()
-    one = J.PreparedImage(jpegs[0], device_prescan=args.device_prescan)
-    t_prep1 = time.perf_counter() - t_prep0                                    # one image, one thread
-    one.close()
+    t_prep1 = None
+    if args.full:
+        t_prep0 = time.perf_counter()
+        one = J.PreparedImage(jpegs[0], device_prescan=args.device_prescan)
+        t_prep1 = time.perf_counter() - t_prep0                                # one image, one thread
+        one.close()
     t_par0 = time.perf_counter()
     prepared = J.prepare_batch(my_files, device_prescan=args.device_prescan, threads=threads)
     t_par = (time.perf_counter() - t_par0) / max(n_mine, 1)
@@ -536,157 +606,158 @@ def run(args, J, out=sys.stdout):
     elapsed = group.max(t1 - t0)         # slowest rank
     kernel_ms = ctx.timer_elapsed_ms() / args.steps
     total_pixels = group.sum(st["source_pixels"])       # whole job, all ranks
+    if args.dump_outputs and rank == 0:                  # (before anything else writes to the surfaces: the end-to-end leg reuses them)
+        dump_outputs(ctx, args.dump_outputs, outputs, geo)
+    sharding = parity = e2e = None
+    if args.full:
+        # ---- the sharding, proved: per-image checksums made where the pixels are, all-reduced; every image exactly once and
+        # equal to the single-GPU decode of its file (rank 0's own decode of the distinct files, broadcast with the same reduce)
+        row_bytes = geo["canvas_w"] * geo["bpp"]
+        sums = ctx.checksums(outputs, [row_bytes] * n_mine)
+        ref_sums = np.zeros(n_distinct, dtype=np.uint64)
+        if rank == 0:
+            have = {}
+            for i in range(lo, hi):
+                have.setdefault(i % n_distinct, sums[i - lo])
+            missing = [d for d in range(n_distinct) if d not in have]
+            if missing:                      # (a shard smaller than the set of distinct files: decode the rest once, here)
+                extra_prep = [J.PreparedImage(jpegs[d]) for d in missing]
+                extra_dev = J.upload_batch(ctx, extra_prep)
+                ex_base = ctx.malloc(img_bytes * len(missing))
+                ex_out = [(ex_base + k * img_bytes, pitch, geo["canvas_w"], geo["canvas_h"]) for k in range(len(missing))]
+                eb = J.Batch(ctx, extra_dev, ex_out, [pt] * len(missing), [args.options] * len(missing))
+                eb.decode(); ctx.sync()
+                for d, v in zip(missing, ctx.checksums(ex_out, [row_bytes] * len(missing))):
+                    have[d] = v
+                eb.close()
+                for d_ in extra_dev:
+                    d_.close()
+                for p_ in extra_prep:
+                    p_.close()
+                ctx.free(ex_base)
+            for d in range(n_distinct):
+                ref_sums[d] = have[d]
+        ref_sums = group.sum_int64_vector(ref_sums.view(np.int64)).view(np.uint64)      # = a broadcast from rank 0
+        sharding = verify_exactly_once(group, n_total, lo, sums, expected_of=lambda i: int(ref_sums[i % n_distinct]))
+        sharding.update({"list": "%d images (%d distinct files), rank r owns the contiguous block shard_range(n, r, %d)" % (n_total, n_distinct, world),
+                         "images_this_rank": n_mine, "host_placement": placement})
 
-    # ---- the sharding, proved: per-image checksums made where the pixels are, all-reduced; every image exactly once and
-    # equal to the single-GPU decode of its file (rank 0's own decode of the distinct files, broadcast with the same reduce)
-    row_bytes = geo["canvas_w"] * geo["bpp"]
-    sums = ctx.checksums(outputs, [row_bytes] * n_mine)
-    ref_sums = np.zeros(n_distinct, dtype=np.uint64)
-    if rank == 0:
-        have = {}
-        for i in range(lo, hi):
-            have.setdefault(i % n_distinct, sums[i - lo])
-        missing = [d for d in range(n_distinct) if d not in have]
-        if missing:                      # (a shard smaller than the set of distinct files: decode the rest once, here)
-            extra_prep = [J.PreparedImage(jpegs[d]) for d in missing]
-            extra_dev = J.upload_batch(ctx, extra_prep)
-            ex_base = ctx.malloc(img_bytes * len(missing))
-            ex_out = [(ex_base + k * img_bytes, pitch, geo["canvas_w"], geo["canvas_h"]) for k in range(len(missing))]
-            eb = J.Batch(ctx, extra_dev, ex_out, [pt] * len(missing), [args.options] * len(missing))
-            eb.decode(); ctx.sync()
-            for d, v in zip(missing, ctx.checksums(ex_out, [row_bytes] * len(missing))):
-                have[d] = v
-            eb.close()
-            for d_ in extra_dev:
-                d_.close()
-            for p_ in extra_prep:
-                p_.close()
-            ctx.free(ex_base)
-        for d in range(n_distinct):
-            ref_sums[d] = have[d]
-    ref_sums = group.sum_int64_vector(ref_sums.view(np.int64)).view(np.uint64)      # = a broadcast from rank 0
-    sharding = verify_exactly_once(group, n_total, lo, sums, expected_of=lambda i: int(ref_sums[i % n_distinct]))
-    sharding.update({"list": "%d images (%d distinct files), rank r owns the contiguous block shard_range(n, r, %d)" % (n_total, n_distinct, world),
-                     "images_this_rank": n_mine, "host_placement": placement})
+        # ---- parity spot check outside the timed region: first image of this rank vs the oracle
+        # (every DISTINCT file of the timed batch is checked, at its first place in this rank's shard)
+        if not args.no_parity and rank == 0:
+            first = {}
+            for i in range(lo, hi):
+                first.setdefault(i % n_distinct, i - lo)
+            checks = [check_against_reference(J, ctx, jpegs[d], pt, args.options, out_base + k * img_bytes, img_bytes, pitch, geo, sums[k]) for d, k in sorted(first.items())]
+            parity = dict(checks[0])
+            parity["distinct_files_checked"] = len(checks)
+            parity["bit_exact"] = None if any(c["bit_exact"] is None for c in checks) else all(c["bit_exact"] for c in checks)
+            parity["device_checksum_equals_host_checksum"] = all(c.get("device_checksum_equals_host_checksum", False) for c in checks)
 
-    # ---- parity spot check outside the timed region: first image of this rank vs the oracle
-    # (every DISTINCT file of the timed batch is checked, at its first place in this rank's shard)
-    parity = None
-    if not args.no_parity and rank == 0:
-        first = {}
-        for i in range(lo, hi):
-            first.setdefault(i % n_distinct, i - lo)
-        checks = [check_against_reference(J, ctx, jpegs[d], pt, args.options, out_base + k * img_bytes, img_bytes, pitch, geo, sums[k]) for d, k in sorted(first.items())]
-        parity = dict(checks[0])
-        parity["distinct_files_checked"] = len(checks)
-        parity["bit_exact"] = None if any(c["bit_exact"] is None for c in checks) else all(c["bit_exact"] for c in checks)
-        parity["device_checksum_equals_host_checksum"] = all(c.get("device_checksum_equals_host_checksum", False) for c in checks)
+        # ---- end to end: the same files streamed from host memory through jda_pipeline (host parse + tables, H2D of the unfiltered
+        # scans, device filter + pre-scan + decode; batches overlapped on three streams), host work included, pixels stay in HBM.
+        # The input lies in page-locked memory (what a loader that feeds a GPU reads into) and is submitted with JDA_SUBMIT_PINNED_INPUT:
+        # the copy engine takes the files where they are, no host core copies them.  Besides the headline figure (this rank's threads,
+        # at most 8): the same with 1, 2, 4, 8 host threads -- an 8-GPU node leaves a rank a few cores --, with COLD input (>= 2 GB of
+        # distinct buffers: nothing the host or the copy engine reads is in a cache), and with pageable input (the pipeline's own
+        # page-locked mirror, filled by the workers).
+        if args.e2e_batches > 0:
+            eb = min(n_mine, args.batch) if args.workload == "metric" else min(n_mine, 256)
+            depth = max(1, min(args.e2e_depth, 4))
+            e2e_distinct = n_distinct
+            pool = jpegs
+            if args.workload == "metric" and args.e2e_distinct > n_distinct:
+                # more distinct files per batch than the resident leg keeps: the pre-scan's late rounds are longer (its chains of changed
+                # entry states differ from file to file), which a batch of two files flatters
+                e2e_distinct = min(args.e2e_distinct, eb)
+                pool = cached_jpegs([(width, height, sub, 1234 + i, args.quality, args.restart_rows) for i in range(e2e_distinct)])
+            picks = [(lo + i) % e2e_distinct for i in range(eb)]
+            surf = [out_base] if eb * depth > n_mine else [out_base + k * eb * img_bytes for k in range(depth)]
+            extra = [ctx.malloc(img_bytes * eb) for _ in range(depth - len(surf))]
+            surf += extra
+            outs_of = [[(base + i * img_bytes, pitch, geo["canvas_w"], geo["canvas_h"]) for i in range(eb)] for base in surf]
+            have_pinned = hasattr(J, "PinnedFiles")
+            # every image of a batch has a page-locked buffer of its own, as a loader's arena has (copies of the distinct files, side by side:
+            # one copy command a batch; 64 images pointing into 16 buffers would be 64 runs that cannot be joined)
+            hot = J.PinnedFiles([pool[k] for k in picks]) if have_pinned else None
 
-    # ---- end to end: the same files streamed from host memory through jda_pipeline (host parse + tables, H2D of the unfiltered
-    # scans, device filter + pre-scan + decode; batches overlapped on three streams), host work included, pixels stay in HBM.
-    # The input lies in page-locked memory (what a loader that feeds a GPU reads into) and is submitted with JDA_SUBMIT_PINNED_INPUT:
-    # the copy engine takes the files where they are, no host core copies them.  Besides the headline figure (this rank's threads,
-    # at most 8): the same with 1, 2, 4, 8 host threads -- an 8-GPU node leaves a rank a few cores --, with COLD input (>= 2 GB of
-    # distinct buffers: nothing the host or the copy engine reads is in a cache), and with pageable input (the pipeline's own
-    # page-locked mirror, filled by the workers).
-    e2e = None
-    if args.e2e_batches > 0:
-        eb = min(n_mine, args.batch) if args.workload == "metric" else min(n_mine, 256)
-        depth = max(1, min(args.e2e_depth, 4))
-        e2e_distinct = n_distinct
-        pool = jpegs
-        if args.workload == "metric" and args.e2e_distinct > n_distinct:
-            # more distinct files per batch than the resident leg keeps: the pre-scan's late rounds are longer (its chains of changed
-            # entry states differ from file to file), which a batch of two files flatters
-            e2e_distinct = min(args.e2e_distinct, eb)
-            pool = [cached_jpeg(width, height, sub, 1234 + i, quality=args.quality, restart_rows=args.restart_rows) for i in range(e2e_distinct)]
-        picks = [(lo + i) % e2e_distinct for i in range(eb)]
-        surf = [out_base] if eb * depth > n_mine else [out_base + k * eb * img_bytes for k in range(depth)]
-        extra = [ctx.malloc(img_bytes * eb) for _ in range(depth - len(surf))]
-        surf += extra
-        outs_of = [[(base + i * img_bytes, pitch, geo["canvas_w"], geo["canvas_h"]) for i in range(eb)] for base in surf]
-        have_pinned = hasattr(J, "PinnedFiles")
-        # every image of a batch has a page-locked buffer of its own, as a loader's arena has (copies of the distinct files, side by side:
-        # one copy command a batch; 64 images pointing into 16 buffers would be 64 runs that cannot be joined)
-        hot = J.PinnedFiles([pool[k] for k in picks]) if have_pinned else None
-
-        def e2e_run(host_threads, batches, source):
-            """source: "pinned" (hot: the same page-locked files every batch), "pageable" (Python bytes through the mirror),
-            or a PinnedFiles arena of many copies (cold)."""
-            pipe = J.Pipeline(ctx, max_images=eb, depth=depth, host_threads=host_threads)
-            if source == "pageable" or not have_pinned:
-                packed = [pipe.pack([pool[k] for k in picks], o, [pt] * eb, [args.options] * eb) for o in outs_of]
-                flags, n_sets = 0, len(packed)
-            elif source == "pinned":
-                packed = [pipe.pack_pinned(hot, list(range(eb)), o, [pt] * eb, [args.options] * eb) for o in outs_of]
-                flags, n_sets = J.SUBMIT_PINNED_INPUT, len(packed)
-            else:                                   # cold: batch k reads copies the copy engine has not seen for len(source.addrs) / eb batches
-                n_sets = max(depth, len(source.addrs) // eb)
-                packed = [pipe.pack_pinned(source, [(k * eb + i) % len(source.addrs) for i in range(eb)], outs_of[k % depth], [pt] * eb, [args.options] * eb) for k in range(n_sets)]
-                flags = J.SUBMIT_PINNED_INPUT
-            submit = (lambda k: pipe.submit_packed(packed[k % n_sets], flags)) if have_pinned else (lambda k: pipe.submit_packed(packed[k % n_sets]))
-            inflight, t_submit, warm = [], 0.0, max(2, depth)
-            tb0, n_failed = 0.0, 0                # (failures are counted, the barriers completed, and the ranks fail together afterwards)
-            for k in range(warm + batches):
-                if k == warm:
-                    while inflight:
-                        pipe.wait(inflight.pop(0))
-                    barrier()
-                    tb0 = time.perf_counter()
-                if len(inflight) == depth:
+            def e2e_run(host_threads, batches, source):
+                """source: "pinned" (hot: the same page-locked files every batch), "pageable" (Python bytes through the mirror),
+                or a PinnedFiles arena of many copies (cold)."""
+                pipe = J.Pipeline(ctx, max_images=eb, depth=depth, host_threads=host_threads)
+                if source == "pageable" or not have_pinned:
+                    packed = [pipe.pack([pool[k] for k in picks], o, [pt] * eb, [args.options] * eb) for o in outs_of]
+                    flags, n_sets = 0, len(packed)
+                elif source == "pinned":
+                    packed = [pipe.pack_pinned(hot, list(range(eb)), o, [pt] * eb, [args.options] * eb) for o in outs_of]
+                    flags, n_sets = J.SUBMIT_PINNED_INPUT, len(packed)
+                else:                                   # cold: batch k reads copies the copy engine has not seen for len(source.addrs) / eb batches
+                    n_sets = max(depth, len(source.addrs) // eb)
+                    packed = [pipe.pack_pinned(source, [(k * eb + i) % len(source.addrs) for i in range(eb)], outs_of[k % depth], [pt] * eb, [args.options] * eb) for k in range(n_sets)]
+                    flags = J.SUBMIT_PINNED_INPUT
+                submit = (lambda k: pipe.submit_packed(packed[k % n_sets], flags)) if have_pinned else (lambda k: pipe.submit_packed(packed[k % n_sets]))
+                inflight, t_submit, warm = [], 0.0, max(2, depth)
+                tb0, n_failed = 0.0, 0                # (failures are counted, the barriers completed, and the ranks fail together afterwards)
+                for k in range(warm + batches):
+                    if k == warm:
+                        while inflight:
+                            pipe.wait(inflight.pop(0))
+                        barrier()
+                        tb0 = time.perf_counter()
+                    if len(inflight) == depth:
+                        n_failed += sum(1 for s_ in pipe.wait(inflight.pop(0)) if s_ != 0)
+                    ts = time.perf_counter()
+                    inflight.append(submit(k))
+                    if k >= warm:
+                        t_submit += time.perf_counter() - ts
+                while inflight:
                     n_failed += sum(1 for s_ in pipe.wait(inflight.pop(0)) if s_ != 0)
-                ts = time.perf_counter()
-                inflight.append(submit(k))
-                if k >= warm:
-                    t_submit += time.perf_counter() - ts
-            while inflight:
-                n_failed += sum(1 for s_ in pipe.wait(inflight.pop(0)) if s_ != 0)
-            barrier()
-            dt = group.max(time.perf_counter() - tb0)
-            n_failed = int(group.sum(float(n_failed)))
-            if n_failed:
-                raise SystemExit("bench.py: %d image(s) of the end-to-end leg did not decode" % n_failed)
-            n_img = eb * batches
-            px_all = group.sum(float(geo["out_w"] * geo["out_h"] * n_img))
-            pst = pipe.stats
-            pipe.close()
-            return {"mpix_s": px_all / dt / 1e6, "ms_per_image": dt / n_img * 1e3, "host_submit_ms_per_image": t_submit / n_img * 1e3,
-                    "host_threads": host_threads, "batches": batches, "device_path_images": pst["device_images"], "host_path_images": pst["host_path_images"]}
+                barrier()
+                dt = group.max(time.perf_counter() - tb0)
+                n_failed = int(group.sum(float(n_failed)))
+                if n_failed:
+                    raise SystemExit("bench.py: %d image(s) of the end-to-end leg did not decode" % n_failed)
+                n_img = eb * batches
+                px_all = group.sum(float(geo["out_w"] * geo["out_h"] * n_img))
+                pst = pipe.stats
+                pipe.close()
+                return {"mpix_s": px_all / dt / 1e6, "ms_per_image": dt / n_img * 1e3, "host_submit_ms_per_image": t_submit / n_img * 1e3,
+                        "host_threads": host_threads, "batches": batches, "device_path_images": pst["device_images"], "host_path_images": pst["host_path_images"]}
 
-        main_threads = min(threads, 8)
-        # (untimed, like the clock ramp: the first few dozen batches that read a fresh page-locked arena run 10-25 % below the rate
-        # every later one has -- profiles/r04_e2e_input_modes.txt, first against second pass over the same six runs)
-        if have_pinned and not args.no_e2e_sweep:
-            e2e_run(main_threads, 2 * args.e2e_batches, "pinned")
-        e2e = e2e_run(main_threads, args.e2e_batches, "pinned")
-        e2e.update({"images_per_batch": eb, "depth": depth, "distinct_images": min(e2e_distinct, eb),
-                    "input": "page-locked, JDA_SUBMIT_PINNED_INPUT: a buffer per image of the batch, side by side (DMA from where they lie, one copy command a batch)" if have_pinned else "pageable",
-                    "what": "files in host memory -> pixels resident in HBM through jda_pipeline: host parse + tables, H2D of the unfiltered scans, "
-                            "device marker filter + per-block index + decode, batches overlapped; whole job, all ranks; the same files are submitted every batch"})
-        if have_pinned and rank == 0 and world == 1 and not args.no_e2e_sweep:
-            short = max(8, args.e2e_batches // 2)
-            e2e["host_thread_sweep"] = {str(t_): round(e2e_run(t_, short, "pinned")["mpix_s"]) for t_ in (1, 2, 4, 8)}
-            e2e["pageable_input"] = {str(t_): round(e2e_run(t_, short, "pageable")["mpix_s"]) for t_ in (2, 8)}
-            # cold input: >= 2 GB of distinct page-locked buffers (copies of the distinct files), each read once per ~2 GB of traffic
-            t_c = time.perf_counter()
-            n_copies = max(eb * depth, int(args.e2e_cold_gb * (1 << 30) / (sum(len(f) for f in pool) / len(pool))) + 1)
-            cold = J.PinnedFiles([pool[k % len(pool)] for k in range(n_copies)])
-            r = e2e_run(main_threads, max(short, 2 * n_copies // eb), cold)
-            e2e["cold_input"] = {"mpix_s": r["mpix_s"], "vs_hot": r["mpix_s"] / e2e["mpix_s"], "distinct_buffers": n_copies, "bytes": cold.bytes,
-                                 "batches": r["batches"], "setup_s": round(time.perf_counter() - t_c, 2),
-                                 "what": "every batch reads page-locked buffers nobody has touched for %d batches (%.1f GB in all)" % (n_copies // eb, cold.bytes / 2 ** 30)}
-            cold.close()
-        if hot:
-            hot.close()
-        for p_ in extra:
-            ctx.free(p_)
+            main_threads = min(threads, 8)
+            # (untimed, like the clock ramp: the first few dozen batches that read a fresh page-locked arena run 10-25 % below the rate
+            # every later one has -- profiles/r04_e2e_input_modes.txt, first against second pass over the same six runs)
+            if have_pinned and not args.no_e2e_sweep:
+                e2e_run(main_threads, 2 * args.e2e_batches, "pinned")
+            e2e = e2e_run(main_threads, args.e2e_batches, "pinned")
+            e2e.update({"images_per_batch": eb, "depth": depth, "distinct_images": min(e2e_distinct, eb),
+                        "input": "page-locked, JDA_SUBMIT_PINNED_INPUT: a buffer per image of the batch, side by side (DMA from where they lie, one copy command a batch)" if have_pinned else "pageable",
+                        "what": "files in host memory -> pixels resident in HBM through jda_pipeline: host parse + tables, H2D of the unfiltered scans, "
+                                "device marker filter + per-block index + decode, batches overlapped; whole job, all ranks; the same files are submitted every batch"})
+            if have_pinned and rank == 0 and world == 1 and not args.no_e2e_sweep:
+                short = max(8, args.e2e_batches // 2)
+                e2e["host_thread_sweep"] = {str(t_): round(e2e_run(t_, short, "pinned")["mpix_s"]) for t_ in (1, 2, 4, 8)}
+                e2e["pageable_input"] = {str(t_): round(e2e_run(t_, short, "pageable")["mpix_s"]) for t_ in (2, 8)}
+                # cold input: >= 2 GB of distinct page-locked buffers (copies of the distinct files), each read once per ~2 GB of traffic
+                t_c = time.perf_counter()
+                n_copies = max(eb * depth, int(args.e2e_cold_gb * (1 << 30) / (sum(len(f) for f in pool) / len(pool))) + 1)
+                cold = J.PinnedFiles([pool[k % len(pool)] for k in range(n_copies)])
+                r = e2e_run(main_threads, max(short, 2 * n_copies // eb), cold)
+                e2e["cold_input"] = {"mpix_s": r["mpix_s"], "vs_hot": r["mpix_s"] / e2e["mpix_s"], "distinct_buffers": n_copies, "bytes": cold.bytes,
+                                     "batches": r["batches"], "setup_s": round(time.perf_counter() - t_c, 2),
+                                     "what": "every batch reads page-locked buffers nobody has touched for %d batches (%.1f GB in all)" % (n_copies // eb, cold.bytes / 2 ** 30)}
+                cold.close()
+            if hot:
+                hot.close()
+            for p_ in extra:
+                ctx.free(p_)
 
     configs = None
-    if not args.no_configs and rank == 0 and world == 1 and args.workload == "metric":
+    if args.full and not args.no_configs and rank == 0 and world == 1 and args.workload == "metric":
         configs = run_config_legs(J, ctx, threads, only=[c for c in args.configs.split(",") if c] or None)
 
     cpu = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         try:
             cpu = cpu_baseline(jpegs, pt, placement["cores_usable"], {k: placement[k] for k in ("affinity_cpus", "cgroup_cpu_quota", "os_cpu_count")}, cpu_model())
         except Exception as e:
@@ -757,7 +828,7 @@ def run(args, J, out=sys.stdout):
             "configs": configs,
             "end_to_end": e2e,
             "end_to_end_mpix_s": e2e["mpix_s"] if e2e else None,
-            "host_prepare_ms_per_image": t_prep1 * 1e3,
+            "host_prepare_ms_per_image": t_prep1 * 1e3 if t_prep1 is not None else None,
             "host_prepare_threads_ms_per_image": t_par * 1e3,
             "host_threads": threads,
             "upload_ms_per_image": t_up * 1e3,
@@ -765,6 +836,7 @@ def run(args, J, out=sys.stdout):
             "clock_ramp_ms": args.ramp_ms,                # untimed launches before the W warm-up steps (see above)
             "kernel_only_mpix_s": px_per_step / (kernel_ms * 1e-3) / 1e6,
             "dist": {"backend": (args.dist_backend if dist_on else "none"), "ranks": world},
+            "full": args.full,
         }
         print(json.dumps(line), file=out)
         out.flush()

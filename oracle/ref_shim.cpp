@@ -94,6 +94,27 @@ int ref_is_simd(void)
 
 #ifndef SHIM_PRODUCT
 int ref_sizeof_state(void) { return (int)sizeof(JPEGIMAGE); }
+
+// the reference's constant tables as it compiles them (jpeg.inl): 0 ucRangeTable, 1 usGrayTo565, 2-4 usRangeTableR / G / B,
+// 5 iScaleBits, 6 cZigZag2.  ref_table_size(k) entries; ref_table_entry(k, i) widened to int (0 outside the table)
+#define REF_TABLES(X) X(0, ucRangeTable) X(1, usGrayTo565) X(2, usRangeTableR) X(3, usRangeTableG) X(4, usRangeTableB) \
+                      X(5, iScaleBits) X(6, cZigZag2)
+int ref_table_size(int k)
+{
+#define REF_TABLE_SIZE(n, t) if (k == n) return (int)(sizeof(t) / sizeof(t[0]));
+    REF_TABLES(REF_TABLE_SIZE)
+#undef REF_TABLE_SIZE
+    return 0;
+}
+int ref_table_entry(int k, int i)
+{
+    if (i < 0 || i >= ref_table_size(k)) return 0;
+#define REF_TABLE_ENTRY(n, t) if (k == n) return (int)t[i];
+    REF_TABLES(REF_TABLE_ENTRY)
+#undef REF_TABLE_ENTRY
+    return 0;
+}
+#undef REF_TABLES
 #endif
 
 // info[0..9] = width,height,subsample,bpp,jpegtype,orientation,hasthumb,thumbw,thumbh,lasterror

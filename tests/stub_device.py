@@ -1,9 +1,12 @@
 """A stand-in for the DEVICE half of jpegdec_amd (context, resident images, launch plans, pipeline) so that bench.py's own
 control flow -- sharding one image list, host placement, the collectives, the exactly-once proof, the JSON record -- can be
 run under gloo on a box without a GPU (tests/test_bench_flow_gloo.py).  The host half (parse, tables, pre-scan) is the real
-library.  Nothing is decoded here: a surface's "checksum" is a hash of the file it would have been decoded from."""
+library.  Nothing is decoded here: a surface's "checksum" is a hash of the file it would have been decoded from, its bytes noise
+seeded by that hash."""
 import hashlib
 import time
+
+import numpy as np
 
 import jpegdec_amd as _J
 
@@ -61,7 +64,10 @@ class Context:
         return [int.from_bytes(self.surfaces[s[0]], "little") for s in surfaces]
 
     def to_host(self, ptr, n):
-        raise RuntimeError("the stub holds no pixels")
+        """the bytes of a surface: noise seeded by the file it would have been decoded from (enough for bench.py --dump-outputs)"""
+        if ptr not in self.surfaces:
+            raise RuntimeError("the stub holds no pixels at 0x%x" % ptr)
+        return np.random.default_rng(int.from_bytes(self.surfaces[ptr], "little")).integers(0, 256, n, dtype=np.uint8)
 
     def close(self):
         pass

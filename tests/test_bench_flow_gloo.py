@@ -19,7 +19,7 @@ def _worker(rank, world, port, out_path, workload):
     import bench
     from tests import stub_device
 
-    argv = ["--gpus", str(world), "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--dist-backend", "gloo", "--no-parity",
+    argv = ["--gpus", str(world), "--full", "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--dist-backend", "gloo", "--no-parity",
             "--no-cpu-baseline", "--e2e-batches", "2"]
     if workload == "c4":
         argv += ["--workload", "c4", "--total-images", "21", "--distinct", "5"]
@@ -102,7 +102,7 @@ def test_bench_py_gpus_2_starts_its_own_ranks(tmp_path, product_lib):
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--ramp-ms", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--ramp-ms", "0",
            "--dist-backend", "gloo", "--device-module", "tests.stub_device", "--no-parity", "--no-cpu-baseline", "--no-configs", "--e2e-batches", "2",
            "--width", "333", "--height", "217", "--batch", "5", "--distinct", "2"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
@@ -121,3 +121,59 @@ def test_bench_py_refuses_a_launcher_world_that_is_not_gpus(tmp_path, product_li
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device-module", "tests.stub_device", "--dist-backend", "gloo"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
+
+
+def test_bench_py_plain_run_and_dump_outputs(tmp_path, product_lib):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (stub device): the headline line and nothing of --full; --dump-outputs writes
+    the last step's pixels as float arrays of bounded size, the same in two runs with the same arguments."""
+    import subprocess
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("dump%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--ramp-ms", "0",
+               "--device-module", "tests.stub_device", "--width", "333", "--height", "217", "--batch", "5", "--distinct", "2",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["metric"] == "Mpixels/s decoded" and line["unit"] == "Mpixels/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "i32" and line["steps"] == 4 and line["ms_per_step"] > 0 and line["full"] is False
+        for key in ("sharding", "parity", "end_to_end", "configs", "cpu_baseline", "host_prepare_ms_per_image"):
+            assert line[key] is None, key
+        files = sorted(os.listdir(d))
+        assert files == ["byte_histogram.npy", "pixels_sample.npy"]
+        arrs = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["pixels_sample.npy"].shape == (5, 1 << 16) and arrs["byte_histogram.npy"].shape == (5, 256)
+        assert np.all(arrs["byte_histogram.npy"].sum(axis=1) == 333 * 217 * 4)
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    # images 0, 2, 4 are copies of one file (--distinct 2): what the path decoded, they hold the same
+    assert np.array_equal(dumps[0]["pixels_sample.npy"][0], dumps[0]["pixels_sample.npy"][2])
+
+
+def test_cached_jpeg_without_a_writable_tree(tmp_path, monkeypatch):
+    """bench.py's synthetic inputs where the tree cannot be written to: cached in the user's cache directory, or made and not
+    cached when that cannot be written either -- the same bytes every time."""
+    import bench
+    from jpegdec_amd.synth import synth_jpeg
+
+    blocked = tmp_path / "not_a_dir"
+    blocked.write_bytes(b"")                         # a file: no directory can be made below it, whoever runs the test
+    monkeypatch.setattr(bench, "ROOT", str(blocked))
+    monkeypatch.setenv("XDG_CACHE_HOME", str(tmp_path / "cache"))
+    want = synth_jpeg(64, 48, "4:2:0", seed=5)
+    assert bench.cached_jpeg(64, 48, "4:2:0", 5) == want
+    cached = tmp_path / "cache" / "jpegdec_amd" / "bench_cache" / "synth_64x48_420_q85_s5.jpg"
+    assert cached.read_bytes() == want
+    assert bench.cached_jpegs([(64, 48, "4:2:0", 5, 85, 0)] * 2) == [want, want]      # (read back from the cache)
+    monkeypatch.setenv("XDG_CACHE_HOME", str(blocked))
+    assert bench.cached_jpeg(64, 48, "4:2:0", 6) == synth_jpeg(64, 48, "4:2:0", seed=6)
+    assert sorted(p.name for p in tmp_path.rglob("*") if p.is_file()) == ["not_a_dir", "synth_64x48_420_q85_s5.jpg"]

@@ -146,12 +146,8 @@ def test_pipeline_one_corrupt_image_in_sixteen(gpu_ctx, oracle):
 
 def test_pipeline_at_bench_size(gpu_ctx, ref_scalar):
     """two 4096x4096 images of the bench workload through the pipeline: frames == the real reference's"""
-    import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    paths = [os.path.join(root, "bench_cache", "synth_4096x4096_420_q85_s%d.jpg" % s) for s in (1234, 1235)]
-    if not all(os.path.exists(p) for p in paths):
-        pytest.skip("bench_cache inputs absent")
-    jp = [open(p, "rb").read() for p in paths]
+    import bench
+    jp = [bench.cached_jpeg(4096, 4096, "4:2:0", s) for s in (1234, 1235)]      # (made by the synthetic recipe where not cached yet)
     pipe = J.Pipeline(gpu_ctx, max_images=8, depth=2)
     outs, metas = _surfaces(gpu_ctx, jp, [J.RGB8888] * 2, [0] * 2)
     st = pipe.wait(pipe.submit(jp, outs, [J.RGB8888] * 2, [0] * 2))

@@ -1,16 +1,11 @@
 """The oracle restatement against the real reference itself (oracle/_ref, built from
 /root/reference by oracle/Makefile).  Skipped where the prebuilt reference is absent."""
-import glob
-import os
-import re
-
 import numpy as np
 import pytest
 
-from oracle.loader import GRAY8, RGB8888, USES_DMA, load_c_array_header
+from oracle.loader import GRAY8, RGB8888, USES_DMA
 from tests.cases import OPTIONS, PIXEL_TYPES, SYNTH_CASES, jpeg_for
-
-REF_ROOT = "/root/reference"
+from tests.ref_fixtures import ref_jpeg
 
 
 def _compare_all_modes(jpeg, oracle, ref):
@@ -40,10 +35,8 @@ def test_oracle_equals_reference_synthetic(name, oracle, ref_scalar):
 @pytest.mark.needs_reference
 @pytest.mark.parametrize("image", ["tulips", "zebra", "st_peters", "sciopero"])
 def test_oracle_equals_reference_on_its_own_test_images(image, oracle, ref_scalar):
-    path = os.path.join(REF_ROOT, "test_images", image + ".h")
-    if not os.path.exists(path):
-        pytest.skip("reference tree absent")
-    _compare_all_modes(load_c_array_header(path), oracle, ref_scalar)
+    """test_images/<image>.h, byte for byte as tests/golden/ref/<image>.jpg"""
+    _compare_all_modes(ref_jpeg(image), oracle, ref_scalar)
 
 
 def test_draw_plan_options(oracle, ref_scalar):
@@ -57,25 +50,20 @@ def test_draw_plan_options(oracle, ref_scalar):
 
 
 @pytest.mark.needs_reference
-def test_closed_form_tables_equal_reference_literals(oracle):
-    """ucRangeTable / usGrayTo565 / usRangeTableR,G,B / iScaleBits / cZigZag2 as literals in jpeg.inl."""
-    src = os.path.join(REF_ROOT, "src", "jpeg.inl")
-    if not os.path.exists(src):
-        pytest.skip("reference tree absent")
-    txt = open(src, errors="replace").read()
+def test_closed_form_tables_equal_reference_literals(oracle, ref_scalar):
+    """ucRangeTable / usGrayTo565 / usRangeTableR,G,B / iScaleBits / cZigZag2 (literals in jpeg.inl) as the reference's build holds them."""
+    R = ref_scalar.lib
 
-    def arr(name):
-        m = re.search(name + r"\s*\[[^\]]*\]\s*=\s*\{(.*?)\};", txt, re.S)
-        body = re.sub(r"//[^\n]*", "", m.group(1))
-        return [int(v, 0) for v in re.findall(r"0[xX][0-9a-fA-F]+|\d+", body)]
+    def arr(k):
+        return [R.ref_table_entry(k, i) for i in range(R.ref_table_size(k))]
 
     L = oracle.lib
-    assert arr("ucRangeTable") == [L.orc_range_limit(i) for i in range(1024)]
-    assert arr("usGrayTo565") == [L.orc_gray565(i) for i in range(256)]
-    for comp, nm in enumerate(("usRangeTableR", "usRangeTableG", "usRangeTableB")):
-        assert arr(nm) == [L.orc_range565(comp, i) for i in range(1024)], nm
-    assert arr("iScaleBits") == [L.orc_aan_scale(i) for i in range(64)]
-    assert arr("cZigZag2") == [L.orc_zigzag_to_natural(i) for i in range(64)]
+    assert arr(0) == [L.orc_range_limit(i) for i in range(1024)]
+    assert arr(1) == [L.orc_gray565(i) for i in range(256)]
+    for comp in range(3):
+        assert arr(2 + comp) == [L.orc_range565(comp, i) for i in range(1024)], comp
+    assert arr(5) == [L.orc_aan_scale(i) for i in range(64)]
+    assert arr(6) == [L.orc_zigzag_to_natural(i) for i in range(64)]
 
 
 @pytest.mark.parametrize("name", ["c420_333x217", "c444_333x217", "gray_333x217", "c422_333x217", "c440_200x120"])

@@ -3,11 +3,13 @@
 # (tools/phase_count_libs.sh's JDA_EXP_SKIP builds, here ab/lib_skip{1,3,7,15,31}.so) under rocprofv3 --pmc; differences of consecutive
 # builds are the phases.  Metric batch (16 images) and the photographs leg.  -> gpurun_out/phase_lanes/table.txt
 out=gpurun_out/phase_lanes; mkdir -p $out; export TMPDIR=/tmp
+R=$PWD; scratch=$(mktemp -d)      # (the profiler runs in a scratch directory; the repository is $R)
 for lib in jpegdec_amd/libjpegdec_amd.so ab/lib_skip1.so ab/lib_skip3.so ab/lib_skip7.so ab/lib_skip15.so ab/lib_skip31.so; do
   tag=$(basename $lib .so)
-  (cd /tmp && JDA_LIBRARY=$GRAFT_REPO_ROOT/$lib timeout -k 5 90 rocprofv3 --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU --output-format csv -d $GRAFT_REPO_ROOT/$out -o m_$tag -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --batch 16 --ramp-ms 0 --no-parity --no-cpu-baseline --e2e-batches 0 --no-configs > /dev/null 2>&1)
-  (cd /tmp && JDA_LIBRARY=$GRAFT_REPO_ROOT/$lib timeout -k 5 90 rocprofv3 --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU --output-format csv -d $GRAFT_REPO_ROOT/$out -o p_$tag -- python $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --batch 16 --ramp-ms 0 --no-parity --no-cpu-baseline --e2e-batches 0 --configs photos > /dev/null 2>&1)
+  (cd "$scratch" && JDA_LIBRARY=$R/$lib timeout -k 5 90 rocprofv3 --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU --output-format csv -d $R/$out -o m_$tag -- python $R/bench.py --steps 2 --warmup 1 --batch 16 --ramp-ms 0 --no-parity --no-cpu-baseline --e2e-batches 0 --no-configs > /dev/null 2>&1)
+  (cd "$scratch" && JDA_LIBRARY=$R/$lib timeout -k 5 90 rocprofv3 --pmc SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU --output-format csv -d $R/$out -o p_$tag -- python $R/bench.py --full --steps 2 --warmup 1 --batch 16 --ramp-ms 0 --no-parity --no-cpu-baseline --e2e-batches 0 --configs photos > /dev/null 2>&1)
 done
+rm -rf "$scratch"
 python - <<PY
 import csv, glob, collections, os
 out = "$out"

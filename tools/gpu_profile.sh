@@ -7,7 +7,7 @@
 tag=${1:-r06_prof}; prefix=${2:-r06}
 out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout -k 10 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 (cd /tmp && timeout -k 5 90 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$out -o kt -- python $R/bench.py --no-parity --no-cpu-baseline --e2e-batches 0 --no-configs > /dev/null 2>&1)
 B="--steps 10 --warmup 2 --ramp-ms 0 --no-parity --no-cpu-baseline --e2e-batches 0 --no-configs"
 (cd /tmp && timeout -k 5 90 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/$out -o fetch -- python $R/bench.py $B > /dev/null 2>&1)
