@@ -84,3 +84,329 @@ def progressive_modes(name):
             if gray and pt == 2:
                 continue       # gray JPEG + RGB8888: the reference emits 565 with iBpp = 32 (SURVEY C.5)
             yield pt, opt
+
+
+# ---- coefficient-level stress streams (tests/coef_jpeg.py): inputs chosen per quantised coefficient --------------------
+# Each builder returns the write_jpeg keyword arguments; COEF_CASES maps a name to (builder, its arguments).  Families:
+#   k_classes_*   the IDCT work lists (jda_p1_lists): per tile every (n1 & 7, n2 & 7) of the class-1 / class-2 counts, every
+#                 column mask with rows 4-7 empty and not, tiles all DC-only / all class 0 / all class 2
+#   k_single_*    one coefficient at each of the 64 positions, +-1 / +-511 / +-1023, flat 8-bit quantisers of 1 and 255: the
+#                 24-bit-multiply kernels driven into the 10-bit wrap of the range limit
+#   k_fastbound_* the two sides of the 24-bit multiply bound max|coef| x max|q'| < 2^21 (prescaled q')
+#   k_huff_*      every AC symbol of both AC tables, Annex K and a custom table with codes of every length 1..16
+#   k_dcdrift_*   DC predictors driven to 32767 / 32768 / -32768 / -32769 (DESIGN.md 3 item 8), and swung past int16 over and
+#                 over in streams long enough for the parallel host pre-scans (*_par*)
+#   k_edge_*      extreme coefficients in the blocks the image does not cover, ragged sizes
+import numpy as _np
+
+from tests import coef_jpeg as _cj
+
+_TILE_MCUS = {"gray": 64, "4:4:4": 20, "4:2:2": 16, "4:4:0": 16, "4:2:0": 10}    # jda_lds_layout<MODE>::MCUS
+_MCU_PX = {"gray": (8, 8), "4:4:4": (8, 8), "4:2:2": (16, 8), "4:4:0": (8, 16), "4:2:0": (16, 16)}
+
+
+def _blocks_in_mcu_order(coefs, sampling, cx, cy):
+    """[(component, block row, block column)] in stream order"""
+    hs, vs = _cj.LUMA_HV[sampling]
+    out = []
+    for m in range(cx * cy):
+        my, mx = divmod(m, cx)
+        out += [(0, my * vs + v, mx * hs + h) for v in range(vs) for h in range(hs)]
+        out += [(c, my, mx) for c in range(1, len(coefs))]
+    return out
+
+
+def _mask_block(rng, mask, rows47, variant):
+    """zig-zag block whose AC coefficients sit in exactly the columns of `mask`, rows 4-7 used or not"""
+    nat = _np.zeros(64, dtype=_np.int64)
+    cols = [c for c in range(8) if mask >> c & 1]
+    for i, c in enumerate(cols):
+        if rows47 and i == 0:
+            r = 4 + variant % 4                                      # (a quarter of them: the only coefficient of its column in row 4)
+        else:
+            r = (1 + (variant + i) % 3) if c == 0 else (variant + i) % 4
+        v = int(rng.integers(1, 16))
+        nat[r * 8 + c] = v if rng.integers(0, 2) else -v
+    zz = nat[_cj._ZIGZAG]
+    zz[0] = 0 if (rows47 and len(cols) == 1) else int(rng.integers(-20, 21))
+    return zz
+
+
+def _k_classes(sampling):
+    rng = _np.random.default_rng(101)
+    per = _TILE_MCUS[sampling]
+    mw, mh = _MCU_PX[sampling]
+    nb = per * {"gray": 1, "4:4:4": 3, "4:2:2": 4, "4:4:0": 4, "4:2:0": 6}[sampling]
+    queues = {0: [(m, r) for m in (1, 2, 3) for r in (0, 1)],
+              1: [(m, r) for m in range(4, 16) for r in (0, 1)],
+              2: [(m, r) for m in range(16, 256) for r in (0, 1)]}
+    pos = {0: 0, 1: 0, 2: 0}
+    plans = []
+    for t in range(64):
+        a, b = t & 7, t >> 3
+        n1, n2 = a + 8 * ((t >> 2) & 1), b + 8 * (t & 3)
+        rest = nb - n1 - n2
+        plans.append([0] * (rest // 2) + [1] * n1 + [2] * n2 + [3] * (rest - rest // 2))
+    plans += [[3] * nb, [0] * nb, [2] * nb]
+    width, height = per * mw, len(plans) * mh
+    coefs = _cj.zero_coefs(width, height, sampling)
+    cx, cy = per, len(plans)
+    order = _blocks_in_mcu_order(coefs, sampling, cx, cy)
+    for t, plan in enumerate(plans):
+        plan = list(plan)
+        rng.shuffle(plan)
+        for k, cls in enumerate(plan):
+            c, by, bx = order[t * nb + k]
+            if cls == 3:
+                coefs[c][by, bx, 0] = int(rng.integers(-20, 21))
+                continue
+            q = queues[cls]
+            mask, rows47 = q[pos[cls] % len(q)]
+            coefs[c][by, bx] = _mask_block(rng, mask, rows47, pos[cls] // len(q))
+            pos[cls] += 1
+    return dict(width=width, height=height, sampling=sampling, coefs=coefs,
+                quant={0: [4] * 64, 1: [6] * 64})
+
+
+_SINGLE_VALUES = (1, -1, 511, -511, 1023, -1023)
+
+
+def _k_single(sampling, q):
+    width = height = 160
+    coefs = _cj.zero_coefs(width, height, sampling)
+    seq = [(p, v) for p in range(64) for v in _SINGLE_VALUES]
+    for c, arr in enumerate(coefs):
+        flat = arr.reshape(-1, 64)
+        for i in range(flat.shape[0]):
+            p, v = seq[(i + 128 * c) % len(seq)]
+            flat[i, p] = v
+    return dict(width=width, height=height, sampling=sampling, coefs=coefs, quant={0: [q] * 64, 1: [q] * 64})
+
+
+# the prescaled quantiser q'[n] = (q[n] * aan[n]) >> 12 (jpeg.inl:1789-1811); these q give q' = 16513 / 16514 at rows 1, 3, 5, 7 of
+# column 7 (checked against the front end's tables by tests/test_coef_streams_cpu.py)
+FASTBOUND_Q = {"lo": (10788, 12726, 19043, 54240), "hi": (10788, 12727, 19044, 54244)}
+
+
+def _k_fastbound(sampling, side, term):
+    """term 'ac': category-7 coefficients (+-127) against q' = 16513 (worst = 127 x 16513 = 2^21 - 1) or, on the 'hi' side, q' = 16514;
+    four of them in one column, signed so that the odd part's z10 + z12 = (c5 - c3) + (c1 - c7) is the largest operand it can be.
+    term 'dc': |DC| x q0' with q0' = 4 x q0: 3942 x 4 x 133 = 2^21 - 8 (an odd worst is out of the DC term's reach), or
+    16384 x 4 x 32 = 2^21 exactly (out of the AC term's reach)."""
+    width, height = 48, 32
+    coefs = _cj.zero_coefs(width, height, sampling)
+    zz = {n: i for i, n in enumerate(_cj._ZIGZAG)}
+    if term == "ac":
+        qz = [1] * 64
+        for r, q in zip((1, 3, 5, 7), FASTBOUND_Q[side]):
+            qz[zz[r * 8 + 7]] = q
+        for arr in coefs:
+            flat = arr.reshape(-1, 64)
+            for i in range(flat.shape[0]):
+                sg = 1 if i % 2 == 0 else -1
+                for r, s in zip((1, 3, 5, 7), (1, -1, 1, -1)):
+                    flat[i, zz[r * 8 + 7]] = sg * s * 127
+                flat[i, zz[7]] = 3                                    # (and something in the rows' direction too)
+        quant = {0: qz, 1: qz}
+    else:
+        q0, dc = (133, 3942) if side == "lo" else (32, 16384)
+        qz = [q0] + [2] * 63
+        order = _blocks_in_mcu_order(coefs, sampling, *_cj.geometry(width, height, sampling)[:2])
+        for comp in range(len(coefs)):
+            # in stream order: ramp in steps the DC category allows, hold +-dc, turn: the peak in several blocks of every component
+            v, i = 0, 0
+            for c, by, bx in order:
+                if c != comp:
+                    continue
+                tgt = dc if (i // 24) % 2 == 0 else -dc
+                v = v + max(-2047, min(2047, tgt - v))
+                coefs[c][by, bx, 0] = v
+                if i % 5 == 1:
+                    coefs[c][by, bx, 1] = 7
+                i += 1
+        quant = {0: qz, 1: qz}
+    return dict(width=width, height=height, sampling=sampling, coefs=coefs, quant=quant)
+
+
+def _huff_blocks(first_dc=0):
+    """zig-zag blocks that use every AC symbol once at least, and the corner cases of the AC syntax"""
+    blocks = []
+    for r in range(16):
+        for s in range(1, 11):
+            zz = _np.zeros(64, dtype=_np.int64)
+            zz[1 + r] = (1 << (s - 1)) + ((r * 7) % (1 << (s - 1)) if s > 1 else 0)
+            if (r + s) & 1:
+                zz[1 + r] = -zz[1 + r]
+            zz[1 + r + 1 + (s % 3)] = 1                               # (a second symbol behind it)
+            blocks.append(zz)
+    zz = _np.zeros(64, dtype=_np.int64); zz[17] = 2; blocks.append(zz)                  # ZRL, then run 0
+    zz = _np.zeros(64, dtype=_np.int64); zz[63] = 5; blocks.append(zz)                  # ZRL x 3, run 14, coefficient 63, no EOB
+    zz = _np.zeros(64, dtype=_np.int64); zz[1] = 1; zz[63] = -300; blocks.append(zz)    # ZRL x 3 in the middle of a block, then 63
+    zz = _np.zeros(64, dtype=_np.int64); zz[0] = 1500; blocks.append(zz)                # DC category 11, EOB right after DC
+    zz = _np.zeros(64, dtype=_np.int64); zz[0] = -300; blocks.append(zz)                # DC category 11 down
+    zz = _np.zeros(64, dtype=_np.int64); zz[0] = 1700; zz[63] = 1; blocks.append(zz)
+    zz = _np.zeros(64, dtype=_np.int64); blocks.append(zz)
+    return blocks
+
+
+# Two AC tables whose code lengths together are every length 1..16, most codes 16 bits long.  (One table of 162 codes cannot
+# have every length: lengths 1..15 once each leave room for one 16-bit code.)  A code longer than 10 bits must start 111111 --
+# the long half of the LUT, jpeg.inl:2232-2233 -- so the short codes fill 63/64 of the code space first.
+CUSTOM_AC_BITS = ([1, 1, 1, 1, 1, 1, 1, 0, 1, 0, 1, 0, 1, 0, 0, 152],
+                  [0, 3, 1, 1, 1, 1, 1, 1, 0, 1, 0, 1, 0, 1, 1, 149])
+
+
+def custom_ac_table(which):
+    order = list(_cj.AC_SYMBOLS)
+    _np.random.default_rng(7 + which).shuffle(order)
+    return list(CUSTOM_AC_BITS[which]), order
+
+
+def _k_huff(sampling, custom):
+    blocks = _huff_blocks()
+    nc = 1 if sampling == "gray" else 3
+    hs, vs = _cj.LUMA_HV[sampling]
+    mcus = len(blocks) + 2
+    cx = 12
+    cy = (mcus + cx - 1) // cx
+    width, height = cx * 8 * hs, cy * 8 * vs
+    coefs = _cj.zero_coefs(width, height, sampling)
+    for c, arr in enumerate(coefs):
+        flat = arr.reshape(-1, 64)
+        for i in range(flat.shape[0]):
+            flat[i] = blocks[(i + 17 * c) % len(blocks)]
+    huff = dict(_cj.annex_k()[2])
+    if custom:
+        huff[(1, 0)] = custom_ac_table(0)
+        huff[(1, 1)] = custom_ac_table(1)
+    return dict(width=width, height=height, sampling=sampling, coefs=coefs, quant={0: [1] * 64, 1: [2] * 64}, huff=huff)
+
+
+def _k_huff_cross(sampling):
+    """a run that crosses position 63 (legal syntax, a corrupt block): ZRL x 3, run 11 to coefficient 60, then run 15 (to 76)"""
+    d = _k_huff(sampling, False)
+    d["ac_pairs"] = {(0, 0, 3): [(15, 0), (15, 0), (15, 0), (11, 3), (15, 1)]}
+    return d
+
+
+def _k_dcdrift(sampling, target, comp, q0, dri):
+    """the DC value of component `comp` ramps (+-2047 a block) to `target` in the LAST block of that component in MCU k - 1, then
+    back; dri: a restart interval of k MCUs resets the predictor before the component's next block"""
+    hs, vs = _cj.LUMA_HV[sampling]
+    per_mcu = hs * vs if comp == 0 else 1
+    steps = (abs(target) + 2046) // 2047
+    k = (steps + per_mcu - 1) // per_mcu + 1
+    cx = 2 * k + 2
+    width, height = cx * 8 * hs, 8 * vs
+    coefs = _cj.zero_coefs(width, height, sampling)
+    order = [b for b in _blocks_in_mcu_order(coefs, sampling, cx, 1) if b[0] == comp]
+    peak = k * per_mcu - 1
+    vals = [0] * len(order)
+    sg = 1 if target > 0 else -1
+    for i in range(peak + 1):
+        vals[peak - i] = target - sg * 2047 * i if abs(target) > 2047 * i else 0
+    for i in range(peak + 1, len(order)):
+        vals[i] = 0 if dri else (target - sg * 2047 * (i - peak) if abs(target) > 2047 * (i - peak) else 0)
+    for (c, by, bx), v in zip(order, vals):
+        coefs[c][by, bx, 0] = v
+    if q0 == 1:
+        c, by, bx = order[peak]
+        coefs[c][by, bx, 2] = 3                                       # (the peak block not DC-only)
+    qs = {0: [q0 if comp == 0 else 3] + [3] * 63, 1: [q0 if comp != 0 else 5] + [5] * 63}
+    return dict(width=width, height=height, sampling=sampling, coefs=coefs, quant=qs if sampling != "gray" else {0: qs[0]},
+                restart_interval=k if dri else 0)
+
+
+def _k_dcdrift_par(dri):
+    """a 1024x256 4:2:0 stream long enough for the parallel host pre-scans (interval workers with a DRI, scan chunks without):
+    luma and Cb predictors swing between +-40000 (+-2047 a block), past int16 again and again; with dri, one MCU row an
+    interval and the swing restarts from 0 in each"""
+    rng = _np.random.default_rng(211)
+    width, height = 1024, 256
+    coefs = _cj.zero_coefs(width, height, "4:2:0")
+    cx, cy = _cj.geometry(width, height, "4:2:0")[:2]
+    order = _blocks_in_mcu_order(coefs, "4:2:0", cx, cy)
+    per_mcu = 6
+    amp = {0: 40000, 1: 35000}
+    v, step = [0, 0, 0], [2047, 2047, 0]
+    for i, (c, by, bx) in enumerate(order):
+        if dri and i % (dri * per_mcu) == 0:
+            v, step = [0, 0, 0], [2047, 2047, 0]
+        if c in amp:
+            if abs(v[c] + step[c]) > amp[c]:
+                step[c] = -step[c]
+            v[c] += step[c]
+        coefs[c][by, bx, 0] = v[c]
+        coefs[c][by, bx, 1:9] = rng.integers(-3, 4, size=8)
+    return dict(width=width, height=height, sampling="4:2:0", coefs=coefs, quant={0: [2] * 64, 1: [3] * 64},
+                restart_interval=dri)
+
+
+def _k_edge(sampling, w, h):
+    rng = _np.random.default_rng(w * 1000 + h)
+    coefs = _cj.zero_coefs(w, h, sampling)
+    hs, vs = _cj.LUMA_HV[sampling]
+    for c, arr in enumerate(coefs):
+        cw, ch = (w, h) if c == 0 else ((w + hs - 1) // hs, (h + vs - 1) // vs)
+        for by in range(arr.shape[0]):
+            for bx in range(arr.shape[1]):
+                inside = (bx + 1) * 8 <= cw and (by + 1) * 8 <= ch
+                if inside:
+                    arr[by, bx, :6] = rng.integers(-12, 13, size=6)
+                else:                                                # a block the image does not (wholly) cover: extremes
+                    arr[by, bx, 0] = 2000 if (bx + by) & 1 else -2000
+                    arr[by, bx, [1, 2, 9, 20, 35, 63]] = _np.where(rng.integers(0, 2, size=6) == 1, 1023, -1023)
+    # DC differences stay inside category 11: walk the DC values in stream order and clamp the steps
+    order = _blocks_in_mcu_order(coefs, sampling, *_cj.geometry(w, h, sampling)[:2])
+    pred = [0] * len(coefs)
+    for c, by, bx in order:
+        v = int(coefs[c][by, bx, 0])
+        v = max(pred[c] - 2047, min(pred[c] + 2047, v))
+        coefs[c][by, bx, 0] = v
+        pred[c] = v
+    return dict(width=w, height=h, sampling=sampling, coefs=coefs, quant={0: [16] * 64, 1: [16] * 64})
+
+
+def _coef_cases():
+    cases = {}
+    for lay in _cj.LAYOUTS:
+        s = _cj.SHORT[lay]
+        cases["k_classes_" + s] = (_k_classes, (lay,))
+        for q in (1, 255):
+            cases["k_single_q%d_%s" % (q, s)] = (_k_single, (lay, q))
+        for term in ("ac", "dc"):
+            for side in ("lo", "hi"):
+                cases["k_fastbound_%s_%s_%s" % (term, side, s)] = (_k_fastbound, (lay, side, term))
+        cases["k_huff_annexk_" + s] = (_k_huff, (lay, False))
+        cases["k_huff_custom_" + s] = (_k_huff, (lay, True))
+        for target in (32767, 32768, -32768, -32769):
+            for comp in ((0,) if lay == "gray" else (0, 1)):
+                for q0 in ((1, 200) if lay in ("gray", "4:2:0") else (200,)):
+                    for dri in (0, 1):
+                        cases["k_dcdrift_%s_%d_%s_q%d%s" % (s, target, "y" if comp == 0 else "cb", q0, "_dri" if dri else "")] = (
+                            _k_dcdrift, (lay, target, comp, q0, dri))
+        mw, mh = _MCU_PX[lay]
+        per = _TILE_MCUS[lay]
+        for w, h in ((1, 1), (7, 9), (17, 15), ((per - 1) * mw - 3, mh + 5), ((per + 1) * mw - 5, 2 * mh - 1)):
+            cases["k_edge_%s_%dx%d" % (s, w, h)] = (_k_edge, (lay, w, h))
+    cases["k_dcdrift_c420_40000_ycb_q2_par"] = (_k_dcdrift_par, (0,))
+    cases["k_dcdrift_c420_40000_ycb_q2_par_dri64"] = (_k_dcdrift_par, (64,))
+    cases["k_huff_cross_c420"] = (_k_huff_cross, ("4:2:0",))
+    cases["k_huff_cross_gray"] = (_k_huff_cross, ("gray",))
+    return cases
+
+
+COEF_CASES = _coef_cases()
+COEF_CORRUPT = sorted(k for k in COEF_CASES if k.startswith("k_huff_cross_"))     # legal syntax, a run past position 63
+
+
+@functools.lru_cache(maxsize=None)
+def coef_spec(name):
+    fn, args = COEF_CASES[name]
+    return fn(*args)
+
+
+@functools.lru_cache(maxsize=None)
+def coef_jpeg_for(name):
+    return _cj.write_jpeg(**coef_spec(name))
+

@@ -32,6 +32,18 @@ extern "C" void hostsim_set_reverse(int on) { g_reverse_tiles = on; }
 static uint32_t g_window_bytes = 1024;   // tests shrink it to exercise the HBM fall-back of the bit reader (each layout caps it at its WIN_BYTES)
 extern "C" void hostsim_set_window(uint32_t bytes) { g_window_bytes = bytes > 1024 ? 1024 : (bytes & ~15u); }
 
+// the IDCT work lists of every tile decoded while recording is on (jda_p1_lists): mcu_y, mcu_x0, count, then cnt[0..5] -- column
+// items of the short and the full column stage, the blocks of row classes 0 / 1 / 2 (after class 1's remainder moved), the DC-only ones
+static std::vector<uint32_t> g_list_counts;
+static int g_record_lists = 0;
+extern "C" void hostsim_set_list_counts(int on) { g_record_lists = on; }
+extern "C" uint32_t hostsim_take_list_counts(uint32_t *out, uint32_t cap_tiles)
+{
+    const uint32_t n = (uint32_t)(g_list_counts.size() / 9);
+    if (out) memcpy(out, g_list_counts.data(), (size_t)(n < cap_tiles ? n : cap_tiles) * 9 * sizeof(uint32_t));
+    g_list_counts.clear();
+    return n;
+}
 // one wavefront = 64 lanes stepping through the kernel's phases; a phase runs for every lane before
 // the next one starts (= the wave-local fence between them)
 template <int MODE, bool FAST>
@@ -72,6 +84,11 @@ static void run_tiles(const jda_dev_desc &D, const std::vector<jda_strip> &tiles
         for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) flags[t] = jda_p1_entropy<MODE>(D, C, in[t], LP[t], tab, wl, wl + L::WIN_OFF, g_window_bytes);
         if (D.scale_shift < 2) {
             for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) jda_p1_lists<MODE>(D, LP[t], t, flags[t], flags, tab, wl);
+            if (g_record_lists) {
+                const uint32_t *cnt = (const uint32_t *)(wl + L::CNT_OFF);
+                const uint32_t rec[9] = { S.mcu_y, S.mcu_x0, S.count, cnt[0], cnt[1], cnt[2], cnt[3], cnt[4], cnt[5] };
+                g_list_counts.insert(g_list_counts.end(), rec, rec + 9);
+            }
             for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) jda_p2_columns<MODE, FAST>(D, t, tab, wl);
             for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) jda_p3_rows<MODE>(D, t, tab, wl);
         }

@@ -1,0 +1,334 @@
+"""The coefficient-level stress streams (tests/coef_jpeg.py, COEF_CASES in tests/cases.py) without a GPU.
+
+First the corpus is checked to be what it claims (the writer round-trips through an independent decoder; a float64 decode
+agrees with Pillow's), then the oracle is pinned to the real reference on it (the oracle is what the GPU tests check
+against), then the wave emulator and the device pre-scan's emulation are held to the oracle.  The coverage assertions keep
+the corpus from drifting into uselessness: every IDCT list remainder pair, both sides of the class-1 move, every AC LUT entry
+of both halves, the 10-bit wrap on a 24-bit-multiply case."""
+import ctypes as C
+import io
+
+import numpy as np
+import pytest
+
+from tests import coef_jpeg as cj
+from tests.cases import COEF_CASES, COEF_CORRUPT, FASTBOUND_Q, all_modes, coef_jpeg_for, coef_spec, custom_ac_table
+
+GOOD = sorted(k for k in COEF_CASES if k not in COEF_CORRUPT)
+FAMILIES = ("k_classes_", "k_single_", "k_fastbound_", "k_huff_", "k_dcdrift_", "k_edge_")
+# the largest difference between the float64 decode and Pillow's (libjpeg-turbo, integer IDCT) on the in-range families,
+# measured: 2 on RGB (libjpeg rounds the samples before the colour conversion), 1 on the luma planes -- asserted with no slack
+FLOAT_BOUND_RGB = 2
+FLOAT_BOUND_LUMA = 1
+
+
+def _leaves_int16(name):
+    if not name.startswith("k_dcdrift_"):
+        return False
+    target = int(name.split("_")[3])
+    return target > 32767 or target < -32768
+
+
+def test_families_present():
+    for f in FAMILIES:
+        assert any(k.startswith(f) for k in COEF_CASES), f
+    for s in ("gray", "c444", "c422", "c440", "c420"):
+        assert sum(k.endswith(s) or ("_" + s + "_") in k for k in COEF_CASES) >= 10, s
+
+
+@pytest.mark.parametrize("name", GOOD)
+def test_writer_round_trip(name):
+    spec = coef_spec(name)
+    d = cj.decode_coefs(coef_jpeg_for(name))
+    assert d["sampling"] == spec["sampling"] and (d["width"], d["height"]) == (spec["width"], spec["height"])
+    assert d["restart_interval"] == spec.get("restart_interval", 0)
+    for c, (got, want) in enumerate(zip(d["coefs"], spec["coefs"])):
+        assert np.array_equal(got, want), (name, c)
+    for t, q in spec["quant"].items():
+        assert d["quant"][t] == list(q)
+
+
+@pytest.mark.parametrize("name", COEF_CORRUPT)
+def test_run_past_63_is_what_it_claims(name):
+    with pytest.raises(cj.DecodeError, match="past coefficient 63"):
+        cj.decode_coefs(coef_jpeg_for(name))
+
+
+def test_huffman_tables():
+    """the Annex K.2 builder gives a complete prefix code within the length limit; the custom AC tables together have codes of
+    every length 1..16, and every code longer than 10 bits starts 111111"""
+    from jpegdec_amd.synth import _codes
+    rng = np.random.default_rng(3)
+    for max_len in (16, 12, 9):
+        hist = {s: int(rng.integers(1, 1 << int(rng.integers(1, 20)))) for s in cj.AC_SYMBOLS}
+        bits, vals = cj.huff_from_hist(hist, max_len)
+        assert sorted(vals) == sorted(cj.AC_SYMBOLS) and sum(bits) == len(vals)
+        assert all(b == 0 for b in bits[max_len:])
+        assert sum(b * 2.0 ** -(i + 1) for i, b in enumerate(bits)) < 1.0
+    lengths = set()
+    for which in (0, 1):
+        bits, vals = custom_ac_table(which)
+        assert sorted(vals) == sorted(cj.AC_SYMBOLS)
+        for s, (code, ln) in _codes(bits, vals).items():
+            lengths.add(ln)
+            assert ln <= 10 or code >> (ln - 6) == 63, (which, s, ln)
+    assert lengths == set(range(1, 17))
+
+
+def _in_range(name):
+    return name.startswith("k_classes_")
+
+
+@pytest.mark.parametrize("name", [k for k in GOOD if _in_range(k)])
+def test_float64_decode_equals_pillow(name):
+    """float64 IDCT + colour conversion against libjpeg-turbo's decode of the same file: the corpus decodes to the pixels its
+    coefficients say.  (Pillow upsamples chroma with a triangle filter: on the subsampled layouts the luma plane is compared,
+    decoded without colour conversion.)"""
+    from PIL import Image
+    jpeg = coef_jpeg_for(name)
+    d = cj.decode_coefs(jpeg)
+    planes = cj.float_planes(d)
+    assert all(p.min() >= -256 and p.max() <= 511 for p in planes)     # (inside libjpeg's range limit: in range)
+    im = Image.open(io.BytesIO(jpeg))
+    w, h = d["width"], d["height"]
+    if d["sampling"] in ("gray", "4:4:4"):
+        got = np.asarray(im.convert("RGB") if d["sampling"] != "gray" else im).astype(np.int32)
+        want = cj.float_decode(d).astype(np.int32)
+        bound = FLOAT_BOUND_RGB if d["sampling"] != "gray" else FLOAT_BOUND_LUMA
+    else:
+        im.draft("YCbCr", None)
+        got = np.asarray(im)[..., 0].astype(np.int32)
+        want = np.clip(np.rint(planes[0][:h, :w]), 0, 255).astype(np.int32)
+        bound = FLOAT_BOUND_LUMA
+    assert got.shape == want.shape
+    assert int(np.abs(got - want).max()) <= bound, (name, int(np.abs(got - want).max()))
+
+
+def _ref_modes(name):
+    for pt, opt in all_modes(name):
+        if "gray" in name and pt == 2:
+            continue                 # the reference writes 16-bit pixels for gray + RGB8888: the oracle's own rule, pinned elsewhere
+        yield pt, opt
+
+
+@pytest.mark.parametrize("name", sorted(COEF_CASES))
+def test_oracle_equals_reference(name, oracle, ref_scalar):
+    """the oracle is the GPU tests' checker: pinned to the real reference on the whole corpus, verdicts included"""
+    jpeg = coef_jpeg_for(name)
+    h = ref_scalar.info(jpeg)["height"]
+    for pt, opt in _ref_modes(name):
+        r = ref_scalar.decode_cb(jpeg, pt, opt)
+        rc, canvas, err = oracle.decode_canvas(jpeg, pt, opt)
+        assert (r["rc"] == 1) == (rc == 1), (name, pt, opt, r["rc"], r["last_error"], rc, err)
+        if name not in COEF_CORRUPT:
+            assert rc == 1, (name, pt, opt, err)
+        if rc == 1:
+            hh = (h + (1 << r["scale_shift"]) - 1) >> r["scale_shift"]
+            assert np.array_equal(canvas[:hh], r["canvas"][:hh, : canvas.shape[1]]), (name, pt, opt)
+
+
+def _hostsim_decode(hostsim, oracle, jpeg, pt, opt):
+    rc, want, err = oracle.decode_canvas(jpeg, pt, opt)
+    got = np.full_like(want, 0x33)
+    inf, cx, cy, mw, mh, bpp, sh = oracle.canvas_geometry(jpeg, pt, opt)
+    hrc = hostsim.hostsim_decode(jpeg, len(jpeg), pt, opt, got.ctypes.data_as(C.c_void_p), got.shape[1], cx * mw, cy * mh)
+    return rc, want, hrc, got
+
+
+@pytest.mark.parametrize("name", sorted(COEF_CASES))
+def test_wave_emulation_equals_oracle(name, hostsim, oracle):
+    jpeg = coef_jpeg_for(name)
+    for pt, opt in all_modes(name):
+        rc, want, hrc, got = _hostsim_decode(hostsim, oracle, jpeg, pt, opt)
+        assert (hrc == 0) == (rc == 1), (name, pt, opt, hrc, rc)
+        assert np.array_equal(got, want), (name, pt, opt, int(np.count_nonzero(got != want)))
+
+
+@pytest.mark.parametrize("name", sorted(COEF_CASES))
+def test_device_prescan_emulation(name, hostsim, oracle):
+    """the segment walk gives the serial pre-scan's index entry for entry -- or, for a predictor that leaves int16, hands the image
+    to the serial pre-scan"""
+    jpeg = coef_jpeg_for(name)
+    pt = 3 if "gray" in name else 2
+    hostsim.hostsim_set_device_prescan(1)
+    try:
+        rc, want, hrc, got = _hostsim_decode(hostsim, oracle, jpeg, pt, 0)
+        if _leaves_int16(name):
+            assert hostsim.hostsim_prescan_used() == 0, name
+        elif name in COEF_CORRUPT:
+            assert hostsim.hostsim_prescan_used() == 0 or hostsim.hostsim_index_equal() == 1, name
+        else:
+            assert hostsim.hostsim_prescan_used() == 2, name
+            assert hostsim.hostsim_index_equal() == 1, name
+        assert (hrc == 0) == (rc == 1) and np.array_equal(got, want), name
+    finally:
+        hostsim.hostsim_set_device_prescan(0)
+
+
+@pytest.mark.parametrize("name", [k for k in COEF_CASES if k.startswith("k_dcdrift_")])
+def test_dc_drift_does_not_end_the_image(name, product_lib):
+    """A predictor past int16 is carried on (the reference keeps it in an int; a block stores it as (short)): the whole image is
+    decoded, every block -- the regression of the host pre-scans that ended the image at the component's next block.  The *_par*
+    streams are long enough for the parallel pre-scans (restart intervals side by side with a DRI, scan chunks without): asked
+    for explicitly, they must give the serial pre-scan's index and DC values."""
+    import jpegdec_amd as J
+    jpeg = coef_jpeg_for(name)
+    d = cj.decode_coefs(jpeg)
+    want = np.asarray([int(np.int64(d["coefs"][c][by, bx, 0]).astype(np.int16)) for c, by, bx in _stream_order(d)], dtype=np.int64)
+    flags = (0, J.PREPARE_SERIAL_PRESCAN, J.PREPARE_PARALLEL_PRESCAN) if "_par" in name else (0,)
+    got = []
+    for f in flags:
+        p = J.PreparedImage(jpeg, flags=f)
+        try:
+            idx, nok = p.block_index()
+            assert nok == p.info.mcus_x * p.info.mcus_y, (name, f, nok)
+            dc = np.asarray(p.block_dc(), dtype=np.int64)
+            assert np.array_equal(dc, want), (name, f)
+            got.append(idx.copy())
+        finally:
+            p.close()
+    for idx in got[1:]:
+        assert J.index_equivalent(idx, got[0]), name
+
+
+def _stream_order(d):
+    cx, cy, shapes, (hs, vs) = cj.geometry(d["width"], d["height"], d["sampling"])
+    out = []
+    for m in range(cx * cy):
+        my, mx = divmod(m, cx)
+        out += [(0, my * vs + v, mx * hs + h) for v in range(vs) for h in range(hs)]
+        out += [(c, my, mx) for c in range(1, len(shapes))]
+    return out
+
+
+def _prescaled(q, n_nat):
+    import math
+    f = [1.0] + [math.cos(k * math.pi / 16) * math.sqrt(2) for k in range(1, 8)]
+    r, c = divmod(n_nat, 8)
+    return (q * int(round(f[r] * f[c] * 16384))) >> 12
+
+
+@pytest.mark.parametrize("name", sorted(k for k in COEF_CASES if k.startswith("k_fastbound_")))
+def test_fast_mul_bound_edges(name, hostsim):
+    """worst = max|coef| x max|q'| on the two sides of 2^21: the 24-bit-multiply kernels exactly below, the 32-bit ones from 2^21 on"""
+    jpeg = coef_jpeg_for(name)
+    d = cj.decode_coefs(jpeg)
+    worst = 0
+    for c, arr in enumerate(d["coefs"]):
+        qz = d["quant"][d["quant_ids"][c]]
+        qp = [_prescaled(qz[i], cj._ZIGZAG[i]) for i in range(64)]
+        cat = max(int(abs(v)).bit_length() for v in arr[..., 1:].reshape(-1))
+        worst = max(worst, ((1 << cat) - 1) * max(qp[1:]), int(np.abs(arr[..., 0]).max()) * qp[0])
+    lo = "_lo_" in name
+    assert worst == ((1 << 21) - 1 if "_ac_lo_" in name else (1 << 21) - 8 if "_dc_lo_" in name else
+                     127 * 16514 if "_ac_hi_" in name else 1 << 21), (name, worst)
+    assert hostsim.hostsim_fast_mul(jpeg, len(jpeg)) == (1 if lo else 0), name
+    if "_ac_" in name:
+        assert [_prescaled(x, r * 8 + 7) for x, r in zip(FASTBOUND_Q["lo"], (1, 3, 5, 7))] == [16513] * 4
+        assert [_prescaled(x, r * 8 + 7) for x, r in zip(FASTBOUND_Q["hi"], (1, 3, 5, 7))] == [16513, 16514, 16514, 16514]
+
+
+def _class_of(zz):
+    nat = np.zeros(64, dtype=np.int64)
+    nat[cj._ZIGZAG] = zz
+    ac = nat.copy()
+    ac[0] = 0
+    cols = 0
+    for n in np.nonzero(ac)[0]:
+        cols |= 1 << (int(n) & 7)
+    rows47 = bool(np.any(ac[32:]))
+    cls = 3 if cols == 0 else (2 if cols & 0xF0 else (1 if cols & 0x0C else 0))
+    return cls, bin(cols | 1).count("1") if cols else 0, rows47
+
+
+@pytest.mark.parametrize("name", sorted(k for k in COEF_CASES if k.startswith("k_classes_")))
+def test_idct_work_list_coverage(name, hostsim, oracle):
+    """every tile's list counts (tests/hostsim hook) against a model made from the decoded coefficients, and what the corpus
+    reaches: all 64 (n1 & 7, n2 & 7) pairs, the class-1 remainder moved into class 2's last pass at rem1 == slack2 and refused at
+    rem1 == slack2 + 1, every column mask with rows 4-7 empty and not, tiles all DC-only / all class 0 / all class 2"""
+    jpeg = coef_jpeg_for(name)
+    d = cj.decode_coefs(jpeg)
+    hostsim.hostsim_take_list_counts(None, 0)
+    hostsim.hostsim_set_list_counts(1)
+    try:
+        rc, want, hrc, got = _hostsim_decode(hostsim, oracle, jpeg, 3 if "gray" in name else 2, 0)
+    finally:
+        hostsim.hostsim_set_list_counts(0)
+    buf = np.zeros((4096, 9), dtype=np.uint32)
+    n = hostsim.hostsim_take_list_counts(buf.ctypes.data_as(C.c_void_p), 4096)
+    assert hrc == 0 and np.array_equal(got, want)
+    tiles = buf[:n][buf[:n, 2] > 0]                       # (without the list's padding entries)
+    cx, cy, shapes, (hs, vs) = cj.geometry(d["width"], d["height"], d["sampling"])
+    assert len(tiles) == cy and np.all(tiles[:, 2] == cx)           # (one tile per MCU row: the corpus' geometry is the kernel's)
+    pairs, moved, refused, masks = set(), False, False, set()
+    kinds = set()
+    for my, mx0, count, c0, c1, k0, k1, k2, k3 in tiles.tolist():
+        ncls, items = [0, 0, 0, 0], [0, 0]
+        for m in range(mx0, mx0 + count):
+            blocks = [(0, my * vs + v, m * hs + h) for v in range(vs) for h in range(hs)] + [(c, my, m) for c in range(1, len(shapes))]
+            for c, by, bx in blocks:
+                zz = d["coefs"][c][by, bx]
+                cls, ncols, rows47 = _class_of(zz)
+                ncls[cls] += 1
+                items[1 if rows47 else 0] += ncols
+                nat = np.zeros(64, dtype=np.int64)
+                nat[cj._ZIGZAG] = zz
+                nat[0] = 0
+                cols = 0
+                for i in np.nonzero(nat)[0]:
+                    cols |= 1 << (int(i) & 7)
+                masks.add((cols, rows47 and cols != 0))
+        n0, n1, n2, n3 = ncls
+        rem1, slack2 = n1 & 7, (8 - (n2 & 7)) & 7
+        k = rem1 if 0 < rem1 <= slack2 else 0
+        assert [c0, c1, k0, k1, k2, k3] == [items[0], items[1], n0, n1 - k, n2 + k, n3], (name, my)
+        pairs.add((n1 & 7, n2 & 7))
+        moved |= rem1 > 0 and rem1 == slack2
+        refused |= rem1 > 0 and rem1 == slack2 + 1
+        kinds.add(tuple(i for i, x in enumerate(ncls) if x))
+    assert len(pairs) == 64, sorted(set((a, b) for a in range(8) for b in range(8)) - pairs)
+    assert moved and refused
+    assert {(3,), (0,), (2,)} <= kinds
+    assert len(masks) == 255 * 2 + 1, len(masks)
+
+
+@pytest.mark.parametrize("name", sorted(k for k in COEF_CASES if k.startswith("k_huff_") and k not in COEF_CORRUPT))
+def test_every_ac_lut_entry_is_hit(name):
+    """every symbol of every AC table the file uses -- short half (codes that do not start 111111) and long half -- is decoded"""
+    from jpegdec_amd.synth import _codes
+    d = cj.decode_coefs(coef_jpeg_for(name))
+    halves = set()
+    used = {ta for _, ta in d["table_ids"]}
+    assert used == ({0} if d["sampling"] == "gray" else {0, 1})
+    for ta in used:
+        bits, vals = d["huff"][(1, ta)]
+        hist = d["hist"][(1, ta)]
+        assert sorted(vals) == sorted(cj.AC_SYMBOLS)
+        missing = [s for s in vals if not hist.get(s)]
+        assert not missing, (name, ta, missing)
+        for s, (code, ln) in _codes(bits, vals).items():
+            halves.add(ln >= 6 and code >> (ln - 6) == 63)
+    assert halves == {False, True}
+    assert 11 in d["hist"][(0, 0)]                          # DC category 11
+
+
+@pytest.mark.parametrize("layout", ["gray", "c444", "c422", "c440", "c420"])
+def test_fast_path_reaches_the_range_wrap(layout, hostsim, oracle):
+    """a 24-bit-multiply case whose samples leave the 10-bit field of the range limit (ucRangeTable[(v >> 5) & 0x3ff]): in the
+    kernels' integer path (the wave emulator's luma plane), blocks whose every sample lies far above 255 come out darker than 255
+    somewhere, and blocks far below 0 brighter than 0 -- what a saturating limit cannot give, the wrap can"""
+    jpeg = coef_jpeg_for("k_single_q255_" + layout)
+    assert hostsim.hostsim_fast_mul(jpeg, len(jpeg)) == 1
+    rc, want, hrc, got = _hostsim_decode(hostsim, oracle, jpeg, 3, 0)
+    assert hrc == 0 and np.array_equal(got, want)
+    y = cj.float_planes(cj.decode_coefs(jpeg))[0]
+    wrapped_hi = wrapped_lo = 0
+    for by in range(y.shape[0] // 8):
+        for bx in range(y.shape[1] // 8):
+            f = y[by * 8:by * 8 + 8, bx * 8:bx * 8 + 8]
+            px = got[by * 8:by * 8 + 8, bx * 8:bx * 8 + 8]
+            if f.min() > 128 + 640:
+                wrapped_hi += bool(np.any(px != 255))
+            elif f.max() < 128 - 640:
+                wrapped_lo += bool(np.any(px != 0))
+    assert wrapped_hi > 0 and wrapped_lo > 0, (wrapped_hi, wrapped_lo)
