@@ -367,6 +367,361 @@ def _k_edge(sampling, w, h):
     return dict(width=w, height=h, sampling=sampling, coefs=coefs, quant={0: [16] * 64, 1: [16] * 64})
 
 
+# ---- scan-window edges (k_window_*) and the 1/4 kernel's five-dword reach (k_q4reach_*) --------------------------------------------
+# A tile stages bytes [win_lo, hi) of the filtered scan in its wavefront's LDS window (jda_tile_setup_from): win_lo = byte(entry of its
+# first block) & ~15, hi = (byte(entry of the first block behind it) + 8 + 12 + 15) & ~15, clamped to (scan_len + 32) & ~15;
+# win_need = hi - win_lo against the layout's WIN_BYTES.  The builders below write tiles whose win_need is chosen to the byte: every
+# DC difference is 0 (a 2-bit code), a block's AC bits are a sum of Annex K symbol lengths, and the last block of each tile is searched
+# for with the reference reader's model (tests/coef_jpeg.py reader_entries) until the next tile's first entry lands where it should --
+# with a bit offset below 8, so that the serial pre-scan's entry and the canonical (bit >> 3, bit & 7) of the parallel and the device
+# pre-scans name the same byte.
+_LT_BYTES, _COEF_STRIDE, _LDS_BYTES = 10528, 136, 160 * 1024          # JDA_LT_BYTES, JDA_COEF_STRIDE, the LDS of a CU
+_NBLK = {"gray": 1, "4:4:4": 3, "4:2:2": 4, "4:4:0": 4, "4:2:0": 6}
+
+
+def lds_layout(sampling, big):
+    """jda_lds_layout<MODE, BIG> restated: (MCUS, WAVES, WIN_BYTES, WIN_OFF) -- tests pin it to the compiled header"""
+    nblk = _NBLK[sampling]
+    mcus = 20 if sampling == "4:4:4" else 64 // nblk
+    blocks = mcus * nblk
+    win_off = (blocks * _COEF_STRIDE + 64 + 32 + 15) // 16 * 16
+    free = _LDS_BYTES - _LT_BYTES - 16
+    waves = min(16, free // (win_off + blocks * 16 + 16)) - big
+    return mcus, waves, min(2048, free // waves // 16 * 16 - win_off), win_off
+
+
+def _sym_costs(huff_t):
+    """{(run, size): bits} of an AC table's symbols (code + magnitude), EOB as (0, 0)"""
+    from jpegdec_amd.synth import _codes
+    return {(rs >> 4, rs & 15): ln + (rs & 15) for rs, (code, ln) in _codes(*huff_t).items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _fill_table(table_key):
+    """fewest run-0 symbols whose bits sum to b, for every b up to 1700: dp[b] = (count, size of one of them).  Only symbols of 17 bits
+    at most (code + magnitude): the reference's 64-bit reader cannot truncate their magnitude reads (it holds 17 bits more than 47)"""
+    costs = _sym_costs(_cj.annex_k()[2][(1, table_key)])
+    sizes = [(costs[(0, sz)], sz) for sz in range(1, 11) if costs[(0, sz)] <= 17]
+    dp = [(0, 0)] + [(10 ** 9, 0)] * 1700
+    for b in range(1, 1701):
+        for c, sz in sizes:
+            if c <= b and dp[b - c][0] + 1 < dp[b][0]:
+                dp[b] = (dp[b - c][0] + 1, sz)
+    return dp, costs[(0, 0)], costs
+
+
+@functools.lru_cache(maxsize=None)
+def _block_sizes(table_key, bits, tail=()):
+    """magnitude sizes of run-0 symbols that, with the symbols of `tail` ((run, size) pairs) and EOB, take exactly `bits` AC bits;
+    None if no such block (at most 62 coefficients before EOB)"""
+    dp, eob, costs = _fill_table(table_key)
+    b = bits - eob - sum(costs[t] for t in tail)
+    if b < 0 or b > 1700 or dp[b][0] + sum(1 + r for r, _ in tail) > 62:
+        return None
+    out = []
+    while b:
+        out.append(dp[b][1])
+        b -= costs[(0, dp[b][1])]
+    return tuple(out)
+
+
+def _reader_step(pos, off, syms, restart=False):
+    """the reference reader over one block whose DC difference is 0 (reader_entries, in (byte, offset) form): syms = [(bits of the
+    code, magnitude size or -1 for EOB)] -> (pos, off behind it, its entry, a truncated read)"""
+    if restart:
+        off = (off + 7) & ~7
+    if off > 47:
+        pos, off = pos + (off >> 3), off & 7
+    off += 2
+    if off > 47:
+        pos, off = pos + (off >> 3), off & 7
+    entry, trunc = (pos, off), False
+    for ln, sz in syms:
+        off += ln
+        if sz < 0:
+            break
+        if sz and off + sz > 64:
+            trunc = True
+        off += sz
+        if off > 47:
+            pos, off = pos + (off >> 3), off & 7
+    return pos, off, entry, trunc
+
+
+@functools.lru_cache(maxsize=None)
+def _symbols(sampling, t, sizes, tail):
+    """(pairs, [(code bits, magnitude size)] + EOB) of a block of run-0 symbols of these sizes, then `tail`"""
+    from jpegdec_amd.synth import _codes
+    lens = {(rs >> 4, rs & 15): ln for rs, (code, ln) in _codes(*_cj.annex_k()[2][(1, t)]).items()}
+    pairs = tuple((0, sz) for sz in sizes) + tuple(tail)
+    return pairs, tuple((lens[p], p[1]) for p in pairs) + ((lens[(0, 0)], -1),)
+
+
+class _WindowStream:
+    """blocks in stream order, planned with the reader model; tiles are added one after the other"""
+
+    def __init__(self, sampling, rng):
+        self.sampling, self.rng = sampling, rng
+        self.pos = self.off = 0
+        self.restart = False                   # the next block starts a restart interval
+        self.blocks = []                       # per block: [(run, value)] of its AC symbols (EOB implied)
+        self.entries = []                      # the model's entry of every block (byte, offset, truncated)
+
+    def table(self, i):
+        nb, nl = _NBLK[self.sampling], _NBLK[self.sampling] - (2 if self.sampling != "gray" else 0)
+        return 0 if i % nb < nl else 1
+
+    def symbols(self, t, sizes, tail):
+        return _symbols(self.sampling, t, sizes, tail)
+
+    def value(self, sz):
+        v = int(self.rng.integers(1 << (sz - 1), 1 << sz))
+        return v if self.rng.integers(0, 2) else -v
+
+    def add(self, pairs):
+        t = self.table(len(self.blocks))
+        _, syms = self.symbols(t, tuple(p[1] for p in pairs if p[0] == 0), tuple(p for p in pairs if p[0] != 0))
+        self.pos, self.off, entry, trunc = _reader_step(self.pos, self.off, syms, self.restart)
+        self.restart = False
+        self.entries.append((entry[0], entry[1], trunc))
+        self.blocks.append([(r, self.value(sz)) for r, sz in pairs])
+
+    def next_entry(self, restart=False):
+        """the entry a block behind the last one would get (its DC difference 0)"""
+        return _reader_step(self.pos, self.off, [], restart)[2]
+
+    def tile(self, nb, target, restart_next=False, trunc_last=False, last=False):
+        """nb blocks; target(pos, off) of the next tile's first entry (or, last=True, of the closing entry) -> bool.  The blocks share
+        the bits in front of the last one; the last one is searched for"""
+        saved = (self.pos, self.off, len(self.blocks), self.restart)
+        for attempt in range(64):
+            if self._tile(nb, target, restart_next, trunc_last, last, 64 + 8 * attempt):
+                self.restart = restart_next
+                return
+            self.pos, self.off, _, self.restart = saved    # (the byte the reader can reach next depends on where it last moved: again,
+            del self.blocks[saved[2]:]                     # with the blocks in front of the last two a little shorter)
+            del self.entries[saved[2]:]
+        raise AssertionError("no block reaches the tile's target")
+
+    def _tile(self, nb, target, restart_next, trunc_last, last, slack):
+        want = target.bits
+        start = 8 * self.pos + self.off
+        per = max(4, (want - start - 2 * nb - slack) // nb)
+        for i in range(nb - 2):
+            t = self.table(len(self.blocks))
+            b = per + int(self.rng.integers(-per // 8, per // 8 + 1))
+            sizes = None
+            while sizes is None:
+                sizes = _block_sizes(t, b)
+                b += 1
+            self.add([(0, sz) for sz in sizes])
+        # the last two blocks: the reader's refills follow the symbols, not only their bits -- the one in front of the last is
+        # varied as well
+        t2, t = self.table(len(self.blocks)), self.table(len(self.blocks) + 1)
+        tail = ((1, 10),) if trunc_last else ()
+        mid = max(8, (want - (8 * self.pos + self.off) - 8 - (26 if trunc_last else 0)) // 2)
+        for d2 in range(0, 48):
+            b2 = mid + (d2 // 2 if d2 % 2 == 0 else -(d2 // 2) - 1)
+            sizes2 = _block_sizes(t2, b2)
+            if sizes2 is None:
+                continue
+            pairs2, syms2 = self.symbols(t2, sizes2, ())
+            pos2, off2, _, _ = _reader_step(self.pos, self.off, syms2)
+            base = want - (8 * pos2 + off2) - 4
+            for d in range(0, 160):
+                b = base + (d // 2 if d % 2 == 0 else -(d // 2) - 1)
+                sizes = _block_sizes(t, b, tail)
+                if sizes is None:
+                    continue
+                pairs, syms = self.symbols(t, sizes, tail)
+                pos, off, entry, trunc = _reader_step(pos2, off2, syms)
+                if trunc_last and not trunc:
+                    continue
+                if last:
+                    ok = target(pos, off)
+                else:
+                    ok = target(*_reader_step(pos, off, [], restart_next)[2])
+                if ok:
+                    self.add(pairs2)
+                    self.add(pairs)
+                    return True
+        return False
+
+
+def _at(x, phase_only=False):
+    """target: the next entry at byte x -- or, phase_only, at a byte of x's phase mod 16 within 64 bytes of x --, offset < 8 (the
+    serial and the canonical entry agree)"""
+    if phase_only:
+        f = lambda pos, off: pos % 16 == x % 16 and abs(pos - x) <= 64 and off < 8
+    else:
+        f = lambda pos, off: pos == x and off < 8
+    f.bits = 8 * x + 3
+    return f
+
+
+def _window_plan(sampling, kind):
+    """(tiles per row, rows, partial MCUs of a row's last tile, restart interval) and the tile specs:
+    {slot: (win_need, 'tight' | 'loose', start phase, options)}, the fillers' byte range"""
+    mcus, ws_waves, ws, _ = lds_layout(sampling, 0)
+    _, wl_waves, wl, _ = lds_layout(sampling, 1)
+    if kind == "dri":
+        full, rows, part, dri = 4, 3, 0, mcus
+    else:
+        # T tiles: ceil(T / waves) differs between the two layouts (112 for 16 / 15 wavefronts, 105 for 15 / 14)
+        full, rows = (7, 14) if ws_waves == 16 else (6, 15)
+        part, dri = mcus // 2, 0
+    per_row = full + (1 if part else 0)
+    T = per_row * rows
+    partial = [r * per_row + full for r in range(rows)] if part else []
+    edges = []
+    if kind in ("small_tight", "small_loose"):
+        edges.append((ws + 32, kind[6:], 0, ""))                                  # the one tile over the small window
+        edges += [(n, f, ph, "") for n in (ws - 16, ws) for f in ("tight", "loose") for ph in (0, 15)]
+        edges += [(ws, "tight", 15, "trunc")]
+        fill, W = (ws * 3 // 4, ws - 48), ws
+    elif kind == "large":
+        edges += [(n, f, ph, "") for n in (wl - 16, wl, wl + 16, wl + 32) for f in ("tight", "loose") for ph in (0, 15)]
+        edges += [(n, f, ph, "") for n in (ws + 16, ws + 32) for f in ("tight", "loose") for ph in (0, 15)]
+        edges += [(wl, "tight", 0, "trunc")]
+        fill, W = (ws + 64, wl - 64), wl
+    else:
+        edges += [(n, "tight", 0, "") for n in (wl + 32, wl + 16, ws + 32, ws + 16)]
+        fill, W = (ws // 2, ws - 64), wl
+    spec = {}
+    # a partial tile at W (a row's last tile, count < MCUS) and the last tile, clamped at the end of the scan
+    odd_partial = [i for i in partial if i % 2 == 1 and i < T - 2]
+    if odd_partial:
+        spec[odd_partial[0]] = (W, "tight", 0, "partial")
+    # (the host's routing count takes hi before the clamp: a last tile clamped to W is over W -- in a "small" image it is clamped to W - 16)
+    spec[T - 1] = (W - 16 if kind.startswith("small") else W, "clamp", 0, "last15" if kind in ("small_loose", "dri") else "last14")
+    slot = 1
+    for e in edges:
+        while slot in spec or slot >= T - 2:
+            slot += 2
+            assert slot < T, (sampling, kind)
+        spec[slot] = e
+        slot += 2
+    return dict(full=full, rows=rows, part=part, dri=dri, T=T, spec=spec, fill=fill, mcus=mcus, big4k=kind == "large")
+
+
+def _k_window(sampling, kind):
+    rng = _np.random.default_rng(sum(map(ord, sampling + kind)))
+    P = _window_plan(sampling, kind)
+    nblk = _NBLK[sampling]
+    mw, mh = _MCU_PX[sampling]
+    mcus_x = P["full"] * P["mcus"] + P["part"]
+    width, height = mcus_x * mw - 3, P["rows"] * mh - 5                        # (ragged: the last MCU column and row are cut)
+    st = _WindowStream(sampling, rng)
+    per_row = P["full"] + (1 if P["part"] else 0)
+    spec = P["spec"]
+    win_lo = 0
+    for i in range(P["T"]):
+        count = P["part"] if P["part"] and i % per_row == P["full"] else P["mcus"]
+        nb = count * nblk
+        if i == P["T"] - 1:
+            # the last tile: hi clamped at (scan_len + 32) & ~15 = win_lo + W -- scan_len = 14 or 15 mod 16, the closing entry's byte
+            # close enough to the end that the +8+12 reach passes the clamp
+            need, _, _, opt = spec[i]
+            cls = 14 if opt == "last14" else 15
+            scan_len = win_lo + need - 32 + cls
+
+            def target(pos, off, scan_len=scan_len, cls=cls):
+                return (8 * pos + off + 7) // 8 == scan_len and pos >= scan_len - (1 if cls == 14 else 2)
+            target.bits = 8 * scan_len - 4
+            st.tile(nb, target, last=True)
+            continue
+        if i in spec:
+            need, fit, _, opt = spec[i]
+            assert i + 1 not in spec
+            x = win_lo + need - (20 if fit == "tight" else 35)            # tight: hi = byte + 20, no spare byte; loose: 15 spare
+        else:
+            a, b = P["fill"]
+            size = 4200 if (P["big4k"] and i == 2) else int(rng.integers(a, b))
+            nxt = spec.get(i + 1)
+            ph = nxt[2] if nxt is not None else int(rng.integers(0, 16))
+            x = st.pos + size
+            x += (ph - x) % 16
+        tgt = _at(x, phase_only=i not in spec)
+        st.tile(nb, tgt, restart_next=bool(P["dri"]), trunc_last=i in spec and spec[i][3] == "trunc")
+        win_lo = st.next_entry(bool(P["dri"]))[0] & ~15
+    coefs = _cj.zero_coefs(width, height, sampling)
+    cx, cy = _cj.geometry(width, height, sampling)[:2]
+    order = _blocks_in_mcu_order(coefs, sampling, cx, cy)
+    assert len(order) == len(st.blocks)
+    for (c, by, bx), pairs in zip(order, st.blocks):
+        k = 1
+        for r, v in pairs:
+            k += r
+            coefs[c][by, bx, k] = v
+            k += 1
+    return dict(width=width, height=height, sampling=sampling, coefs=coefs, quant={0: [2] * 64, 1: [2] * 64},
+                restart_interval=P["dri"])
+
+
+def _k_q4reach(sampling, variant):
+    """the 1/4 kernel's five dwords (jda_q4_load): one AC table (Annex K's luma table for both: every S = 10 symbol has a 16-bit
+    code).  'phase': blocks whose first four AC symbols are (0, 10) -- 4 x 26 = 104 bits, the most four symbols take -- with the first
+    AC bit at every bit of its dword; blocks that end with EOB on the first trip in front of such blocks.  'endK': such a block, behind
+    an EOB-only block, is the scan's last, its first AC bit late in its dword, scan_len = K mod 4."""
+    rng = _np.random.default_rng(sum(map(ord, sampling + variant)))
+    nblk = _NBLK[sampling]
+    M, E = ((0, 10),) * 4, ()
+    lens = _symbols(sampling, 0, (), ())[1][-1][0]               # (EOB's code length)
+    seq, cur = [], 0                                             # blocks' AC pairs; bit position of the next block's start
+
+    def add(pairs):
+        nonlocal cur
+        seq.append(pairs)
+        _, syms = _symbols(sampling, 0, tuple(p[1] for p in pairs), ())
+        cur += 2 + sum(ln + max(sz, 0) for ln, sz in syms)
+
+    def filler_to(phase, extra=0):                               # a filler block: the block behind `extra` bits of others starts its AC at `phase`
+        b = 10 + ((phase - cur - 2 - extra - 2 - 10) % 32)
+        add(tuple((0, sz) for sz in _block_sizes(0, b)))
+    if variant == "phase":
+        n = {1: 88, 3: 90, 4: 96, 6: 90}[nblk]
+        for ph in range(32):
+            filler_to(ph)
+            add(M)
+        for ph in range(24, 32):
+            filler_to(ph, extra=2 + lens)
+            add(E)
+            add(M)
+        while len(seq) < n:
+            add(tuple((0, sz) for sz in _block_sizes(0, int(rng.integers(10, 60)))))
+    else:
+        k = int(variant[3:])
+        n = {1: 16, 3: 18, 4: 16, 6: 18}[nblk]
+        while len(seq) < n - 3:
+            add(tuple((0, sz) for sz in _block_sizes(0, int(rng.integers(10, 60)))))
+        best = None
+        for b in range(10, 42):                                  # (of the bit phases with scan_len = K mod 4, the latest)
+            p_m = cur + 2 + b + 2 + lens + 2                         # the last block's first AC bit
+            if ((p_m + 104 + lens + 7) // 8) % 4 == k and (best is None or ((p_m - 1) & 31) > best[0]):
+                best = ((p_m - 1) & 31, b)
+        add(tuple((0, sz) for sz in _block_sizes(0, best[1])))
+        add(E)
+        add(M)
+    cx = {1: 8, 3: 6, 4: 4, 6: 3}[nblk]
+    mcus = len(seq) // nblk
+    assert mcus * nblk == len(seq) and mcus % cx == 0, (sampling, variant, len(seq))
+    mw, mh = _MCU_PX[sampling]
+    width, height = cx * mw, mcus // cx * mh
+    coefs = _cj.zero_coefs(width, height, sampling)
+    order = _blocks_in_mcu_order(coefs, sampling, cx, mcus // cx)
+    for (c, by, bx), pairs in zip(order, seq):
+        for i, (r, sz) in enumerate(pairs):
+            v = int(rng.integers(1 << (sz - 1), 1 << sz))
+            coefs[c][by, bx, 1 + i] = v if rng.integers(0, 2) else -v
+    huff = dict(_cj.annex_k()[2])
+    huff[(1, 1)] = huff[(1, 0)]
+    return dict(width=width, height=height, sampling=sampling, coefs=coefs, quant={0: [1] * 64, 1: [1] * 64}, huff=huff)
+
+
+WINDOW_KINDS = ("small_tight", "small_loose", "large", "dri")
+Q4REACH_VARIANTS = ("phase", "end0", "end1", "end2", "end3")
+
+
 def _coef_cases():
     cases = {}
     for lay in _cj.LAYOUTS:
@@ -389,6 +744,11 @@ def _coef_cases():
         per = _TILE_MCUS[lay]
         for w, h in ((1, 1), (7, 9), (17, 15), ((per - 1) * mw - 3, mh + 5), ((per + 1) * mw - 5, 2 * mh - 1)):
             cases["k_edge_%s_%dx%d" % (s, w, h)] = (_k_edge, (lay, w, h))
+    for lay in _cj.LAYOUTS:
+        for kind in WINDOW_KINDS:
+            cases["k_window_%s_%s" % (_cj.SHORT[lay], kind)] = (_k_window, (lay, kind))
+        for v in Q4REACH_VARIANTS:
+            cases["k_q4reach_%s_%s" % (_cj.SHORT[lay], v)] = (_k_q4reach, (lay, v))
     cases["k_dcdrift_c420_40000_ycb_q2_par"] = (_k_dcdrift_par, (0,))
     cases["k_dcdrift_c420_40000_ycb_q2_par_dri64"] = (_k_dcdrift_par, (64,))
     cases["k_huff_cross_c420"] = (_k_huff_cross, ("4:2:0",))

@@ -94,24 +94,31 @@ def _mag(v):
 
 
 class _BitWriter:
+    """MSB-first bit packer with byte stuffing; `bits` counts the bits of the FILTERED scan (no stuffing, no markers)"""
     def __init__(self):
         self.out = bytearray()
         self.acc = 0
         self.n = 0
+        self.bits = 0
 
     def put(self, code, ln):
-        for i in range(ln - 1, -1, -1):
-            self.acc = (self.acc << 1) | ((code >> i) & 1)
-            self.n += 1
-            if self.n == 8:
-                self.out.append(self.acc)
-                if self.acc == 0xFF:
-                    self.out.append(0)
-                self.acc = self.n = 0
+        self.acc = (self.acc << ln) | (code & ((1 << ln) - 1))
+        self.n += ln
+        self.bits += ln
+        if self.n >= 64:
+            self._drain()
+
+    def _drain(self):
+        k = self.n >> 3
+        if k:
+            self.n -= 8 * k
+            self.out += (self.acc >> self.n).to_bytes(k, "big").replace(b"\xff", b"\xff\x00")
+            self.acc &= (1 << self.n) - 1
 
     def flush(self):
-        if self.n:
-            self.put((1 << (8 - self.n)) - 1, 8 - self.n)
+        if self.n & 7:
+            self.put((1 << (8 - (self.n & 7))) - 1, 8 - (self.n & 7))
+        self._drain()
 
 
 def _seg(marker, payload):
@@ -119,14 +126,18 @@ def _seg(marker, payload):
 
 
 def write_jpeg(width, height, sampling, coefs, quant, quant_ids=None, huff=None, table_ids=None, restart_interval=0,
-               ac_pairs=None, pad_to=300):
+               ac_pairs=None, pad_to=300, return_layout=False):
     """coefs: per component (block rows, block columns, 64) zig-zag arrays over the MCU grid (zero_coefs' shapes).
     quant: {table id: 64 zig-zag entries}; a table with an entry above 255 is written at 16-bit precision.
     quant_ids: quantiser per component (default luma 0, chroma 1, or 0 where only table 0 is given).
     huff: {(class, id): (bits, vals)} (default Annex K); table_ids: (DC, AC) table per component.
     ac_pairs: {(component, block row, block column): [(run, value), ...]} -- that block's AC symbols exactly as given, no EOB
     added (the syntax of runs past position 63).  pad_to: a COM segment brings smaller files up to this size (the reference
-    refuses files under 256 bytes)."""
+    refuses files under 256 bytes).
+    return_layout: also return the scan's layout, (jpeg, layout): layout["blocks"] lists every block in stream order as
+    (component, block row, block column, DC symbol, AC symbols), a symbol = (position of its first bit in the FILTERED scan,
+    code length, magnitude bits or -1 for EOB); layout["restarts"] the filtered bit position of every restart interval's start;
+    layout["scan_bits"] the filtered scan's length in bits (whole bytes)."""
     cx, cy, shapes, (hs, vs) = geometry(width, height, sampling)
     nc = len(shapes)
     assert len(coefs) == nc and all(c.shape == (r, w, 64) for c, (r, w) in zip(coefs, shapes))
@@ -140,6 +151,7 @@ def write_jpeg(width, height, sampling, coefs, quant, quant_ids=None, huff=None,
     ac_t = {th: _codes(*huff[(1, th)]) for (tc, th) in huff if tc == 1}
     ac_pairs = ac_pairs or {}
     bw = _BitWriter()
+    blocks, restarts = [], []
 
     def block(c, by, bx, pred):
         td, ta = table_ids[c]
@@ -147,30 +159,39 @@ def write_jpeg(width, height, sampling, coefs, quant, quant_ids=None, huff=None,
         dc = int(zz[0])
         s, b = _mag(dc - pred)
         assert s <= 11, ("DC difference out of range", c, by, bx, dc - pred)
+        syms = []
+        dc_sym = (bw.bits, dc_t[td][s][1], s)
         bw.put(*dc_t[td][s])
         if s:
             bw.put(b, s)
+
+        def ac(rs, s, b):
+            code, ln = ac_t[ta][rs]
+            syms.append((bw.bits, ln, s if rs else -1))
+            bw.put(code, ln)
+            if s:
+                bw.put(b, s)
+
         if (c, by, bx) in ac_pairs:
             for run, v in ac_pairs[(c, by, bx)]:
                 s, b = _mag(v)
-                bw.put(*ac_t[ta][(run << 4) | s])
-                if s:
-                    bw.put(b, s)
-            return dc
-        nz = [i for i in range(1, 64) if zz[i]]
-        run, k = 0, 1
-        for i in nz:
-            run = i - k
-            while run > 15:
-                bw.put(*ac_t[ta][0xF0])
-                run -= 16
-            s, b = _mag(zz[i])
-            assert 1 <= s <= 10, ("AC value out of range", c, by, bx, i, int(zz[i]))
-            bw.put(*ac_t[ta][(run << 4) | s])
-            bw.put(b, s)
-            k = i + 1
-        if not nz or nz[-1] < 63:
-            bw.put(*ac_t[ta][0x00])
+                ac((run << 4) | s, s, b)
+        else:
+            nz = [i for i in range(1, 64) if zz[i]]
+            run, k = 0, 1
+            for i in nz:
+                run = i - k
+                while run > 15:
+                    ac(0xF0, 0, 0)
+                    run -= 16
+                s, b = _mag(zz[i])
+                assert 1 <= s <= 10, ("AC value out of range", c, by, bx, i, int(zz[i]))
+                ac((run << 4) | s, s, b)
+                k = i + 1
+            if not nz or nz[-1] < 63:
+                ac(0x00, 0, 0)
+        if return_layout:
+            blocks.append((c, by, bx, dc_sym, syms))
         return dc
 
     pred = [0] * nc
@@ -182,6 +203,7 @@ def write_jpeg(width, height, sampling, coefs, quant, quant_ids=None, huff=None,
             bw.out += bytes([0xFF, 0xD0 + (rst & 7)])
             rst += 1
             pred = [0] * nc
+            restarts.append(bw.bits)
         for v in range(vs):
             for h in range(hs):
                 pred[0] = block(0, my * vs + v, mx * hs + h, pred[0])
@@ -212,7 +234,56 @@ def write_jpeg(width, height, sampling, coefs, quant, quant_ids=None, huff=None,
     if short > 0:
         hdr += _seg(0xFE, b"\x00" * max(short, 1))
     hdr += _seg(0xDA, bytes([nc]) + b"".join(bytes([c[0], (td << 4) | ta]) for c, (td, ta) in zip(comp, table_ids)) + bytes([0, 63, 0]))
+    if return_layout:
+        return bytes(hdr) + body, dict(blocks=blocks, restarts=restarts, scan_bits=bw.bits,
+                                       round_last=bool(restart_interval) and (cx * cy) % restart_interval == 0)
     return bytes(hdr) + body
+
+
+def reader_entries(layout):
+    """The block index the reference's bit reader implies (the serial host pre-scan writes it): for every block,
+    (byte, bit offset, truncated) of the reader at the block's first AC symbol -- behind the refill at the top of the AC loop --
+    and the closing entry (byte, offset) where the last block leaves it.  The reader holds 64 bits from its byte on and moves
+    its byte on (off >> 3 bytes) only when more than 47 bits of them are used: at a block's start, in front of a DC magnitude
+    the DC table's lookup does not hold (code + magnitude longer than six bits), at the top of the AC loop and behind every AC
+    symbol but EOB.  A magnitude read is truncated where it reaches past the 64 bits (the bits it misses read as zeros).  A
+    restart interval starts on the next byte boundary (the byte is not moved); so does the closing entry where the last interval
+    is whole."""
+    pos = off = 0
+    out = []
+    restarts = set(layout["restarts"])
+
+    def check(pos, off):
+        return (pos + (off >> 3), off & 7) if off > 47 else (pos, off)
+
+    for c, by, bx, (p, ln, s), syms in layout["blocks"]:
+        if p in restarts:
+            assert (8 * pos + off + 7) // 8 * 8 == p
+            off = p - 8 * pos
+        assert 8 * pos + off == p
+        pos, off = check(pos, off)
+        if s and ln + s <= 6:
+            off += ln + s
+        else:
+            off += ln
+            if s:
+                pos, off = check(pos, off)
+                off += s
+        pos, off = check(pos, off)
+        entry = [pos, off, False]
+        for q, ln, s in syms:
+            assert 8 * pos + off == q
+            off += ln
+            if s < 0:
+                break
+            if s and off + s > 64:
+                entry[2] = True
+            off += s
+            pos, off = check(pos, off)
+        out.append(tuple(entry))
+    if layout.get("round_last"):              # (the interval count runs out behind the last MCU as well)
+        off = (off + 7) & ~7
+    return out, (pos, off)
 
 
 # ---- the independent decoder ---------------------------------------------------------------------------------------

@@ -10,8 +10,6 @@
 #include <string.h>
 
 #include <vector>
-
-#include <vector>
 static unsigned g_seg_steps = 0;
 static unsigned long long g_all_steps = 0;
 static bool g_pair_off = false;
@@ -29,8 +27,34 @@ extern "C" void hostsim_set_chunked(int on) { g_use_cont = on; }      // (the se
 extern "C" const uint32_t *jda_image_block_cont(const jda_image *img, const uint32_t **cont_first, uint32_t *n_cont);
 static int g_reverse_tiles = 0;   // tests run the tiles in reverse order too: results must not depend on which wave finishes first
 extern "C" void hostsim_set_reverse(int on) { g_reverse_tiles = on; }
-static uint32_t g_window_bytes = 1024;   // tests shrink it to exercise the HBM fall-back of the bit reader (each layout caps it at its WIN_BYTES)
-extern "C" void hostsim_set_window(uint32_t bytes) { g_window_bytes = bytes > 1024 ? 1024 : (bytes & ~15u); }
+// the scan window of the emulated wavefront: 1,024 bytes by default; tests shrink it to exercise the HBM fall-back of the bit reader, or
+// set a layout's own WIN_BYTES (hostsim_lds_layout).  Each layout caps it at its large-window WIN_BYTES: (1 << 20) = the most there is
+static uint32_t g_window_bytes = 1024;
+extern "C" void hostsim_set_window(uint32_t bytes) { g_window_bytes = bytes & ~15u; }
+static uint8_t g_poison = 0xA5;          // what the wavefront's LDS holds before a tile is staged (it is not zero-initialised on the GPU either)
+extern "C" void hostsim_set_poison(uint32_t byte) { g_poison = (uint8_t)byte; }
+// jda_lds_layout<mode, big> as compiled from the kernels' header: out = MCUS, WAVES, WIN_BYTES, WIN_OFF
+template <int MODE, int BIG> static void lds_layout_of(uint32_t *out)
+{
+    typedef jda_lds_layout<MODE, BIG> L;
+    out[0] = L::MCUS; out[1] = L::WAVES; out[2] = L::WIN_BYTES; out[3] = L::WIN_OFF;
+}
+extern "C" int hostsim_lds_layout(int mode, int big, uint32_t *out)
+{
+    switch (mode * 2 + (big ? 1 : 0)) {
+    case JDA_MODE_GRAY * 2: lds_layout_of<JDA_MODE_GRAY, 0>(out); return 0;
+    case JDA_MODE_GRAY * 2 + 1: lds_layout_of<JDA_MODE_GRAY, 1>(out); return 0;
+    case JDA_MODE_444 * 2: lds_layout_of<JDA_MODE_444, 0>(out); return 0;
+    case JDA_MODE_444 * 2 + 1: lds_layout_of<JDA_MODE_444, 1>(out); return 0;
+    case JDA_MODE_420 * 2: lds_layout_of<JDA_MODE_420, 0>(out); return 0;
+    case JDA_MODE_420 * 2 + 1: lds_layout_of<JDA_MODE_420, 1>(out); return 0;
+    case JDA_MODE_422 * 2: lds_layout_of<JDA_MODE_422, 0>(out); return 0;
+    case JDA_MODE_422 * 2 + 1: lds_layout_of<JDA_MODE_422, 1>(out); return 0;
+    case JDA_MODE_440 * 2: lds_layout_of<JDA_MODE_440, 0>(out); return 0;
+    case JDA_MODE_440 * 2 + 1: lds_layout_of<JDA_MODE_440, 1>(out); return 0;
+    default: return -1;
+    }
+}
 
 // the IDCT work lists of every tile decoded while recording is on (jda_p1_lists): mcu_y, mcu_x0, count, then cnt[0..5] -- column
 // items of the short and the full column stage, the blocks of row classes 0 / 1 / 2 (after class 1's remainder moved), the DC-only ones
@@ -50,26 +74,37 @@ template <int MODE, bool FAST>
 static void run_tiles(const jda_dev_desc &D, const std::vector<jda_strip> &tiles)
 {
     typedef jda_lds_layout<MODE> L;
-    std::vector<uint64_t> tab_store((JDA_LT_BYTES + 7) / 8), lds_store((L::WAVE_BYTES + 7) / 8);
+    typedef jda_lds_layout<MODE, 1> LB;        // (the large-window layout: the same offsets, a larger share of the LDS)
+    static_assert((int)LB::WIN_OFF == (int)L::WIN_OFF && (int)LB::WAVE_BYTES >= (int)L::WAVE_BYTES, "one emulated wavefront serves both layouts");
+    typedef jda_mode_traits<MODE> T;
+    const uint32_t window = g_window_bytes < (uint32_t)LB::WIN_BYTES ? g_window_bytes : (uint32_t)LB::WIN_BYTES;
+    std::vector<uint64_t> tab_store((JDA_LT_BYTES + 7) / 8), lds_store((LB::WAVE_BYTES + 7) / 8);
     uint8_t *tab = (uint8_t *)tab_store.data(), *wl = (uint8_t *)lds_store.data();
     for (uint32_t tid = 0; tid < 256; tid++) jda_p0_tables(D, tid, 256, tab, L::LONG_LDS != 0);
     for (size_t ii = 0; ii < tiles.size(); ii++) {
         const size_t i = g_reverse_tiles ? tiles.size() - 1 - ii : ii;
         const jda_strip &S = tiles[i];
-        memset(wl, 0xA5, L::WAVE_BYTES);         // poison: LDS is not zero-initialised on the GPU either
-        const jda_tile_ctx C = jda_tile_setup<MODE>(D, S);
+        memset(wl, g_poison, LB::WAVE_BYTES);    // poison: LDS is not zero-initialised on the GPU either
+        // the tile's window as the kernel sets it up (jda_issue_index_loads + jda_tile_setup_from): the entries of its first block and
+        // of the first block behind it, the window the launch list's layout gives
+        uint32_t count = S.count;
+        const uint32_t first_mcu = S.mcu_y * D.mcus_x + S.mcu_x0;
+        if (first_mcu >= D.n_mcus_ok) count = 0;
+        else if (first_mcu + count > D.n_mcus_ok) count = D.n_mcus_ok - first_mcu;
+        const uint32_t first_block = first_mcu * T::NBLK, nb = count * T::NBLK;
+        const uint32_t ix_first = nb ? D.blk_index[first_block] : 0u, ix_end = nb ? D.blk_index[first_block + nb] : 0u;
+        const jda_tile_ctx C = jda_tile_setup_from<MODE>(D, S, ix_first, ix_end, window);
         jda_p1_inputs in[JDA_TILE_THREADS];
         for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) in[t] = jda_p1_prefetch<MODE>(D, C, t);
-        for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) jda_p0_stage<MODE>(D, C, t, wl, g_window_bytes);
+        for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) jda_p0_stage<MODE>(D, C, t, wl, window);
         uint32_t flags[JDA_TILE_THREADS];
         jda_lane_pre LP[JDA_TILE_THREADS];
         for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) jda_lane_prepare<MODE>(LP[t], D, t, tab);
         if (D.blk_cont_first && D.scale_shift < 2) {       // P1 in chunks (jda_p1c_*): pass A for every lane, the tile's continuation entries, the finish
-            typedef jda_mode_traits<MODE> T;
-            const uint32_t win_len = C.win_len < g_window_bytes ? C.win_len : g_window_bytes;
+            const uint32_t win_len = C.win_len < window ? C.win_len : window;
             const bool chunked = C.win_need <= win_len && !(D.pad_[0] & JDA_DESC_GENERAL_P1);
             jda_p1c_own own[JDA_TILE_THREADS];
-            for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) own[t] = jda_p1c_block<MODE>(D, C, in[t], LP[t], tab, wl, wl + L::WIN_OFF, g_window_bytes, chunked);
+            for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) own[t] = jda_p1c_block<MODE>(D, C, in[t], LP[t], tab, wl, wl + L::WIN_OFF, window, chunked);
             if (chunked && C.count) {
                 const uint32_t nb = C.count * (uint32_t)T::NBLK, c0 = D.blk_cont_first[C.first_block], c1 = D.blk_cont_first[C.first_block + nb];
                 for (uint32_t e = c0; e < c1; e++) {
@@ -81,7 +116,7 @@ static void run_tiles(const jda_dev_desc &D, const std::vector<jda_strip> &tiles
             }
             for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) flags[t] = jda_p1c_finish<MODE>(own[t], t, wl);
         } else
-        for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) flags[t] = jda_p1_entropy<MODE>(D, C, in[t], LP[t], tab, wl, wl + L::WIN_OFF, g_window_bytes);
+        for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) flags[t] = jda_p1_entropy<MODE>(D, C, in[t], LP[t], tab, wl, wl + L::WIN_OFF, window);
         if (D.scale_shift < 2) {
             for (uint32_t t = 0; t < JDA_TILE_THREADS; t++) jda_p1_lists<MODE>(D, LP[t], t, flags[t], flags, tab, wl);
             if (g_record_lists) {

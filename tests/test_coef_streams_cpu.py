@@ -15,7 +15,7 @@ from tests import coef_jpeg as cj
 from tests.cases import COEF_CASES, COEF_CORRUPT, FASTBOUND_Q, all_modes, coef_jpeg_for, coef_spec, custom_ac_table
 
 GOOD = sorted(k for k in COEF_CASES if k not in COEF_CORRUPT)
-FAMILIES = ("k_classes_", "k_single_", "k_fastbound_", "k_huff_", "k_dcdrift_", "k_edge_")
+FAMILIES = ("k_classes_", "k_single_", "k_fastbound_", "k_huff_", "k_dcdrift_", "k_edge_", "k_window_", "k_q4reach_")
 # the largest difference between the float64 decode and Pillow's (libjpeg-turbo, integer IDCT) on the in-range families,
 # measured: 2 on RGB (libjpeg rounds the samples before the colour conversion), 1 on the luma planes -- asserted with no slack
 FLOAT_BOUND_RGB = 2
