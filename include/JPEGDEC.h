@@ -60,7 +60,7 @@ typedef struct jpeg_draw_tag {
     int x, y;                 // upper left corner of this block of pixels
     int iWidth, iHeight;      // size of this block
     int iWidthUsed;           // columns that lie inside the image
-    int iBpp;                 // 8, 16 or 32
+    int iBpp;                 // 8, 16 or 32; 4, 2 or 1 from decodeDither (packed, most significant bits first)
     uint16_t *pPixels;        // strip of iWidth x (MCU height) pixels, pitch = iWidth pixels
     void *pUser;
 } JPEGDRAW;
@@ -99,6 +99,13 @@ class JPEGDEC {
     void getCropArea(int *x, int *y, int *w, int *h);
     void close();
     int decode(int x, int y, int iOptions);
+    // decodeDither: the image decoded as EIGHT_BIT_GRAYSCALE and error-diffused to FOUR / TWO / ONE_BIT_DITHERED on the GPU, bit-exact with the
+    // reference's JPEGDither; ONE draw callback per MCU row (iWidth = the whole MCU-padded row), the packed strip at the front of pDither
+    // (>= one MCU row of 8-bit pixels, as the reference needs; the bytes behind the packed strip are not written).  Refused:
+    // a null pDither or a pixel type that is not a dithered one (JPEG_INVALID_PARAMETER); a framebuffer, a crop rectangle, JPEG_USES_DMA
+    // (JPEG_UNSUPPORTED_FEATURE); a colour progressive file (as EIGHT_BIT_GRAYSCALE).  decode() with a dithered pixel type stays
+    // JPEG_UNSUPPORTED_FEATURE (the reference dereferences a null buffer there).  MCU-padded widths above 4096 pixels, where the
+    // reference's error row overruns its buffer, are dithered by the same rule.
     int decodeDither(uint8_t *pDither, int iOptions);
     int decodeDither(int x, int y, uint8_t *pDither, int iOptions);
     int getOrientation();

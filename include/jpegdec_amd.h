@@ -50,7 +50,12 @@ enum {
     JDA_RGB565_LITTLE_ENDIAN = 0,
     JDA_RGB565_BIG_ENDIAN = 1,
     JDA_RGB8888 = 2,            /* memory order R,G,B,A as the reference's scalar path (jpeg.inl:3162-3175) */
-    JDA_EIGHT_BIT_GRAYSCALE = 3
+    JDA_EIGHT_BIT_GRAYSCALE = 3,
+    /* error-diffused 4 / 2 / 1 bits per pixel (JPEGDither, jpeg.inl:4871-4940): not decode targets of jda_batch_create / jda_decode_to_host
+     * (jda_output_geometry refuses them); made from a GRAY8 canvas by jda_dither_surfaces / jda_decode_dither_to_host */
+    JDA_FOUR_BIT_DITHERED = 4,
+    JDA_TWO_BIT_DITHERED = 5,
+    JDA_ONE_BIT_DITHERED = 6
 };
 
 /* decode options: the reference's bits (src/JPEGDEC.h:68-75) */
@@ -303,6 +308,30 @@ int jda_sync(jda_ctx *ctx);
  * a row's tail bytes zero-extended.  Lets a multi-GPU driver prove "every image decoded exactly once, identically" without moving
  * pixels (the reference has no such notion: its pixels go to a display as they are made).  Synchronous. */
 int jda_checksum_surfaces(jda_ctx *ctx, int32_t n, const jda_output *surfaces, const int32_t *row_bytes, uint64_t *checksums);
+/* ---- 4 / 2 / 1-bpp Floyd-Steinberg output (the reference's decodeDither: JPEGDither, jpeg.inl:4871-4940, run after every MCU row, :5309-5311)
+ * The packed form of a GRAY8 canvas of canvas_w x canvas_h pixels (the canvas of jda_output_geometry for JDA_EIGHT_BIT_GRAYSCALE): rows of
+ * *pitch_bytes = (canvas_w * bits + 7) / 8 bytes, most significant bits first, every padded column and row included; *bits = 4 / 2 / 1;
+ * *bytes = pitch * canvas_h.  JDA_INVALID_PARAMETER for any other pixel type or an empty canvas. */
+int jda_dither_geometry(int32_t canvas_w, int32_t canvas_h, int32_t pixel_type, int32_t *bits, int32_t *pitch_bytes, int64_t *bytes);
+/* Dither n GRAY8 canvases resident in HBM in ONE launch on the context's stream (behind whatever decodes them there); synchronous.
+ * gray[i]: pixels (16-byte aligned), pitch_bytes (a multiple of 16), width_px x rows = the canvas.  strip_rows[i]: the rows the reference
+ * dithers at a time = the height of an MCU row in output pixels (16, 8, 4, 2 or 1): the image is ONE error chain, but the first row of
+ * every strip starts with the error under its pixel 1 cleared (jpeg.inl:4882) -- the bytes depend on it; seeds: below.  packed[i]: pixels (4-byte
+ * aligned), pitch_bytes (a multiple of 4, >= the pitch of jda_dither_geometry), rows >= gray[i].rows; width_px is not read.  The gray
+ * canvases are left as they are.  Where canvas_w * bits is not a whole number of bytes, a row's last byte is what the reference's in-place
+ * packing leaves there: the gray byte at offset y * pitch + pitch - 1 of the strip (y: the row within it).  The reference's own error
+ * row holds 4,096 pixels; wider canvases are dithered by the same rule (it has no defined behaviour there). */
+int jda_dither_surfaces(jda_ctx *ctx, int32_t n, const jda_output *gray, const int32_t *strip_rows, const int32_t *pixel_types,
+                        const uint8_t *const *seeds, const jda_output *packed);
+/* What the chain starts from.  The reference's error row is NOT clear before the first strip: it lies in the buffer (usPixels) in which the
+ * header parse keeps the file's raw DHT contents -- table id t (DC 0-3, AC 4-7) at byte 273 t: 16 code counts, then the symbols
+ * (jpeg.inl:837-873, :4881) -- so error byte i of the first row is byte i of that area (bytes 0-2 are cleared, :4882).  jda_dither_seed lays
+ * a file's DHT segments out that way: seed[JDA_DITHER_SEED_BYTES]; overlay = 0 starts from zeros (an opened file), overlay = 1 writes over
+ * what seed holds (the reference parses an EXIF thumbnail's header over the main image's).  seeds (HOST pointers; the array or an entry
+ * may be NULL: zeros) gives jda_dither_surfaces one per canvas. */
+#define JDA_DITHER_SEED_BYTES 2184
+int jda_dither_seed(const uint8_t *jpeg, int32_t len, int32_t overlay, uint8_t *seed);
+
 /* PCI bus id ("0000:8e:00.0") of the context's GPU, for NUMA placement of the host threads that feed it; buf >= 16 bytes */
 int jda_device_pci_bus_id(jda_ctx *ctx, char *buf, int32_t len);
 int jda_device_pci_bus_id_of(int32_t device, char *buf, int32_t len);      /* the same by device ordinal, without a context */
@@ -322,6 +351,13 @@ int jda_decode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t p
  * canvas holds the MCUs before it, zeros behind). */
 int jda_decode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type,
                           int32_t options, void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded);
+/* jda_decode_to_host_ex for pixel_type JDA_FOUR_BIT_DITHERED / JDA_TWO_BIT_DITHERED / JDA_ONE_BIT_DITHERED: the image is decoded to GRAY8 (luma
+ * only) on the device, dithered there MCU row by MCU row as the reference does (jda_dither_surfaces, strip_rows = an MCU row's height) and
+ * only the packed rows come back: row r of the canvas at host_packed + r * pitch_bytes, pitch_bytes >= the pitch of jda_dither_geometry.
+ * Pre-scan, host fallback, status and *mcus_decoded as jda_decode_to_host_ex for JDA_EIGHT_BIT_GRAYSCALE (JDA_DECODE_ERROR: the MCUs from
+ * the bad one on are dithered as zeros).  seed: JDA_DITHER_SEED_BYTES the chain starts from, or NULL: jda_dither_seed of the file. */
+int jda_decode_dither_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options,
+                              const uint8_t *seed, void *host_packed, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded);
 /* The same, decoding only the MCUs of mcu_rect = {mx0, my0, mx1, my1} (half open; NULL: everything): the canvas keeps its
  * geometry, the rows of the rectangle are written (zeros left and right of it), the others are not touched.  tiles (may be NULL):
  * [0] wavefront tiles launched, [1] tiles of the whole image. */

@@ -6,6 +6,8 @@ import numpy as np
 
 # constants = include/jpegdec_amd.h (= the reference's src/JPEGDEC.h values)
 RGB565_LE, RGB565_BE, RGB8888, GRAY8 = 0, 1, 2, 3
+FOUR_BIT_DITHERED, TWO_BIT_DITHERED, ONE_BIT_DITHERED = 4, 5, 6      # made from a GRAY8 canvas: dither_surfaces / decode_dither_to_host
+DITHER_SEED_BYTES = 2184
 SCALE_HALF, SCALE_QUARTER, SCALE_EIGHTH, LUMA_ONLY = 2, 4, 8, 64
 
 ERROR_NAMES = {0: "JDA_SUCCESS", 1: "JDA_INVALID_PARAMETER", 2: "JDA_DECODE_ERROR",
@@ -117,6 +119,10 @@ _PROTOTYPES = [
     ("jda_pipeline_wait", C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32)]),
     ("jda_pipeline_get_stats", C.c_int, [_P, C.POINTER(PipelineStats)]),
     ("jda_pipeline_read_index", C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_uint32)]),
+    ("jda_dither_geometry", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    ("jda_dither_seed", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _P]),
+    ("jda_dither_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(Output)]),
+    ("jda_decode_dither_to_host", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     ("jda_checksum_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("jda_device_pci_bus_id", C.c_int, [_P, C.c_char_p, C.c_int32]),
     ("jda_upload_batch_ex", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32)]),
@@ -321,6 +327,10 @@ class Context:
         res = (C.c_uint64 * n)()
         self.check(self.lib.jda_checksum_surfaces(self.handle, n, outs, rb, res), "jda_checksum_surfaces")
         return [int(v) for v in res]
+
+    def from_host(self, ptr, data):
+        a = np.ascontiguousarray(data, dtype=np.uint8)
+        self.check(self.lib.jda_copy_to_device(self.handle, ptr, a.ctypes.data_as(_P), a.size), "jda_copy_to_device")
 
     def pci_bus_id(self) -> str:
         buf = C.create_string_buffer(32)
@@ -607,6 +617,52 @@ def decode_to_host(ctx: Context, jpeg: bytes, pixel_type=RGB8888, options=0, out
     rc = ctx.lib.jda_decode_to_host(ctx.handle, jpeg, len(jpeg), pixel_type, options,
                                     canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0])
     return rc, canvas, g
+
+
+def dither_geometry(canvas_w, canvas_h, pixel_type):
+    """jda_dither_geometry: {"bits", "pitch", "bytes"} of the packed form of a GRAY8 canvas."""
+    bits, pitch, nbytes = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    rc = load_library().jda_dither_geometry(canvas_w, canvas_h, pixel_type, C.byref(bits), C.byref(pitch), C.byref(nbytes))
+    if rc != 0:
+        raise JdaError(rc, "jda_dither_geometry")
+    return {"bits": bits.value, "pitch": pitch.value, "bytes": nbytes.value}
+
+
+def dither_seed(jpeg: bytes, base=None) -> np.ndarray:
+    """jda_dither_seed: what the error row holds before the first strip of this file (base: a main image's seed to write over)."""
+    seed = np.zeros(DITHER_SEED_BYTES, np.uint8) if base is None else np.array(base, dtype=np.uint8, copy=True)
+    rc = load_library().jda_dither_seed(jpeg, len(jpeg), 0 if base is None else 1, seed.ctypes.data_as(_P))
+    if rc != 0:
+        raise JdaError(rc, "jda_dither_seed")
+    return seed
+
+
+def dither_surfaces(ctx: Context, gray, strip_rows, pixel_types, packed, seeds=None):
+    """jda_dither_surfaces: gray / packed = lists of (device_ptr, pitch_bytes, width_px, rows); one launch for all of them.
+    seeds: None, or one uint8 array of DITHER_SEED_BYTES (or None) per canvas."""
+    n = len(gray)
+    g = (Output * n)(*[Output(*o) for o in gray])
+    p = (Output * n)(*[Output(*o) for o in packed])
+    keep = [None if (seeds is None or s is None) else np.ascontiguousarray(s, dtype=np.uint8) for s in (seeds or [None] * n)]
+    sp = (_P * n)(*[None if s is None else s.ctypes.data for s in keep])
+    ctx.check(ctx.lib.jda_dither_surfaces(ctx.handle, n, g, (C.c_int32 * n)(*strip_rows), (C.c_int32 * n)(*pixel_types), sp, p), "jda_dither_surfaces")
+
+
+def decode_dither_to_host(ctx: Context, jpeg: bytes, pixel_type=ONE_BIT_DITHERED, options=0, seed=None):
+    """jda_decode_dither_to_host: (rc, packed rows (canvas_h x pitch), geometry of the gray canvas + "bits", "pitch", "strip_rows")."""
+    info = ImageInfo()
+    rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
+    if rc != 0:
+        raise JdaError(rc, "jda_parse")
+    g = output_geometry(info, GRAY8, options)
+    d = dither_geometry(g["canvas_w"], g["canvas_h"], pixel_type)
+    g.update(bits=d["bits"], pitch=d["pitch"], strip_rows=g["canvas_h"] // info.mcus_y)
+    packed = np.zeros((g["canvas_h"], d["pitch"]), dtype=np.uint8)
+    sd = None if seed is None else np.ascontiguousarray(seed, dtype=np.uint8)
+    nok = C.c_int32(0)
+    rc = ctx.lib.jda_decode_dither_to_host(ctx.handle, jpeg, len(jpeg), pixel_type, options, None if sd is None else sd.ctypes.data_as(_P),
+                                           packed.ctypes.data_as(_P), d["pitch"], g["canvas_h"], C.byref(nok))
+    return rc, packed, g
 
 
 def decode_resident(ctx: Context, prepared: PreparedImage, pixel_type=RGB8888, options=0):

@@ -259,8 +259,89 @@ void JPEGDEC::getCropArea(int *x, int *y, int *w, int *h)
     *x = _jpeg->crop_x; *y = _jpeg->crop_y; *w = _jpeg->crop_w; *h = _jpeg->crop_h;
 }
 
-int JPEGDEC::decodeDither(uint8_t *, int) { _jpeg->error = JPEG_UNSUPPORTED_FEATURE; return 0; }   // JPEGDither is off this path
-int JPEGDEC::decodeDither(int, int, uint8_t *, int) { _jpeg->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
+// decode(JPEG_EXIF_THUMBNAIL): the JPEG embedded in the EXIF block takes the object over (jpeg.inl:4967-4976); false: s->error is set
+static bool enter_exif_thumbnail(jpegdec_amd_state *s, int &iOptions)
+{
+    if (s->info.thumb_offset == 0 || s->info.thumb_w == 0) { s->error = JPEG_INVALID_PARAMETER; return false; }
+    if (s->info.thumb_offset < 0 || s->info.thumb_offset > s->size - 256) { s->error = JPEG_INVALID_FILE; return false; }   // (JPEGParseInfo wants 256 bytes, :1598)
+    // jpeg.inl:4964-4966 runs BEFORE the thumbnail is parsed: it is the MAIN image's mode that ORs JPEG_SCALE_EIGHTH in
+    if (s->info.jpeg_type == 1) iOptions |= JPEG_SCALE_EIGHTH;
+    jda_image_info ti;
+    const int prc = jda_parse(s->data + s->info.thumb_offset, s->size - s->info.thumb_offset, &ti);   // JPEGParseInfo(pJPEG, 1)
+    if (prc != JDA_SUCCESS) { s->error = prc; return false; }
+    // a progressive thumbnail inside a baseline file would go through the reference's DC-only decode at whatever scale was
+    // asked for (no EIGHTH OR-ed in): not a case this path reproduces
+    if (ti.jpeg_type == 1 && s->info.jpeg_type == 0 && !(iOptions & (JPEG_SCALE_HALF | JPEG_SCALE_EIGHTH))) { s->error = JPEG_UNSUPPORTED_FEATURE; return false; }
+    // the reference parses the thumbnail over its own state: the object now describes the thumbnail
+    ti.has_thumb = s->info.has_thumb; ti.thumb_w = s->info.thumb_w; ti.thumb_h = s->info.thumb_h; ti.thumb_offset = 0;
+    if (!ti.orientation) ti.orientation = s->info.orientation;       // (ucOrientation is only written when an orientation tag is met: the main image's stays)
+    s->data += s->info.thumb_offset; s->size -= s->info.thumb_offset;
+    s->info = ti;
+    s->crop_x = s->crop_y = 0; s->crop_w = ti.width; s->crop_h = ti.height;      // the SOF handler resets the whole crop rectangle (jpeg.inl:1683-1685)
+    iOptions &= ~JPEG_EXIF_THUMBNAIL;
+    return true;
+}
+
+// decodeDither (src/JPEGDEC.cpp:259-273): the image is decoded as EIGHT_BIT_GRAYSCALE and error-diffused to 4 / 2 / 1 bits per pixel on the
+// GPU (jda_decode_dither_to_host); then, MCU row by MCU row, the packed strip goes to the front of the caller's buffer -- where the reference's
+// in-place JPEGDither leaves it -- and ONE draw callback is made for it (jpeg.inl:5077-5079, 5094-5105, 5307-5325).  The bytes of pDither behind
+// the packed strip are not written (the reference leaves stale gray there).  Refused: a null buffer or a pixel type that is not a dithered one
+// (JPEG_INVALID_PARAMETER); a framebuffer (the reference never dithers into one, :5300), a crop rectangle and JPEG_USES_DMA
+// (JPEG_UNSUPPORTED_FEATURE).  A second decodeDither on an open object starts from the same error row as the first (the reference goes on
+// from what the first one left in it).
+static int decode_dither(jpegdec_amd_state *s, uint8_t *pDither, int iOptions)
+{
+    s->options = iOptions;
+    if (!s->opened || !pDither || s->pixel_type < FOUR_BIT_DITHERED || s->pixel_type > ONE_BIT_DITHERED) { s->error = JPEG_INVALID_PARAMETER; return 0; }
+    if (s->framebuffer) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
+    // JPEG_USES_DMA: the reference's strip buffer alternates between two halves after every draw (jpeg.inl:5073-5075, :5131, :5326) and its
+    // error row lies in that buffer (:4881): alternate strips run on two error rows, which overlap above 2,046 pixels.  Not reproduced.
+    if (iOptions & JPEG_USES_DMA) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
+    // what the reference's error row holds before the first strip: the raw DHT contents its header parse left there (jda_dither_seed) --
+    // the main image's, and over them the thumbnail's when that is what is decoded
+    uint8_t seed[JDA_DITHER_SEED_BYTES];
+    (void)jda_dither_seed(s->data, s->size, 0, seed);
+    if (iOptions & JPEG_EXIF_THUMBNAIL) {
+        if (!enter_exif_thumbnail(s, iOptions)) return 0;
+        (void)jda_dither_seed(s->data, s->size, 1, seed);
+    }
+    if (s->crop_x != 0 || s->crop_y != 0 || s->crop_w != s->info.width || s->crop_h != s->info.height) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
+    int bpp, ow, oh, cw, ch;
+    int rc = jda_output_geometry(&s->info, EIGHT_BIT_GRAYSCALE, iOptions, &bpp, &ow, &oh, &cw, &ch);
+    if (rc != JDA_SUCCESS) { s->error = s->info.mcu_w ? rc : JPEG_UNSUPPORTED_FEATURE; return 0; }
+    int32_t bits = 0, pitch = 0;
+    int64_t bytes = 0;
+    rc = jda_dither_geometry(cw, ch, s->pixel_type, &bits, &pitch, &bytes);
+    if (rc != JDA_SUCCESS || s->info.mcus_y <= 0) { s->error = rc != JDA_SUCCESS ? rc : JPEG_INVALID_PARAMETER; return 0; }
+    int cerr = JDA_SUCCESS;
+    jda_ctx *ctx = thread_ctx(s->device, &cerr);
+    if (!ctx) { s->error = cerr; return 0; }
+    if (s->canvas.size() < (size_t)bytes) s->canvas.resize((size_t)bytes);
+    int32_t mcus_decoded = 0;
+    rc = jda_decode_dither_to_host(ctx, s->data, s->size, s->pixel_type, iOptions, seed, s->canvas.data(), pitch, ch, &mcus_decoded);
+    const bool partial = rc == JDA_DECODE_ERROR;              // the reference still delivers the MCU rows in front of the bad MCU
+    if (rc != JDA_SUCCESS && !partial) { s->error = rc; return 0; }
+    const int mh = ch / s->info.mcus_y;
+    JPEGDRAW jd;
+    jd.iHeight = mh;                                          // set once (jpeg.inl:5108), trimmed on the last row (:5318-5320)
+    for (int my = 0; my < s->info.mcus_y && s->draw; my++) {
+        if (partial && (my + 1) * s->info.mcus_x > mcus_decoded) break;
+        memcpy(pDither, s->canvas.data() + (size_t)my * mh * pitch, (size_t)mh * pitch);
+        jd.x = s->xoff; jd.y = s->yoff + my * mh;
+        jd.iWidth = cw; jd.iWidthUsed = cw > ow ? ow : cw;
+        if (my * mh + mh > oh) jd.iHeight = oh - my * mh;
+        jd.iBpp = bits; jd.pPixels = (uint16_t *)pDither; jd.pUser = s->user;
+        if (!(*s->draw)(&jd)) break;                          // jpeg.inl:5325, :5109
+    }
+    if (partial) { s->error = JPEG_DECODE_ERROR; return 0; }
+    return 1;
+}
+int JPEGDEC::decodeDither(uint8_t *pDither, int iOptions) { return decode_dither(_jpeg, pDither, iOptions); }      // (the offsets stay what they were, src/JPEGDEC.cpp:268-273)
+int JPEGDEC::decodeDither(int x, int y, uint8_t *pDither, int iOptions)
+{
+    _jpeg->xoff = x; _jpeg->yoff = y;
+    return decode_dither(_jpeg, pDither, iOptions);
+}
 
 int JPEGDEC::decode(int x, int y, int iOptions)
 {
@@ -268,25 +349,7 @@ int JPEGDEC::decode(int x, int y, int iOptions)
     s->xoff = x; s->yoff = y; s->options = iOptions;
     if (!s->opened) { s->error = JPEG_INVALID_PARAMETER; return 0; }
     if (s->pixel_type > EIGHT_BIT_GRAYSCALE) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
-    if (iOptions & JPEG_EXIF_THUMBNAIL) {              // jpeg.inl:4967-4976: decode the JPEG embedded in the EXIF block instead
-        if (s->info.thumb_offset == 0 || s->info.thumb_w == 0) { s->error = JPEG_INVALID_PARAMETER; return 0; }
-        if (s->info.thumb_offset < 0 || s->info.thumb_offset > s->size - 256) { s->error = JPEG_INVALID_FILE; return 0; }   // (JPEGParseInfo wants 256 bytes, :1598)
-        // jpeg.inl:4964-4966 runs BEFORE the thumbnail is parsed: it is the MAIN image's mode that ORs JPEG_SCALE_EIGHTH in
-        if (s->info.jpeg_type == 1) iOptions |= JPEG_SCALE_EIGHTH;
-        jda_image_info ti;
-        const int prc = jda_parse(s->data + s->info.thumb_offset, s->size - s->info.thumb_offset, &ti);   // JPEGParseInfo(pJPEG, 1)
-        if (prc != JDA_SUCCESS) { s->error = prc; return 0; }
-        // a progressive thumbnail inside a baseline file would go through the reference's DC-only decode at whatever scale was
-        // asked for (no EIGHTH OR-ed in): not a case this path reproduces
-        if (ti.jpeg_type == 1 && s->info.jpeg_type == 0 && !(iOptions & (JPEG_SCALE_HALF | JPEG_SCALE_EIGHTH))) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
-        // the reference parses the thumbnail over its own state: the object now describes the thumbnail
-        ti.has_thumb = s->info.has_thumb; ti.thumb_w = s->info.thumb_w; ti.thumb_h = s->info.thumb_h; ti.thumb_offset = 0;
-        if (!ti.orientation) ti.orientation = s->info.orientation;       // (ucOrientation is only written when an orientation tag is met: the main image's stays)
-        s->data += s->info.thumb_offset; s->size -= s->info.thumb_offset;
-        s->info = ti;
-        s->crop_x = s->crop_y = 0; s->crop_w = ti.width; s->crop_h = ti.height;      // the SOF handler resets the whole crop rectangle (jpeg.inl:1683-1685)
-        iOptions &= ~JPEG_EXIF_THUMBNAIL;
-    }
+    if ((iOptions & JPEG_EXIF_THUMBNAIL) && !enter_exif_thumbnail(s, iOptions)) return 0;   // jpeg.inl:4967-4976: decode the JPEG embedded in the EXIF block instead
     if (s->crop_w <= 0 || s->crop_h <= 0) { s->error = JPEG_INVALID_PARAMETER; return 0; }   // image smaller than one MCU / overhanging request (jpeg.inl:713-719 leaves w <= 0): nothing sane to deliver
     const bool cropped = s->crop_x != 0 || s->crop_y != 0 || s->crop_w != s->info.width || s->crop_h != s->info.height;
     int pt = s->pixel_type;

@@ -3149,4 +3149,78 @@ JDA_HD void jda_q4_store(const jda_dev_desc &D, const jda_strip &S, uint32_t cou
     }
 }
 
+// ---- 4 / 2 / 1-bpp error diffusion (JPEGDither, jpeg.inl:4871-4940) ---------------------------------------------------------------
+// The reference keeps ONE byte row E[0 .. W + 1] for the whole image: pixel x of a row adds its forward error, clips at 255, keeps the
+// top `bits` bits, halves the residue (h) and spreads it as e1 = 7h >> 3 (to pixel x + 1 of the row), e2 = h - e1 (E[x + 2] is SET to
+// it), e3 = 5h >> 3 (added to E[x + 1]), e4 = h - e3 (added to E[x]); the next row's pixel p >= 1 starts from e1 of its left
+// neighbour plus E[p + 1].  Followed through one row that byte is
+//     down(p) = e2(p - 1) + e3(p) + e4(p + 1)          (terms of pixels outside the row drop out; <= 8 + 39 + 24, so the byte never wraps)
+// -- a pure function of the row above, which pixel 0 never reads (its forward error is zero and E[1] is write-only).  The first row of
+// a strip reads down(1) as zero (E[0..2] are cleared there and nowhere else), every other byte carries over: the image is one chain.
+// A row can therefore run two pixels behind the row above it, the value handed down in a register: lanes = rows.
+struct jda_dither_lane {
+    uint32_t fwd;       // e1 of the pixel before
+    uint32_t a, b;      // a = e2(q - 2) + e3(q - 1), b = e2(q - 1): the parts of down(q - 1), down(q) this row's pixels < q have made
+};
+JDA_HD uint32_t jda_dither_bits(int32_t pixel_type)
+{
+    return pixel_type == JDA_FOUR_BIT_DITHERED ? 4u : pixel_type == JDA_TWO_BIT_DITHERED ? 2u : pixel_type == JDA_ONE_BIT_DITHERED ? 1u : 0u;
+}
+JDA_HD uint32_t jda_dither_pitch(uint32_t width, uint32_t bits) { return (width * bits + 7u) >> 3; }      // (W + 1) / 2, (W + 3) / 4, (W + 7) / 8
+// One step of a row: pixel q (live: q lies inside the row and the row inside the image; otherwise the lane only moves its sums along, so
+// that the step after the row's last pixel hands down(W - 1) on).  `down`: what the row above handed down for pixel q (the caller passes
+// zero for q == 1 of a strip's first row and for the image's first row).  Returns down(q - 1) for the row below; px = the pixel's bits.
+JDA_HD uint32_t jda_dither_step(jda_dither_lane &L, bool live, int32_t q, uint32_t gray, uint32_t down, uint32_t bits, uint32_t &px)
+{
+    uint32_t e1 = 0, e2 = 0, e3 = 0, e4 = 0;
+    px = 0;
+    if (live) {
+        uint32_t c = gray + (q > 0 ? L.fwd + down : 0u);
+        if (c > 255u) c = 255u;                              // (the only clip: the sum is never negative)
+        px = c >> (8u - bits);
+        const uint32_t h = (c & (0xffu >> bits)) >> 1;
+        e1 = (7u * h) >> 3; e2 = h - e1; e3 = (5u * h) >> 3; e4 = h - e3;
+    }
+    const uint32_t out = L.a + e4;
+    L.a = L.b + e3; L.b = e2; L.fwd = e1;
+    return out;
+}
+// The byte of a row whose width is not a whole number of bytes: the reference packs in place and never stores the unfinished byte, so
+// byte (pitch - 1) of packed row y of a strip still holds the strip's gray byte at linear offset y * pitch + pitch - 1 (row pitch W).
+// Returns that offset's (row in the strip, column).
+JDA_HD void jda_dither_stale_src(uint32_t y_in_strip, uint32_t width, uint32_t pitch, uint32_t &src_row, uint32_t &src_col)
+{
+    const uint32_t o = y_in_strip * pitch + pitch - 1u;
+    src_row = o / width; src_col = o - src_row * width;
+}
+// A lane's gray bytes.  Every lane of a wavefront loads at the SAME steps -- t % 16 == 0 -- so that the wavefront waits for memory once
+// per 16 steps, for loads issued 16 steps before (a lane that loaded when ITS pixel index reached a multiple of 16 made the whole
+// wavefront wait for a load issued a step ago on every other step).  At such a step lane r stands at pixel x0 = t - 2 r = 16 m - s with
+// s = (2 r) & 15 and m = t / 16 - (r >> 3): its next 16 pixels are the last s bytes of the aligned 16-byte chunk m - 1 and the first
+// 16 - s of chunk m.  It keeps p = chunk m - 1, q = chunk m and n = chunk m + 1 (on its way), and cuts its window w out of p:q at
+// the byte offset 16 - s, which never changes.
+struct jda_dither_feed { uint32_t p[4], q[4], n[4], w[4]; };
+JDA_HD void jda_dither_feed_turn(jda_dither_feed &F, uint32_t s)
+{
+    uint32_t e[9];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { F.p[j] = F.q[j]; F.q[j] = F.n[j]; e[j] = F.p[j]; e[4 + j] = F.q[j]; }
+    e[8] = 0;
+    const uint32_t o = 16u - s, d0 = o >> 2, sh = (o & 3u) * 8u;      // (s is even: sh is 0 or 16)
+    uint32_t a[5];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        uint32_t v = e[j];
+#pragma unroll
+        for (int k = 1; k < 5; k++) v = d0 == (uint32_t)k ? e[j + k < 8 ? j + k : 8] : v;
+        a[j] = v;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) F.w[j] = sh ? (a[j] >> sh) | (a[j + 1] << (32u - sh)) : a[j];
+}
+#define JDA_DITHER_MAX_WAVES 8
+#define JDA_DITHER_LAG 2                     // pixels a row runs behind the row above
+#define JDA_DITHER_PUBLISH 32                // the last row of a 64-row group tells the next group every so many pixels
+#define JDA_DITHER_LDS_HEAD 64               // bytes in front of the hand-over rows: one progress counter per wavefront
+
 #endif // JDA_DEVICE_CORE_H

@@ -181,4 +181,13 @@ struct jda_front {
     uint32_t rec_cap;            // jda_record_cap of the image's tables
 };
 
+// One image of a dither launch (device pointers): gray = canvas_w x canvas_h bytes at gray_pitch (16-byte aligned rows), out = packed
+// rows at out_pitch (a multiple of 4, >= jda_dither_pitch)
+struct jda_dither_job {
+    const uint8_t *gray;
+    uint8_t *out;
+    const uint8_t *seed;   // JDA_DITHER_SEED_BYTES the error row starts from (device), or NULL: zeros
+    uint32_t gray_pitch, out_pitch, width, height, strip_rows, bits;
+};
+
 #endif

@@ -1682,6 +1682,150 @@ extern "C" hipError_t jda_launch_checksum(const void *base, uint32_t pitch, uint
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// jda_dither_rows: GRAY8 canvases -> 4 / 2 / 1 bits per pixel, error-diffused exactly as the reference's JPEGDither (the recurrence and
+// why a row may run two pixels behind the row above: jda_dither_step in jda_device_core.h).
+//   workgroup = image.  Wavefront w of its WAVES takes the 64-row groups w, w + WAVES, ..; lane r owns row 64 g + r and, at step t,
+//   pixel t - 2 r.  What a row hands down crosses to the next lane by DPP (wave_shr:1), the forward error stays in a register.  The
+//   last lane's values go into the wavefront's hand-over row in LDS, and a counter beside it says how many are there; the wavefront
+//   with the next group reads them as its lane 0 goes along, looking at the counter every JDA_DITHER_PUBLISH pixels -- the wavefronts
+//   chase each other through the image about 170 steps apart (126 for the skew of 64 lanes, 40 of look-ahead).  (A hand-over row is written again WAVES groups later; by then its reader is
+//   long past: every later group waits, link by link, on that reader's own last lane.)  No workgroup barrier after the first.
+//   Gray bytes come 16 at a time per lane, every lane loading at the same steps and a load ahead (jda_dither_feed); packed bits leave as
+//   whole big-endian dwords, also at wave-uniform steps, a row's tail as bytes.
+// The first row of an image starts from the job's seed (what the reference's error row holds then: jda_dither_seed).
+// A wait that does not end (it cannot, unless the launch is wrong) gives up after 2^22 looks and raises *fail: the runtime reports it.
+__global__ __launch_bounds__(64 * JDA_DITHER_MAX_WAVES)
+void jda_dither_rows(const jda_dither_job *__restrict__ jobs, uint32_t wpad, uint32_t *fail)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t dither_lds[];
+    uint32_t *prog = (uint32_t *)dither_lds;
+    const uint32_t lane = threadIdx.x & 63u, wave = jda_uni32(threadIdx.x >> 6), waves = jda_uni32(blockDim.x >> 6);
+    const jda_dither_job *job = jobs + blockIdx.x;
+    const uint8_t JDA_GLOBAL *gray = JDA_G(const uint8_t, jda_uni_ptr(job->gray));
+    uint8_t JDA_GLOBAL *out = JDA_G(uint8_t, jda_uni_ptr(job->out));
+    const uint8_t *seed = jda_uni_ptr(job->seed);
+    const uint32_t gpitch = jda_uni32(job->gray_pitch), opitch = jda_uni32(job->out_pitch), W = jda_uni32(job->width), H = jda_uni32(job->height);
+    const uint32_t strip = jda_uni32(job->strip_rows), bits = jda_uni32(job->bits);
+    if (threadIdx.x < JDA_DITHER_LDS_HEAD / 4) prog[threadIdx.x] = 0;
+    __syncthreads();
+    if (W == 0 || H == 0 || bits == 0 || strip == 0 || W > wpad) return;          // (the launch validates; nothing waits on a wavefront that leaves)
+    uint8_t *hand_mine = dither_lds + JDA_DITHER_LDS_HEAD + (size_t)wave * wpad;
+    const uint32_t prod = (wave + waves - 1u) % waves;
+    const uint8_t *hand_prod = dither_lds + JDA_DITHER_LDS_HEAD + (size_t)prod * wpad;
+    const uint32_t dpitch = jda_dither_pitch(W, bits), tail_bits = (W * bits) & 31u;
+    const uint32_t ppd_log2 = bits == 4u ? 3u : bits == 2u ? 4u : 5u, ppd_mask = (1u << ppd_log2) - 1u;      // pixels per dword: 8, 16, 32
+    bool gave_up = false;
+    for (uint32_t it = 0;; it++) {
+        const uint32_t g = it * waves + wave, row0 = g * 64u;
+        if (row0 >= H) break;
+        const uint32_t row = row0 + lane;
+        const bool row_ok = row < H, has_prod = g > 0;
+        const uint32_t prod_base = (wave == 0 ? it - 1u : it) * W, my_base = it * W;
+        const bool strip_first = row % strip == 0;
+        const uint8_t JDA_GLOBAL *grow = gray + (size_t)(row_ok ? row : 0u) * gpitch;
+        uint8_t JDA_GLOBAL *orow = out + (size_t)(row_ok ? row : 0u) * opitch;
+        jda_dither_lane L;
+        L.fwd = L.a = L.b = 0;
+        uint32_t handed = 0, acc = 0, curw = 0, hw = 0, hn = 0, pend_word = 0, pend_at = 0;
+        bool pend = false;
+        jda_dither_feed F;
+#pragma unroll
+        for (int j = 0; j < 4; j++) F.p[j] = F.q[j] = F.n[j] = F.w[j] = 0;
+        const uint32_t phase = (JDA_DITHER_LAG * lane) & 15u;
+        const int32_t chunk0 = -(int32_t)((JDA_DITHER_LAG * lane) >> 4);      // m at step 0
+        if (row_ok && chunk0 == 0) { const uint4 v = *(const uint4 JDA_GLOBAL *)grow; F.n[0] = v.x; F.n[1] = v.y; F.n[2] = v.z; F.n[3] = v.w; }
+        const uint32_t steps = W + 2u * 63u + 1u;
+        for (uint32_t t = 0; t < steps; t++) {
+            const int32_t x = (int32_t)t - (int32_t)(JDA_DITHER_LAG * lane);
+            if (has_prod && !gave_up && (t % JDA_DITHER_PUBLISH) == 0 && t < W) {
+                const uint32_t need = prod_base + (t + JDA_DITHER_PUBLISH + 8u < W ? t + JDA_DITHER_PUBLISH + 8u : W);   // (+ 8: lane 0 reads ahead)
+                uint32_t looks = 0;
+                while (__hip_atomic_load(&prog[prod], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need) {
+                    __builtin_amdgcn_s_sleep(1);
+                    if (++looks > (1u << 22)) { gave_up = true; if (lane == 0) atomicOr(fail, 1u); break; }
+                }
+            }
+            const bool in_row = x >= 0 && (uint32_t)x < W, live = row_ok && in_row;
+            // memory traffic at wave-uniform steps only: the finished dword of the last 8 steps leaves, the chunk asked for 16 steps ago is
+            // taken and the one after it asked for (jda_dither_feed)
+            if ((t & 7u) == 0) {
+                if ((t & 15u) == 0) {
+                    jda_dither_feed_turn(F, phase);
+                    const int32_t c = chunk0 + (int32_t)(t >> 4) + 1;
+#pragma unroll
+                    for (int j = 0; j < 4; j++) F.n[j] = 0;
+                    if (row_ok && c >= 0 && (uint32_t)c * 16u < W) { const uint4 v = *(const uint4 JDA_GLOBAL *)(grow + (size_t)c * 16u); F.n[0] = v.x; F.n[1] = v.y; F.n[2] = v.z; F.n[3] = v.w; }
+                }
+                if (pend) { *(jda_u32_alias JDA_GLOBAL *)(orow + pend_at) = pend_word; pend = false; }
+            }
+            if ((t & 3u) == 0) { curw = F.w[0]; F.w[0] = F.w[1]; F.w[1] = F.w[2]; F.w[2] = F.w[3]; }
+            const uint32_t gpx = curw & 0xffu;
+            curw >>= 8;
+            // what the row above handed down for this pixel: the lane above made it in the step before; lane 0 takes the group above's
+            uint32_t down = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)handed, 0x138, 0xf, 0xf, false);
+            if (lane == 0) {
+                down = 0;
+                if (!has_prod && seed && in_row && (uint32_t)x + 1u < JDA_DITHER_SEED_BYTES) down = JDA_G(const uint8_t, seed)[x + 1];   // the image's first row
+                if (has_prod && in_row) {                    // four hand-over bytes at a time, one load ahead (the wait above covers them)
+                    if ((x & 3) == 0) {
+                        hw = x == 0 ? *(const jda_u32_alias *)hand_prod : hn;
+                        if ((uint32_t)x + 4u < W) hn = *(const jda_u32_alias *)(hand_prod + x + 4);
+                    }
+                    down = hw & 0xffu;
+                    hw >>= 8;
+                }
+            }
+            if (x == 1 && strip_first) down = 0;
+            uint32_t px;
+            handed = jda_dither_step(L, live, x, gpx, down, bits, px);
+            if (lane == 63u && x >= 1 && (uint32_t)x <= W) {
+                hand_mine[x - 1] = (uint8_t)handed;
+                if (((uint32_t)x % JDA_DITHER_PUBLISH) == 0 || (uint32_t)x == W)
+                    __hip_atomic_store(&prog[wave], my_base + (uint32_t)x, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            if (live) {
+                acc = (acc << bits) | px;
+                const uint32_t done = (uint32_t)x + 1u;
+                if ((done & ppd_mask) == 0) {                       // a whole dword: first pixel in the top bits of the first byte; it leaves at the next uniform step
+                    pend_word = __builtin_bswap32(acc); pend_at = ((done >> ppd_log2) - 1u) * 4u; pend = true;
+                } else if (done == W) {                        // the row's tail: its whole bytes, then the byte the reference never stores
+                    uint8_t JDA_GLOBAL *tp = orow + (size_t)(W >> ppd_log2) * 4u;
+                    const uint32_t whole = tail_bits >> 3;
+                    for (uint32_t k = 0; k < whole; k++) tp[k] = (uint8_t)(acc >> (tail_bits - 8u * (k + 1u)));
+                    if (tail_bits & 7u) {
+                        uint32_t sr, sc;
+                        jda_dither_stale_src(row % strip, W, dpitch, sr, sc);
+                        const uint32_t srow = row - row % strip + sr;
+                        tp[whole] = srow < H ? gray[(size_t)srow * gpitch + sc] : (uint8_t)0;
+                    }
+                }
+            }
+        }
+        if (pend) *(jda_u32_alias JDA_GLOBAL *)(orow + pend_at) = pend_word;      // (a row that ended on a whole dword inside the last 8 steps)
+    }
+}
+// n images, one workgroup each; max_w: the widest canvas of the launch (it sizes the hand-over rows, and with them how many wavefronts
+// share an image: 8 up to 8,176 pixels, 1 from 32,752 on)
+extern "C" hipError_t jda_launch_dither(const jda_dither_job *jobs, uint32_t n, uint32_t max_w, uint32_t max_h, uint32_t *fail, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    const uint32_t wpad = (max_w + 15u) & ~15u;
+    if (wpad == 0 || wpad > 65536u) return hipErrorInvalidValue;
+    uint32_t waves = 65536u / wpad;
+    if (waves > JDA_DITHER_MAX_WAVES) waves = JDA_DITHER_MAX_WAVES;
+    const uint32_t groups = (max_h + 63u) / 64u;
+    if (waves > groups) waves = groups ? groups : 1u;
+    const uint32_t lds = JDA_DITHER_LDS_HEAD + waves * wpad;
+    static std::atomic<unsigned long long> lds_done{0};
+    if (lds > 32u * 1024u) {
+        const hipError_t e = jda_ensure_lds_limit((const void *)jda_dither_rows, 65536 + JDA_DITHER_LDS_HEAD, lds_done);
+        if (e != hipSuccess) return e;
+    }
+    JDA_LAUNCH(jda_dither_rows, dim3(n), dim3(64u * waves), lds, stream, jobs, wpad, fail);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t jda_internal_set_wgtrace(unsigned long long *dev_buf)
 {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_jda_wgtrace), &dev_buf, sizeof(dev_buf));

@@ -1095,4 +1095,159 @@ int jda_decode_to_host_bands(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int
     return rc;
 }
 
+// ---- 4 / 2 / 1-bpp output (jda_dither_rows in jda_kernels.hip)
+static inline uint32_t dither_bits_of(int32_t pt) { return pt == JDA_FOUR_BIT_DITHERED ? 4u : pt == JDA_TWO_BIT_DITHERED ? 2u : pt == JDA_ONE_BIT_DITHERED ? 1u : 0u; }
+// Upload the job records of n canvases (and wait for them: they leave pageable memory that goes away with this frame); *d_block (pool
+// block: jobs, the give-up flag, seeds) is the caller's to release once the stream has drained.  dither_launch then queues the kernel.
+struct dither_plan { void *block; uint32_t *d_fail; uint32_t n, max_w, max_h; };
+static int dither_upload(jda_ctx *ctx, int32_t n, const jda_output *gray, const int32_t *strip_rows, const int32_t *pixel_types, const uint8_t *const *seeds,
+                         const jda_output *packed, dither_plan *plan)
+{
+    plan->block = NULL;
+    std::vector<jda_dither_job> jobs((size_t)n);
+    const size_t jobs_bytes = align16(jobs.size() * sizeof(jda_dither_job)), seed_stride = align16(JDA_DITHER_SEED_BYTES);
+    std::vector<uint8_t> seed_host;
+    for (int i = 0; i < n && seeds; i++) if (seeds[i]) { seed_host.assign((size_t)n * seed_stride, 0); break; }
+    uint32_t max_w = 0, max_h = 0;
+    for (int i = 0; i < n; i++) {
+        const jda_output &G = gray[i], &P = packed[i];
+        const uint32_t bits = dither_bits_of(pixel_types[i]);
+        if (!bits || !G.pixels || !P.pixels || G.width_px <= 0 || G.width_px > 65535 || G.rows <= 0 || strip_rows[i] <= 0) return JDA_INVALID_PARAMETER;
+        if (((uintptr_t)G.pixels & 15u) || (G.pitch_bytes & 15) || G.pitch_bytes < G.width_px) return JDA_INVALID_PARAMETER;
+        const int32_t dp = (int32_t)(((uint32_t)G.width_px * bits + 7u) >> 3);
+        if (((uintptr_t)P.pixels & 3u) || (P.pitch_bytes & 3) || P.pitch_bytes < dp || P.rows < G.rows) return JDA_INVALID_PARAMETER;
+        jda_dither_job &J = jobs[(size_t)i];
+        J.gray = (const uint8_t *)G.pixels; J.out = (uint8_t *)P.pixels;
+        J.gray_pitch = (uint32_t)G.pitch_bytes; J.out_pitch = (uint32_t)P.pitch_bytes;
+        J.width = (uint32_t)G.width_px; J.height = (uint32_t)G.rows; J.strip_rows = (uint32_t)strip_rows[i]; J.bits = bits;
+        max_w = std::max(max_w, J.width); max_h = std::max(max_h, J.height);
+    }
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, jobs_bytes + 16 + seed_host.size());
+    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(dither jobs)");
+    plan->block = blk; plan->d_fail = (uint32_t *)(blk + jobs_bytes); plan->n = (uint32_t)n; plan->max_w = max_w; plan->max_h = max_h;
+    for (int i = 0; i < n; i++) {
+        jobs[(size_t)i].seed = NULL;
+        if (seed_host.empty() || !seeds[i]) continue;
+        memcpy(&seed_host[(size_t)i * seed_stride], seeds[i], JDA_DITHER_SEED_BYTES);
+        jobs[(size_t)i].seed = blk + jobs_bytes + 16 + (size_t)i * seed_stride;
+    }
+    e = hipMemcpyAsync(blk, jobs.data(), jobs.size() * sizeof(jda_dither_job), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && !seed_host.empty()) e = hipMemcpyAsync(blk + jobs_bytes + 16, seed_host.data(), seed_host.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(plan->d_fail, 0, 16, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { jda_pool_free(ctx, blk); plan->block = NULL; return jda_set_err(ctx, e, "dither jobs"); }
+    return JDA_SUCCESS;
+}
+static int dither_launch(jda_ctx *ctx, const dither_plan &plan)
+{
+    const hipError_t e = jda_launch_dither((const jda_dither_job *)plan.block, plan.n, plan.max_w, plan.max_h, plan.d_fail, ctx->stream);
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_dither_rows");
+}
+// page-locked staging of at least `bytes` (the context's grow-only block; whatever used it before has drained: the stream is synchronised first)
+static uint8_t *dither_staging(jda_ctx *ctx, size_t bytes)
+{
+    if (bytes <= ctx->pinned_cap) return ctx->pinned;
+    (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    ctx->pinned = NULL; ctx->pinned_cap = 0;
+    if (hipHostMalloc((void **)&ctx->pinned, bytes, hipHostMallocDefault) != hipSuccess) { ctx->pinned = NULL; return NULL; }
+    ctx->pinned_cap = bytes;
+    return ctx->pinned;
+}
+
+int jda_dither_surfaces(jda_ctx *ctx, int32_t n, const jda_output *gray, const int32_t *strip_rows, const int32_t *pixel_types,
+                        const uint8_t *const *seeds, const jda_output *packed)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n <= 0 || !gray || !strip_rows || !pixel_types || !packed) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    dither_plan plan;
+    uint32_t fail = 0;
+    int rc = dither_upload(ctx, n, gray, strip_rows, pixel_types, seeds, packed, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = dither_launch(ctx, plan);
+    hipError_t e = rc == JDA_SUCCESS ? hipMemcpyAsync(&fail, plan.d_fail, sizeof(fail), hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+    jda_pool_free(ctx, plan.block);
+    if (rc != JDA_SUCCESS) return rc;
+    if (e != hipSuccess) return jda_set_err(ctx, e, "jda_dither_surfaces");
+    if (fail) { snprintf(ctx->last_error, sizeof(ctx->last_error), "jda_dither_rows: a wavefront gave up waiting for the rows above it"); return JDA_ERROR_HIP; }
+    return JDA_SUCCESS;
+}
+
+int jda_decode_dither_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options,
+                              const uint8_t *seed, void *host_packed, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded)
+{
+    uint8_t own_seed[JDA_DITHER_SEED_BYTES];
+    if (!seed && jpeg) { (void)jda_dither_seed(jpeg, len, 0, own_seed); seed = own_seed; }
+    if (mcus_decoded) *mcus_decoded = 0;
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    const uint32_t bits = dither_bits_of(pixel_type);
+    if (!bits || !jpeg || !host_packed) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    int32_t err = JDA_SUCCESS;
+    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
+    if (!img) return err;
+    const jda_image_info I = *jda_image_get_info(img);
+    int bpp, ow, oh, cw, ch;
+    int32_t gray_type = JDA_EIGHT_BIT_GRAYSCALE;
+    int rc = jda_output_geometry(&I, gray_type, options, &bpp, &ow, &oh, &cw, &ch);
+    int32_t dbits = 0, dpitch = 0;
+    int64_t dbytes = 0;
+    if (rc == JDA_SUCCESS) rc = jda_dither_geometry(cw, ch, pixel_type, &dbits, &dpitch, &dbytes);
+    if (rc == JDA_SUCCESS && (pitch_bytes < dpitch || I.mcus_y <= 0 || ch % I.mcus_y)) rc = JDA_INVALID_PARAMETER;
+    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
+    jda_dev_image *dimg = jda_upload(ctx, img, &err);
+    uint32_t nok = 0;
+    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
+    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
+    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
+    jda_image_free(img);
+    if (!dimg) return err;
+    // (the packed surface at the caller's own pitch where the kernel's dword stores allow it: the copy back then lands where it belongs)
+    const int gpitch = (int)align16((size_t)cw), ppitch = (pitch_bytes == dpitch && !(dpitch & 3)) ? dpitch : (int)align16((size_t)dpitch);
+    const size_t gbytes = (size_t)gpitch * ch;
+    uint8_t *dsurf = NULL;                              // the gray canvas, the packed rows behind it
+    if (jda_pool_alloc(ctx, (void **)&dsurf, gbytes + (size_t)ppitch * ch) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
+    jda_output G, P;
+    G.pixels = dsurf; G.pitch_bytes = gpitch; G.width_px = cw; G.rows = ch;
+    P.pixels = dsurf + gbytes; P.pitch_bytes = ppitch; P.width_px = cw; P.rows = ch;
+    jda_batch *b = jda_batch_create(ctx, 1, &dimg, &G, &gray_type, &options, &err);
+    rc = err;
+    if (b) {
+        // everything that has to wait for the host -- the job record, the staging block -- first; then decode, dither and the copy back are
+        // queued back to back
+        dither_plan plan;
+        uint32_t fail = 0;
+        const int32_t strip = ch / I.mcus_y;            // the rows of one MCU row, as scaled (jpeg.inl:5048-5049, :5310)
+        const int drows = rows < ch ? rows : ch;
+        rc = dither_upload(ctx, 1, &G, &strip, &pixel_type, &seed, &P, &plan);
+        // the packed rows come back as ONE copy at the device pitch into page-locked memory and are brought to the caller's pitch here: a
+        // 2-D copy of thousands of rows of an odd width into pageable memory goes row by row (3596 x 2840 at 1 bpp: 450-byte rows, +25 ms)
+        uint8_t *stage = NULL;
+        if (rc == JDA_SUCCESS && drows > 0 && pitch_bytes != ppitch) { stage = dither_staging(ctx, (size_t)ppitch * drows); if (!stage) rc = JDA_ERROR_MEMORY; }
+        if (rc == JDA_SUCCESS && !complete) (void)hipMemsetAsync(dsurf, 0, gbytes, ctx->stream);
+        if (rc == JDA_SUCCESS) rc = jda_batch_decode(ctx, b);
+        if (rc == JDA_SUCCESS) rc = dither_launch(ctx, plan);
+        void *blk = plan.block;
+        if (rc == JDA_SUCCESS) {
+            hipError_t e = hipSuccess;
+            if (drows > 0) e = hipMemcpyAsync(stage ? (void *)stage : host_packed, P.pixels, (size_t)ppitch * drows, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&fail, plan.d_fail, sizeof(fail), hipMemcpyDeviceToHost, ctx->stream);
+            { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+            if (e == hipSuccess && stage)
+                for (int r = 0; r < drows; r++) memcpy((uint8_t *)host_packed + (size_t)r * pitch_bytes, stage + (size_t)r * ppitch, (size_t)dpitch);
+            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+            else if (fail) { snprintf(ctx->last_error, sizeof(ctx->last_error), "jda_dither_rows: a wavefront gave up waiting for the rows above it"); rc = JDA_ERROR_HIP; }
+        } else (void)hipStreamSynchronize(ctx->stream);
+        if (blk) jda_pool_free(ctx, blk);
+        jda_batch_destroy(ctx, b);
+    }
+    jda_pool_free(ctx, dsurf);
+    jda_dev_image_free(ctx, dimg);
+    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
+    return rc;
+}
+
 } // extern "C"
