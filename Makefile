@@ -22,13 +22,17 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so
+hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
 # the dither kernel's lane schedule and its row-major twin on the CPU (tests/test_dither_cpu.py) -- test infrastructure
 tests/hostsim/libjda_dithersim.so: tests/hostsim/dither_sim.cpp tests/hostsim/dither_twin.h $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/dither_sim.cpp $(CSRC)/jda_frontend.cpp
+
+# the orient kernel's tile schedule, lane by lane, and its row-major twin on the CPU (tests/test_orient_cpu.py) -- test infrastructure
+tests/hostsim/libjda_orientsim.so: tests/hostsim/orient_sim.cpp tests/hostsim/orient_twin.h $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/orient_sim.cpp $(CSRC)/jda_frontend.cpp
 
 # the reference-API driver (oracle/ref_shim.cpp) built against the product's JPEGDEC class -- test infrastructure
 classshim: tests/libjpegdec_class_shim.so
@@ -39,11 +43,11 @@ tests/libjpegdec_class_shim.so: oracle/ref_shim.cpp include/JPEGDEC.h $(LIB)
 # (tests/class_cpu/stub_runtime.cpp: pixels from the oracle) -- test infrastructure: the recorded reference walks run on it without a
 # GPU (tests/test_class_walks_cpu.py), the second build under AddressSanitizer
 classcpu: tests/class_cpu/libjpegdec_class_cpu.so tests/class_cpu/walks_asan
-CLASS_CPU_SRCS = oracle/ref_shim.cpp $(CSRC)/JPEGDEC.cpp $(CSRC)/jda_frontend.cpp tests/class_cpu/stub_runtime.cpp tests/class_cpu/stub_dither.cpp
-tests/class_cpu/libjpegdec_class_cpu.so: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h oracle/jpegdec_oracle.c include/JPEGDEC.h include/jpegdec_amd.h
+CLASS_CPU_SRCS = oracle/ref_shim.cpp $(CSRC)/JPEGDEC.cpp $(CSRC)/jda_frontend.cpp tests/class_cpu/stub_runtime.cpp tests/class_cpu/stub_dither.cpp tests/class_cpu/stub_orient.cpp
+tests/class_cpu/libjpegdec_class_cpu.so: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h tests/hostsim/orient_twin.h oracle/jpegdec_oracle.c include/JPEGDEC.h include/jpegdec_amd.h
 	$(CC) -O2 -std=c11 -fPIC -c -o tests/class_cpu/oracle.o oracle/jpegdec_oracle.c
 	$(CXX) -O2 -std=c++17 -fPIC -shared -w -DSHIM_PRODUCT -Iinclude -o $@ $(CLASS_CPU_SRCS) tests/class_cpu/oracle.o -lpthread
-tests/class_cpu/walks_asan: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h tests/class_cpu/walks_main.cpp oracle/jpegdec_oracle.c include/JPEGDEC.h include/jpegdec_amd.h
+tests/class_cpu/walks_asan: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h tests/hostsim/orient_twin.h tests/class_cpu/walks_main.cpp oracle/jpegdec_oracle.c include/JPEGDEC.h include/jpegdec_amd.h
 	$(CC) -O1 -g -std=c11 -fsanitize=address,undefined -fno-omit-frame-pointer -c -o tests/class_cpu/oracle_asan.o oracle/jpegdec_oracle.c
 	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -w -DSHIM_PRODUCT -Iinclude -o $@ $(CLASS_CPU_SRCS) tests/class_cpu/walks_main.cpp tests/class_cpu/oracle_asan.o -lpthread
 
@@ -87,7 +91,7 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user
+	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib oracle hostsim classshim classcpu cuser nodeuser semuser perfuser fronttsan chunkequiv jpegtest frontfuzz nodestub clean

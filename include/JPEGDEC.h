@@ -14,7 +14,7 @@
 #include <stdint.h>
 
 // ---- decoder options (reference src/JPEGDEC.h:68-75)
-#define JPEG_AUTO_ROTATE 1        /* defined but never read by the reference either */
+#define JPEG_AUTO_ROTATE 1        /* decode(): apply the EXIF orientation on the GPU (below); the reference defines it and never reads it */
 #define JPEG_SCALE_HALF 2
 #define JPEG_SCALE_QUARTER 4
 #define JPEG_SCALE_EIGHTH 8
@@ -99,6 +99,13 @@ class JPEGDEC {
     void getCropArea(int *x, int *y, int *w, int *h);
     void close();
     int decode(int x, int y, int iOptions);
+    // decode() with JPEG_AUTO_ROTATE on an image whose getOrientation() is 2..8 (after JPEG_EXIF_THUMBNAIL: the thumbnail's, else the main
+    // image's) delivers the image upright: W' x H' = the visible (scaled) width x height, swapped for 5..8.  Framebuffer: H' rows of W' * bpp
+    // bytes, tightly packed (no MCU padding).  Callback: full-width strips in raster order, x = the x offset, y = the y offset + k * strip
+    // rows, iWidth = iWidthUsed = W', strip rows = the file's MCU height (0-4) or width (5-8) as scaled, the last one what is left;
+    // setMaxOutputSize does NOT split these strips and JPEG_USES_DMA has no effect.  A crop rectangle: JPEG_UNSUPPORTED_FEATURE.  A bad MCU:
+    // all of it is delivered with zeros for what was not decoded, then 0 / JPEG_DECODE_ERROR.  getWidth / getHeight stay the file's.  With
+    // the bit clear, or an orientation of 0, 1 or above 8, decode() is what it is without the bit; decodeDither ignores the bit.
     // decodeDither: the image decoded as EIGHT_BIT_GRAYSCALE and error-diffused to FOUR / TWO / ONE_BIT_DITHERED on the GPU, bit-exact with the
     // reference's JPEGDither; ONE draw callback per MCU row (iWidth = the whole MCU-padded row), the packed strip at the front of pDither
     // (>= one MCU row of 8-bit pixels, as the reference needs; the bytes behind the packed strip are not written).  Refused:

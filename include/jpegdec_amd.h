@@ -332,6 +332,27 @@ int jda_dither_surfaces(jda_ctx *ctx, int32_t n, const jda_output *gray, const i
 #define JDA_DITHER_SEED_BYTES 2184
 int jda_dither_seed(const uint8_t *jpeg, int32_t len, int32_t overlay, uint8_t *seed);
 
+/* ---- EXIF orientation applied on the GPU (the class's JPEG_AUTO_ROTATE; the reference defines the bit and never reads it)
+ * src = the VISIBLE rectangle of a decoded canvas: W = out_w x H = out_h pixels of bytes_per_pixel bytes (jda_output_geometry), never the MCU
+ * padding.  dst = W' x H' pixels, dst(y', x') = src(y, x):
+ *     orientation 0, 1: W x H, (y', x')       2: W x H, (y', W-1-x')       3: W x H, (H-1-y', W-1-x')       4: W x H, (H-1-y', x')
+ *                 5: H x W, (x', y')          6: H x W, (H-1-x', y')       7: H x W, (H-1-x', W-1-y')       8: H x W, (x', W-1-y')
+ * (what Pillow's exif_transpose does: FLIP_LEFT_RIGHT, ROTATE_180, FLIP_TOP_BOTTOM, TRANSPOSE, ROTATE_270, TRANSVERSE, ROTATE_90).  A file's
+ * orientation is one byte (EXIF tag 274, jda_image_info.orientation); any value outside 2..8 means "as it is".
+ * jda_oriented_geometry: orientation < 0: the file's.  *w, *h = W' x H'; *strip_rows = the source MCU's extent, in output pixels, along the
+ * axis that became vertical (mcu_h >> shift for 0-4, mcu_w >> shift for 5-8, at least 1): the height of the strips the class hands to a draw
+ * callback.  Refuses what jda_output_geometry refuses, with the same codes. */
+int jda_oriented_geometry(const jda_image_info *info, int32_t pixel_type, int32_t options, int32_t orientation,
+                          int32_t *bytes_per_pixel, int32_t *w, int32_t *h, int32_t *strip_rows);
+/* Orient n surfaces resident in HBM in ONE launch on the context's stream (behind whatever decoded them there); synchronous.
+ * src[i]: pixels (16-byte aligned), pitch_bytes (a multiple of 16), width_px x rows = the visible rectangle (rows are read in whole aligned
+ * 16-byte vectors: up to the next multiple of 16 behind width_px * bytes_per_pixel, inside the pitch).  dst[i]: the same alignment rules;
+ * width_px and rows must equal W' and H'.  Bytes of dst behind W' * bytes_per_pixel in a row, and rows behind H', are not written.
+ * orientations[i]: 0..8; 0 or 1 is a copy.  bytes_per_pixel: 1, 2 or 4, of every surface of the call.  JDA_INVALID_PARAMETER: an orientation
+ * outside 0..8, another pixel size, a wrong dst size, a null or misaligned pointer, a pitch too small or not a multiple of 16, byte ranges of
+ * a dst and of any src or other dst that overlap.  n == 0 succeeds and launches nothing. */
+int jda_orient_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *orientations, const jda_output *dst);
+
 /* PCI bus id ("0000:8e:00.0") of the context's GPU, for NUMA placement of the host threads that feed it; buf >= 16 bytes */
 int jda_device_pci_bus_id(jda_ctx *ctx, char *buf, int32_t len);
 int jda_device_pci_bus_id_of(int32_t device, char *buf, int32_t len);      /* the same by device ordinal, without a context */
@@ -358,6 +379,14 @@ int jda_decode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
  * the bad one on are dithered as zeros).  seed: JDA_DITHER_SEED_BYTES the chain starts from, or NULL: jda_dither_seed of the file. */
 int jda_decode_dither_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options,
                               const uint8_t *seed, void *host_packed, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded);
+/* jda_decode_to_host_ex followed by the orientation: prepare, upload, decode to a device canvas, orient its visible rectangle into a second
+ * device surface (jda_orient_surfaces) and copy back only the W' * bpp x H' bytes of jda_oriented_geometry: row r at host_pixels + r * pitch_bytes,
+ * pitch_bytes >= W' * bpp (any value), rows >= H'.  orientation < 0: the file's; 0..8 as given (0, 1: the visible rectangle as it is); above
+ * 8: JDA_INVALID_PARAMETER.  Pre-scan, host fallback, status and *mcus_decoded as jda_decode_to_host_ex; with JDA_DECODE_ERROR the MCUs from the
+ * bad one on are zeros BEFORE the orientation and the oriented canvas is still delivered.  Decode, orient and the copy are queued back to back.
+ * Dithered pixel types: JDA_INVALID_PARAMETER.  (jda_decode_to_host*, jda_batch_* and jda_pipeline_* keep ignoring option bit 1.) */
+int jda_decode_to_host_oriented(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, int32_t orientation,
+                                void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded);
 /* The same, decoding only the MCUs of mcu_rect = {mx0, my0, mx1, my1} (half open; NULL: everything): the canvas keeps its
  * geometry, the rows of the rectangle are written (zeros left and right of it), the others are not touched.  tiles (may be NULL):
  * [0] wavefront tiles launched, [1] tiles of the whole image. */

@@ -9,6 +9,7 @@ RGB565_LE, RGB565_BE, RGB8888, GRAY8 = 0, 1, 2, 3
 FOUR_BIT_DITHERED, TWO_BIT_DITHERED, ONE_BIT_DITHERED = 4, 5, 6      # made from a GRAY8 canvas: dither_surfaces / decode_dither_to_host
 DITHER_SEED_BYTES = 2184
 SCALE_HALF, SCALE_QUARTER, SCALE_EIGHTH, LUMA_ONLY = 2, 4, 8, 64
+AUTO_ROTATE = 1      # the class's decode() applies the EXIF orientation; the C-ABI takes it as an argument (decode_oriented_to_host, orient_surfaces)
 
 ERROR_NAMES = {0: "JDA_SUCCESS", 1: "JDA_INVALID_PARAMETER", 2: "JDA_DECODE_ERROR",
                3: "JDA_UNSUPPORTED_FEATURE", 4: "JDA_INVALID_FILE", 5: "JDA_ERROR_MEMORY",
@@ -123,6 +124,9 @@ _PROTOTYPES = [
     ("jda_dither_seed", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, _P]),
     ("jda_dither_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(Output)]),
     ("jda_decode_dither_to_host", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    ("jda_oriented_geometry", C.c_int, [C.POINTER(ImageInfo), C.c_int32, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4),
+    ("jda_orient_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output)]),
+    ("jda_decode_to_host_oriented", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     ("jda_checksum_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("jda_device_pci_bus_id", C.c_int, [_P, C.c_char_p, C.c_int32]),
     ("jda_upload_batch_ex", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32)]),
@@ -663,6 +667,42 @@ def decode_dither_to_host(ctx: Context, jpeg: bytes, pixel_type=ONE_BIT_DITHERED
     rc = ctx.lib.jda_decode_dither_to_host(ctx.handle, jpeg, len(jpeg), pixel_type, options, None if sd is None else sd.ctypes.data_as(_P),
                                            packed.ctypes.data_as(_P), d["pitch"], g["canvas_h"], C.byref(nok))
     return rc, packed, g
+
+
+def oriented_geometry(info: ImageInfo, pixel_type=RGB8888, options=0, orientation=None):
+    """jda_oriented_geometry: {"bpp", "w", "h", "strip_rows"} of the image after its EXIF orientation (orientation None: the file's)."""
+    vals = [C.c_int32(0) for _ in range(4)]
+    rc = load_library().jda_oriented_geometry(C.byref(info), pixel_type, options, -1 if orientation is None else orientation, *[C.byref(v) for v in vals])
+    if rc != 0:
+        raise JdaError(rc, "jda_oriented_geometry")
+    return dict(zip(("bpp", "w", "h", "strip_rows"), [v.value for v in vals]))
+
+
+def orient_surfaces(ctx: Context, src, bytes_per_pixel, orientations, dst):
+    """jda_orient_surfaces: src / dst = lists of (device_ptr, pitch_bytes, width_px, rows); one launch for all of them."""
+    n = len(src)
+    s = (Output * max(n, 1))(*[Output(*o) for o in src])
+    d = (Output * max(n, 1))(*[Output(*o) for o in dst])
+    ctx.check(ctx.lib.jda_orient_surfaces(ctx.handle, n, s, bytes_per_pixel, (C.c_int32 * max(n, 1))(*orientations), d), "jda_orient_surfaces")
+
+
+def decode_oriented_to_host(ctx: Context, jpeg: bytes, pixel_type=RGB8888, options=0, orientation=None, out=None):
+    """jda_decode_to_host_oriented: (rc, the oriented visible pixels (h x w * bpp bytes), geometry of the unrotated decode + "w", "h",
+    "strip_rows", "orientation").  orientation None: the file's.  out: an array of that shape from an earlier call, to decode into."""
+    info = ImageInfo()
+    rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
+    if rc != 0:
+        raise JdaError(rc, "jda_parse")
+    g = output_geometry(info, pixel_type, options)
+    t = oriented_geometry(info, pixel_type, options, orientation)
+    g.update(w=t["w"], h=t["h"], strip_rows=t["strip_rows"], orientation=info.orientation if orientation is None else orientation)
+    shape = (t["h"], t["w"] * t["bpp"])
+    pixels = out if out is not None and out.shape == shape and out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] else np.zeros(shape, dtype=np.uint8)
+    nok = C.c_int32(0)
+    rc = ctx.lib.jda_decode_to_host_oriented(ctx.handle, jpeg, len(jpeg), pixel_type, options, -1 if orientation is None else orientation,
+                                             pixels.ctypes.data_as(_P), t["w"] * t["bpp"], t["h"], C.byref(nok))
+    g["mcus_decoded"] = nok.value
+    return rc, pixels, g
 
 
 def decode_resident(ctx: Context, prepared: PreparedImage, pixel_type=RGB8888, options=0):

@@ -343,6 +343,42 @@ int JPEGDEC::decodeDither(int x, int y, uint8_t *pDither, int iOptions)
     return decode_dither(_jpeg, pDither, iOptions);
 }
 
+// decode(JPEG_AUTO_ROTATE) of an image whose EXIF orientation is 2..8 (the reference defines the bit and never reads it: everything here is
+// this library's own): the image is decoded and turned upright on the GPU (jda_decode_to_host_oriented) and only the W' x H' visible
+// pixels of jda_oriented_geometry come back, rows packed.  Framebuffer mode: they land in the caller's buffer, H' rows of W' * bpp bytes.
+// Callback mode: full-width strips of the upright image in raster order, strip_rows rows each (what an MCU row of the file has become),
+// iWidth = iWidthUsed = W'; setMaxOutputSize does not split them and JPEG_USES_DMA changes nothing.  A crop rectangle is refused.  A stream
+// with a bad MCU: everything is delivered, zeros where nothing was decoded, then 0 / JPEG_DECODE_ERROR.
+static int decode_oriented(jpegdec_amd_state *s, int pt, int iOptions, int orientation, bool cropped)
+{
+    if (cropped) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
+    int32_t bpp = 0, tw = 0, th = 0, strip = 1;
+    int rc = jda_oriented_geometry(&s->info, pt, iOptions, orientation, &bpp, &tw, &th, &strip);
+    if (rc != JDA_SUCCESS) { s->error = s->info.mcu_w ? rc : JPEG_UNSUPPORTED_FEATURE; return 0; }
+    int cerr = JDA_SUCCESS;
+    jda_ctx *ctx = thread_ctx(s->device, &cerr);
+    if (!ctx) { s->error = cerr; return 0; }
+    const size_t row_bytes = (size_t)tw * bpp, bytes = row_bytes * th;
+    if (!s->framebuffer && s->canvas.size() < bytes) s->canvas.resize(bytes);
+    uint8_t *const pixels = s->framebuffer ? (uint8_t *)s->framebuffer : s->canvas.data();
+    int32_t mcus_decoded = 0;
+    rc = jda_decode_to_host_oriented(ctx, s->data, s->size, pt, iOptions, orientation, pixels, (int32_t)row_bytes, th, &mcus_decoded);
+    const bool partial = rc == JDA_DECODE_ERROR;
+    if (rc != JDA_SUCCESS && !partial) { s->error = rc; return 0; }
+    if (!s->framebuffer && s->draw) {
+        JPEGDRAW jd;
+        for (int y0 = 0; y0 < th; y0 += strip) {
+            jd.x = s->xoff; jd.y = s->yoff + y0;
+            jd.iWidth = jd.iWidthUsed = tw; jd.iHeight = th - y0 < strip ? th - y0 : strip;
+            jd.iBpp = pt == RGB8888 ? 32 : pt == EIGHT_BIT_GRAYSCALE ? 8 : 16;          // (as the unrotated decode reports it)
+            jd.pPixels = (uint16_t *)(pixels + (size_t)y0 * row_bytes); jd.pUser = s->user;
+            if (!(*s->draw)(&jd)) break;                   // (as jpeg.inl:5325 ends the unrotated decode)
+        }
+    }
+    if (partial) { s->error = JPEG_DECODE_ERROR; return 0; }
+    return 1;
+}
+
 int JPEGDEC::decode(int x, int y, int iOptions)
 {
     jpegdec_amd_state *s = _jpeg;
@@ -354,6 +390,8 @@ int JPEGDEC::decode(int x, int y, int iOptions)
     const bool cropped = s->crop_x != 0 || s->crop_y != 0 || s->crop_w != s->info.width || s->crop_h != s->info.height;
     int pt = s->pixel_type;
     if ((iOptions & JPEG_LUMA_ONLY) && pt < EIGHT_BIT_GRAYSCALE) pt = s->pixel_type = EIGHT_BIT_GRAYSCALE;   // jpeg.inl:4991-4993
+    // JPEG_AUTO_ROTATE with an EXIF orientation that changes anything (of what is being decoded: a thumbnail without one has the main image's)
+    if ((iOptions & JPEG_AUTO_ROTATE) && s->info.orientation >= 2 && s->info.orientation <= 8) return decode_oriented(s, pt, iOptions, s->info.orientation, cropped);
     int bpp, ow, oh, cw, ch;
     int rc = jda_output_geometry(&s->info, pt, iOptions, &bpp, &ow, &oh, &cw, &ch);
     if (rc != JDA_SUCCESS) { s->error = s->info.mcu_w ? rc : JPEG_UNSUPPORTED_FEATURE; return 0; }

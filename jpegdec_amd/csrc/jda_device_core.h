@@ -3223,4 +3223,196 @@ JDA_HD void jda_dither_feed_turn(jda_dither_feed &F, uint32_t s)
 #define JDA_DITHER_PUBLISH 32                // the last row of a 64-row group tells the next group every so many pixels
 #define JDA_DITHER_LDS_HEAD 64               // bytes in front of the hand-over rows: one progress counter per wavefront
 
+// ---- EXIF orientation (JPEG_AUTO_ROTATE): a pure permutation of the pixels of a decoded canvas -------------------------------------
+// src = W x H pixels of BPP bytes, dst = W' x H'; dst(y', x') = src(y, x):
+//     0, 1: (y', x')    2: (y', W-1-x')    3: (H-1-y', W-1-x')    4: (H-1-y', x')                       W' x H' = W x H
+//     5: (x', y')       6: (H-1-x', y')    7: (H-1-x', W-1-y')    8: (x', W-1-y')                       W' x H' = H x W
+// i.e. "source x runs against the destination" for 2, 3, 7, 8 and "source y runs against it" for 3, 4, 6, 7, after a transposition for 5-8.
+// Tiles are laid on the DESTINATION, JDA_ORIENT_THREADS lanes a tile, every tile on its own:
+//   0-4   a tile is 16 vectors of 16 bytes x 64 rows; a lane moves one vector of four rows.  A mirrored row is read backwards: the 16
+//         destination bytes at X come from source bytes [Wb - X - 16, Wb - X), which are not 16-byte aligned when Wb % 16 != 0 -- the lane
+//         then loads the two aligned vectors around them and cuts its window out (jda_orient_window16; the cut is the same for the
+//         whole surface), reverses the pixels inside it (v_perm) and stores ONE aligned vector.
+//   5-8   a tile is 32 x 32 BLOCKS of P x P pixels, P = 4 / BPP: a block is one dword of P source rows and one dword of P destination
+//         rows.  Stage: lane = (source row r, dword c) reads along source rows -- both mirrors are applied HERE, rows taken in falling order
+//         and dwords cut from falling addresses (jda_orient_window4) and reversed -- and writes the dword to LDS.  Emit: lane = (block row
+//         bi, block column bj) reads the P dwords of its block, transposes them in registers (v_perm) and stores one dword to each of P
+//         destination rows, 32 lanes side by side along a row.  LDS: source row r at line (r % P) * 32 + r / P, JDA_ORIENT_LDS_STRIDE = 33
+//         dwords a line: the stage writes 32 consecutive dwords of a line per half wave, the emit reads dwords 33 apart -- every bank once.
+// Only the last vector (dword) of a destination row may be stored narrower; nothing behind W' * BPP bytes of a row or behind row H' is
+// written.  Source rows are read in whole aligned vectors: up to the next multiple of 16 (of 4 for 5-8) behind W * BPP, inside the pitch.
+// Memory goes through an IO policy so that the kernel (jda_kernels.hip) and the lane-by-lane run on the CPU (tests/hostsim/orient_sim.cpp)
+// are the same code.
+#define JDA_ORIENT_THREADS 256
+#define JDA_ORIENT_ROW_VECS 16u              // 0-4: vectors of 16 bytes across a tile
+#define JDA_ORIENT_ROW_ROWS 64u              // 0-4: rows of a tile (four per lane)
+#define JDA_ORIENT_BLOCKS 32u                // 5-8: blocks across and down a tile
+#define JDA_ORIENT_LDS_STRIDE 33u            // 5-8: dwords from one LDS line to the next
+#define JDA_ORIENT_LDS_DWORDS(bpp) (JDA_ORIENT_BLOCKS * (4u / (bpp)) * JDA_ORIENT_LDS_STRIDE)
+JDA_HD bool jda_orient_transposes(uint32_t o) { return o >= 5u && o <= 8u; }
+JDA_HD bool jda_orient_flips_x(uint32_t o) { return o == 2u || o == 3u || o == 7u || o == 8u; }
+JDA_HD bool jda_orient_flips_y(uint32_t o) { return o == 3u || o == 4u || o == 6u || o == 7u; }
+JDA_HD void jda_orient_dims(uint32_t o, uint32_t w, uint32_t h, uint32_t &dw, uint32_t &dh)
+{
+    const bool t = jda_orient_transposes(o);
+    dw = t ? h : w; dh = t ? w : h;
+}
+// tiles across and down the destination of a w x h source
+JDA_HD void jda_orient_tile_grid(uint32_t o, uint32_t bpp, uint32_t w, uint32_t h, uint32_t &tiles_x, uint32_t &tiles_y)
+{
+    uint32_t dw, dh;
+    jda_orient_dims(o, w, h, dw, dh);
+    if (jda_orient_transposes(o)) {
+        const uint32_t tp = JDA_ORIENT_BLOCKS * (4u / bpp);
+        tiles_x = (dw + tp - 1u) / tp; tiles_y = (dh + tp - 1u) / tp;
+    } else {
+        tiles_x = (dw * bpp + JDA_ORIENT_ROW_VECS * 16u - 1u) / (JDA_ORIENT_ROW_VECS * 16u); tiles_y = (dh + JDA_ORIENT_ROW_ROWS - 1u) / JDA_ORIENT_ROW_ROWS;
+    }
+}
+// the surface a tile of the flat list belongs to: the last job whose tile0 is not behind it (tile0 rises; n >= 1)
+JDA_HD uint32_t jda_orient_find_job(const jda_orient_job *jobs, uint32_t n, uint32_t tile)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (JDA_G(const jda_orient_job, jobs)[mid].tile0 <= tile) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// the pixels of a dword in falling order
+template <int BPP> JDA_HD uint32_t jda_orient_reverse(uint32_t v)
+{
+    return BPP == 4 ? v : BPP == 2 ? jda_perm(0u, v, 0x01000302u) : jda_perm(0u, v, 0x00010203u);
+}
+// P dwords of P pixels each -> pixel m of out[k] = pixel k of in[m]
+template <int BPP> JDA_HD void jda_orient_transpose_block(const uint32_t *in, uint32_t *out)
+{
+    if (BPP == 4) out[0] = in[0];
+    else if (BPP == 2) {
+        out[0] = jda_perm(in[1], in[0], 0x05040100u);
+        out[1] = jda_perm(in[1], in[0], 0x07060302u);
+    } else {
+        const uint32_t t0 = jda_perm(in[1], in[0], 0x05010400u), t1 = jda_perm(in[1], in[0], 0x07030602u);
+        const uint32_t u0 = jda_perm(in[3], in[2], 0x05010400u), u1 = jda_perm(in[3], in[2], 0x07030602u);
+        out[0] = jda_perm(u0, t0, 0x05040100u); out[1] = jda_perm(u0, t0, 0x07060302u);
+        out[2] = jda_perm(u1, t1, 0x05040100u); out[3] = jda_perm(u1, t1, 0x07060302u);
+    }
+}
+struct jda_orient_geo {                      // a job, wave-uniform
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t src_pitch, dst_pitch, w, h, o;
+};
+// bytes [so, so + 16) of a source row of row_bytes bytes (so < row_bytes, so > -16; what lies outside the aligned vectors that hold a byte
+// of the row reads zero): one aligned load when so is a multiple of 16, else two and a cut at so & 15 -- the same for every lane
+template <class IO> JDA_HD void jda_orient_window16(IO &io, const uint8_t *row, int32_t so, uint32_t row_bytes, uint32_t *d)
+{
+    const uint32_t cut = (uint32_t)so & 15u;
+    if (cut == 0u) { io.ld128(row + so, d); return; }
+    const int32_t a = so - (int32_t)cut;
+    uint32_t e[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) e[j] = 0u;
+    if (a >= 0) io.ld128(row + a, e);
+    if ((uint32_t)(a + 16) < row_bytes) io.ld128(row + a + 16, e + 4);
+    const uint32_t dw = cut >> 2, by = cut & 3u;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        uint32_t lo = e[j], hi = e[j + 1];
+#pragma unroll
+        for (int k = 1; k < 4; k++) if (dw == (uint32_t)k) { lo = e[j + k]; hi = e[j + k + 1]; }
+        d[j] = jda_alignbyte(hi, lo, by);
+    }
+}
+// bytes [so, so + 4) of a source row (so < row_bytes, so > -4), the same way with dwords
+template <class IO> JDA_HD uint32_t jda_orient_window4(IO &io, const uint8_t *row, int32_t so, uint32_t row_bytes)
+{
+    const uint32_t cut = (uint32_t)so & 3u;
+    if (cut == 0u) return io.ld32(row + so);
+    const int32_t a = so - (int32_t)cut;
+    const uint32_t lo = a >= 0 ? io.ld32(row + a) : 0u;
+    const uint32_t hi = (uint32_t)(a + 4) < row_bytes ? io.ld32(row + a + 4) : 0u;
+    return jda_alignbyte(hi, lo, cut);
+}
+// the first n (1-3) bytes of v: the end of a row that is not a whole number of dwords
+template <class IO> JDA_HD void jda_orient_store_tail(IO &io, uint8_t *p, uint32_t v, uint32_t n)
+{
+    if (n & 2u) { io.st16(p, v & 0xffffu); p += 2; v >>= 16; }
+    if (n & 1u) io.st8(p, v & 0xffu);
+}
+// orientations 0-4, tile (tx, ty), lane tid
+template <int BPP, class IO> JDA_HD void jda_orient_rows(const jda_orient_geo &G, uint32_t tx, uint32_t ty, uint32_t tid, IO &io)
+{
+    const uint32_t row_bytes = G.w * (uint32_t)BPP;
+    const uint32_t xb = (tx * JDA_ORIENT_ROW_VECS + (tid & (JDA_ORIENT_ROW_VECS - 1u))) * 16u, r0 = ty * JDA_ORIENT_ROW_ROWS + tid / JDA_ORIENT_ROW_VECS;
+    if (xb >= row_bytes) return;
+    const bool fx = jda_orient_flips_x(G.o), fy = jda_orient_flips_y(G.o);
+    const int32_t so = fx ? (int32_t)row_bytes - (int32_t)xb - 16 : (int32_t)xb;
+    const uint32_t step = JDA_ORIENT_THREADS / JDA_ORIENT_ROW_VECS, n = row_bytes - xb < 16u ? row_bytes - xb : 16u;
+    uint32_t d[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {            // every load of the lane first, then its stores
+        const uint32_t y = r0 + (uint32_t)i * step;
+        if (y < G.h) jda_orient_window16(io, G.src + (size_t)(fy ? G.h - 1u - y : y) * G.src_pitch, so, row_bytes, d[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t y = r0 + (uint32_t)i * step;
+        if (y >= G.h) continue;
+        uint32_t q[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) q[j] = fx ? jda_orient_reverse<BPP>(d[i][3 - j]) : d[i][j];
+        uint8_t *p = G.dst + (size_t)y * G.dst_pitch + xb;
+        if (n == 16u) { io.st128(p, q); continue; }
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) {                      // the row's last, partial vector: whole dwords, then what is left
+            if (j < (n >> 2)) io.st32(p + 4u * j, q[j]);
+            else if (j == (n >> 2) && (n & 3u)) jda_orient_store_tail(io, p + 4u * j, q[j], n & 3u);
+        }
+    }
+}
+// orientations 5-8, first half: the tile's source dwords into LDS, mirrors applied
+template <int BPP, class IO> JDA_HD void jda_orient_stage(const jda_orient_geo &G, uint32_t tx, uint32_t ty, uint32_t tid, IO &io)
+{
+    const uint32_t P = 4u / (uint32_t)BPP, TP = JDA_ORIENT_BLOCKS * P, row_bytes = G.w * (uint32_t)BPP;
+    const bool fx = jda_orient_flips_x(G.o), fy = jda_orient_flips_y(G.o);
+#pragma unroll
+    for (uint32_t i = 0; i < TP * JDA_ORIENT_BLOCKS / JDA_ORIENT_THREADS; i++) {
+        const uint32_t idx = i * JDA_ORIENT_THREADS + tid, r = idx / JDA_ORIENT_BLOCKS, c = idx % JDA_ORIENT_BLOCKS;
+        const uint32_t dx = tx * TP + r;                         // the destination column this source row becomes
+        const uint32_t dy = ty * TP + c * P;                     // the first of the P destination rows this dword's pixels go to
+        uint32_t v = 0u;
+        if (dx < G.h && dy < G.w) {
+            const uint8_t *row = G.src + (size_t)(fy ? G.h - 1u - dx : dx) * G.src_pitch;
+            const int32_t so = fx ? (int32_t)row_bytes - (int32_t)(dy * (uint32_t)BPP) - 4 : (int32_t)(dy * (uint32_t)BPP);
+            v = jda_orient_window4(io, row, so, row_bytes);
+            if (fx) v = jda_orient_reverse<BPP>(v);
+        }
+        io.lds_wr(((r % P) * JDA_ORIENT_BLOCKS + r / P) * JDA_ORIENT_LDS_STRIDE + c, v);
+    }
+}
+// .. second half (behind a workgroup barrier): blocks out of LDS, transposed, to the destination
+template <int BPP, class IO> JDA_HD void jda_orient_emit(const jda_orient_geo &G, uint32_t tx, uint32_t ty, uint32_t tid, IO &io)
+{
+    const uint32_t P = 4u / (uint32_t)BPP, TP = JDA_ORIENT_BLOCKS * P, dst_row_bytes = G.h * (uint32_t)BPP;
+#pragma unroll
+    for (uint32_t i = 0; i < JDA_ORIENT_BLOCKS * JDA_ORIENT_BLOCKS / JDA_ORIENT_THREADS; i++) {
+        const uint32_t idx = i * JDA_ORIENT_THREADS + tid, bi = idx / JDA_ORIENT_BLOCKS, bj = idx % JDA_ORIENT_BLOCKS;
+        uint32_t in[4], out[4];
+#pragma unroll
+        for (uint32_t m = 0; m < P; m++) in[m] = io.lds_rd((m * JDA_ORIENT_BLOCKS + bj) * JDA_ORIENT_LDS_STRIDE + bi);
+        jda_orient_transpose_block<BPP>(in, out);
+        const uint32_t xb = (tx * JDA_ORIENT_BLOCKS + bj) * 4u;
+        if (xb >= dst_row_bytes) continue;
+        const uint32_t n = dst_row_bytes - xb < 4u ? dst_row_bytes - xb : 4u;
+#pragma unroll
+        for (uint32_t k = 0; k < P; k++) {
+            const uint32_t y = ty * TP + bi * P + k;
+            if (y >= G.w) continue;
+            uint8_t *p = G.dst + (size_t)y * G.dst_pitch + xb;
+            if (n == 4u) io.st32(p, out[k]); else jda_orient_store_tail(io, p, out[k], n);
+        }
+    }
+}
+
 #endif // JDA_DEVICE_CORE_H

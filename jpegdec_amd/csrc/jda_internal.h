@@ -190,4 +190,13 @@ struct jda_dither_job {
     uint32_t gray_pitch, out_pitch, width, height, strip_rows, bits;
 };
 
+// One surface of an orient launch (device pointers): src = the visible rectangle of a decoded canvas, width x height pixels of the
+// launch's pixel size at src_pitch; dst = the oriented rectangle (jda_orient_dims) at dst_pitch.  Both 16-byte aligned, both pitches
+// multiples of 16.  tile0: the index of the surface's first tile in the launch's flat tile list, tiles_x: tiles across the destination.
+struct jda_orient_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t src_pitch, dst_pitch, width, height, orientation, tile0, tiles_x, pad_;
+};
+
 #endif

@@ -1826,6 +1826,59 @@ extern "C" hipError_t jda_launch_dither(const jda_dither_job *jobs, uint32_t n, 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// jda_orient_tiles<BPP>: the EXIF orientation applied to decoded canvases -- a permutation of pixels, tile by tile (the address map
+// and the lane schedule: jda_orient_rows / _stage / _emit in jda_device_core.h).  grid = the flat list of every surface's tiles; a
+// workgroup finds its surface by bisection over the jobs' first tile numbers (scalar loads) and keeps the job in SGPRs, so the
+// orientation is wave-uniform.  Global accesses: 16-byte vectors (0-4) or dwords (5-8), aligned, lanes side by side; narrower only
+// for the last partial vector of a destination row.  One workgroup barrier (5-8); no atomics, nothing shared between tiles.
+struct jda_orient_io {
+    uint32_t *lds;
+    __device__ __forceinline__ uint32_t ld32(const uint8_t *p) const { return *(const jda_u32_alias JDA_GLOBAL *)JDA_G(const uint8_t, p); }
+    __device__ __forceinline__ void ld128(const uint8_t *p, uint32_t *v) const
+    {
+        const uint4 q = *(const uint4 JDA_GLOBAL *)JDA_G(const uint8_t, p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+    __device__ __forceinline__ void st128(uint8_t *p, const uint32_t *v) const { *(uint4 JDA_GLOBAL *)JDA_G(uint8_t, p) = make_uint4(v[0], v[1], v[2], v[3]); }
+    __device__ __forceinline__ void st32(uint8_t *p, uint32_t v) const { *(jda_u32_alias JDA_GLOBAL *)JDA_G(uint8_t, p) = v; }
+    __device__ __forceinline__ void st16(uint8_t *p, uint32_t v) const { *(uint16_t JDA_GLOBAL *)JDA_G(uint8_t, p) = (uint16_t)v; }
+    __device__ __forceinline__ void st8(uint8_t *p, uint32_t v) const { *JDA_G(uint8_t, p) = (uint8_t)v; }
+    __device__ __forceinline__ void lds_wr(uint32_t i, uint32_t v) const { lds[i] = v; }
+    __device__ __forceinline__ uint32_t lds_rd(uint32_t i) const { return lds[i]; }
+};
+template <int BPP>
+__global__ __launch_bounds__(JDA_ORIENT_THREADS)
+void jda_orient_tiles(const jda_orient_job *__restrict__ jobs, uint32_t n_jobs)
+{
+    __shared__ uint32_t orient_lds[JDA_ORIENT_LDS_DWORDS(BPP)];
+    const uint32_t tile = blockIdx.x;
+    const jda_orient_job JDA_GLOBAL *job = JDA_G(const jda_orient_job, jobs) + jda_uni32(jda_orient_find_job(jobs, n_jobs, tile));
+    jda_orient_geo G;
+    G.src = jda_uni_ptr(job->src); G.dst = jda_uni_ptr(job->dst);
+    G.src_pitch = jda_uni32(job->src_pitch); G.dst_pitch = jda_uni32(job->dst_pitch);
+    G.w = jda_uni32(job->width); G.h = jda_uni32(job->height); G.o = jda_uni32(job->orientation);
+    const uint32_t local = tile - jda_uni32(job->tile0), tiles_x = jda_uni32(job->tiles_x);
+    if (tiles_x == 0u) return;
+    const uint32_t ty = local / tiles_x, tx = local - ty * tiles_x;
+    jda_orient_io io;
+    io.lds = orient_lds;
+    if (!jda_orient_transposes(G.o)) { jda_orient_rows<BPP>(G, tx, ty, threadIdx.x, io); return; }
+    jda_orient_stage<BPP>(G, tx, ty, threadIdx.x, io);
+    __syncthreads();
+    jda_orient_emit<BPP>(G, tx, ty, threadIdx.x, io);
+}
+// n surfaces of one pixel size, n_tiles = the sum of their tile grids (the jobs carry where each one's tiles begin)
+extern "C" hipError_t jda_launch_orient(const jda_orient_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, hipStream_t stream)
+{
+    if (n == 0 || n_tiles == 0) return hipSuccess;
+    if (bytes_per_pixel == 4u) JDA_LAUNCH(jda_orient_tiles<4>, dim3(n_tiles), dim3(JDA_ORIENT_THREADS), 0, stream, jobs, n);
+    else if (bytes_per_pixel == 2u) JDA_LAUNCH(jda_orient_tiles<2>, dim3(n_tiles), dim3(JDA_ORIENT_THREADS), 0, stream, jobs, n);
+    else if (bytes_per_pixel == 1u) JDA_LAUNCH(jda_orient_tiles<1>, dim3(n_tiles), dim3(JDA_ORIENT_THREADS), 0, stream, jobs, n);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 extern "C" hipError_t jda_internal_set_wgtrace(unsigned long long *dev_buf)
 {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_jda_wgtrace), &dev_buf, sizeof(dev_buf));

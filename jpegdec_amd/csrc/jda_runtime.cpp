@@ -1250,4 +1250,183 @@ int jda_decode_dither_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
     return rc;
 }
 
+// ---- EXIF orientation (jda_orient_tiles in jda_kernels.hip; the permutation and its tiles: jda_device_core.h)
+// Check n surfaces and upload their job records (and wait for them: they leave pageable memory that goes away with this frame); plan->block
+// (pool block) is the caller's to release once the stream has drained.  orient_launch then queues the kernel.
+struct orient_plan { void *block; uint32_t n, n_tiles, bpp; };
+static int orient_upload(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *orientations, const jda_output *dst, orient_plan *plan)
+{
+    plan->block = NULL; plan->n = (uint32_t)n; plan->n_tiles = 0; plan->bpp = (uint32_t)bytes_per_pixel;
+    if (bytes_per_pixel != 1 && bytes_per_pixel != 2 && bytes_per_pixel != 4) return JDA_INVALID_PARAMETER;
+    std::vector<jda_orient_job> jobs((size_t)n);
+    struct range { uintptr_t a, b; int32_t i; bool is_dst; };
+    std::vector<range> ranges;
+    ranges.reserve((size_t)n * 2);
+    uint64_t tiles = 0;
+    for (int i = 0; i < n; i++) {
+        const jda_output &S = src[i], &D = dst[i];
+        const int32_t o = orientations[i];
+        if (o < 0 || o > 8 || !S.pixels || !D.pixels || S.width_px <= 0 || S.rows <= 0 || S.width_px > (1 << 24) || S.rows > (1 << 24)) return JDA_INVALID_PARAMETER;
+        uint32_t dw, dh;
+        jda_orient_dims((uint32_t)o, (uint32_t)S.width_px, (uint32_t)S.rows, dw, dh);
+        if (D.width_px != (int32_t)dw || D.rows != (int32_t)dh) return JDA_INVALID_PARAMETER;
+        const int64_t srow = (int64_t)S.width_px * bytes_per_pixel, drow = (int64_t)dw * bytes_per_pixel;
+        if (((uintptr_t)S.pixels & 15u) || ((uintptr_t)D.pixels & 15u) || (S.pitch_bytes & 15) || (D.pitch_bytes & 15)) return JDA_INVALID_PARAMETER;
+        if (S.pitch_bytes < srow || D.pitch_bytes < drow) return JDA_INVALID_PARAMETER;
+        // what the launch reads (whole aligned vectors of every row) and what it writes
+        ranges.push_back({ (uintptr_t)S.pixels, (uintptr_t)S.pixels + (size_t)(S.rows - 1) * (size_t)S.pitch_bytes + align16((size_t)srow), i, false });
+        ranges.push_back({ (uintptr_t)D.pixels, (uintptr_t)D.pixels + (size_t)(dh - 1) * (size_t)D.pitch_bytes + (size_t)drow, i, true });
+        jda_orient_job &J = jobs[(size_t)i];
+        J.src = (const uint8_t *)S.pixels; J.dst = (uint8_t *)D.pixels;
+        J.src_pitch = (uint32_t)S.pitch_bytes; J.dst_pitch = (uint32_t)D.pitch_bytes;
+        J.width = (uint32_t)S.width_px; J.height = (uint32_t)S.rows; J.orientation = (uint32_t)o; J.pad_ = 0;
+        uint32_t tx, ty;
+        jda_orient_tile_grid((uint32_t)o, (uint32_t)bytes_per_pixel, J.width, J.height, tx, ty);
+        J.tile0 = (uint32_t)tiles; J.tiles_x = tx;
+        tiles += (uint64_t)tx * ty;
+        if (tiles > 0x7fffffffull) return JDA_INVALID_PARAMETER;
+    }
+    // a destination may share no byte with a source or with another destination: sorted by start, a range that begins inside the union of
+    // the ranges before it overlaps one of them -- two sources may, anything with a destination in it may not
+    std::sort(ranges.begin(), ranges.end(), [](const range &x, const range &y) { return x.a < y.a; });
+    uintptr_t end_any = 0, end_dst = 0;
+    for (const range &r : ranges) {
+        if (r.is_dst ? r.a < end_any : r.a < end_dst) return JDA_INVALID_PARAMETER;
+        end_any = std::max(end_any, r.b);
+        if (r.is_dst) end_dst = std::max(end_dst, r.b);
+    }
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, align16(jobs.size() * sizeof(jda_orient_job)));
+    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(orient jobs)");
+    e = hipMemcpyAsync(blk, jobs.data(), jobs.size() * sizeof(jda_orient_job), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { jda_pool_free(ctx, blk); return jda_set_err(ctx, e, "orient jobs"); }
+    plan->block = blk; plan->n_tiles = (uint32_t)tiles;
+    return JDA_SUCCESS;
+}
+static int orient_launch(jda_ctx *ctx, const orient_plan &plan)
+{
+    const hipError_t e = jda_launch_orient((const jda_orient_job *)plan.block, plan.n, plan.n_tiles, plan.bpp, ctx->stream);
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_orient_tiles");
+}
+
+int jda_orient_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *orientations, const jda_output *dst)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0 || (bytes_per_pixel != 1 && bytes_per_pixel != 2 && bytes_per_pixel != 4)) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    if (!src || !orientations || !dst) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    orient_plan plan;
+    int rc = orient_upload(ctx, n, src, bytes_per_pixel, orientations, dst, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = orient_launch(ctx, plan);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, plan.block);
+    if (rc != JDA_SUCCESS) return rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_orient_surfaces");
+}
+
+int jda_decode_to_host_oriented(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, int32_t orientation,
+                                void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded)
+{
+    if (mcus_decoded) *mcus_decoded = 0;
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!jpeg || !host_pixels || orientation > 8 || pixel_type < 0 || pixel_type > JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    int32_t err = JDA_SUCCESS;
+    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
+    if (!img) return err;
+    const jda_image_info I = *jda_image_get_info(img);
+    int bpp, ow, oh, cw, ch, tw = 0, th = 0;
+    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
+    if (rc == JDA_SUCCESS) rc = jda_oriented_geometry(&I, pixel_type, options, orientation, NULL, &tw, &th, NULL);
+    if (rc == JDA_SUCCESS && (ow > cw || oh > ch || pitch_bytes < tw * bpp || rows < th)) rc = JDA_INVALID_PARAMETER;
+    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
+    int32_t o = orientation < 0 ? I.orientation : orientation;
+    if (o < 2 || o > 8) o = 0;                          // "as it is": the visible rectangle goes back from the canvas itself
+    jda_dev_image *dimg = jda_upload(ctx, img, &err);
+    uint32_t nok = 0;
+    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
+    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
+    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
+    jda_image_free(img);
+    if (!dimg) return err;
+    const int cpitch = (int)align16((size_t)cw * bpp), opitch = (int)align16((size_t)tw * bpp);
+    const size_t cbytes = (size_t)cpitch * ch;
+    uint8_t *dsurf = NULL;                              // the decoded canvas, the oriented surface behind it
+    if (jda_pool_alloc(ctx, (void **)&dsurf, cbytes + (o ? (size_t)opitch * th : 0)) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
+    jda_output C, S, D;
+    C.pixels = dsurf; C.pitch_bytes = cpitch; C.width_px = cw; C.rows = ch;
+    S = C; S.width_px = ow; S.rows = oh;                // the visible rectangle of the canvas
+    D.pixels = dsurf + cbytes; D.pitch_bytes = opitch; D.width_px = tw; D.rows = th;
+    jda_batch *b = jda_batch_create(ctx, 1, &dimg, &C, &pixel_type, &options, &err);
+    rc = err;
+    if (b) {
+        // what has to wait for the host -- the job record -- first; then decode, orient and the copy back are queued back to back
+        orient_plan plan;
+        plan.block = NULL;
+        if (o) rc = orient_upload(ctx, 1, &S, bpp, &o, &D, &plan);
+        if (rc == JDA_SUCCESS && !complete) (void)hipMemsetAsync(dsurf, 0, cbytes, ctx->stream);       // (the MCUs a bad stream does not reach are zeros before they are turned)
+        if (rc == JDA_SUCCESS) rc = jda_batch_decode(ctx, b);
+        if (rc == JDA_SUCCESS && o) rc = orient_launch(ctx, plan);
+        if (rc == JDA_SUCCESS) {
+            const uint8_t *from = o ? (const uint8_t *)D.pixels : dsurf;
+            const size_t fpitch = (size_t)(o ? opitch : cpitch), row_bytes = (size_t)tw * bpp;
+            hipError_t e;
+            if ((size_t)pitch_bytes == fpitch && row_bytes == fpitch) e = hipMemcpyAsync(host_pixels, from, row_bytes * (size_t)th, hipMemcpyDeviceToHost, ctx->stream);      // (rows without a gap on either side: one piece)
+            else e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, from, fpitch, row_bytes, (size_t)th, hipMemcpyDeviceToHost, ctx->stream);
+            { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+        } else (void)hipStreamSynchronize(ctx->stream);
+        if (plan.block) jda_pool_free(ctx, plan.block);
+        jda_batch_destroy(ctx, b);
+    }
+    jda_pool_free(ctx, dsurf);
+    jda_dev_image_free(ctx, dimg);
+    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
+    return rc;
+}
+
+// Measuring hooks of tools/orient_bench.py (not part of the public header): the orient launch, and a device-to-device copy to hold it
+// against, each between the context's two timer events on its stream -- the job records go up before the first event.  ms[k]: repeat k.
+int jda_internal_orient_time(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *orientations, const jda_output *dst,
+                             int32_t reps, float *ms)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n <= 0 || !src || !orientations || !dst || reps <= 0 || !ms) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    orient_plan plan;
+    int rc = orient_upload(ctx, n, src, bytes_per_pixel, orientations, dst, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < reps && rc == JDA_SUCCESS && e == hipSuccess; k++) {
+        e = hipEventRecord(ctx->ev_start, ctx->stream);
+        if (e == hipSuccess) rc = orient_launch(ctx, plan);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, plan.block);
+    if (rc != JDA_SUCCESS) return rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_orient_time");
+}
+int jda_internal_copy_time(jda_ctx *ctx, void *dst, const void *src, size_t bytes, int32_t reps, float *ms)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!dst || !src || !bytes || reps <= 0 || !ms) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < reps && e == hipSuccess; k++) {
+        e = hipEventRecord(ctx->ev_start, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_copy_time");
+}
+
 } // extern "C"

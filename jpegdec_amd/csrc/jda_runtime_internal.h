@@ -103,6 +103,8 @@ extern "C" hipError_t jda_launch_segscan_fused(const jda_segscan_params *params,
 extern "C" hipError_t jda_launch_checksum(const void *base, uint32_t pitch, uint32_t row_bytes, uint32_t rows, unsigned long long *out, hipStream_t stream);
 // n GRAY8 canvases -> packed 4 / 2 / 1-bpp rows, one workgroup an image; *fail (device, zeroed by the caller) is raised if a wavefront gave up waiting
 extern "C" hipError_t jda_launch_dither(const jda_dither_job *jobs, uint32_t n, uint32_t max_w, uint32_t max_h, uint32_t *fail, hipStream_t stream);
+// n surfaces of one pixel size -> their EXIF orientations, one workgroup a destination tile; n_tiles: the length of the flat tile list
+extern "C" hipError_t jda_launch_orient(const jda_orient_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, hipStream_t stream);
 extern "C" hipError_t jda_launch_segscan_tail(const jda_segscan_params *params, uint32_t n_images, uint32_t max_segs, uint32_t first_round, uint32_t max_round, hipStream_t stream);
 extern "C" hipError_t jda_launch_filter(const jda_filter_params *params, uint32_t n_images, uint32_t max_raw_len, hipStream_t stream);
 extern "C" hipError_t jda_launch_fill_strips(const jda_strips_params *params, uint32_t n_images, uint32_t max_tiles, hipStream_t stream);
