@@ -10,7 +10,7 @@ CSRC  = jpegdec_amd/csrc
 EXTRA ?=
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared -fwrapv -pthread -Wall -Wno-unused-function -Iinclude $(EXTRA)
 LIB = jpegdec_amd/libjpegdec_amd.so
-LIB_SRCS = $(CSRC)/jda_frontend.cpp $(CSRC)/jda_runtime.cpp $(CSRC)/jda_pipeline.cpp $(CSRC)/jda_node.cpp $(CSRC)/jda_kernels.hip $(CSRC)/JPEGDEC.cpp
+LIB_SRCS = $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp $(CSRC)/jda_runtime.cpp $(CSRC)/jda_pipeline.cpp $(CSRC)/jda_node.cpp $(CSRC)/jda_kernels.hip $(CSRC)/JPEGDEC.cpp
 LIB_DEPS = $(LIB_SRCS) $(CSRC)/jda_runtime_internal.h $(CSRC)/jda_internal.h $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h include/jpegdec_amd.h include/JPEGDEC.h
 
 all: lib oracle hostsim classshim
@@ -22,7 +22,7 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so
+hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
@@ -34,6 +34,10 @@ tests/hostsim/libjda_dithersim.so: tests/hostsim/dither_sim.cpp tests/hostsim/di
 tests/hostsim/libjda_orientsim.so: tests/hostsim/orient_sim.cpp tests/hostsim/orient_twin.h $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/orient_sim.cpp $(CSRC)/jda_frontend.cpp
 
+# the coefficient-tile kernel's lane schedule and its row-major twin on the CPU (tests/test_progressive_full_cpu.py) -- test infrastructure
+tests/hostsim/libjda_coefsim.so: tests/hostsim/coef_sim.cpp tests/hostsim/coef_twin.h $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/coef_sim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp
+
 # the reference-API driver (oracle/ref_shim.cpp) built against the product's JPEGDEC class -- test infrastructure
 classshim: tests/libjpegdec_class_shim.so
 tests/libjpegdec_class_shim.so: oracle/ref_shim.cpp include/JPEGDEC.h $(LIB)
@@ -43,11 +47,11 @@ tests/libjpegdec_class_shim.so: oracle/ref_shim.cpp include/JPEGDEC.h $(LIB)
 # (tests/class_cpu/stub_runtime.cpp: pixels from the oracle) -- test infrastructure: the recorded reference walks run on it without a
 # GPU (tests/test_class_walks_cpu.py), the second build under AddressSanitizer
 classcpu: tests/class_cpu/libjpegdec_class_cpu.so tests/class_cpu/walks_asan
-CLASS_CPU_SRCS = oracle/ref_shim.cpp $(CSRC)/JPEGDEC.cpp $(CSRC)/jda_frontend.cpp tests/class_cpu/stub_runtime.cpp tests/class_cpu/stub_dither.cpp tests/class_cpu/stub_orient.cpp
-tests/class_cpu/libjpegdec_class_cpu.so: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h tests/hostsim/orient_twin.h oracle/jpegdec_oracle.c include/JPEGDEC.h include/jpegdec_amd.h
+CLASS_CPU_SRCS = oracle/ref_shim.cpp $(CSRC)/JPEGDEC.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp tests/class_cpu/stub_runtime.cpp tests/class_cpu/stub_dither.cpp tests/class_cpu/stub_orient.cpp tests/class_cpu/stub_coef.cpp
+tests/class_cpu/libjpegdec_class_cpu.so: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h tests/hostsim/orient_twin.h tests/hostsim/coef_twin.h oracle/jpegdec_oracle.c include/JPEGDEC.h include/jpegdec_amd.h
 	$(CC) -O2 -std=c11 -fPIC -c -o tests/class_cpu/oracle.o oracle/jpegdec_oracle.c
 	$(CXX) -O2 -std=c++17 -fPIC -shared -w -DSHIM_PRODUCT -Iinclude -o $@ $(CLASS_CPU_SRCS) tests/class_cpu/oracle.o -lpthread
-tests/class_cpu/walks_asan: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h tests/hostsim/orient_twin.h tests/class_cpu/walks_main.cpp oracle/jpegdec_oracle.c include/JPEGDEC.h include/jpegdec_amd.h
+tests/class_cpu/walks_asan: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h tests/hostsim/orient_twin.h tests/hostsim/coef_twin.h tests/class_cpu/walks_main.cpp oracle/jpegdec_oracle.c include/JPEGDEC.h include/jpegdec_amd.h
 	$(CC) -O1 -g -std=c11 -fsanitize=address,undefined -fno-omit-frame-pointer -c -o tests/class_cpu/oracle_asan.o oracle/jpegdec_oracle.c
 	$(CXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -w -DSHIM_PRODUCT -Iinclude -o $@ $(CLASS_CPU_SRCS) tests/class_cpu/walks_main.cpp tests/class_cpu/oracle_asan.o -lpthread
 
@@ -55,6 +59,11 @@ tests/class_cpu/walks_asan: $(CLASS_CPU_SRCS) tests/hostsim/dither_twin.h tests/
 cuser: tests/capi_c/c_user
 tests/capi_c/c_user: tests/capi_c/c_user.c include/JPEGDEC.h $(LIB)
 	$(CC) -std=c99 -O2 -Wall -Iinclude -o $@ tests/capi_c/c_user.c -Ljpegdec_amd -ljpegdec_amd -Wl,-rpath,'$$ORIGIN/../../jpegdec_amd'
+
+# a plain C program decoding with a caller-chosen option word (JPEG_PROGRESSIVE_FULL: tests/test_gpu_progressive_full.py)
+proguser: tests/capi_c/prog_user
+tests/capi_c/prog_user: tests/capi_c/prog_user.c include/JPEGDEC.h $(LIB)
+	$(CC) -std=c99 -O2 -Wall -Iinclude -o $@ tests/capi_c/prog_user.c -Ljpegdec_amd -ljpegdec_amd -Wl,-rpath,'$$ORIGIN/../../jpegdec_amd'
 
 # a plain C program on the node entry points (jda_node_*): one file decoded n times over every GPU of the node
 nodeuser: tests/capi_c/node_user
@@ -91,10 +100,10 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user
+	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle hostsim classshim classcpu cuser nodeuser semuser perfuser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
+.PHONY: all lib oracle hostsim classshim classcpu cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
 
 # jda_node.cpp (host code above the C-ABI) over eight pretend devices -- test infrastructure, no GPU (tests/test_c_api.py)
 nodestub: tests/node_stub/node_stub_user

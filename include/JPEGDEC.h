@@ -22,6 +22,7 @@
 #define JPEG_EXIF_THUMBNAIL 32
 #define JPEG_LUMA_ONLY 64
 #define JPEG_USES_DMA 128
+#define JPEG_PROGRESSIVE_FULL 256 /* not in the reference: decode() delivers EVERY scan of a progressive file at full size (below) */
 
 #define MAX_BUFFERED_PIXELS 2048  /* size of the strip a draw callback receives, in uint16 units */
 
@@ -106,6 +107,12 @@ class JPEGDEC {
     // setMaxOutputSize does NOT split these strips and JPEG_USES_DMA has no effect.  A crop rectangle: JPEG_UNSUPPORTED_FEATURE.  A bad MCU:
     // all of it is delivered with zeros for what was not decoded, then 0 / JPEG_DECODE_ERROR.  getWidth / getHeight stay the file's.  With
     // the bit clear, or an orientation of 0, 1 or above 8, decode() is what it is without the bit; decodeDither ignores the bit.
+    // decode() with JPEG_PROGRESSIVE_FULL on a progressive file (getJPEGType() == JPEG_MODE_PROGRESSIVE): every scan is decoded -- the host
+    // reads the scans into coefficients, the GPU does the rest -- and the image arrives at full size instead of as the 1/8 thumbnail of
+    // its first scan: framebuffer layout, draw strips (setMaxOutputSize, JPEG_USES_DMA) and every getter are those of a baseline file of
+    // the same dimensions and sampling.  A JPEG_SCALE_* bit, a crop rectangle, JPEG_AUTO_ROTATE on an orientation 2..8 or
+    // JPEG_EXIF_THUMBNAIL together with it: JPEG_UNSUPPORTED_FEATURE.  A scan that cannot be decoded: 0 / JPEG_DECODE_ERROR and nothing is
+    // delivered (no callback, the framebuffer untouched).  On a baseline file the bit has no effect; decodeDither ignores it.
     // decodeDither: the image decoded as EIGHT_BIT_GRAYSCALE and error-diffused to FOUR / TWO / ONE_BIT_DITHERED on the GPU, bit-exact with the
     // reference's JPEGDither; ONE draw callback per MCU row (iWidth = the whole MCU-padded row), the packed strip at the front of pDither
     // (>= one MCU row of 8-bit pixels, as the reference needs; the bytes behind the packed strip are not written).  Refused:

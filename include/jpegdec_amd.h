@@ -63,7 +63,13 @@ enum {
     JDA_SCALE_HALF = 2,
     JDA_SCALE_QUARTER = 4,
     JDA_SCALE_EIGHTH = 8,
-    JDA_LUMA_ONLY = 64
+    JDA_LUMA_ONLY = 64,
+    /* ours (the reference has nothing like it): decode EVERY scan of a progressive file to a full-size canvas instead of the 1/8
+     * thumbnail of its first scan.  No effect on a baseline file.  With a JDA_SCALE_* bit: JDA_UNSUPPORTED_FEATURE.  Taken by
+     * jda_decode_to_host / _ex / _flags (whole image); every other decode entry point -- jda_batch_create*, jda_pipeline_submit*,
+     * jda_node_submit* (per image, in status[]), jda_decode_to_host_rect / _bands / _strips / _oriented, jda_decode_dither_to_host and
+     * any call with an MCU rectangle -- answers JDA_UNSUPPORTED_FEATURE for a progressive file asked for with it. */
+    JDA_PROGRESSIVE_FULL = 256
 };
 
 /* ------------------------------------------------------------------ host front end */
@@ -91,6 +97,9 @@ typedef struct jda_image_info {
  * scan only, as a 1/8 thumbnail -- JPEG_SCALE_EIGHTH is OR-ed in (jpeg.inl:4964-4966) before the HALF / QUARTER /
  * EIGHTH chain (:4978-4990) picks the first bit that is set. */
 int32_t jda_effective_options(const jda_image_info *info, int32_t options);
+/* .. unless JDA_PROGRESSIVE_FULL is set: on a progressive file the bit is kept and JPEG_SCALE_EIGHTH is not OR-ed in; on a baseline
+ * file the bit is cleared.  1 when the effective options carry the bit (the shared refusal check of the paths that lack it). */
+int jda_progressive_full_requested(const jda_image_info *info, int32_t options);
 
 /* Header parse only.  Accept/reject rules follow JPEGParseInfo (jpeg.inl:1572-1785). */
 int jda_parse(const uint8_t *jpeg, int32_t len, jda_image_info *info);
@@ -492,6 +501,44 @@ int jda_node_wait(jda_node *node, int32_t ticket, int32_t *status);
 int jda_node_placement(const jda_node *node, int32_t k, int32_t *numa_node, int32_t *cpus_pinned);
 int jda_node_checksums(jda_node *node, int32_t n, const jda_output *surfaces, const int32_t *row_bytes, uint64_t *checksums);
 int jda_node_get_stats(const jda_node *node, jda_pipeline_stats *out);   /* sums over the devices' pipelines */
+
+/* ------------------------------------------------------------------ coefficient images (JDA_PROGRESSIVE_FULL, DCT-domain callers)
+ * A coefficient image is a file's geometry and prescaled quantisers plus one int16[64] per block: natural (row-major) order, entry 0
+ * the DC value, 128 bytes a block, 16-byte aligned, values modulo 2^16; blocks in the order of the per-block index (MCU-interleaved
+ * scan order, mcus_x * mcus_y * blocks_per_mcu of them) -- the decode kernel's LDS slot without its padding.
+ *   jda_progressive_prepare           every scan of a progressive (SOF2) file decoded on the host (T.81 Annex G): DC and AC, first passes and
+ *                                     refinements, EOB runs, spectral selection, restart intervals, DHT and DQT segments in front of and between the
+ *                                     scans -- Huffman tables are those in force at each SOS (ids 0-3 of either class; none of the baseline path's
+ *                                     table restrictions applies), a component's quantiser is latched at the first scan that names it (a table
+ *                                     defined or redefined behind that scan does not reach the component; none defined by then: JDA_DECODE_ERROR)
+ *                                     --, non-interleaved scans over the component's own extent -- ceil(w_c / 8) x ceil(h_c / 8) blocks, never the
+ *                                     MCU padding, whose blocks keep what the interleaved scans gave them.  The image's quantiser table c is
+ *                                     component c's (q_id = 0, 1, 2).  An invalid Huffman code, a scan naming an unknown component or table, a band
+ *                                     against the Ss / Se / Ah / Al rules: NULL with JDA_DECODE_ERROR, nothing delivered.  A file that ends (EOI
+ *                                     or end of data) behind at least one scan is valid and decodes to what its scans carry; where the data end
+ *                                     INSIDE a scan, that scan is read on as if zero bits followed (what libjpeg does with a truncated file).  A
+ *                                     baseline file: JDA_INVALID_PARAMETER.
+ *   jda_coef_image_from_coefficients  geometry and quantisers from the headers of any supported file, baseline or progressive; coefficients
+ *                                     from the caller (copied), n_blocks must match
+ *   jda_coef_image_quant              the four prescaled quantiser tables (4 x 64 int16, natural order); q_id (may be NULL): table of Y, Cb, Cr */
+typedef struct jda_coef_image jda_coef_image;
+jda_coef_image *jda_progressive_prepare(const uint8_t *jpeg, int32_t len, int32_t *err);
+jda_coef_image *jda_coef_image_from_coefficients(const uint8_t *jpeg, int32_t len, const int16_t *coefs, uint32_t n_blocks, int32_t *err);
+void jda_coef_image_free(jda_coef_image *img);
+const jda_image_info *jda_coef_image_get_info(const jda_coef_image *img);
+const int16_t *jda_coef_image_coefficients(const jda_coef_image *img, uint32_t *n_blocks);
+const int16_t *jda_coef_image_quant(const jda_coef_image *img, uint8_t *q_id);
+/* H2D of one coefficient image (quantisers + coefficients, one allocation), and the decode of n resident ones on the context's stream: ONE
+ * launch for the images of one MCU layout -- the kernel is a template over the layout, as the decode kernel is, so a call whose images mix
+ * layouts makes one launch per layout present, five at most -- (kernel jda_coef_tiles: dequantise, IDCT with the reference's column / row shortcuts -- driven by the occupancy
+ * flags JPEGDecodeMCU would have formed from these coefficients, jpeg.inl:2207-2208 --, colour conversion); synchronous like
+ * jda_orient_surfaces.  outputs as jda_batch_create; pixel_types: the four decode targets; options: JDA_LUMA_ONLY (and
+ * JDA_PROGRESSIVE_FULL, ignored); a scale bit: JDA_UNSUPPORTED_FEATURE -- full size only. */
+typedef struct jda_dev_coef jda_dev_coef;
+jda_dev_coef *jda_coef_upload(jda_ctx *ctx, const jda_coef_image *img, int32_t *err);
+void jda_dev_coef_free(jda_ctx *ctx, jda_dev_coef *dimg);
+int jda_coef_decode_surfaces(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types,
+                             const int32_t *options);
 
 const char *jda_version(void);
 

@@ -9,6 +9,7 @@ RGB565_LE, RGB565_BE, RGB8888, GRAY8 = 0, 1, 2, 3
 FOUR_BIT_DITHERED, TWO_BIT_DITHERED, ONE_BIT_DITHERED = 4, 5, 6      # made from a GRAY8 canvas: dither_surfaces / decode_dither_to_host
 DITHER_SEED_BYTES = 2184
 SCALE_HALF, SCALE_QUARTER, SCALE_EIGHTH, LUMA_ONLY = 2, 4, 8, 64
+PROGRESSIVE_FULL = 256      # ours: every scan of a progressive file at full size (decode_to_host); no effect on a baseline file
 AUTO_ROTATE = 1      # the class's decode() applies the EXIF orientation; the C-ABI takes it as an argument (decode_oriented_to_host, orient_surfaces)
 
 ERROR_NAMES = {0: "JDA_SUCCESS", 1: "JDA_INVALID_PARAMETER", 2: "JDA_DECODE_ERROR",
@@ -140,6 +141,16 @@ _PROTOTYPES = [
     ("jda_host_free", None, [_P]),
     ("jda_host_register", C.c_int, [_P, C.c_size_t]),
     ("jda_host_unregister", C.c_int, [_P]),
+    ("jda_progressive_full_requested", C.c_int, [C.POINTER(ImageInfo), C.c_int32]),
+    ("jda_progressive_prepare", _P, [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+    ("jda_coef_image_from_coefficients", _P, [C.c_char_p, C.c_int32, _P, C.c_uint32, C.POINTER(C.c_int32)]),
+    ("jda_coef_image_free", None, [_P]),
+    ("jda_coef_image_get_info", C.POINTER(ImageInfo), [_P]),
+    ("jda_coef_image_coefficients", _P, [_P, C.POINTER(C.c_uint32)]),
+    ("jda_coef_image_quant", _P, [_P, _P]),
+    ("jda_coef_upload", _P, [_P, _P, C.POINTER(C.c_int32)]),
+    ("jda_dev_coef_free", None, [_P, _P]),
+    ("jda_coef_decode_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 ]
 
 
@@ -621,6 +632,79 @@ def decode_to_host(ctx: Context, jpeg: bytes, pixel_type=RGB8888, options=0, out
     rc = ctx.lib.jda_decode_to_host(ctx.handle, jpeg, len(jpeg), pixel_type, options,
                                     canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0])
     return rc, canvas, g
+
+
+class CoefImage:
+    """A coefficient image (host): every scan of a progressive file decoded by jda_progressive_prepare, or -- coefs given -- the
+    caller's own coefficients under the headers of any supported file (jda_coef_image_from_coefficients).  coefs: int16,
+    (blocks, 64), natural order, blocks in MCU-interleaved scan order."""
+    def __init__(self, jpeg: bytes, coefs=None):
+        self.lib = load_library()
+        err = C.c_int32(0)
+        if coefs is None:
+            self.handle = self.lib.jda_progressive_prepare(jpeg, len(jpeg), C.byref(err))
+        else:
+            a = np.ascontiguousarray(coefs, dtype=np.int16).reshape(-1, 64)
+            self.handle = self.lib.jda_coef_image_from_coefficients(jpeg, len(jpeg), a.ctypes.data_as(_P), a.shape[0], C.byref(err))
+        if not self.handle:
+            raise JdaError(err.value, "jda_progressive_prepare" if coefs is None else "jda_coef_image_from_coefficients")
+        self.info = self.lib.jda_coef_image_get_info(self.handle).contents
+
+    def coefficients(self) -> np.ndarray:
+        n = C.c_uint32(0)
+        p = self.lib.jda_coef_image_coefficients(self.handle, C.byref(n))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), shape=(n.value, 64)).copy() if n.value else np.zeros((0, 64), np.int16)
+
+    def quant(self):
+        """(4 x 64 prescaled quantisers in natural order, table ids of Y / Cb / Cr)"""
+        ids = (C.c_uint8 * 3)()
+        p = self.lib.jda_coef_image_quant(self.handle, ids)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), shape=(4, 64)).copy(), list(ids)
+
+    def geometry(self, pixel_type=RGB8888, options=0):
+        return output_geometry(self.info, pixel_type, options | (PROGRESSIVE_FULL if self.info.jpeg_type == 1 else 0))
+
+    def close(self):
+        if self.handle:
+            self.lib.jda_coef_image_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def coef_decode(ctx: Context, images, pixel_types, options=None):
+    """jda_coef_upload + ONE jda_coef_decode_surfaces over all the images: [(canvas, geometry)] in MCU-padded host canvases."""
+    n = len(images)
+    options = list(options) if options is not None else [0] * n
+    geos = [im.geometry(pt, opt) for im, pt, opt in zip(images, pixel_types, options)]
+    pitch = [(g["canvas_w"] * g["bpp"] + 15) & ~15 for g in geos]
+    offs, total = [], 0
+    for g, p in zip(geos, pitch):
+        offs.append(total)
+        total += (p * g["canvas_h"] + 255) & ~255
+    devs, base = [], ctx.malloc(max(total, 256))
+    try:
+        for im in images:
+            err = C.c_int32(0)
+            d = ctx.lib.jda_coef_upload(ctx.handle, im.handle, C.byref(err))
+            if not d:
+                raise JdaError(err.value, "jda_coef_upload")
+            devs.append(d)
+        outs = (Output * n)(*[Output(base + offs[i], pitch[i], geos[i]["canvas_w"], geos[i]["canvas_h"]) for i in range(n)])
+        ctx.check(ctx.lib.jda_coef_decode_surfaces(ctx.handle, n, (_P * n)(*devs), outs, (C.c_int32 * n)(*pixel_types), (C.c_int32 * n)(*options)),
+                  "jda_coef_decode_surfaces")
+        res = []
+        for i, g in enumerate(geos):
+            res.append((ctx.to_host(base + offs[i], pitch[i] * g["canvas_h"]).reshape(g["canvas_h"], pitch[i])[:, : g["canvas_w"] * g["bpp"]].copy(), g))
+        return res
+    finally:
+        for d in devs:
+            ctx.lib.jda_dev_coef_free(ctx.handle, d)
+        ctx.free(base)
 
 
 def dither_geometry(canvas_w, canvas_h, pixel_type):

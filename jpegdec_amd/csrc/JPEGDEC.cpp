@@ -292,6 +292,7 @@ static bool enter_exif_thumbnail(jpegdec_amd_state *s, int &iOptions)
 static int decode_dither(jpegdec_amd_state *s, uint8_t *pDither, int iOptions)
 {
     s->options = iOptions;
+    iOptions &= ~JPEG_PROGRESSIVE_FULL;                      // (decodeDither ignores the bit)
     if (!s->opened || !pDither || s->pixel_type < FOUR_BIT_DITHERED || s->pixel_type > ONE_BIT_DITHERED) { s->error = JPEG_INVALID_PARAMETER; return 0; }
     if (s->framebuffer) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
     // JPEG_USES_DMA: the reference's strip buffer alternates between two halves after every draw (jpeg.inl:5073-5075, :5131, :5326) and its
@@ -379,18 +380,59 @@ static int decode_oriented(jpegdec_amd_state *s, int pt, int iOptions, int orien
     return 1;
 }
 
+// decode(JPEG_PROGRESSIVE_FULL) of a progressive file (ours: the reference decodes the first scan as a 1/8 thumbnail and nothing else): the
+// host decodes every scan into coefficient planes (jda_progressive_prepare), the GPU dequantises, transforms and colour-converts them in one
+// launch (jda_coef_decode_surfaces), and the full-size MCU-padded canvas comes back for the usual replay -- framebuffer layout, draw strips,
+// setMaxOutputSize and JPEG_USES_DMA as for a baseline file of that geometry.  JDA_DECODE_ERROR: the canvas is not written.
+static int decode_progressive_full(jda_ctx *ctx, jpegdec_amd_state *s, int pt, int iOptions, uint8_t *canvas, int cw, int ch, int bpp, int32_t *mcus_decoded)
+{
+    *mcus_decoded = 0;
+    int32_t err = JDA_SUCCESS;
+    jda_coef_image *ci = jda_progressive_prepare(s->data, s->size, &err);
+    if (!ci) return err;
+    jda_dev_coef *dc = jda_coef_upload(ctx, ci, &err);
+    jda_coef_image_free(ci);
+    if (!dc) return err;
+    const int dpitch = (cw * bpp + 15) & ~15;
+    void *surf = jda_malloc(ctx, (size_t)dpitch * ch);
+    int rc = surf ? JDA_SUCCESS : JDA_ERROR_MEMORY;
+    if (rc == JDA_SUCCESS) {
+        jda_output O;
+        O.pixels = surf; O.pitch_bytes = dpitch; O.width_px = cw; O.rows = ch;
+        const jda_dev_coef *one = dc;
+        const int32_t pt32 = pt, opt32 = iOptions;
+        rc = jda_coef_decode_surfaces(ctx, 1, &one, &O, &pt32, &opt32);
+    }
+    if (rc == JDA_SUCCESS) {
+        if (dpitch == cw * bpp) rc = jda_copy_to_host(ctx, canvas, surf, (size_t)dpitch * ch);
+        else {
+            std::vector<uint8_t> padded((size_t)dpitch * ch);
+            rc = jda_copy_to_host(ctx, padded.data(), surf, padded.size());
+            for (int r = 0; r < ch && rc == JDA_SUCCESS; r++) memcpy(canvas + (size_t)r * cw * bpp, padded.data() + (size_t)r * dpitch, (size_t)cw * bpp);
+        }
+    }
+    if (surf) jda_free(ctx, surf);
+    jda_dev_coef_free(ctx, dc);
+    if (rc == JDA_SUCCESS) *mcus_decoded = s->info.mcus_x * s->info.mcus_y;
+    return rc;
+}
+
 int JPEGDEC::decode(int x, int y, int iOptions)
 {
     jpegdec_amd_state *s = _jpeg;
     s->xoff = x; s->yoff = y; s->options = iOptions;
     if (!s->opened) { s->error = JPEG_INVALID_PARAMETER; return 0; }
     if (s->pixel_type > EIGHT_BIT_GRAYSCALE) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
+    // JPEG_PROGRESSIVE_FULL on a progressive file: every scan, full size (decode_progressive_full below)
+    const bool prog_full = jda_progressive_full_requested(&s->info, iOptions) != 0;
+    if (prog_full && (iOptions & JPEG_EXIF_THUMBNAIL)) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
     if ((iOptions & JPEG_EXIF_THUMBNAIL) && !enter_exif_thumbnail(s, iOptions)) return 0;   // jpeg.inl:4967-4976: decode the JPEG embedded in the EXIF block instead
     if (s->crop_w <= 0 || s->crop_h <= 0) { s->error = JPEG_INVALID_PARAMETER; return 0; }   // image smaller than one MCU / overhanging request (jpeg.inl:713-719 leaves w <= 0): nothing sane to deliver
     const bool cropped = s->crop_x != 0 || s->crop_y != 0 || s->crop_w != s->info.width || s->crop_h != s->info.height;
     int pt = s->pixel_type;
     if ((iOptions & JPEG_LUMA_ONLY) && pt < EIGHT_BIT_GRAYSCALE) pt = s->pixel_type = EIGHT_BIT_GRAYSCALE;   // jpeg.inl:4991-4993
     // JPEG_AUTO_ROTATE with an EXIF orientation that changes anything (of what is being decoded: a thumbnail without one has the main image's)
+    if (prog_full && (cropped || ((iOptions & JPEG_AUTO_ROTATE) && s->info.orientation >= 2 && s->info.orientation <= 8))) { s->error = JPEG_UNSUPPORTED_FEATURE; return 0; }
     if ((iOptions & JPEG_AUTO_ROTATE) && s->info.orientation >= 2 && s->info.orientation <= 8) return decode_oriented(s, pt, iOptions, s->info.orientation, cropped);
     int bpp, ow, oh, cw, ch;
     int rc = jda_output_geometry(&s->info, pt, iOptions, &bpp, &ow, &oh, &cw, &ch);
@@ -405,7 +447,7 @@ int JPEGDEC::decode(int x, int y, int iOptions)
     // Framebuffer mode, full size, no crop, a width that is a whole number of MCUs: the caller's buffer has the layout of the
     // decoded canvas (pitch = width, MCU-padded rows: what the reference writes, jpeg.inl:5114-5124), so the copy back from the
     // GPU lands in it directly -- no intermediate canvas, no second copy
-    if (s->framebuffer && !cropped && shift0 == 0 && cw == s->info.width && s->crop_w == s->info.width) {
+    if (s->framebuffer && !prog_full && !cropped && shift0 == 0 && cw == s->info.width && s->crop_w == s->info.width) {
         // (a stream with a bad MCU: the MCUs in front of it land in the framebuffer, the rest of it is left alone -- the reference returns there)
         rc = jda_decode_to_host_flags(ctx, s->data, s->size, pt, iOptions, NULL, s->framebuffer, cw * bpp, ch, &mcus_decoded, NULL, JDA_TO_HOST_KEEP_UNDECODED);
         if (rc != JDA_SUCCESS && rc != JDA_DECODE_ERROR) { s->error = rc; return 0; }
@@ -413,7 +455,7 @@ int JPEGDEC::decode(int x, int y, int iOptions)
         return 1;
     }
     const size_t canvas_bytes = (size_t)cw * ch * bpp;
-    const bool banded = !s->framebuffer && s->draw && !cropped && canvas_bytes >= ((size_t)2 << 20);      // a large image with draw callbacks
+    const bool banded = !prog_full && !s->framebuffer && s->draw && !cropped && canvas_bytes >= ((size_t)2 << 20);      // a large image with draw callbacks
     if (banded && s->pinned_cap < canvas_bytes) {
         if (s->pinned_canvas) jda_host_free(s->pinned_canvas);
         s->pinned_canvas = (uint8_t *)jda_host_alloc(canvas_bytes + canvas_bytes / 8);
@@ -573,6 +615,9 @@ int JPEGDEC::decode(int x, int y, int iOptions)
         else
         rc = jda_decode_to_host_bands(ctx, s->data, s->size, pt, iOptions, NULL, canvas, cw * bpp, ch, &mcus_decoded, NULL, 0, JDA_MAX_REPLAY_BANDS,
                                       [](void *u, int32_t, int32_t row1) { Trampoline *t = (Trampoline *)u; *t->partial = *t->decoded < t->total; (*t->fn)(row1); }, &tr);
+    } else if (prog_full) {
+        rc = decode_progressive_full(ctx, s, pt, iOptions, canvas, cw, ch, bpp, &mcus_decoded);
+        if (rc == JDA_DECODE_ERROR) { s->error = JPEG_DECODE_ERROR; return 0; }      // a scan that cannot be decoded: nothing is delivered
     } else
     rc = jda_decode_to_host_rect(ctx, s->data, s->size, pt, iOptions, cropped ? rect : NULL, canvas, cw * bpp, ch, &mcus_decoded, NULL);
     // the reference walks the MCU rows down to the crop's bottom only (jpeg.inl:5014-5037): a bad MCU below it is never met

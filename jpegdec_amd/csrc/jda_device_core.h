@@ -3415,4 +3415,113 @@ template <int BPP, class IO> JDA_HD void jda_orient_emit(const jda_orient_geo &G
     }
 }
 
+// ================================================================================================
+// jda_coef_tiles: a tile decoded from COEFFICIENTS (a coefficient image: every scan of a progressive file decoded on the host, or a
+// DCT-domain caller's own).  The tile is the decode kernel's -- one wave64, <= 64 consecutive blocks of an MCU row,
+// the same LDS slots --, and P1 is replaced by a load phase:
+//   load    lane = 16-byte chunk = one row of a block's 8x8 coefficients (natural order, 128 bytes a block in HBM): the tile's
+//           blocks are consecutive there, so a pass of 64 lanes is 1 KiB of coalesced 16-byte loads; all eight passes are issued,
+//           without a branch between them, before the first one is stored (in the compiled code the waits count down at the
+//           stores: read off the ISA, profiles/progressive_code_object.txt, not timed).  A chunk goes into its block's slot (two 8-byte LDS
+//           stores: the slots are 136 bytes apart, 8-byte aligned), and while it passes through registers its share of the block's
+//           u16MCUFlags is formed as JPEGDecodeMCU would have (jpeg.inl:2207-2208, :2253-2254): for every nonzero AC coefficient
+//           at natural index n, (1 << (n & 7)) | (n << 8) -- one uint16 per chunk, parked where the column list will be;
+//   flags   lane = block: the OR of its eight chunk words (one 16-byte LDS read).  0 = DC only (:5146-5154).
+// (The LDS stores' bank pattern -- 16 bytes a lane, a 136-byte step every eight lanes -- has not been measured nor run through a conflict
+// counter: tests/hostsim/coef_sim.cpp checks addresses and values, not banks.)
+// In a baseline stream those flags depend only on which positions hold a coded (hence nonzero) coefficient, so equal coefficients
+// give equal pixels.  Behind the flags come the decode kernel's own list, column, row and colour stages (jda_p1_lists .. jda_p4_output),
+// every multiply in 32 bits.  The table copy in LDS holds what those stages read: the nibble lists and the four quantiser tables.
+#define JDA_CT_TAB_BYTES 2048u                               // (JDA_LT_NIB and JDA_LT_QUANT_OFF(0..3) lie below 1,792)
+#define JDA_CT_QUANT_BYTES 512u                              // a coefficient image's table blob in HBM: 4 x 64 int16, prescaled, natural order
+#define JDA_CT_BLOCK_BYTES 128u
+template <int MODE> struct jda_ct_layout {
+    enum { WAVE_BYTES = (JDA_CT_TAB_BYTES + jda_lds_layout<MODE>::BASE_BYTES + 15) / 16 * 16 };
+};
+
+// io.ld128(base, i, v): the i-th 16-byte vector behind the global pointer `base` (16-byte aligned).  Every load of the load phase is
+// UNCONDITIONAL (a lane with nothing to fetch re-reads a vector that is there): no branch between the loads, so they are issued back to
+// back (what the compiled code shows; no timing behind it).
+template <class IO> JDA_HD void jda_ct_tables(IO &io, const uint8_t *quant, uint32_t lane, uint8_t *tab)
+{
+    uint32_t v[4];
+    io.ld128(quant, lane & (JDA_CT_QUANT_BYTES / 16u - 1u), v);
+    if (lane < JDA_CT_QUANT_BYTES / 16u) {
+        jda_u32_alias *dst = (jda_u32_alias *)(tab + JDA_LT_QUANT_OFF(lane >> 3) + 16u * (lane & 7u));
+        dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
+    } else if (lane < JDA_CT_QUANT_BYTES / 16u + 2u) {      // the 16 nibble lists (as jda_p0_tables_from makes them)
+        const uint32_t i = lane - JDA_CT_QUANT_BYTES / 16u;
+        jda_u32_alias *dst = (jda_u32_alias *)(tab + JDA_LT_NIB + 16u * i);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) dst[k] = jda_nibble_list(i * 8u + 2u * k) | (jda_nibble_list(i * 8u + 2u * k + 1u) << 16);
+    }
+}
+
+// what the list and column stages need of jda_lane_pre: the lane's quantiser table and its column work item
+template <int MODE> JDA_HD void jda_ct_lane_prepare(jda_lane_pre &LP, const jda_dev_desc &D, uint32_t lane)
+{
+    typedef jda_mode_traits<MODE> T;
+    const uint32_t b = lane % (uint32_t)T::NBLK;
+    const uint32_t c = b < (uint32_t)T::NLUMA ? 0u : b - T::NLUMA + 1u;
+    const uint32_t q_id = jda_pick3(D.q_id, c) & 3u;
+    LP.dc_off = 0; LP.ac_off = 0; LP.ac_long_off = 0; LP.eob_sh = 0; LP.eob_code = 0;
+    LP.quant_off = JDA_LT_QUANT_OFF(q_id);
+    LP.qsel = (JDA_LT_QUANT_OFF(q_id) >> 7) << 10;
+    LP.item_pre = LP.qsel | (lane << 4);
+    LP.chroma = b >= (uint32_t)T::NLUMA ? 1u : 0u;
+}
+
+// the flag word of row `row` of a block: v = its eight int16, two to a dword
+JDA_HD uint32_t jda_ct_row_flags(const uint32_t v[4], uint32_t row)
+{
+    uint32_t cols = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        if (v[j] & 0xffffu) cols |= 1u << (2u * j);
+        if (v[j] >> 16) cols |= 2u << (2u * j);
+    }
+    if (row == 0u) cols &= ~1u;                              // (entry 0 is the DC value: no flag)
+    if (cols == 0u) return 0u;
+    // OR of n = 8 row + column over the nonzero ones: the row's bits, and bit k of the OR of the columns
+    const uint32_t orn = (row << 3) | ((cols & 0xaau) ? 1u : 0u) | ((cols & 0xccu) ? 2u : 0u) | ((cols & 0xf0u) ? 4u : 0u);
+    return cols | (orn << 8);
+}
+
+// D.scan: the image's coefficients (16-byte aligned).  C: first_block / count of the tile (count >= 1).
+template <int MODE, class IO> JDA_HD void jda_ct_load(IO &io, const jda_dev_desc &D, const jda_tile_ctx &C, uint32_t lane, uint8_t *wl)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_lds_layout<MODE> L;
+    const uint32_t n_chunks = C.count * (uint32_t)T::NBLK * 8u;
+    const uint32_t c0 = C.first_block * 8u;                  // the tile's first chunk among the image's
+    uint32_t v[8][4];
+#pragma unroll
+    for (uint32_t p = 0; p < 8; p++) {
+        const uint32_t c = p * 64u + lane;
+        io.ld128(D.scan, c0 + (c < n_chunks ? c : 0u), v[p]);
+    }
+    uint16_t *cw = (uint16_t *)(wl + L::COLLIST_OFF);
+#pragma unroll
+    for (uint32_t p = 0; p < 8; p++) {
+        const uint32_t c = p * 64u + lane, blk = c >> 3, row = c & 7u;
+        if (c >= n_chunks) continue;
+        jda_u64_alias *dst = (jda_u64_alias *)(wl + L::COEF_OFF + blk * JDA_COEF_STRIDE + row * 16u);
+        dst[0] = (uint64_t)v[p][0] | ((uint64_t)v[p][1] << 32);
+        dst[1] = (uint64_t)v[p][2] | ((uint64_t)v[p][3] << 32);
+        cw[c] = (uint16_t)jda_ct_row_flags(v[p], row);
+    }
+}
+
+// lane = block: its u16MCUFlags (0 = DC only), or JDA_NO_LIST (no block, chroma of a luma-only decode)
+template <int MODE> JDA_HD uint32_t jda_ct_flags(const jda_dev_desc &D, const jda_tile_ctx &C, const jda_lane_pre &LP, uint32_t lane, const uint8_t *wl)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_lds_layout<MODE> L;
+    if (lane >= C.count * (uint32_t)T::NBLK) return JDA_NO_LIST;
+    if (MODE != JDA_MODE_GRAY && D.gray_from_color && LP.chroma) return JDA_NO_LIST;
+    const jda_u32_alias *w = (const jda_u32_alias *)(wl + L::COLLIST_OFF + 16u * lane);
+    const uint32_t f = w[0] | w[1] | w[2] | w[3];
+    return (f | (f >> 16)) & 0xffffu;
+}
+
 #endif // JDA_DEVICE_CORE_H

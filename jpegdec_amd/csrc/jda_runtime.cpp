@@ -639,6 +639,7 @@ int jda_fill_launch_desc(jda_dev_desc &D, const jda_image_info &I, const uint8_t
 {
     const int opt = jda_effective_options(&I, options);      // progressive: 1/8 thumbnail from the DC scan
     memset(&D, 0, sizeof(D));
+    if (jda_progressive_full_requested(&I, options)) return JDA_UNSUPPORTED_FEATURE;      // every scan of a progressive file: jda_decode_to_host only
     if (pt_req < 0 || pt_req > JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
     int pt = pt_req;
     if ((opt & JDA_LUMA_ONLY) && pt < JDA_EIGHT_BIT_GRAYSCALE) pt = JDA_EIGHT_BIT_GRAYSCALE;   // jpeg.inl:4991-4993
@@ -901,9 +902,151 @@ int jda_decode_to_host_rect(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int3
     return jda_decode_to_host_flags(ctx, jpeg, len, pixel_type, options, mcu_rect, host_pixels, pitch_bytes, rows, mcus_decoded, tiles, 0);
 }
 
+// ---- coefficient images (jda_coef_tiles in jda_kernels.hip)
+jda_dev_coef *jda_coef_upload(jda_ctx *ctx, const jda_coef_image *img, int32_t *err)
+{
+    int32_t dummy;
+    if (!err) err = &dummy;
+    if (!ctx) { *err = JDA_ERROR_NO_DEVICE; return NULL; }
+    if (!img) { *err = JDA_INVALID_PARAMETER; return NULL; }
+    (void)hipSetDevice(ctx->device);
+    jda_dev_coef *d = new (std::nothrow) jda_dev_coef;
+    if (!d) { *err = JDA_ERROR_MEMORY; return NULL; }
+    memset(d, 0, sizeof(*d));
+    d->info = *jda_coef_image_get_info(img);
+    const int16_t *coefs = jda_coef_image_coefficients(img, &d->n_blocks);
+    const int16_t *quant = jda_coef_image_quant(img, d->q_id);
+    d->bytes = JDA_CT_QUANT_BYTES + align16((size_t)d->n_blocks * JDA_CT_BLOCK_BYTES);
+    hipError_t e = jda_pool_alloc(ctx, (void **)&d->base, d->bytes);
+    if (e != hipSuccess) { delete d; jda_set_err(ctx, e, "hipMalloc(coefficient image)"); *err = JDA_ERROR_MEMORY; return NULL; }
+    e = hipMemcpyAsync(d->base, quant, JDA_CT_QUANT_BYTES, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && d->n_blocks) e = hipMemcpyAsync(d->base + JDA_CT_QUANT_BYTES, coefs, (size_t)d->n_blocks * JDA_CT_BLOCK_BYTES, hipMemcpyHostToDevice, ctx->stream);
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }      // (the image's host memory is the caller's again)
+    if (e != hipSuccess) { jda_pool_free(ctx, d->base); delete d; jda_set_err(ctx, e, "jda_coef_upload"); *err = JDA_ERROR_HIP; return NULL; }
+    *err = JDA_SUCCESS;
+    return d;
+}
+
+void jda_dev_coef_free(jda_ctx *ctx, jda_dev_coef *d)
+{
+    if (!d) return;
+    if (d->base) { if (ctx) { (void)hipSetDevice(ctx->device); jda_pool_free(ctx, d->base); } else (void)hipFree(d->base); }
+    delete d;
+}
+
+// descriptors and tile lists of n coefficient images -> one pool block (descs | the lists of the five layouts), uploaded and waited for (the
+// records leave pageable memory that goes away with this frame); coef_launch then queues the kernels: one launch per layout present
+struct coef_plan { uint8_t *block; size_t off[JDA_N_MODES]; uint32_t n_tiles[JDA_N_MODES]; };
+static int coef_upload_plan(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types, const int32_t *options, coef_plan *plan)
+{
+    memset(plan, 0, sizeof(*plan));
+    std::vector<jda_dev_desc> descs((size_t)n);
+    std::vector<jda_strip> strips[JDA_N_MODES];
+    for (int i = 0; i < n; i++) {
+        const jda_dev_coef *im = imgs[i];
+        if (!im) return JDA_INVALID_PARAMETER;
+        jda_image_info I = im->info;
+        I.jpeg_type = 0;                                   // (coefficients of every scan: geometry and rules of a baseline file of this SOF)
+        const int opt = (options ? options[i] : 0) & ~JDA_PROGRESSIVE_FULL;
+        if (opt & (JDA_SCALE_HALF | JDA_SCALE_QUARTER | JDA_SCALE_EIGHTH)) return JDA_UNSUPPORTED_FEATURE;      // full size only
+        const uint8_t no_huff[3] = { 0, 0, 0 };
+        jda_dev_desc &D = descs[(size_t)i];
+        const int rc = jda_fill_launch_desc(D, I, no_huff, no_huff, im->q_id, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, outputs[i],
+                                            pixel_types ? pixel_types[i] : JDA_RGB8888, opt, NULL);
+        if (rc != JDA_SUCCESS) return rc;
+        D.pad_[0] = 0;
+        D.tables = im->base;
+        D.scan = im->base + JDA_CT_QUANT_BYTES;
+        jda_append_strips(strips[D.mode], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+    }
+    size_t bytes = align16(descs.size() * sizeof(jda_dev_desc));
+    for (int m = 0; m < JDA_N_MODES; m++) { plan->off[m] = bytes; plan->n_tiles[m] = (uint32_t)strips[m].size(); bytes += align16(strips[m].size() * sizeof(jda_strip)); }
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, bytes);
+    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(coefficient plan)");
+    e = hipMemcpyAsync(blk, descs.data(), descs.size() * sizeof(jda_dev_desc), hipMemcpyHostToDevice, ctx->stream);
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess; m++)
+        if (!strips[m].empty()) e = hipMemcpyAsync(blk + plan->off[m], strips[m].data(), strips[m].size() * sizeof(jda_strip), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { jda_pool_free(ctx, blk); return jda_set_err(ctx, e, "coefficient plan"); }
+    plan->block = blk;
+    return JDA_SUCCESS;
+}
+static int coef_launch(jda_ctx *ctx, const coef_plan &plan)
+{
+    hipError_t e = hipSuccess;
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess; m++)
+        if (plan.n_tiles[m]) e = jda_launch_coef_tiles(m, (const jda_dev_desc *)plan.block, (const jda_strip *)(plan.block + plan.off[m]), plan.n_tiles[m], ctx->stream);
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_coef_tiles");
+}
+
+int jda_coef_decode_surfaces(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types,
+                             const int32_t *options)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    if (!imgs || !outputs) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    coef_plan plan;
+    int rc = coef_upload_plan(ctx, n, imgs, outputs, pixel_types, options, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = coef_launch(ctx, plan);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, plan.block);
+    if (rc != JDA_SUCCESS) return rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_coef_decode_surfaces");
+}
+
+// jda_decode_to_host* with JDA_PROGRESSIVE_FULL on a progressive file: every scan on the host, the coefficients to the GPU, the canvas back
+static int progressive_full_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options,
+                                    void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded)
+{
+    if (!jpeg || !host_pixels) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    int32_t err = JDA_SUCCESS;
+    jda_coef_image *img = jda_progressive_prepare(jpeg, len, &err);
+    if (!img) return err;                                 // JDA_DECODE_ERROR: nothing decoded, the canvas untouched
+    const jda_image_info I = *jda_coef_image_get_info(img);
+    int bpp, ow, oh, cw, ch;
+    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
+    if (rc != JDA_SUCCESS) { jda_coef_image_free(img); return rc; }
+    jda_dev_coef *dimg = jda_coef_upload(ctx, img, &err);
+    jda_coef_image_free(img);
+    if (!dimg) return err;
+    const int dpitch = (int)align16((size_t)cw * bpp), drows = rows < ch ? rows : ch;
+    void *dout = NULL;
+    if (jda_pool_alloc(ctx, &dout, (size_t)dpitch * ch) != hipSuccess) { jda_dev_coef_free(ctx, dimg); return JDA_ERROR_MEMORY; }
+    jda_output O;
+    O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = cw; O.rows = drows;
+    coef_plan plan;
+    const jda_dev_coef *one = dimg;
+    rc = coef_upload_plan(ctx, 1, &one, &O, &pixel_type, &options, &plan);
+    if (rc == JDA_SUCCESS) rc = coef_launch(ctx, plan);
+    if (rc == JDA_SUCCESS && drows > 0) {
+        const size_t row_bytes = (size_t)cw * bpp < (size_t)pitch_bytes ? (size_t)cw * bpp : (size_t)pitch_bytes;
+        hipError_t e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, row_bytes, (size_t)drows, hipMemcpyDeviceToHost, ctx->stream);
+        { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+        if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+    } else (void)hipStreamSynchronize(ctx->stream);
+    if (plan.block) jda_pool_free(ctx, plan.block);
+    jda_pool_free(ctx, dout);
+    jda_dev_coef_free(ctx, dimg);
+    if (rc == JDA_SUCCESS && mcus_decoded) *mcus_decoded = I.mcus_x * I.mcus_y;
+    return rc;
+}
+
 int jda_decode_to_host_flags(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *mcu_rect,
                              void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded, int32_t *tiles, int32_t flags)
 {
+    if (ctx && !mcu_rect && (options & JDA_PROGRESSIVE_FULL)) {      // (a baseline file: the bit means nothing, the usual path)
+        jda_image_info I;
+        if (jda_parse(jpeg, len, &I) == JDA_SUCCESS && jda_progressive_full_requested(&I, options)) {
+            if (mcus_decoded) *mcus_decoded = 0;
+            if (tiles) tiles[0] = tiles[1] = 0;
+            return progressive_full_to_host(ctx, jpeg, len, pixel_type, options, host_pixels, pitch_bytes, rows, mcus_decoded);
+        }
+    }
     return jda_decode_to_host_bands(ctx, jpeg, len, pixel_type, options, mcu_rect, host_pixels, pitch_bytes, rows, mcus_decoded, tiles, flags, 1, NULL, NULL);
 }
 

@@ -52,6 +52,14 @@ struct jda_dev_image {
     uint8_t *tables_host;     // a host copy of the tables (JDA_TABLE_BYTES): a launch plan lets consecutive images with equal tables share the first one's copy
 };
 
+struct jda_dev_coef {
+    uint8_t *base;            // one allocation: quantisers (JDA_CT_QUANT_BYTES) | coefficients (n_blocks x 128 bytes)
+    size_t bytes;
+    jda_image_info info;
+    uint8_t q_id[3];
+    uint32_t n_blocks;
+};
+
 struct jda_batch {
     int32_t n_images;
     jda_dev_desc *d_descs;
@@ -118,6 +126,8 @@ extern "C" hipError_t jda_launch_prescan_passes_ex(const jda_segscan_params *par
 // aux: JDA_LIST_THUMB_FLAT: the most items an image of the batch's flat lists has (jda_flat_items); 0 otherwise
 extern "C" hipError_t jda_launch_decode(int mode, int fast_mul, int variant, int big, int cont, const jda_dev_desc *descs, const jda_strip *strips,
                                         uint32_t n_strips, uint32_t aux, hipStream_t stream);
+// tiles of coefficient images of one MCU layout (descs[i].scan: coefficients, .tables: JDA_CT_QUANT_BYTES of quantisers): jda_coef_tiles<mode>
+extern "C" hipError_t jda_launch_coef_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
 inline uint32_t jda_flat_items(const jda_dev_desc &D) { return (D.mode == JDA_MODE_GRAY ? (D.mcus_x + 3u) >> 2 : D.mcus_x) * D.mcus_y; }      // quads of blocks (gray) / MCUs
 
 #endif
