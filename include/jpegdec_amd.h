@@ -517,6 +517,8 @@ int jda_node_get_stats(const jda_node *node, jda_pipeline_stats *out);   /* sums
  *                                     against the Ss / Se / Ah / Al rules: NULL with JDA_DECODE_ERROR, nothing delivered.  A file that ends (EOI
  *                                     or end of data) behind at least one scan is valid and decodes to what its scans carry; where the data end
  *                                     INSIDE a scan, that scan is read on as if zero bits followed (what libjpeg does with a truncated file).  A
+ *                                     first-pass value whose point transform leaves int16 (value << Al, DC or AC: no 8-bit encoder writes one) is
+ *                                     kept modulo 2^16, as every coefficient of the image is: defined at coefficient level, no pixels promised.  A
  *                                     baseline file: JDA_INVALID_PARAMETER.
  *   jda_coef_image_from_coefficients  geometry and quantisers from the headers of any supported file, baseline or progressive; coefficients
  *                                     from the caller (copied), n_blocks must match

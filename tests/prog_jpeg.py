@@ -5,7 +5,9 @@ restart markers and unstuffed as a whole, and the bits are read from the unstuff
 shape of tests/coef_jpeg.decode_coefs: per component a (block rows, block columns, 64) array in ZIG-ZAG order over the whole MCU
 grid, entry 0 the DC value -- so that coef_jpeg.write_jpeg can re-encode it as a baseline file with the same quantisers.
 
-  decode_coefs(jpeg)   -> dict(width, height, sampling, coefs, quant, quant_ids, restart_interval, n_scans, scan_ends)
+  decode_coefs(jpeg)   -> dict(width, height, sampling, coefs, quant, quant_ids, quant_latched, restart_interval, n_scans, scan_ends)
+                          quant: the DQT contents at the end of the file; quant_latched[c]: component c's table as it stood at the
+                          first scan that names c (None: never named, or no table then)
                           scan_ends[k]: the file offset just behind scan k's entropy-coded bytes (where a file may be cut)
 """
 import numpy as np
@@ -120,6 +122,7 @@ def decode_coefs(jpeg):
             cx, cy, shapes, (hs, vs) = geometry(w, h, sampling)
             coefs = [np.zeros((r, c, 64), dtype=np.int64) for r, c in shapes]
             frame = (w, h, comps)
+            latched = [None] * nc
             # a component's own extent in blocks (A.1.1): what a non-interleaved scan visits
             own = []
             for k in range(nc):
@@ -129,13 +132,17 @@ def decode_coefs(jpeg):
         elif m == 0xDA:
             if frame is None:
                 raise DecodeError("SOS before SOF")
+            for k in range(seg[0]):                        # a component's quantiser is the one in force at the first scan that names it
+                for c, comp in enumerate(frame[2]):
+                    if comp[0] == seg[1 + 2 * k] and latched[c] is None:
+                        latched[c] = list(quant[comp[2]]) if comp[2] in quant else None
             _scan(jpeg, seg, ent, frame, (cx, cy, hs, vs), own, coefs, huff, dri)
             scan_ends.append(ent[1])
     if not scan_ends:
         raise DecodeError("no scan")
     w, h, comps = frame
     return dict(width=w, height=h, sampling=sampling, coefs=coefs, quant=quant, quant_ids=[c[2] for c in comps],
-                restart_interval=dri, n_scans=len(scan_ends), scan_ends=scan_ends)
+                quant_latched=latched, restart_interval=dri, n_scans=len(scan_ends), scan_ends=scan_ends)
 
 
 def _scan(jpeg, seg, ent, frame, grid, own, coefs, huff, dri):
@@ -149,8 +156,10 @@ def _scan(jpeg, seg, ent, frame, grid, own, coefs, huff, dri):
             raise DecodeError("unknown component")
         members.append((ids[seg[1 + 2 * k]], seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15))
     ss, se, ah, al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
-    if ss > se or se > 63 or (ss == 0 and se != 0) or (ss > 0 and ns != 1) or (ah and al != ah - 1):
+    if ss > se or se > 63 or (ss == 0 and se != 0) or (ss > 0 and ns != 1) or al > 13 or (ah and al != ah - 1):
         raise DecodeError("band")
+    if any(a[0] >= b[0] for a, b in zip(members, members[1:])):
+        raise DecodeError("components out of frame order, or one named twice (B.2.3)")
     # restart intervals: cut the entropy-coded bytes at the RSTn markers
     raw = jpeg[ent[0]:ent[1]]
     pieces, a, j = [], 0, 0

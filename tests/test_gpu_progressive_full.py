@@ -2,7 +2,8 @@
 call with the bit, the class and the C flavour, the default behaviour without the bit, and the refusals.
 
 Every comparison is bit-exact.  Expected pixels of a progressive file: tests/prog_jpeg (pure Python) -> coef_jpeg.write_jpeg (baseline,
-same DQT, no truncation event: asserted) -> the oracle (tests/prog_cases.py).  This file sorts before test_gpu_zz_kernel_coverage.py, which
+same DQT, no truncation event: asserted) -> the oracle (tests/prog_cases.py: Pillow's files; tests/prog_scripts.py: files written under
+other scan scripts by tests/prog_write.py, every MCU layout among them).  This file sorts before test_gpu_zz_kernel_coverage.py, which
 holds the process to every kernel of the code object: (a) below launches all five jda_coef_tiles instantiations."""
 import ctypes as C
 import os
@@ -13,12 +14,13 @@ import pytest
 
 import jpegdec_amd as J
 from oracle.loader import RefDecoder
-from tests import prog_cases as PC
+from tests import prog_cases as PC, prog_scripts as PS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FULL = J.PROGRESSIVE_FULL
 NAMES = sorted(PC.CASES)
+WRITTEN = PS.NAMES + PS.LONG_NAMES
 MODES = ((J.RGB8888, 0), (J.RGB565_LE, 0), (J.RGB565_BE, 0), (J.GRAY8, 0), (J.RGB565_LE, J.LUMA_ONLY))
 
 
@@ -94,12 +96,12 @@ def test_coef_decode_surfaces_arguments(gpu_ctx, oracle):
 
 
 # ---- (b) the one call with the bit ----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + WRITTEN)
 def test_one_call_with_the_bit(name, gpu_ctx, oracle):
-    pj = PC.files(name)[0]
-    base, events = PC.reencoded(name)
+    pj = PS.files(name)[0]
+    base, events = PS.reencoded(name)
     assert events == 0, "the re-encoded baseline has %d truncation events" % events
-    for pt, opt in MODES:
+    for pt, opt in MODES[:1] if name in PS.LONG_NAMES else MODES:
         orc, want, err = oracle.decode_canvas(base, pt, opt)
         rc, got, g = J.decode_to_host(gpu_ctx, pj, pt, opt | FULL)
         assert orc == 1 and rc == 0 and got.shape == want.shape, (name, pt, opt, rc)
@@ -113,7 +115,7 @@ def test_one_call_with_the_bit(name, gpu_ctx, oracle):
     assert rc == 0 and nok.value == info.mcus_x * info.mcus_y
     assert np.array_equal(part, want[:part.shape[0], :part.shape[1]])
     # on the baseline twin the bit changes nothing
-    tw = PC.files(name)[1]
+    tw = PS.files(name)[1]
     rc, got, g = J.decode_to_host(gpu_ctx, tw, J.RGB8888, FULL)
     assert rc == 0 and np.array_equal(got, oracle.decode_canvas(tw, J.RGB8888, 0)[1])
 
@@ -156,13 +158,13 @@ def test_a_scan_that_cannot_be_decoded_delivers_nothing(gpu_ctx):
 
 
 # ---- (c) the class and the C flavour ----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["gray_200x136_q85", "c444_333x217_q85", "c422_200x136_q50_rst", "c420_640x368_q85", "c420_17x9_q85_rst"])
+@pytest.mark.parametrize("name", ["gray_200x136_q85", "c444_333x217_q85", "c422_200x136_q50_rst", "c420_640x368_q85", "c420_17x9_q85_rst"] + PS.ONE_PER_LAYOUT)
 def test_class_framebuffer_and_callbacks(name, product_class, oracle, gpu_ctx):
-    pj = PC.files(name)[0]
-    base, events = PC.reencoded(name)
+    pj = PS.files(name)[0]
+    base, events = PS.reencoded(name)
     assert events == 0
     for pt, opt, max_mcus in ((J.RGB565_LE, 0, 0), (J.RGB8888, 0, 3), (J.GRAY8, 0, 0), (J.RGB565_BE, 128, 0), (J.RGB565_LE, 64, 0)):
-        if name.startswith("gray") and pt == J.RGB8888:
+        if PS.decoded(name)["sampling"] == "gray" and pt == J.RGB8888:
             continue
         orc, want, err = oracle.decode_canvas(base, pt, opt & 64)
         g = J.output_geometry(_info(base), pt, opt & 64)
@@ -198,16 +200,16 @@ def test_class_refusals(product_class, gpu_ctx):
     assert rc == 0 and product_class.last_error == 2 and bool((fb == 0x5A).all())
 
 
-@pytest.mark.parametrize("name", ["gray_200x136_q85", "c420_333x217_q98", "c444_17x9_q50"])
+@pytest.mark.parametrize("name", ["gray_200x136_q85", "c420_333x217_q98", "c444_17x9_q50"] + PS.ONE_PER_LAYOUT)
 def test_c_flavour(name, prog_user, oracle, gpu_ctx, tmp_path):
     """JPEG_decode with JPEG_PROGRESSIVE_FULL from a plain C program: callbacks (log == the oracle's draw plan of the re-encoded baseline,
     pixels == the expected ones) and framebuffer mode"""
-    pj = PC.files(name)[0]
-    base, events = PC.reencoded(name)
+    pj = PS.files(name)[0]
+    base, events = PS.reencoded(name)
     assert events == 0
     f = tmp_path / "p.jpg"
     f.write_bytes(pj)
-    for pt in (J.RGB565_LE, J.GRAY8) + (() if name.startswith("gray") else (J.RGB8888,)):
+    for pt in (J.RGB565_LE, J.GRAY8) + (() if PS.decoded(name)["sampling"] == "gray" else (J.RGB8888,)):
         g = J.output_geometry(_info(base), pt, 0)
         orc, want, err = oracle.decode_canvas(base, pt, 0)
         out, log = tmp_path / "o.bin", tmp_path / "l.txt"
@@ -232,13 +234,18 @@ def test_c_flavour(name, prog_user, oracle, gpu_ctx, tmp_path):
 
 
 # ---- (d) without the bit: the 1/8 thumbnail, byte for byte ------------------------------------------------------------------------
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + PS.NAMES)
 def test_without_the_bit_nothing_changes(name, gpu_ctx, oracle):
-    pj = PC.files(name)[0]
-    gray = name.startswith("gray")
+    """a written file too gets what the reference gives it: the thumbnail of its first scan -- whatever that scan is (Y alone in split_dc and
+    pair) -- or the reference's refusal (tables: DC table ids 2 and 3 in the header)"""
+    pj = PS.files(name)[0]
+    gray = PS.decoded(name)["sampling"] == "gray"
     for pt, opt in ((J.RGB8888, 0), (J.RGB565_LE, 0), (J.RGB565_BE, J.SCALE_HALF), (J.RGB565_LE, J.SCALE_EIGHTH)) + (((J.GRAY8, 0),) if gray else ()):
         orc, want, err = oracle.decode_canvas(pj, pt, opt)
         rc, got, g = J.decode_to_host(gpu_ctx, pj, pt, opt)
+        if name in PS.NEW and PS.NEW[name][1] not in PS.FIRST_SCAN_ALL_DC and orc != 1:
+            assert rc == err and rc in (2, 3), (name, pt, opt, rc, orc, err)
+            continue
         assert orc == 1 and rc == 0 and np.array_equal(got, want), (name, pt, opt)
         assert g == J.output_geometry(_info(pj), pt, opt | J.SCALE_EIGHTH)
 

@@ -2,7 +2,9 @@
 per-lane logic on the CPU emulator, the class over the CPU stand-in device, and the error paths.
 
 Every comparison is bit-exact.  Inputs and the chain that makes the expected pixels -- tests/prog_jpeg (pure Python) ->
-coef_jpeg.write_jpeg (baseline, same DQT) -> the oracle -- are in tests/prog_cases.py."""
+coef_jpeg.write_jpeg (baseline, same DQT) -> the oracle -- are in tests/prog_cases.py (Pillow's files: libjpeg's default script)
+and tests/prog_scripts.py (files written by tests/prog_write.py under other scan scripts: every MCU layout, DC scans split and
+paired, deep successive approximation, band splits, restart intervals that move, all table ids, long EOB runs)."""
 import ctypes as C
 import os
 import subprocess
@@ -12,12 +14,13 @@ import pytest
 
 import jpegdec_amd as J
 from oracle.loader import RefDecoder
-from tests import coef_jpeg, prog_cases as PC, prog_jpeg
+from tests import coef_jpeg, prog_cases as PC, prog_jpeg, prog_scripts as PS
 from tests.cases import jpeg_for
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FULL = J.PROGRESSIVE_FULL
 NAMES = sorted(PC.CASES)
+WRITTEN = PS.NAMES + PS.LONG_NAMES                        # the files of tests/prog_scripts.py
 
 
 @pytest.fixture(scope="module")
@@ -48,12 +51,35 @@ def _own_extent(dec, c):
 
 
 # ---- the host decoder ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", NAMES)
+def _prescaled_quant(baseline):
+    """the four prescaled quantisers of a baseline file, as the baseline path builds them (JDA_TB_QUANT of the table blob)"""
+    p = J.PreparedImage(baseline)
+    try:
+        return np.frombuffer(bytes(p.tables()[10240:10752]), dtype=np.int16).reshape(4, 64).copy()
+    finally:
+        p.close()
+
+
+@pytest.mark.parametrize("name", NAMES + WRITTEN)
 def test_host_decoder_equals_the_independent_decoder(name, product_lib):
-    jpeg = PC.files(name)[0]
-    dec = PC.decoded(name)
-    assert dec["n_scans"] == (6 if dec["sampling"] == "gray" else 10)        # libjpeg's default script
+    jpeg, twin = PS.files(name)
+    dec = PS.decoded(name)
+    if name in PC.CASES:
+        assert dec["n_scans"] == (6 if dec["sampling"] == "gray" else 10)    # libjpeg's default script
+    else:
+        assert dec["n_scans"] == len(PS.case(name)["script"])
     img = J.CoefImage(jpeg)
+    if name not in PC.CASES:
+        # the quantisers: those in force at each component's first scan -- what the writer put there (a DQT in front of a later scan, a
+        # redefinition behind the first scan), found so by the independent decoder, prescaled as the baseline path prescales the twin's
+        cs = PS.case(name)["set"]
+        raw = prog_jpeg.decode_coefs(jpeg)
+        assert raw["quant_latched"] == [[int(x) for x in cs["quant"][t]] for t in cs["quant_ids"]]
+        q, ids = img.quant()
+        tq = _prescaled_quant(twin)
+        assert ids[:len(cs["quant_ids"])] == [0, 1, 2][:len(cs["quant_ids"])]
+        for c, t in enumerate(cs["quant_ids"]):
+            assert np.array_equal(q[c], tq[t]), (name, c)
     got = img.coefficients()
     want = prog_jpeg.to_library_order(dec)
     assert got.shape == want.shape == (img.info.mcus_x * img.info.mcus_y * img.info.blocks_per_mcu, 64)
@@ -61,26 +87,30 @@ def test_host_decoder_equals_the_independent_decoder(name, product_lib):
     img.close()
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + WRITTEN)
 def test_independent_decoder_equals_the_baseline_twin(name):
     """Pillow decodes both files to identical pixels (same coefficients); inside every component's own extent the coefficients
-    agree -- the padding blocks differ legitimately: the progressive file never codes their AC terms"""
+    agree -- the padding blocks differ legitimately: the progressive file never codes their AC terms.  For a written file the twin is
+    coef_jpeg.write_jpeg of the coefficients the script sends: Pillow (libjpeg) is the third party that reads the writer's Annex G."""
     from PIL import Image
     import io
-    pj, tw = PC.files(name)
-    assert np.array_equal(np.asarray(Image.open(io.BytesIO(pj))), np.asarray(Image.open(io.BytesIO(tw))))
-    dec, base = PC.decoded(name), coef_jpeg.decode_coefs(tw)
+    pj, tw = PS.files(name)
+    assert tw is not None
+    if name not in PS.PILLOW_EXEMPT:
+        assert np.array_equal(np.asarray(Image.open(io.BytesIO(pj))), np.asarray(Image.open(io.BytesIO(tw))))
+    dec, base = PS.decoded(name), coef_jpeg.decode_coefs(tw)
     assert dec["quant"] == base["quant"] and dec["quant_ids"] == base["quant_ids"]
     for c, (a, b) in enumerate(zip(dec["coefs"], base["coefs"])):
         r, w = _own_extent(dec, c)
         assert np.array_equal(a[:r, :w], b[:r, :w]), (name, c)
 
 
-@pytest.mark.parametrize("name", ["gray_200x136_q85", "c444_200x136_q98_rst", "c422_200x136_q50_rst", "c420_200x136_q50_rst", "c420_17x9_q85_rst"])
+@pytest.mark.parametrize("name", ["gray_200x136_q85", "c444_200x136_q98_rst", "c422_200x136_q50_rst", "c420_200x136_q50_rst", "c420_17x9_q85_rst",
+                                  "fx_c420__deep_sa", "fx_c440__split_dc"])
 def test_files_cut_after_each_complete_scan(name, product_lib):
     """a file that ends behind a complete scan is valid and decodes to what its scans carry"""
-    jpeg = PC.files(name)[0]
-    dec = PC.decoded(name)
+    jpeg = PS.files(name)[0]
+    dec = PS.decoded(name)
     for k in range(dec["n_scans"]):
         cut = PC.cut_after_scan(jpeg, dec, k)
         want = prog_jpeg.to_library_order(prog_jpeg.decode_coefs(cut))
@@ -144,15 +174,25 @@ def _sim(coefsim, jpeg, coefs, pt, opt, mode, shape, flags=None):
     return rc, buf[:, :shape[1]]
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + WRITTEN)
 def test_lane_schedule_equals_the_oracle_and_the_twin(name, product_lib, coefsim, oracle):
-    pj = PC.files(name)[0]
-    base, events = PC.reencoded(name)
+    """the coefficients come from the product's own scan decoder here (J.CoefImage), so that a scan decoder that differs from the independent
+    one shows in the pixels too"""
+    pj = PS.files(name)[0]
+    base, events = PS.reencoded(name)
     assert events == 0, "the re-encoded baseline has %d truncation events: its pixels are not the coefficients' (SURVEY fact 6)" % events
-    coefs = prog_jpeg.to_library_order(PC.decoded(name))
+    coefs = prog_jpeg.to_library_order(PS.decoded(name))
     n, ocoefs, oflags, _, _ = oracle.entropy(base)
     assert n == len(coefs) and np.array_equal(ocoefs, coefs)                  # the re-encoded baseline carries exactly these coefficients
-    for pt, opt in ((J.RGB8888, 0), (J.RGB565_LE, 0), (J.RGB565_BE, 0), (J.GRAY8, 0), (J.RGB565_LE, J.LUMA_ONLY)):
+    if name not in PC.CASES:
+        img = J.CoefImage(pj)
+        coefs = img.coefficients().copy()
+        img.close()
+        # (the emulator takes geometry and quantisers from a file's header by the baseline path's rules, which a written file's tables need not
+        # meet: it gets the re-encoded baseline, whose quantisers are the latched ones -- test_host_decoder_equals_the_independent_decoder)
+        pj = base
+    modes = ((J.RGB8888, 0), (J.RGB565_LE, 0), (J.RGB565_BE, 0), (J.GRAY8, 0), (J.RGB565_LE, J.LUMA_ONLY))
+    for pt, opt in modes[:1] if name in PS.LONG_NAMES else modes:
         orc, want, err = oracle.decode_canvas(base, pt, opt)
         assert orc == 1
         flags = np.zeros(len(coefs), np.uint32)
@@ -184,13 +224,14 @@ def test_sim_refuses_scaled_output(product_lib, coefsim):
 
 
 # ---- the class over the CPU stand-in device ------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["gray_200x136_q85", "c444_333x217_q85", "c422_200x136_q50_rst", "c420_640x368_q85", "c420_17x9_q85_rst"])
+@pytest.mark.parametrize("name", ["gray_200x136_q85", "c444_333x217_q85", "c422_200x136_q50_rst", "c420_640x368_q85", "c420_17x9_q85_rst"] + PS.ONE_PER_LAYOUT)
 def test_class_cpu_build_walks(name, class_cpu, oracle):
-    pj = PC.files(name)[0]
-    base, events = PC.reencoded(name)
+    pj = PS.files(name)[0]
+    base, events = PS.reencoded(name)
     assert events == 0
+    gray = PS.decoded(name)["sampling"] == "gray"
     for pt, opt, max_mcus in ((J.RGB565_LE, 0, 0), (J.RGB8888, 0, 3), (J.GRAY8, 0, 0), (J.RGB565_BE, 128, 0), (J.RGB565_LE, 64, 0)):
-        if name.startswith("gray") and pt == J.RGB8888:
+        if gray and pt == J.RGB8888:
             continue
         orc, want, err = oracle.decode_canvas(base, pt, opt & 64)
         g = J.output_geometry(_info(base), pt, opt & 64)
@@ -210,7 +251,7 @@ def test_class_cpu_build_walks(name, class_cpu, oracle):
         rc2, fb2 = class_cpu.decode_fb(base, pt, opt, fill=0x5A)
         assert rc1 == 1 and rc2 == 1 and np.array_equal(fb1, fb2), (name, pt, opt, rc1, rc2)
         # without the bit: still the 1/8 thumbnail of the first scan
-        if name.startswith("gray") or (pt != J.GRAY8 and not opt & 64):      # (a colour progressive file to 8-bit gray: refused)
+        if gray or (pt != J.GRAY8 and not opt & 64):      # (a colour progressive file to 8-bit gray: refused)
             t = class_cpu.decode_cb(pj, pt, opt, want_log=True)
             orc, thumb, err = oracle.decode_canvas(pj, pt, opt & 64)
             assert t["rc"] == 1 and t["scale_shift"] == 3 and orc == 1
@@ -397,3 +438,127 @@ def test_a_file_cut_inside_a_scan_is_read_with_zero_bits(product_lib):
     img = J.CoefImage(cut)
     assert img.coefficients().shape == (prog_jpeg.to_library_order(dec).shape)
     img.close()
+
+
+# ---- the written files (tests/prog_write.py, tests/prog_scripts.py) -------------------------------------------------------------------------
+@pytest.mark.parametrize("name", WRITTEN)
+def test_written_files_hold_the_coefficients_their_script_sends(name):
+    """the independent decoder reads back what went in, over the whole MCU grid: the input inside each component's own extent, truncated to
+    the lowest bit sent; zero in the bands, components and padding blocks that no scan carries"""
+    c = PS.case(name)
+    dec = prog_jpeg.decode_coefs(c["jpeg"])
+    cs = c["set"]
+    assert (dec["width"], dec["height"], dec["sampling"]) == (cs["width"], cs["height"], cs["sampling"])
+    sent = np.zeros((len(cs["coefs"]), 64), bool)
+    for sc in c["script"]:
+        for comp in sc["comps"]:
+            sent[comp, sc["ss"]:sc["se"] + 1] = True
+    final = all(sc["al"] == 0 for sc in c["script"] if not any(o["ss"] == sc["ss"] and o["comps"] == sc["comps"] and o["ah"] == sc["al"] and o["ah"] for o in c["script"]))
+    for k, (got, eff, src) in enumerate(zip(dec["coefs"], c["effective"], cs["coefs"])):
+        assert np.array_equal(got, eff), (name, k)
+        r, w = _own_extent(dec, k)
+        assert not got[..., ~sent[k]].any()
+        if final:                                           # every band that was sent was sent down to bit 0
+            assert np.array_equal(got[:r, :w][..., sent[k]], np.asarray(src)[:r, :w][..., sent[k]]), (name, k)
+
+
+def test_pillow_exemptions_are_bounded():
+    """the third-party anchor may leave out only DC-edge stress sets and the long-EOB files, by name; as it stands it leaves out none"""
+    assert set(PS.PILLOW_EXEMPT) <= set(PS.PILLOW_EXEMPT_ALLOWED)
+    assert all(n.startswith(("k_fastbound_dc_", "k_dcdrift_", "long_eob_")) for n in PS.PILLOW_EXEMPT_ALLOWED)
+    assert len(PS.PILLOW_EXEMPT) == 0
+
+
+@pytest.mark.parametrize("path", sorted(PS.PATHS))
+def test_written_files_reach_the_paths_they_exist_for(path):
+    """measured from the writer's own symbol log, so that a change to a generator cannot silently stop exercising the path"""
+    name, measure, holds = PS.PATHS[path]
+    value = measure(PS.case(name)["log"])
+    assert holds(value), "%s in %s: measured %r" % (path, name, value)
+
+
+def test_every_layout_has_written_files():
+    layouts = {}
+    for name in PS.NAMES:
+        layouts.setdefault(PS.case(name)["set"]["sampling"], []).append(name)
+    assert sorted(layouts) == sorted(coef_jpeg.LAYOUTS), sorted(layouts)
+    n440 = len(layouts["4:4:0"])
+    assert n440 >= 10, "4:4:0 files: %d" % n440
+    info = _info(PS.files(PS.ONE_PER_LAYOUT[3])[0])
+    assert info.subsample == 0x12 and info.jpeg_type == 1
+
+
+@pytest.mark.parametrize("name", PS.NAMES)
+def test_without_the_bit_the_answer_is_the_references(name, class_cpu, oracle):
+    """without JPEG_PROGRESSIVE_FULL a written file gets what the reference gives it -- the 1/8 thumbnail of the first scan where that scan is
+    the DC scan of every component, and the reference's return code and pixels whatever the first scan is"""
+    pj = PS.files(name)[0]
+    gray = PS.decoded(name)["sampling"] == "gray"
+    for pt in (J.RGB565_LE, J.RGB8888) + ((J.GRAY8,) if gray else ()):
+        if gray and pt == J.RGB8888:
+            continue
+        orc, thumb, err = oracle.decode_canvas(pj, pt, 0)
+        t = class_cpu.decode_cb(pj, pt, 0, want_log=True)
+        assert t["rc"] == orc, (name, pt, t["rc"], t["last_error"], orc, err)
+        if PS.NEW[name][1] in PS.FIRST_SCAN_ALL_DC:
+            assert orc == 1 and t["scale_shift"] == 3
+        elif PS.NEW[name][1] == "tables":                  # (DC tables of ids 2 and 3 in the header: the reference has no room for them)
+            assert orc == 0 and err == 3
+        if orc == 1:
+            g = J.output_geometry(_info(pj), pt, J.SCALE_EIGHTH)
+            assert np.array_equal(t["canvas"][:g["out_h"], :thumb.shape[1]], thumb[:g["out_h"]]), (name, pt)
+        else:
+            assert t["last_error"] == err, (name, pt, t["last_error"], err)
+
+
+@pytest.mark.parametrize("kind", sorted(PS.malformed()))
+def test_malformed_scans_are_refused(kind, product_lib, class_cpu):
+    """Annex G's error exits: JDA_DECODE_ERROR from the host decoder, DecodeError from the independent one; nothing reaches a kernel"""
+    bad = PS.malformed()[kind]
+    with pytest.raises(coef_jpeg.DecodeError):
+        prog_jpeg.decode_coefs(bad)
+    with pytest.raises(J.JdaError) as e:
+        J.CoefImage(bad)
+    assert e.value.code == 2
+    r = class_cpu.decode_cb(bad, J.RGB565_LE, FULL, want_log=True, canvas_shape=(400, 2600))
+    assert r["rc"] == 0 and r["last_error"] == 2 and r["n_calls"] == 0
+    rc, fb = class_cpu.decode_fb(bad, J.RGB565_LE, FULL, fill=0x5A)
+    assert rc == 0 and class_cpu.last_error == 2 and bool((fb == 0x5A).all())
+
+
+def test_malformed_files_come_from_valid_ones(product_lib):
+    """each malformed file differs from a file the decoder accepts only by the writer's malform hook: the same scripts without it decode"""
+    cs = PS.coef_set("fx_c420")
+    for script in (PS._deep_sa(3, cs["quant"])[0][:8], PS._seq(3, cs["quant"])[0], PS._pair(3, cs["quant"])[0], [PS.scan((0, 1, 2), 0, 0, 0, 13)]):
+        ok = PS.PW.write_progressive(cs["width"], cs["height"], cs["sampling"], cs["coefs"], cs["quant"], cs["quant_ids"], script)
+        img = J.CoefImage(ok)
+        assert np.array_equal(img.coefficients(), prog_jpeg.to_library_order(prog_jpeg.decode_coefs(ok)))
+        img.close()
+
+
+def test_ac_first_pass_values_that_leave_int16_wrap(product_lib):
+    """documented behaviour (include/jpegdec_amd.h): value << Al is kept modulo 2^16, at coefficient level only -- no pixels are promised"""
+    jpeg, eff = PS.wrap_case()
+    dec = prog_jpeg.decode_coefs(jpeg)
+    assert np.array_equal(dec["coefs"][0], eff[0]) and int(eff[0].max()) == 40000 and int(eff[0].min()) == -40000
+    img = J.CoefImage(jpeg)
+    got, want = img.coefficients(), prog_jpeg.to_library_order(dec)
+    assert np.array_equal(got, want)
+    assert sorted(int(v) for v in got[got != 0] if abs(int(v)) > 20000) == [-25536, 25536, 32766]
+    img.close()
+
+
+def test_written_and_malformed_files_under_asan_ubsan(class_cpu, tmp_path):
+    """every written file and every malformed one once through the sanitizer build of the class and the host decoder, with the bit (callbacks
+    and framebuffer) and without it"""
+    files = [PS.files(n)[0] for n in PS.NAMES + PS.LONG_NAMES[:1]] + [PS.malformed()[k] for k in sorted(PS.malformed())] + [PS.wrap_case()[0]]
+    lines = []
+    for k, f in enumerate(files):
+        (tmp_path / ("img%d.jpg" % k)).write_bytes(f)
+        lines += ["W %d 0 0 %d 0 0 0 -1 -1 -1 -1" % (k, FULL), "W %d 1 2 %d 0 0 0 -1 -1 -1 -1" % (k, FULL), "W %d 0 0 0 0 0 0 -1 -1 -1 -1" % k]
+    (tmp_path / "walks.txt").write_text("\n".join(lines) + "\n")
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([os.path.join(ROOT, "tests", "class_cpu", "walks_asan"), str(tmp_path), str(len(files))], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=1200)
+    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+    assert "walks done" in r.stdout and int(r.stdout.split("walks done")[0].split()[-1]) == len(lines), r.stdout[-300:]
