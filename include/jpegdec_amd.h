@@ -67,7 +67,7 @@ enum {
     /* ours (the reference has nothing like it): decode EVERY scan of a progressive file to a full-size canvas instead of the 1/8
      * thumbnail of its first scan.  No effect on a baseline file.  With a JDA_SCALE_* bit: JDA_UNSUPPORTED_FEATURE.  Taken by
      * jda_decode_to_host / _ex / _flags (whole image); every other decode entry point -- jda_batch_create*, jda_pipeline_submit*,
-     * jda_node_submit* (per image, in status[]), jda_decode_to_host_rect / _bands / _strips / _oriented, jda_decode_dither_to_host and
+     * jda_node_submit* (per image, in status[]), jda_decode_to_host_rect / _bands / _strips / _oriented / _packed, jda_decode_dither_to_host and
      * any call with an MCU rectangle -- answers JDA_UNSUPPORTED_FEATURE for a progressive file asked for with it. */
     JDA_PROGRESSIVE_FULL = 256
 };
@@ -362,6 +362,31 @@ int jda_oriented_geometry(const jda_image_info *info, int32_t pixel_type, int32_
  * a dst and of any src or other dst that overlap.  n == 0 succeeds and launches nothing. */
 int jda_orient_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *orientations, const jda_output *dst);
 
+/* ---- Decoded surfaces repacked for a GPU-side consumer: three-byte RGB / BGR or planar CHW, tightly packed, as bytes or through a table
+ * src[i] = a decoded surface resident in HBM: JDA_RGB8888 (src_bytes_per_pixel 4: bytes R, G, B, A) or JDA_EIGHT_BIT_GRAYSCALE (1); pixels 16-byte
+ * aligned, pitch_bytes a multiple of 16 and >= width_px * src_bytes_per_pixel.  rects: {x, y, w, h} in pixels per image, inside width_px x rows;
+ * NULL: all of width_px x rows -- pass the visible size (jda_output_geometry's out_w x out_h), not the canvas, and the MCU padding is gone.
+ * dst[i] = DENSE, no padding anywhere: JDA_PACK_HWC h * w * C elements pixel-major, JDA_PACK_CHW C planes of h * w elements.  C = 3 for an
+ * RGB8888 source (the alpha byte is never read into the result; | JDA_PACK_BGR: destination channel c is source channel 2 - c), C = 1 for a
+ * gray source (the layout makes no difference).  dst[i] is aligned to its ELEMENT and to nothing else: image n of a uint8 [N,3,H,W] tensor
+ * begins n * 3 * H * W bytes into it.  No byte outside [dst[i], dst[i] + jda_pack_bytes) is written.
+ * elem_type JDA_PACK_U8: the source byte, table == NULL.  JDA_PACK_F16 / JDA_PACK_F32: table[c][v], c = the DESTINATION channel -- table =
+ * C * 256 elements of the destination type in DEVICE memory, 16-byte aligned, one for the whole call.  The result is a lookup and nothing
+ * else: normalisation ((v / 255 - mean) / std), gamma, any transfer is what the caller writes into the table; the kernel does no float
+ * arithmetic, so every result is the table's bit pattern.
+ * ONE launch on the context's stream (behind whatever decoded the surfaces there), synchronous.  n == 0 succeeds and launches nothing.
+ * JDA_INVALID_PARAMETER: a null or misaligned pointer; a pitch too small or not a multiple of 16; a rectangle that is empty or leaves the
+ * surface; a pixel size other than 1 or 4; unknown layout bits or element type; a table with U8, none with F16 / F32; JDA_PACK_BGR on a gray
+ * source; byte ranges of a destination and of any source (the table included) or other destination that overlap; a job whose dense
+ * destination is larger than JDA_PACK_MAX_BYTES (the kernel counts a job's bytes, elements and pixels in 32 bits). */
+enum { JDA_PACK_HWC = 0, JDA_PACK_CHW = 1, JDA_PACK_BGR = 2 };          /* layout_flags */
+enum { JDA_PACK_U8 = 0, JDA_PACK_F16 = 1, JDA_PACK_F32 = 2 };           /* elem_type */
+#define JDA_PACK_MAX_BYTES 0x7fff0000u
+/* w * h * channels elements of elem_type in bytes; 0 for arguments that are not positive or an unknown element type */
+size_t jda_pack_bytes(int32_t w, int32_t h, int32_t channels, int32_t elem_type);
+int jda_pack_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t src_bytes_per_pixel, const int32_t *rects,
+                      int32_t layout_flags, int32_t elem_type, const void *table, void *const *dst);
+
 /* PCI bus id ("0000:8e:00.0") of the context's GPU, for NUMA placement of the host threads that feed it; buf >= 16 bytes */
 int jda_device_pci_bus_id(jda_ctx *ctx, char *buf, int32_t len);
 int jda_device_pci_bus_id_of(int32_t device, char *buf, int32_t len);      /* the same by device ordinal, without a context */
@@ -388,6 +413,16 @@ int jda_decode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
  * the bad one on are dithered as zeros).  seed: JDA_DITHER_SEED_BYTES the chain starts from, or NULL: jda_dither_seed of the file. */
 int jda_decode_dither_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options,
                               const uint8_t *seed, void *host_packed, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded);
+/* jda_decode_to_host_ex followed by jda_pack_surfaces: prepare, upload, decode to a device canvas, pack its visible rectangle and copy back
+ * only the dense bytes -- decode, pack and the copy are queued back to back.  The image is decoded as JDA_RGB8888 (C = 3); a gray file, or
+ * JDA_LUMA_ONLY, as JDA_EIGHT_BIT_GRAYSCALE (C = 1).  layout_flags, elem_type as jda_pack_surfaces; table: C * 256 elements in HOST memory
+ * (any alignment), NULL with JDA_PACK_U8.  host_out: out_bytes >= jda_pack_bytes(*w, *h, C, elem_type) or JDA_INVALID_PARAMETER.  *w, *h (may be
+ * NULL): the visible size, jda_output_geometry's out_w x out_h.  The JDA_SCALE_* bits and the default 1/8 thumbnail of a progressive file
+ * as in jda_decode_to_host_ex, with the same refusals and codes; JDA_PROGRESSIVE_FULL on a progressive file: JDA_UNSUPPORTED_FEATURE.
+ * Pre-scan, host fallback, status and *mcus_decoded as jda_decode_to_host_ex; with JDA_DECODE_ERROR the MCUs from the bad one on are zeros
+ * BEFORE the pack (table[c][0] behind it) and the whole result is still delivered. */
+int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, int32_t layout_flags, int32_t elem_type,
+                              const void *table, void *host_out, size_t out_bytes, int32_t *w, int32_t *h, int32_t *mcus_decoded);
 /* jda_decode_to_host_ex followed by the orientation: prepare, upload, decode to a device canvas, orient its visible rectangle into a second
  * device surface (jda_orient_surfaces) and copy back only the W' * bpp x H' bytes of jda_oriented_geometry: row r at host_pixels + r * pitch_bytes,
  * pitch_bytes >= W' * bpp (any value), rows >= H'.  orientation < 0: the file's; 0..8 as given (0, 1: the visible rectangle as it is); above

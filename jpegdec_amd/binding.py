@@ -10,6 +10,9 @@ FOUR_BIT_DITHERED, TWO_BIT_DITHERED, ONE_BIT_DITHERED = 4, 5, 6      # made from
 DITHER_SEED_BYTES = 2184
 SCALE_HALF, SCALE_QUARTER, SCALE_EIGHTH, LUMA_ONLY = 2, 4, 8, 64
 PROGRESSIVE_FULL = 256      # ours: every scan of a progressive file at full size (decode_to_host); no effect on a baseline file
+PACK_HWC, PACK_CHW, PACK_BGR = 0, 1, 2      # pack_surfaces / decode_packed_to_host: layout flags (PACK_BGR is OR-ed in)
+PACK_U8, PACK_F16, PACK_F32 = 0, 1, 2       # .. element types
+PACK_DTYPES = {PACK_U8: np.uint8, PACK_F16: np.float16, PACK_F32: np.float32}
 AUTO_ROTATE = 1      # the class's decode() applies the EXIF orientation; the C-ABI takes it as an argument (decode_oriented_to_host, orient_surfaces)
 
 ERROR_NAMES = {0: "JDA_SUCCESS", 1: "JDA_INVALID_PARAMETER", 2: "JDA_DECODE_ERROR",
@@ -128,6 +131,9 @@ _PROTOTYPES = [
     ("jda_oriented_geometry", C.c_int, [C.POINTER(ImageInfo), C.c_int32, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 4),
     ("jda_orient_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output)]),
     ("jda_decode_to_host_oriented", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    ("jda_pack_bytes", C.c_size_t, [C.c_int32] * 4),
+    ("jda_pack_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    ("jda_decode_to_host_packed", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t] + [C.POINTER(C.c_int32)] * 3),
     ("jda_checksum_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("jda_device_pci_bus_id", C.c_int, [_P, C.c_char_p, C.c_int32]),
     ("jda_upload_batch_ex", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32)]),
@@ -787,6 +793,38 @@ def decode_oriented_to_host(ctx: Context, jpeg: bytes, pixel_type=RGB8888, optio
                                              pixels.ctypes.data_as(_P), t["w"] * t["bpp"], t["h"], C.byref(nok))
     g["mcus_decoded"] = nok.value
     return rc, pixels, g
+
+
+def pack_surfaces(ctx: Context, src, src_bytes_per_pixel, dst, layout=PACK_HWC, elem_type=PACK_U8, table=None, rects=None):
+    """jda_pack_surfaces: src = list of (device_ptr, pitch_bytes, width_px, rows) of RGB8888 (4) or GRAY8 (1) surfaces, dst = list of device
+    pointers of the dense results, table = device pointer of the C x 256 lookup table (F16 / F32), rects = list of (x, y, w, h) or None: all
+    of width_px x rows.  One launch for all of them."""
+    n = len(src)
+    s = (Output * max(n, 1))(*[Output(*o) for o in src])
+    d = (_P * max(n, 1))(*dst)
+    r = None if rects is None else (C.c_int32 * max(4 * n, 1))(*[v for q in rects for v in q])
+    ctx.check(ctx.lib.jda_pack_surfaces(ctx.handle, n, s, src_bytes_per_pixel, r, layout, elem_type, table, d), "jda_pack_surfaces")
+
+
+def decode_packed_to_host(ctx: Context, jpeg: bytes, options=0, layout=PACK_HWC, elem_type=PACK_U8, table=None):
+    """jda_decode_to_host_packed: (rc, the dense visible pixels -- [h, w, C] or, with PACK_CHW, [C, h, w]; uint8, float16 or float32; None when
+    the call refused --, {"w", "h", "channels", "mcus_decoded"}).  table: a numpy array of C x 256 elements of the result's type, or None."""
+    info = ImageInfo()
+    rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
+    if rc != 0:
+        raise JdaError(rc, "jda_parse")
+    channels = 1 if info.ncomp == 1 or (options & LUMA_ONLY) else 3
+    dtype = PACK_DTYPES.get(elem_type, np.uint8)
+    flat = np.zeros(info.width * info.height * channels, dtype=dtype)      # (at least the visible size at any scale)
+    tab = None if table is None else np.ascontiguousarray(table)
+    w, h, nok = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = ctx.lib.jda_decode_to_host_packed(ctx.handle, jpeg, len(jpeg), options, layout, elem_type, None if tab is None else tab.ctypes.data_as(_P),
+                                           flat.ctypes.data_as(_P), flat.nbytes, C.byref(w), C.byref(h), C.byref(nok))
+    g = {"w": w.value, "h": h.value, "channels": channels, "mcus_decoded": nok.value}
+    if w.value == 0:
+        return rc, None, g
+    shape = (channels, h.value, w.value) if layout & PACK_CHW else (h.value, w.value, channels)
+    return rc, flat[:w.value * h.value * channels].reshape(shape), g
 
 
 def decode_resident(ctx: Context, prepared: PreparedImage, pixel_type=RGB8888, options=0):

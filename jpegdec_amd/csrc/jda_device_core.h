@@ -3415,6 +3415,188 @@ template <int BPP, class IO> JDA_HD void jda_orient_emit(const jda_orient_geo &G
     }
 }
 
+// ---- jda_pack_*: decoded surfaces repacked for a GPU-side consumer -------------------------------------------------
+// src = a pixel rectangle {x, y, w, h} of a decoded surface: RGB8888 (bytes R, G, B, A: jda_pixel_rgba) or EIGHT_BIT_GRAYSCALE, at src_pitch.
+// dst = DENSE: h * w * C elements pixel-major (JDA_PACK_HWC) or C planes of h * w elements (JDA_PACK_CHW); C = 3 (the alpha byte is never
+// part of the result; JDA_PACK_BGR: destination channel c is source byte 2 - c) or 1 (gray).  An element is the source byte (ES = 1) or
+// table[c][byte], c = the DESTINATION channel, ES = 2 or 4 bytes: a lookup in the LDS copy of the caller's table, no arithmetic.
+// The destination is aligned to ES and to nothing else, so the schedule is laid on ADDRESSES: a RUN is a stretch of destination bytes
+// whose element index determines the source byte -- the whole HWC image, or one plane; a gray image is one plane -- and vector v of a run
+// is the v-th ALIGNED 16 bytes that hold a byte of it.  A tile = JDA_PACK_THREADS consecutive vectors (4 KiB), a lane = one vector: it
+// finds the pixel of its first element (one division by w), walks the rectangle from there (x + 1, at w the next row), loads the aligned
+// dword of every pixel it touches, cuts the bytes out (v_perm_b32 for HWC bytes: a destination dword is three bytes of one pixel and one of
+// the next, in one of three phases) and stores ONE aligned vector.  Only the first and the last vector of a run may be partial: those go
+// out as the aligned dwords, halves and bytes that lie inside the run, so that nothing in front of or behind a run is written (in a batch
+// tensor those bytes are the neighbouring image's).  A CHW tile does its vectors of ALL planes, one plane after the other, so that the
+// three passes over the same source pixels meet in the cache (the planes' vectors are shifted against each other by what h * w * ES
+// leaves of 16).  A lane whose vector reaches in front of the run or behind it still loads -- the first / last pixel again: every load is
+// unconditional, no branch between them.  Memory goes through an IO policy: the kernel (jda_kernels.hip) and the lane-by-lane run on the
+// CPU (tests/hostsim/pack_sim.cpp) are the same code.
+#define JDA_PACK_THREADS 256
+#define JDA_PACK_TILE_BYTES (JDA_PACK_THREADS * 16u)
+#define JDA_PACK_LDS_DWORDS(es) ((es) == 1 ? 4u : 3u * 256u * (uint32_t)(es) / 4u)
+struct jda_pack_geo {                        // a job and the launch's format, wave-uniform
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t src_pitch, x, y, w, h, bpp, bgr;
+};
+// bytes of one run and the number of runs of a job
+JDA_HD uint32_t jda_pack_run_bytes(bool hwc, uint32_t es, uint32_t w, uint32_t h) { return w * h * es * (hwc ? 3u : 1u); }
+JDA_HD uint32_t jda_pack_runs(bool hwc, uint32_t bpp) { return hwc || bpp == 1u ? 1u : 3u; }
+// tiles of a job: the vectors of a run begin up to 15 bytes in front of it
+JDA_HD uint32_t jda_pack_tiles_of(uint32_t run_bytes) { return (run_bytes + 15u + JDA_PACK_TILE_BYTES - 1u) / JDA_PACK_TILE_BYTES; }
+// the job a tile of the flat list belongs to (as jda_orient_find_job)
+JDA_HD uint32_t jda_pack_find_job(const jda_pack_job *jobs, uint32_t n, uint32_t tile)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (JDA_G(const jda_pack_job, jobs)[mid].tile0 <= tile) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// the caller's table (C * 256 elements of ES bytes, 16-byte aligned) into LDS, a 16-byte vector a lane and pass
+template <int ES, class IO> JDA_HD void jda_pack_stage_table(IO &io, const uint8_t *table, uint32_t channels, uint32_t tid)
+{
+    const uint32_t vecs = channels * 256u * (uint32_t)ES / 16u;
+#pragma unroll
+    for (uint32_t i = 0; i < 3u * 256u * (uint32_t)ES / 16u / JDA_PACK_THREADS + 1u; i++) {
+        const uint32_t v = i * JDA_PACK_THREADS + tid;
+        if (v >= vecs) continue;
+        uint32_t q[4];
+        io.ld_table128(table + 16u * v, q);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) io.lds_wr(4u * v + j, q[j]);
+    }
+}
+// where a lane is in the rectangle: pixel p = y * w + x, held inside [0, w * h)
+struct jda_pack_cursor { uint32_t p, x, y; };
+JDA_HD void jda_pack_seek(jda_pack_cursor &c, const jda_pack_geo &G, int32_t q)
+{
+    const uint32_t npx = G.w * G.h;
+    c.p = q < 0 ? 0u : (uint32_t)q < npx ? (uint32_t)q : npx - 1u;
+    c.y = c.p / G.w; c.x = c.p - c.y * G.w;
+}
+// from pixel q to q + 1 (q may lie in front of the rectangle or behind it: the cursor stays on the first / last pixel then)
+JDA_HD void jda_pack_step(jda_pack_cursor &c, const jda_pack_geo &G, int32_t q)
+{
+    const uint32_t adv = (q >= 0 && c.p + 1u < G.w * G.h) ? 1u : 0u;
+    c.p += adv; c.x += adv;
+    if (c.x == G.w) { c.x = 0u; c.y++; }
+}
+// the aligned dword that holds the cursor's pixel; shift: the bit its first byte begins at (0 for RGB8888)
+template <class IO> JDA_HD uint32_t jda_pack_fetch(IO &io, const jda_pack_geo &G, const jda_pack_cursor &c, uint32_t &shift)
+{
+    const uint32_t off = (G.x + c.x) * G.bpp;
+    shift = (off & 3u) * 8u;
+    return io.ld32(G.src + (size_t)(G.y + c.y) * G.src_pitch + (off & ~3u));
+}
+// K = 16 / ES element bytes v[] of destination channels ch[] -> the vector's four dwords
+template <int ES, class IO> JDA_HD void jda_pack_elements(IO &io, const uint32_t *v, const uint32_t *ch, uint32_t *out)
+{
+    if (ES == 1) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) out[d] = v[4 * d] | (v[4 * d + 1] << 8) | (v[4 * d + 2] << 16) | (v[4 * d + 3] << 24);
+    } else if (ES == 2) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) out[d] = io.lds_rd16(ch[2 * d] * 256u + v[2 * d]) | (io.lds_rd16(ch[2 * d + 1] * 256u + v[2 * d + 1]) << 16);
+    } else {
+#pragma unroll
+        for (int d = 0; d < 4; d++) out[d] = io.lds_rd32(ch[d] * 256u + v[d]);
+    }
+}
+// the vector at p = run + rel (16-byte aligned; rel < 0: the run begins inside it) of a run of run_bytes bytes: one store where the run
+// holds all of it, else the aligned dwords, halves and bytes inside the run
+template <class IO> JDA_HD void jda_pack_store(IO &io, uint8_t *p, int32_t rel, uint32_t run_bytes, const uint32_t *out)
+{
+    const uint32_t b0 = rel < 0 ? (uint32_t)-rel : 0u;
+    const uint32_t left = run_bytes - (uint32_t)(rel < 0 ? 0 : rel), b1 = rel < 0 ? (run_bytes + b0 < 16u ? run_bytes + b0 : 16u) : (left < 16u ? left : 16u);
+    if (b0 == 0u && b1 == 16u) { io.st128(p, out); return; }
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) {
+        if (4u * j >= b0 && 4u * j + 4u <= b1) { io.st32(p + 4u * j, out[j]); continue; }
+#pragma unroll
+        for (uint32_t hh = 0; hh < 2u; hh++) {
+            const uint32_t s = 4u * j + 2u * hh, half = (out[j] >> (16u * hh)) & 0xffffu;
+            if (s >= b0 && s + 2u <= b1) { io.st16(p + s, half); continue; }
+            if (s >= b0 && s < b1) io.st8(p + s, half & 0xffu);
+            if (s + 1u >= b0 && s + 1u < b1) io.st8(p + s + 1u, half >> 8);
+        }
+    }
+}
+// vector `vec` of plane `run` (JDA_PACK_CHW of an RGB8888 surface: run = destination channel; a gray surface: run 0)
+template <int ES, class IO> JDA_HD void jda_pack_planar(const jda_pack_geo &G, uint32_t run, uint32_t vec, IO &io)
+{
+    const uint32_t K = 16u / (uint32_t)ES, run_bytes = jda_pack_run_bytes(false, ES, G.w, G.h);
+    uint8_t *start = G.dst + (size_t)run * run_bytes;
+    const int32_t rel = (int32_t)(vec * 16u) - (int32_t)((uintptr_t)start & 15u);
+    if (rel >= (int32_t)run_bytes) return;
+    const int32_t q0 = rel / ES;                               // (rel is a multiple of ES: the run is aligned to it)
+    const uint32_t csh = G.bpp == 4u ? 8u * (G.bgr ? 2u - run : run) : 0u;
+    jda_pack_cursor c;
+    jda_pack_seek(c, G, q0);
+    uint32_t v[16], ch[16], out[4];
+#pragma unroll
+    for (uint32_t k = 0; k < K; k++) {
+        uint32_t sh;
+        const uint32_t d = jda_pack_fetch(io, G, c, sh);
+        v[k] = (d >> (sh + csh)) & 0xffu; ch[k] = run;
+        jda_pack_step(c, G, q0 + (int32_t)k);
+    }
+    jda_pack_elements<ES>(io, v, ch, out);
+    jda_pack_store(io, start + rel, rel, run_bytes, out);
+}
+// vector `vec` of a JDA_PACK_HWC image (RGB8888 surface).  Element e = 3 * pixel + channel; the vector's first element e0 >= -15, so
+// e0 + 15 = 3 * (its pixel + 5) + its channel: no division of a negative number
+template <int ES, class IO> JDA_HD void jda_pack_hwc(const jda_pack_geo &G, uint32_t vec, IO &io)
+{
+    const uint32_t K = 16u / (uint32_t)ES, NP = (K + 1u) / 3u + 1u, run_bytes = jda_pack_run_bytes(true, ES, G.w, G.h);
+    const int32_t rel = (int32_t)(vec * 16u) - (int32_t)((uintptr_t)G.dst & 15u);
+    if (rel >= (int32_t)run_bytes) return;
+    const uint32_t ii = (uint32_t)(rel / ES + 15), c0 = ii % 3u;
+    const int32_t q0 = (int32_t)(ii / 3u) - 5;
+    jda_pack_cursor c;
+    jda_pack_seek(c, G, q0);
+    uint32_t px[8], out[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; j++) px[j] = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < NP; j++) {
+        uint32_t sh;
+        px[j] = jda_pack_fetch(io, G, c, sh);
+        jda_pack_step(c, G, q0 + (int32_t)j);
+    }
+    if (ES == 1) {
+        // destination dword d = elements c0 + 4 d ..: pixel a = (c0 + 4 d) / 3 from its channel ph = (c0 + 4 d) % 3 on, then pixel a + 1
+#pragma unroll
+        for (uint32_t d = 0; d < 4u; d++) {
+            const uint32_t A = 4u * d / 3u, s = c0 + 4u * d % 3u, wrap = s >= 3u ? 1u : 0u, ph = s - 3u * wrap;
+            const uint32_t lo = wrap ? px[A + 1u] : px[A], hi = wrap ? px[A + 2u] : px[A + 1u];
+            const uint32_t sel = G.bgr ? (ph == 0u ? 0x06000102u : ph == 1u ? 0x05060001u : 0x04050600u)
+                                       : (ph == 0u ? 0x04020100u : ph == 1u ? 0x05040201u : 0x06050402u);
+            out[d] = jda_perm(hi, lo, sel);
+        }
+    } else {
+        uint32_t v[8], ch[8];
+#pragma unroll
+        for (uint32_t k = 0; k < K; k++) {
+            const uint32_t s = c0 + k % 3u, wrap = s >= 3u ? 1u : 0u, cd = s - 3u * wrap;
+            const uint32_t p = wrap ? px[k / 3u + 1u] : px[k / 3u];
+            v[k] = (p >> (8u * (G.bgr ? 2u - cd : cd))) & 0xffu; ch[k] = cd;
+        }
+        jda_pack_elements<ES>(io, v, ch, out);
+    }
+    jda_pack_store(io, G.dst + rel, rel, run_bytes, out);
+}
+// tile `tile` of a job, lane tid (behind the barrier that follows jda_pack_stage_table where ES > 1)
+template <int HWC, int ES, class IO> JDA_HD void jda_pack_tile(const jda_pack_geo &G, uint32_t tile, uint32_t tid, IO &io)
+{
+    const uint32_t vec = tile * JDA_PACK_THREADS + tid;
+    if (HWC) { jda_pack_hwc<ES>(G, vec, io); return; }
+    const uint32_t runs = jda_pack_runs(false, G.bpp);
+    for (uint32_t r = 0; r < runs; r++) jda_pack_planar<ES>(G, r, vec, io);
+}
+
 // ================================================================================================
 // jda_coef_tiles: a tile decoded from COEFFICIENTS (a coefficient image: every scan of a progressive file decoded on the host, or a
 // DCT-domain caller's own).  The tile is the decode kernel's -- one wave64, <= 64 consecutive blocks of an MCU row,

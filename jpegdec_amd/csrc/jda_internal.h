@@ -199,4 +199,13 @@ struct jda_orient_job {
     uint32_t src_pitch, dst_pitch, width, height, orientation, tile0, tiles_x, pad_;
 };
 
+// One image of a pack launch (device pointers): src = a decoded surface (16-byte aligned, src_pitch a multiple of 16) of the launch's
+// pixel size, {x, y, w, h} = the pixel rectangle that is packed; dst = the dense destination, aligned to its element.  tile0: the index
+// of the job's first tile in the launch's flat tile list.
+struct jda_pack_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t src_pitch, x, y, w, h, tile0;
+};
+
 #endif

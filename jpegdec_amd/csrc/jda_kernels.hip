@@ -1880,6 +1880,69 @@ extern "C" hipError_t jda_launch_orient(const jda_orient_job *jobs, uint32_t n, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// jda_pack_tiles<HWC, ES>: decoded surfaces repacked into dense three-byte / planar tensors (the runs, vectors and the lane's walk:
+// jda_pack_* in jda_device_core.h).  grid = the flat list of every job's tiles, a workgroup finds its job by bisection
+// (scalar loads) and keeps it in SGPRs.  HWC = 1: pixel-major from RGB8888; HWC = 0: planes (RGB8888) or the one plane of a gray surface,
+// bpp wave-uniform.  ES = bytes of an element: 1 = the source byte; 2 / 4 = the caller's table, staged into LDS by the workgroup (one
+// barrier).  Global accesses: aligned dword loads, one aligned 16-byte store a lane and run; narrower stores only in the first and last
+// vector of a run.  No atomics, nothing shared between tiles.
+struct jda_pack_io {
+    uint32_t *lds;
+    __device__ __forceinline__ uint32_t ld32(const uint8_t *p) const { return *(const jda_u32_alias JDA_GLOBAL *)JDA_G(const uint8_t, p); }
+    __device__ __forceinline__ void ld_table128(const uint8_t *p, uint32_t *v) const
+    {
+        const uint4 q = *(const uint4 JDA_GLOBAL *)JDA_G(const uint8_t, p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+    __device__ __forceinline__ void st128(uint8_t *p, const uint32_t *v) const { *(uint4 JDA_GLOBAL *)JDA_G(uint8_t, p) = make_uint4(v[0], v[1], v[2], v[3]); }
+    __device__ __forceinline__ void st32(uint8_t *p, uint32_t v) const { *(jda_u32_alias JDA_GLOBAL *)JDA_G(uint8_t, p) = v; }
+    __device__ __forceinline__ void st16(uint8_t *p, uint32_t v) const { *(uint16_t JDA_GLOBAL *)JDA_G(uint8_t, p) = (uint16_t)v; }
+    __device__ __forceinline__ void st8(uint8_t *p, uint32_t v) const { *JDA_G(uint8_t, p) = (uint8_t)v; }
+    __device__ __forceinline__ void lds_wr(uint32_t i, uint32_t v) const { lds[i] = v; }
+    __device__ __forceinline__ uint32_t lds_rd32(uint32_t i) const { return lds[i]; }
+    __device__ __forceinline__ uint32_t lds_rd16(uint32_t i) const { return ((const uint16_t *)lds)[i]; }
+};
+template <int HWC, int ES>
+__global__ __launch_bounds__(JDA_PACK_THREADS)
+void jda_pack_tiles(const jda_pack_job *__restrict__ jobs, uint32_t n_jobs, const uint8_t *__restrict__ table, uint32_t bpp, uint32_t bgr)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t pack_lds[JDA_PACK_LDS_DWORDS(ES)];
+    const uint32_t tile = blockIdx.x;
+    const jda_pack_job JDA_GLOBAL *job = JDA_G(const jda_pack_job, jobs) + jda_uni32(jda_pack_find_job(jobs, n_jobs, tile));
+    jda_pack_geo G;
+    G.src = jda_uni_ptr(job->src); G.dst = jda_uni_ptr(job->dst);
+    G.src_pitch = jda_uni32(job->src_pitch);
+    G.x = jda_uni32(job->x); G.y = jda_uni32(job->y); G.w = jda_uni32(job->w); G.h = jda_uni32(job->h);
+    G.bpp = HWC ? 4u : bpp; G.bgr = bgr;
+    const uint32_t local = tile - jda_uni32(job->tile0);
+    if (G.w == 0u || G.h == 0u) return;
+    jda_pack_io io;
+    io.lds = pack_lds;
+    if (ES > 1) {
+        jda_pack_stage_table<ES>(io, table, G.bpp == 4u ? 3u : 1u, threadIdx.x);
+        __syncthreads();
+    }
+    jda_pack_tile<HWC, ES>(G, local, threadIdx.x, io);
+}
+template <int HWC>
+static hipError_t launch_pack(uint32_t es, const jda_pack_job *jobs, uint32_t n, uint32_t n_tiles, const uint8_t *table, uint32_t bpp, uint32_t bgr, hipStream_t stream)
+{
+    if (es == 1u) JDA_LAUNCH((jda_pack_tiles<HWC, 1>), dim3(n_tiles), dim3(JDA_PACK_THREADS), 0, stream, jobs, n, table, bpp, bgr);
+    else if (es == 2u) JDA_LAUNCH((jda_pack_tiles<HWC, 2>), dim3(n_tiles), dim3(JDA_PACK_THREADS), 0, stream, jobs, n, table, bpp, bgr);
+    else if (es == 4u) JDA_LAUNCH((jda_pack_tiles<HWC, 4>), dim3(n_tiles), dim3(JDA_PACK_THREADS), 0, stream, jobs, n, table, bpp, bgr);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// n jobs of one source pixel size, layout and element size; n_tiles = the sum of their tiles (the jobs carry where each one's begin)
+extern "C" hipError_t jda_launch_pack(const jda_pack_job *jobs, uint32_t n, uint32_t n_tiles, int hwc, uint32_t es, const uint8_t *table,
+                                      uint32_t bpp, uint32_t bgr, hipStream_t stream)
+{
+    if (n == 0 || n_tiles == 0) return hipSuccess;
+    if ((bpp != 1u && bpp != 4u) || (hwc && bpp != 4u) || (es > 1u && !table)) return hipErrorInvalidValue;
+    return hwc ? launch_pack<1>(es, jobs, n, n_tiles, table, bpp, bgr, stream) : launch_pack<0>(es, jobs, n, n_tiles, table, bpp, bgr, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
 // jda_coef_tiles<MODE>: tiles decoded from coefficient images (jda_ct_* in jda_device_core.h: the load phase that stands in for
 // P1, then the decode kernel's own list / column / row / colour stages).  A wavefront = a tile of the launch list, four to a
 // workgroup; a wavefront owns its share of the LDS, its own copy of the image's quantisers included -- the tiles of a workgroup may

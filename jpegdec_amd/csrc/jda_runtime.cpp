@@ -21,6 +21,7 @@
 #include <mutex>
 
 #include "jda_runtime_internal.h"
+#include "jda_pack_plan.h"
 
 extern "C" uint32_t jda_image_fast_mul(const jda_image *img);
 extern "C" uint32_t jda_image_general_p1(const jda_image *img);
@@ -1529,6 +1530,148 @@ int jda_decode_to_host_oriented(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, 
     jda_dev_image_free(ctx, dimg);
     if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
     return rc;
+}
+
+// ---- dense RGB / BGR / planar output (jda_pack_tiles in jda_kernels.hip; runs, vectors and the lane's walk: jda_device_core.h)
+// Check n jobs (jda_pack_plan.h) and upload their records, and wait for them as orient_upload does; pack_launch then queues the kernel.
+struct pack_plan { void *block; uint32_t n, n_tiles, es, hwc, bpp, bgr; const uint8_t *table; };
+static int pack_upload(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t src_bytes_per_pixel, const int32_t *rects, int32_t layout_flags, int32_t elem_type,
+                       const void *table, void *const *dst, pack_plan *plan)
+{
+    plan->block = NULL; plan->n = (uint32_t)n; plan->n_tiles = 0;
+    jda_pack_plan_out P;
+    const int rc = jda_pack_plan_jobs(n, src, src_bytes_per_pixel, rects, layout_flags, elem_type, table, dst, &P);
+    if (rc != JDA_SUCCESS) return rc;
+    plan->es = P.es; plan->hwc = P.hwc; plan->bpp = (uint32_t)src_bytes_per_pixel; plan->bgr = (layout_flags & JDA_PACK_BGR) ? 1u : 0u;
+    plan->table = (const uint8_t *)table;
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, align16(P.jobs.size() * sizeof(jda_pack_job)));
+    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(pack jobs)");
+    e = hipMemcpyAsync(blk, P.jobs.data(), P.jobs.size() * sizeof(jda_pack_job), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { jda_pool_free(ctx, blk); return jda_set_err(ctx, e, "pack jobs"); }
+    plan->block = blk; plan->n_tiles = P.n_tiles;
+    return JDA_SUCCESS;
+}
+static int pack_launch(jda_ctx *ctx, const pack_plan &plan)
+{
+    const hipError_t e = jda_launch_pack((const jda_pack_job *)plan.block, plan.n, plan.n_tiles, (int)plan.hwc, plan.es, plan.table, plan.bpp, plan.bgr, ctx->stream);
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_pack_tiles");
+}
+
+size_t jda_pack_bytes(int32_t w, int32_t h, int32_t channels, int32_t elem_type)
+{
+    const uint32_t es = jda_pack_elem_bytes(elem_type);
+    if (w <= 0 || h <= 0 || channels <= 0 || !es) return 0;
+    return (size_t)w * (size_t)h * (size_t)channels * es;
+}
+
+int jda_pack_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t src_bytes_per_pixel, const int32_t *rects,
+                      int32_t layout_flags, int32_t elem_type, const void *table, void *const *dst)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0) return JDA_INVALID_PARAMETER;
+    { const int frc = jda_pack_check_format(src_bytes_per_pixel, layout_flags, elem_type, table); if (frc != JDA_SUCCESS) return frc; }
+    if (n == 0) return JDA_SUCCESS;
+    (void)hipSetDevice(ctx->device);
+    pack_plan plan;
+    int rc = pack_upload(ctx, n, src, src_bytes_per_pixel, rects, layout_flags, elem_type, table, dst, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = pack_launch(ctx, plan);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, plan.block);
+    if (rc != JDA_SUCCESS) return rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_pack_surfaces");
+}
+
+int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, int32_t layout_flags, int32_t elem_type,
+                              const void *table, void *host_out, size_t out_bytes, int32_t *w, int32_t *h, int32_t *mcus_decoded)
+{
+    if (mcus_decoded) *mcus_decoded = 0;
+    if (w) *w = 0;
+    if (h) *h = 0;
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!jpeg || !host_out) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    int32_t err = JDA_SUCCESS;
+    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
+    if (!img) return err;
+    const jda_image_info I = *jda_image_get_info(img);
+    int32_t pixel_type = (I.ncomp == 1 || (options & JDA_LUMA_ONLY)) ? JDA_EIGHT_BIT_GRAYSCALE : JDA_RGB8888;
+    int bpp, ow, oh, cw, ch;
+    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
+    const uint32_t es = jda_pack_elem_bytes(elem_type), channels = pixel_type == JDA_RGB8888 ? 3u : 1u;
+    // (the table is HOST memory here: its alignment does not matter, the device copy's does)
+    if (rc == JDA_SUCCESS) rc = jda_pack_check_format(bpp, layout_flags, elem_type, table ? (const void *)16 : NULL);
+    const size_t dense = rc == JDA_SUCCESS ? jda_pack_bytes(ow, oh, (int32_t)channels, elem_type) : 0;
+    if (rc == JDA_SUCCESS && (ow > cw || oh > ch || out_bytes < dense)) rc = JDA_INVALID_PARAMETER;
+    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
+    if (w) *w = ow;
+    if (h) *h = oh;
+    jda_dev_image *dimg = jda_upload(ctx, img, &err);
+    uint32_t nok = 0;
+    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
+    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
+    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
+    jda_image_free(img);
+    if (!dimg) return err;
+    const int cpitch = (int)align16((size_t)cw * bpp);
+    const size_t cbytes = (size_t)cpitch * ch, tbytes = table ? (size_t)channels * 256u * es : 0;
+    uint8_t *dsurf = NULL;                              // the decoded canvas, the dense result and the table behind it
+    if (jda_pool_alloc(ctx, (void **)&dsurf, cbytes + align16(dense) + tbytes) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
+    uint8_t *ddense = dsurf + cbytes, *dtable = table ? ddense + align16(dense) : NULL;
+    jda_output C, S;
+    C.pixels = dsurf; C.pitch_bytes = cpitch; C.width_px = cw; C.rows = ch;
+    S = C; S.width_px = ow; S.rows = oh;                // the visible rectangle of the canvas
+    jda_batch *b = jda_batch_create(ctx, 1, &dimg, &C, &pixel_type, &options, &err);
+    rc = err;
+    if (b) {
+        // what has to wait for the host -- the table and the job record -- first; then decode, pack and the copy back are queued back to back
+        pack_plan plan;
+        plan.block = NULL;
+        if (table && hipMemcpyAsync(dtable, table, tbytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = JDA_ERROR_HIP;
+        void *const dsts[1] = { ddense };
+        if (rc == JDA_SUCCESS) rc = pack_upload(ctx, 1, &S, bpp, NULL, layout_flags, elem_type, dtable, dsts, &plan);
+        if (rc == JDA_SUCCESS && !complete) (void)hipMemsetAsync(dsurf, 0, cbytes, ctx->stream);       // (the MCUs a bad stream does not reach are zeros before they are packed)
+        if (rc == JDA_SUCCESS) rc = jda_batch_decode(ctx, b);
+        if (rc == JDA_SUCCESS) rc = pack_launch(ctx, plan);
+        if (rc == JDA_SUCCESS) {
+            hipError_t e = hipMemcpyAsync(host_out, ddense, dense, hipMemcpyDeviceToHost, ctx->stream);
+            { const hipError_t es2 = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es2; }
+            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+        } else (void)hipStreamSynchronize(ctx->stream);
+        if (plan.block) jda_pool_free(ctx, plan.block);
+        jda_batch_destroy(ctx, b);
+    }
+    jda_pool_free(ctx, dsurf);
+    jda_dev_image_free(ctx, dimg);
+    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
+    return rc;
+}
+
+// Measuring hook of tools/pack_bench.py (not part of the public header): the pack launch between the context's two timer events on its
+// stream -- the job records go up before the first event.  ms[k]: repeat k.
+int jda_internal_pack_time(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t src_bytes_per_pixel, const int32_t *rects, int32_t layout_flags,
+                           int32_t elem_type, const void *table, void *const *dst, int32_t reps, float *ms)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n <= 0 || reps <= 0 || !ms) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    pack_plan plan;
+    int rc = pack_upload(ctx, n, src, src_bytes_per_pixel, rects, layout_flags, elem_type, table, dst, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < reps && rc == JDA_SUCCESS && e == hipSuccess; k++) {
+        e = hipEventRecord(ctx->ev_start, ctx->stream);
+        if (e == hipSuccess) rc = pack_launch(ctx, plan);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, plan.block);
+    if (rc != JDA_SUCCESS) return rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_pack_time");
 }
 
 // Measuring hooks of tools/orient_bench.py (not part of the public header): the orient launch, and a device-to-device copy to hold it

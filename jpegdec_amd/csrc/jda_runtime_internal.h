@@ -113,6 +113,10 @@ extern "C" hipError_t jda_launch_checksum(const void *base, uint32_t pitch, uint
 extern "C" hipError_t jda_launch_dither(const jda_dither_job *jobs, uint32_t n, uint32_t max_w, uint32_t max_h, uint32_t *fail, hipStream_t stream);
 // n surfaces of one pixel size -> their EXIF orientations, one workgroup a destination tile; n_tiles: the length of the flat tile list
 extern "C" hipError_t jda_launch_orient(const jda_orient_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, hipStream_t stream);
+// n jobs of one source pixel size (bpp 1 or 4), layout (hwc: pixel-major, RGB8888 sources only) and element size (es 1: bytes, 2 / 4: through
+// `table`, device memory), one workgroup a tile of 4 KiB of destination; n_tiles: the length of the flat tile list
+extern "C" hipError_t jda_launch_pack(const jda_pack_job *jobs, uint32_t n, uint32_t n_tiles, int hwc, uint32_t es, const uint8_t *table,
+                                      uint32_t bpp, uint32_t bgr, hipStream_t stream);
 extern "C" hipError_t jda_launch_segscan_tail(const jda_segscan_params *params, uint32_t n_images, uint32_t max_segs, uint32_t first_round, uint32_t max_round, hipStream_t stream);
 extern "C" hipError_t jda_launch_filter(const jda_filter_params *params, uint32_t n_images, uint32_t max_raw_len, hipStream_t stream);
 extern "C" hipError_t jda_launch_fill_strips(const jda_strips_params *params, uint32_t n_images, uint32_t max_tiles, hipStream_t stream);

@@ -1,0 +1,109 @@
+"""Decoded images as torch tensors on the GPU that decoded them: a Pipeline batch into scratch canvases, then ONE jda_pack_surfaces launch
+straight into the tensors' memory (include/jpegdec_amd.h: dense RGB / BGR or planar CHW, uint8 or float through a lookup table).
+torch is imported when decode_to_tensors runs, not when the package is.  One process, one HIP runtime: a torch build that ships its own
+(a wheel does) must be imported BEFORE libjpegdec_amd.so is loaded (before the first Context), so that the library binds to the runtime
+torch already brought; the other way round the process holds two runtimes, torch finds no GPU, and decode_to_tensors says so."""
+import ctypes as C
+
+import numpy as np
+
+from . import binding as B
+
+
+def _np_dtype(dtype):
+    """numpy's float16 / float32 / uint8 for a numpy or torch dtype (or their names)"""
+    name = str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+    try:
+        return {"uint8": np.uint8, "float16": np.float16, "half": np.float16, "float32": np.float32, "float": np.float32}[name]
+    except KeyError:
+        raise ValueError("no packed element type for dtype %r: uint8, float16 or float32" % (dtype,))
+
+
+def normalise_table(mean, std, dtype=np.float32):
+    """The lookup table of the usual input normalisation: table[c][v] = (v / 255 - mean[c]) / std[c], worked out in float64 and cast to
+    dtype (float16 or float32) -- a numpy array [len(mean), 256] for pack_surfaces / decode_packed_to_host / decode_to_tensors.  The channel
+    is the DESTINATION channel: with BGR output, mean[0] is blue's."""
+    mean, std = np.atleast_1d(np.asarray(mean, np.float64)), np.atleast_1d(np.asarray(std, np.float64))
+    if mean.shape != std.shape or mean.ndim != 1:
+        raise ValueError("mean and std: one value per channel each")
+    t = (np.arange(256, dtype=np.float64)[None, :] / 255.0 - mean[:, None]) / std[:, None]
+    return np.ascontiguousarray(t.astype(_np_dtype(dtype)))
+
+
+def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False):
+    """files (JPEG bytes, all colour or all gray) -> tensors on cuda:<ctx.device>.  layout "CHW" or "HWC"; dtype torch.uint8 (default), or
+    torch.float16 / torch.float32 with table = [C, 256] values of that type (normalise_table; numpy or torch).  options: the decode option
+    bits of every file (a JDA_SCALE_* bit, JDA_LUMA_ONLY: one channel).  Returns a list of [C,H,W] / [H,W,C] tensors, or, when all images
+    have one size, ONE [N,C,H,W] / [N,H,W,C] tensor.  A file that fails to decode raises JdaError with its status."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("torch sees no GPU in this process: if libjpegdec_amd.so was loaded first (a Context exists) and torch ships a HIP "
+                           "runtime of its own, the process holds two runtimes -- import torch before the first jpegdec_amd.Context")
+    dtype = torch.uint8 if dtype is None else dtype
+    npdt = _np_dtype(dtype)
+    elem = {np.uint8: B.PACK_U8, np.float16: B.PACK_F16, np.float32: B.PACK_F32}[npdt]
+    es = np.dtype(npdt).itemsize
+    if layout not in ("CHW", "HWC"):
+        raise ValueError("layout: 'CHW' or 'HWC'")
+    flags = (B.PACK_CHW if layout == "CHW" else B.PACK_HWC) | (B.PACK_BGR if bgr else 0)
+    files = list(files)
+    n = len(files)
+    device = torch.device("cuda", ctx.device)
+    if n == 0:
+        return []
+    infos = []
+    for f in files:
+        info = B.ImageInfo()
+        rc = ctx.lib.jda_parse(f, len(f), C.byref(info))
+        if rc != 0:
+            raise B.JdaError(rc, "jda_parse")
+        infos.append(info)
+    gray = [i.ncomp == 1 or bool(options & B.LUMA_ONLY) for i in infos]
+    if any(gray) != all(gray):
+        raise ValueError("gray and colour files in one call: one jda_pack_surfaces launch takes one source format")
+    pt, channels = (B.GRAY8, 1) if gray[0] else (B.RGB8888, 3)
+    geos = [B.output_geometry(i, pt, options) for i in infos]
+    bpp = geos[0]["bpp"]
+    pitches = [(g["canvas_w"] * bpp + 15) & ~15 for g in geos]
+    offs, total = [], 0
+    for g, p in zip(geos, pitches):
+        offs.append(total)
+        total += (p * g["canvas_h"] + 255) & ~255
+    sizes = [(g["out_h"], g["out_w"]) for g in geos]
+    same = all(s == sizes[0] for s in sizes)
+
+    def shape(h, w):
+        return (channels, h, w) if layout == "CHW" else (h, w, channels)
+    if same:
+        whole = torch.empty((n,) + shape(*sizes[0]), dtype=dtype, device=device)
+        per = whole[0].numel() * es
+        ptrs = [whole.data_ptr() + k * per for k in range(n)]          # (image k at its own, unaligned, offset)
+        result = whole
+    else:
+        result = [torch.empty(shape(h, w), dtype=dtype, device=device) for h, w in sizes]
+        ptrs = [t.data_ptr() for t in result]
+    dev_table = None
+    if table is not None:
+        host = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+        if host.dtype != npdt or host.size != channels * 256:
+            raise ValueError("table: %d x 256 values of %s" % (channels, np.dtype(npdt).name))
+        dev_table = torch.from_numpy(np.ascontiguousarray(host).reshape(channels, 256)).to(device)
+        torch.cuda.synchronize(device)                                   # (the table's copy ran on torch's stream)
+    base = ctx.malloc(total)
+    try:
+        pipe = B.Pipeline(ctx, max_images=n, depth=1)
+        try:
+            outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
+            status = pipe.wait(pipe.submit(files, outs, [pt] * n, [options] * n))
+        finally:
+            pipe.close()
+        for k, st in enumerate(status):
+            if st != 0:
+                raise B.JdaError(st, "file %d of the batch" % k)
+        # the VISIBLE rectangles of the canvases, one launch, straight into the tensors
+        B.pack_surfaces(ctx, [(base + offs[k], pitches[k], geos[k]["out_w"], geos[k]["out_h"]) for k in range(n)], bpp, ptrs, flags, elem,
+                        None if dev_table is None else dev_table.data_ptr())
+    finally:
+        ctx.free(base)
+    return result
