@@ -285,7 +285,12 @@ jda_batch *jda_batch_create(jda_ctx *ctx, int32_t n, jda_dev_image *const *image
 /* The same with a rectangle of MCUs per image: mcu_rects[4 i ..] = {mx0, my0, mx1, my1} (half open, MCU units), or NULL for whole
  * images.  Only the tiles of the rectangle are launched -- the crop-aware decode (the reference skips the MCU rows above the crop
  * and the MCUs left and right of it, jpeg.inl:5111, 5134-5137; here they are not even visited: the per-block index lets a tile start
- * at any MCU).  The surface keeps the whole image's geometry; pixels outside the rectangle are not written. */
+ * at any MCU).  The surface keeps the whole image's geometry; pixels outside the rectangle are not written.
+ * A rectangle is clamped, never refused: a negative mx0 / my0 counts as 0, mx1 / my1 above the image's MCU counts as those counts, a
+ * negative mx1 / my1 as 0.  What is left empty -- mx0 >= mx1 or my0 >= my1 after the clamp: an inverted rectangle, one that lies behind
+ * the image -- launches no tile and writes nothing; the image keeps its place in the plan and its status is what the stream's is
+ * (JDA_SUCCESS for a good file).  The rectangle of a hole (images[i] == NULL) is not looked at.  Each MCU row of a rectangle is cut into
+ * tiles from the rectangle's own first MCU, so jda_batch_stats::tiles is, per image, (my1 - my0) * ceil((mx1 - mx0) / MCUs per tile). */
 jda_batch *jda_batch_create_rect(jda_ctx *ctx, int32_t n, jda_dev_image *const *images,
                                  const jda_output *outputs, const int32_t *pixel_types,
                                  const int32_t *options, const int32_t *mcu_rects, int32_t *err);

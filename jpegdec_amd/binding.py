@@ -450,8 +450,9 @@ def upload_batch(ctx: Context, prepared_list):
 class Batch:
     """Launch plan over resident images (jda_batch_create / jda_batch_decode)."""
 
-    def __init__(self, ctx: Context, images, outputs, pixel_types, options):
-        """outputs: list of (device_ptr, pitch_bytes, width_px, rows)."""
+    def __init__(self, ctx: Context, images, outputs, pixel_types, options, mcu_rects=None):
+        """outputs: list of (device_ptr, pitch_bytes, width_px, rows).  mcu_rects: None, or one (mx0, my0, mx1, my1) per image
+        (jda_batch_create_rect; an image's entry is ignored where the image is a hole and may be None there)."""
         n = len(images)
         self.ctx = ctx
         self.n = n
@@ -460,7 +461,13 @@ class Batch:
         pts = (C.c_int32 * n)(*pixel_types)
         opts = (C.c_int32 * n)(*options)
         err = C.c_int32(0)
-        self.handle = ctx.lib.jda_batch_create(ctx.handle, n, himgs, outs, pts, opts, C.byref(err))
+        if mcu_rects is None:
+            self.handle = ctx.lib.jda_batch_create(ctx.handle, n, himgs, outs, pts, opts, C.byref(err))
+        else:
+            if len(mcu_rects) != n or any(r is None and im is not None for r, im in zip(mcu_rects, images)):
+                raise ValueError("mcu_rects: one rectangle per image")
+            rects = (C.c_int32 * (4 * n))(*[v for r in mcu_rects for v in (r if r is not None else (0, 0, 0, 0))])
+            self.handle = ctx.lib.jda_batch_create_rect(ctx.handle, n, himgs, outs, pts, opts, rects, C.byref(err))
         if not self.handle:
             raise JdaError(err.value, "jda_batch_create: " + (ctx.lib.jda_last_hip_error(ctx.handle) or b"").decode())
         st = BatchStats()
@@ -863,19 +870,28 @@ def kernel_launch_counts() -> dict:
     return out
 
 
-def decode_to_host_rect(ctx: Context, jpeg: bytes, pixel_type, options, mcu_rect):
-    """jda_decode_to_host_rect: (rc, canvas, geometry, (tiles launched, tiles of the whole image))"""
+def decode_to_host_rect(ctx: Context, jpeg: bytes, pixel_type, options, mcu_rect, out=None):
+    """jda_decode_to_host_rect: (rc, canvas, geometry, (tiles launched, tiles of the whole image)); the geometry carries "mcus_decoded".
+    out: the caller's 2-D uint8 array to decode into -- at least canvas_h rows, its row stride is the pitch handed to the call (at least
+    a canvas row's bytes), its last axis contiguous; it is returned as the canvas."""
     info = ImageInfo()
     rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
     if rc != 0:
         raise JdaError(rc, "jda_parse")
     g = output_geometry(info, pixel_type, options)
-    canvas = np.zeros((g["canvas_h"], g["canvas_w"] * g["bpp"]), dtype=np.uint8)
+    if out is None:
+        canvas = np.zeros((g["canvas_h"], g["canvas_w"] * g["bpp"]), dtype=np.uint8)
+    else:
+        canvas = out
+        if (canvas.dtype != np.uint8 or canvas.ndim != 2 or not canvas.flags["WRITEABLE"] or canvas.strides[1] != 1 or canvas.shape[0] < g["canvas_h"]
+                or canvas.shape[1] < g["canvas_w"] * g["bpp"] or canvas.strides[0] < canvas.shape[1]):
+            raise ValueError("out: a writable 2-D uint8 array of at least canvas_h rows x canvas_w * bpp bytes")
     rect = (C.c_int32 * 4)(*mcu_rect) if mcu_rect is not None else None
     tiles = (C.c_int32 * 2)()
     nok = C.c_int32(0)
-    rc = ctx.lib.jda_decode_to_host_rect(ctx.handle, jpeg, len(jpeg), pixel_type, options, rect, canvas.ctypes.data_as(_P), canvas.shape[1],
+    rc = ctx.lib.jda_decode_to_host_rect(ctx.handle, jpeg, len(jpeg), pixel_type, options, rect, canvas.ctypes.data_as(_P), canvas.strides[0],
                                          canvas.shape[0], C.byref(nok), tiles)
+    g["mcus_decoded"] = nok.value
     return rc, canvas, g, (tiles[0], tiles[1])
 
 

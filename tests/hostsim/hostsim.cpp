@@ -27,6 +27,10 @@ extern "C" void hostsim_set_chunked(int on) { g_use_cont = on; }      // (the se
 extern "C" const uint32_t *jda_image_block_cont(const jda_image *img, const uint32_t **cont_first, uint32_t *n_cont);
 static int g_reverse_tiles = 0;   // tests run the tiles in reverse order too: results must not depend on which wave finishes first
 extern "C" void hostsim_set_reverse(int on) { g_reverse_tiles = on; }
+// the MCU rectangle of a crop-aware decode (jda_append_strips' rect, as jda_batch_create_rect hands it on): off = the whole image
+static int g_use_rect = 0;
+static int32_t g_rect[4] = { 0, 0, 0, 0 };
+extern "C" void hostsim_set_rect(int on, int x0, int y0, int x1, int y1) { g_use_rect = on; g_rect[0] = x0; g_rect[1] = y0; g_rect[2] = x1; g_rect[3] = y1; }
 // the scan window of the emulated wavefront: 1,024 bytes by default; tests shrink it to exercise the HBM fall-back of the bit reader, or
 // set a layout's own WIN_BYTES (hostsim_lds_layout).  Each layout caps it at its large-window WIN_BYTES: (1 << 20) = the most there is
 static uint32_t g_window_bytes = 1024;
@@ -435,7 +439,7 @@ extern "C" int hostsim_decode(const uint8_t *jpeg, int len, int pixel_type, int 
     if (g_use_cont && !g_prescan_used) { uint32_t nc = 0; D.blk_cont = jda_image_block_cont(img, &D.blk_cont_first, &nc); }
     D.tables = jda_image_tables(img, &n);
     std::vector<jda_strip> strips;
-    jda_append_strips(strips, 0, D.mcus_x, D.mcus_y, D.mode);
+    jda_append_strips(strips, 0, D.mcus_x, D.mcus_y, D.mode, 0, g_use_rect ? g_rect : nullptr);
     if (D.scale_shift == 2 && D.strip_mcus == 0) {                    // JDA_LIST_QUARTER (jda_list_index): the 1/4-scale kernel
         switch (D.mode) {
         case JDA_MODE_GRAY: run_quarter_tiles<JDA_MODE_GRAY>(D, strips); break;

@@ -92,12 +92,20 @@ def test_error_codes(product_class):
 CROPS = [(50, 50, 125, 170), (0, 0, 64, 64), (100, 20, 200, 100), (16, 16, 16, 16), (0, 180, 64, 30)]
 
 
-@pytest.mark.parametrize("name", ["c420_640x368_rstrow", "c444_600x16", "c420_1280x720", "gray_333x217"])
+@pytest.mark.parametrize("name", ["c420_640x368_rstrow", "c444_600x16", "c420_1280x720", "gray_333x217", "c422_333x217", "c440_200x120"])
 def test_crop_area_matches_the_reference(name, product_class, ref_scalar):
     """setCropArea (jpeg.inl:682-727) + the skip/draw bookkeeping of :5111, :5134-5137, :5300-5336 --
     the reference's own test 2 (MacOS/JPEGDEC_Test/JPEGDEC_Test/main.cpp) checks the drawn union only;
-    here every strip and every pixel is compared with the reference itself."""
+    here every strip and every pixel is compared with the reference itself.
+    A crop whose x + w passes the image's width is widened by setCropArea to width - one MCU (:721) and overhangs the image: the row's
+    last strip is then drawn at the full buffer width although the MCUs stop at the image's edge (:5300, :5307), and right of that
+    edge the strip shows what the reference's pixel buffer held before the decode -- the scratch bytes of its Huffman table builder,
+    no pixels (c440_200x120 with (100, 20, 200, 100): 13 MCUs = 104 of 128 columns).  The class delivers zeros there; the columns
+    of the image, up to its right edge, are compared."""
+    import jpegdec_amd as J
     jpeg = jpeg_for(name)
+    prepared = J.PreparedImage(jpeg)                  # (its info lives as long as it does)
+    info = prepared.info
     checked = 0
     for crop in CROPS:
         for pt, opt in ((RGB565_LE, 0), (RGB8888, 0), (GRAY8, 0)):
@@ -111,8 +119,13 @@ def test_crop_area_matches_the_reference(name, product_class, ref_scalar):
                 continue
             assert a["rc"] == 1 and a["last_error"] == 0
             assert np.array_equal(a["log"], b["log"]), (name, crop, pt)
-            assert np.array_equal(a["canvas"], b["canvas"]), (name, crop, pt)
+            rx, ry, rw, rh = J.crop_round(info, *crop)
+            inside = (info.width - rx) * a["bpp"]      # bytes of a canvas row (x = 0 is the crop's left edge) inside the image
+            assert np.array_equal(a["canvas"][:, :inside], b["canvas"][:, :inside]), (name, crop, pt)
+            assert not a["canvas"][:, inside:].any(), (name, crop, pt)
+            assert rx + rw > info.width or not b["canvas"][:, inside:].any(), (name, crop, pt)      # (whole canvases equal unless the crop overhangs)
             checked += 1
+    prepared.close()
     assert checked >= 6
 
 
