@@ -8,10 +8,10 @@ CXX   ?= g++
 ARCH  ?= gfx950
 CSRC  = jpegdec_amd/csrc
 EXTRA ?=
-HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared -fwrapv -pthread -Wall -Wno-unused-function -Iinclude $(EXTRA)
+HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared -fwrapv -pthread -Wall -Wno-unused-function -Xarch_host -ffp-contract=off -Iinclude $(EXTRA)
 LIB = jpegdec_amd/libjpegdec_amd.so
 LIB_SRCS = $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp $(CSRC)/jda_runtime.cpp $(CSRC)/jda_pipeline.cpp $(CSRC)/jda_node.cpp $(CSRC)/jda_kernels.hip $(CSRC)/JPEGDEC.cpp
-LIB_DEPS = $(LIB_SRCS) $(CSRC)/jda_runtime_internal.h $(CSRC)/jda_internal.h $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_pack_plan.h include/jpegdec_amd.h include/JPEGDEC.h
+LIB_DEPS = $(LIB_SRCS) $(CSRC)/jda_runtime_internal.h $(CSRC)/jda_internal.h $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_pack_plan.h $(CSRC)/jda_resize_plan.h include/jpegdec_amd.h include/JPEGDEC.h
 
 all: lib oracle hostsim classshim
 
@@ -22,7 +22,7 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so
+hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
@@ -41,6 +41,11 @@ tests/hostsim/libjda_coefsim.so: tests/hostsim/coef_sim.cpp tests/hostsim/coef_t
 # the pack kernel's vector schedule, lane by lane, its row-major twin and the argument checks of jda_pack_surfaces on the CPU (tests/test_pack_cpu.py) -- test infrastructure
 tests/hostsim/libjda_packsim.so: tests/hostsim/pack_sim.cpp tests/hostsim/pack_twin.h $(CSRC)/jda_pack_plan.h $(CSRC)/jda_device_core.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/pack_sim.cpp
+
+# the resize kernel's two passes, lane by lane, its row-major twin, the host's tap tables and the argument checks of jda_resize_surfaces on
+# the CPU (tests/test_resize_cpu.py) -- test infrastructure.  -ffp-contract=off: the taps are Pillow's only in Pillow's order of operations
+tests/hostsim/libjda_resizesim.so: tests/hostsim/resize_sim.cpp tests/hostsim/resize_twin.h $(CSRC)/jda_resize_plan.h $(CSRC)/jda_device_core.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -ffp-contract=off -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/resize_sim.cpp
 
 # the reference-API driver (oracle/ref_shim.cpp) built against the product's JPEGDEC class -- test infrastructure
 classshim: tests/libjpegdec_class_shim.so
@@ -104,7 +109,7 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
+	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib oracle hostsim classshim classcpu cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean

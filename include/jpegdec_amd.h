@@ -67,7 +67,7 @@ enum {
     /* ours (the reference has nothing like it): decode EVERY scan of a progressive file to a full-size canvas instead of the 1/8
      * thumbnail of its first scan.  No effect on a baseline file.  With a JDA_SCALE_* bit: JDA_UNSUPPORTED_FEATURE.  Taken by
      * jda_decode_to_host / _ex / _flags (whole image); every other decode entry point -- jda_batch_create*, jda_pipeline_submit*,
-     * jda_node_submit* (per image, in status[]), jda_decode_to_host_rect / _bands / _strips / _oriented / _packed, jda_decode_dither_to_host and
+     * jda_node_submit* (per image, in status[]), jda_decode_to_host_rect / _bands / _strips / _oriented / _packed / _resized, jda_decode_dither_to_host and
      * any call with an MCU rectangle -- answers JDA_UNSUPPORTED_FEATURE for a progressive file asked for with it. */
     JDA_PROGRESSIVE_FULL = 256
 };
@@ -392,6 +392,26 @@ size_t jda_pack_bytes(int32_t w, int32_t h, int32_t channels, int32_t elem_type)
 int jda_pack_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t src_bytes_per_pixel, const int32_t *rects,
                       int32_t layout_flags, int32_t elem_type, const void *table, void *const *dst);
 
+/* ---- Decoded surfaces resized on the GPU: Pillow's Image.resize((ow, oh), Image.BILINEAR, box=(x, y, x + w, y + h)), bit for bit
+ * src[i] = a decoded surface resident in HBM, JDA_RGB8888 (bytes_per_pixel 4) or JDA_EIGHT_BIT_GRAYSCALE (1); dst[i] = the result,
+ * dst[i].width_px x dst[i].rows pixels of the same format: that IS the output size.  Both: pixels 16-byte aligned, pitch_bytes a multiple
+ * of 16 and >= width_px * bytes_per_pixel.  rects: {x, y, w, h} in pixels per image, inside width_px x rows; NULL: all of width_px x
+ * rows -- pass the visible size (jda_output_geometry's out_w x out_h), not the canvas, and the MCU padding is never sampled.
+ * The filter is Pillow's antialiased triangle ("BILINEAR" with reducing_gap unset): per axis scale = box / output size, support =
+ * max(scale, 1), 2 * ceil(support) + 1 taps at most per output coordinate, normalised and rounded to 22-bit fixed point on the HOST in
+ * double; out = clip8((2^21 + sum in * k) >> 22) per byte, the horizontal pass first into 8-bit intermediates, then the vertical one.
+ * All bytes of a pixel are channels: the fourth byte of RGB8888 is resampled like the others (Pillow's mode RGBX).  An axis whose size
+ * and box are unchanged comes out as it went in.  No byte of dst[i] outside width_px * bytes_per_pixel x rows is written.
+ * ONE launch on the context's stream (behind whatever decoded the surfaces there), synchronous.  n == 0 succeeds and launches nothing.
+ * JDA_INVALID_PARAMETER: a null or misaligned pointer; a pitch too small or not a multiple of 16; a rectangle that is empty or leaves the
+ * surface; an output size that is not positive; a side above 2^24; a pixel size other than 1 or 4; byte ranges of a destination and of any
+ * source, tap table or other destination that overlap.  JDA_UNSUPPORTED_FEATURE: an axis with more than JDA_RESIZE_MAX_KSIZE taps -- a
+ * downscale beyond 80 : 1 (every upscale has three) --, or a call whose tap tables ((2 + taps) * 4 bytes per output coordinate and axis;
+ * images with equal size, rectangle and output size on an axis share one) pass JDA_RESIZE_MAX_TABLE_BYTES. */
+#define JDA_RESIZE_MAX_KSIZE 161
+#define JDA_RESIZE_MAX_TABLE_BYTES (64u << 20)
+int jda_resize_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst);
+
 /* PCI bus id ("0000:8e:00.0") of the context's GPU, for NUMA placement of the host threads that feed it; buf >= 16 bytes */
 int jda_device_pci_bus_id(jda_ctx *ctx, char *buf, int32_t len);
 int jda_device_pci_bus_id_of(int32_t device, char *buf, int32_t len);      /* the same by device ordinal, without a context */
@@ -428,6 +448,18 @@ int jda_decode_dither_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
  * BEFORE the pack (table[c][0] behind it) and the whole result is still delivered. */
 int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, int32_t layout_flags, int32_t elem_type,
                               const void *table, void *host_out, size_t out_bytes, int32_t *w, int32_t *h, int32_t *mcus_decoded);
+/* jda_decode_to_host_ex followed by jda_resize_surfaces: prepare, upload, decode to a device canvas, resize rect = {x, y, w, h} (pixels of
+ * the visible image, jda_output_geometry's out_w x out_h at the options' scale; NULL: all of it) to out_w x out_h and copy back only those
+ * out_w * bpp x out_h bytes: row r at host_pixels + r * pitch_bytes, pitch_bytes >= out_w * bpp (any value), rows >= out_h.  pixel_type:
+ * JDA_RGB8888 or JDA_EIGHT_BIT_GRAYSCALE; any other: JDA_INVALID_PARAMETER.  Only the MCUs that hold a pixel the taps read are decoded
+ * (jda_batch_create_rect): tiles (may be NULL): [0] wavefront tiles launched, [1] tiles of the whole image.  The rectangle never leaves
+ * the visible image, so the MCU padding is never sampled.  Option bits, the default 1/8 thumbnail of a progressive file, refusals and
+ * codes as in jda_decode_to_host_ex; JDA_PROGRESSIVE_FULL on a progressive file: JDA_UNSUPPORTED_FEATURE; the limits of
+ * jda_resize_surfaces.  With JDA_DECODE_ERROR the MCUs from the bad one on are zeros BEFORE the resize and the whole result is still
+ * delivered. */
+int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *rect,
+                               int32_t out_w, int32_t out_h, void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded,
+                               int32_t *tiles);
 /* jda_decode_to_host_ex followed by the orientation: prepare, upload, decode to a device canvas, orient its visible rectangle into a second
  * device surface (jda_orient_surfaces) and copy back only the W' * bpp x H' bytes of jda_oriented_geometry: row r at host_pixels + r * pitch_bytes,
  * pitch_bytes >= W' * bpp (any value), rows >= H'.  orientation < 0: the file's; 0..8 as given (0, 1: the visible rectangle as it is); above

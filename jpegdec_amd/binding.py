@@ -13,6 +13,7 @@ PROGRESSIVE_FULL = 256      # ours: every scan of a progressive file at full siz
 PACK_HWC, PACK_CHW, PACK_BGR = 0, 1, 2      # pack_surfaces / decode_packed_to_host: layout flags (PACK_BGR is OR-ed in)
 PACK_U8, PACK_F16, PACK_F32 = 0, 1, 2       # .. element types
 PACK_DTYPES = {PACK_U8: np.uint8, PACK_F16: np.float16, PACK_F32: np.float32}
+RESIZE_MAX_KSIZE, RESIZE_MAX_TABLE_BYTES = 161, 64 << 20      # resize_surfaces: taps per output coordinate (a downscale of 80 : 1), tap tables of one call
 AUTO_ROTATE = 1      # the class's decode() applies the EXIF orientation; the C-ABI takes it as an argument (decode_oriented_to_host, orient_surfaces)
 
 ERROR_NAMES = {0: "JDA_SUCCESS", 1: "JDA_INVALID_PARAMETER", 2: "JDA_DECODE_ERROR",
@@ -134,6 +135,8 @@ _PROTOTYPES = [
     ("jda_pack_bytes", C.c_size_t, [C.c_int32] * 4),
     ("jda_pack_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     ("jda_decode_to_host_packed", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t] + [C.POINTER(C.c_int32)] * 3),
+    ("jda_resize_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output)]),
+    ("jda_decode_to_host_resized", C.c_int, [_P, C.c_char_p] + [C.c_int32] * 3 + [C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("jda_checksum_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("jda_device_pci_bus_id", C.c_int, [_P, C.c_char_p, C.c_int32]),
     ("jda_upload_batch_ex", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32)]),
@@ -832,6 +835,43 @@ def decode_packed_to_host(ctx: Context, jpeg: bytes, options=0, layout=PACK_HWC,
         return rc, None, g
     shape = (channels, h.value, w.value) if layout & PACK_CHW else (h.value, w.value, channels)
     return rc, flat[:w.value * h.value * channels].reshape(shape), g
+
+
+def resize_surfaces(ctx: Context, src, bytes_per_pixel, dst, rects=None):
+    """jda_resize_surfaces: src / dst = lists of (device_ptr, pitch_bytes, width_px, rows) of RGB8888 (4) or GRAY8 (1) surfaces -- a
+    destination's width_px x rows is the output size --, rects = list of (x, y, w, h) or None: all of width_px x rows.  Pillow's
+    resize(BILINEAR, box), bit for bit; one launch for all of them."""
+    n = len(src)
+    s = (Output * max(n, 1))(*[Output(*o) for o in src])
+    d = (Output * max(n, 1))(*[Output(*o) for o in dst])
+    r = None if rects is None else (C.c_int32 * max(4 * n, 1))(*[v for q in rects for v in q])
+    ctx.check(ctx.lib.jda_resize_surfaces(ctx.handle, n, s, bytes_per_pixel, r, d), "jda_resize_surfaces")
+
+
+def decode_resized_to_host(ctx: Context, jpeg: bytes, size, pixel_type=RGB8888, options=0, rect=None, out=None):
+    """jda_decode_to_host_resized: size = (out_w, out_h), rect = (x, y, w, h) in pixels of the visible image at the options' scale, or None:
+    all of it.  (rc, the resized pixels [out_h, out_w * bpp] uint8, geometry of the decode + "mcus_decoded", (tiles launched, tiles of the
+    whole image)).  out: the caller's 2-D uint8 array to decode into, its row stride is the pitch handed to the call."""
+    info = ImageInfo()
+    rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
+    if rc != 0:
+        raise JdaError(rc, "jda_parse")
+    out_w, out_h = size
+    bpp = 1 if pixel_type == GRAY8 else 4
+    pixels = out if out is not None else np.zeros((max(out_h, 1), max(out_w, 1) * bpp), dtype=np.uint8)
+    if pixels.dtype != np.uint8 or pixels.ndim != 2 or not pixels.flags["WRITEABLE"] or pixels.strides[1] != 1:
+        raise ValueError("out: a writable 2-D uint8 array, its last axis contiguous")
+    r = (C.c_int32 * 4)(*rect) if rect is not None else None
+    tiles = (C.c_int32 * 2)()
+    nok = C.c_int32(0)
+    rc = ctx.lib.jda_decode_to_host_resized(ctx.handle, jpeg, len(jpeg), pixel_type, options, r, out_w, out_h, pixels.ctypes.data_as(_P), pixels.strides[0],
+                                            pixels.shape[0], C.byref(nok), tiles)
+    try:
+        g = output_geometry(info, pixel_type, options)
+    except JdaError:
+        g = {}
+    g["mcus_decoded"] = nok.value
+    return rc, pixels, g, (tiles[0], tiles[1])
 
 
 def decode_resident(ctx: Context, prepared: PreparedImage, pixel_type=RGB8888, options=0):

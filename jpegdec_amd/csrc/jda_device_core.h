@@ -3597,6 +3597,137 @@ template <int HWC, int ES, class IO> JDA_HD void jda_pack_tile(const jda_pack_ge
     for (uint32_t r = 0; r < runs; r++) jda_pack_planar<ES>(G, r, vec, io);
 }
 
+// ---- jda_rs_*: decoded surfaces resized with an antialiased triangle filter -------------------------------------------
+// The result is Pillow's resize(BILINEAR, box): a horizontal pass into 8-bit intermediates, then a vertical pass, both
+//   out = clip8((2^21 + sum_x in[min + x] * k[x]) >> 22)     per byte of a pixel, 32-bit sum, k >= 0, sum(k) ~ 2^22
+// with the taps {min, cnt, k[ksize]} of every output coordinate made by the HOST in double (jda_resize_plan.h): the kernel is integer.
+// An axis table, in dwords: {min, cnt} of coordinate i at [2 i], its ksize coefficients at [2 out_size + i ksize].
+// A workgroup owns one output TILE: JDA_RS_TILE_DWORDS dwords of th <= JDA_RS_TILE_ROWS output rows -- a dword is a pixel of RGB8888
+// (its four bytes are four channels) or four neighbouring gray pixels; the vertical pass cannot tell them apart.
+//   1. horizontal (jda_rs_horizontal): the source rows [row0, row0 + span) that the tile's vertical taps read, resampled at the tile's
+//      columns into LDS, one LDS row of JDA_RS_TILE_DWORDS dwords a source row.  A lane = one dword column (tid & 63), a wave =
+//      JDA_RS_HROWS source rows at a time: a coefficient is loaded once for the four rows, and the four row loads are independent.
+//      Neighbouring lanes load `scale` pixels apart: strided, but tap x + 1 reads the neighbouring dword of the same line.
+//   2. the workgroup barrier
+//   3. vertical (jda_rs_vertical): a lane = one aligned 16-byte vector (tid & 15) of one output row (tid >> 4): it sums its four
+//      dword columns over the row's taps with ds_read_b128 and stores the vector.  An LDS row is exactly the 256-byte bank row, so the
+//      sixteen vectors of a row lie on sixteen different slots whatever the row: every lane group of a ds_read_b128 ({0-3, 12-15,
+//      20-27}, ..) holds sixteen different tid & 15, i.e. no bank conflict, without padding.  Only a row's last vector may be partial:
+//      it goes out as the dwords and bytes in front of out_w * bpp.
+// The host picks th per job so that span <= JDA_RS_LDS_ROWS for every tile (one row at the ksize cap).  Memory goes through an IO
+// policy: the kernel (jda_kernels.hip) and the lane-by-lane run on the CPU (tests/hostsim/resize_sim.cpp) are the same code.
+#define JDA_RS_THREADS 256
+#define JDA_RS_TILE_DWORDS 64u
+#define JDA_RS_TILE_ROWS 16u
+#define JDA_RS_LDS_ROWS 192u                 // 48 KiB: the LDS budget of a tile
+#define JDA_RS_HROWS 4u
+struct jda_rs_geo {                          // a job, wave-uniform
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t src_pitch, dst_pitch, out_w, out_h, htab, vtab, hk, vk, th;
+};
+// the job a tile of the flat list belongs to (as jda_orient_find_job)
+JDA_HD uint32_t jda_rs_find_job(const jda_resize_job *jobs, uint32_t n, uint32_t tile)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (JDA_G(const jda_resize_job, jobs)[mid].tile0 <= tile) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+JDA_HD uint32_t jda_rs_clip(uint32_t acc)
+{
+    const uint32_t v = (acc + (1u << 21)) >> 22;
+    return v < 255u ? v : 255u;
+}
+// tile row ty of a job: its first output row, and the source rows [row0, row0 + span) its vertical taps read (min and min + cnt rise
+// with the coordinate, so the first and the last row of the tile bound them)
+template <class IO> JDA_HD void jda_rs_tile_rows(const jda_rs_geo &G, uint32_t ty, IO &io, uint32_t &oy0, uint32_t &row0, uint32_t &span)
+{
+    oy0 = ty * G.th;
+    const uint32_t last = (oy0 + G.th < G.out_h ? oy0 + G.th : G.out_h) - 1u;
+    row0 = io.ld_tap(G.vtab + 2u * oy0);
+    span = io.ld_tap(G.vtab + 2u * last) + io.ld_tap(G.vtab + 2u * last + 1u) - row0;
+}
+template <int BPP, class IO> JDA_HD void jda_rs_horizontal(const jda_rs_geo &G, uint32_t tx, uint32_t row0, uint32_t span, uint32_t tid, IO &io)
+{
+    const uint32_t S = BPP == 4 ? 1u : 4u, C = BPP == 4 ? 4u : 1u;          // output pixels of a dword, channels of a pixel
+    const uint32_t col = tid & (JDA_RS_TILE_DWORDS - 1u), wave = tid / JDA_RS_TILE_DWORDS;
+    const uint32_t dwc = tx * JDA_RS_TILE_DWORDS + col, row_bytes = G.out_w * (uint32_t)BPP;
+    if ((dwc & ~3u) * 4u >= row_bytes) return;                             // (no vector of the row holds this column)
+    const bool live = dwc * 4u < row_bytes;                                // (else: behind the row in its last vector, zeros)
+    for (uint32_t base = wave * JDA_RS_HROWS; base < span; base += JDA_RS_THREADS / JDA_RS_TILE_DWORDS * JDA_RS_HROWS) {
+        const uint8_t *rp[JDA_RS_HROWS];
+        uint32_t res[JDA_RS_HROWS];
+#pragma unroll
+        for (uint32_t j = 0; j < JDA_RS_HROWS; j++) {
+            const uint32_t r = base + j < span ? base + j : span - 1u;     // (behind the span: the last row again, not stored)
+            rp[j] = G.src + (size_t)(row0 + r) * G.src_pitch;
+            res[j] = 0u;
+        }
+        if (live) {
+#pragma unroll
+            for (uint32_t s = 0; s < S; s++) {
+                const uint32_t ox = dwc * S + s;
+                if (ox >= G.out_w) continue;
+                const uint32_t xmin = io.ld_tap(G.htab + 2u * ox), cnt = io.ld_tap(G.htab + 2u * ox + 1u), kb = G.htab + 2u * G.out_w + ox * G.hk;
+                uint32_t acc[JDA_RS_HROWS][4];
+#pragma unroll
+                for (uint32_t j = 0; j < JDA_RS_HROWS; j++)
+#pragma unroll
+                    for (uint32_t c = 0; c < 4u; c++) acc[j][c] = 0u;
+                for (uint32_t x = 0; x < cnt; x++) {
+                    const uint32_t k = io.ld_tap(kb + x) & 0xffffffu, off = (xmin + x) * (uint32_t)BPP, sh = (off & 3u) * 8u;
+#pragma unroll
+                    for (uint32_t j = 0; j < JDA_RS_HROWS; j++) {
+                        const uint32_t d = io.ld32(rp[j] + (off & ~3u)) >> sh;
+#pragma unroll
+                        for (uint32_t c = 0; c < C; c++) acc[j][c] += jda_umul24((d >> (8u * c)) & 0xffu, k);
+                    }
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < JDA_RS_HROWS; j++)
+#pragma unroll
+                    for (uint32_t c = 0; c < C; c++) res[j] |= jda_rs_clip(acc[j][c]) << (8u * (BPP == 4 ? c : s));
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < JDA_RS_HROWS; j++)
+            if (base + j < span) io.lds_wr((base + j) * JDA_RS_TILE_DWORDS + col, res[j]);
+    }
+}
+template <int BPP, class IO> JDA_HD void jda_rs_vertical(const jda_rs_geo &G, uint32_t tx, uint32_t oy0, uint32_t row0, uint32_t tid, IO &io)
+{
+    const uint32_t vc = tid & 15u, orow = tid >> 4, oy = oy0 + orow, row_bytes = G.out_w * (uint32_t)BPP;
+    const uint32_t b0 = (tx * JDA_RS_TILE_DWORDS + vc * 4u) * 4u;           // the vector's first byte in its destination row
+    if (orow >= G.th || oy >= G.out_h || b0 >= row_bytes) return;
+    const uint32_t ymin = io.ld_tap(G.vtab + 2u * oy), cnt = io.ld_tap(G.vtab + 2u * oy + 1u), kb = G.vtab + 2u * G.out_h + oy * G.vk;
+    uint32_t acc[16], out[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 16u; i++) acc[i] = 0u;
+    for (uint32_t y = 0; y < cnt; y++) {
+        const uint32_t k = io.ld_tap(kb + y) & 0xffffffu;
+        uint32_t q[4];
+        io.lds_rd128((ymin - row0 + y) * JDA_RS_TILE_DWORDS + vc * 4u, q);
+#pragma unroll
+        for (uint32_t i = 0; i < 16u; i++) acc[i] += jda_umul24((q[i >> 2] >> (8u * (i & 3u))) & 0xffu, k);
+    }
+#pragma unroll
+    for (uint32_t d = 0; d < 4u; d++)
+        out[d] = jda_rs_clip(acc[4u * d]) | (jda_rs_clip(acc[4u * d + 1u]) << 8) | (jda_rs_clip(acc[4u * d + 2u]) << 16) | (jda_rs_clip(acc[4u * d + 3u]) << 24);
+    uint8_t *p = G.dst + (size_t)oy * G.dst_pitch + b0;
+    const uint32_t left = row_bytes - b0;
+    if (left >= 16u) { io.st128(p, out); return; }
+#pragma unroll
+    for (uint32_t d = 0; d < 4u; d++) {
+        if (4u * d + 4u <= left) { io.st32(p + 4u * d, out[d]); continue; }
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b++)
+            if (4u * d + b < left) io.st8(p + 4u * d + b, (out[d] >> (8u * b)) & 0xffu);
+    }
+}
+
 // ================================================================================================
 // jda_coef_tiles: a tile decoded from COEFFICIENTS (a coefficient image: every scan of a progressive file decoded on the host, or a
 // DCT-domain caller's own).  The tile is the decode kernel's -- one wave64, <= 64 consecutive blocks of an MCU row,

@@ -22,6 +22,7 @@
 
 #include "jda_runtime_internal.h"
 #include "jda_pack_plan.h"
+#include "jda_resize_plan.h"
 
 extern "C" uint32_t jda_image_fast_mul(const jda_image *img);
 extern "C" uint32_t jda_image_general_p1(const jda_image *img);
@@ -1647,6 +1648,152 @@ int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
     jda_dev_image_free(ctx, dimg);
     if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
     return rc;
+}
+
+// ---- antialiased resize (jda_resize_tiles in jda_kernels.hip; the passes and the tile: jda_device_core.h; checks, taps and tiles: jda_resize_plan.h)
+// Check n jobs, build their tap tables and upload both in one block (the job records, the tables behind them), and wait for them as
+// orient_upload does; resize_launch then queues the kernel.  reads (may be NULL): per job the source pixels {x0, y0, x1, y1} its taps read.
+struct resize_plan { void *block; uint32_t n, n_tiles, bpp, lds_bytes; const int32_t *tables; };
+static int resize_upload(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst, resize_plan *plan,
+                         int32_t *reads)
+{
+    plan->block = NULL; plan->n = (uint32_t)n; plan->n_tiles = 0; plan->bpp = (uint32_t)bytes_per_pixel; plan->lds_bytes = 0; plan->tables = NULL;
+    jda_resize_plan_out P;
+    int rc = jda_resize_plan_jobs(n, src, bytes_per_pixel, rects, dst, &P);
+    if (rc != JDA_SUCCESS) return rc;
+    const size_t jbytes = align16(P.jobs.size() * sizeof(jda_resize_job)), tbytes = P.tables.size() * sizeof(int32_t);
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, jbytes + align16(tbytes));
+    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(resize jobs)");
+    rc = jda_resize_plan_place(&P, blk + jbytes);
+    if (rc != JDA_SUCCESS) { jda_pool_free(ctx, blk); return rc; }
+    e = hipMemcpyAsync(blk, P.jobs.data(), P.jobs.size() * sizeof(jda_resize_job), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk + jbytes, P.tables.data(), tbytes, hipMemcpyHostToDevice, ctx->stream);
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+    if (e != hipSuccess) { jda_pool_free(ctx, blk); return jda_set_err(ctx, e, "resize jobs"); }
+    plan->block = blk; plan->n_tiles = P.n_tiles; plan->lds_bytes = P.lds_bytes; plan->tables = (const int32_t *)(blk + jbytes);
+    if (reads) memcpy(reads, P.reads.data(), P.reads.size() * sizeof(int32_t));
+    return JDA_SUCCESS;
+}
+static int resize_launch(jda_ctx *ctx, const resize_plan &plan)
+{
+    const hipError_t e = jda_launch_resize((const jda_resize_job *)plan.block, plan.n, plan.n_tiles, plan.bpp, plan.tables, plan.lds_bytes, ctx->stream);
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_resize_tiles");
+}
+
+int jda_resize_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0 || (bytes_per_pixel != 1 && bytes_per_pixel != 4)) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    if (!src || !dst) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    resize_plan plan;
+    int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = resize_launch(ctx, plan);
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, plan.block);
+    if (rc != JDA_SUCCESS) return rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_resize_surfaces");
+}
+
+int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *rect,
+                               int32_t out_w, int32_t out_h, void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded,
+                               int32_t *tiles)
+{
+    if (mcus_decoded) *mcus_decoded = 0;
+    if (tiles) tiles[0] = tiles[1] = 0;
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!jpeg || !host_pixels || out_w <= 0 || out_h <= 0) return JDA_INVALID_PARAMETER;
+    if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    int32_t err = JDA_SUCCESS;
+    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
+    if (!img) return err;
+    const jda_image_info I = *jda_image_get_info(img);
+    int bpp, ow, oh, cw, ch;
+    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
+    if (rc == JDA_SUCCESS && (ow > cw || oh > ch || (int64_t)pitch_bytes < (int64_t)out_w * bpp || rows < out_h || out_w > (1 << 24) || out_h > (1 << 24))) rc = JDA_INVALID_PARAMETER;
+    const int32_t whole[4] = { 0, 0, ow, oh };
+    const int32_t *box = rect ? rect : whole;
+    if (rc == JDA_SUCCESS && (box[0] < 0 || box[1] < 0 || box[2] <= 0 || box[3] <= 0 || (int64_t)box[0] + box[2] > ow || (int64_t)box[1] + box[3] > oh)) rc = JDA_INVALID_PARAMETER;
+    // (the limits of the resize before anything is uploaded)
+    { uint32_t k; if (rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[0], box[0] + box[2], out_w, &k); if (rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[1], box[1] + box[3], out_h, &k); }
+    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
+    jda_dev_image *dimg = jda_upload(ctx, img, &err);
+    uint32_t nok = 0;
+    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
+    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
+    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
+    jda_image_free(img);
+    if (!dimg) return err;
+    const int cpitch = (int)align16((size_t)cw * bpp), opitch = (int)align16((size_t)out_w * bpp);
+    const size_t cbytes = (size_t)cpitch * ch;
+    uint8_t *dsurf = NULL;                              // the decoded canvas, the resized surface behind it
+    if (jda_pool_alloc(ctx, (void **)&dsurf, cbytes + (size_t)opitch * out_h) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
+    jda_output C, S, D;
+    C.pixels = dsurf; C.pitch_bytes = cpitch; C.width_px = cw; C.rows = ch;
+    S = C; S.width_px = ow; S.rows = oh;                // the visible rectangle of the canvas
+    D.pixels = dsurf + cbytes; D.pitch_bytes = opitch; D.width_px = out_w; D.rows = out_h;
+    // what has to wait for the host -- the job record and the taps -- first: the taps say which MCUs have to be decoded at all
+    resize_plan plan;
+    int32_t reads[4] = { 0, 0, 0, 0 };
+    rc = resize_upload(ctx, 1, &S, bpp, box, &D, &plan, reads);
+    if (rc == JDA_SUCCESS) {
+        const int mw_out = cw / (I.mcus_x ? I.mcus_x : 1), mh_out = ch / (I.mcus_y ? I.mcus_y : 1);
+        int32_t mcu_rect[4] = { reads[0] / mw_out, reads[1] / mh_out, (reads[2] + mw_out - 1) / mw_out, (reads[3] + mh_out - 1) / mh_out };
+        mcu_rect[2] = std::min(mcu_rect[2], I.mcus_x); mcu_rect[3] = std::min(mcu_rect[3], I.mcus_y);
+        const bool all = mcu_rect[0] == 0 && mcu_rect[1] == 0 && mcu_rect[2] == I.mcus_x && mcu_rect[3] == I.mcus_y;
+        jda_batch *b = jda_batch_create_rect(ctx, 1, &dimg, &C, &pixel_type, &options, all ? NULL : mcu_rect, &err);
+        rc = err;
+        if (b) {
+            if (tiles) { tiles[0] = (int32_t)b->stats.tiles; tiles[1] = (int32_t)b->stats.tiles_whole_images; }
+            // then decode, resize and the copy back are queued back to back (the MCUs a bad stream does not reach are zeros before they are sampled)
+            if (!complete) (void)hipMemsetAsync(dsurf + (size_t)mcu_rect[1] * mh_out * cpitch, 0, (size_t)(mcu_rect[3] - mcu_rect[1]) * mh_out * cpitch, ctx->stream);
+            rc = jda_batch_decode(ctx, b);
+            if (rc == JDA_SUCCESS) rc = resize_launch(ctx, plan);
+            if (rc == JDA_SUCCESS) {
+                const size_t row_bytes = (size_t)out_w * bpp;
+                hipError_t e;
+                if ((size_t)pitch_bytes == (size_t)opitch && row_bytes == (size_t)opitch) e = hipMemcpyAsync(host_pixels, D.pixels, row_bytes * (size_t)out_h, hipMemcpyDeviceToHost, ctx->stream);
+                else e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, D.pixels, (size_t)opitch, row_bytes, (size_t)out_h, hipMemcpyDeviceToHost, ctx->stream);
+                { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+                if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+            } else (void)hipStreamSynchronize(ctx->stream);
+            jda_batch_destroy(ctx, b);
+        }
+        jda_pool_free(ctx, plan.block);
+    }
+    jda_pool_free(ctx, dsurf);
+    jda_dev_image_free(ctx, dimg);
+    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
+    return rc;
+}
+
+// Measuring hook of tools/resize_bench.py (not part of the public header): the resize launch between the context's two timer events on
+// its stream -- job records and taps go up before the first event.  ms[k]: repeat k.
+int jda_internal_resize_time(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
+                             int32_t reps, float *ms)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n <= 0 || reps <= 0 || !ms || !src || !dst) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    resize_plan plan;
+    int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL);
+    if (rc != JDA_SUCCESS) return rc;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < reps && rc == JDA_SUCCESS && e == hipSuccess; k++) {
+        e = hipEventRecord(ctx->ev_start, ctx->stream);
+        if (e == hipSuccess) rc = resize_launch(ctx, plan);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, plan.block);
+    if (rc != JDA_SUCCESS) return rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_resize_time");
 }
 
 // Measuring hook of tools/pack_bench.py (not part of the public header): the pack launch between the context's two timer events on its

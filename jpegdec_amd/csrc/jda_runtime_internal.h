@@ -117,6 +117,10 @@ extern "C" hipError_t jda_launch_orient(const jda_orient_job *jobs, uint32_t n, 
 // `table`, device memory), one workgroup a tile of 4 KiB of destination; n_tiles: the length of the flat tile list
 extern "C" hipError_t jda_launch_pack(const jda_pack_job *jobs, uint32_t n, uint32_t n_tiles, int hwc, uint32_t es, const uint8_t *table,
                                       uint32_t bpp, uint32_t bgr, hipStream_t stream);
+// n jobs of one pixel size (1 or 4) resized through the tap tables in `tables` (device memory; the jobs carry where theirs begin), one
+// workgroup a tile of 64 output dwords x the job's tile rows; n_tiles: the length of the flat tile list, lds_bytes: the largest tile's LDS
+extern "C" hipError_t jda_launch_resize(const jda_resize_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, const int32_t *tables,
+                                        uint32_t lds_bytes, hipStream_t stream);
 extern "C" hipError_t jda_launch_segscan_tail(const jda_segscan_params *params, uint32_t n_images, uint32_t max_segs, uint32_t first_round, uint32_t max_round, hipStream_t stream);
 extern "C" hipError_t jda_launch_filter(const jda_filter_params *params, uint32_t n_images, uint32_t max_raw_len, hipStream_t stream);
 extern "C" hipError_t jda_launch_fill_strips(const jda_strips_params *params, uint32_t n_images, uint32_t max_tiles, hipStream_t stream);

@@ -1,5 +1,6 @@
 """Decoded images as torch tensors on the GPU that decoded them: a Pipeline batch into scratch canvases, then ONE jda_pack_surfaces launch
-straight into the tensors' memory (include/jpegdec_amd.h: dense RGB / BGR or planar CHW, uint8 or float through a lookup table).
+straight into the tensors' memory (include/jpegdec_amd.h: dense RGB / BGR or planar CHW, uint8 or float through a lookup table).  With
+size=(H, W) ONE jda_resize_surfaces launch (Pillow's antialiased BILINEAR, bit for bit) stands between the two, and the result is one batch.
 torch is imported when decode_to_tensors runs, not when the package is.  One process, one HIP runtime: a torch build that ships its own
 (a wheel does) must be imported BEFORE libjpegdec_amd.so is loaded (before the first Context), so that the library binds to the runtime
 torch already brought; the other way round the process holds two runtimes, torch finds no GPU, and decode_to_tensors says so."""
@@ -30,11 +31,42 @@ def normalise_table(mean, std, dtype=np.float32):
     return np.ascontiguousarray(t.astype(_np_dtype(dtype)))
 
 
-def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False):
+def prescale_option(info, pixel_type, options, size):
+    """The largest of SCALE_HALF / QUARTER / EIGHTH with which the file's visible size is still at least size = (H, W) on both axes, or 0"""
+    for bit in (B.SCALE_EIGHTH, B.SCALE_QUARTER, B.SCALE_HALF):
+        g = B.output_geometry(info, pixel_type, options | bit)
+        if g["out_w"] >= size[1] and g["out_h"] >= size[0]:
+            return bit
+    return 0
+
+
+def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False):
     """files (JPEG bytes, all colour or all gray) -> tensors on cuda:<ctx.device>.  layout "CHW" or "HWC"; dtype torch.uint8 (default), or
     torch.float16 / torch.float32 with table = [C, 256] values of that type (normalise_table; numpy or torch).  options: the decode option
     bits of every file (a JDA_SCALE_* bit, JDA_LUMA_ONLY: one channel).  Returns a list of [C,H,W] / [H,W,C] tensors, or, when all images
-    have one size, ONE [N,C,H,W] / [N,H,W,C] tensor.  A file that fails to decode raises JdaError with its status."""
+    have one size, ONE [N,C,H,W] / [N,H,W,C] tensor.  A file that fails to decode raises JdaError with its status.
+    size = (H, W): every image -- or crops[k] = (x, y, w, h) of image k, in pixels of its visible size -- is resized to H x W on the GPU
+    (jda_resize_surfaces: Pillow's resize(BILINEAR, box), bit for bit) before it is packed, and the result is always ONE [N,C,H,W] /
+    [N,H,W,C] tensor.  prescale=True (whole images only): each file is decoded at the largest of 1/2, 1/4, 1/8 whose visible size is still
+    at least W x H on both axes -- the DCT-domain shortcut for thumbnails; it changes pixels, so it is opt-in."""
+    files = list(files)
+    if layout not in ("CHW", "HWC"):
+        raise ValueError("layout: 'CHW' or 'HWC'")
+    if size is None:
+        if crops is not None or prescale:
+            raise ValueError("crops and prescale go with size=(H, W)")
+    else:
+        size = tuple(int(v) for v in size)
+        if len(size) != 2 or size[0] <= 0 or size[1] <= 0:
+            raise ValueError("size: (H, W), both positive")
+        if crops is not None and prescale:
+            raise ValueError("prescale is for whole images: not with crops")
+        if prescale and options & (B.SCALE_HALF | B.SCALE_QUARTER | B.SCALE_EIGHTH):
+            raise ValueError("prescale chooses the scale: no JDA_SCALE_* bit in options")
+        if crops is not None:
+            crops = [tuple(int(v) for v in c) for c in crops]
+            if len(crops) != len(files) or any(len(c) != 4 for c in crops):
+                raise ValueError("crops: one (x, y, w, h) per file")
     import torch
 
     if not torch.cuda.is_available():
@@ -44,10 +76,7 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     npdt = _np_dtype(dtype)
     elem = {np.uint8: B.PACK_U8, np.float16: B.PACK_F16, np.float32: B.PACK_F32}[npdt]
     es = np.dtype(npdt).itemsize
-    if layout not in ("CHW", "HWC"):
-        raise ValueError("layout: 'CHW' or 'HWC'")
     flags = (B.PACK_CHW if layout == "CHW" else B.PACK_HWC) | (B.PACK_BGR if bgr else 0)
-    files = list(files)
     n = len(files)
     device = torch.device("cuda", ctx.device)
     if n == 0:
@@ -63,15 +92,19 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     if any(gray) != all(gray):
         raise ValueError("gray and colour files in one call: one jda_pack_surfaces launch takes one source format")
     pt, channels = (B.GRAY8, 1) if gray[0] else (B.RGB8888, 3)
-    geos = [B.output_geometry(i, pt, options) for i in infos]
+    opts = [options | (prescale_option(i, pt, options, size) if prescale else 0) for i in infos]
+    geos = [B.output_geometry(i, pt, o) for i, o in zip(infos, opts)]
     bpp = geos[0]["bpp"]
     pitches = [(g["canvas_w"] * bpp + 15) & ~15 for g in geos]
     offs, total = [], 0
     for g, p in zip(geos, pitches):
         offs.append(total)
         total += (p * g["canvas_h"] + 255) & ~255
-    sizes = [(g["out_h"], g["out_w"]) for g in geos]
+    sizes = [(g["out_h"], g["out_w"]) if size is None else size for g in geos]
     same = all(s == sizes[0] for s in sizes)
+    # size=(H, W): a second scratch allocation of H x W surfaces behind the canvases, the resize launch's destinations and the pack launch's sources
+    rpitch = 0 if size is None else (size[1] * bpp + 15) & ~15
+    rbytes = 0 if size is None else (rpitch * size[0] + 255) & ~255
 
     def shape(h, w):
         return (channels, h, w) if layout == "CHW" else (h, w, channels)
@@ -91,19 +124,28 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
         dev_table = torch.from_numpy(np.ascontiguousarray(host).reshape(channels, 256)).to(device)
         torch.cuda.synchronize(device)                                   # (the table's copy ran on torch's stream)
     base = ctx.malloc(total)
+    rbase = None
     try:
+        if size is not None:
+            rbase = ctx.malloc(rbytes * n)
         pipe = B.Pipeline(ctx, max_images=n, depth=1)
         try:
             outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
-            status = pipe.wait(pipe.submit(files, outs, [pt] * n, [options] * n))
+            status = pipe.wait(pipe.submit(files, outs, [pt] * n, opts))
         finally:
             pipe.close()
         for k, st in enumerate(status):
             if st != 0:
                 raise B.JdaError(st, "file %d of the batch" % k)
-        # the VISIBLE rectangles of the canvases, one launch, straight into the tensors
-        B.pack_surfaces(ctx, [(base + offs[k], pitches[k], geos[k]["out_w"], geos[k]["out_h"]) for k in range(n)], bpp, ptrs, flags, elem,
-                        None if dev_table is None else dev_table.data_ptr())
+        # the VISIBLE rectangles of the canvases, one launch, straight into the tensors -- or resized first, where they lie, in one launch
+        visible = [(base + offs[k], pitches[k], geos[k]["out_w"], geos[k]["out_h"]) for k in range(n)]
+        if size is not None:
+            resized = [(rbase + k * rbytes, rpitch, size[1], size[0]) for k in range(n)]
+            B.resize_surfaces(ctx, visible, bpp, resized, crops)
+            visible = resized
+        B.pack_surfaces(ctx, visible, bpp, ptrs, flags, elem, None if dev_table is None else dev_table.data_ptr())
     finally:
         ctx.free(base)
+        if rbase is not None:
+            ctx.free(rbase)
     return result
