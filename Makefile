@@ -22,7 +22,7 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so
+hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
@@ -37,6 +37,16 @@ tests/hostsim/libjda_orientsim.so: tests/hostsim/orient_sim.cpp tests/hostsim/or
 # the coefficient-tile kernel's lane schedule and its row-major twin on the CPU (tests/test_progressive_full_cpu.py) -- test infrastructure
 tests/hostsim/libjda_coefsim.so: tests/hostsim/coef_sim.cpp tests/hostsim/coef_twin.h $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/coef_sim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp
+
+# the sparse coefficient form and the load phase of jda_sparse_tiles, lane by lane, against the dense load phase (tests/test_sparse_coef_cpu.py) -- test infrastructure
+COEFSPARSE_SRCS = tests/hostsim/coef_sparse_sim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp
+COEFSPARSE_DEPS = $(COEFSPARSE_SRCS) $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
+tests/hostsim/libjda_coefsparsesim.so: $(COEFSPARSE_DEPS)
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ $(COEFSPARSE_SRCS)
+# .. and the same with a main of its own under AddressSanitizer + UBSan: a program, nothing loaded into an interpreter
+sparsepack: tests/hostsim/sparse_pack_asan
+tests/hostsim/sparse_pack_asan: tests/hostsim/sparse_pack_main.cpp $(COEFSPARSE_DEPS)
+	$(CXX) -O1 -g -std=c++17 -fwrapv -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/sparse_pack_main.cpp $(COEFSPARSE_SRCS)
 
 # the pack kernel's vector schedule, lane by lane, its row-major twin and the argument checks of jda_pack_surfaces on the CPU (tests/test_pack_cpu.py) -- test infrastructure
 tests/hostsim/libjda_packsim.so: tests/hostsim/pack_sim.cpp tests/hostsim/pack_twin.h $(CSRC)/jda_pack_plan.h $(CSRC)/jda_device_core.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
@@ -109,10 +119,10 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
+	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle hostsim classshim classcpu cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
+.PHONY: all lib oracle hostsim classshim classcpu sparsepack cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
 
 # jda_node.cpp (host code above the C-ABI) over eight pretend devices -- test infrastructure, no GPU (tests/test_c_api.py)
 nodestub: tests/node_stub/node_stub_user

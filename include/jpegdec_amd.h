@@ -68,7 +68,10 @@ enum {
      * thumbnail of its first scan.  No effect on a baseline file.  With a JDA_SCALE_* bit: JDA_UNSUPPORTED_FEATURE.  Taken by
      * jda_decode_to_host / _ex / _flags (whole image); every other decode entry point -- jda_batch_create*, jda_pipeline_submit*,
      * jda_node_submit* (per image, in status[]), jda_decode_to_host_rect / _bands / _strips / _oriented / _packed / _resized, jda_decode_dither_to_host and
-     * any call with an MCU rectangle -- answers JDA_UNSUPPORTED_FEATURE for a progressive file asked for with it. */
+     * any call with an MCU rectangle -- answers JDA_UNSUPPORTED_FEATURE for a progressive file asked for with it.  The exceptions stand behind
+     * doors of their own: jda_pipeline_submit_ex / jda_node_submit_ex with JDA_SUBMIT_PROGRESSIVE_FULL decode such a file at full size with its
+     * batch (without the flag: JDA_UNSUPPORTED_FEATURE in status[], as ever), and jda_coef_decode_surfaces_rect decodes an MCU rectangle of a
+     * coefficient image (jda_progressive_prepare + jda_coef_upload_ex). */
     JDA_PROGRESSIVE_FULL = 256
 };
 
@@ -530,6 +533,15 @@ int jda_pipeline_submit(jda_pipeline *p, int32_t n, const uint8_t *const *jpegs,
  * buffers) travel as one copy command; a command that would carry less than 128 KB is not worth what it costs the submitting
  * thread, so isolated small files still go through the mirror. */
 #define JDA_SUBMIT_PINNED_INPUT 1
+/* JDA_SUBMIT_PROGRESSIVE_FULL: honour JDA_PROGRESSIVE_FULL in options[i] for a progressive file instead of refusing it (without the flag:
+ * JDA_UNSUPPORTED_FEATURE in status[i], as ever).  Such a file's scans are walked on the host, on the pipeline's workers next to the other
+ * files' header parses, one image a worker; its coefficients travel in whichever form is smaller (JDA_COEF_AUTO) through a page-locked
+ * mirror, and all such images of the batch are decoded at full size into outputs[i] by one launch per (form, layout) present, queued behind
+ * the batch's decode: jda_pipeline_wait returns when their pixels are in place.  A scale bit beside the option bit: JDA_UNSUPPORTED_FEATURE
+ * in status[i] (no DCT-domain scale on this path); a scan error: JDA_DECODE_ERROR in status[i], the surface untouched, the batch goes on.
+ * In the statistics these images count in images and host_path_images (their entropy decode ran on the host), in source_pixels and
+ * compressed_bytes like any decoded file, their bytes in h2d_bytes, their launches in launches.  Baseline files, and progressive files without the bit, are not affected. */
+#define JDA_SUBMIT_PROGRESSIVE_FULL 2
 int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpegs, const int32_t *lens, const jda_output *outputs,
                            const int32_t *pixel_types, const int32_t *options, int32_t flags, int32_t *ticket);
 int jda_pipeline_wait(jda_pipeline *p, int32_t ticket, int32_t *status);
@@ -602,6 +614,14 @@ void jda_coef_image_free(jda_coef_image *img);
 const jda_image_info *jda_coef_image_get_info(const jda_coef_image *img);
 const int16_t *jda_coef_image_coefficients(const jda_coef_image *img, uint32_t *n_blocks);
 const int16_t *jda_coef_image_quant(const jda_coef_image *img, uint8_t *q_id);
+/* The SPARSE form of a coefficient image: an entry per NONZERO coefficient (mod 2^16), DC included.  Built on first request, owned by the
+ * image and cached (thread-safe).  first[n_blocks + 1]: block g's entries are entries[first[g] .. first[g + 1]); *n_entries = first[n_blocks].
+ * entry = (g & 1023) << 22 | n << 16 | (uint16_t)value:  n = natural index 0..63 (0 = DC), ascending within a block.  A tile of the kernel is
+ * <= 64 consecutive blocks, so ten bits of g place an entry in its tile without a search.  2^31 entries and more: NULL, and
+ * jda_coef_image_sparse_status answers JDA_UNSUPPORTED_FEATURE (JDA_SUCCESS otherwise). */
+const uint32_t *jda_coef_image_sparse(const jda_coef_image *img, const uint32_t **first, uint32_t *n_entries);
+int jda_coef_image_sparse_status(const jda_coef_image *img);
+size_t jda_coef_image_sparse_bytes(const jda_coef_image *img);   /* 4 * (n_blocks + 1) + 4 * n_entries, each part rounded up to 16; 0: no sparse form */
 /* H2D of one coefficient image (quantisers + coefficients, one allocation), and the decode of n resident ones on the context's stream: ONE
  * launch for the images of one MCU layout -- the kernel is a template over the layout, as the decode kernel is, so a call whose images mix
  * layouts makes one launch per layout present, five at most -- (kernel jda_coef_tiles: dequantise, IDCT with the reference's column / row shortcuts -- driven by the occupancy
@@ -613,6 +633,20 @@ jda_dev_coef *jda_coef_upload(jda_ctx *ctx, const jda_coef_image *img, int32_t *
 void jda_dev_coef_free(jda_ctx *ctx, jda_dev_coef *dimg);
 int jda_coef_decode_surfaces(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types,
                              const int32_t *options);
+/* Upload with a choice of form.  JDA_COEF_DENSE: 128 bytes a block (jda_coef_upload).  JDA_COEF_SPARSE: quantisers | first[] | entries[] in one
+ * allocation, each part 16-byte aligned: 4 bytes a block + 4 a nonzero coefficient -- smaller than dense unless a block holds more than 31
+ * nonzero terms (quality-100 noise).  JDA_COEF_AUTO: whichever is fewer bytes for THIS image (dense on a tie, and where the sparse form is
+ * refused).  A form outside 0..2 or a NULL image: JDA_INVALID_PARAMETER. */
+enum { JDA_COEF_DENSE = 0, JDA_COEF_SPARSE = 1, JDA_COEF_AUTO = 2 };
+jda_dev_coef *jda_coef_upload_ex(jda_ctx *ctx, const jda_coef_image *img, int32_t form, int32_t *err);
+int jda_dev_coef_form(const jda_dev_coef *d);      /* JDA_COEF_DENSE or JDA_COEF_SPARSE: what is resident */
+size_t jda_dev_coef_bytes(const jda_dev_coef *d);  /* of the device allocation, quantisers included */
+/* jda_coef_decode_surfaces over images of either form, mixed freely -- sparse ones are decoded by kernel jda_sparse_tiles, whose load phase
+ * scatters the entries into the LDS slots the dense load phase fills: equal slots, equal pixels --: one launch per (form, layout) present, ten
+ * at most.  mcu_rects (NULL: whole images): {mx0, my0, mx1, my1} per image in MCUs, half open, with the rules of jda_batch_create_rect:
+ * clamped to the image, an empty rectangle decodes nothing, tiles are cut from the rectangle's own first MCU; pixels outside are untouched. */
+int jda_coef_decode_surfaces_rect(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types,
+                                  const int32_t *options, const int32_t *mcu_rects);
 
 const char *jda_version(void);
 

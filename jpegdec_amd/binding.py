@@ -157,7 +157,14 @@ _PROTOTYPES = [
     ("jda_coef_image_get_info", C.POINTER(ImageInfo), [_P]),
     ("jda_coef_image_coefficients", _P, [_P, C.POINTER(C.c_uint32)]),
     ("jda_coef_image_quant", _P, [_P, _P]),
+    ("jda_coef_image_sparse", _P, [_P, C.POINTER(_P), C.POINTER(C.c_uint32)]),
+    ("jda_coef_image_sparse_status", C.c_int, [_P]),
+    ("jda_coef_image_sparse_bytes", C.c_size_t, [_P]),
     ("jda_coef_upload", _P, [_P, _P, C.POINTER(C.c_int32)]),
+    ("jda_coef_upload_ex", _P, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
+    ("jda_dev_coef_form", C.c_int, [_P]),
+    ("jda_dev_coef_bytes", C.c_size_t, [_P]),
+    ("jda_coef_decode_surfaces_rect", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("jda_dev_coef_free", None, [_P, _P]),
     ("jda_coef_decode_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 ]
@@ -535,9 +542,10 @@ class Pipeline:
         self._keep[t.value] = packed                                      # the buffers stay alive until the batch is waited for
         return t.value
 
-    def submit(self, jpegs, outputs, pixel_types, options) -> int:
-        """outputs: list of (device_ptr, pitch_bytes, width_px, rows).  Returns the batch's ticket."""
-        return self.submit_packed(self.pack(jpegs, outputs, pixel_types, options))
+    def submit(self, jpegs, outputs, pixel_types, options, flags: int = 0) -> int:
+        """outputs: list of (device_ptr, pitch_bytes, width_px, rows).  flags: SUBMIT_* bits (SUBMIT_PROGRESSIVE_FULL: a progressive file
+        whose option word carries PROGRESSIVE_FULL is decoded at full size instead of refused).  Returns the batch's ticket."""
+        return self.submit_packed(self.pack(jpegs, outputs, pixel_types, options), flags)
 
     def wait(self, ticket: int):
         """Blocks until the batch is decoded; returns the list of per-image status codes."""
@@ -620,6 +628,8 @@ class PinnedFiles:
 
 
 SUBMIT_PINNED_INPUT = 1
+SUBMIT_PROGRESSIVE_FULL = 2      # honour PROGRESSIVE_FULL in a progressive file's option word (without it: status 3, as ever)
+COEF_DENSE, COEF_SPARSE, COEF_AUTO = 0, 1, 2      # jda_coef_upload_ex: the form that travels (AUTO: the smaller one for the image)
 
 
 def surface_checksum_host(canvas: np.ndarray) -> int:
@@ -677,6 +687,27 @@ class CoefImage:
         p = self.lib.jda_coef_image_quant(self.handle, ids)
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), shape=(4, 64)).copy(), list(ids)
 
+    def sparse(self):
+        """(first, entries): the sparse form (jda_coef_image_sparse) as numpy views of the image's own arrays -- valid until close().
+        first: uint32[blocks + 1]; entries: uint32, (block & 1023) << 22 | natural index << 16 | value & 0xffff, nonzero values only."""
+        first, n = _P(), C.c_uint32(0)
+        p = self.lib.jda_coef_image_sparse(self.handle, C.byref(first), C.byref(n))
+        if not p:
+            raise JdaError(self.lib.jda_coef_image_sparse_status(self.handle), "jda_coef_image_sparse")
+        nb = C.c_uint32(0)
+        self.lib.jda_coef_image_coefficients(self.handle, C.byref(nb))
+        f = np.ctypeslib.as_array(C.cast(first, C.POINTER(C.c_uint32)), shape=(nb.value + 1,))
+        e = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(n.value,)) if n.value else np.zeros(0, np.uint32)
+        return f, e
+
+    def sparse_bytes(self) -> int:
+        return int(self.lib.jda_coef_image_sparse_bytes(self.handle))
+
+    def dense_bytes(self) -> int:
+        nb = C.c_uint32(0)
+        self.lib.jda_coef_image_coefficients(self.handle, C.byref(nb))
+        return (nb.value * 128 + 15) & ~15
+
     def geometry(self, pixel_type=RGB8888, options=0):
         return output_geometry(self.info, pixel_type, options | (PROGRESSIVE_FULL if self.info.jpeg_type == 1 else 0))
 
@@ -692,10 +723,15 @@ class CoefImage:
             pass
 
 
-def coef_decode(ctx: Context, images, pixel_types, options=None):
-    """jda_coef_upload + ONE jda_coef_decode_surfaces over all the images: [(canvas, geometry)] in MCU-padded host canvases."""
+def coef_decode(ctx: Context, images, pixel_types, options=None, form=COEF_DENSE, rects=None):
+    """jda_coef_upload_ex + ONE jda_coef_decode_surfaces_rect over all the images: [(canvas, geometry)] in MCU-padded host canvases.
+    form: COEF_DENSE / COEF_SPARSE / COEF_AUTO for all images, or one per image (dense and sparse images may share the call).
+    rects: None, or per image None / (mx0, my0, mx1, my1) in MCUs (half open); the canvases start as zeros, which is what a rectangle leaves
+    outside it.
+    With the defaults (dense, no rectangles) the call is jda_coef_upload + jda_coef_decode_surfaces, as before."""
     n = len(images)
     options = list(options) if options is not None else [0] * n
+    forms = [form] * n if isinstance(form, int) else list(form)
     geos = [im.geometry(pt, opt) for im, pt, opt in zip(images, pixel_types, options)]
     pitch = [(g["canvas_w"] * g["bpp"] + 15) & ~15 for g in geos]
     offs, total = [], 0
@@ -703,16 +739,29 @@ def coef_decode(ctx: Context, images, pixel_types, options=None):
         offs.append(total)
         total += (p * g["canvas_h"] + 255) & ~255
     devs, base = [], ctx.malloc(max(total, 256))
+    plain = all(f == COEF_DENSE for f in forms) and rects is None
     try:
-        for im in images:
+        if rects is not None:
+            ctx.memset(base, 0, max(total, 256))
+        for im, f in zip(images, forms):
             err = C.c_int32(0)
-            d = ctx.lib.jda_coef_upload(ctx.handle, im.handle, C.byref(err))
+            d = ctx.lib.jda_coef_upload(ctx.handle, im.handle, C.byref(err)) if plain else ctx.lib.jda_coef_upload_ex(ctx.handle, im.handle, f, C.byref(err))
             if not d:
                 raise JdaError(err.value, "jda_coef_upload")
             devs.append(d)
         outs = (Output * n)(*[Output(base + offs[i], pitch[i], geos[i]["canvas_w"], geos[i]["canvas_h"]) for i in range(n)])
-        ctx.check(ctx.lib.jda_coef_decode_surfaces(ctx.handle, n, (_P * n)(*devs), outs, (C.c_int32 * n)(*pixel_types), (C.c_int32 * n)(*options)),
-                  "jda_coef_decode_surfaces")
+        if plain:
+            ctx.check(ctx.lib.jda_coef_decode_surfaces(ctx.handle, n, (_P * n)(*devs), outs, (C.c_int32 * n)(*pixel_types), (C.c_int32 * n)(*options)),
+                      "jda_coef_decode_surfaces")
+        else:
+            r = None
+            if rects is not None:
+                flat = []
+                for im, rc in zip(images, rects):
+                    flat += list(rc) if rc is not None else [0, 0, im.info.mcus_x, im.info.mcus_y]
+                r = (C.c_int32 * (4 * n))(*flat)
+            ctx.check(ctx.lib.jda_coef_decode_surfaces_rect(ctx.handle, n, (_P * n)(*devs), outs, (C.c_int32 * n)(*pixel_types), (C.c_int32 * n)(*options), r),
+                      "jda_coef_decode_surfaces_rect")
         res = []
         for i, g in enumerate(geos):
             res.append((ctx.to_host(base + offs[i], pitch[i] * g["canvas_h"]).reshape(g["canvas_h"], pitch[i])[:, : g["canvas_w"] * g["bpp"]].copy(), g))

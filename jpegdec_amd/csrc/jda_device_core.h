@@ -3837,4 +3837,81 @@ template <int MODE> JDA_HD uint32_t jda_ct_flags(const jda_dev_desc &D, const jd
     return (f | (f >> 16)) & 0xffffu;
 }
 
+// ================================================================================================
+// jda_sparse_tiles: the same tile from the SPARSE form of a coefficient image: an entry per nonzero coefficient,
+//   entry = (g & 1023) << 22 | n << 16 | (uint16_t)value     g: the block's number, n: natural index (0 = DC), ascending within a block
+//   first[g] .. first[g + 1]: block g's entries -- a tile's blocks are consecutive, so its entries are ONE contiguous range.
+// D.tables: quantisers | first[] (behind JDA_CT_QUANT_BYTES); D.scan: the entries (16-byte aligned).  The load phase that stands in
+// for jda_ct_load:
+//   zero     the tile's slots (128 bytes of each, 8-byte stores: the slots are 136 bytes apart) and its chunk words;
+//   range    first[b0] and first[b0 + nb]: wave-uniform;
+//   scatter  lane = 16-byte vector of four entries of the range aligned down to 16 bytes, 64 vectors a pass, JDA_CS_GROUP passes
+//            issued back to back without a branch between them (a lane with nothing to fetch re-reads the range's first vector),
+//            entries outside [e0, e1) masked.  An entry's slot in the tile is ((e >> 22) - b0) & 1023 -- a tile is <= 64 blocks, so
+//            ten bits of g suffice, as for the continuation entries of the baseline index --; its value is one 16-bit LDS store, and
+//            for n > 0 its flag word (1 << (n & 7)) | (n << 8) is ORed into the block's chunk word n >> 3 (an LDS atomic OR on the
+//            dword that holds the word: several entries of a row, and of the neighbouring row, meet there).
+// Behind it the slots and chunk words are those jda_ct_load leaves over the dense form of the same coefficients -- cols = OR of
+// 1 << (n & 7), the high byte = OR of n --, so jda_ct_flags and every later stage run unchanged and give equal pixels.
+// (Neither the bank pattern of the 2-byte scatter nor the cost of the LDS atomics has been measured on hardware.)
+#define JDA_CS_GROUP 4u
+// io.ld32u(base, i): the i-th dword behind `base`, the same address in every lane (wave-uniform)
+template <int MODE, class IO> JDA_HD void jda_cs_range(IO &io, const jda_dev_desc &D, const jda_tile_ctx &C, uint32_t *e0, uint32_t *e1)
+{
+    typedef jda_mode_traits<MODE> T;
+    const uint8_t *first = D.tables + JDA_CT_QUANT_BYTES;
+    *e0 = io.ld32u(first, C.first_block);
+    *e1 = io.ld32u(first, C.first_block + C.count * (uint32_t)T::NBLK);
+}
+
+template <int MODE> JDA_HD void jda_cs_zero(const jda_tile_ctx &C, uint32_t lane, uint8_t *wl)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_lds_layout<MODE> L;
+    const uint32_t nb = C.count * (uint32_t)T::NBLK;
+#pragma unroll
+    for (uint32_t p = 0; p < 16; p++) {                      // 16 8-byte stores a block
+        const uint32_t i = p * 64u + lane;
+        if (i < nb * 16u) *(jda_u64_alias *)(wl + L::COEF_OFF + (i >> 4) * JDA_COEF_STRIDE + (i & 15u) * 8u) = 0;
+    }
+    if (lane < nb) {                                         // eight chunk words a block
+        jda_u64_alias *cw = (jda_u64_alias *)(wl + L::COLLIST_OFF + 16u * lane);
+        cw[0] = 0; cw[1] = 0;
+    }
+}
+
+typedef uint16_t __attribute__((may_alias)) jda_u16_alias;
+template <int MODE, class IO> JDA_HD void jda_cs_scatter(IO &io, const jda_dev_desc &D, const jda_tile_ctx &C, uint32_t lane, uint32_t e0, uint32_t e1, uint8_t *wl)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_lds_layout<MODE> L;
+    if (e1 <= e0) return;                                    // (wave-uniform: a tile of empty blocks)
+    const uint32_t nb = C.count * (uint32_t)T::NBLK;
+    const uint32_t v0 = e0 >> 2, v1 = (e1 + 3u) >> 2;        // the vectors that hold the range
+    for (uint32_t base = v0; base < v1; base += 64u * JDA_CS_GROUP) {       // (wave-uniform trip count)
+        uint32_t v[JDA_CS_GROUP][4];
+#pragma unroll
+        for (uint32_t p = 0; p < JDA_CS_GROUP; p++) {
+            const uint32_t vi = base + p * 64u + lane;
+            io.ld128(D.scan, vi < v1 ? vi : v0, v[p]);
+        }
+#pragma unroll
+        for (uint32_t p = 0; p < JDA_CS_GROUP; p++) {
+            const uint32_t vi = base + p * 64u + lane;
+            if (vi >= v1) continue;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) {
+                const uint32_t ei = vi * 4u + j, e = v[p][j];
+                const uint32_t slot = ((e >> 22) - C.first_block) & 1023u, n = (e >> 16) & 63u;
+                if (ei < e0 || ei >= e1 || slot >= nb) continue;      // (slot < nb for every entry the host packs: nothing leaves the tile's LDS)
+                *(jda_u16_alias *)(wl + L::COEF_OFF + slot * JDA_COEF_STRIDE + 2u * n) = (uint16_t)e;
+                if (n) {
+                    const uint32_t ci = slot * 8u + (n >> 3);
+                    jda_lds_or_u32(wl + L::COLLIST_OFF + (ci >> 1) * 4u, ((1u << (n & 7u)) | (n << 8)) << ((ci & 1u) * 16u));
+                }
+            }
+        }
+    }
+}
+
 #endif // JDA_DEVICE_CORE_H

@@ -2075,6 +2075,83 @@ extern "C" hipError_t jda_launch_coef_tiles(int mode, const jda_dev_desc *descs,
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// jda_sparse_tiles<MODE>: the same tiles from the SPARSE form of coefficient images (jda_cs_* in jda_device_core.h): jda_ct_load is
+// replaced by zero / range / scatter, everything behind it is jda_coef_tiles' own.  descs[i].tables = quantisers | first[], .scan = entries.
+struct jda_sparse_io {
+    __device__ __forceinline__ void ld128(const uint8_t *base, uint32_t i, uint32_t *v) const
+    {
+        const uint4 q = ((const uint4 JDA_GLOBAL *)JDA_G(const uint8_t, base))[i];
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+    __device__ __forceinline__ uint32_t ld32u(const uint8_t *base, uint32_t i) const
+    {
+        return jda_uni32(((const uint32_t JDA_GLOBAL *)JDA_G(const uint8_t, base))[i]);
+    }
+};
+template <int MODE>
+__global__ __launch_bounds__(64 * JDA_CT_WAVES, 4)
+void jda_sparse_tiles(const jda_dev_desc *__restrict__ descs, const jda_strip *__restrict__ tiles, uint32_t n_tiles)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    typedef jda_mode_traits<MODE> T;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_CT_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;                                              // a padding record of the list
+    uint8_t *tab = lds + wave * (uint32_t)jda_ct_layout<MODE>::WAVE_BYTES;
+    uint8_t *wl = tab + JDA_CT_TAB_BYTES;
+    jda_dev_desc D = jda_desc_uniform<0, MODE>(descs + S.image);
+    D.scale_shift = 0; D.strip_mcus = 0; D.pad_[0] = 0;
+    jda_tile_ctx C;
+    C.first_mcu = S.mcu_y * D.mcus_x + S.mcu_x0;
+    C.count = S.count;
+    C.first_block = C.first_mcu * (uint32_t)T::NBLK;
+    C.win_lo = C.win_len = C.win_need = 0;
+    jda_sparse_io io;
+    uint32_t e0, e1;
+    jda_cs_range<MODE>(io, D, C, &e0, &e1);
+    jda_ct_tables(io, D.tables, lane, tab);
+    jda_cs_zero<MODE>(C, lane, wl);
+    JDA_WAVE_SYNC();                                                       // (the zeros lie in LDS before the first entry lands: a wavefront's LDS accesses are served in order)
+    jda_cs_scatter<MODE>(io, D, C, lane, e0, e1, wl);
+    jda_lane_pre LP;
+    jda_ct_lane_prepare<MODE>(LP, D, lane);
+    jda_p4_pre P4;
+    jda_p4_prepare<MODE>(P4, D, lane);
+    JDA_WAVE_SYNC();
+    const uint32_t flags = jda_ct_flags<MODE>(D, C, LP, lane, wl);
+    JDA_WAVE_SYNC();                                                       // (the column list overwrites the chunk words)
+    jda_p1_lists<MODE>(D, LP, lane, flags, nullptr, tab, wl);
+    JDA_WAVE_SYNC();
+    jda_p2_columns<MODE, false>(D, lane, tab, wl);
+    JDA_WAVE_SYNC();
+    jda_p3_rows<MODE>(D, lane, tab, wl);
+    JDA_WAVE_SYNC();
+    jda_p4_output<MODE>(D, S, C, lane, wl, P4);
+}
+template <int MODE>
+static hipError_t launch_sparse_tiles(const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    const uint32_t lds_bytes = JDA_CT_WAVES * (uint32_t)jda_ct_layout<MODE>::WAVE_BYTES;
+    JDA_LAUNCH(jda_sparse_tiles<MODE>, dim3((n_tiles + JDA_CT_WAVES - 1u) / JDA_CT_WAVES), dim3(64u * JDA_CT_WAVES), lds_bytes, stream, descs, tiles, n_tiles);
+    return hipGetLastError();
+}
+// descs[i].tables = image i's quantisers | first[], .scan = its entries; tiles: jda_append_strips records of images of ONE mode
+extern "C" hipError_t jda_launch_sparse_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    if (n_tiles == 0) return hipSuccess;
+    switch (mode) {
+    case JDA_MODE_GRAY: return launch_sparse_tiles<JDA_MODE_GRAY>(descs, tiles, n_tiles, stream);
+    case JDA_MODE_444: return launch_sparse_tiles<JDA_MODE_444>(descs, tiles, n_tiles, stream);
+    case JDA_MODE_420: return launch_sparse_tiles<JDA_MODE_420>(descs, tiles, n_tiles, stream);
+    case JDA_MODE_422: return launch_sparse_tiles<JDA_MODE_422>(descs, tiles, n_tiles, stream);
+    case JDA_MODE_440: return launch_sparse_tiles<JDA_MODE_440>(descs, tiles, n_tiles, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 extern "C" hipError_t jda_internal_set_wgtrace(unsigned long long *dev_buf)
 {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_jda_wgtrace), &dev_buf, sizeof(dev_buf));

@@ -164,6 +164,11 @@ struct Img {
     uint32_t list, n_tiles;      // launch list it is in, tiles (padded)
     size_t strip_off;            // its first strip inside the list
     uint32_t ord;
+    // JDA_SUBMIT_PROGRESSIVE_FULL: a progressive file whose option word carries JDA_PROGRESSIVE_FULL
+    bool prog;                   // every scan walked on the host (jda_progressive_prepare), decoded by the batch's coefficient launches
+    jda_coef_image *ci;          // .. until its payload lies in the page-locked mirror
+    int cform;                   // the form JDA_COEF_AUTO picked
+    size_t cbytes, coff;         // quantisers + payload; where they lie in the slot's coefficient block
 };
 
 } // namespace
@@ -196,6 +201,12 @@ struct jda_pipeline {
         size_t off_descs;
         uint32_t flat_max_items;             // JDA_LIST_THUMB_FLAT: the launch's width
         jda_pipeline_stats st;
+        // coefficient images of the batch (Img::prog): one device block + its page-locked mirror for their payloads, one for the launch
+        // plan (grow-only, the slot's own: nothing is allocated or released per image); ev_coef: both copies are done
+        uint8_t *cdev, *cpin; size_t ccap;
+        uint8_t *bdev, *bpin; size_t bcap;
+        hipEvent_t ev_coef;
+        jda_coef_plan cplan;
     } slots[JDA_PIPE_MAX_DEPTH];
     int next_ticket;
     jda_pipeline_stats total;
@@ -206,6 +217,30 @@ static void slot_free(jda_pipeline::Slot &s)
     if (s.dev) (void)hipFree(s.dev);
     if (s.pin) (void)hipHostFree(s.pin);
     s.dev = NULL; s.pin = NULL; s.dev_cap = s.pin_cap = 0;
+    if (s.cdev) (void)hipFree(s.cdev);
+    if (s.cpin) (void)hipHostFree(s.cpin);
+    if (s.bdev) (void)hipFree(s.bdev);
+    if (s.bpin) (void)hipHostFree(s.bpin);
+    s.cdev = s.cpin = s.bdev = s.bpin = NULL; s.ccap = s.bcap = 0;
+}
+
+// a device block and its page-locked mirror, grown together (the slot is not in flight: nothing reads the old ones)
+static bool grow_pair(uint8_t **dev, uint8_t **pin, size_t *cap, size_t need)
+{
+    if (*cap >= need) return true;
+    if (*dev) (void)hipFree(*dev);
+    if (*pin) (void)hipHostFree(*pin);
+    *dev = *pin = NULL; *cap = 0;
+    const size_t want = a256(need + need / 4);
+    if (hipMalloc((void **)dev, want) != hipSuccess || hipHostMalloc((void **)pin, want, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        if (*dev) (void)hipFree(*dev);
+        if (*pin) (void)hipHostFree(*pin);
+        *dev = *pin = NULL;
+        return false;
+    }
+    *cap = want;
+    return true;
 }
 
 // tiles of one image, padded to whole workgroups (the same list jda_append_strips makes)
@@ -238,7 +273,8 @@ jda_pipeline *jda_pipeline_create(jda_ctx *ctx, int32_t max_images, int32_t dept
     for (int i = 0; i < JDA_PIPE_MAX_DEPTH; i++) {
         jda_pipeline::Slot &s = p->slots[i];
         s.ticket = -1; s.in_flight = false; s.dev = NULL; s.pin = NULL; s.dev_cap = s.pin_cap = 0; s.ev_copy = s.ev_up = s.ev_dec = NULL;
-        if (i < depth && ok) ok = hipEventCreateWithFlags(&s.ev_copy, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.ev_dec, hipEventDisableTiming) == hipSuccess;
+        s.cdev = s.cpin = s.bdev = s.bpin = NULL; s.ccap = s.bcap = 0; s.ev_coef = NULL;
+        if (i < depth && ok) ok = hipEventCreateWithFlags(&s.ev_coef, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.ev_copy, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&s.ev_dec, hipEventDisableTiming) == hipSuccess;
     }
     if (!ok) { jda_pipeline_destroy(p); *err = JDA_ERROR_HIP; return NULL; }
     unsigned nt = host_threads > 0 ? (unsigned)host_threads : std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
@@ -262,6 +298,8 @@ void jda_pipeline_destroy(jda_pipeline *p)
         if (s.ev_copy) (void)hipEventDestroy(s.ev_copy);
         if (s.ev_up) (void)hipEventDestroy(s.ev_up);
         if (s.ev_dec) (void)hipEventDestroy(s.ev_dec);
+        if (s.ev_coef) (void)hipEventDestroy(s.ev_coef);
+        for (Img &im : s.imgs) if (im.ci) { jda_coef_image_free(im.ci); im.ci = NULL; }
     }
     if (p->s_up) (void)hipStreamDestroy(p->s_up);
     for (int i = 0; i < 2; i++) if (p->s_upx[i]) (void)hipStreamDestroy(p->s_upx[i]);
@@ -332,8 +370,23 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
     // ---- host: parse + tables, in parallel
     p->workers->run(n, [&](int i) {
         Img &im = S.imgs[(size_t)i];
-        im.err = (jpegs[i] && lens[i] > 0) ? jda_front_prepare(jpegs[i], lens[i], S.pin + im.ctl_tables, &im.f) : JDA_INVALID_PARAMETER;
+        im.prog = false; im.ci = NULL; im.cform = JDA_COEF_DENSE; im.cbytes = im.coff = 0;
         im.tab_owner = i; im.tab_hash = 0;
+        if ((flags & JDA_SUBMIT_PROGRESSIVE_FULL) && (S.opts[(size_t)i] & JDA_PROGRESSIVE_FULL) && jpegs[i] && lens[i] > 0 &&
+            jda_parse(jpegs[i], lens[i], &im.f.info) == JDA_SUCCESS && im.f.info.jpeg_type == 1) {
+            // every scan on this worker, then the sparse pack (JDA_COEF_AUTO needs its size); a scan error: the image's status, nothing decoded
+            im.prog = true;
+            if (S.opts[(size_t)i] & (JDA_SCALE_HALF | JDA_SCALE_QUARTER | JDA_SCALE_EIGHTH)) { im.err = JDA_UNSUPPORTED_FEATURE; return; }      // no DCT-domain scale on this path
+            int32_t err = JDA_SUCCESS;
+            im.ci = jda_progressive_prepare(jpegs[i], lens[i], &err);
+            im.err = im.ci ? JDA_SUCCESS : err;
+            size_t payload = 0;
+            if (im.ci) im.err = jda_coef_pick_form(im.ci, JDA_COEF_AUTO, &im.cform, &payload);
+            im.cbytes = JDA_CT_QUANT_BYTES + payload;
+            if (im.err != JDA_SUCCESS && im.ci) { jda_coef_image_free(im.ci); im.ci = NULL; }
+            return;
+        }
+        im.err = (jpegs[i] && lens[i] > 0) ? jda_front_prepare(jpegs[i], lens[i], S.pin + im.ctl_tables, &im.f) : JDA_INVALID_PARAMETER;
         if (im.err == JDA_SUCCESS) {                          // FNV-1a over the tables (8 bytes a step) and the table ids
             uint64_t h = 0xcbf29ce484222325ull;
             const uint64_t *w = (const uint64_t *)(S.pin + im.ctl_tables);
@@ -346,6 +399,7 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
     // over the bus per image (a tenth of a 1280x720 file, a quarter of a 640x480 one), one set of walk tables to build and to keep in the
     // L2 instead of one per image.  The owners' copies are moved together at the front of the blob.
     static_assert(JDA_TABLE_BYTES % 8 == 0, "hashed 8 bytes a step");
+    auto free_coef_images = [&]() { for (Img &im : S.imgs) if (im.ci) { jda_coef_image_free(im.ci); im.ci = NULL; } };      // (a submit that gives up before they reach the mirror)
     size_t n_tab = 0;
     {
         auto same_tables = [&](const Img &om, const Img &im) {
@@ -358,18 +412,18 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
         first.reserve((size_t)n);
         for (int i = 0; i < n; i++) {
             Img &im = S.imgs[(size_t)i];
-            if (im.err != JDA_SUCCESS) continue;
+            if (im.err != JDA_SUCCESS || im.prog) continue;
             auto it = first.find(im.tab_hash);
             if (it == first.end()) first.emplace(im.tab_hash, i); else im.tab_owner = it->second;
         }
         p->workers->run(n, [&](int i) {
             Img &im = S.imgs[(size_t)i];
-            if (im.err == JDA_SUCCESS && im.tab_owner != i && !same_tables(S.imgs[(size_t)im.tab_owner], im)) im.tab_owner = -1 - im.tab_owner;
+            if (im.err == JDA_SUCCESS && !im.prog && im.tab_owner != i && !same_tables(S.imgs[(size_t)im.tab_owner], im)) im.tab_owner = -1 - im.tab_owner;
         });
         std::vector<int> odd;                                  // (owners made by a failed compare, in order)
         for (int i = 0; i < n; i++) {
             Img &im = S.imgs[(size_t)i];
-            if (im.err != JDA_SUCCESS) continue;
+            if (im.err != JDA_SUCCESS || im.prog) continue;
             if (im.tab_owner < 0) {                             // a collision: among the images that collided before, or an owner of its own
                 im.tab_owner = i;
                 for (int o : odd) if (S.imgs[(size_t)o].tab_hash == im.tab_hash && same_tables(S.imgs[(size_t)o], im)) { im.tab_owner = o; break; }
@@ -403,7 +457,7 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
     for (int i = 0; i < n; i++) {
         Img &im = S.imgs[(size_t)i];
         im.device = false;
-        if (im.err != JDA_SUCCESS) continue;
+        if (im.err != JDA_SUCCESS || im.prog) continue;
         const jda_image_info &I = im.f.info;
         jda_dev_desc &D = descs[(size_t)i];
         int bpp = 0;
@@ -537,7 +591,7 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
     if (S.pin_cap < pin_stats + S.stats_bytes + 256) {        // (strips and scans did not fit: grow, keeping the tables)
         uint8_t *np = NULL;
         const size_t want = a256((pin_stats + S.stats_bytes) * 5 / 4 + ((size_t)1 << 20));
-        if (hipHostMalloc((void **)&np, want, hipHostMallocDefault) != hipSuccess) return JDA_ERROR_MEMORY;
+        if (hipHostMalloc((void **)&np, want, hipHostMallocDefault) != hipSuccess) { free_coef_images(); return JDA_ERROR_MEMORY; }
         memcpy(np, S.pin, off_fparams);
         (void)hipHostFree(S.pin);
         S.pin = np; S.pin_cap = want;
@@ -554,10 +608,68 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
                 if (&o != &S && !o.in_flight && o.dev) { (void)hipFree(o.dev); o.dev = NULL; o.dev_cap = 0; }
             }
             e = hipMalloc((void **)&S.dev, a256(arena));
-            if (e != hipSuccess) { S.dev = NULL; return jda_set_err(ctx, e, "hipMalloc(pipeline arena)"), JDA_ERROR_MEMORY; }
+            if (e != hipSuccess) { S.dev = NULL; free_coef_images(); return jda_set_err(ctx, e, "hipMalloc(pipeline arena)"), JDA_ERROR_MEMORY; }
             S.dev_cap = a256(arena);
         } else
         S.dev_cap = want;
+    }
+
+    // ---- coefficient images: their block, the launch plan over it, the payloads into the page-locked mirror (in parallel)
+    std::vector<int> prog_ix;
+    size_t ctotal = 0;
+    for (int i = 0; i < n; i++) {
+        Img &im = S.imgs[(size_t)i];
+        if (!im.prog || im.err != JDA_SUCCESS) continue;
+        im.coff = ctotal; ctotal += a256(im.cbytes);
+        prog_ix.push_back(i);
+    }
+    S.cplan.blob.clear(); S.cplan.n_launches = 0;
+    if (!prog_ix.empty()) {
+        auto drop_all = [&](int code) { for (int i : prog_ix) { Img &im = S.imgs[(size_t)i]; im.err = code; jda_coef_image_free(im.ci); im.ci = NULL; } prog_ix.clear(); };
+        if (!grow_pair(&S.cdev, &S.cpin, &S.ccap, ctotal)) drop_all(JDA_ERROR_MEMORY);
+        else {
+            std::vector<jda_dev_coef> cimgs((size_t)n);      // (what the plan reads of an image: where it will lie in the slot's block)
+            std::vector<const jda_dev_coef *> cptr((size_t)n, (const jda_dev_coef *)NULL);
+            std::vector<int32_t> cerr((size_t)n, JDA_SUCCESS);
+            for (int i : prog_ix) {
+                Img &im = S.imgs[(size_t)i];
+                jda_dev_coef &d = cimgs[(size_t)i];
+                memset(&d, 0, sizeof(d));
+                d.base = S.cdev + im.coff; d.bytes = im.cbytes; d.info = *jda_coef_image_get_info(im.ci); d.form = im.cform;
+                (void)jda_coef_image_coefficients(im.ci, &d.n_blocks);
+                (void)jda_coef_image_quant(im.ci, d.q_id);
+                d.off_entries = im.cform == JDA_COEF_SPARSE ? JDA_CT_QUANT_BYTES + a16(((size_t)d.n_blocks + 1) * 4) : JDA_CT_QUANT_BYTES;
+                cptr[(size_t)i] = &d;
+            }
+            const int rc = jda_coef_plan_build(n, cptr.data(), outputs, S.pts.data(), S.opts.data(), NULL, cerr.data(), &S.cplan);
+            if (rc != JDA_SUCCESS) drop_all(rc);
+            else if (!grow_pair(&S.bdev, &S.bpin, &S.bcap, S.cplan.blob.size())) drop_all(JDA_ERROR_MEMORY);
+            else {
+                memcpy(S.bpin, S.cplan.blob.data(), S.cplan.blob.size());
+                for (int i : prog_ix) {
+                    if (cerr[(size_t)i] != JDA_SUCCESS) { S.imgs[(size_t)i].err = cerr[(size_t)i]; continue; }      // (a surface too small, a pixel type: the image's own status)
+                    S.st.source_pixels += (int64_t)cimgs[(size_t)i].info.width * cimgs[(size_t)i].info.height;     // (counted like the files of the baseline path)
+                    S.st.compressed_bytes += lens[i];
+                }
+                p->workers->run((int)prog_ix.size(), [&](int k) {
+                    Img &im = S.imgs[(size_t)prog_ix[(size_t)k]];
+                    if (im.err == JDA_SUCCESS) {
+                        uint8_t *dst = S.cpin + im.coff;
+                        uint32_t nb = 0, ne = 0;
+                        memcpy(dst, jda_coef_image_quant(im.ci, NULL), JDA_CT_QUANT_BYTES);
+                        const int16_t *coefs = jda_coef_image_coefficients(im.ci, &nb);
+                        if (im.cform == JDA_COEF_SPARSE) {      // (the host arrays are padded with zeros to 16 bytes, as the parts of the block are)
+                            const uint32_t *first = NULL;
+                            const uint32_t *entries = jda_coef_image_sparse(im.ci, &first, &ne);
+                            const size_t fb = a16(((size_t)nb + 1) * 4);
+                            memcpy(dst + JDA_CT_QUANT_BYTES, first, fb);
+                            copy_to_mirror(dst + JDA_CT_QUANT_BYTES + fb, (const uint8_t *)entries, a16((size_t)ne * 4));
+                        } else copy_to_mirror(dst + JDA_CT_QUANT_BYTES, (const uint8_t *)coefs, (size_t)nb * JDA_CT_BLOCK_BYTES);
+                    }
+                    jda_coef_image_free(im.ci); im.ci = NULL;
+                });
+            }
+        }
     }
 
     g_submit_clock.lap(3);
@@ -676,6 +788,14 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
         }
         if (e == hipSuccess) e = hipMemcpyAsync(S.pin + S.pin_stats, B + S.off_stats_dev, S.stats_bytes, hipMemcpyDeviceToHost, s_up);
     }
+    // the coefficient block and its plan: behind the batch's own copy on the copy stream (page-locked sources: the submit does not wait)
+    const bool coef_launch = !prog_ix.empty() && S.cplan.n_launches > 0;
+    if (coef_launch) {
+        if (e == hipSuccess) e = hipMemcpyAsync(S.cdev, S.cpin, ctotal, hipMemcpyHostToDevice, p->s_copy);
+        if (e == hipSuccess) e = hipMemcpyAsync(S.bdev, S.bpin, S.cplan.blob.size(), hipMemcpyHostToDevice, p->s_copy);
+        if (e == hipSuccess) e = hipEventRecord(S.ev_coef, p->s_copy);
+        S.st.h2d_bytes += (int64_t)(ctotal + S.cplan.blob.size());
+    }
     if (e == hipSuccess) e = hipEventRecord(S.ev_up, s_up);
     // ---- enqueue: decode stream
     if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, S.ev_up, 0);
@@ -684,6 +804,14 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
         e = jda_launch_decode(JDA_LIST_MODE(m), JDA_LIST_FAST(m), JDA_LIST_VARIANT(m), JDA_LIST_BIG(m), JDA_LIST_CONT(m), (const jda_dev_desc *)(B + S.off_descs), (const jda_strip *)(B + S.list_off[m]), S.list_n[m],
                               JDA_LIST_IS_THUMB_FLAT(m) ? S.flat_max_items : 0u, ctx->stream);
         S.st.launches++;
+    }
+    // .. and the coefficient launches, one per (form, layout) present, behind the batch's decode and in front of its event: the stream
+    // waits for the two copies (ev_coef), jda_pipeline_wait for ev_dec, so the pixels are in place when it returns, and the slot's
+    // blocks are rewritten only by a submit behind that wait
+    if (coef_launch) {
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, S.ev_coef, 0);
+        if (e == hipSuccess) e = jda_coef_plan_launch_kernels(S.cplan, S.bdev, ctx->stream);
+        S.st.launches += S.cplan.n_launches;
     }
     if (e == hipSuccess) e = hipEventRecord(S.ev_dec, ctx->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(p->s_copy); (void)hipStreamSynchronize(s_up); (void)hipStreamSynchronize(ctx->stream); return jda_set_err(ctx, e, "jda_pipeline_submit"); }
@@ -748,7 +876,8 @@ int jda_pipeline_wait(jda_pipeline *p, int32_t ticket, int32_t *status)
     for (int i = 0; i < n; i++) {
         Img &im = S.imgs[(size_t)i];
         int st = im.err;
-        if (st == JDA_SUCCESS) {
+        if (st == JDA_SUCCESS && im.prog) S.st.host_path_images++;      // (its entropy decode ran on the host; its pixels came with the batch)
+        else if (st == JDA_SUCCESS) {
             bool redo = !im.device;
             if (im.device) {
                 const uint32_t *rb = (const uint32_t *)(S.pin + S.pin_stats + (im.off_stats - S.off_stats_dev));

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
 #include <new>
 
 #include "jda_internal.h"
@@ -25,6 +26,11 @@ struct jda_coef_image {
     alignas(16) int16_t quant[4 * 64];      // prescaled (JPEGFixQuantD, jpeg.inl:1789-1811), natural order: JDA_TB_QUANT of the table blob
     int16_t *coefs;                          // n_blocks x int16[64], natural order, MCU-interleaved scan order; 16-byte aligned
     uint32_t n_blocks;
+    // the sparse form (jda_coef_image_sparse): made on first request, kept; coefs is constant once the image is handed out
+    std::once_flag sparse_once;
+    uint32_t *sp_first, *sp_entries;        // first[n_blocks + 1] and entries[n_entries], each padded with zeros to 16 bytes
+    uint32_t sp_n_entries;
+    int sp_status;                           // JDA_SUCCESS / JDA_UNSUPPORTED_FEATURE (2^31 entries and more) / JDA_ERROR_MEMORY
 };
 
 namespace {
@@ -340,11 +346,53 @@ jda_coef_image *coef_image_new(const uint8_t *jpeg, int32_t len, int want_progre
     memcpy(img->quant, tables + JDA_TB_QUANT, sizeof(img->quant));
     img->n_blocks = (uint32_t)(F.info.mcus_x * F.info.mcus_y * F.info.blocks_per_mcu);
     img->coefs = NULL;
+    img->sp_first = img->sp_entries = NULL; img->sp_n_entries = 0; img->sp_status = JDA_SUCCESS;
     const size_t bytes = ((size_t)img->n_blocks * 128 + 15) & ~(size_t)15;
     if (posix_memalign((void **)&img->coefs, 64, bytes ? bytes : 64) != 0) { delete img; *err = JDA_ERROR_MEMORY; return NULL; }
     memset(img->coefs, 0, bytes);
     *err = JDA_SUCCESS;
     return img;
+}
+
+// the sparse form: an entry per nonzero coefficient (DC included), blocks in order, natural index ascending within a block
+void sparse_pack(jda_coef_image *img)
+{
+    const uint32_t nb = img->n_blocks;
+    const size_t first_bytes = (((size_t)nb + 1) * 4 + 15) & ~(size_t)15;
+    uint32_t *first = NULL;
+    if (posix_memalign((void **)&first, 64, first_bytes) != 0) { img->sp_status = JDA_ERROR_MEMORY; return; }
+    memset(first, 0, first_bytes);
+    uint64_t total = 0;
+    for (uint32_t g = 0; g < nb; g++) {
+        const int16_t *b = img->coefs + (size_t)g * 64;
+        first[g] = (uint32_t)total;
+        uint32_t k = 0;
+        for (int q = 0; q < 16; q++) {
+            uint64_t w;
+            memcpy(&w, b + 4 * q, 8);
+            if (w) for (int j = 0; j < 4; j++) k += b[4 * q + j] != 0;
+        }
+        total += k;
+        if (total >= ((uint64_t)1 << 31)) { free(first); img->sp_status = JDA_UNSUPPORTED_FEATURE; return; }
+    }
+    first[nb] = (uint32_t)total;
+    const size_t entry_bytes = ((size_t)total * 4 + 15) & ~(size_t)15;
+    uint32_t *entries = NULL;
+    if (posix_memalign((void **)&entries, 64, entry_bytes ? entry_bytes : 64) != 0) { free(first); img->sp_status = JDA_ERROR_MEMORY; return; }
+    memset(entries, 0, entry_bytes ? entry_bytes : 64);
+    uint32_t *e = entries;
+    for (uint32_t g = 0; g < nb; g++) {
+        const int16_t *b = img->coefs + (size_t)g * 64;
+        const uint32_t hi = (g & 1023u) << 22;
+        for (int q = 0; q < 16; q++) {
+            uint64_t w;
+            memcpy(&w, b + 4 * q, 8);
+            if (!w) continue;
+            for (int j = 0; j < 4; j++)
+                if (b[4 * q + j] != 0) *e++ = hi | ((uint32_t)(4 * q + j) << 16) | (uint16_t)b[4 * q + j];
+        }
+    }
+    img->sp_first = first; img->sp_entries = entries; img->sp_n_entries = (uint32_t)total;
 }
 
 } // namespace
@@ -414,6 +462,8 @@ void jda_coef_image_free(jda_coef_image *img)
 {
     if (!img) return;
     free(img->coefs);
+    free(img->sp_first);
+    free(img->sp_entries);
     delete img;
 }
 
@@ -430,6 +480,32 @@ const int16_t *jda_coef_image_quant(const jda_coef_image *img, uint8_t *q_id)
     if (!img) return NULL;
     if (q_id) memcpy(q_id, img->q_id, 3);
     return img->quant;
+}
+
+const uint32_t *jda_coef_image_sparse(const jda_coef_image *img, const uint32_t **first, uint32_t *n_entries)
+{
+    if (first) *first = NULL;
+    if (n_entries) *n_entries = 0;
+    if (!img) return NULL;
+    jda_coef_image *m = const_cast<jda_coef_image *>(img);        // (the cache is the image's own)
+    std::call_once(m->sparse_once, sparse_pack, m);
+    if (!img->sp_first) return NULL;
+    if (first) *first = img->sp_first;
+    if (n_entries) *n_entries = img->sp_n_entries;
+    return img->sp_entries;
+}
+
+int jda_coef_image_sparse_status(const jda_coef_image *img)
+{
+    if (!img) return JDA_INVALID_PARAMETER;
+    (void)jda_coef_image_sparse(img, NULL, NULL);
+    return img->sp_status;
+}
+
+size_t jda_coef_image_sparse_bytes(const jda_coef_image *img)
+{
+    if (!img || !jda_coef_image_sparse(img, NULL, NULL)) return 0;
+    return ((((size_t)img->n_blocks + 1) * 4 + 15) & ~(size_t)15) + (((size_t)img->sp_n_entries * 4 + 15) & ~(size_t)15);
 }
 
 } // extern "C"

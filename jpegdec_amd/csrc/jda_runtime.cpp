@@ -904,30 +904,73 @@ int jda_decode_to_host_rect(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int3
     return jda_decode_to_host_flags(ctx, jpeg, len, pixel_type, options, mcu_rect, host_pixels, pitch_bytes, rows, mcus_decoded, tiles, 0);
 }
 
-// ---- coefficient images (jda_coef_tiles in jda_kernels.hip)
+// ---- coefficient images (jda_coef_tiles / jda_sparse_tiles in jda_kernels.hip)
 jda_dev_coef *jda_coef_upload(jda_ctx *ctx, const jda_coef_image *img, int32_t *err)
+{
+    if (!ctx) { if (err) *err = JDA_ERROR_NO_DEVICE; return NULL; }      // (this call's order of checks, as ever)
+    return jda_coef_upload_ex(ctx, img, JDA_COEF_DENSE, err);
+}
+
+// which form an upload of `form` makes resident, and its bytes behind the quantisers (JDA_COEF_AUTO: the smaller one for THIS image)
+int jda_coef_pick_form(const jda_coef_image *img, int32_t form, int *picked, size_t *payload_bytes)
+{
+    if (!img || form < JDA_COEF_DENSE || form > JDA_COEF_AUTO) return JDA_INVALID_PARAMETER;
+    uint32_t n_blocks = 0;
+    (void)jda_coef_image_coefficients(img, &n_blocks);
+    const size_t dense = align16((size_t)n_blocks * JDA_CT_BLOCK_BYTES);
+    if (form == JDA_COEF_DENSE) { *picked = JDA_COEF_DENSE; *payload_bytes = dense; return JDA_SUCCESS; }
+    const int st = jda_coef_image_sparse_status(img);
+    if (st != JDA_SUCCESS) {
+        if (form == JDA_COEF_AUTO && st == JDA_UNSUPPORTED_FEATURE) { *picked = JDA_COEF_DENSE; *payload_bytes = dense; return JDA_SUCCESS; }
+        return st;
+    }
+    const size_t sparse = jda_coef_image_sparse_bytes(img);
+    if (form == JDA_COEF_AUTO && sparse >= dense) { *picked = JDA_COEF_DENSE; *payload_bytes = dense; return JDA_SUCCESS; }
+    *picked = JDA_COEF_SPARSE; *payload_bytes = sparse;
+    return JDA_SUCCESS;
+}
+
+jda_dev_coef *jda_coef_upload_ex(jda_ctx *ctx, const jda_coef_image *img, int32_t form, int32_t *err)
 {
     int32_t dummy;
     if (!err) err = &dummy;
+    if (!img || form < JDA_COEF_DENSE || form > JDA_COEF_AUTO) { *err = JDA_INVALID_PARAMETER; return NULL; }      // (checked on the host, whatever the context)
     if (!ctx) { *err = JDA_ERROR_NO_DEVICE; return NULL; }
-    if (!img) { *err = JDA_INVALID_PARAMETER; return NULL; }
     (void)hipSetDevice(ctx->device);
+    int picked = JDA_COEF_DENSE;
+    size_t payload = 0;
+    const int rc = jda_coef_pick_form(img, form, &picked, &payload);
+    if (rc != JDA_SUCCESS) { *err = rc; return NULL; }
     jda_dev_coef *d = new (std::nothrow) jda_dev_coef;
     if (!d) { *err = JDA_ERROR_MEMORY; return NULL; }
     memset(d, 0, sizeof(*d));
     d->info = *jda_coef_image_get_info(img);
     const int16_t *coefs = jda_coef_image_coefficients(img, &d->n_blocks);
     const int16_t *quant = jda_coef_image_quant(img, d->q_id);
-    d->bytes = JDA_CT_QUANT_BYTES + align16((size_t)d->n_blocks * JDA_CT_BLOCK_BYTES);
+    d->form = picked;
+    d->bytes = JDA_CT_QUANT_BYTES + payload;
     hipError_t e = jda_pool_alloc(ctx, (void **)&d->base, d->bytes);
     if (e != hipSuccess) { delete d; jda_set_err(ctx, e, "hipMalloc(coefficient image)"); *err = JDA_ERROR_MEMORY; return NULL; }
     e = hipMemcpyAsync(d->base, quant, JDA_CT_QUANT_BYTES, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && d->n_blocks) e = hipMemcpyAsync(d->base + JDA_CT_QUANT_BYTES, coefs, (size_t)d->n_blocks * JDA_CT_BLOCK_BYTES, hipMemcpyHostToDevice, ctx->stream);
+    if (picked == JDA_COEF_DENSE) {
+        d->off_entries = JDA_CT_QUANT_BYTES;
+        if (e == hipSuccess && d->n_blocks) e = hipMemcpyAsync(d->base + JDA_CT_QUANT_BYTES, coefs, (size_t)d->n_blocks * JDA_CT_BLOCK_BYTES, hipMemcpyHostToDevice, ctx->stream);
+    } else {                                               // quantisers | first[] | entries[], each part 16-byte aligned (the host arrays are padded alike)
+        const uint32_t *first = NULL;
+        const uint32_t *entries = jda_coef_image_sparse(img, &first, &d->n_entries);
+        const size_t first_bytes = align16(((size_t)d->n_blocks + 1) * 4), entry_bytes = align16((size_t)d->n_entries * 4);
+        d->off_entries = JDA_CT_QUANT_BYTES + first_bytes;
+        if (e == hipSuccess) e = hipMemcpyAsync(d->base + JDA_CT_QUANT_BYTES, first, first_bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && entry_bytes) e = hipMemcpyAsync(d->base + d->off_entries, entries, entry_bytes, hipMemcpyHostToDevice, ctx->stream);
+    }
     { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }      // (the image's host memory is the caller's again)
     if (e != hipSuccess) { jda_pool_free(ctx, d->base); delete d; jda_set_err(ctx, e, "jda_coef_upload"); *err = JDA_ERROR_HIP; return NULL; }
     *err = JDA_SUCCESS;
     return d;
 }
+
+int jda_dev_coef_form(const jda_dev_coef *d) { return d ? d->form : JDA_COEF_DENSE; }
+size_t jda_dev_coef_bytes(const jda_dev_coef *d) { return d ? d->bytes : 0; }
 
 void jda_dev_coef_free(jda_ctx *ctx, jda_dev_coef *d)
 {
@@ -936,68 +979,94 @@ void jda_dev_coef_free(jda_ctx *ctx, jda_dev_coef *d)
     delete d;
 }
 
-// descriptors and tile lists of n coefficient images -> one pool block (descs | the lists of the five layouts), uploaded and waited for (the
-// records leave pageable memory that goes away with this frame); coef_launch then queues the kernels: one launch per layout present
-struct coef_plan { uint8_t *block; size_t off[JDA_N_MODES]; uint32_t n_tiles[JDA_N_MODES]; };
-static int coef_upload_plan(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types, const int32_t *options, coef_plan *plan)
+// descriptors and tile lists of n coefficient images -> one host blob (descs | the lists of the two forms x five layouts); host work only.
+// per_image_err != NULL: imgs[i] == NULL is a hole, and an image that cannot be planned gets its code there and is left out, nothing launched
+// for either.  mcu_rects: as jda_batch_create_rect (jda_append_strips).
+int jda_coef_plan_build(int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types, const int32_t *options,
+                        const int32_t *mcu_rects, int32_t *per_image_err, jda_coef_plan *plan)
 {
-    memset(plan, 0, sizeof(*plan));
+    plan->blob.clear(); plan->n_launches = 0;
+    memset(plan->off, 0, sizeof(plan->off)); memset(plan->n_tiles, 0, sizeof(plan->n_tiles));
     std::vector<jda_dev_desc> descs((size_t)n);
-    std::vector<jda_strip> strips[JDA_N_MODES];
+    std::vector<jda_strip> strips[2][JDA_N_MODES];
     for (int i = 0; i < n; i++) {
         const jda_dev_coef *im = imgs[i];
-        if (!im) return JDA_INVALID_PARAMETER;
+        jda_dev_desc &D = descs[(size_t)i];
+        if (per_image_err) per_image_err[i] = JDA_SUCCESS;
+        if (!im) { if (!per_image_err) return JDA_INVALID_PARAMETER; memset(&D, 0, sizeof(D)); continue; }
         jda_image_info I = im->info;
         I.jpeg_type = 0;                                   // (coefficients of every scan: geometry and rules of a baseline file of this SOF)
         const int opt = (options ? options[i] : 0) & ~JDA_PROGRESSIVE_FULL;
-        if (opt & (JDA_SCALE_HALF | JDA_SCALE_QUARTER | JDA_SCALE_EIGHTH)) return JDA_UNSUPPORTED_FEATURE;      // full size only
         const uint8_t no_huff[3] = { 0, 0, 0 };
-        jda_dev_desc &D = descs[(size_t)i];
-        const int rc = jda_fill_launch_desc(D, I, no_huff, no_huff, im->q_id, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, outputs[i],
-                                            pixel_types ? pixel_types[i] : JDA_RGB8888, opt, NULL);
-        if (rc != JDA_SUCCESS) return rc;
+        int rc = (opt & (JDA_SCALE_HALF | JDA_SCALE_QUARTER | JDA_SCALE_EIGHTH)) ? JDA_UNSUPPORTED_FEATURE : JDA_SUCCESS;      // full size only
+        if (rc == JDA_SUCCESS) rc = jda_fill_launch_desc(D, I, no_huff, no_huff, im->q_id, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, outputs[i],
+                                                         pixel_types ? pixel_types[i] : JDA_RGB8888, opt, NULL);
+        if (rc != JDA_SUCCESS) {
+            if (!per_image_err) return rc;
+            per_image_err[i] = rc; memset(&D, 0, sizeof(D)); continue;
+        }
         D.pad_[0] = 0;
         D.tables = im->base;
-        D.scan = im->base + JDA_CT_QUANT_BYTES;
-        jda_append_strips(strips[D.mode], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        D.scan = im->base + im->off_entries;
+        jda_append_strips(strips[im->form == JDA_COEF_SPARSE ? 1 : 0][D.mode], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode, 0, mcu_rects ? mcu_rects + 4 * i : NULL);
     }
     size_t bytes = align16(descs.size() * sizeof(jda_dev_desc));
-    for (int m = 0; m < JDA_N_MODES; m++) { plan->off[m] = bytes; plan->n_tiles[m] = (uint32_t)strips[m].size(); bytes += align16(strips[m].size() * sizeof(jda_strip)); }
-    uint8_t *blk = NULL;
-    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, bytes);
-    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(coefficient plan)");
-    e = hipMemcpyAsync(blk, descs.data(), descs.size() * sizeof(jda_dev_desc), hipMemcpyHostToDevice, ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess; m++)
-        if (!strips[m].empty()) e = hipMemcpyAsync(blk + plan->off[m], strips[m].data(), strips[m].size() * sizeof(jda_strip), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { jda_pool_free(ctx, blk); return jda_set_err(ctx, e, "coefficient plan"); }
-    plan->block = blk;
+    for (int f = 0; f < 2; f++)
+        for (int m = 0; m < JDA_N_MODES; m++) {
+            plan->off[f][m] = bytes; plan->n_tiles[f][m] = (uint32_t)strips[f][m].size();
+            bytes += align16(strips[f][m].size() * sizeof(jda_strip));
+            if (plan->n_tiles[f][m]) plan->n_launches++;
+        }
+    plan->blob.assign(bytes, 0);
+    memcpy(plan->blob.data(), descs.data(), descs.size() * sizeof(jda_dev_desc));
+    for (int f = 0; f < 2; f++)
+        for (int m = 0; m < JDA_N_MODES; m++)
+            if (!strips[f][m].empty()) memcpy(plan->blob.data() + plan->off[f][m], strips[f][m].data(), strips[f][m].size() * sizeof(jda_strip));
     return JDA_SUCCESS;
 }
-static int coef_launch(jda_ctx *ctx, const coef_plan &plan)
+
+// the blob's copy into `block` (device, blob.size() bytes) and the launches, one per (form, layout) present, queued on `stream`; the blob is
+// read until the copy is done
+hipError_t jda_coef_plan_launch(const jda_coef_plan &plan, uint8_t *block, hipStream_t stream)
+{
+    const hipError_t e = hipMemcpyAsync(block, plan.blob.data(), plan.blob.size(), hipMemcpyHostToDevice, stream);
+    return e == hipSuccess ? jda_coef_plan_launch_kernels(plan, block, stream) : e;
+}
+hipError_t jda_coef_plan_launch_kernels(const jda_coef_plan &plan, const uint8_t *block, hipStream_t stream)
 {
     hipError_t e = hipSuccess;
     for (int m = 0; m < JDA_N_MODES && e == hipSuccess; m++)
-        if (plan.n_tiles[m]) e = jda_launch_coef_tiles(m, (const jda_dev_desc *)plan.block, (const jda_strip *)(plan.block + plan.off[m]), plan.n_tiles[m], ctx->stream);
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_coef_tiles");
+        if (plan.n_tiles[0][m]) e = jda_launch_coef_tiles(m, (const jda_dev_desc *)block, (const jda_strip *)(block + plan.off[0][m]), plan.n_tiles[0][m], stream);
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess; m++)
+        if (plan.n_tiles[1][m]) e = jda_launch_sparse_tiles(m, (const jda_dev_desc *)block, (const jda_strip *)(block + plan.off[1][m]), plan.n_tiles[1][m], stream);
+    return e;
 }
 
-int jda_coef_decode_surfaces(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types,
-                             const int32_t *options)
+int jda_coef_decode_surfaces_rect(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types,
+                                  const int32_t *options, const int32_t *mcu_rects)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (n < 0) return JDA_INVALID_PARAMETER;
     if (n == 0) return JDA_SUCCESS;
     if (!imgs || !outputs) return JDA_INVALID_PARAMETER;
+    jda_coef_plan plan;
+    int rc = jda_coef_plan_build(n, imgs, outputs, pixel_types, options, mcu_rects, NULL, &plan);
+    if (rc != JDA_SUCCESS) return rc;
     (void)hipSetDevice(ctx->device);
-    coef_plan plan;
-    int rc = coef_upload_plan(ctx, n, imgs, outputs, pixel_types, options, &plan);
-    if (rc != JDA_SUCCESS) return rc;
-    rc = coef_launch(ctx, plan);
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    jda_pool_free(ctx, plan.block);
-    if (rc != JDA_SUCCESS) return rc;
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_coef_decode_surfaces");
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, plan.blob.size());
+    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(coefficient plan)");
+    e = jda_coef_plan_launch(plan, blk, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);     // (the blob leaves pageable memory that goes away with this frame)
+    jda_pool_free(ctx, blk);
+    if (e != hipSuccess) return jda_set_err(ctx, e, "jda_coef_tiles");
+    return es == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, es, "jda_coef_decode_surfaces");
+}
+
+int jda_coef_decode_surfaces(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types,
+                             const int32_t *options)
+{
+    return jda_coef_decode_surfaces_rect(ctx, n, imgs, outputs, pixel_types, options, NULL);
 }
 
 // jda_decode_to_host* with JDA_PROGRESSIVE_FULL on a progressive file: every scan on the host, the coefficients to the GPU, the canvas back
@@ -1021,17 +1090,19 @@ static int progressive_full_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t l
     if (jda_pool_alloc(ctx, &dout, (size_t)dpitch * ch) != hipSuccess) { jda_dev_coef_free(ctx, dimg); return JDA_ERROR_MEMORY; }
     jda_output O;
     O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = cw; O.rows = drows;
-    coef_plan plan;
+    jda_coef_plan plan;
     const jda_dev_coef *one = dimg;
-    rc = coef_upload_plan(ctx, 1, &one, &O, &pixel_type, &options, &plan);
-    if (rc == JDA_SUCCESS) rc = coef_launch(ctx, plan);
+    uint8_t *blk = NULL;
+    rc = jda_coef_plan_build(1, &one, &O, &pixel_type, &options, NULL, NULL, &plan);
+    if (rc == JDA_SUCCESS && jda_pool_alloc(ctx, (void **)&blk, plan.blob.size()) != hipSuccess) rc = JDA_ERROR_MEMORY;
+    if (rc == JDA_SUCCESS) { const hipError_t e = jda_coef_plan_launch(plan, blk, ctx->stream); if (e != hipSuccess) rc = jda_set_err(ctx, e, "jda_coef_tiles"); }
     if (rc == JDA_SUCCESS && drows > 0) {
         const size_t row_bytes = (size_t)cw * bpp < (size_t)pitch_bytes ? (size_t)cw * bpp : (size_t)pitch_bytes;
         hipError_t e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, row_bytes, (size_t)drows, hipMemcpyDeviceToHost, ctx->stream);
         { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
         if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
     } else (void)hipStreamSynchronize(ctx->stream);
-    if (plan.block) jda_pool_free(ctx, plan.block);
+    if (blk) jda_pool_free(ctx, blk);
     jda_pool_free(ctx, dout);
     jda_dev_coef_free(ctx, dimg);
     if (rc == JDA_SUCCESS && mcus_decoded) *mcus_decoded = I.mcus_x * I.mcus_y;

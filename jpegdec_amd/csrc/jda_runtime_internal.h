@@ -53,12 +53,31 @@ struct jda_dev_image {
 };
 
 struct jda_dev_coef {
-    uint8_t *base;            // one allocation: quantisers (JDA_CT_QUANT_BYTES) | coefficients (n_blocks x 128 bytes)
-    size_t bytes;
+    uint8_t *base;            // one allocation: quantisers (JDA_CT_QUANT_BYTES) | coefficients (n_blocks x 128 bytes)  -- JDA_COEF_DENSE
+    size_t bytes;             //                 quantisers | first[n_blocks + 1] | entries[n_entries], each part 16-byte aligned -- JDA_COEF_SPARSE
     jda_image_info info;
     uint8_t q_id[3];
     uint32_t n_blocks;
+    int form;                 // what is resident
+    uint32_t n_entries;
+    size_t off_entries;       // the coefficients (dense) / the entries (sparse)
 };
+
+// launch plan of a call over coefficient images: descs | tile lists of (form, layout), in one host blob that goes to the device as it is
+struct jda_coef_plan {
+    std::vector<uint8_t> blob;
+    size_t off[2][JDA_N_MODES];
+    uint32_t n_tiles[2][JDA_N_MODES];
+    int n_launches;           // (form, layout) pairs present
+};
+// (defined inside jda_runtime.cpp's extern "C" block)
+// per_image_err != NULL: an image that cannot be planned (a scale bit, a surface too small) gets its code there and is left out; else the call fails
+extern "C" int jda_coef_pick_form(const jda_coef_image *img, int32_t form, int *picked, size_t *payload_bytes);
+extern "C" int jda_coef_plan_build(int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types, const int32_t *options,
+                                   const int32_t *mcu_rects, int32_t *per_image_err, jda_coef_plan *plan);
+// the launches alone: the blob is in `block` already, or its copy is queued in front
+extern "C" hipError_t jda_coef_plan_launch_kernels(const jda_coef_plan &plan, const uint8_t *block, hipStream_t stream);
+extern "C" hipError_t jda_coef_plan_launch(const jda_coef_plan &plan, uint8_t *block, hipStream_t stream);
 
 struct jda_batch {
     int32_t n_images;
@@ -136,6 +155,8 @@ extern "C" hipError_t jda_launch_decode(int mode, int fast_mul, int variant, int
                                         uint32_t n_strips, uint32_t aux, hipStream_t stream);
 // tiles of coefficient images of one MCU layout (descs[i].scan: coefficients, .tables: JDA_CT_QUANT_BYTES of quantisers): jda_coef_tiles<mode>
 extern "C" hipError_t jda_launch_coef_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
+// the same from the sparse form (descs[i].tables: quantisers | first[], .scan: entries): jda_sparse_tiles<mode>
+extern "C" hipError_t jda_launch_sparse_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
 inline uint32_t jda_flat_items(const jda_dev_desc &D) { return (D.mode == JDA_MODE_GRAY ? (D.mcus_x + 3u) >> 2 : D.mcus_x) * D.mcus_y; }      // quads of blocks (gray) / MCUs
 
 #endif

@@ -40,7 +40,7 @@ def prescale_option(info, pixel_type, options, size):
     return 0
 
 
-def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False):
+def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False, progressive="thumbnail"):
     """files (JPEG bytes, all colour or all gray) -> tensors on cuda:<ctx.device>.  layout "CHW" or "HWC"; dtype torch.uint8 (default), or
     torch.float16 / torch.float32 with table = [C, 256] values of that type (normalise_table; numpy or torch).  options: the decode option
     bits of every file (a JDA_SCALE_* bit, JDA_LUMA_ONLY: one channel).  Returns a list of [C,H,W] / [H,W,C] tensors, or, when all images
@@ -48,8 +48,15 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     size = (H, W): every image -- or crops[k] = (x, y, w, h) of image k, in pixels of its visible size -- is resized to H x W on the GPU
     (jda_resize_surfaces: Pillow's resize(BILINEAR, box), bit for bit) before it is packed, and the result is always ONE [N,C,H,W] /
     [N,H,W,C] tensor.  prescale=True (whole images only): each file is decoded at the largest of 1/2, 1/4, 1/8 whose visible size is still
-    at least W x H on both axes -- the DCT-domain shortcut for thumbnails; it changes pixels, so it is opt-in."""
+    at least W x H on both axes -- the DCT-domain shortcut for thumbnails; it changes pixels, so it is opt-in.
+    progressive="thumbnail" (the default): a progressive file comes back as the reference decodes it, the 1/8 thumbnail of its first scan.
+    progressive="full": every file whose header says progressive gets PROGRESSIVE_FULL in its options and the batch is submitted with
+    SUBMIT_PROGRESSIVE_FULL -- every scan, full size, so a batch that mixes baseline and progressive files of one size is still ONE
+    tensor; size= and crops= work as for any file.  There is no DCT-domain scale for such a file: with prescale=True it is decoded at full
+    size and resized from there, and a JDA_SCALE_* bit in options is refused for it (JdaError 3)."""
     files = list(files)
+    if progressive not in ("thumbnail", "full"):
+        raise ValueError("progressive: 'thumbnail' or 'full'")
     if layout not in ("CHW", "HWC"):
         raise ValueError("layout: 'CHW' or 'HWC'")
     if size is None:
@@ -92,7 +99,8 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     if any(gray) != all(gray):
         raise ValueError("gray and colour files in one call: one jda_pack_surfaces launch takes one source format")
     pt, channels = (B.GRAY8, 1) if gray[0] else (B.RGB8888, 3)
-    opts = [options | (prescale_option(i, pt, options, size) if prescale else 0) for i in infos]
+    full = [progressive == "full" and i.jpeg_type == 1 for i in infos]
+    opts = [options | B.PROGRESSIVE_FULL if fl else options | (prescale_option(i, pt, options, size) if prescale else 0) for i, fl in zip(infos, full)]
     geos = [B.output_geometry(i, pt, o) for i, o in zip(infos, opts)]
     bpp = geos[0]["bpp"]
     pitches = [(g["canvas_w"] * bpp + 15) & ~15 for g in geos]
@@ -131,7 +139,7 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
         pipe = B.Pipeline(ctx, max_images=n, depth=1)
         try:
             outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
-            status = pipe.wait(pipe.submit(files, outs, [pt] * n, opts))
+            status = pipe.wait(pipe.submit(files, outs, [pt] * n, opts, B.SUBMIT_PROGRESSIVE_FULL if any(full) else 0))
         finally:
             pipe.close()
         for k, st in enumerate(status):

@@ -14,6 +14,20 @@ For 640x480, 1920x1080 and 4096x4096 pictures in 4:2:0 and 4:4:4 (Pillow, qualit
                    between the same two events.  With --baseline-lib PATH (a build of the parent commit) the twin's figures are taken in a
                    child process that loads that library; without it, with this build (the decode kernels are the same code).
 
+With --sparse the tool measures the sparse coefficient form instead and writes profiles/progressive_sparse.json (or --out).
+Per file -- Pillow's progressive files of tests/prog_cases.py, one synthetic 2048x2048 quality-75 photograph-like file of jpegdec_amd.synth,
+and this tool's own pictures --:
+
+  dense_bytes / sparse_bytes / auto   128 bytes a block; 4 bytes a block + 4 a nonzero coefficient; the form JDA_COEF_AUTO picks
+  sparse_pack_ms                      jda_coef_image_sparse on a fresh image (one thread, a host clock)
+and, unless --no-gpu (then the figures above are all there is: they need no device):
+  upload_ms {dense, sparse}           jda_coef_upload_ex of that form (a host clock around a call that ends in a synchronise; pageable source)
+  kernel_ms {dense, sparse}           jda_coef_decode_surfaces_rect over that one image between two events: jda_coef_tiles / jda_sparse_tiles AND
+                                      the upload of the launch plan, as kernel_ms above
+  pipeline                            a batch of --batch copies of the file submitted with JDA_SUBMIT_PROGRESSIVE_FULL (submit + wait, a host clock,
+                                      scans on the pipeline's workers) against the same files sent one by one through jda_decode_to_host with the
+                                      bit -- with --baseline-lib in a child process on the parent commit's build, else on this build
+
 Warm-up before every timed figure; each is the median of --repeat rounds with min and max beside it.  One JSON line on stdout and,
 with --out, in a file.  Nothing is asserted: no timing threshold gates anything.  Fails without a GPU."""
 import argparse
@@ -141,13 +155,138 @@ def progressive_figures(ctx, jpeg, repeat):
             "coefficient_bytes": n_blocks * 128, "canvas_bytes": g["canvas_w"] * g["canvas_h"] * 4}
 
 
+def sparse_files(with_large):
+    from tests import prog_cases as PC
+    from jpegdec_amd.synth import synth_jpeg
+    files = [("fixture_" + n, PC.files(n)[0]) for n in sorted(PC.CASES)]
+    files.append(("synth_2048x2048_420_q75", synth_jpeg(2048, 2048, "4:2:0", seed=11, quality=75, progressive=True)))
+    if with_large:
+        for w, h in SHAPES:
+            im = picture(w, h)
+            for sampling in SAMPLINGS:
+                files.append(("picture_%dx%d_%s_q85" % (w, h, sampling.replace(":", "")), encode(im, sampling, True)))
+    return files
+
+
+def one_by_one(ctx, jpeg, batch, repeat):
+    canvas = [None]
+
+    def run():
+        for _ in range(batch):
+            rc, canvas[0], g = J.decode_to_host(ctx, jpeg, J.RGB8888 if J.parse(jpeg)["ncomp"] == 3 else J.GRAY8, J.PROGRESSIVE_FULL, out=canvas[0])
+            assert rc == 0
+    return stats(host_ms(run, repeat))
+
+
+def sparse_figures(ctx, jpeg, repeat, batch):
+    """the byte counts and the pack time; with a context the upload, kernel and pipeline times"""
+    lib = J.load_library()
+    pack = []
+    for _ in range(max(3, repeat // 4)):
+        img = J.CoefImage(jpeg)
+        t = time.perf_counter()
+        img.sparse()
+        pack.append((time.perf_counter() - t) * 1e3)
+        img.close()
+    img = J.CoefImage(jpeg)
+    first, entries = img.sparse()
+    dense_b, sparse_b = img.dense_bytes(), img.sparse_bytes()
+    res = {"file_bytes": len(jpeg), "blocks": int(first.size - 1), "nonzero_coefficients": int(entries.size), "dense_bytes": dense_b, "sparse_bytes": sparse_b,
+           "auto": "sparse" if sparse_b < dense_b else "dense", "sparse_pack": stats(pack)}
+    if ctx is None:
+        img.close()
+        return res
+    pt = J.RGB8888 if img.info.ncomp == 3 else J.GRAY8
+    g = img.geometry(pt, 0)
+    pitch = (g["canvas_w"] * g["bpp"] + 15) & ~15
+    surf = ctx.malloc(pitch * g["canvas_h"])
+    outs = (Output * 1)(Output(surf, pitch, g["canvas_w"], g["canvas_h"]))
+    res["upload"], res["kernel"] = {}, {}
+    for name, form in (("dense", J.COEF_DENSE), ("sparse", J.COEF_SPARSE)):
+        devs = []
+
+        def upload():
+            err = C.c_int32(0)
+            d = lib.jda_coef_upload_ex(ctx.handle, img.handle, form, C.byref(err))
+            assert d and err.value == 0
+            devs.append(d)
+            if len(devs) > 1:
+                lib.jda_dev_coef_free(ctx.handle, devs.pop(0))
+        res["upload"][name] = stats(host_ms(upload, repeat))
+        one_img, pts, opts = (C.c_void_p * 1)(devs[0]), (C.c_int32 * 1)(pt), (C.c_int32 * 1)(0)
+        kern = []
+        for k in range(repeat + 2):
+            ctx.timer_start()
+            ctx.check(lib.jda_coef_decode_surfaces_rect(ctx.handle, 1, one_img, outs, pts, opts, None), "jda_coef_decode_surfaces_rect")
+            ctx.timer_stop()
+            ms = ctx.timer_elapsed_ms()
+            if k >= 2:
+                kern.append(ms)
+        res["kernel"][name] = stats(kern)
+        lib.jda_dev_coef_free(ctx.handle, devs[0])
+    img.close()
+    # a pipeline batch of `batch` copies, every one into the same surface (what is timed is the path, not the pixels)
+    pipe = J.Pipeline(ctx, max_images=batch, depth=1)
+    packed = pipe.pack([jpeg] * batch, [(surf, pitch, g["canvas_w"], g["canvas_h"])] * batch, [pt] * batch, [J.PROGRESSIVE_FULL] * batch)
+
+    def run():
+        st = pipe.wait(pipe.submit_packed(packed, J.SUBMIT_PROGRESSIVE_FULL))
+        assert st == [0] * batch, st
+    res["pipeline"] = {"batch": batch, "submit_and_wait": stats(host_ms(run, max(3, repeat // 2)))}
+    pipe.close()
+    ctx.free(surf)
+    return res
+
+
+def sparse_main(args):
+    if args.baseline_only:
+        raw = C.CDLL(J.library_path())
+        J.binding._PROTOTYPES[:] = [p for p in J.binding._PROTOTYPES if hasattr(raw, p[0])]
+        ctx = J.Context(0)
+        res = {"cases": {name: {"one_by_one": one_by_one(ctx, jpeg, args.batch, max(3, args.repeat // 2))} for name, jpeg in sparse_files(True)}}
+        ctx.close()
+        print(json.dumps(res))
+        return
+    ctx = None if args.no_gpu else J.Context(0)
+    res = {"tool": "progressive_bench --sparse", "library": os.path.relpath(J.library_path(), ROOT), "gpu": ctx is not None, "cases": {}}
+    for name, jpeg in sparse_files(ctx is not None):
+        res["cases"][name] = sparse_figures(ctx, jpeg, args.repeat, args.batch)
+        if ctx is not None and not args.baseline_lib:
+            res["cases"][name]["pipeline"]["one_by_one"] = one_by_one(ctx, jpeg, args.batch, max(3, args.repeat // 2))
+    if ctx is not None:
+        ctx.close()
+    if ctx is not None and args.baseline_lib:
+        env = dict(os.environ, JDA_LIBRARY=os.path.abspath(args.baseline_lib))
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--sparse", "--baseline-only", "--repeat", str(args.repeat), "--batch", str(args.batch)],
+                           env=env, capture_output=True, text=True, timeout=900)
+        if r.returncode != 0:
+            raise SystemExit("baseline child failed: " + r.stderr[-2000:])
+        child = json.loads(r.stdout.strip().splitlines()[-1])
+        res["one_by_one_library"] = "the parent commit's build"
+        for name, v in child["cases"].items():
+            res["cases"][name]["pipeline"]["one_by_one"] = v["one_by_one"]
+    if args.note:
+        res["note"] = args.note
+    print(json.dumps(res))
+    out = args.out or os.path.join(ROOT, "profiles", "progressive_sparse.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sparse", action="store_true", help="measure the sparse coefficient form (profiles/progressive_sparse.json)")
+    ap.add_argument("--no-gpu", action="store_true", help="--sparse: the byte counts and the pack time only")
+    ap.add_argument("--batch", type=int, default=8, help="--sparse: files in the pipeline batch")
+    ap.add_argument("--note", default=None, help="--sparse: a line on the machine's load, kept in the file")
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--baseline-lib", default=None, help="libjpegdec_amd.so of the parent commit: the twin's figures are measured with it")
     ap.add_argument("--baseline-only", action="store_true", help="(the child process of --baseline-lib)")
     args = ap.parse_args()
+    if args.sparse:
+        return sparse_main(args)
     if args.baseline_only:
         # (an older build of the library lacks the entry points this tool's other half measures: bind what it has)
         raw = C.CDLL(J.library_path())
