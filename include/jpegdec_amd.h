@@ -415,6 +415,29 @@ int jda_pack_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t sr
 #define JDA_RESIZE_MAX_TABLE_BYTES (64u << 20)
 int jda_resize_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst);
 
+/* ---- Decoded surfaces encoded on the GPU as baseline JFIF files: libjpeg's file, byte for byte
+ * A job turns the pixel rectangle {x, y, w, h} (1 <= w, h <= 65535, inside width_px x rows) of src[i] -- a surface resident in HBM,
+ * JDA_RGB8888 (bytes_per_pixel 4: bytes R, G, B, A; A ignored; pixels and pitch multiples of 4) or JDA_EIGHT_BIT_GRAYSCALE (1) -- into
+ * the file libjpeg (Pillow's Image.save(quality=, subsampling=, optimize=False, restart_marker_blocks=)) writes for these pixels, behind
+ * its SOS header byte for byte: SOI, JFIF APP0, one 8-bit DQT per table, SOF0 (component ids 1..3), the four Annex K DHTs (two for gray),
+ * DRI when restart_interval != 0, SOS, the entropy-coded data, EOI.  quality 1..100 scales the Annex K quantisers as jpeg_set_quality
+ * does; colour is jccolor.c's, downsampling jcsample.c's h2v1 / h2v2 with edge replication, the transform jfdctint.c's, the rounding
+ * jcdctmgr.c's; restart_interval 0..65535 MCUs (0: none); reserved = 0.  The rules in full: DESIGN.md 5.13.
+ * dst[i] = DEVICE memory of dst_capacity[i] bytes, any alignment; dst_bytes[i] and status[i] are HOST arrays: the file's size and
+ * JDA_SUCCESS, or -- the file does not fit dst_capacity[i] -- the size it needs and JDA_ERROR_MEMORY, and then NO byte of dst[i] is
+ * written; the rest of the call goes on.  jda_encode_bound gives a capacity no file of that shape passes.
+ * A fixed number of launches per call on the context's stream (behind whatever made the surfaces there), synchronous; n == 0 succeeds and
+ * launches nothing.  JDA_INVALID_PARAMETER, before anything is launched: a null or misaligned pointer, a pitch too small, a rectangle
+ * that is empty, too large or leaves the surface, a quality, sampling or pixel size out of range, reserved != 0, a gray surface with a
+ * colour sampling or the reverse, a negative capacity, a destination that shares a byte with a source rectangle or another destination.
+ * JDA_UNSUPPORTED_FEATURE: a call of more than 2^31 - 1 blocks.  JDA_ERROR_MEMORY from the call: no scratch (144 bytes a block and the
+ * coded bytes). */
+enum { JDA_ENCODE_GRAY = 0, JDA_ENCODE_444 = 1, JDA_ENCODE_422 = 2, JDA_ENCODE_420 = 3 };
+typedef struct jda_encode_job { int32_t x, y, w, h, sampling, quality, restart_interval, reserved; } jda_encode_job;
+int jda_encode_bound(int32_t w, int32_t h, int32_t sampling, int32_t restart_interval, int64_t *bytes);
+int jda_encode_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,
+                        void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status);
+
 /* PCI bus id ("0000:8e:00.0") of the context's GPU, for NUMA placement of the host threads that feed it; buf >= 16 bytes */
 int jda_device_pci_bus_id(jda_ctx *ctx, char *buf, int32_t len);
 int jda_device_pci_bus_id_of(int32_t device, char *buf, int32_t len);      /* the same by device ordinal, without a context */
@@ -463,6 +486,15 @@ int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
 int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *rect,
                                int32_t out_w, int32_t out_h, void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded,
                                int32_t *tiles);
+/* jda_decode_to_host_ex, jda_resize_surfaces (only when out_w x out_h differs from the rectangle's size) and jda_encode_surfaces: a JPEG file
+ * in, a baseline JPEG file of rect = {x, y, w, h} (pixels of the visible image at the options' scale; NULL: all of it) at out_w x out_h out;
+ * only files cross the bus.  The image is decoded as JDA_RGB8888, a gray file as JDA_EIGHT_BIT_GRAYSCALE -- and then sampling must be
+ * JDA_ENCODE_GRAY, as it must not be for a colour file (JDA_INVALID_PARAMETER).  Only the MCUs that hold a pixel that is read are decoded.
+ * host_file: capacity bytes of HOST memory; *file_bytes = the file's size; a file that does not fit: JDA_ERROR_MEMORY, *file_bytes = the size
+ * it needs, host_file untouched.  Option bits, refusals and codes as in jda_decode_to_host_resized and jda_encode_surfaces; with
+ * JDA_DECODE_ERROR the MCUs from the bad one on are zeros before the resize and the file is still delivered. */
+int jda_transcode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
+                          int32_t sampling, int32_t quality, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes);
 /* jda_decode_to_host_ex followed by the orientation: prepare, upload, decode to a device canvas, orient its visible rectangle into a second
  * device surface (jda_orient_surfaces) and copy back only the W' * bpp x H' bytes of jda_oriented_geometry: row r at host_pixels + r * pitch_bytes,
  * pitch_bytes >= W' * bpp (any value), rows >= H'.  orientation < 0: the file's; 0..8 as given (0, 1: the visible rectangle as it is); above

@@ -3914,4 +3914,386 @@ template <int MODE, class IO> JDA_HD void jda_cs_scatter(IO &io, const jda_dev_d
     }
 }
 
+// ================================================================================================
+// jda_en_*: decoded surfaces encoded as baseline JPEG files.  The definition is libjpeg's (jcparam.c, jccolor.c,
+// jcsample.c, jfdctint.c, jcdctmgr.c, jchuff.c) and is stated once more, in numpy, in tests/encode_util.py.  Six stages, each a
+// kernel of jda_kernels.hip, the work of a lane written here behind an IO policy so that tests/hostsim/encode_sim.cpp steps the same code:
+//   blocks   lane = one block of the call's flat list (a job's blocks in the order of its scan): the 64 samples of its component
+//            -- colour conversion, replication at the rectangle's edges, h2v1 / h2v2 downsampling -- in registers, the islow FDCT rows
+//            then columns, quantisation by a host-made reciprocal, 64 x int16 in zig-zag order (128 bytes) to HBM, and beside it the
+//            block's DC and the length of its AC code.  A dummy block (luma blocks of the MCU grid that hold no pixel) is zeros.
+//   lengths  lane = block: the DC of the block before it of its component (dummies passed over; none at an interval's start) gives
+//            the DC difference and the block's whole code length; a dummy takes that DC as its own.
+//   scan     a workgroup = a job: positions from lengths.  Every lane sums a run of consecutive elements, then the runs in front of
+//            its own, then walks its run again.  An interval starts on a byte, so the sum is of functions p -> (round ? ceil8(p + a)
+//            : p) + b, which compose.  The same stage sums the 0xFF counts of the stuffing chunks.
+//   emit     lane = block: its code at its bit position in the job's UNSTUFFED scan, dword by dword with an atomic OR into zeroed
+//            memory (a dword may hold the ends of two blocks, or many whole ones); an interval's last block adds the 1-bits to the byte.
+//   count    lane = a 64-byte chunk of an unstuffed scan: the 0xFF bytes in it.
+//   write    lane = chunk: the chunk's bytes at their place in the file -- behind the header, the stuffed zeros of the chunks before
+//            and two bytes for every RSTm before --, RSTm in front of an interval's first byte, EOI behind the last byte; the header's
+//            chunks are copied.  A job whose file is longer than its capacity is left out as a whole.
+#define JDA_EN_THREADS 256
+#define JDA_EN_DUMMY 0x80000000u           // in a block's word of the blocks stage: (AC bits << 16) | (DC & 0xffff)
+struct jda_en_arrays {                     // the call's scratch, device pointers
+    const jda_encode_dev_job *jobs;
+    const jda_encode_quant *quant;
+    const uint32_t *huff;
+    const uint8_t *hdr;
+    int16_t *coef;                         // 64 a block
+    uint32_t *meta, *code;                 // a block: blocks stage -> lengths stage ((difference << 16) | code bits)
+    uint64_t *end;                         // a block: the bit behind its code, from its job's first
+    uint64_t *istart;                      // an interval: its first byte in the unstuffed scan
+    jda_encode_totals *totals;             // a job
+    uint8_t *u;                            // the unstuffed scans (zeros before emit)
+    uint32_t *ffcnt;                       // a chunk
+    uint64_t *ffend;
+    uint32_t n_jobs;
+};
+template <class IO> JDA_HD uint32_t jda_en_find_block(const jda_encode_dev_job *jobs, uint32_t n, uint32_t b, IO &io)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (io.ld32(&jobs[mid].block0) <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+template <class IO> JDA_HD uint32_t jda_en_find_chunk(const jda_encode_dev_job *jobs, uint32_t n, uint32_t c, IO &io)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (io.ld32(&jobs[mid].chunk0) <= c) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+JDA_HD uint32_t jda_en_zigzag(uint32_t z)  // natural index of zig-zag position z (folded: every caller's z is a constant of an unrolled loop)
+{
+    constexpr uint8_t nat[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                                  35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63 };
+    return nat[z];
+}
+JDA_HD uint32_t jda_en_nbits(uint32_t a) { return a ? 32u - (uint32_t)__builtin_clz(a) : 0u; }
+// one pass of jfdctint.c over eight values; FIRST: the row pass (results up by PASS1_BITS), else the column pass (down by it)
+template <bool FIRST> JDA_HD void jda_en_fdct8(int32_t &d0, int32_t &d1, int32_t &d2, int32_t &d3, int32_t &d4, int32_t &d5, int32_t &d6, int32_t &d7)
+{
+    constexpr int N = FIRST ? 11 : 15;
+    const int32_t R = 1 << (N - 1);
+    const int32_t t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4;
+    const int32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    if (FIRST) { d0 = (t10 + t11) << 2; d4 = (t10 - t11) << 2; }
+    else { d0 = (t10 + t11 + 2) >> 2; d4 = (t10 - t11 + 2) >> 2; }
+    int32_t z1 = (t12 + t13) * 4433;
+    d2 = (z1 + t13 * 6270 + R) >> N;
+    d6 = (z1 - t12 * 15137 + R) >> N;
+    z1 = t4 + t7;
+    int32_t z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int32_t z5 = (z3 + z4) * 9633;
+    const int32_t u4 = t4 * 2446, u5 = t5 * 16819, u6 = t6 * 25172, u7 = t7 * 12299;
+    z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+    d7 = (u4 + z1 + z3 + R) >> N;
+    d5 = (u5 + z2 + z4 + R) >> N;
+    d3 = (u6 + z2 + z3 + R) >> N;
+    d1 = (u7 + z1 + z4 + R) >> N;
+}
+// where block s of a job lies: its MCU, its component (0: luma), its block row and column in the component
+JDA_HD void jda_en_place(const jda_encode_dev_job &J, uint32_t s, uint32_t &m, uint32_t &c, uint32_t &by, uint32_t &bx)
+{
+    m = s / J.bpm;
+    const uint32_t k = s - m * J.bpm, my = m / J.cx, mx = m - my * J.cx, nl = J.hs * J.vs;
+    if (k < nl) { const uint32_t v = k / J.hs; c = 0; by = my * J.vs + v; bx = mx * J.hs + (k - v * J.hs); }
+    else { c = 1u + k - nl; by = my; bx = mx; }
+}
+// component c of a pixel: (kr R + kg G + kb B + add) >> 16, libjpeg's jccolor.c
+JDA_HD int32_t jda_en_comp(uint32_t px, int32_t kr, int32_t kg, int32_t kb, int32_t add)
+{
+    return (kr * (int32_t)(px & 0xffu) + kg * (int32_t)((px >> 8) & 0xffu) + kb * (int32_t)((px >> 16) & 0xffu) + add) >> 16;
+}
+template <class IO> JDA_HD void jda_en_block(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t b, IO &io)
+{
+    const uint32_t s = b - J.block0;
+    uint32_t m, c, by, bx;
+    jda_en_place(J, s, m, c, by, bx);
+    uint32_t w[32];
+    const uint32_t t = c ? 1u : 0u;
+    int16_t *out = A.coef + (size_t)b * 64u;
+    if (c == 0u && (bx >= J.wb || by >= J.hb)) {              // a dummy: zeros (the lengths stage gives it its DC), an EOB
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; i++) w[i] = 0u;
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++) io.st128(out + 8u * i, w);
+        io.st32(A.meta + b, JDA_EN_DUMMY | ((io.ld32(A.huff) >> 16) << 16));
+        return;
+    }
+    int32_t d[64];
+    const uint8_t *base = J.src + (size_t)J.y * J.src_pitch;
+    if (J.nc == 1u) {
+#pragma unroll
+        for (uint32_t r = 0; r < 8u; r++) {
+            const uint32_t py = by * 8u + r < J.h ? by * 8u + r : J.h - 1u;
+            const uint8_t *row = base + (size_t)py * J.src_pitch + J.x;
+#pragma unroll
+            for (uint32_t q = 0; q < 8u; q++) {
+                const uint32_t px = bx * 8u + q < J.w ? bx * 8u + q : J.w - 1u;
+                d[r * 8u + q] = (int32_t)io.ld_px8(row + px) - 128;
+            }
+        }
+    } else {
+        const int32_t kr = c == 0u ? 19595 : c == 1u ? -11059 : 32768, kg = c == 0u ? 38470 : c == 1u ? -21709 : -27439;
+        const int32_t kb = c == 0u ? 7471 : c == 1u ? 32768 : -5329, add = c == 0u ? 32768 : (128 << 16) + 32767;
+        const uint32_t sh = c ? J.hs : 1u, sv = c ? J.vs : 1u;         // source pixels of a sample
+        if (sh == 1u) {
+#pragma unroll
+            for (uint32_t r = 0; r < 8u; r++) {
+                const uint32_t py = by * 8u + r < J.h ? by * 8u + r : J.h - 1u;
+                const uint8_t *row = base + (size_t)py * J.src_pitch + (size_t)J.x * 4u;
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; q++) {
+                    const uint32_t px = bx * 8u + q < J.w ? bx * 8u + q : J.w - 1u;
+                    d[r * 8u + q] = jda_en_comp(io.ld_px32(row + px * 4u), kr, kg, kb, add) - 128;
+                }
+            }
+        } else {
+            // the plane goes down by replication to a multiple of sv rows only; the DOWNSAMPLED plane's last row is replicated below that
+            const uint32_t ch = (J.h + sv - 1u) / sv;
+#pragma unroll
+            for (uint32_t r = 0; r < 8u; r++) {
+                const uint32_t oy = by * 8u + r < ch ? by * 8u + r : ch - 1u;
+                const uint32_t y0 = oy * sv, y1 = oy * sv + sv - 1u < J.h ? oy * sv + sv - 1u : J.h - 1u;
+                const uint8_t *row0 = base + (size_t)y0 * J.src_pitch + (size_t)J.x * 4u, *row1 = base + (size_t)y1 * J.src_pitch + (size_t)J.x * 4u;
+#pragma unroll
+                for (uint32_t q = 0; q < 8u; q++) {
+                    const uint32_t ox = bx * 8u + q;
+                    const uint32_t x0 = 2u * ox < J.w ? 2u * ox : J.w - 1u, x1 = 2u * ox + 1u < J.w ? 2u * ox + 1u : J.w - 1u;
+                    int32_t v = jda_en_comp(io.ld_px32(row0 + x0 * 4u), kr, kg, kb, add) + jda_en_comp(io.ld_px32(row0 + x1 * 4u), kr, kg, kb, add);
+                    if (sv == 2u) {
+                        v += jda_en_comp(io.ld_px32(row1 + x0 * 4u), kr, kg, kb, add) + jda_en_comp(io.ld_px32(row1 + x1 * 4u), kr, kg, kb, add);
+                        v = (v + 1 + (int32_t)(q & 1u)) >> 2;          // bias 1, 2, 1, 2 along the row (ox and q have the same parity)
+                    } else v = (v + (int32_t)(q & 1u)) >> 1;            // bias 0, 1, 0, 1
+                    d[r * 8u + q] = v - 128;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < 8u; r++) jda_en_fdct8<true>(d[r * 8u], d[r * 8u + 1u], d[r * 8u + 2u], d[r * 8u + 3u], d[r * 8u + 4u], d[r * 8u + 5u], d[r * 8u + 6u], d[r * 8u + 7u]);
+#pragma unroll
+    for (uint32_t q = 0; q < 8u; q++) jda_en_fdct8<false>(d[q], d[8u + q], d[16u + q], d[24u + q], d[32u + q], d[40u + q], d[48u + q], d[56u + q]);
+    // quantise in zig-zag order; the AC code's length on the way
+    const jda_encode_quant *Q = A.quant + J.quant;
+    const uint32_t *ac = A.huff + t * 256u;
+    uint32_t bits = 0, run = 0, dc = 0;
+#pragma unroll
+    for (uint32_t z = 0; z < 64u; z++) {
+        const uint32_t n = jda_en_zigzag(z);
+        const int32_t v = d[n];
+        const uint32_t a = (uint32_t)(v < 0 ? -v : v) + io.ld32(&Q->half[t][n]);
+        const uint32_t r = (uint32_t)(((uint64_t)a * io.ld32(&Q->recip[t][n])) >> 32);       // = a / (8 q): a < 2^17, 8 q <= 2040
+        const uint32_t val = (uint32_t)(v < 0 ? -(int32_t)r : (int32_t)r) & 0xffffu;
+        if (z & 1u) w[z >> 1] |= val << 16; else w[z >> 1] = val;
+        if (z == 0u) dc = val;
+        else if (r == 0u) run++;
+        else {
+            bits += (run >> 4) * (io.ld32(ac + 0xf0u) >> 16) + (io.ld32(ac + (((run & 15u) << 4) | jda_en_nbits(r))) >> 16) + jda_en_nbits(r);
+            run = 0;
+        }
+    }
+    if (run) bits += io.ld32(ac) >> 16;
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) io.st128(out + 8u * i, w + 4u * i);
+    io.st32(A.meta + b, (bits << 16) | dc);
+}
+template <class IO> JDA_HD void jda_en_length(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t b, IO &io)
+{
+    const uint32_t s = b - J.block0, m = s / J.bpm, k = s - m * J.bpm, nl = J.hs * J.vs;
+    const uint32_t *meta = A.meta + J.block0;
+    const uint32_t me = io.ld32(meta + s);
+    const bool fresh = m == 0u || (J.ri && m % J.ri == 0u);          // the MCU opens an interval
+    int32_t pred = 0;
+    if (k < nl && k > 0u) {
+        uint32_t j = s - 1u, v = io.ld32(meta + j);
+        while (v & JDA_EN_DUMMY) v = io.ld32(meta + --j);             // (an MCU's first block is never a dummy)
+        pred = (int16_t)(v & 0xffffu);
+    } else if (!fresh) {
+        uint32_t j = k < nl ? (m - 1u) * J.bpm + nl - 1u : s - J.bpm, v = io.ld32(meta + j);
+        while (v & JDA_EN_DUMMY) v = io.ld32(meta + --j);
+        pred = (int16_t)(v & 0xffffu);
+    }
+    int32_t diff = 0;
+    if (me & JDA_EN_DUMMY) io.st16(A.coef + (size_t)b * 64u, (int16_t)pred);
+    else diff = (int32_t)(int16_t)(me & 0xffffu) - pred;
+    const uint32_t cat = jda_en_nbits((uint32_t)(diff < 0 ? -diff : diff));
+    const uint32_t bits = ((me >> 16) & 0x7fffu) + (io.ld32(A.huff + 512u + (k < nl ? 0u : 16u) + cat) >> 16) + cat;
+    io.st32(A.code + b, ((uint32_t)diff << 16) | bits);
+}
+
+// ---- scan: position of every element of a job's list from the elements' lengths.  Element i of [first, first + n) has the length
+// vals[i] & mask and, with period != 0, starts on a byte where (i - first) % period == 0.  end[i] = the position behind it.
+// LDS: 768 x 64 bits: a lane's run as the function p -> (r ? ceil8(p + a) : p) + b: a at [tid], b at [256 + tid], r at [512 + tid].
+struct jda_en_fn { uint64_t a, b; uint32_t r; };
+JDA_HD uint64_t jda_en_ceil8(uint64_t p) { return (p + 7u) & ~(uint64_t)7u; }
+JDA_HD uint64_t jda_en_apply(const jda_en_fn &f, uint64_t p) { return (f.r ? jda_en_ceil8(p + f.a) : p) + f.b; }
+JDA_HD void jda_en_then(jda_en_fn &f, bool round, uint64_t len)      // f := (an element of length len, on a byte if round) after f
+{
+    if (!round) { f.b += len; return; }
+    if (f.r) f.b = jda_en_ceil8(f.b) + len;
+    else { f.r = 1u; f.a = f.b; f.b = len; }
+}
+JDA_HD void jda_en_run(uint32_t n, uint32_t tid, uint32_t &i0, uint32_t &i1)
+{
+    const uint32_t per = (n + JDA_EN_THREADS - 1u) / JDA_EN_THREADS;
+    i0 = tid * per < n ? tid * per : n;
+    i1 = i0 + per < n ? i0 + per : n;
+}
+template <class IO> JDA_HD void jda_en_scan_local(const uint32_t *vals, uint32_t mask, uint32_t first, uint32_t n, uint32_t period, uint32_t tid, IO &io)
+{
+    uint32_t i0, i1;
+    jda_en_run(n, tid, i0, i1);
+    jda_en_fn f = { 0u, 0u, 0u };
+    for (uint32_t i = i0; i < i1; i++) jda_en_then(f, period && i && i % period == 0u, io.ld32(vals + first + i) & mask);
+    io.lds_wr64(tid, f.a); io.lds_wr64(256u + tid, f.b); io.lds_wr64(512u + tid, f.r);
+}
+// behind the barrier.  Returns the position behind the job's last element in the lane that owns it, else ~0
+template <class IO> JDA_HD uint64_t jda_en_scan_write(const uint32_t *vals, uint32_t mask, uint32_t first, uint32_t n, uint32_t period, uint64_t *end, uint64_t *istart,
+                                                      uint32_t tid, IO &io)
+{
+    uint32_t i0, i1;
+    jda_en_run(n, tid, i0, i1);
+    if (i0 >= i1) return ~(uint64_t)0;
+    uint64_t p = 0;
+    for (uint32_t j = 0; j < tid; j++) {
+        jda_en_fn f;
+        f.a = io.lds_rd64(j); f.b = io.lds_rd64(256u + j); f.r = (uint32_t)io.lds_rd64(512u + j);
+        p = jda_en_apply(f, p);
+    }
+    for (uint32_t i = i0; i < i1; i++) {
+        if (istart && (period ? i % period == 0u : i == 0u)) {
+            p = jda_en_ceil8(p);
+            io.st64(istart + (period ? i / period : 0u), p >> 3);
+        }
+        p += io.ld32(vals + first + i) & mask;
+        io.st64(end + first + i, p);
+    }
+    return i1 == n ? p : ~(uint64_t)0;
+}
+
+// ---- emit: a block's code into the unstuffed scan
+template <class IO> struct jda_en_bits { uint64_t acc; uint32_t n; uint32_t *dw; IO *io; };
+template <class IO> JDA_HD void jda_en_flush(jda_en_bits<IO> &W)
+{
+    const uint32_t v = (uint32_t)(W.acc >> 32);
+    if (v) W.io->atomic_or(W.dw, ((v & 0xffu) << 24) | ((v & 0xff00u) << 8) | ((v >> 8) & 0xff00u) | (v >> 24));
+}
+template <class IO> JDA_HD void jda_en_put(jda_en_bits<IO> &W, uint32_t v, uint32_t len)      // len <= 16 bits of v, n < 32 on entry
+{
+    if (!len) return;
+    W.acc |= (uint64_t)(v & ((1u << len) - 1u)) << (64u - W.n - len);
+    W.n += len;
+    if (W.n >= 32u) { jda_en_flush(W); W.acc <<= 32; W.n -= 32u; W.dw++; }
+}
+template <class IO> JDA_HD void jda_en_emit(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t b, IO &io)
+{
+    const uint32_t s = b - J.block0, m = s / J.bpm, k = s - m * J.bpm, t = k < J.hs * J.vs ? 0u : 1u;
+    const uint32_t code = io.ld32(A.code + b);
+    const int32_t diff = (int32_t)(int16_t)(code >> 16);
+    const uint64_t start = J.u_off * 8u + io.ld64(A.end + b) - (code & 0xffffu);
+    jda_en_bits<IO> W;
+    W.acc = 0; W.n = (uint32_t)(start & 31u); W.dw = (uint32_t *)A.u + (start >> 5); W.io = &io;
+    const uint32_t *ac = A.huff + t * 256u;
+    const uint32_t cat = jda_en_nbits((uint32_t)(diff < 0 ? -diff : diff)), hd = io.ld32(A.huff + 512u + t * 16u + cat);
+    jda_en_put(W, hd & 0xffffu, hd >> 16);
+    jda_en_put(W, (uint32_t)(diff < 0 ? diff - 1 : diff), cat);
+    const uint32_t zrl = io.ld32(ac + 0xf0u);
+    uint32_t run = 0;
+    for (uint32_t i = 0; i < 8u; i++) {
+        uint32_t w[4];
+        io.ld128(A.coef + (size_t)b * 64u + 8u * i, w);
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; j++) {
+            if (i == 0u && j == 0u) continue;
+            const int32_t v = (int32_t)(int16_t)((w[j >> 1] >> (16u * (j & 1u))) & 0xffffu);
+            if (v == 0) { run++; continue; }
+            for (; run > 15u; run -= 16u) jda_en_put(W, zrl & 0xffffu, zrl >> 16);
+            const uint32_t sz = jda_en_nbits((uint32_t)(v < 0 ? -v : v)), h = io.ld32(ac + ((run << 4) | sz));
+            jda_en_put(W, h & 0xffffu, h >> 16);
+            jda_en_put(W, (uint32_t)(v < 0 ? v - 1 : v), sz);
+            run = 0;
+        }
+    }
+    if (run) { const uint32_t h = io.ld32(ac); jda_en_put(W, h & 0xffffu, h >> 16); }
+    const uint32_t period = J.ri * J.bpm;
+    if (s + 1u == J.n_blocks || (period && (s + 1u) % period == 0u)) jda_en_put(W, 0xffu, (8u - (W.n & 7u)) & 7u);      // the interval's 1-bits to the byte
+    if (W.n) jda_en_flush(W);
+}
+
+// ---- count and write: the unstuffed scan's chunks
+template <class IO> JDA_HD void jda_en_count(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t c, IO &io)
+{
+    const uint32_t local = c - J.chunk0;
+    uint32_t cnt = 0;
+    if (local >= J.h_chunks) {
+        const uint8_t *p = A.u + J.u_off + (size_t)(local - J.h_chunks) * JDA_EN_CHUNK;
+        for (uint32_t i = 0; i < JDA_EN_CHUNK / 16u; i++) {
+            uint32_t w[4];
+            io.ld128(p + 16u * i, w);
+#pragma unroll
+            for (uint32_t j = 0; j < 16u; j++) cnt += ((w[j >> 2] >> (8u * (j & 3u))) & 0xffu) == 0xffu ? 1u : 0u;
+        }
+    }
+    io.st32(A.ffcnt + c, cnt);
+}
+template <class IO> JDA_HD void jda_en_write(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t job, uint32_t c, IO &io)
+{
+    const uint64_t u_bytes = io.ld64(&A.totals[job].u_bytes);
+    if (io.ld64(&A.totals[job].file_bytes) > J.capacity) return;       // the file does not fit: no byte of it is written
+    const uint32_t local = c - J.chunk0;
+    if (local < J.h_chunks) {
+        const uint32_t o = local * JDA_EN_CHUNK, left = J.hdr_len - o < JDA_EN_CHUNK ? J.hdr_len - o : JDA_EN_CHUNK;
+        for (uint32_t i = 0; i < left; i++) io.st8(J.dst + o + i, io.ld8(A.hdr + J.hdr_off + o + i));
+        return;
+    }
+    const uint64_t p0 = (uint64_t)(local - J.h_chunks) * JDA_EN_CHUNK;
+    const uint64_t *ist = A.istart + J.int0;
+    uint32_t lo = 0, hi = J.n_int;                                      // intervals [1, next) start in front of p0: their markers are in front of this chunk
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (io.ld64(ist + mid) < p0) lo = mid; else hi = mid;
+    }
+    uint32_t next = lo + 1u;
+    uint8_t *q = J.dst + J.hdr_len + p0 + (io.ld64(A.ffend + c) - io.ld32(A.ffcnt + c)) + 2u * (uint64_t)lo;
+    uint64_t nx = next < J.n_int ? io.ld64(ist + next) : ~(uint64_t)0;
+    const uint8_t *src = A.u + J.u_off + p0;
+    for (uint32_t i = 0; i < JDA_EN_CHUNK / 16u; i++) {
+        if (p0 + 16u * i >= u_bytes) break;
+        uint32_t w[4];
+        io.ld128(src + 16u * i, w);
+#pragma unroll
+        for (uint32_t j = 0; j < 16u; j++) {
+            const uint64_t p = p0 + 16u * i + j;
+            if (p >= u_bytes) continue;
+            if (p == nx) {
+                io.st8(q++, 0xffu); io.st8(q++, 0xd0u + ((next - 1u) & 7u));
+                next++;
+                nx = next < J.n_int ? io.ld64(ist + next) : ~(uint64_t)0;
+            }
+            const uint32_t v = (w[j >> 2] >> (8u * (j & 3u))) & 0xffu;
+            io.st8(q++, v);
+            if (v == 0xffu) io.st8(q++, 0u);
+            if (p + 1u == u_bytes) { io.st8(q++, 0xffu); io.st8(q++, 0xd9u); }
+        }
+    }
+}
+// a job's scan, one lane: bytes = the 0xFF counts of its chunks (else its blocks' code lengths), second = behind the barrier
+template <class IO> JDA_HD void jda_en_scan_job(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t job, bool bytes, bool second, uint32_t tid, IO &io)
+{
+    const uint32_t *vals = bytes ? A.ffcnt : A.code;
+    const uint32_t mask = bytes ? 0xffffffffu : 0xffffu, first = bytes ? J.chunk0 : J.block0, n = bytes ? J.n_chunks : J.n_blocks, period = bytes ? 0u : J.ri * J.bpm;
+    if (!second) { jda_en_scan_local(vals, mask, first, n, period, tid, io); return; }
+    const uint64_t p = jda_en_scan_write(vals, mask, first, n, period, bytes ? A.ffend : A.end, bytes ? (uint64_t *)0 : A.istart + J.int0, tid, io);
+    if (p == ~(uint64_t)0) return;
+    if (!bytes) io.st64(&A.totals[job].u_bytes, jda_en_ceil8(p) >> 3);
+    else io.st64(&A.totals[job].file_bytes, (uint64_t)J.hdr_len + io.ld64(&A.totals[job].u_bytes) + p + 2u * (uint64_t)(J.n_int - 1u) + 2u);
+}
+
 #endif // JDA_DEVICE_CORE_H

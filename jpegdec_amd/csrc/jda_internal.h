@@ -219,4 +219,24 @@ struct jda_resize_job {
     uint32_t src_pitch, dst_pitch, out_w, out_h, htab, vtab, hk, vk, tile0, tiles_x, th, pad_;
 };
 
+// One image of an encode call (device pointers; jda_en_* in jda_device_core.h): the rectangle {x, y, w, h} of the surface
+// at src becomes a baseline file at dst.  hs x vs: luma blocks of an MCU (1 x 1 with nc = 1: gray); cx x cy MCUs of bpm blocks; wb x hb:
+// the luma blocks that hold a pixel (the others of the MCU grid are dummies); ri: the restart interval in MCUs.  The job's blocks are
+// [block0, block0 + n_blocks) of the call's flat list, in the order of the scan; its intervals' first bytes lie at istart[int0 ..
+// int0 + n_int); quant: its record in the call's quantisers; its header: hdr_len bytes at hdr_off of the header blob.  Known once the
+// lengths are (the second upload): u_off, where its unstuffed scan lies in the call's stream buffer (a multiple of 64), and [chunk0,
+// chunk0 + n_chunks) of the flat list of 64-byte chunks, the first h_chunks of them the header's.
+struct jda_encode_dev_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint64_t capacity, u_off;
+    uint32_t src_pitch, x, y, w, h, hs, vs, nc, cx, cy, bpm, wb, hb, ri, block0, n_blocks, quant, hdr_off, hdr_len, int0, n_int, chunk0, n_chunks, h_chunks;
+};
+struct jda_encode_quant { uint32_t recip[2][64]; uint32_t half[2][64]; };      // natural order, per table: ceil(2^32 / (8 q)) and (8 q) >> 1
+struct jda_encode_totals { uint64_t u_bytes, file_bytes; };                    // per job: its unstuffed scan, its whole file
+#define JDA_EN_HUFF_DWORDS 544u           // (length << 16) | code: AC symbol rs of table t at [t * 256 + rs], DC category s at [512 + t * 16 + s]
+#define JDA_EN_CHUNK 64u                  // bytes of a stuffing chunk
+#define JDA_EN_BLOCK_BITS 1665u           // no block's code is longer
+enum { JDA_EN_STAGE_BLOCKS = 0, JDA_EN_STAGE_LENGTHS, JDA_EN_STAGE_SCAN_BITS, JDA_EN_STAGE_EMIT, JDA_EN_STAGE_COUNT, JDA_EN_STAGE_SCAN_BYTES, JDA_EN_STAGE_WRITE, JDA_EN_STAGES };
+
 #endif

@@ -2002,6 +2002,107 @@ extern "C" hipError_t jda_launch_resize(const jda_resize_job *jobs, uint32_t n, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// jda_encode_*: decoded surfaces encoded as baseline JPEG files (the stages and what a lane of each does: jda_en_* in jda_device_core.h;
+// DESIGN.md 5.13).  blocks, lengths and emit run a lane per block of the call's flat block list, count and write a lane per 64-byte chunk
+// of its flat chunk list (the job of a lane: bisection over the job records); scan runs a workgroup per job, twice in a call.  The
+// transform lives in registers: no LDS but the scan's 6 KiB.  Global accesses: dword (RGB8888) or byte (gray) pixel loads, 16-byte
+// coefficient stores and loads, dword atomic ORs into the zeroed unstuffed scan, byte stores into the file (a file may begin anywhere).
+struct jda_encode_io {
+    uint64_t *lds;
+    __device__ __forceinline__ uint32_t ld_px32(const uint8_t *p) const { return *(const jda_u32_alias JDA_GLOBAL *)JDA_G(const uint8_t, p); }
+    __device__ __forceinline__ uint32_t ld_px8(const uint8_t *p) const { return *JDA_G(const uint8_t, p); }
+    __device__ __forceinline__ uint32_t ld8(const uint8_t *p) const { return *JDA_G(const uint8_t, p); }
+    __device__ __forceinline__ uint32_t ld32(const uint32_t *p) const { return *JDA_G(const uint32_t, p); }
+    __device__ __forceinline__ uint64_t ld64(const uint64_t *p) const { return *JDA_G(const uint64_t, p); }
+    __device__ __forceinline__ void ld128(const void *p, uint32_t *v) const
+    {
+        const uint4 q = *JDA_G(const uint4, p);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+    __device__ __forceinline__ void st8(uint8_t *p, uint32_t v) const { *JDA_G(uint8_t, p) = (uint8_t)v; }
+    __device__ __forceinline__ void st16(int16_t *p, int16_t v) const { *JDA_G(int16_t, p) = v; }
+    __device__ __forceinline__ void st32(uint32_t *p, uint32_t v) const { *JDA_G(uint32_t, p) = v; }
+    __device__ __forceinline__ void st64(uint64_t *p, uint64_t v) const { *JDA_G(uint64_t, p) = v; }
+    __device__ __forceinline__ void st128(void *p, const uint32_t *v) const { *JDA_G(uint4, p) = make_uint4(v[0], v[1], v[2], v[3]); }
+    __device__ __forceinline__ void atomic_or(uint32_t *p, uint32_t v) const { (void)__hip_atomic_fetch_or(JDA_G(uint32_t, p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ void lds_wr64(uint32_t i, uint64_t v) const { lds[i] = v; }
+    __device__ __forceinline__ uint64_t lds_rd64(uint32_t i) const { return lds[i]; }
+};
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_encode_blocks(jda_en_arrays A, uint32_t n_blocks)
+{
+    const uint32_t b = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (b >= n_blocks) return;
+    jda_encode_io io; io.lds = nullptr;
+    const jda_encode_dev_job J = A.jobs[jda_en_find_block(A.jobs, A.n_jobs, b, io)];
+    jda_en_block(A, J, b, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_encode_lengths(jda_en_arrays A, uint32_t n_blocks)
+{
+    const uint32_t b = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (b >= n_blocks) return;
+    jda_encode_io io; io.lds = nullptr;
+    const jda_encode_dev_job J = A.jobs[jda_en_find_block(A.jobs, A.n_jobs, b, io)];
+    jda_en_length(A, J, b, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_encode_scan(jda_en_arrays A, uint32_t bytes)
+{
+    __shared__ uint64_t scan_lds[3 * JDA_EN_THREADS];
+    const uint32_t job = blockIdx.x;
+    const jda_encode_dev_job J = A.jobs[job];
+    jda_encode_io io; io.lds = scan_lds;
+    jda_en_scan_job(A, J, job, bytes != 0u, false, threadIdx.x, io);
+    __syncthreads();
+    jda_en_scan_job(A, J, job, bytes != 0u, true, threadIdx.x, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_encode_emit(jda_en_arrays A, uint32_t n_blocks)
+{
+    const uint32_t b = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (b >= n_blocks) return;
+    jda_encode_io io; io.lds = nullptr;
+    const jda_encode_dev_job J = A.jobs[jda_en_find_block(A.jobs, A.n_jobs, b, io)];
+    jda_en_emit(A, J, b, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_encode_count(jda_en_arrays A, uint32_t n_chunks)
+{
+    const uint32_t c = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (c >= n_chunks) return;
+    jda_encode_io io; io.lds = nullptr;
+    const jda_encode_dev_job J = A.jobs[jda_en_find_chunk(A.jobs, A.n_jobs, c, io)];
+    jda_en_count(A, J, c, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_encode_write(jda_en_arrays A, uint32_t n_chunks)
+{
+    const uint32_t c = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (c >= n_chunks) return;
+    jda_encode_io io; io.lds = nullptr;
+    const uint32_t job = jda_en_find_chunk(A.jobs, A.n_jobs, c, io);
+    const jda_encode_dev_job J = A.jobs[job];
+    jda_en_write(A, J, job, c, io);
+}
+// One stage of a call (JDA_EN_STAGE_*, the order they run in); the two halves of jda_encode_surfaces are stages 0..2 and 3..6.
+extern "C" hipError_t jda_launch_encode_stage(const jda_en_arrays *A, uint32_t stage, uint32_t n_blocks, uint32_t n_chunks, hipStream_t stream)
+{
+    if (!A || A->n_jobs == 0u || n_blocks == 0u || stage >= JDA_EN_STAGES || (stage >= JDA_EN_STAGE_EMIT && (n_chunks == 0u || !A->u))) return hipErrorInvalidValue;
+    const dim3 block(JDA_EN_THREADS), bgrid((n_blocks + JDA_EN_THREADS - 1u) / JDA_EN_THREADS), cgrid((n_chunks + JDA_EN_THREADS - 1u) / JDA_EN_THREADS);
+    switch (stage) {
+    case JDA_EN_STAGE_BLOCKS: JDA_LAUNCH(jda_encode_blocks, bgrid, block, 0, stream, *A, n_blocks); break;
+    case JDA_EN_STAGE_LENGTHS: JDA_LAUNCH(jda_encode_lengths, bgrid, block, 0, stream, *A, n_blocks); break;
+    case JDA_EN_STAGE_SCAN_BITS: JDA_LAUNCH(jda_encode_scan, dim3(A->n_jobs), block, 0, stream, *A, 0u); break;
+    case JDA_EN_STAGE_EMIT: JDA_LAUNCH(jda_encode_emit, bgrid, block, 0, stream, *A, n_blocks); break;
+    case JDA_EN_STAGE_COUNT: JDA_LAUNCH(jda_encode_count, cgrid, block, 0, stream, *A, n_chunks); break;
+    case JDA_EN_STAGE_SCAN_BYTES: JDA_LAUNCH(jda_encode_scan, dim3(A->n_jobs), block, 0, stream, *A, 1u); break;
+    default: JDA_LAUNCH(jda_encode_write, cgrid, block, 0, stream, *A, n_chunks); break;
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // jda_coef_tiles<MODE>: tiles decoded from coefficient images (jda_ct_* in jda_device_core.h: the load phase that stands in for
 // P1, then the decode kernel's own list / column / row / colour stages).  A wavefront = a tile of the launch list, four to a
 // workgroup; a wavefront owns its share of the LDS, its own copy of the image's quantisers included -- the tiles of a workgroup may

@@ -23,6 +23,7 @@
 #include "jda_runtime_internal.h"
 #include "jda_pack_plan.h"
 #include "jda_resize_plan.h"
+#include "jda_encode_plan.h"
 
 extern "C" uint32_t jda_image_fast_mul(const jda_image *img);
 extern "C" uint32_t jda_image_general_p1(const jda_image *img);
@@ -1839,6 +1840,192 @@ int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, i
     jda_pool_free(ctx, dsurf);
     jda_dev_image_free(ctx, dimg);
     if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
+    return rc;
+}
+
+// ---- baseline encode (jda_encode_* in jda_kernels.hip; the stages: jda_en_* in jda_device_core.h; checks, records and headers: jda_encode_plan.h)
+// Two halves with the host between them: the records go up, blocks / lengths / scan run, the per-job sizes of the unstuffed scans come back
+// (16 bytes a job), the scans' buffer is taken from the pool and zeroed, the records go up again with every job's place in it, and emit /
+// count / scan / write run; then the files' sizes come back.
+int jda_encode_bound(int32_t w, int32_t h, int32_t sampling, int32_t restart_interval, int64_t *bytes)
+{
+    return jda_encode_bound_bytes(w, h, sampling, restart_interval, bytes);
+}
+struct encode_run { uint8_t *a, *b; jda_en_arrays A; jda_encode_plan_out P; std::vector<jda_encode_totals> totals; float *stage_ms; };
+// stages [s0, s1) queued back to back; with stage_ms (the measuring hook) each between the context's two timer events, its time added to stage_ms[stage]
+static hipError_t encode_stages(jda_ctx *ctx, encode_run &R, uint32_t s0, uint32_t s1)
+{
+    hipError_t e = hipSuccess;
+    for (uint32_t s = s0; s < s1 && e == hipSuccess; s++) {
+        if (R.stage_ms) e = hipEventRecord(ctx->ev_start, ctx->stream);
+        if (e == hipSuccess) e = jda_launch_encode_stage(&R.A, s, R.P.n_blocks, R.P.n_chunks, ctx->stream);
+        if (R.stage_ms) {
+            float ms = 0.f;
+            if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
+            if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop);
+            R.stage_ms[s] += ms;
+        }
+    }
+    return e;
+}
+static int encode_lengths(jda_ctx *ctx, encode_run &R)
+{
+    jda_encode_plan_out &P = R.P;
+    const size_t n = P.jobs.size(), nb = P.n_blocks;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_jobs = take(n * sizeof(jda_encode_dev_job)), o_quant = take(P.quant.size() * sizeof(jda_encode_quant)), o_huff = take(P.huff.size() * 4), o_hdr = take(P.hdr.size());
+    const size_t o_coef = take(nb * 128), o_meta = take(nb * 4), o_code = take(nb * 4), o_end = take(nb * 8), o_ist = take((size_t)P.n_int * 8), o_tot = take(n * sizeof(jda_encode_totals));
+    hipError_t e = jda_pool_alloc(ctx, (void **)&R.a, off);
+    if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(encode scratch)"); return JDA_ERROR_MEMORY; }
+    jda_en_arrays &A = R.A;
+    memset(&A, 0, sizeof(A));
+    A.jobs = (const jda_encode_dev_job *)(R.a + o_jobs); A.quant = (const jda_encode_quant *)(R.a + o_quant); A.huff = (const uint32_t *)(R.a + o_huff); A.hdr = R.a + o_hdr;
+    A.coef = (int16_t *)(R.a + o_coef); A.meta = (uint32_t *)(R.a + o_meta); A.code = (uint32_t *)(R.a + o_code); A.end = (uint64_t *)(R.a + o_end);
+    A.istart = (uint64_t *)(R.a + o_ist); A.totals = (jda_encode_totals *)(R.a + o_tot); A.n_jobs = (uint32_t)n;
+    e = hipMemcpyAsync(R.a + o_jobs, P.jobs.data(), n * sizeof(jda_encode_dev_job), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_quant, P.quant.data(), P.quant.size() * sizeof(jda_encode_quant), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_huff, P.huff.data(), P.huff.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_hdr, P.hdr.data(), P.hdr.size(), hipMemcpyHostToDevice, ctx->stream);
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }      // (the records are on the stack of this call)
+    if (e == hipSuccess) e = encode_stages(ctx, R, JDA_EN_STAGE_BLOCKS, JDA_EN_STAGE_EMIT);
+    R.totals.resize(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.totals.data(), A.totals, n * sizeof(jda_encode_totals), hipMemcpyDeviceToHost, ctx->stream);
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_encode_lengths");
+}
+static int encode_files(jda_ctx *ctx, encode_run &R)
+{
+    jda_encode_plan_out &P = R.P;
+    const size_t n = P.jobs.size();
+    int rc = jda_encode_plan_place(&P, R.totals.data());
+    if (rc != JDA_SUCCESS) return rc;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_u = take((size_t)P.u_total), o_cnt = take((size_t)P.n_chunks * 4), o_end = take((size_t)P.n_chunks * 8);
+    hipError_t e = jda_pool_alloc(ctx, (void **)&R.b, off);
+    if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(encode streams)"); return JDA_ERROR_MEMORY; }
+    R.A.u = R.b + o_u; R.A.ffcnt = (uint32_t *)(R.b + o_cnt); R.A.ffend = (uint64_t *)(R.b + o_end);
+    e = hipMemsetAsync(R.A.u, 0, (size_t)P.u_total, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((void *)R.A.jobs, P.jobs.data(), n * sizeof(jda_encode_dev_job), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = encode_stages(ctx, R, JDA_EN_STAGE_EMIT, JDA_EN_STAGES);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.totals.data(), R.A.totals, n * sizeof(jda_encode_totals), hipMemcpyDeviceToHost, ctx->stream);
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_encode_files");
+}
+
+static int encode_call(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,
+                       void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0 || (bytes_per_pixel != 1 && bytes_per_pixel != 4)) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    if (!src || !jobs || !dst || !dst_capacity || !dst_bytes || !status) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    encode_run R;
+    R.a = R.b = NULL; R.stage_ms = stage_ms;
+    int rc = jda_encode_plan_jobs(n, src, bytes_per_pixel, jobs, dst, dst_capacity, &R.P);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = encode_lengths(ctx, R);
+    if (rc == JDA_SUCCESS) rc = encode_files(ctx, R);
+    if (R.b) jda_pool_free(ctx, R.b);
+    if (R.a) jda_pool_free(ctx, R.a);
+    if (rc != JDA_SUCCESS) return rc;
+    for (int i = 0; i < n; i++) {
+        dst_bytes[i] = (int64_t)R.totals[(size_t)i].file_bytes;
+        status[i] = R.totals[(size_t)i].file_bytes > (uint64_t)dst_capacity[i] ? JDA_ERROR_MEMORY : JDA_SUCCESS;
+    }
+    return JDA_SUCCESS;
+}
+int jda_encode_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,
+                        void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status)
+{
+    return encode_call(ctx, n, src, bytes_per_pixel, jobs, dst, dst_capacity, dst_bytes, status, NULL);
+}
+// Measuring hook of tools/encode_bench.py (not part of the public header): jda_encode_surfaces with every one of its seven launches between
+// the context's two timer events on its stream; stage_ms[JDA_EN_STAGES] (order: JDA_EN_STAGE_*) is ADDED to, so the caller zeroes it.
+int jda_internal_encode_time(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,
+                             void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
+{
+    if (!stage_ms) return JDA_INVALID_PARAMETER;
+    return encode_call(ctx, n, src, bytes_per_pixel, jobs, dst, dst_capacity, dst_bytes, status, stage_ms);
+}
+
+int jda_transcode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
+                          int32_t sampling, int32_t quality, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes)
+{
+    if (file_bytes) *file_bytes = 0;
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!jpeg || !host_file || !file_bytes || capacity < 0 || out_w <= 0 || out_h <= 0) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    int32_t err = JDA_SUCCESS;
+    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
+    if (!img) return err;
+    const jda_image_info I = *jda_image_get_info(img);
+    const int32_t pixel_type = I.ncomp == 1 ? JDA_EIGHT_BIT_GRAYSCALE : JDA_RGB8888;       // a gray file is encoded as it is decoded
+    int bpp, ow, oh, cw, ch;
+    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
+    if (rc == JDA_SUCCESS && (ow > cw || oh > ch)) rc = JDA_INVALID_PARAMETER;
+    const int32_t whole[4] = { 0, 0, ow, oh };
+    const int32_t *box = rect ? rect : whole;
+    if (rc == JDA_SUCCESS && (box[0] < 0 || box[1] < 0 || box[2] <= 0 || box[3] <= 0 || (int64_t)box[0] + box[2] > ow || (int64_t)box[1] + box[3] > oh)) rc = JDA_INVALID_PARAMETER;
+    int64_t bound = 0;
+    if (rc == JDA_SUCCESS) rc = jda_encode_bound_bytes(out_w, out_h, sampling, restart_interval, &bound);
+    if (rc == JDA_SUCCESS && (quality < 1 || quality > 100 || (sampling == JDA_ENCODE_GRAY) != (bpp == 1))) rc = JDA_INVALID_PARAMETER;
+    const bool resized = rc == JDA_SUCCESS && (out_w != box[2] || out_h != box[3]);
+    { uint32_t k; if (resized) rc = jda_resize_axis_ksize(box[0], box[0] + box[2], out_w, &k); if (resized && rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[1], box[1] + box[3], out_h, &k); }
+    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
+    jda_dev_image *dimg = jda_upload(ctx, img, &err);
+    uint32_t nok = 0;
+    jda_image_block_index(img, &nok);
+    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
+    jda_image_free(img);
+    if (!dimg) return err;
+    const int cpitch = (int)align16((size_t)cw * bpp), opitch = (int)align16((size_t)out_w * bpp);
+    const size_t cbytes = (size_t)cpitch * ch, rbytes = resized ? (size_t)opitch * out_h : 0;
+    const int64_t fcap = std::min(capacity, bound);                                        // (no file is longer than the bound)
+    uint8_t *dsurf = NULL;                                                                  // the decoded canvas, the resized surface behind it, the file behind that
+    if (jda_pool_alloc(ctx, (void **)&dsurf, cbytes + rbytes + (size_t)fcap + 16) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
+    jda_output C, S, D;
+    C.pixels = dsurf; C.pitch_bytes = cpitch; C.width_px = cw; C.rows = ch;
+    S = C; S.width_px = ow; S.rows = oh;
+    D.pixels = dsurf + cbytes; D.pitch_bytes = opitch; D.width_px = out_w; D.rows = out_h;
+    resize_plan plan;
+    plan.block = NULL;
+    int32_t reads[4] = { box[0], box[1], box[0] + box[2], box[1] + box[3] };               // without a resize the encoder reads the rectangle itself
+    if (resized) rc = resize_upload(ctx, 1, &S, bpp, box, &D, &plan, reads);
+    if (rc == JDA_SUCCESS) {
+        const int mw_out = cw / (I.mcus_x ? I.mcus_x : 1), mh_out = ch / (I.mcus_y ? I.mcus_y : 1);
+        int32_t mcu_rect[4] = { reads[0] / mw_out, reads[1] / mh_out, (reads[2] + mw_out - 1) / mw_out, (reads[3] + mh_out - 1) / mh_out };
+        mcu_rect[2] = std::min(mcu_rect[2], I.mcus_x); mcu_rect[3] = std::min(mcu_rect[3], I.mcus_y);
+        const bool all = mcu_rect[0] == 0 && mcu_rect[1] == 0 && mcu_rect[2] == I.mcus_x && mcu_rect[3] == I.mcus_y;
+        jda_batch *b = jda_batch_create_rect(ctx, 1, &dimg, &C, &pixel_type, &options, all ? NULL : mcu_rect, &err);
+        rc = err;
+        if (b) {
+            if (!complete) (void)hipMemsetAsync(dsurf + (size_t)mcu_rect[1] * mh_out * cpitch, 0, (size_t)(mcu_rect[3] - mcu_rect[1]) * mh_out * cpitch, ctx->stream);
+            rc = jda_batch_decode(ctx, b);
+            if (rc == JDA_SUCCESS && resized) rc = resize_launch(ctx, plan);
+            if (rc == JDA_SUCCESS) {
+                // the encoder's stages follow on the same stream; its two looks at the sizes are the only waits
+                const jda_encode_job E = { resized ? 0 : box[0], resized ? 0 : box[1], out_w, out_h, sampling, quality, restart_interval, 0 };
+                void *dfile = dsurf + cbytes + rbytes;
+                int32_t st = JDA_SUCCESS;
+                rc = jda_encode_surfaces(ctx, 1, resized ? &D : &S, bpp, &E, &dfile, &fcap, file_bytes, &st);
+                if (rc == JDA_SUCCESS) rc = st;
+                if (rc == JDA_SUCCESS) {
+                    hipError_t e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);
+                    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+                    if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+                }
+            } else (void)hipStreamSynchronize(ctx->stream);
+            jda_batch_destroy(ctx, b);
+        }
+        if (plan.block) jda_pool_free(ctx, plan.block);
+    }
+    jda_pool_free(ctx, dsurf);
+    jda_dev_image_free(ctx, dimg);
+    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;
     return rc;
 }
 

@@ -157,3 +157,66 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
         if rbase is not None:
             ctx.free(rbase)
     return result
+
+
+def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=True, restart_interval=0):
+    """files (JPEG bytes, all colour or all gray) -> list of JPEG files (bytes), each image -- or crops[k] = (x, y, w, h) of image k, in pixels
+    of its visible size -- resized to size = (H, W) and encoded at `quality`; gray files take the gray sampling whatever `sampling` says.
+    One Pipeline batch, one jda_resize_surfaces launch and one jda_encode_surfaces call; only the files are copied back.  prescale (whole
+    images only, ignored with crops): as decode_to_tensors.  No torch in here.  A file that fails to decode raises JdaError with its status."""
+    files = list(files)
+    size = tuple(int(v) for v in size)
+    if len(size) != 2 or size[0] <= 0 or size[1] <= 0:
+        raise ValueError("size: (H, W), both positive")
+    n = len(files)
+    if n == 0:
+        return []
+    if crops is not None:
+        crops = [tuple(int(v) for v in c) for c in crops]
+        if len(crops) != n or any(len(c) != 4 for c in crops):
+            raise ValueError("crops: one (x, y, w, h) per file")
+    infos = []
+    for f in files:
+        info = B.ImageInfo()
+        rc = ctx.lib.jda_parse(f, len(f), C.byref(info))
+        if rc != 0:
+            raise B.JdaError(rc, "jda_parse")
+        infos.append(info)
+    gray = [i.ncomp == 1 for i in infos]
+    if any(gray) != all(gray):
+        raise ValueError("gray and colour files in one call: one jda_resize_surfaces launch takes one source format")
+    pt = B.GRAY8 if gray[0] else B.RGB8888
+    samp = B.ENCODE_GRAY if gray[0] else B.ENCODE_SAMPLINGS[sampling] if isinstance(sampling, str) else int(sampling)
+    opts = [prescale_option(i, pt, 0, size) if prescale and crops is None else 0 for i in infos]
+    geos = [B.output_geometry(i, pt, o) for i, o in zip(infos, opts)]
+    bpp = geos[0]["bpp"]
+    pitches = [(g["canvas_w"] * bpp + 15) & ~15 for g in geos]
+    offs, total = [], 0
+    for g, p in zip(geos, pitches):
+        offs.append(total)
+        total += (p * g["canvas_h"] + 255) & ~255
+    rpitch = (size[1] * bpp + 15) & ~15
+    rbytes = (rpitch * size[0] + 255) & ~255
+    cap = B.encode_bound(size[1], size[0], samp, restart_interval)
+    base = ctx.malloc(total + rbytes * n + cap * n)
+    try:
+        rbase, fbase = base + total, base + total + rbytes * n
+        pipe = B.Pipeline(ctx, max_images=n, depth=1)
+        try:
+            outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
+            status = pipe.wait(pipe.submit(files, outs, [pt] * n, opts))
+        finally:
+            pipe.close()
+        for k, st in enumerate(status):
+            if st != 0:
+                raise B.JdaError(st, "file %d of the batch" % k)
+        visible = [(base + offs[k], pitches[k], geos[k]["out_w"], geos[k]["out_h"]) for k in range(n)]
+        resized = [(rbase + k * rbytes, rpitch, size[1], size[0]) for k in range(n)]
+        B.resize_surfaces(ctx, visible, bpp, resized, crops)
+        nbytes, st = B.encode_surfaces(ctx, resized, bpp, [(0, 0, size[1], size[0], samp, quality, restart_interval)] * n, [fbase + k * cap for k in range(n)], [cap] * n)
+        if any(st):
+            raise B.JdaError(max(st), "jda_encode_surfaces")
+        # (the files alone come back: nbytes[k] bytes each)
+        return [ctx.to_host(fbase + k * cap, nbytes[k]).tobytes() for k in range(n)]
+    finally:
+        ctx.free(base)
