@@ -6,7 +6,11 @@ the quantisation are written out here; entropy coding and the file are tests/coe
   coefficients(img, sampling, q)      per component (block rows, block columns, 64) zig-zag arrays over the MCU grid, dummy blocks included
   file_bytes(img, sampling, q, ri)    the whole file
 
+and the pictures of the test grid, LONG_JOBS among them: the jobs that take the scan stage past one element a lane.
+
 img: H x W x 3 or 4 (R, G, B[, A]) uint8 for the colour samplings, H x W uint8 for "gray"."""
+import functools
+
 import numpy as np
 
 from jpegdec_amd.synth import _ZIGZAG
@@ -168,7 +172,8 @@ SECOND_TILE_WIDTH = {"gray": 528, "4:4:4": 360, "4:2:2": 272, "4:2:0": 184}
 
 
 def picture(kind, w, h, sampling, seed=0):
-    """'noise' | 'smooth' | 'pixels' (a pixel checkerboard) | 'blocks' (an 8x8-block checkerboard): H x W (gray) or H x W x 4 uint8"""
+    """'noise' | 'smooth' | 'pixels' (a pixel checkerboard) | 'blocks' (an 8x8-block checkerboard) | 'flat' (every sample 200): H x W (gray)
+    or H x W x 4 uint8"""
     yy, xx = np.mgrid[0:h, 0:w]
     rng = np.random.RandomState(seed * 7919 + w * 131 + h)
     if kind == "noise":
@@ -179,6 +184,8 @@ def picture(kind, w, h, sampling, seed=0):
         a = np.repeat((((xx + yy) & 1) * 255)[..., None], 4, -1)
     elif kind == "blocks":
         a = np.repeat(((((xx >> 3) + (yy >> 3)) & 1) * 255)[..., None], 4, -1)
+    elif kind == "flat":
+        a = np.full((h, w, 4), 200)
     else:
         raise ValueError(kind)
     a = a.astype(np.uint8)
@@ -189,3 +196,95 @@ def restart_intervals(w, h, sampling):
     """0, 1, 3, the MCUs of a row, all MCUs, all + 1"""
     cx, cy = coef_jpeg.geometry(w, h, sampling)[:2]
     return sorted({0, 1, 3, cx, cx * cy, cx * cy + 1})
+
+
+# ---- long jobs: a lane of the scan stage sums a run of per = ceil(n / 256) elements -- a job's blocks, then its 64-byte chunks ----------
+SCAN_LANES, CHUNK = 256, 64
+# (kind, w, h, sampling, quality, restart interval, seed) -> what the job is in the list for (long_job_facts: asserted from the twin)
+LONG_JOBS = (
+    (("noise", 264, 240, "gray", 75, 1, 11), {"starts": 4}),           # 990 blocks, per 4, an interval a block
+    (("noise", 264, 240, "gray", 75, 2, 12), {"starts": 2}),
+    (("noise", 264, 240, "gray", 75, 3, 13), {"starts": 2}),
+    (("noise", 256, 128, "4:4:4", 75, 1, 14), {"starts": 2}),          # 1536 blocks, per 6, an interval every 3
+    (("noise", 368, 184, "4:2:2", 75, 1, 15), {"starts": 2}),          # 2116 blocks, per 9, every 4
+    (("noise", 352, 352, "4:2:0", 75, 1, 16), {"starts": 2}),          # 2904 blocks, per 12, every 6
+    (("noise", 160, 160, "4:4:4", 100, 0, 17), {"chunk_per": 3}),      # 1200 blocks, per 5; a file of about 105 KB: the chunks' scan
+    (("flat", 2056, 8, "gray", 1, 0, 0), {"in_a_dword": 5, "shared": ((63, 64), (255, 256))}),      # 257 blocks of 6 bits behind the first
+    (("flat", 2056, 8, "gray", 75, 0, 0), {"in_a_dword": 5, "shared": ((63, 64), (255, 256))}),
+    (("flat", 264, 240, "gray", 1, 0, 0), {"in_a_dword": 5, "shared": ((63, 64), (255, 256))}),     # 990
+    (("flat", 264, 240, "gray", 75, 0, 0), {"in_a_dword": 5, "shared": ((63, 64), (255, 256))}),
+)
+
+
+def long_job_case(job):
+    kind, w, h, sampling, q, ri, seed = job
+    return picture(kind, w, h, sampling, seed), sampling, q, ri
+
+
+@functools.lru_cache(maxsize=None)
+def long_job_twin(job):
+    """(the twin's file, its layout)"""
+    return file_bytes(*long_job_case(job), return_layout=True)
+
+
+def long_job_facts(job):
+    """From the TWIN's layout alone: starts = the most interval starts in one lane's run of blocks; chunk_per = the run of a lane of the
+    chunks' scan (the header's chunks left out: they only add); in_a_dword = the most blocks with a bit in one dword of the unstuffed scan;
+    shared = the pairs of neighbouring blocks (a, a + 1), a + 1 a multiple of 64, that have bits in one dword."""
+    kind, w, h, sampling, q, ri, seed = job
+    jpeg, lay = long_job_twin(job)
+    cx, cy, shapes, (hs, vs) = coef_jpeg.geometry(w, h, sampling)
+    n = len(lay["blocks"])
+    bpm = n // (cx * cy)
+    per, period = -(-n // SCAN_LANES), ri * bpm
+    first = np.zeros(n, dtype=np.int64)
+    first[0] = 1
+    if period:
+        first[::period] = 1
+    starts = max(int(first[i:i + per].sum()) for i in range(0, n, per))
+    assert lay["scan_bits"] % 8 == 0
+    chunk_per = -(-(-(-(lay["scan_bits"] // 8) // CHUNK)) // SCAN_LANES)
+    p0 = np.asarray([blk[3][0] for blk in lay["blocks"]], dtype=np.int64)
+    p1 = np.asarray([blk[4][-1][0] + blk[4][-1][1] + max(blk[4][-1][2], 0) if blk[4] else blk[3][0] + blk[3][1] + blk[3][2] for blk in lay["blocks"]], dtype=np.int64)
+    d0, d1 = p0 >> 5, (p1 - 1) >> 5                                    # a block's first and last dword
+    count = np.zeros(int(d1[-1]) + 2, dtype=np.int64)
+    np.add.at(count, d0, 1)
+    np.add.at(count, d1 + 1, -1)
+    shared = tuple((a, a + 1) for a in range(63, n - 1, 64) if d1[a] == d0[a + 1])
+    return dict(blocks=n, per=per, period=period, starts=starts, chunk_per=chunk_per, in_a_dword=int(np.cumsum(count).max()), shared=shared)
+
+
+def long_job_holds(job, why):
+    """whether the job, by its twin, is what LONG_JOBS lists it for"""
+    f = long_job_facts(job)
+    return all(set(v) <= set(f[k]) if k == "shared" else f[k] >= v for k, v in why.items())
+
+
+def long_batch(sampling_class):
+    """'gray' | 'colour' -> (cases, per case its LONG_JOBS entry or None): the LONG_JOBS of one pixel size with a 1 x 1 job in front of,
+    between and behind them -- a job's blocks and chunks begin in the middle of a wavefront, and the bisections over the jobs run over
+    large block0 / chunk0"""
+    jobs = [(job, why) for job, why in LONG_JOBS if (job[3] == "gray") == (sampling_class == "gray")]
+    cases, whys = [], []
+    for k, (job, why) in enumerate(jobs):
+        cases += [(picture("noise", 1, 1, job[3], seed=k), job[3], 75, k % 2), long_job_case(job)]
+        whys += [None, (job, why)]
+    cases.append((picture("noise", 1, 1, jobs[-1][0][3], seed=99), jobs[-1][0][3], 75, 0))
+    whys.append(None)
+    return cases, whys
+
+
+# ---- zero runs of 16 and more: a ZRL symbol for every 16 zeros in front of a coefficient ------------------------------------------------------
+ZRL_RUNS = (15, 16, 31, 32, 47, 48, 62)                                # the zeros in front of a block's only AC coefficient
+ZRL_QUALITY = 20
+
+
+def zrl_picture(amplitude=100):
+    """gray, a block for every run of ZRL_RUNS: 128 + amplitude x the DCT basis function at zig-zag position run + 1 -- at ZRL_QUALITY the
+    only AC coefficient the twin keeps (the test asserts it from the twin's symbols)"""
+    yy, xx = np.mgrid[0:8, 0:8]
+    blocks = []
+    for run in ZRL_RUNS:
+        v, u = divmod(int(_ZZ[run + 1]), 8)
+        blocks.append(128 + amplitude * np.cos((2 * xx + 1) * u * np.pi / 16) * np.cos((2 * yy + 1) * v * np.pi / 16))
+    return np.ascontiguousarray(np.clip(np.rint(np.concatenate(blocks, axis=1)), 0, 255).astype(np.uint8))

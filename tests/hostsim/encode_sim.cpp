@@ -8,8 +8,9 @@
 // is poisoned and a byte of it is read only after a lane wrote it; the unstuffed scans are zeros and change only by atomic OR; the scan's
 // LDS is poisoned before every workgroup and read only where this workgroup wrote it; no byte of a file is written twice, none behind the
 // capacity, and in the end every byte of a file that fits once -- of one that does not, none.
-// encodesim_coefs runs the stages behind the first over coefficients the caller chose (what no picture gives); encodesim_check runs the
-// argument checks alone; encodesim_divide tries the reciprocal of every divisor on every numerator.
+// encodesim_coefs runs the stages behind the first over coefficients the caller chose (what no picture gives); encodesim_scan runs the scan
+// stage alone over lengths the caller chose, the second half's lanes in reverse order; encodesim_check runs the argument checks alone;
+// encodesim_divide tries the reciprocal of every divisor on every numerator.
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -261,6 +262,34 @@ extern "C" int encodesim_coefs(int w, int h, int sampling, int quality, int ri, 
     const int e = finish(R, dst_bytes, status, code, end, NULL, NULL, 0);
     if (e) return e;
     if (info) { info[0] = R.P.n_blocks; info[1] = R.P.n_int; info[2] = R.P.n_chunks; info[3] = R.P.u_total; }
+    return 0;
+}
+
+// the scan stage alone over n lengths of the caller's (bytes_mode: the chunks' 0xFF counts, all bits of a value and no interval; else the
+// blocks' code lengths, the low 16 bits, an interval every `period` elements): a workgroup's first half lane 0 .. 255 into poisoned LDS,
+// its second half lane 255 DOWN TO 0 -- no lane's second half may need another's.  end: n, istart: an interval (unused in bytes_mode),
+// total: the unstuffed bytes (bytes_mode: the sum), as jda_en_scan_job takes it from the one lane that owns the last element.
+extern "C" int encodesim_scan(const uint32_t *vals, uint32_t n, int bytes_mode, uint32_t period, uint64_t *end, uint64_t *istart, uint64_t *total)
+{
+    SimIO io;
+    io.cur = NULL; io.bpp = 0; io.jobs = NULL; io.n_jobs = 0; io.err = 0;
+    if (!n || (bytes_mode && period)) return -60;                              // (-6x: this entry's own)
+    const uint32_t mask = bytes_mode ? 0xffffffffu : 0xffffu, n_int = period ? (n + period - 1u) / period : 1u;
+    io.add((void *)vals, (size_t)n * 4, false, false);
+    io.add(end, (size_t)n * 8, true, true);
+    if (!bytes_mode) io.add(istart, (size_t)n_int * 8, true, true);
+    io.lds.assign(3 * JDA_EN_THREADS, 0xEEEEEEEEEEEEEEEEull); io.lds_set.assign(3 * JDA_EN_THREADS, 0);
+    for (uint32_t tid = 0; tid < JDA_EN_THREADS; tid++) jda_en_scan_local(vals, mask, 0u, n, period, tid, io);
+    uint32_t owners = 0;
+    for (uint32_t tid = JDA_EN_THREADS; tid-- > 0u;) {
+        const uint64_t p = jda_en_scan_write(vals, mask, 0u, n, period, end, bytes_mode ? (uint64_t *)0 : istart, tid, io);
+        if (p == ~(uint64_t)0) continue;
+        owners++;
+        *total = bytes_mode ? p : jda_en_ceil8(p) >> 3;
+    }
+    if (io.err) return io.err;
+    if (owners != 1u) return -61;
+    for (const Alloc &a : io.allocs) for (uint8_t s : a.init) if (!s) return -62;      // an element or an interval that no lane wrote
     return 0;
 }
 

@@ -5,10 +5,15 @@
   Pillow opens the twin's files (skipped where Pillow is absent);
 * the six stages, lane by lane through the kernels' own code over the host plan's records (tests/hostsim/encode_sim.cpp over jda_en_* of
   jda_device_core.h), against the twin: coefficients, code lengths, bit positions and the file, for the grid, for one width per sampling
-  that makes a row of more than 64 blocks, and for the edges of the design, each asserted FROM THE TWIN to be in the input;
+  that makes a row of more than 64 blocks, for the edges of the design and for zero runs of 15 .. 62, each asserted FROM THE TWIN to be in
+  the input;
+* the scan stage alone over lengths of the test's own against positions counted one after the other: runs of a lane with no, one, two and
+  more interval starts, empty runs, positions past 2^32; and the long jobs of encode_util.LONG_JOBS through all six stages -- several
+  interval starts in a lane's run, three and more chunks a lane, dwords that the blocks of two wavefronts and workgroups share;
 * the reciprocal division, every divisor against every numerator; the header; every refusal; the capacity rule; jda_encode_bound;
 * the plan, the header builder and the simulator once more as a program under AddressSanitizer + UBSan."""
 import ctypes as C
+import functools
 import io
 import os
 import subprocess
@@ -42,6 +47,7 @@ def sim(built_checkers):
     lib.encodesim_bound.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int64)]
     lib.encodesim_header.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_int]
     lib.encodesim_divide.restype = C.c_int64
+    lib.encodesim_scan.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     return lib
 
 
@@ -94,8 +100,18 @@ def run_sim(sim, cases, caps=None):
     return files, list(nbytes), list(status), per
 
 
+_TWINS = {}
+
+
 def twin_layout(img, sampling, q, ri):
-    """the twin's file, and per block in the order of the scan (coefficients, first bit, code bits) in the unstuffed scan"""
+    """the twin's file, and per block in the order of the scan (coefficients, first bit, code bits) in the unstuffed scan (computed once a case)"""
+    key = (img.shape, img.tobytes(), sampling, q, ri)
+    if key not in _TWINS:
+        _TWINS[key] = _twin_layout(img, sampling, q, ri)
+    return _TWINS[key]
+
+
+def _twin_layout(img, sampling, q, ri):
     coefs = E.coefficients(img, sampling, q)
     jpeg, lay = E.file_bytes(img, sampling, q, ri, return_layout=True)
     rows = []
@@ -200,6 +216,150 @@ def test_lanes_second_tile_in_an_mcu_row(sim, sampling):
         check_case(f, got, *case)
 
 
+# ---- the scan stage alone, over lengths of the test's own -------------------------------------------------------------------------------------
+LANES = 256
+
+
+def scan_serial(vals, mask, period, intervals):
+    """the positions, one element after the other: (end, istart in bytes, the position behind the last element)"""
+    p, end, istart = 0, [], []
+    for i, v in enumerate(vals.tolist()):
+        if intervals and (i == 0 or (period and i % period == 0)):
+            p = (p + 7) & ~7
+            istart.append(p // 8)
+        p += v & mask
+        end.append(p)
+    return np.asarray(end, dtype=np.uint64), np.asarray(istart, dtype=np.uint64), p
+
+
+def scan_numpy(vals, mask, period, intervals):
+    """the same without a loop: an interval starts on a byte, so ceil8(start + its bits) = start + ceil8(its bits)"""
+    ln = (vals & np.uint32(mask)).astype(np.uint64)
+    n = len(ln)
+    if not intervals:
+        end = np.cumsum(ln, dtype=np.uint64)
+        return end, np.zeros(0, dtype=np.uint64), int(end[-1])
+    k = period or n
+    pad = np.concatenate([ln, np.zeros(-n % k, dtype=np.uint64)]).reshape(-1, k)
+    within = np.cumsum(pad, axis=1, dtype=np.uint64)
+    start = np.concatenate([[0], np.cumsum((within[:-1, -1] + np.uint64(7)) & ~np.uint64(7), dtype=np.uint64)]).astype(np.uint64)
+    end = (within + start[:, None]).reshape(-1)[:n]
+    return end, start >> np.uint64(3), int(end[-1])
+
+
+def run_scan(sim, vals, bytes_mode, period):
+    n = len(vals)
+    end = np.zeros(n, dtype=np.uint64)
+    istart = np.zeros(1 if bytes_mode else (-(-n // period) if period else 1), dtype=np.uint64)
+    total = C.c_uint64(~0)
+    rc = sim.encodesim_scan(vals.ctypes.data, n, int(bytes_mode), period, end.ctypes.data, istart.ctypes.data, C.byref(total))
+    assert rc == 0, rc
+    return end, (istart[:0] if bytes_mode else istart), total.value
+
+
+def runs_of(n, period):
+    """what the lanes' runs of per = ceil(n / 256) elements hold, from n and the period alone: the interval starts in every run that has an
+    element, whether a run behind the first begins on a start, whether empty runs follow a run that is not full"""
+    per = -(-n // LANES)
+    first = np.zeros(n, dtype=np.int64)
+    first[0] = 1
+    if period:
+        first[::period] = 1
+    bounds = [(min(t * per, n), min(t * per + per, n)) for t in range(LANES)]
+    counts = {int(first[a:b].sum()) for a, b in bounds if a < b}
+    on_start = any(0 < a < b and first[a] for a, b in bounds)
+    ragged = any(0 < b - a < per and bounds[t + 1][0] == bounds[t + 1][1] for t, (a, b) in enumerate(bounds[:-1]))
+    return per, counts, on_start, ragged
+
+
+def scan_lengths(kind, n, rng):
+    if kind == "random":                      # 2 .. 1665 bits, and garbage above bit 15 that the mask of the blocks' scan takes off
+        return (rng.randint(2, 1666, size=n).astype(np.uint32) | (rng.randint(0, 1 << 16, size=n).astype(np.uint32) << np.uint32(16))).astype(np.uint32)
+    if kind == "bytes":                       # every element ends on a byte
+        return (8 * rng.randint(1, 209, size=n)).astype(np.uint32)
+    if kind == "odd":                         # every element one bit past a byte
+        return (8 * rng.randint(0, 208, size=n) + 1).astype(np.uint32)
+    return np.full(n, 1665, dtype=np.uint32)  # JDA_EN_BLOCK_BITS, the longest
+
+
+SCAN_SIZES = (1, 2, 255, 256, 257, 511, 512, 513, 769, 1000, 4097)
+
+
+def test_scan_runs_with_many_interval_starts(sim):
+    """jda_en_scan_local / jda_en_scan_write over lengths of the test's own (encodesim_scan; the second half's lanes in reverse order), against
+    positions counted one element after the other.  per = ceil(n / 256) elements a lane, an interval every `period`: the grid holds -- asserted
+    from n and the period alone -- runs with 0, 1, 2 and more interval starts, a run that begins on a start, and empty runs behind a partly
+    filled one; the blocks' scan takes only the low 16 bits of a value, the chunks' scan all of them."""
+    rng = np.random.RandomState(5)
+    seen, begins, ragged = set(), False, False
+    for n in SCAN_SIZES:
+        per = -(-n // LANES)
+        for period in sorted({0, 1, 2, 3, per - 1, per, per + 1, 2 * per + 1, n - 1, n, n + 1} - {-1}):
+            if period < 0:
+                continue
+            _, counts, b, r = runs_of(n, period)
+            seen |= {min(c, 3) for c in counts}
+            begins, ragged = begins or b, ragged or r
+            for kind in ("random", "bytes", "odd", "longest"):
+                vals = scan_lengths(kind, n, rng)
+                want = scan_serial(vals, 0xFFFF, period, True)
+                fast = scan_numpy(vals, 0xFFFF, period, True)
+                assert all(np.array_equal(a, b) for a, b in zip(want[:2], fast[:2])) and want[2] == fast[2]
+                end, istart, total = run_scan(sim, vals, False, period)
+                where = (n, period, kind)
+                assert np.array_equal(istart, want[1]), where
+                assert np.array_equal(end, want[0]), where
+                assert total == (want[2] + 7) // 8, where
+        vals = rng.randint(0, 65, size=n).astype(np.uint32)                      # the 0xFF bytes of 64-byte chunks
+        vals[rng.randint(0, n)] |= np.uint32(1 << 20)                            # (no mask here: a high bit counts)
+        want = scan_serial(vals, 0xFFFFFFFF, 0, False)
+        end, istart, total = run_scan(sim, vals, True, 0)
+        assert np.array_equal(end, want[0]) and total == want[2] and np.array_equal(end, scan_numpy(vals, 0xFFFFFFFF, 0, False)[0]), n
+    assert seen == {0, 1, 2, 3} and begins and ragged
+    assert runs_of(257, 0)[3] and -(-257 // LANES) == 2                          # lane 128 holds one element, the lanes behind it none
+
+
+def test_scan_positions_past_32_bits(sim):
+    """about 2.6 M blocks of the longest code, an interval every 7: the positions pass 2^32 bits (the reference: numpy in 64 bits)"""
+    n = 2_600_000
+    vals = np.full(n, 1665, dtype=np.uint32)
+    want_end, want_istart, last = scan_numpy(vals, 0xFFFF, 7, True)
+    assert last > 1 << 32 and int(want_end[n // 2]) < 1 << 32 and min(runs_of(n, 7)[1]) > 1000
+    end, istart, total = run_scan(sim, vals, False, 7)
+    assert np.array_equal(istart, want_istart) and np.array_equal(end, want_end) and total == (last + 7) // 8
+
+
+# ---- long jobs: runs of many blocks and chunks a lane, through all six stages ----------------------------------------------------------------
+def test_long_jobs_are_what_they_are_listed_for():
+    """from the twin alone: two or more interval starts in a lane's run, three or more chunks a lane of the chunks' scan, dwords of the
+    unstuffed scan with bits of five blocks and more, and of the blocks either side of a wavefront's (63 | 64) and a workgroup's (255 | 256) edge"""
+    reached = set()
+    for job, why in E.LONG_JOBS:
+        f = E.long_job_facts(job)
+        assert E.long_job_holds(job, why), (job, f)
+        assert f["per"] >= 2
+        reached |= set(why)
+        if "starts" in why:
+            assert f["period"] and f["starts"] >= 2 and f["per"] > f["period"]
+        if "chunk_per" in why:
+            assert f["chunk_per"] >= 3 and len(E.long_job_twin(job)[0]) > 3 * LANES * 64 + 1024      # the file's size alone says so
+        if "shared" in why:
+            assert {(63, 64), (255, 256)} <= set(f["shared"]) and f["in_a_dword"] >= 5
+    assert reached == {"starts", "chunk_per", "in_a_dword", "shared"}
+    assert {job[3] for job, why in E.LONG_JOBS if "starts" in why} == set(E.SAMPLINGS)
+
+
+@pytest.mark.parametrize("sampling_class", ("gray", "colour"))
+def test_lanes_are_the_twin_over_long_jobs(sim, sampling_class):
+    cases, whys = E.long_batch(sampling_class)
+    files, nbytes, status, per = run_sim(sim, cases)                                                 # one call
+    for f, st, got, case, why in zip(files, status, per, cases, whys):
+        assert st == 0
+        jpeg, rows, lay = check_case(f, got, *case)
+        if why:
+            assert jpeg == E.long_job_twin(why[0])[0]
+
+
 def unstuffed(jpeg):
     """the entropy-coded bytes without stuffing and markers, and every interval's first byte in them"""
     b = body(jpeg)
@@ -238,31 +398,106 @@ def edges_of(jpeg, rows, lay):
         s, e = rows[k][1], ends[k]
         if s % 32 and e % 32 and s // 32 != (e - 1) // 32 and ends[k - 1] == s and rows[k + 1][1] == e:
             found.add("dwords shared with both neighbours")
+    if any(b % 64 == 0 for b in starts[1:]):            # (behind the first interval: the ones that have a marker in front)
+        found.add("interval starts on a chunk's first byte")
+    if any(b % 64 == 63 for b in starts[1:]):
+        found.add("interval starts on a chunk's last byte")
+    if len(u) % 64 == 0:
+        found.add("unstuffed size a multiple of 64")
+    elif len(u) % 16 == 0:
+        found.add("unstuffed size a multiple of 16 but not of 64")
     return found
 
 
-ALL_EDGES = {"0xFF first in a chunk", "0xFF last in a chunk", "interval without pad", "0xFF pad byte", "dwords shared with both neighbours"}
+ALL_EDGES = {"0xFF first in a chunk", "0xFF last in a chunk", "interval without pad", "0xFF pad byte", "dwords shared with both neighbours",
+             "interval starts on a chunk's first byte", "interval starts on a chunk's last byte", "unstuffed size a multiple of 64",
+             "unstuffed size a multiple of 16 but not of 64"}
+
+
+def edge_candidates():
+    """the noise pictures of every sampling first, then tiny gray ones with an interval a block (a few blocks: cheap, and every block's end
+    is an interval's)"""
+    for seed in range(40):
+        sampling = E.SAMPLINGS[seed % 4]
+        yield E.picture("noise", 64 + seed, 33, sampling, seed=seed), sampling, 100 if seed % 2 else 92, (1, 2, 7)[seed % 3]
+    for seed in range(40, 1000):
+        yield E.picture("noise", 24 + 8 * (seed % 4), 8, "gray", seed=seed), "gray", 100 if seed % 2 else 92, 1
+
+
+@functools.lru_cache(maxsize=None)
+def edge_cases():
+    """((case, the edges it is there for), ..): inputs picked by what the TWIN's file holds until every edge of ALL_EDGES is covered.  Bounded
+    and the same every time; the bounds were tried on the twin alone."""
+    missing, used = set(ALL_EDGES), []
+    for case in edge_candidates():
+        hit = edges_of(*twin_layout(*case)) & missing
+        if hit:
+            used.append((case, frozenset(hit)))
+            missing -= hit
+        if not missing:
+            break
+    assert not missing, missing
+    return tuple(used)
 
 
 def test_lanes_edges_of_the_design(sim):
     """Inputs picked by what the TWIN's file holds -- an 0xFF as the first and as the last byte of a 64-byte stuffing chunk, a pad byte that
     is 0xFF, an interval that ends on a byte without pad bits, a block whose code shares a dword with the block before AND one with the
-    block behind -- until every edge is covered; each input then goes through the lanes."""
-    missing, used = set(ALL_EDGES), []
-    for seed in range(40):
-        sampling = E.SAMPLINGS[seed % 4]
-        case = (E.picture("noise", 64 + seed, 33, sampling, seed=seed), sampling, 100 if seed % 2 else 92, (1, 2, 7)[seed % 3])
-        hit = edges_of(*twin_layout(*case)) & missing
-        if hit:
-            used.append((case, hit))
-            missing -= hit
-        if not missing:
-            break
-    assert not missing, missing
+    block behind, an interval (behind the first) whose first byte is a chunk's first and one whose first byte is a chunk's last, an unstuffed
+    scan of whole chunks (EOI behind a full last chunk) and one of whole 16-byte loads that is not -- until every edge is covered; each input
+    then goes through the lanes."""
+    used = edge_cases()
+    assert set().union(*[hit for case, hit in used]) == ALL_EDGES
     for case, hit in used:
         files, nbytes, status, per = run_sim(sim, [case])
         jpeg, rows, lay = check_case(files[0], per[0], *case)
         assert hit <= edges_of(jpeg, rows, lay)
+
+
+def zrl_symbols(lay):
+    """per block of the twin's layout: (ZRL symbols, whether an EOB closes it)"""
+    return [(sum(1 for _, ln, m in syms if m == 0), any(m == -1 for _, ln, m in syms)) for c, by, bx, dc, syms in lay["blocks"]]
+
+
+ZRL_WANT = [(0, True), (1, True), (1, True), (2, True), (2, True), (3, True), (3, False)]
+
+
+def test_lanes_zero_runs_from_a_picture(sim):
+    """a block for every zero run of 15, 16, 31, 32, 47, 48 and 62 in front of its only AC coefficient: 0, 1, 1, 2, 2, 3, 3 ZRL symbols, the
+    last block's coefficient at position 63 and so without EOB -- both the length the blocks stage counts and the code the emit stage writes"""
+    img = E.zrl_picture()
+    case = (img, "gray", E.ZRL_QUALITY, 0)
+    jpeg, rows, lay = twin_layout(*case)
+    for row, run in zip(rows, E.ZRL_RUNS):
+        assert np.flatnonzero(row[0][1:]).tolist() == [run]
+    assert zrl_symbols(lay) == ZRL_WANT
+    files, nbytes, status, per = run_sim(sim, [case])
+    check_case(files[0], per[0], *case)
+
+
+def zrl_coefficients():
+    """(w, h, coefficients): the same runs from chosen coefficients, the values of both signs and of categories 3 .. 9"""
+    w, h = 8 * len(E.ZRL_RUNS), 8
+    coefs = coef_jpeg.zero_coefs(w, h, "gray")
+    for b, run in enumerate(E.ZRL_RUNS):
+        coefs[0][0, b, 0] = 5 * b - 9
+        coefs[0][0, b, run + 1] = (-1) ** b * ((1 << (b + 3)) - 1)
+    return w, h, coefs
+
+
+def test_lanes_zero_runs_from_coefficients(sim):
+    w, h, coefs = zrl_coefficients()
+    n = len(E.ZRL_RUNS)
+    want, lay = coef_jpeg.write_jpeg(w, h, "gray", coefs, E.quant_tables(50, "gray"), pad_to=0, return_layout=True)
+    assert zrl_symbols(lay) == ZRL_WANT
+    flat = np.ascontiguousarray(coefs[0][0].astype(np.int16))
+    cap = bound(sim, w, h, "gray", 0)
+    dst = np.full(cap, GUARD, dtype=np.uint8)
+    nbytes, status = C.c_int64(), C.c_int32()
+    code, end = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+    assert sim.encodesim_coefs(w, h, 0, 50, 0, flat.ctypes.data, dst.ctypes.data, cap, C.byref(nbytes), C.byref(status), code.ctypes.data, end.ctypes.data, None) == 0
+    assert status.value == 0 and dst[:nbytes.value].tobytes() == want and np.all(dst[nbytes.value:] == GUARD)
+    assert np.array_equal(end.astype(np.int64) - (code & 0xFFFF), [blk[3][0] for blk in lay["blocks"]])
 
 
 def test_lanes_longest_code_from_coefficients(sim):

@@ -2,7 +2,9 @@
 whole grid, ONE call per (sampling, restart interval), the jobs as rectangles at unaligned places inside larger guard-filled surfaces, the
 files back to back in one guard-filled allocation; (b) fitting and too-small capacities in one call; (c) the product's own decode of every
 file; (d) jda_transcode_to_host against the twin over the oracle's canvas, cut and resized by tests/resize_util.py; (e) thumbnails() over a
-list of mixed sizes and samplings; (f) the refusals, which launch nothing; (g) every encode kernel in the launch counts.  All bit-exact."""
+list of mixed sizes and samplings; (f) the refusals, which launch nothing; (g) every encode kernel in the launch counts; (h) the long jobs
+of tests/encode_util.LONG_JOBS -- runs of many blocks and chunks a lane of the scan stage, several interval starts in a run, dwords of the
+unstuffed scan that wavefronts and workgroups share -- and the inputs of the named edges of tests/test_encode_cpu.py.  All bit-exact."""
 import functools
 
 import numpy as np
@@ -13,6 +15,7 @@ from tests import coef_jpeg
 from tests import encode_util as E
 from tests import resize_util as R
 from tests.cases import jpeg_for
+from tests.test_encode_cpu import ALL_EDGES, ZRL_WANT, edge_cases, twin_layout, zrl_symbols
 from tests.test_gpu_resize import visible_pixels
 
 pytestmark = pytest.mark.gpu
@@ -127,6 +130,45 @@ def test_round_trip_through_the_products_decode(sampling, gpu_ctx, oracle):
         orc, want, err = oracle.decode_canvas(E.file_bytes(*case), pt, 0)
         rc, got, g = J.decode_to_host(gpu_ctx, f, pt, 0)
         assert orc == 1 and rc == 0 and np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("sampling_class", ("gray", "colour"))
+def test_long_jobs_one_call(sampling_class, gpu_ctx, oracle):
+    """E.LONG_JOBS of one pixel size with 1 x 1 jobs between them in ONE call: what each is listed for is asserted from the twin; the
+    files are the twin's; the first long file of every sampling comes back through the product's decode as the oracle decodes the twin's"""
+    cases, whys = E.long_batch(sampling_class)
+    want = [E.long_job_twin(why[0])[0] if why else E.file_bytes(*case) for case, why in zip(cases, whys)]
+    for why in whys:
+        assert why is None or E.long_job_holds(*why), why
+    reached = set().union(*[set(why[1]) for why in whys if why])
+    assert reached == ({"starts", "in_a_dword", "shared"} if sampling_class == "gray" else {"starts", "chunk_per"})
+    files, nbytes, status = encode_batch(gpu_ctx, cases, caps=[len(f) + 5 for f in want])
+    assert status == [0] * len(cases)
+    decoded = set()
+    for f, wf, case, why in zip(files, want, cases, whys):
+        assert f == wf, why or case[1:]
+        if why and case[1] not in decoded:
+            decoded.add(case[1])
+            pt = J.GRAY8 if case[1] == "gray" else J.RGB8888
+            orc, px, err = oracle.decode_canvas(wf, pt, 0)
+            rc, got, g = J.decode_to_host(gpu_ctx, f, pt, 0)
+            assert orc == 1 and rc == 0 and np.array_equal(got, px), why
+    assert decoded == ({"gray"} if sampling_class == "gray" else set(E.SAMPLINGS) - {"gray"})
+
+
+def test_named_edges_and_zero_runs(gpu_ctx):
+    """the inputs tests/test_encode_cpu.py picks by what the twin's file holds (every edge of ALL_EDGES: 0xFF bytes, interval starts and the
+    scan's end against the 64-byte chunks, pad bits, shared dwords) and the picture of zero runs of 15 .. 62: one call a pixel size"""
+    used = edge_cases()
+    assert set().union(*[hit for case, hit in used]) == ALL_EDGES
+    zrl = (E.zrl_picture(), "gray", E.ZRL_QUALITY, 0)
+    assert zrl_symbols(twin_layout(*zrl)[2]) == ZRL_WANT
+    cases = [case for case, hit in used] + [zrl]
+    for gray in (True, False):
+        batch = [c for c in cases if (c[1] == "gray") == gray]
+        want = [twin_layout(*c)[0] for c in batch]
+        files, nbytes, status = encode_batch(gpu_ctx, batch, caps=[len(f) + 5 for f in want])
+        assert status == [0] * len(batch) and files == want
 
 
 @pytest.mark.parametrize("sampling", E.SAMPLINGS)
