@@ -437,6 +437,18 @@ typedef struct jda_encode_job { int32_t x, y, w, h, sampling, quality, restart_i
 int jda_encode_bound(int32_t w, int32_t h, int32_t sampling, int32_t restart_interval, int64_t *bytes);
 int jda_encode_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,
                         void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status);
+/* jda_encode_surfaces with a word of flags per job: job_flags = NULL (every job as above) or n words.  JDA_ENCODE_OPTIMIZE: the file gets
+ * Huffman tables of its own, made from its symbol counts as libjpeg's jpeg_gen_optimal_table makes them -- Pillow's optimize=True, behind
+ * the SOS header byte for byte and the same four DHT segments (DC 0, AC 0, and for colour DC 1, AC 1, one segment per table in that order).
+ * The symbols are counted and the code lengths summed on the GPU; the tables are made on the host from 2,176 bytes of counts per optimised
+ * job, which costs the call one more wait and two more launches (nine whatever n is; a call without an optimised job is jda_encode_surfaces,
+ * launch for launch).  jda_encode_bound holds unchanged: the header only shrinks and no code passes 16 bits.  Any other flag bit:
+ * JDA_INVALID_PARAMETER before anything is launched.  JDA_UNSUPPORTED_FEATURE: an optimised job of more than 15,625,000 blocks (a symbol
+ * count could pass libjpeg's limit of 10^9), or -- after the first launches -- counts for which libjpeg itself gives up (a code of more than
+ * 32 bits before the lengths are limited; no picture has been seen to give them). */
+enum { JDA_ENCODE_OPTIMIZE = 1 };
+int jda_encode_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs, const uint32_t *job_flags,
+                           void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status);
 
 /* PCI bus id ("0000:8e:00.0") of the context's GPU, for NUMA placement of the host threads that feed it; buf >= 16 bytes */
 int jda_device_pci_bus_id(jda_ctx *ctx, char *buf, int32_t len);
@@ -495,6 +507,10 @@ int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, i
  * JDA_DECODE_ERROR the MCUs from the bad one on are zeros before the resize and the file is still delivered. */
 int jda_transcode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
                           int32_t sampling, int32_t quality, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes);
+/* the same with the encoder's flags (JDA_ENCODE_OPTIMIZE, as in jda_encode_surfaces_ex; 0: jda_transcode_to_host) */
+int jda_transcode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
+                             int32_t sampling, int32_t quality, int32_t restart_interval, uint32_t encode_flags, void *host_file, int64_t capacity,
+                             int64_t *file_bytes);
 /* jda_decode_to_host_ex followed by the orientation: prepare, upload, decode to a device canvas, orient its visible rectangle into a second
  * device surface (jda_orient_surfaces) and copy back only the W' * bpp x H' bytes of jda_oriented_geometry: row r at host_pixels + r * pitch_bytes,
  * pitch_bytes >= W' * bpp (any value), rows >= H'.  orientation < 0: the file's; 0..8 as given (0, 1: the visible rectangle as it is); above

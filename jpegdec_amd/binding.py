@@ -14,6 +14,7 @@ PACK_HWC, PACK_CHW, PACK_BGR = 0, 1, 2      # pack_surfaces / decode_packed_to_h
 PACK_U8, PACK_F16, PACK_F32 = 0, 1, 2       # .. element types
 PACK_DTYPES = {PACK_U8: np.uint8, PACK_F16: np.float16, PACK_F32: np.float32}
 ENCODE_GRAY, ENCODE_444, ENCODE_422, ENCODE_420 = 0, 1, 2, 3           # jda_encode_job.sampling
+ENCODE_OPTIMIZE = 1                                                    # a job's word of jda_encode_surfaces_ex: Huffman tables of the file's own
 ENCODE_SAMPLINGS = {"gray": ENCODE_GRAY, "4:4:4": ENCODE_444, "4:2:2": ENCODE_422, "4:2:0": ENCODE_420}
 RESIZE_MAX_KSIZE, RESIZE_MAX_TABLE_BYTES = 161, 64 << 20      # resize_surfaces: taps per output coordinate (a downscale of 80 : 1), tap tables of one call
 AUTO_ROTATE = 1      # the class's decode() applies the EXIF orientation; the C-ABI takes it as an argument (decode_oriented_to_host, orient_surfaces)
@@ -144,7 +145,11 @@ _PROTOTYPES = [
     ("jda_resize_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output)]),
     ("jda_transcode_to_host", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
                                         C.c_int64, C.POINTER(C.c_int64)]),
+    ("jda_transcode_to_host_ex", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                                           _P, C.c_int64, C.POINTER(C.c_int64)]),
     ("jda_encode_bound", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("jda_encode_surfaces_ex", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(EncodeJob), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("jda_encode_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(EncodeJob), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("jda_decode_to_host_resized", C.c_int, [_P, C.c_char_p] + [C.c_int32] * 3 + [C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -921,23 +926,31 @@ def encode_bound(w, h, sampling, restart_interval=0) -> int:
     return b.value
 
 
-def encode_surfaces(ctx: Context, src, bytes_per_pixel, jobs, dst, capacities):
-    """jda_encode_surfaces: src = list of (device_ptr, pitch_bytes, width_px, rows) of RGB8888 (4) or GRAY8 (1) surfaces; jobs = list of
+def encode_surfaces(ctx: Context, src, bytes_per_pixel, jobs, dst, capacities, flags=None):
+    """jda_encode_surfaces[_ex]: src = list of (device_ptr, pitch_bytes, width_px, rows) of RGB8888 (4) or GRAY8 (1) surfaces; jobs = list of
     (x, y, w, h, sampling, quality, restart_interval); dst = device pointers, capacities = their bytes.  -> (file sizes, statuses): libjpeg's
-    baseline file for every rectangle, written where it lies in HBM; ERROR_MEMORY and the size it needs for a file that does not fit."""
+    baseline file for every rectangle, written where it lies in HBM; ERROR_MEMORY and the size it needs for a file that does not fit.
+    flags: None, or a word per job (ENCODE_OPTIMIZE: Pillow's optimize=True for that file) -- then the call is jda_encode_surfaces_ex."""
     n = len(src)
     s = (Output * max(n, 1))(*[Output(*o) for o in src])
     j = (EncodeJob * max(n, 1))(*[EncodeJob(q[0], q[1], q[2], q[3], _sampling(q[4]), q[5], q[6] if len(q) > 6 else 0, 0) for q in jobs])
     d = (C.c_void_p * max(n, 1))(*dst)
     c = (C.c_int64 * max(n, 1))(*capacities)
     nbytes, status = (C.c_int64 * max(n, 1))(), (C.c_int32 * max(n, 1))()
-    ctx.check(ctx.lib.jda_encode_surfaces(ctx.handle, n, s, bytes_per_pixel, j, d, c, nbytes, status), "jda_encode_surfaces")
+    if flags is None:
+        ctx.check(ctx.lib.jda_encode_surfaces(ctx.handle, n, s, bytes_per_pixel, j, d, c, nbytes, status), "jda_encode_surfaces")
+    else:
+        if len(flags) != n:
+            raise ValueError("flags: one word per job")
+        f = (C.c_uint32 * max(n, 1))(*[int(v) for v in flags])
+        ctx.check(ctx.lib.jda_encode_surfaces_ex(ctx.handle, n, s, bytes_per_pixel, j, f, d, c, nbytes, status), "jda_encode_surfaces_ex")
     return list(nbytes)[:n], list(status)[:n]
 
 
-def transcode_to_host(ctx: Context, jpeg: bytes, size=None, sampling="4:2:0", quality=75, restart_interval=0, options=0, rect=None, capacity=None):
-    """jda_transcode_to_host: decode (rect = (x, y, w, h) of the visible image, or all of it), resize to size = (out_w, out_h) where that
-    differs, encode; -> (rc, the file's bytes or None, the size the file has or needs).  capacity: the host buffer's bytes (default: the bound)."""
+def transcode_to_host(ctx: Context, jpeg: bytes, size=None, sampling="4:2:0", quality=75, restart_interval=0, options=0, rect=None, capacity=None, optimize=False):
+    """jda_transcode_to_host[_ex]: decode (rect = (x, y, w, h) of the visible image, or all of it), resize to size = (out_w, out_h) where that
+    differs, encode; -> (rc, the file's bytes or None, the size the file has or needs).  capacity: the host buffer's bytes (default: the bound).
+    optimize: Huffman tables of the file's own (ENCODE_OPTIMIZE)."""
     if size is None:
         if rect is not None:
             size = (rect[2], rect[3])
@@ -952,8 +965,12 @@ def transcode_to_host(ctx: Context, jpeg: bytes, size=None, sampling="4:2:0", qu
     buf = np.zeros(max(cap, 1), dtype=np.uint8)
     r = (C.c_int32 * 4)(*rect) if rect is not None else None
     nbytes = C.c_int64(0)
-    rc = ctx.lib.jda_transcode_to_host(ctx.handle, jpeg, len(jpeg), options, r, size[0], size[1], _sampling(sampling), quality, restart_interval,
-                                       buf.ctypes.data_as(_P), cap, C.byref(nbytes))
+    if optimize:
+        rc = ctx.lib.jda_transcode_to_host_ex(ctx.handle, jpeg, len(jpeg), options, r, size[0], size[1], _sampling(sampling), quality, restart_interval,
+                                              ENCODE_OPTIMIZE, buf.ctypes.data_as(_P), cap, C.byref(nbytes))
+    else:
+        rc = ctx.lib.jda_transcode_to_host(ctx.handle, jpeg, len(jpeg), options, r, size[0], size[1], _sampling(sampling), quality, restart_interval,
+                                           buf.ctypes.data_as(_P), cap, C.byref(nbytes))
     return rc, (buf[:nbytes.value].tobytes() if rc in (0, 2) and nbytes.value <= cap else None), nbytes.value
 
 

@@ -4200,8 +4200,8 @@ template <class IO> JDA_HD void jda_en_emit(const jda_en_arrays &A, const jda_en
     const uint64_t start = J.u_off * 8u + io.ld64(A.end + b) - (code & 0xffffu);
     jda_en_bits<IO> W;
     W.acc = 0; W.n = (uint32_t)(start & 31u); W.dw = (uint32_t *)A.u + (start >> 5); W.io = &io;
-    const uint32_t *ac = A.huff + t * 256u;
-    const uint32_t cat = jda_en_nbits((uint32_t)(diff < 0 ? -diff : diff)), hd = io.ld32(A.huff + 512u + t * 16u + cat);
+    const uint32_t *huff = A.huff + J.huff_off, *ac = huff + t * 256u;      // (the job's own words where it is optimised)
+    const uint32_t cat = jda_en_nbits((uint32_t)(diff < 0 ? -diff : diff)), hd = io.ld32(huff + 512u + t * 16u + cat);
     jda_en_put(W, hd & 0xffffu, hd >> 16);
     jda_en_put(W, (uint32_t)(diff < 0 ? diff - 1 : diff), cat);
     const uint32_t zrl = io.ld32(ac + 0xf0u);
@@ -4294,6 +4294,64 @@ template <class IO> JDA_HD void jda_en_scan_job(const jda_en_arrays &A, const jd
     if (p == ~(uint64_t)0) return;
     if (!bytes) io.st64(&A.totals[job].u_bytes, jda_en_ceil8(p) >> 3);
     else io.st64(&A.totals[job].file_bytes, (uint64_t)J.hdr_len + io.ld64(&A.totals[job].u_bytes) + p + 2u * (uint64_t)(J.n_int - 1u) + 2u);
+}
+
+// ---- jda_ho_*: Huffman tables of a file's own (JDA_ENCODE_OPTIMIZE; DESIGN.md 5.13 rule 9).  Two stages between lengths and scan, each a
+// kernel of jda_kernels.hip (jda_huffopt_*), stepped by tests/hostsim/huffopt_sim.cpp:
+//   gather   lane = block, a workgroup = 256 consecutive blocks of the flat list.  A workgroup keeps ONE histogram of JDA_EN_HUFF_DWORDS in
+//            LDS -- the word tables' index layout: AC symbol rs of table t at [t * 256 + rs], DC category s at [512 + t * 16 + s] -- and
+//            takes the jobs that own blocks of its 256 one after the other: clear, barrier, the job's lanes add their symbols (the DC
+//            category from the difference of the lengths stage, the AC symbols from the block's 128 bytes of coefficients, a ZRL for
+//            every 16 zeros in front of a coefficient, an EOB where the block ends in zeros), barrier, the nonzero bins are added to
+//            the job's histogram in HBM, barrier.  Dummy blocks count like any other.  A job that is not optimised is passed over.
+//   lengths  lane = block: the same walk once more with the job's own code words: the low 16 bits of the block's word of the lengths
+//            stage are written again.  A standard job's blocks are left alone.
+template <class IO> JDA_HD void jda_ho_clear(uint32_t tid, IO &io)
+{
+    for (uint32_t i = tid; i < JDA_EN_HUFF_DWORDS; i += JDA_EN_THREADS) io.lds_st32(i, 0u);
+}
+template <class IO> JDA_HD void jda_ho_flush(uint32_t *hist, uint32_t tid, IO &io)
+{
+    for (uint32_t i = tid; i < JDA_EN_HUFF_DWORDS; i += JDA_EN_THREADS) {
+        const uint32_t v = io.lds_ld32(i);
+        if (v) io.atomic_add(hist + i, v);
+    }
+}
+// a block's symbols, each handed to sym(index in the word tables' layout, extra bits behind its code)
+template <class IO, class F> JDA_HD void jda_ho_symbols(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t b, IO &io, F &&sym)
+{
+    const uint32_t s = b - J.block0, m = s / J.bpm, k = s - m * J.bpm, t = k < J.hs * J.vs ? 0u : 1u;
+    const int32_t diff = (int32_t)(int16_t)(io.ld32(A.code + b) >> 16);
+    const uint32_t cat = jda_en_nbits((uint32_t)(diff < 0 ? -diff : diff));
+    sym(512u + t * 16u + cat, cat);
+    uint32_t run = 0;
+    for (uint32_t i = 0; i < 8u; i++) {
+        uint32_t w[4];
+        io.ld128(A.coef + (size_t)b * 64u + 8u * i, w);
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; j++) {
+            if (i == 0u && j == 0u) continue;
+            const int32_t v = (int32_t)(int16_t)((w[j >> 1] >> (16u * (j & 1u))) & 0xffffu);
+            if (v == 0) { run++; continue; }
+            for (; run > 15u; run -= 16u) sym(t * 256u + 0xf0u, 0u);
+            const uint32_t sz = jda_en_nbits((uint32_t)(v < 0 ? -v : v));
+            sym(t * 256u + ((run << 4) | sz), sz);
+            run = 0;
+        }
+    }
+    if (run) sym(t * 256u, 0u);
+}
+template <class IO> JDA_HD void jda_ho_count(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t b, IO &io)
+{
+    jda_ho_symbols(A, J, b, io, [&io](uint32_t index, uint32_t) { io.lds_add32(index, 1u); });
+}
+template <class IO> JDA_HD void jda_ho_length(const jda_en_arrays &A, const jda_encode_dev_job &J, uint32_t b, IO &io)
+{
+    if (J.hist_off == JDA_EN_NO_HIST) return;
+    const uint32_t *huff = A.huff + J.huff_off;
+    uint32_t bits = 0;
+    jda_ho_symbols(A, J, b, io, [&io, &bits, huff](uint32_t index, uint32_t extra) { bits += (io.ld32(huff + index) >> 16) + extra; });
+    io.st32(A.code + b, (io.ld32(A.code + b) & 0xffff0000u) | bits);
 }
 
 #endif // JDA_DEVICE_CORE_H

@@ -225,18 +225,24 @@ struct jda_resize_job {
 // [block0, block0 + n_blocks) of the call's flat list, in the order of the scan; its intervals' first bytes lie at istart[int0 ..
 // int0 + n_int); quant: its record in the call's quantisers; its header: hdr_len bytes at hdr_off of the header blob.  Known once the
 // lengths are (the second upload): u_off, where its unstuffed scan lies in the call's stream buffer (a multiple of 64), and [chunk0,
-// chunk0 + n_chunks) of the flat list of 64-byte chunks, the first h_chunks of them the header's.
+// chunk0 + n_chunks) of the flat list of 64-byte chunks, the first h_chunks of them the header's.  huff_off: where the job's code words lie
+// in the call's word tables, in dwords (0: the Annex K tables every standard job uses); hist_off: where its symbol histogram lies in the
+// call's histograms, in dwords (~0u: the job is not optimised and has none).  An optimised job's header is made once its histogram is known.
 struct jda_encode_dev_job {
     const uint8_t *src;
     uint8_t *dst;
     uint64_t capacity, u_off;
-    uint32_t src_pitch, x, y, w, h, hs, vs, nc, cx, cy, bpm, wb, hb, ri, block0, n_blocks, quant, hdr_off, hdr_len, int0, n_int, chunk0, n_chunks, h_chunks;
+    uint32_t src_pitch, x, y, w, h, hs, vs, nc, cx, cy, bpm, wb, hb, ri, block0, n_blocks, quant, hdr_off, hdr_len, int0, n_int, chunk0, n_chunks, h_chunks, huff_off, hist_off;
 };
 struct jda_encode_quant { uint32_t recip[2][64]; uint32_t half[2][64]; };      // natural order, per table: ceil(2^32 / (8 q)) and (8 q) >> 1
 struct jda_encode_totals { uint64_t u_bytes, file_bytes; };                    // per job: its unstuffed scan, its whole file
 #define JDA_EN_HUFF_DWORDS 544u           // (length << 16) | code: AC symbol rs of table t at [t * 256 + rs], DC category s at [512 + t * 16 + s]
 #define JDA_EN_CHUNK 64u                  // bytes of a stuffing chunk
 #define JDA_EN_BLOCK_BITS 1665u           // no block's code is longer
+#define JDA_EN_NO_HIST 0xffffffffu        // jda_encode_dev_job.hist_off of a job that keeps the Annex K tables
+#define JDA_EN_OPT_MAX_BLOCKS 15625000u   // of an optimised job: 64 symbols a block at the most, and no count may pass libjpeg's 10^9
 enum { JDA_EN_STAGE_BLOCKS = 0, JDA_EN_STAGE_LENGTHS, JDA_EN_STAGE_SCAN_BITS, JDA_EN_STAGE_EMIT, JDA_EN_STAGE_COUNT, JDA_EN_STAGE_SCAN_BYTES, JDA_EN_STAGE_WRITE, JDA_EN_STAGES };
+// the two stages an optimised job adds (jda_huffopt_*): gather runs behind lengths, huffopt_lengths in front of the scan
+enum { JDA_EN_STAGE_GATHER = JDA_EN_STAGES, JDA_EN_STAGE_OPT_LENGTHS, JDA_EN_STAGES_OPT };
 
 #endif

@@ -2102,6 +2102,56 @@ extern "C" hipError_t jda_launch_encode_stage(const jda_en_arrays *A, uint32_t s
     return hipGetLastError();
 }
 
+// jda_huffopt_*: the two stages an optimised job adds (jda_ho_* in jda_device_core.h; DESIGN.md 5.13 rule 9).  gather: a workgroup's one
+// histogram in LDS (2,176 bytes), LDS atomic adds, then no-return dword atomic adds of its nonzero bins into the job's histogram in HBM;
+// lengths: a lane per block, 16-byte coefficient loads and one dword store.  The jobs a workgroup's 256 blocks belong to are taken in
+// turn, the loop's bounds the same in every lane, so every lane meets every barrier.
+struct jda_huffopt_io : jda_encode_io {
+    uint32_t *hist_lds;
+    __device__ __forceinline__ void lds_st32(uint32_t i, uint32_t v) const { hist_lds[i] = v; }
+    __device__ __forceinline__ uint32_t lds_ld32(uint32_t i) const { return hist_lds[i]; }
+    __device__ __forceinline__ void lds_add32(uint32_t i, uint32_t v) const { (void)__hip_atomic_fetch_add(hist_lds + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    __device__ __forceinline__ void atomic_add(uint32_t *p, uint32_t v) const { (void)__hip_atomic_fetch_add(JDA_G(uint32_t, p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_huffopt_gather(jda_en_arrays A, uint32_t n_blocks, uint32_t *hist)
+{
+    __shared__ uint32_t hist_lds[JDA_EN_HUFF_DWORDS];
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = hist_lds;
+    const uint32_t first = blockIdx.x * JDA_EN_THREADS, b = first + threadIdx.x;
+    const uint32_t last = first + JDA_EN_THREADS - 1u < n_blocks ? first + JDA_EN_THREADS - 1u : n_blocks - 1u;
+    const uint32_t j0 = jda_en_find_block(A.jobs, A.n_jobs, first, io), j1 = jda_en_find_block(A.jobs, A.n_jobs, last, io);
+    const uint32_t mine = b < n_blocks ? jda_en_find_block(A.jobs, A.n_jobs, b, io) : ~0u;
+    for (uint32_t j = j0; j <= j1; j++) {
+        const uint32_t hoff = io.ld32(&A.jobs[j].hist_off);
+        if (hoff == JDA_EN_NO_HIST) continue;
+        jda_ho_clear(threadIdx.x, io);
+        __syncthreads();
+        if (mine == j) jda_ho_count(A, A.jobs[j], b, io);
+        __syncthreads();
+        jda_ho_flush(hist + hoff, threadIdx.x, io);
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_huffopt_lengths(jda_en_arrays A, uint32_t n_blocks)
+{
+    const uint32_t b = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (b >= n_blocks) return;
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = nullptr;
+    const jda_encode_dev_job J = A.jobs[jda_en_find_block(A.jobs, A.n_jobs, b, io)];
+    jda_ho_length(A, J, b, io);
+}
+// JDA_EN_STAGE_GATHER (hist: the call's histograms, zeroed) or JDA_EN_STAGE_OPT_LENGTHS of a call with an optimised job
+extern "C" hipError_t jda_launch_huffopt_stage(const jda_en_arrays *A, uint32_t stage, uint32_t n_blocks, uint32_t *hist, hipStream_t stream)
+{
+    if (!A || A->n_jobs == 0u || n_blocks == 0u || (stage != JDA_EN_STAGE_GATHER && stage != JDA_EN_STAGE_OPT_LENGTHS) || (stage == JDA_EN_STAGE_GATHER && !hist)) return hipErrorInvalidValue;
+    const dim3 block(JDA_EN_THREADS), bgrid((n_blocks + JDA_EN_THREADS - 1u) / JDA_EN_THREADS);
+    if (stage == JDA_EN_STAGE_GATHER) JDA_LAUNCH(jda_huffopt_gather, bgrid, block, 0, stream, *A, n_blocks, hist);
+    else JDA_LAUNCH(jda_huffopt_lengths, bgrid, block, 0, stream, *A, n_blocks);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // jda_coef_tiles<MODE>: tiles decoded from coefficient images (jda_ct_* in jda_device_core.h: the load phase that stands in for
 // P1, then the decode kernel's own list / column / row / colour stages).  A wavefront = a tile of the launch list, four to a

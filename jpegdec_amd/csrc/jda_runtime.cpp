@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <new>
 #include <thread>
 #include <vector>
@@ -1846,27 +1847,52 @@ int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, i
 // ---- baseline encode (jda_encode_* in jda_kernels.hip; the stages: jda_en_* in jda_device_core.h; checks, records and headers: jda_encode_plan.h)
 // Two halves with the host between them: the records go up, blocks / lengths / scan run, the per-job sizes of the unstuffed scans come back
 // (16 bytes a job), the scans' buffer is taken from the pool and zeroed, the records go up again with every job's place in it, and emit /
-// count / scan / write run; then the files' sizes come back.
+// count / scan / write run; then the files' sizes come back.  A call with an optimised job (JDA_ENCODE_OPTIMIZE) has one more step in its first
+// half: behind lengths, gather counts the symbols, the histograms come back (2,176 bytes a job) and the host makes the tables, the code words
+// and the headers, sends them up, and the second lengths pass writes the code lengths again before the scan sums them.
 int jda_encode_bound(int32_t w, int32_t h, int32_t sampling, int32_t restart_interval, int64_t *bytes)
 {
     return jda_encode_bound_bytes(w, h, sampling, restart_interval, bytes);
 }
-struct encode_run { uint8_t *a, *b; jda_en_arrays A; jda_encode_plan_out P; std::vector<jda_encode_totals> totals; float *stage_ms; };
+struct encode_run {
+    uint8_t *a, *b; jda_en_arrays A; jda_encode_plan_out P; std::vector<jda_encode_totals> totals;
+    float *stage_ms; uint32_t timed_stages;      // (the measuring hooks: stage_ms[timed_stages], and behind it the host's step between gather and the second lengths pass)
+    uint32_t *hist;
+};
 // stages [s0, s1) queued back to back; with stage_ms (the measuring hook) each between the context's two timer events, its time added to stage_ms[stage]
 static hipError_t encode_stages(jda_ctx *ctx, encode_run &R, uint32_t s0, uint32_t s1)
 {
     hipError_t e = hipSuccess;
     for (uint32_t s = s0; s < s1 && e == hipSuccess; s++) {
         if (R.stage_ms) e = hipEventRecord(ctx->ev_start, ctx->stream);
-        if (e == hipSuccess) e = jda_launch_encode_stage(&R.A, s, R.P.n_blocks, R.P.n_chunks, ctx->stream);
+        if (e == hipSuccess) e = s < JDA_EN_STAGES ? jda_launch_encode_stage(&R.A, s, R.P.n_blocks, R.P.n_chunks, ctx->stream)
+                                                   : jda_launch_huffopt_stage(&R.A, s, R.P.n_blocks, R.hist, ctx->stream);
         if (R.stage_ms) {
             float ms = 0.f;
             if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
             if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
             if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop);
-            R.stage_ms[s] += ms;
+            if (s < R.timed_stages) R.stage_ms[s] += ms;
         }
     }
+    return e;
+}
+// an optimised call's step between lengths and scan; rc: the plan's refusal (libjpeg's own limit), e: HIP's
+static hipError_t encode_tables(jda_ctx *ctx, encode_run &R, size_t o_huff, size_t o_hdr, int *rc)
+{
+    jda_encode_plan_out &P = R.P;
+    std::vector<uint32_t> hist((size_t)P.n_opt * JDA_EN_HUFF_DWORDS);
+    hipError_t e = encode_stages(ctx, R, JDA_EN_STAGE_GATHER, JDA_EN_STAGE_GATHER + 1u);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (e == hipSuccess) e = hipMemcpyAsync(hist.data(), R.hist, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream);
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+    if (e != hipSuccess) return e;
+    *rc = jda_encode_plan_tables(&P, hist.data());
+    if (*rc != JDA_SUCCESS) return hipSuccess;
+    e = hipMemcpyAsync(R.a + o_huff + (size_t)JDA_EN_HUFF_DWORDS * 4, P.huff.data() + JDA_EN_HUFF_DWORDS, (size_t)P.n_opt * JDA_EN_HUFF_DWORDS * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_hdr, P.hdr.data(), P.hdr.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (R.stage_ms && R.timed_stages == JDA_EN_STAGES_OPT) R.stage_ms[JDA_EN_STAGES_OPT] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (e == hipSuccess) e = encode_stages(ctx, R, JDA_EN_STAGE_OPT_LENGTHS, JDA_EN_STAGE_OPT_LENGTHS + 1u);
     return e;
 }
 static int encode_lengths(jda_ctx *ctx, encode_run &R)
@@ -1877,6 +1903,7 @@ static int encode_lengths(jda_ctx *ctx, encode_run &R)
     auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
     const size_t o_jobs = take(n * sizeof(jda_encode_dev_job)), o_quant = take(P.quant.size() * sizeof(jda_encode_quant)), o_huff = take(P.huff.size() * 4), o_hdr = take(P.hdr.size());
     const size_t o_coef = take(nb * 128), o_meta = take(nb * 4), o_code = take(nb * 4), o_end = take(nb * 8), o_ist = take((size_t)P.n_int * 8), o_tot = take(n * sizeof(jda_encode_totals));
+    const size_t o_hist = take((size_t)P.n_opt * JDA_EN_HUFF_DWORDS * 4);
     hipError_t e = jda_pool_alloc(ctx, (void **)&R.a, off);
     if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(encode scratch)"); return JDA_ERROR_MEMORY; }
     jda_en_arrays &A = R.A;
@@ -1884,12 +1911,20 @@ static int encode_lengths(jda_ctx *ctx, encode_run &R)
     A.jobs = (const jda_encode_dev_job *)(R.a + o_jobs); A.quant = (const jda_encode_quant *)(R.a + o_quant); A.huff = (const uint32_t *)(R.a + o_huff); A.hdr = R.a + o_hdr;
     A.coef = (int16_t *)(R.a + o_coef); A.meta = (uint32_t *)(R.a + o_meta); A.code = (uint32_t *)(R.a + o_code); A.end = (uint64_t *)(R.a + o_end);
     A.istart = (uint64_t *)(R.a + o_ist); A.totals = (jda_encode_totals *)(R.a + o_tot); A.n_jobs = (uint32_t)n;
+    R.hist = (uint32_t *)(R.a + o_hist);
     e = hipMemcpyAsync(R.a + o_jobs, P.jobs.data(), n * sizeof(jda_encode_dev_job), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_quant, P.quant.data(), P.quant.size() * sizeof(jda_encode_quant), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_huff, P.huff.data(), P.huff.size() * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_hdr, P.hdr.data(), P.hdr.size(), hipMemcpyHostToDevice, ctx->stream);
     { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }      // (the records are on the stack of this call)
-    if (e == hipSuccess) e = encode_stages(ctx, R, JDA_EN_STAGE_BLOCKS, JDA_EN_STAGE_EMIT);
+    if (P.n_opt) {                                                                                     // (the pool hands out what earlier calls left in it)
+        if (e == hipSuccess) e = hipMemsetAsync(R.hist, 0, (size_t)P.n_opt * JDA_EN_HUFF_DWORDS * 4, ctx->stream);
+        if (e == hipSuccess) e = encode_stages(ctx, R, JDA_EN_STAGE_BLOCKS, JDA_EN_STAGE_SCAN_BITS);
+        int rc = JDA_SUCCESS;
+        if (e == hipSuccess) e = encode_tables(ctx, R, o_huff, o_hdr, &rc);
+        if (rc != JDA_SUCCESS) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        if (e == hipSuccess) e = encode_stages(ctx, R, JDA_EN_STAGE_SCAN_BITS, JDA_EN_STAGE_EMIT);
+    } else if (e == hipSuccess) e = encode_stages(ctx, R, JDA_EN_STAGE_BLOCKS, JDA_EN_STAGE_EMIT);
     R.totals.resize(n);
     if (e == hipSuccess) e = hipMemcpyAsync(R.totals.data(), A.totals, n * sizeof(jda_encode_totals), hipMemcpyDeviceToHost, ctx->stream);
     { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
@@ -1915,8 +1950,8 @@ static int encode_files(jda_ctx *ctx, encode_run &R)
     return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_encode_files");
 }
 
-static int encode_call(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,
-                       void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
+static int encode_call(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs, const uint32_t *job_flags,
+                       void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms, uint32_t timed_stages)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (n < 0 || (bytes_per_pixel != 1 && bytes_per_pixel != 4)) return JDA_INVALID_PARAMETER;
@@ -1924,8 +1959,8 @@ static int encode_call(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t b
     if (!src || !jobs || !dst || !dst_capacity || !dst_bytes || !status) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     encode_run R;
-    R.a = R.b = NULL; R.stage_ms = stage_ms;
-    int rc = jda_encode_plan_jobs(n, src, bytes_per_pixel, jobs, dst, dst_capacity, &R.P);
+    R.a = R.b = NULL; R.stage_ms = stage_ms; R.timed_stages = timed_stages; R.hist = NULL;
+    int rc = jda_encode_plan_jobs_ex(n, src, bytes_per_pixel, jobs, job_flags, dst, dst_capacity, &R.P);
     if (rc != JDA_SUCCESS) return rc;
     rc = encode_lengths(ctx, R);
     if (rc == JDA_SUCCESS) rc = encode_files(ctx, R);
@@ -1941,7 +1976,12 @@ static int encode_call(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t b
 int jda_encode_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,
                         void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status)
 {
-    return encode_call(ctx, n, src, bytes_per_pixel, jobs, dst, dst_capacity, dst_bytes, status, NULL);
+    return encode_call(ctx, n, src, bytes_per_pixel, jobs, NULL, dst, dst_capacity, dst_bytes, status, NULL, 0u);
+}
+int jda_encode_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs, const uint32_t *job_flags,
+                           void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status)
+{
+    return encode_call(ctx, n, src, bytes_per_pixel, jobs, job_flags, dst, dst_capacity, dst_bytes, status, NULL, 0u);
 }
 // Measuring hook of tools/encode_bench.py (not part of the public header): jda_encode_surfaces with every one of its seven launches between
 // the context's two timer events on its stream; stage_ms[JDA_EN_STAGES] (order: JDA_EN_STAGE_*) is ADDED to, so the caller zeroes it.
@@ -1949,14 +1989,29 @@ int jda_internal_encode_time(jda_ctx *ctx, int32_t n, const jda_output *src, int
                              void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
 {
     if (!stage_ms) return JDA_INVALID_PARAMETER;
-    return encode_call(ctx, n, src, bytes_per_pixel, jobs, dst, dst_capacity, dst_bytes, status, stage_ms);
+    return encode_call(ctx, n, src, bytes_per_pixel, jobs, NULL, dst, dst_capacity, dst_bytes, status, stage_ms, JDA_EN_STAGES);
+}
+// .. and of its --optimize leg: jda_encode_surfaces_ex timed the same way; stage_ms[JDA_EN_STAGES_OPT + 1]: the nine launches (ids 7 and 8: gather and
+// the second lengths pass) and, last, the host's wall time between them -- the histograms' copy, the wait, the tables, their upload.
+int jda_internal_encode_time_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs, const uint32_t *job_flags,
+                                void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
+{
+    if (!stage_ms) return JDA_INVALID_PARAMETER;
+    return encode_call(ctx, n, src, bytes_per_pixel, jobs, job_flags, dst, dst_capacity, dst_bytes, status, stage_ms, JDA_EN_STAGES_OPT);
 }
 
 int jda_transcode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
                           int32_t sampling, int32_t quality, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes)
 {
+    return jda_transcode_to_host_ex(ctx, jpeg, len, options, rect, out_w, out_h, sampling, quality, restart_interval, 0u, host_file, capacity, file_bytes);
+}
+int jda_transcode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
+                             int32_t sampling, int32_t quality, int32_t restart_interval, uint32_t encode_flags, void *host_file, int64_t capacity,
+                             int64_t *file_bytes)
+{
     if (file_bytes) *file_bytes = 0;
     if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (encode_flags & ~(uint32_t)JDA_ENCODE_OPTIMIZE) return JDA_INVALID_PARAMETER;
     if (!jpeg || !host_file || !file_bytes || capacity < 0 || out_w <= 0 || out_h <= 0) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     int32_t err = JDA_SUCCESS;
@@ -2011,7 +2066,7 @@ int jda_transcode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
                 const jda_encode_job E = { resized ? 0 : box[0], resized ? 0 : box[1], out_w, out_h, sampling, quality, restart_interval, 0 };
                 void *dfile = dsurf + cbytes + rbytes;
                 int32_t st = JDA_SUCCESS;
-                rc = jda_encode_surfaces(ctx, 1, resized ? &D : &S, bpp, &E, &dfile, &fcap, file_bytes, &st);
+                rc = jda_encode_surfaces_ex(ctx, 1, resized ? &D : &S, bpp, &E, encode_flags ? &encode_flags : NULL, &dfile, &fcap, file_bytes, &st);
                 if (rc == JDA_SUCCESS) rc = st;
                 if (rc == JDA_SUCCESS) {
                     hipError_t e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);

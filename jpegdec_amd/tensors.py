@@ -159,11 +159,12 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     return result
 
 
-def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=True, restart_interval=0):
+def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=True, restart_interval=0, optimize=False):
     """files (JPEG bytes, all colour or all gray) -> list of JPEG files (bytes), each image -- or crops[k] = (x, y, w, h) of image k, in pixels
     of its visible size -- resized to size = (H, W) and encoded at `quality`; gray files take the gray sampling whatever `sampling` says.
     One Pipeline batch, one jda_resize_surfaces launch and one jda_encode_surfaces call; only the files are copied back.  prescale (whole
-    images only, ignored with crops): as decode_to_tensors.  No torch in here.  A file that fails to decode raises JdaError with its status."""
+    images only, ignored with crops): as decode_to_tensors.  optimize: every file with Huffman tables of its own (Pillow's optimize=True; a
+    thumbnail loses a few hundred bytes of standard tables).  No torch in here.  A file that fails to decode raises JdaError with its status."""
     files = list(files)
     size = tuple(int(v) for v in size)
     if len(size) != 2 or size[0] <= 0 or size[1] <= 0:
@@ -213,7 +214,8 @@ def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, presc
         visible = [(base + offs[k], pitches[k], geos[k]["out_w"], geos[k]["out_h"]) for k in range(n)]
         resized = [(rbase + k * rbytes, rpitch, size[1], size[0]) for k in range(n)]
         B.resize_surfaces(ctx, visible, bpp, resized, crops)
-        nbytes, st = B.encode_surfaces(ctx, resized, bpp, [(0, 0, size[1], size[0], samp, quality, restart_interval)] * n, [fbase + k * cap for k in range(n)], [cap] * n)
+        nbytes, st = B.encode_surfaces(ctx, resized, bpp, [(0, 0, size[1], size[0], samp, quality, restart_interval)] * n, [fbase + k * cap for k in range(n)], [cap] * n,
+                                       [B.ENCODE_OPTIMIZE] * n if optimize else None)
         if any(st):
             raise B.JdaError(max(st), "jda_encode_surfaces")
         # (the files alone come back: nbytes[k] bytes each)

@@ -11,6 +11,11 @@ warm-up rounds first, each figure the median of --repeat rounds with min and max
 Where Pillow is present the same pictures are saved by Image.save(quality=75, subsampling=2) on --cpus processes (default 16) for comparison:
 in freshly SPAWNED processes that never open the GPU, before this process creates its context.  equals_pillow: the first and the last file
 of the timed size are one file, and its entropy-coded bytes are Pillow's for the same picture.
+--optimize adds a leg per workload: the same jobs through jda_encode_surfaces_ex with JDA_ENCODE_OPTIMIZE on every job (Pillow's optimize=True) --
+the call as a caller sees it beside the standard call of the same round, its nine launches one by one through jda_internal_encode_time_ex
+(gather and the second lengths pass are the two new ones), the host's step between those two (the copy of 2,176 bytes of counts per job, the
+wait, the tables, their upload: wall time) and the files' sizes.  profiles/encode_opt_bench.json is the place for such a run on an MI355X.
+--no-pillow leaves the Pillow comparison out.
 One JSON line on stdout and, with --out FILE (profiles/encode_bench.json is the place for a run on an MI355X), in a file.  Fails without a GPU."""
 import argparse
 import io
@@ -79,9 +84,10 @@ def pillow_ms(img, n, cpus):
 
 
 STAGES = ("blocks", "lengths", "scan_bits", "emit", "count", "scan_bytes", "write")
+OPT_STAGES = STAGES + ("gather", "huffopt_lengths", "host_between_gather_and_lengths")      # jda_internal_encode_time_ex: ids 7 and 8, then the host's step
 
 
-def workload(J, ctx, n, w, h, warmup, repeat, hbm_gbps, pillow, want):
+def workload(J, ctx, n, w, h, warmup, repeat, hbm_gbps, pillow, want, optimize=False):
     import ctypes as C
     from jpegdec_amd.binding import EncodeJob, Output
     img = picture(w, h)
@@ -102,6 +108,10 @@ def workload(J, ctx, n, w, h, warmup, repeat, hbm_gbps, pillow, want):
         sb, ss = (C.c_int64 * n)(), (C.c_int32 * n)()
         ctx.lib.jda_internal_encode_time.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(EncodeJob), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        ctx.lib.jda_internal_encode_time_ex.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(EncodeJob), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p),
+                                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        sf = (C.c_uint32 * n)(*[J.ENCODE_OPTIMIZE] * n)
+        opt_ms, opt_stage, opt_bytes = [], [], None
         first = None
         for r in range(warmup + repeat):
             ctx.timer_start()
@@ -115,6 +125,20 @@ def workload(J, ctx, n, w, h, warmup, repeat, hbm_gbps, pillow, want):
             if r >= warmup:
                 ms.append(t)
                 per_stage.append(list(st))
+            if optimize:                                   # (behind the standard call of the same round; the files are overwritten)
+                ctx.timer_start()
+                opt_bytes, status = J.encode_surfaces(ctx, srcs, 4, jobs, dsts, caps, [J.ENCODE_OPTIMIZE] * n)
+                ctx.timer_stop()
+                assert not any(status)
+                t = ctx.timer_elapsed_ms()
+                st = (C.c_float * len(OPT_STAGES))()
+                ctx.check(ctx.lib.jda_internal_encode_time_ex(ctx.handle, n, so, 4, sj, sf, sd, sc, sb, ss, st), "jda_internal_encode_time_ex")
+                assert list(sb) == opt_bytes and not any(ss)
+                if r >= warmup:
+                    opt_ms.append(t)
+                    opt_stage.append(list(st))
+        if optimize:
+            nbytes, status = J.encode_surfaces(ctx, srcs, 4, jobs, dsts, caps)      # (the standard files once more, for the comparison below)
         first, last = (ctx.to_host(dsts[k], nbytes[k]).tobytes() for k in (0, n - 1))
     finally:
         ctx.free(src)
@@ -140,7 +164,13 @@ def workload(J, ctx, n, w, h, warmup, repeat, hbm_gbps, pillow, want):
         rd, wr = stage_bytes[name]
         st.update(bytes_read=rd, bytes_written=wr, hbm_roofline_fraction=round((rd + wr) / (st["median_ms"] * 1e-3) / (hbm_gbps * 1e9), 4) if st["median_ms"] > 0 else None)
         stages[name] = st
-    return {"images": n, "width": w, "height": h, "call": stats(ms), "megapixels_per_s": round(n * w * h / med / 1e3, 1), "file_bytes": files, "blocks": blocks,
+    opt = None
+    if optimize:
+        opt = {"call": stats(opt_ms), "call_over_standard": round(statistics.median(opt_ms) / med, 4), "file_bytes": int(sum(opt_bytes)),
+               "file_bytes_over_standard": round(sum(opt_bytes) / files, 4), "histogram_bytes_copied": n * 2176,
+               "stages": {name: stats([row[k] for row in opt_stage]) for k, name in enumerate(OPT_STAGES)}}
+        opt["kernel_ms_new_stages"] = round(opt["stages"]["gather"]["median_ms"] + opt["stages"]["huffopt_lengths"]["median_ms"], 4)
+    return {"images": n, "width": w, "height": h, "optimize": opt, "call": stats(ms), "megapixels_per_s": round(n * w * h / med / 1e3, 1), "file_bytes": files, "blocks": blocks,
             "stages": stages, "kernel_ms_all_stages": round(sum(v["median_ms"] for v in stages.values()), 4), "bytes_all_stages": total, "pillow": pillow,
             "equals_pillow": "Pillow is not installed" if want is None else bool(first == last and entropy_coded(first) == entropy_coded(want))}
 
@@ -152,6 +182,8 @@ def main():
     ap.add_argument("--hbm-gbps", type=float, default=8000.0)
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--small", action="store_true", help="an eighth of the images (a first look)")
+    ap.add_argument("--optimize", action="store_true", help="add the JDA_ENCODE_OPTIMIZE leg")
+    ap.add_argument("--no-pillow", action="store_true", help="leave the Pillow comparison out")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     div = 8 if args.small else 1
@@ -159,15 +191,15 @@ def main():
     # Pillow first, in spawned processes, while this process has not touched the GPU: no child ever holds it
     pillow, files = {}, {}
     for name, (n, w, h) in shapes.items():
-        p = pillow_ms(picture(w, h), n, args.cpus)
-        pillow[name] = {"cpus": args.cpus, "ms": p} if p is not None else "Pillow is not installed"
+        p = None if args.no_pillow else pillow_ms(picture(w, h), n, args.cpus)
+        pillow[name] = {"cpus": args.cpus, "ms": p} if p is not None else "left out" if args.no_pillow else "Pillow is not installed"
         files[name] = pillow_file(picture(w, h))
     import jpegdec_amd as J
     ctx = J.Context(0)
     try:
         res = {"tool": "tools/encode_bench.py", "sampling": "4:2:0", "quality": 75}
         for name, (n, w, h) in shapes.items():
-            res[name] = workload(J, ctx, n, w, h, args.warmup, args.repeat, args.hbm_gbps, pillow[name], files[name])
+            res[name] = workload(J, ctx, n, w, h, args.warmup, args.repeat, args.hbm_gbps, pillow[name], files[name], args.optimize)
     finally:
         ctx.close()
     line = json.dumps(res)
