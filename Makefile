@@ -22,7 +22,7 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so
+hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
@@ -56,6 +56,16 @@ tests/hostsim/libjda_packsim.so: tests/hostsim/pack_sim.cpp tests/hostsim/pack_t
 # the CPU (tests/test_resize_cpu.py) -- test infrastructure.  -ffp-contract=off: the taps are Pillow's only in Pillow's order of operations
 tests/hostsim/libjda_resizesim.so: tests/hostsim/resize_sim.cpp tests/hostsim/resize_twin.h $(CSRC)/jda_resize_plan.h $(CSRC)/jda_device_core.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -ffp-contract=off -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/resize_sim.cpp
+
+# the same for Pillow's five filters through jda_resize_surfaces_ex's plan and the signed instances of the two passes
+# (tests/test_resize_filters_cpu.py) -- test infrastructure; resize_filters_sim.cpp includes resize_sim.cpp for its memory policy
+RESIZEFSIM_DEPS = tests/hostsim/resize_filters_sim.cpp tests/hostsim/resize_sim.cpp tests/hostsim/resize_twin.h $(CSRC)/jda_resize_plan.h $(CSRC)/jda_device_core.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
+tests/hostsim/libjda_resizefilterssim.so: $(RESIZEFSIM_DEPS)
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -ffp-contract=off -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/resize_filters_sim.cpp
+# .. and the same with a main of its own under AddressSanitizer + UBSan: a program, nothing loaded into an interpreter
+resizefiltersasan: tests/hostsim/resize_filters_asan
+tests/hostsim/resize_filters_asan: tests/hostsim/resize_filters_main.cpp $(RESIZEFSIM_DEPS)
+	$(CXX) -O1 -g -std=c++17 -fwrapv -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/resize_filters_main.cpp tests/hostsim/resize_filters_sim.cpp
 
 # the encode kernels' six stages, lane by lane, the header builder and the argument checks of jda_encode_surfaces on the CPU
 # (tests/test_encode_cpu.py) -- test infrastructure
@@ -138,10 +148,10 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
+	rm -f tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
+.PHONY: all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan resizefiltersasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
 
 # jda_node.cpp (host code above the C-ABI) over eight pretend devices -- test infrastructure, no GPU (tests/test_c_api.py)
 nodestub: tests/node_stub/node_stub_user

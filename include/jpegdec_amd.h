@@ -414,6 +414,21 @@ int jda_pack_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t sr
 #define JDA_RESIZE_MAX_KSIZE 161
 #define JDA_RESIZE_MAX_TABLE_BYTES (64u << 20)
 int jda_resize_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst);
+/* The same with one of Pillow's five convolution filters for the whole call: Image.resize((ow, oh), F, box), bit for bit.  All share one
+ * definition (Pillow's precompute_coeffs + normalize_coeffs_8bpc, then the two integer passes) and differ in the filter function and its
+ * support, so in the taps of an axis and in the largest downscale below JDA_RESIZE_MAX_KSIZE:
+ *   JDA_RESIZE_BILINEAR  support 1    3 taps in an upscale   downscales to  80 : 1   (jda_resize_surfaces)
+ *   JDA_RESIZE_BOX       support 0.5  3                                    160 : 1
+ *   JDA_RESIZE_HAMMING   support 1    3                                     80 : 1
+ *   JDA_RESIZE_BICUBIC   support 2    5                                     40 : 1
+ *   JDA_RESIZE_LANCZOS   support 3    7                                     26.6 : 1
+ * BICUBIC and LANCZOS have negative taps and run kernel instances of their own (signed 24-bit multiply-adds, a two-sided clip); the other
+ * three run the instances of jda_resize_surfaces.  Everything else as jda_resize_surfaces, which is this call with JDA_RESIZE_BILINEAR.
+ * JDA_INVALID_PARAMETER: a filter id that is none of the five.  JDA_UNSUPPORTED_FEATURE also for a tap table that fails the host's guard
+ * (a tap of 2^23 or more in size, or an output coordinate whose taps' sum could leave 32 bits: no axis is known that does). */
+enum { JDA_RESIZE_BILINEAR = 0, JDA_RESIZE_BOX = 1, JDA_RESIZE_HAMMING = 2, JDA_RESIZE_BICUBIC = 3, JDA_RESIZE_LANCZOS = 4 };
+int jda_resize_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
+                           int32_t filter);
 
 /* ---- Decoded surfaces encoded on the GPU as baseline JFIF files: libjpeg's file, byte for byte
  * A job turns the pixel rectangle {x, y, w, h} (1 <= w, h <= 65535, inside width_px x rows) of src[i] -- a surface resident in HBM,
@@ -498,7 +513,13 @@ int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
 int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *rect,
                                int32_t out_w, int32_t out_h, void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded,
                                int32_t *tiles);
-/* jda_decode_to_host_ex, jda_resize_surfaces (only when out_w x out_h differs from the rectangle's size) and jda_encode_surfaces: a JPEG file
+/* the same with a filter (JDA_RESIZE_*; 0: jda_decode_to_host_resized).  The MCUs that are decoded are those the CHOSEN filter's taps read: a
+ * LANCZOS crop reads up to three times the scale beyond its rectangle on each side -- clipped at the visible image, never at the rectangle. */
+int jda_decode_to_host_resized_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *rect,
+                                  int32_t out_w, int32_t out_h, int32_t filter, void *host_pixels, int32_t pitch_bytes, int32_t rows,
+                                  int32_t *mcus_decoded, int32_t *tiles);
+/* jda_decode_to_host_ex, jda_resize_surfaces (only when out_w x out_h differs from the rectangle's size; always the triangle filter,
+ * JDA_RESIZE_BILINEAR: the transcode call takes no filter) and jda_encode_surfaces: a JPEG file
  * in, a baseline JPEG file of rect = {x, y, w, h} (pixels of the visible image at the options' scale; NULL: all of it) at out_w x out_h out;
  * only files cross the bus.  The image is decoded as JDA_RGB8888, a gray file as JDA_EIGHT_BIT_GRAYSCALE -- and then sampling must be
  * JDA_ENCODE_GRAY, as it must not be for a colour file (JDA_INVALID_PARAMETER).  Only the MCUs that hold a pixel that is read are decoded.

@@ -16,6 +16,8 @@ PACK_DTYPES = {PACK_U8: np.uint8, PACK_F16: np.float16, PACK_F32: np.float32}
 ENCODE_GRAY, ENCODE_444, ENCODE_422, ENCODE_420 = 0, 1, 2, 3           # jda_encode_job.sampling
 ENCODE_OPTIMIZE = 1                                                    # a job's word of jda_encode_surfaces_ex: Huffman tables of the file's own
 ENCODE_SAMPLINGS = {"gray": ENCODE_GRAY, "4:4:4": ENCODE_444, "4:2:2": ENCODE_422, "4:2:0": ENCODE_420}
+RESIZE_BILINEAR, RESIZE_BOX, RESIZE_HAMMING, RESIZE_BICUBIC, RESIZE_LANCZOS = range(5)      # JDA_RESIZE_*: Pillow's five convolution filters
+RESIZE_FILTERS = {"bilinear": RESIZE_BILINEAR, "box": RESIZE_BOX, "hamming": RESIZE_HAMMING, "bicubic": RESIZE_BICUBIC, "lanczos": RESIZE_LANCZOS}
 RESIZE_MAX_KSIZE, RESIZE_MAX_TABLE_BYTES = 161, 64 << 20      # resize_surfaces: taps per output coordinate (a downscale of 80 : 1), tap tables of one call
 AUTO_ROTATE = 1      # the class's decode() applies the EXIF orientation; the C-ABI takes it as an argument (decode_oriented_to_host, orient_surfaces)
 
@@ -143,6 +145,7 @@ _PROTOTYPES = [
     ("jda_pack_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     ("jda_decode_to_host_packed", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t] + [C.POINTER(C.c_int32)] * 3),
     ("jda_resize_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output)]),
+    ("jda_resize_surfaces_ex", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output), C.c_int32]),
     ("jda_transcode_to_host", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
                                         C.c_int64, C.POINTER(C.c_int64)]),
     ("jda_transcode_to_host_ex", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
@@ -153,6 +156,7 @@ _PROTOTYPES = [
     ("jda_encode_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(EncodeJob), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("jda_decode_to_host_resized", C.c_int, [_P, C.c_char_p] + [C.c_int32] * 3 + [C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("jda_decode_to_host_resized_ex", C.c_int, [_P, C.c_char_p] + [C.c_int32] * 3 + [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("jda_checksum_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("jda_device_pci_bus_id", C.c_int, [_P, C.c_char_p, C.c_int32]),
     ("jda_upload_batch_ex", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32)]),
@@ -902,15 +906,28 @@ def decode_packed_to_host(ctx: Context, jpeg: bytes, options=0, layout=PACK_HWC,
     return rc, flat[:w.value * h.value * channels].reshape(shape), g
 
 
-def resize_surfaces(ctx: Context, src, bytes_per_pixel, dst, rects=None):
-    """jda_resize_surfaces: src / dst = lists of (device_ptr, pitch_bytes, width_px, rows) of RGB8888 (4) or GRAY8 (1) surfaces -- a
+def resize_filter(resample) -> int:
+    """a filter's name ("bilinear", "box", "hamming", "bicubic", "lanczos", any case) or id (RESIZE_*) -> its id; ValueError for anything else"""
+    if isinstance(resample, str):
+        if resample.lower() in RESIZE_FILTERS:
+            return RESIZE_FILTERS[resample.lower()]
+    elif isinstance(resample, int) and not isinstance(resample, bool) and resample in RESIZE_FILTERS.values():
+        return resample
+    raise ValueError("resample: one of %s, or RESIZE_BILINEAR .. RESIZE_LANCZOS; not %r" % (", ".join(repr(k) for k in RESIZE_FILTERS), resample))
+
+
+def resize_surfaces(ctx: Context, src, bytes_per_pixel, dst, rects=None, filter=0):
+    """jda_resize_surfaces[_ex]: src / dst = lists of (device_ptr, pitch_bytes, width_px, rows) of RGB8888 (4) or GRAY8 (1) surfaces -- a
     destination's width_px x rows is the output size --, rects = list of (x, y, w, h) or None: all of width_px x rows.  Pillow's
-    resize(BILINEAR, box), bit for bit; one launch for all of them."""
+    resize(F, box), bit for bit, F = filter (RESIZE_BILINEAR by default, .. RESIZE_LANCZOS; one for the call); one launch for all of them."""
     n = len(src)
     s = (Output * max(n, 1))(*[Output(*o) for o in src])
     d = (Output * max(n, 1))(*[Output(*o) for o in dst])
     r = None if rects is None else (C.c_int32 * max(4 * n, 1))(*[v for q in rects for v in q])
-    ctx.check(ctx.lib.jda_resize_surfaces(ctx.handle, n, s, bytes_per_pixel, r, d), "jda_resize_surfaces")
+    if filter == 0:
+        ctx.check(ctx.lib.jda_resize_surfaces(ctx.handle, n, s, bytes_per_pixel, r, d), "jda_resize_surfaces")
+    else:
+        ctx.check(ctx.lib.jda_resize_surfaces_ex(ctx.handle, n, s, bytes_per_pixel, r, d, filter), "jda_resize_surfaces_ex")
 
 
 def _sampling(s):
@@ -974,8 +991,8 @@ def transcode_to_host(ctx: Context, jpeg: bytes, size=None, sampling="4:2:0", qu
     return rc, (buf[:nbytes.value].tobytes() if rc in (0, 2) and nbytes.value <= cap else None), nbytes.value
 
 
-def decode_resized_to_host(ctx: Context, jpeg: bytes, size, pixel_type=RGB8888, options=0, rect=None, out=None):
-    """jda_decode_to_host_resized: size = (out_w, out_h), rect = (x, y, w, h) in pixels of the visible image at the options' scale, or None:
+def decode_resized_to_host(ctx: Context, jpeg: bytes, size, pixel_type=RGB8888, options=0, rect=None, out=None, filter=0):
+    """jda_decode_to_host_resized[_ex] (filter: RESIZE_*, the triangle by default): size = (out_w, out_h), rect = (x, y, w, h) in pixels of the visible image at the options' scale, or None:
     all of it.  (rc, the resized pixels [out_h, out_w * bpp] uint8, geometry of the decode + "mcus_decoded", (tiles launched, tiles of the
     whole image)).  out: the caller's 2-D uint8 array to decode into, its row stride is the pitch handed to the call."""
     info = ImageInfo()
@@ -990,8 +1007,12 @@ def decode_resized_to_host(ctx: Context, jpeg: bytes, size, pixel_type=RGB8888, 
     r = (C.c_int32 * 4)(*rect) if rect is not None else None
     tiles = (C.c_int32 * 2)()
     nok = C.c_int32(0)
-    rc = ctx.lib.jda_decode_to_host_resized(ctx.handle, jpeg, len(jpeg), pixel_type, options, r, out_w, out_h, pixels.ctypes.data_as(_P), pixels.strides[0],
-                                            pixels.shape[0], C.byref(nok), tiles)
+    if filter == 0:
+        rc = ctx.lib.jda_decode_to_host_resized(ctx.handle, jpeg, len(jpeg), pixel_type, options, r, out_w, out_h, pixels.ctypes.data_as(_P), pixels.strides[0],
+                                                pixels.shape[0], C.byref(nok), tiles)
+    else:
+        rc = ctx.lib.jda_decode_to_host_resized_ex(ctx.handle, jpeg, len(jpeg), pixel_type, options, r, out_w, out_h, filter, pixels.ctypes.data_as(_P),
+                                                   pixels.strides[0], pixels.shape[0], C.byref(nok), tiles)
     try:
         g = output_geometry(info, pixel_type, options)
     except JdaError:

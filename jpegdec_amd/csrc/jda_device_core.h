@@ -3597,9 +3597,12 @@ template <int HWC, int ES, class IO> JDA_HD void jda_pack_tile(const jda_pack_ge
     for (uint32_t r = 0; r < runs; r++) jda_pack_planar<ES>(G, r, vec, io);
 }
 
-// ---- jda_rs_*: decoded surfaces resized with an antialiased triangle filter -------------------------------------------
-// The result is Pillow's resize(BILINEAR, box): a horizontal pass into 8-bit intermediates, then a vertical pass, both
-//   out = clip8((2^21 + sum_x in[min + x] * k[x]) >> 22)     per byte of a pixel, 32-bit sum, k >= 0, sum(k) ~ 2^22
+// ---- jda_rs_*: decoded surfaces resized with one of Pillow's antialiased convolution filters -------------------------
+// The result is Pillow's resize(F, box): a horizontal pass into 8-bit intermediates, then a vertical pass, both
+//   out = clip8((2^21 + sum_x in[min + x] * k[x]) >> 22)     per byte of a pixel, 32-bit sum, sum(k) ~ 2^22
+// BILINEAR, BOX and HAMMING have k >= 0: unsigned 24-bit multiply-adds, unsigned sums, a one-sided clip (SIGNED = false).  BICUBIC and LANCZOS
+// have negative taps (SIGNED = true): u8 x signed 24-bit multiply-adds, signed sums, an arithmetic shift and a two-sided clip; the host's
+// guard (jda_resize_axis_guard) holds |k| < 2^23 and every sum inside 32 bits.  Schedule, LDS image, loads and stores are the same.
 // with the taps {min, cnt, k[ksize]} of every output coordinate made by the HOST in double (jda_resize_plan.h): the kernel is integer.
 // An axis table, in dwords: {min, cnt} of coordinate i at [2 i], its ksize coefficients at [2 out_size + i ksize].
 // A workgroup owns one output TILE: JDA_RS_TILE_DWORDS dwords of th <= JDA_RS_TILE_ROWS output rows -- a dword is a pixel of RGB8888
@@ -3641,6 +3644,33 @@ JDA_HD uint32_t jda_rs_clip(uint32_t acc)
     const uint32_t v = (acc + (1u << 21)) >> 22;
     return v < 255u ? v : 255u;
 }
+// .. of a signed filter: clip8(t >> 22) with an arithmetic shift, t = acc + 2^21 (inside 32 bits: the host's guard).  Written as both
+// sides first (v_med3_i32 between 0 and 2^30 - 1, the largest t that gives 255), then the shift: the same value for every t.  Shift first
+// and the compiler packs two results with v_ashr_pk_u8_i32, whose upper 16 bits it takes for zero; on the MI355X they were not (bytes 2
+// and 3 of a dword came out wrong), so the kernels must not contain that instruction.
+JDA_HD uint32_t jda_rs_clip(int32_t acc)
+{
+    const int32_t t = acc + (1 << 21);
+    return (uint32_t)(t < 0 ? 0 : (t > (1 << 30) - 1 ? (1 << 30) - 1 : t)) >> 22;
+}
+// sample x tap into the sum: u8 x k >= 0 (v_mad_u32_u24), or u8 x signed k, |k| < 2^23 (v_mad_i32_i24)
+JDA_HD uint32_t jda_rs_mul(uint32_t px, uint32_t k) { return jda_umul24(px, k); }
+JDA_HD int32_t jda_rs_mul(uint32_t px, int32_t k)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __mul24((int32_t)px, k);
+#else
+    return (int32_t)px * k;
+#endif
+}
+// the sum's and the tap's type (unsigned with the 24-bit mask as ever, or signed: the host's guard holds every tap inside 24 bits)
+template <bool SIGNED> struct jda_rs_acc { typedef uint32_t type; };
+template <> struct jda_rs_acc<true> { typedef int32_t type; };
+template <bool SIGNED> JDA_HD typename jda_rs_acc<SIGNED>::type jda_rs_tap(uint32_t raw)
+{
+    typedef typename jda_rs_acc<SIGNED>::type T;
+    return SIGNED ? (T)raw : (T)(raw & 0xffffffu);
+}
 // tile row ty of a job: its first output row, and the source rows [row0, row0 + span) its vertical taps read (min and min + cnt rise
 // with the coordinate, so the first and the last row of the tile bound them)
 template <class IO> JDA_HD void jda_rs_tile_rows(const jda_rs_geo &G, uint32_t ty, IO &io, uint32_t &oy0, uint32_t &row0, uint32_t &span)
@@ -3650,7 +3680,7 @@ template <class IO> JDA_HD void jda_rs_tile_rows(const jda_rs_geo &G, uint32_t t
     row0 = io.ld_tap(G.vtab + 2u * oy0);
     span = io.ld_tap(G.vtab + 2u * last) + io.ld_tap(G.vtab + 2u * last + 1u) - row0;
 }
-template <int BPP, class IO> JDA_HD void jda_rs_horizontal(const jda_rs_geo &G, uint32_t tx, uint32_t row0, uint32_t span, uint32_t tid, IO &io)
+template <int BPP, bool SIGNED = false, class IO> JDA_HD void jda_rs_horizontal(const jda_rs_geo &G, uint32_t tx, uint32_t row0, uint32_t span, uint32_t tid, IO &io)
 {
     const uint32_t S = BPP == 4 ? 1u : 4u, C = BPP == 4 ? 4u : 1u;          // output pixels of a dword, channels of a pixel
     const uint32_t col = tid & (JDA_RS_TILE_DWORDS - 1u), wave = tid / JDA_RS_TILE_DWORDS;
@@ -3672,18 +3702,19 @@ template <int BPP, class IO> JDA_HD void jda_rs_horizontal(const jda_rs_geo &G, 
                 const uint32_t ox = dwc * S + s;
                 if (ox >= G.out_w) continue;
                 const uint32_t xmin = io.ld_tap(G.htab + 2u * ox), cnt = io.ld_tap(G.htab + 2u * ox + 1u), kb = G.htab + 2u * G.out_w + ox * G.hk;
-                uint32_t acc[JDA_RS_HROWS][4];
+                typename jda_rs_acc<SIGNED>::type acc[JDA_RS_HROWS][4];
 #pragma unroll
                 for (uint32_t j = 0; j < JDA_RS_HROWS; j++)
 #pragma unroll
-                    for (uint32_t c = 0; c < 4u; c++) acc[j][c] = 0u;
+                    for (uint32_t c = 0; c < 4u; c++) acc[j][c] = 0;
                 for (uint32_t x = 0; x < cnt; x++) {
-                    const uint32_t k = io.ld_tap(kb + x) & 0xffffffu, off = (xmin + x) * (uint32_t)BPP, sh = (off & 3u) * 8u;
+                    const typename jda_rs_acc<SIGNED>::type k = jda_rs_tap<SIGNED>(io.ld_tap(kb + x));
+                    const uint32_t off = (xmin + x) * (uint32_t)BPP, sh = (off & 3u) * 8u;
 #pragma unroll
                     for (uint32_t j = 0; j < JDA_RS_HROWS; j++) {
                         const uint32_t d = io.ld32(rp[j] + (off & ~3u)) >> sh;
 #pragma unroll
-                        for (uint32_t c = 0; c < C; c++) acc[j][c] += jda_umul24((d >> (8u * c)) & 0xffu, k);
+                        for (uint32_t c = 0; c < C; c++) acc[j][c] += jda_rs_mul((d >> (8u * c)) & 0xffu, k);
                     }
                 }
 #pragma unroll
@@ -3697,21 +3728,22 @@ template <int BPP, class IO> JDA_HD void jda_rs_horizontal(const jda_rs_geo &G, 
             if (base + j < span) io.lds_wr((base + j) * JDA_RS_TILE_DWORDS + col, res[j]);
     }
 }
-template <int BPP, class IO> JDA_HD void jda_rs_vertical(const jda_rs_geo &G, uint32_t tx, uint32_t oy0, uint32_t row0, uint32_t tid, IO &io)
+template <int BPP, bool SIGNED = false, class IO> JDA_HD void jda_rs_vertical(const jda_rs_geo &G, uint32_t tx, uint32_t oy0, uint32_t row0, uint32_t tid, IO &io)
 {
     const uint32_t vc = tid & 15u, orow = tid >> 4, oy = oy0 + orow, row_bytes = G.out_w * (uint32_t)BPP;
     const uint32_t b0 = (tx * JDA_RS_TILE_DWORDS + vc * 4u) * 4u;           // the vector's first byte in its destination row
     if (orow >= G.th || oy >= G.out_h || b0 >= row_bytes) return;
     const uint32_t ymin = io.ld_tap(G.vtab + 2u * oy), cnt = io.ld_tap(G.vtab + 2u * oy + 1u), kb = G.vtab + 2u * G.out_h + oy * G.vk;
-    uint32_t acc[16], out[4];
+    typename jda_rs_acc<SIGNED>::type acc[16];
+    uint32_t out[4];
 #pragma unroll
-    for (uint32_t i = 0; i < 16u; i++) acc[i] = 0u;
+    for (uint32_t i = 0; i < 16u; i++) acc[i] = 0;
     for (uint32_t y = 0; y < cnt; y++) {
-        const uint32_t k = io.ld_tap(kb + y) & 0xffffffu;
+        const typename jda_rs_acc<SIGNED>::type k = jda_rs_tap<SIGNED>(io.ld_tap(kb + y));
         uint32_t q[4];
         io.lds_rd128((ymin - row0 + y) * JDA_RS_TILE_DWORDS + vc * 4u, q);
 #pragma unroll
-        for (uint32_t i = 0; i < 16u; i++) acc[i] += jda_umul24((q[i >> 2] >> (8u * (i & 3u))) & 0xffu, k);
+        for (uint32_t i = 0; i < 16u; i++) acc[i] += jda_rs_mul((q[i >> 2] >> (8u * (i & 3u))) & 0xffu, k);
     }
 #pragma unroll
     for (uint32_t d = 0; d < 4u; d++)

@@ -1943,7 +1943,7 @@ extern "C" hipError_t jda_launch_pack(const jda_pack_job *jobs, uint32_t n, uint
 }
 
 // ------------------------------------------------------------------------------------------------
-// jda_resize_tiles<BPP>: decoded surfaces resized with Pillow's antialiased triangle filter (the passes, the tile and its LDS image:
+// jda_resize_tiles<BPP> / jda_resize_tiles_signed<BPP>: decoded surfaces resized with one of Pillow's antialiased filters (the passes, the tile and its LDS image:
 // jda_rs_* in jda_device_core.h).  grid = the flat list of every job's tiles, a workgroup finds its job by bisection
 // (scalar loads) and keeps it in SGPRs.  A workgroup resamples the source rows its tile needs horizontally into LDS (8-bit pixels), and
 // after ONE barrier every lane sums its 16-byte column over the rows' vertical taps and stores it: the intermediate image never leaves
@@ -1964,38 +1964,51 @@ struct jda_resize_io {
         v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
     }
 };
+// the body of both kernels (SIGNED: the template argument of the two passes)
+#define JDA_RESIZE_TILE_BODY(SIGNED) \
+    extern __shared__ __attribute__((aligned(16))) uint32_t resize_lds[]; \
+    const uint32_t tile = blockIdx.x; \
+    const jda_resize_job JDA_GLOBAL *job = JDA_G(const jda_resize_job, jobs) + jda_uni32(jda_rs_find_job(jobs, n_jobs, tile)); \
+    jda_rs_geo G; \
+    G.src = jda_uni_ptr(job->src); G.dst = jda_uni_ptr(job->dst); \
+    G.src_pitch = jda_uni32(job->src_pitch); G.dst_pitch = jda_uni32(job->dst_pitch); \
+    G.out_w = jda_uni32(job->out_w); G.out_h = jda_uni32(job->out_h); \
+    G.htab = jda_uni32(job->htab); G.vtab = jda_uni32(job->vtab); G.hk = jda_uni32(job->hk); G.vk = jda_uni32(job->vk); \
+    G.th = jda_uni32(job->th); \
+    const uint32_t local = tile - jda_uni32(job->tile0), tiles_x = jda_uni32(job->tiles_x); \
+    if (tiles_x == 0u || G.th == 0u) return; \
+    const uint32_t ty = local / tiles_x, tx = local - ty * tiles_x; \
+    jda_resize_io io; \
+    io.lds = resize_lds; io.tables = tables; \
+    uint32_t oy0, row0, span; \
+    jda_rs_tile_rows(G, ty, io, oy0, row0, span); \
+    oy0 = jda_uni32(oy0); row0 = jda_uni32(row0); span = jda_uni32(span); \
+    jda_rs_horizontal<BPP, SIGNED>(G, tx, row0, span, threadIdx.x, io); \
+    __syncthreads(); \
+    jda_rs_vertical<BPP, SIGNED>(G, tx, oy0, row0, threadIdx.x, io);
 template <int BPP>
 __global__ __launch_bounds__(JDA_RS_THREADS)
 void jda_resize_tiles(const jda_resize_job *__restrict__ jobs, uint32_t n_jobs, const int32_t *__restrict__ tables)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t resize_lds[];
-    const uint32_t tile = blockIdx.x;
-    const jda_resize_job JDA_GLOBAL *job = JDA_G(const jda_resize_job, jobs) + jda_uni32(jda_rs_find_job(jobs, n_jobs, tile));
-    jda_rs_geo G;
-    G.src = jda_uni_ptr(job->src); G.dst = jda_uni_ptr(job->dst);
-    G.src_pitch = jda_uni32(job->src_pitch); G.dst_pitch = jda_uni32(job->dst_pitch);
-    G.out_w = jda_uni32(job->out_w); G.out_h = jda_uni32(job->out_h);
-    G.htab = jda_uni32(job->htab); G.vtab = jda_uni32(job->vtab); G.hk = jda_uni32(job->hk); G.vk = jda_uni32(job->vk);
-    G.th = jda_uni32(job->th);
-    const uint32_t local = tile - jda_uni32(job->tile0), tiles_x = jda_uni32(job->tiles_x);
-    if (tiles_x == 0u || G.th == 0u) return;
-    const uint32_t ty = local / tiles_x, tx = local - ty * tiles_x;
-    jda_resize_io io;
-    io.lds = resize_lds; io.tables = tables;
-    uint32_t oy0, row0, span;
-    jda_rs_tile_rows(G, ty, io, oy0, row0, span);
-    oy0 = jda_uni32(oy0); row0 = jda_uni32(row0); span = jda_uni32(span);
-    jda_rs_horizontal<BPP>(G, tx, row0, span, threadIdx.x, io);
-    __syncthreads();
-    jda_rs_vertical<BPP>(G, tx, oy0, row0, threadIdx.x, io);
+    JDA_RESIZE_TILE_BODY(false)
 }
-// n jobs of one pixel size (1 or 4); n_tiles = the sum of their tiles, lds_bytes = what the largest of them needs (<= JDA_RS_LDS_ROWS rows)
-extern "C" hipError_t jda_launch_resize(const jda_resize_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, const int32_t *tables,
+// the instances of the filters with negative taps (BICUBIC, LANCZOS): signed multiply-adds and sums, a two-sided clip; nothing else differs
+template <int BPP>
+__global__ __launch_bounds__(JDA_RS_THREADS)
+void jda_resize_tiles_signed(const jda_resize_job *__restrict__ jobs, uint32_t n_jobs, const int32_t *__restrict__ tables)
+{
+    JDA_RESIZE_TILE_BODY(true)
+}
+// n jobs of one pixel size (1 or 4), signed_taps: of a filter with negative taps; n_tiles = the sum of their tiles, lds_bytes = what the largest of them needs (<= JDA_RS_LDS_ROWS rows)
+extern "C" hipError_t jda_launch_resize(const jda_resize_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, uint32_t signed_taps, const int32_t *tables,
                                         uint32_t lds_bytes, hipStream_t stream)
 {
     if (n == 0 || n_tiles == 0) return hipSuccess;
     if (!tables || lds_bytes == 0u || lds_bytes > JDA_RS_LDS_ROWS * JDA_RS_TILE_DWORDS * 4u) return hipErrorInvalidValue;
-    if (bytes_per_pixel == 4u) JDA_LAUNCH(jda_resize_tiles<4>, dim3(n_tiles), dim3(JDA_RS_THREADS), lds_bytes, stream, jobs, n, tables);
+    if (bytes_per_pixel != 4u && bytes_per_pixel != 1u) return hipErrorInvalidValue;
+    if (signed_taps && bytes_per_pixel == 4u) JDA_LAUNCH(jda_resize_tiles_signed<4>, dim3(n_tiles), dim3(JDA_RS_THREADS), lds_bytes, stream, jobs, n, tables);
+    else if (signed_taps) JDA_LAUNCH(jda_resize_tiles_signed<1>, dim3(n_tiles), dim3(JDA_RS_THREADS), lds_bytes, stream, jobs, n, tables);
+    else if (bytes_per_pixel == 4u) JDA_LAUNCH(jda_resize_tiles<4>, dim3(n_tiles), dim3(JDA_RS_THREADS), lds_bytes, stream, jobs, n, tables);
     else if (bytes_per_pixel == 1u) JDA_LAUNCH(jda_resize_tiles<1>, dim3(n_tiles), dim3(JDA_RS_THREADS), lds_bytes, stream, jobs, n, tables);
     else return hipErrorInvalidValue;
     return hipGetLastError();

@@ -2,7 +2,7 @@
 // list of one jda_resize_tiles launch.  No HIP in here: the runtime (jda_runtime.cpp) and the CPU tests (tests/hostsim/resize_sim.cpp)
 // run the same checks and build the same tables.
 //
-// The taps are Pillow's (src/libImaging/Resample.c: precompute_coeffs + normalize_coeffs_8bpc with the bilinear filter), in double, in
+// The taps are Pillow's (src/libImaging/Resample.c: precompute_coeffs + normalize_coeffs_8bpc with one of its five filters), in double, in
 // Pillow's order of operations: compile this header with -ffp-contract=off -- a fused multiply-add in `center` or in w / ww moves a
 // coefficient by one.
 #ifndef JDA_RESIZE_PLAN_H
@@ -31,24 +31,94 @@ struct jda_resize_plan_out {
     uint32_t n_tiles, lds_bytes;         // lds_bytes: what the largest tile of the launch needs
 };
 
-// coefficients per output coordinate of an axis that takes [in0, in1) to out_size; JDA_UNSUPPORTED_FEATURE past JDA_RESIZE_MAX_KSIZE
-static inline int jda_resize_axis_ksize(int32_t in0, int32_t in1, int32_t out_size, uint32_t *ksize)
+// The filters (the ids of include/jpegdec_amd.h: JDA_RESIZE_BILINEAR .. JDA_RESIZE_LANCZOS) are Pillow's, in double, in Pillow's order of
+// operations, with the C library's sin / cos.  Support, the taps of an upscale and the largest downscale below JDA_RESIZE_MAX_KSIZE = 161:
+//   BOX 0.5: 3 taps, 160 : 1     BILINEAR 1: 3 taps, 80 : 1     HAMMING 1: 3 taps, 80 : 1     BICUBIC 2: 5 taps, 40 : 1
+//   LANCZOS 3: 7 taps, 26.6 : 1
+// BICUBIC and LANCZOS have negative taps: the SIGNED filters, for which the kernel has instances of its own (jda_rs_* in jda_device_core.h).
+#define JDA_RESIZE_FILTERS 5
+// (Pillow writes the window's two constants as float literals: they enter the double arithmetic as 0.54f and 0.46f, and a tap in a few
+// hundred differs by one from what 0.54 and 0.46 give)
+#define JDA_RESIZE_HAMMING_A ((double)0.54f)
+#define JDA_RESIZE_HAMMING_B ((double)0.46f)
+static inline bool jda_resize_filter_signed(int32_t filter) { return filter == JDA_RESIZE_BICUBIC || filter == JDA_RESIZE_LANCZOS; }
+static inline double jda_resize_filter_support(int32_t filter)
 {
-    const double scale = (double)(in1 - in0) / (double)out_size;
-    const double support = scale < 1.0 ? 1.0 : scale;
-    const double c = ceil(support);
+    return filter == JDA_RESIZE_BOX ? 0.5 : filter == JDA_RESIZE_BICUBIC ? 2.0 : filter == JDA_RESIZE_LANCZOS ? 3.0 : 1.0;
+}
+static inline double jda_resize_sinc(double x)
+{
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+static inline double jda_resize_filter_weight(int32_t filter, double x)
+{
+    switch (filter) {
+    case JDA_RESIZE_BOX:
+        return x > -0.5 && x <= 0.5 ? 1.0 : 0.0;
+    case JDA_RESIZE_HAMMING:
+        if (x < 0.0) x = -x;
+        if (x == 0.0) return 1.0;
+        if (x >= 1.0) return 0.0;
+        x = x * M_PI;
+        return sin(x) / x * (JDA_RESIZE_HAMMING_A + JDA_RESIZE_HAMMING_B * cos(x));
+    case JDA_RESIZE_BICUBIC: {
+        const double a = -0.5;
+        if (x < 0.0) x = -x;
+        if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+        if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+        return 0.0;
+    }
+    case JDA_RESIZE_LANCZOS:
+        return -3.0 <= x && x < 3.0 ? jda_resize_sinc(x) * jda_resize_sinc(x / 3) : 0.0;
+    default:
+        if (x < 0.0) x = -x;
+        return x < 1.0 ? 1.0 - x : 0.0;
+    }
+}
+
+// coefficients per output coordinate of an axis that takes [in0, in1) to out_size; JDA_UNSUPPORTED_FEATURE past JDA_RESIZE_MAX_KSIZE,
+// JDA_INVALID_PARAMETER for a filter id that is none
+static inline int jda_resize_axis_ksize(int32_t in0, int32_t in1, int32_t out_size, uint32_t *ksize, int32_t filter = JDA_RESIZE_BILINEAR)
+{
     *ksize = 0;
+    if (filter < 0 || filter >= JDA_RESIZE_FILTERS) return JDA_INVALID_PARAMETER;
+    const double scale = (double)(in1 - in0) / (double)out_size;
+    const double support = jda_resize_filter_support(filter) * (scale < 1.0 ? 1.0 : scale);
+    const double c = ceil(support);
     if (c * 2.0 + 1.0 > (double)JDA_RESIZE_MAX_KSIZE) return JDA_UNSUPPORTED_FEATURE;
     *ksize = (uint32_t)((int)c * 2 + 1);
     return JDA_SUCCESS;
 }
 
-// the table of one axis: tab[2 i] = min, tab[2 i + 1] = cnt, tab[2 out_size + i ksize + x] = k[x] (zero behind cnt)
-static inline void jda_resize_axis_taps(int32_t in_size, int32_t in0, int32_t in1, int32_t out_size, uint32_t ksize, int32_t *tab)
+// what the kernel's arithmetic leans on, checked on every table made for a filter other than BILINEAR (whose taps are 0 .. 2^22 by
+// construction): a signed filter's taps fit the signed 24-bit multiply (|k| < 2^23) and the 32-bit sum of every output coordinate
+// (255 * the positive taps + 2^21 < 2^31, 255 * the negative taps + 2^21 > -2^31); BOX and HAMMING have no negative tap, as the unsigned
+// instances need.  JDA_UNSUPPORTED_FEATURE for a table that fails.
+static inline int jda_resize_axis_guard(int32_t filter, const int32_t *tab, int32_t out_size, uint32_t ksize)
+{
+    if (filter == JDA_RESIZE_BILINEAR) return JDA_SUCCESS;
+    const bool sgn = jda_resize_filter_signed(filter);
+    const int32_t *k = tab + 2 * (size_t)out_size;
+    for (int32_t xx = 0; xx < out_size; xx++, k += ksize) {
+        int64_t pos = 0, neg = 0;
+        for (uint32_t x = 0; x < ksize; x++) {
+            if (k[x] <= -(1 << 23) || k[x] >= (1 << 23) || (!sgn && k[x] < 0)) return JDA_UNSUPPORTED_FEATURE;
+            if (k[x] > 0) pos += k[x]; else neg += k[x];
+        }
+        if (255 * pos + (1 << 21) >= ((int64_t)1 << 31) || 255 * neg + (1 << 21) <= -((int64_t)1 << 31)) return JDA_UNSUPPORTED_FEATURE;
+    }
+    return JDA_SUCCESS;
+}
+
+// the table of one axis: tab[2 i] = min, tab[2 i + 1] = cnt, tab[2 out_size + i ksize + x] = k[x] (zero behind cnt); the guard's answer
+static inline int jda_resize_axis_taps(int32_t in_size, int32_t in0, int32_t in1, int32_t out_size, uint32_t ksize, int32_t *tab,
+                                       int32_t filter = JDA_RESIZE_BILINEAR)
 {
     const double scale = (double)(in1 - in0) / (double)out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs, ss = 1.0 / fs;
+    const double support = jda_resize_filter_support(filter) * fs, ss = 1.0 / fs;
     std::vector<double> w((size_t)ksize);
     int32_t *k = tab + 2 * (size_t)out_size;
     for (int32_t xx = 0; xx < out_size; xx++, k += ksize) {
@@ -59,18 +129,17 @@ static inline void jda_resize_axis_taps(int32_t in_size, int32_t in0, int32_t in
         const int32_t cnt = xmax - xmin;
         double ww = 0.0;
         for (int32_t x = 0; x < cnt; x++) {
-            double a = ((double)(x + xmin) - center + 0.5) * ss;
-            if (a < 0.0) a = -a;
-            w[(size_t)x] = a < 1.0 ? 1.0 - a : 0.0;
+            w[(size_t)x] = jda_resize_filter_weight(filter, ((double)(x + xmin) - center + 0.5) * ss);
             ww += w[(size_t)x];
         }
         for (int32_t x = 0; x < (int32_t)ksize; x++) {
             if (x >= cnt) { k[x] = 0; continue; }
             const double v = ww != 0.0 ? w[(size_t)x] / ww : w[(size_t)x];
-            k[x] = (int32_t)(0.5 + v * 4194304.0);
+            k[x] = v < 0.0 ? (int32_t)(-0.5 + v * 4194304.0) : (int32_t)(0.5 + v * 4194304.0);
         }
         tab[2 * xx] = xmin; tab[2 * xx + 1] = cnt;
     }
+    return jda_resize_axis_guard(filter, tab, out_size, ksize);
 }
 
 // output rows of a tile: the most (<= JDA_RS_TILE_ROWS) with which every tile's source rows fit the LDS budget (one at the ksize cap)
@@ -88,13 +157,13 @@ static inline uint32_t jda_resize_tile_rows(const int32_t *vtab, uint32_t out_h,
     return 1u;
 }
 
-// n >= 1 jobs.  rects: {x, y, w, h} per job, or NULL: the whole width_px x rows of every source.  dst[i].width_px x rows is the output size.
+// n >= 1 jobs, one filter for all of them.  rects: {x, y, w, h} per job, or NULL: the whole width_px x rows of every source.  dst[i].width_px x rows is the output size.
 static inline int jda_resize_plan_jobs(int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
-                                       jda_resize_plan_out *plan)
+                                       jda_resize_plan_out *plan, int32_t filter = JDA_RESIZE_BILINEAR)
 {
     plan->jobs.clear(); plan->tables.clear(); plan->reads.clear(); plan->ranges.clear(); plan->n_tiles = 0; plan->lds_bytes = 0;
     if (bytes_per_pixel != 1 && bytes_per_pixel != 4) return JDA_INVALID_PARAMETER;
-    if (n <= 0 || !src || !dst) return JDA_INVALID_PARAMETER;
+    if (n <= 0 || !src || !dst || filter < 0 || filter >= JDA_RESIZE_FILTERS) return JDA_INVALID_PARAMETER;
     const uint32_t bpp = (uint32_t)bytes_per_pixel;
     struct axis { uint32_t off, ksize, th, span; int32_t r0, r1; };
     std::map<std::array<int32_t, 4>, axis> axes;
@@ -117,14 +186,15 @@ static inline int jda_resize_plan_jobs(int32_t n, const jda_output *src, int32_t
             auto it = axes.find(keys[a]);
             if (it == axes.end()) {
                 axis N;
-                const int krc = jda_resize_axis_ksize(keys[a][1], keys[a][2], keys[a][3], &N.ksize);
+                const int krc = jda_resize_axis_ksize(keys[a][1], keys[a][2], keys[a][3], &N.ksize, filter);
                 if (krc != JDA_SUCCESS) return krc;
                 const uint64_t dwords = (uint64_t)keys[a][3] * (2u + N.ksize);
                 if ((plan->tables.size() + dwords) * 4u > (uint64_t)JDA_RESIZE_MAX_TABLE_BYTES) return JDA_UNSUPPORTED_FEATURE;
                 N.off = (uint32_t)plan->tables.size();
                 plan->tables.resize(plan->tables.size() + (size_t)dwords);
                 int32_t *tab = plan->tables.data() + N.off;
-                jda_resize_axis_taps(keys[a][0], keys[a][1], keys[a][2], keys[a][3], N.ksize, tab);
+                const int grc = jda_resize_axis_taps(keys[a][0], keys[a][1], keys[a][2], keys[a][3], N.ksize, tab, filter);
+                if (grc != JDA_SUCCESS) return grc;
                 const int32_t last = keys[a][3] - 1;
                 N.r0 = tab[0]; N.r1 = tab[2 * last] + tab[2 * last + 1];
                 N.th = 0; N.span = 0;

@@ -1726,13 +1726,14 @@ int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
 // ---- antialiased resize (jda_resize_tiles in jda_kernels.hip; the passes and the tile: jda_device_core.h; checks, taps and tiles: jda_resize_plan.h)
 // Check n jobs, build their tap tables and upload both in one block (the job records, the tables behind them), and wait for them as
 // orient_upload does; resize_launch then queues the kernel.  reads (may be NULL): per job the source pixels {x0, y0, x1, y1} its taps read.
-struct resize_plan { void *block; uint32_t n, n_tiles, bpp, lds_bytes; const int32_t *tables; };
+struct resize_plan { void *block; uint32_t n, n_tiles, bpp, lds_bytes, signed_taps; const int32_t *tables; };
 static int resize_upload(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst, resize_plan *plan,
-                         int32_t *reads)
+                         int32_t *reads, int32_t filter = JDA_RESIZE_BILINEAR)
 {
+    plan->signed_taps = jda_resize_filter_signed(filter) ? 1u : 0u;      // (the signed instances: BICUBIC, LANCZOS)
     plan->block = NULL; plan->n = (uint32_t)n; plan->n_tiles = 0; plan->bpp = (uint32_t)bytes_per_pixel; plan->lds_bytes = 0; plan->tables = NULL;
     jda_resize_plan_out P;
-    int rc = jda_resize_plan_jobs(n, src, bytes_per_pixel, rects, dst, &P);
+    int rc = jda_resize_plan_jobs(n, src, bytes_per_pixel, rects, dst, &P, filter);
     if (rc != JDA_SUCCESS) return rc;
     const size_t jbytes = align16(P.jobs.size() * sizeof(jda_resize_job)), tbytes = P.tables.size() * sizeof(int32_t);
     uint8_t *blk = NULL;
@@ -1750,19 +1751,24 @@ static int resize_upload(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t
 }
 static int resize_launch(jda_ctx *ctx, const resize_plan &plan)
 {
-    const hipError_t e = jda_launch_resize((const jda_resize_job *)plan.block, plan.n, plan.n_tiles, plan.bpp, plan.tables, plan.lds_bytes, ctx->stream);
+    const hipError_t e = jda_launch_resize((const jda_resize_job *)plan.block, plan.n, plan.n_tiles, plan.bpp, plan.signed_taps, plan.tables, plan.lds_bytes, ctx->stream);
     return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_resize_tiles");
 }
 
 int jda_resize_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst)
 {
+    return jda_resize_surfaces_ex(ctx, n, src, bytes_per_pixel, rects, dst, JDA_RESIZE_BILINEAR);
+}
+int jda_resize_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
+                           int32_t filter)
+{
     if (!ctx) return JDA_ERROR_NO_DEVICE;
-    if (n < 0 || (bytes_per_pixel != 1 && bytes_per_pixel != 4)) return JDA_INVALID_PARAMETER;
+    if (n < 0 || (bytes_per_pixel != 1 && bytes_per_pixel != 4) || filter < 0 || filter >= JDA_RESIZE_FILTERS) return JDA_INVALID_PARAMETER;
     if (n == 0) return JDA_SUCCESS;
     if (!src || !dst) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     resize_plan plan;
-    int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL);
+    int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL, filter);
     if (rc != JDA_SUCCESS) return rc;
     rc = resize_launch(ctx, plan);
     const hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -1775,10 +1781,16 @@ int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, i
                                int32_t out_w, int32_t out_h, void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *mcus_decoded,
                                int32_t *tiles)
 {
+    return jda_decode_to_host_resized_ex(ctx, jpeg, len, pixel_type, options, rect, out_w, out_h, JDA_RESIZE_BILINEAR, host_pixels, pitch_bytes, rows, mcus_decoded, tiles);
+}
+int jda_decode_to_host_resized_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *rect,
+                                  int32_t out_w, int32_t out_h, int32_t filter, void *host_pixels, int32_t pitch_bytes, int32_t rows,
+                                  int32_t *mcus_decoded, int32_t *tiles)
+{
     if (mcus_decoded) *mcus_decoded = 0;
     if (tiles) tiles[0] = tiles[1] = 0;
     if (!ctx) return JDA_ERROR_NO_DEVICE;
-    if (!jpeg || !host_pixels || out_w <= 0 || out_h <= 0) return JDA_INVALID_PARAMETER;
+    if (!jpeg || !host_pixels || out_w <= 0 || out_h <= 0 || filter < 0 || filter >= JDA_RESIZE_FILTERS) return JDA_INVALID_PARAMETER;
     if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     int32_t err = JDA_SUCCESS;
@@ -1792,7 +1804,7 @@ int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, i
     const int32_t *box = rect ? rect : whole;
     if (rc == JDA_SUCCESS && (box[0] < 0 || box[1] < 0 || box[2] <= 0 || box[3] <= 0 || (int64_t)box[0] + box[2] > ow || (int64_t)box[1] + box[3] > oh)) rc = JDA_INVALID_PARAMETER;
     // (the limits of the resize before anything is uploaded)
-    { uint32_t k; if (rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[0], box[0] + box[2], out_w, &k); if (rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[1], box[1] + box[3], out_h, &k); }
+    { uint32_t k; if (rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[0], box[0] + box[2], out_w, &k, filter); if (rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[1], box[1] + box[3], out_h, &k, filter); }
     if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
     jda_dev_image *dimg = jda_upload(ctx, img, &err);
     uint32_t nok = 0;
@@ -1812,7 +1824,7 @@ int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, i
     // what has to wait for the host -- the job record and the taps -- first: the taps say which MCUs have to be decoded at all
     resize_plan plan;
     int32_t reads[4] = { 0, 0, 0, 0 };
-    rc = resize_upload(ctx, 1, &S, bpp, box, &D, &plan, reads);
+    rc = resize_upload(ctx, 1, &S, bpp, box, &D, &plan, reads, filter);      // (reads: what the chosen filter's taps read, clipped at the visible image)
     if (rc == JDA_SUCCESS) {
         const int mw_out = cw / (I.mcus_x ? I.mcus_x : 1), mh_out = ch / (I.mcus_y ? I.mcus_y : 1);
         int32_t mcu_rect[4] = { reads[0] / mw_out, reads[1] / mh_out, (reads[2] + mw_out - 1) / mw_out, (reads[3] + mh_out - 1) / mh_out };
@@ -2086,14 +2098,21 @@ int jda_transcode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int
 
 // Measuring hook of tools/resize_bench.py (not part of the public header): the resize launch between the context's two timer events on
 // its stream -- job records and taps go up before the first event.  ms[k]: repeat k.
+int jda_internal_resize_time_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
+                                int32_t filter, int32_t reps, float *ms);
 int jda_internal_resize_time(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
                              int32_t reps, float *ms)
+{
+    return jda_internal_resize_time_ex(ctx, n, src, bytes_per_pixel, rects, dst, JDA_RESIZE_BILINEAR, reps, ms);
+}
+int jda_internal_resize_time_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
+                                int32_t filter, int32_t reps, float *ms)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (n <= 0 || reps <= 0 || !ms || !src || !dst) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     resize_plan plan;
-    int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL);
+    int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL, filter);
     if (rc != JDA_SUCCESS) return rc;
     hipError_t e = hipSuccess;
     for (int k = 0; k < reps && rc == JDA_SUCCESS && e == hipSuccess; k++) {

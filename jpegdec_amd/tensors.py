@@ -40,14 +40,15 @@ def prescale_option(info, pixel_type, options, size):
     return 0
 
 
-def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False, progressive="thumbnail"):
+def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False, progressive="thumbnail", resample=None):
     """files (JPEG bytes, all colour or all gray) -> tensors on cuda:<ctx.device>.  layout "CHW" or "HWC"; dtype torch.uint8 (default), or
     torch.float16 / torch.float32 with table = [C, 256] values of that type (normalise_table; numpy or torch).  options: the decode option
     bits of every file (a JDA_SCALE_* bit, JDA_LUMA_ONLY: one channel).  Returns a list of [C,H,W] / [H,W,C] tensors, or, when all images
     have one size, ONE [N,C,H,W] / [N,H,W,C] tensor.  A file that fails to decode raises JdaError with its status.
     size = (H, W): every image -- or crops[k] = (x, y, w, h) of image k, in pixels of its visible size -- is resized to H x W on the GPU
-    (jda_resize_surfaces: Pillow's resize(BILINEAR, box), bit for bit) before it is packed, and the result is always ONE [N,C,H,W] /
-    [N,H,W,C] tensor.  prescale=True (whole images only): each file is decoded at the largest of 1/2, 1/4, 1/8 whose visible size is still
+    (jda_resize_surfaces_ex: Pillow's resize(F, box), bit for bit) before it is packed, and the result is always ONE [N,C,H,W] /
+    [N,H,W,C] tensor.  resample: F -- "bilinear" (the default), "box", "hamming", "bicubic" or "lanczos", or the id (RESIZE_*); it goes
+    with size=.  prescale=True (whole images only): each file is decoded at the largest of 1/2, 1/4, 1/8 whose visible size is still
     at least W x H on both axes -- the DCT-domain shortcut for thumbnails; it changes pixels, so it is opt-in.
     progressive="thumbnail" (the default): a progressive file comes back as the reference decodes it, the 1/8 thumbnail of its first scan.
     progressive="full": every file whose header says progressive gets PROGRESSIVE_FULL in its options and the batch is submitted with
@@ -60,9 +61,10 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     if layout not in ("CHW", "HWC"):
         raise ValueError("layout: 'CHW' or 'HWC'")
     if size is None:
-        if crops is not None or prescale:
-            raise ValueError("crops and prescale go with size=(H, W)")
+        if crops is not None or prescale or resample is not None:
+            raise ValueError("crops, prescale and resample go with size=(H, W)")
     else:
+        filt = B.resize_filter("bilinear" if resample is None else resample)
         size = tuple(int(v) for v in size)
         if len(size) != 2 or size[0] <= 0 or size[1] <= 0:
             raise ValueError("size: (H, W), both positive")
@@ -149,7 +151,7 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
         visible = [(base + offs[k], pitches[k], geos[k]["out_w"], geos[k]["out_h"]) for k in range(n)]
         if size is not None:
             resized = [(rbase + k * rbytes, rpitch, size[1], size[0]) for k in range(n)]
-            B.resize_surfaces(ctx, visible, bpp, resized, crops)
+            B.resize_surfaces(ctx, visible, bpp, resized, crops, filt)
             visible = resized
         B.pack_surfaces(ctx, visible, bpp, ptrs, flags, elem, None if dev_table is None else dev_table.data_ptr())
     finally:
@@ -159,13 +161,15 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     return result
 
 
-def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=True, restart_interval=0, optimize=False):
+def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=True, restart_interval=0, optimize=False, resample="bilinear"):
     """files (JPEG bytes, all colour or all gray) -> list of JPEG files (bytes), each image -- or crops[k] = (x, y, w, h) of image k, in pixels
     of its visible size -- resized to size = (H, W) and encoded at `quality`; gray files take the gray sampling whatever `sampling` says.
-    One Pipeline batch, one jda_resize_surfaces launch and one jda_encode_surfaces call; only the files are copied back.  prescale (whole
+    resample: the filter, as in decode_to_tensors (Pillow's own thumbnail() takes "bicubic").
+    One Pipeline batch, one jda_resize_surfaces_ex launch and one jda_encode_surfaces call; only the files are copied back.  prescale (whole
     images only, ignored with crops): as decode_to_tensors.  optimize: every file with Huffman tables of its own (Pillow's optimize=True; a
     thumbnail loses a few hundred bytes of standard tables).  No torch in here.  A file that fails to decode raises JdaError with its status."""
     files = list(files)
+    filt = B.resize_filter(resample)
     size = tuple(int(v) for v in size)
     if len(size) != 2 or size[0] <= 0 or size[1] <= 0:
         raise ValueError("size: (H, W), both positive")
@@ -213,7 +217,7 @@ def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, presc
                 raise B.JdaError(st, "file %d of the batch" % k)
         visible = [(base + offs[k], pitches[k], geos[k]["out_w"], geos[k]["out_h"]) for k in range(n)]
         resized = [(rbase + k * rbytes, rpitch, size[1], size[0]) for k in range(n)]
-        B.resize_surfaces(ctx, visible, bpp, resized, crops)
+        B.resize_surfaces(ctx, visible, bpp, resized, crops, filt)
         nbytes, st = B.encode_surfaces(ctx, resized, bpp, [(0, 0, size[1], size[0], samp, quality, restart_interval)] * n, [fbase + k * cap for k in range(n)], [cap] * n,
                                        [B.ENCODE_OPTIMIZE] * n if optimize else None)
         if any(st):

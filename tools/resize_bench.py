@@ -7,6 +7,8 @@ resize launch runs between the context's two timer events (jda_internal_resize_t
 the copy likewise (jda_internal_copy_time).  Rounds alternate over resize and copy, so that a drift of the clock hits both alike; warm-up
 rounds first; each figure is the median of --repeat rounds with min and max beside it.  gbps = SOURCE bytes read (4 a pixel of the box)
 over the time; the copy's figure counts the bytes it reads, too.  One JSON line on stdout and, with --out, in a file.
+--filter NAME (bilinear, box, hamming, bicubic, lanczos; the default is bilinear through the hook of jda_resize_surfaces itself): Pillow's
+filter of that name through jda_internal_resize_time_ex -- BICUBIC and LANCZOS run the signed instances, with 2 and 3 times the taps.
 
 --tensors: decode_to_tensors(size=(224, 224)) against the same call without size, wall clock around the call and a device
 synchronisation, --batch files of 500 x 375 (4:2:0), alternating, median of --repeat.  torch is imported first (jpegdec_amd/tensors.py).
@@ -29,10 +31,11 @@ def stats(xs):
     return {"median_ms": round(statistics.median(xs), 5), "min_ms": round(min(xs), 5), "max_ms": round(max(xs), 5), "n": len(xs)}
 
 
-def kernel_workload(J, ctx, n, w, h, ow, oh, warmup, repeat):
+def kernel_workload(J, ctx, n, w, h, ow, oh, warmup, repeat, filt=0):
     from jpegdec_amd.binding import Output
     lib = ctx.lib
     lib.jda_internal_resize_time.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output), C.c_int32, C.POINTER(C.c_float)]
+    lib.jda_internal_resize_time_ex.argtypes = lib.jda_internal_resize_time.argtypes[:6] + [C.c_int32] + lib.jda_internal_resize_time.argtypes[6:]
     lib.jda_internal_copy_time.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_float)]
     pitch, opitch = (w * 4 + 15) & ~15, (ow * 4 + 15) & ~15
     surf, osurf = (pitch * h + 255) & ~255, (opitch * oh + 255) & ~255
@@ -46,7 +49,10 @@ def kernel_workload(J, ctx, n, w, h, ow, oh, warmup, repeat):
     try:
         for k in range(warmup + repeat):
             out = (C.c_float * 1)()
-            ctx.check(lib.jda_internal_resize_time(ctx.handle, n, src, 4, None, dst, 1, out), "jda_internal_resize_time")
+            if filt == 0:
+                ctx.check(lib.jda_internal_resize_time(ctx.handle, n, src, 4, None, dst, 1, out), "jda_internal_resize_time")
+            else:
+                ctx.check(lib.jda_internal_resize_time_ex(ctx.handle, n, src, 4, None, dst, filt, 1, out), "jda_internal_resize_time_ex")
             if k >= warmup:
                 t_resize.append(out[0])
             ctx.check(lib.jda_internal_copy_time(ctx.handle, copy_mem, src_mem, surf * n, 1, out), "jda_internal_copy_time")
@@ -91,17 +97,19 @@ def main():
     ap.add_argument("--repeat", type=int, default=10)
     ap.add_argument("--tensors", action="store_true")
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--filter", default="bilinear")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.tensors:
         res = tensors_workload(a.batch, a.warmup, a.repeat)
     else:
         import jpegdec_amd as J
+        filt = J.resize_filter(a.filter)
         ctx = J.Context(0)
         try:
-            res = {"what": "resize_bench", "format": "RGB8888", "source": "random bytes, a buffer a surface",
-                   "loader_500x375": kernel_workload(J, ctx, 1024, 500, 375, 224, 224, a.warmup, a.repeat),
-                   "thumbnail_4096": kernel_workload(J, ctx, 64, 4096, 4096, 224, 224, a.warmup, a.repeat)}
+            res = {"what": "resize_bench", "format": "RGB8888", "source": "random bytes, a buffer a surface", "filter": a.filter.lower(),
+                   "loader_500x375": kernel_workload(J, ctx, 1024, 500, 375, 224, 224, a.warmup, a.repeat, filt),
+                   "thumbnail_4096": kernel_workload(J, ctx, 64, 4096, 4096, 224, 224, a.warmup, a.repeat, filt)}
         finally:
             ctx.close()
     line = json.dumps(res, sort_keys=True)
