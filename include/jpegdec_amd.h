@@ -464,6 +464,24 @@ int jda_encode_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t 
 enum { JDA_ENCODE_OPTIMIZE = 1 };
 int jda_encode_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs, const uint32_t *job_flags,
                            void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status);
+/* jda_encode_surfaces for PROGRESSIVE files: the file Pillow's Image.save(quality=, subsampling=, progressive=True) writes for these pixels,
+ * from its SOF2 marker to EOI byte for byte (optimize=True changes nothing in such a file).  SOI, JFIF APP0, one 8-bit DQT per table, SOF2,
+ * then libjpeg's default scan script (jpeg_simple_progression: ten scans for colour, six for gray), every scan behind the DHT segment(s) of
+ * the table(s) made from its own symbol counts (jpeg_gen_optimal_table) and its SOS, then EOI; no DRI.  The coefficients are those of
+ * jda_encode_surfaces; the passes are jcphuff.c's, its two flushes of an end-of-band run -- at 0x7FFF blocks, and once more than 937
+ * correction bits are buffered -- included.  The rules in full: DESIGN.md 5.13, rules 10 to 14.
+ * Arguments, statuses and refusals as in jda_encode_surfaces, and: restart_interval must be 0 (JDA_INVALID_PARAMETER before anything is
+ * launched: restart intervals in progressive scans are not written); a job of more than 15,625,000 blocks is refused
+ * (JDA_UNSUPPORTED_FEATURE), as an optimised baseline job is.  Gray and colour jobs may be mixed across calls, not within one.  A file that
+ * does not fit its capacity is reported with the size it needs and no byte of it is written.  ELEVEN launches per call whatever n is
+ * (blocks and lengths of jda_encode_surfaces, then classify, resolve, gather, lengths, scan, emit, count, scan, write) and three waits: the
+ * symbol counts (1 KiB a scan) come back for the host to make the tables, the scans' sizes for it to place them, then the files' sizes.
+ * jda_encode_bound_progressive gives a capacity no file of that shape passes (larger than jda_encode_bound: 3,928 bits a block over all
+ * scans, and 568 bytes of DHT and SOS a scan).  Scratch: 128 + 8 bytes a block, 20 bytes a unit (a block of a scan), 2 KiB a scan, and
+ * the coded bytes. */
+int jda_encode_bound_progressive(int32_t w, int32_t h, int32_t sampling, int64_t *bytes);
+int jda_encode_surfaces_progressive(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,
+                                    void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status);
 
 /* PCI bus id ("0000:8e:00.0") of the context's GPU, for NUMA placement of the host threads that feed it; buf >= 16 bytes */
 int jda_device_pci_bus_id(jda_ctx *ctx, char *buf, int32_t len);
@@ -532,6 +550,9 @@ int jda_transcode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
 int jda_transcode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
                              int32_t sampling, int32_t quality, int32_t restart_interval, uint32_t encode_flags, void *host_file, int64_t capacity,
                              int64_t *file_bytes);
+/* jda_transcode_to_host with jda_encode_surfaces_progressive as its encoder: a progressive file out (restart_interval must be 0) */
+int jda_transcode_to_host_progressive(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
+                                      int32_t sampling, int32_t quality, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes);
 /* jda_decode_to_host_ex followed by the orientation: prepare, upload, decode to a device canvas, orient its visible rectangle into a second
  * device surface (jda_orient_surfaces) and copy back only the W' * bpp x H' bytes of jda_oriented_geometry: row r at host_pixels + r * pitch_bytes,
  * pitch_bytes >= W' * bpp (any value), rows >= H'.  orientation < 0: the file's; 0..8 as given (0, 1: the visible rectangle as it is); above

@@ -153,6 +153,11 @@ _PROTOTYPES = [
     ("jda_encode_bound", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     ("jda_encode_surfaces_ex", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(EncodeJob), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("jda_encode_bound_progressive", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("jda_encode_surfaces_progressive", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(EncodeJob), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("jda_transcode_to_host_progressive", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                                    C.c_int64, C.POINTER(C.c_int64)]),
     ("jda_encode_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(EncodeJob), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("jda_decode_to_host_resized", C.c_int, [_P, C.c_char_p] + [C.c_int32] * 3 + [C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -964,10 +969,34 @@ def encode_surfaces(ctx: Context, src, bytes_per_pixel, jobs, dst, capacities, f
     return list(nbytes)[:n], list(status)[:n]
 
 
-def transcode_to_host(ctx: Context, jpeg: bytes, size=None, sampling="4:2:0", quality=75, restart_interval=0, options=0, rect=None, capacity=None, optimize=False):
+def encode_bound_progressive(w, h, sampling) -> int:
+    """jda_encode_bound_progressive: a capacity no progressive w x h file of that sampling passes"""
+    b = C.c_int64()
+    rc = load_library().jda_encode_bound_progressive(w, h, _sampling(sampling), C.byref(b))
+    if rc != 0:
+        raise JdaError(rc, "jda_encode_bound_progressive")
+    return b.value
+
+
+def encode_surfaces_progressive(ctx: Context, src, bytes_per_pixel, jobs, dst, capacities):
+    """jda_encode_surfaces_progressive: encode_surfaces' arguments (a job's restart interval must be 0) -> (file sizes, statuses): the
+    progressive file libjpeg writes for every rectangle (Pillow's progressive=True), written where it lies in HBM."""
+    n = len(src)
+    s = (Output * max(n, 1))(*[Output(*o) for o in src])
+    j = (EncodeJob * max(n, 1))(*[EncodeJob(q[0], q[1], q[2], q[3], _sampling(q[4]), q[5], q[6] if len(q) > 6 else 0, 0) for q in jobs])
+    d = (C.c_void_p * max(n, 1))(*dst)
+    c = (C.c_int64 * max(n, 1))(*capacities)
+    nbytes, status = (C.c_int64 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    ctx.check(ctx.lib.jda_encode_surfaces_progressive(ctx.handle, n, s, bytes_per_pixel, j, d, c, nbytes, status), "jda_encode_surfaces_progressive")
+    return list(nbytes)[:n], list(status)[:n]
+
+
+def transcode_to_host(ctx: Context, jpeg: bytes, size=None, sampling="4:2:0", quality=75, restart_interval=0, options=0, rect=None, capacity=None, optimize=False,
+                      progressive=False):
     """jda_transcode_to_host[_ex]: decode (rect = (x, y, w, h) of the visible image, or all of it), resize to size = (out_w, out_h) where that
     differs, encode; -> (rc, the file's bytes or None, the size the file has or needs).  capacity: the host buffer's bytes (default: the bound).
-    optimize: Huffman tables of the file's own (ENCODE_OPTIMIZE)."""
+    optimize: Huffman tables of the file's own (ENCODE_OPTIMIZE).  progressive: a progressive file (jda_transcode_to_host_progressive; its
+    tables are always the file's own, so optimize changes nothing in it; restart_interval must be 0)."""
     if size is None:
         if rect is not None:
             size = (rect[2], rect[3])
@@ -978,11 +1007,17 @@ def transcode_to_host(ctx: Context, jpeg: bytes, size=None, sampling="4:2:0", qu
                 raise JdaError(rc, "jda_parse")
             g = output_geometry(info, GRAY8 if info.ncomp == 1 else RGB8888, options)
             size = (g["out_w"], g["out_h"])
-    cap = capacity if capacity is not None else encode_bound(size[0], size[1], sampling, restart_interval)
+    if capacity is not None:
+        cap = capacity
+    else:
+        cap = encode_bound_progressive(size[0], size[1], sampling) if progressive else encode_bound(size[0], size[1], sampling, restart_interval)
     buf = np.zeros(max(cap, 1), dtype=np.uint8)
     r = (C.c_int32 * 4)(*rect) if rect is not None else None
     nbytes = C.c_int64(0)
-    if optimize:
+    if progressive:
+        rc = ctx.lib.jda_transcode_to_host_progressive(ctx.handle, jpeg, len(jpeg), options, r, size[0], size[1], _sampling(sampling), quality, restart_interval,
+                                                       buf.ctypes.data_as(_P), cap, C.byref(nbytes))
+    elif optimize:
         rc = ctx.lib.jda_transcode_to_host_ex(ctx.handle, jpeg, len(jpeg), options, r, size[0], size[1], _sampling(sampling), quality, restart_interval,
                                               ENCODE_OPTIMIZE, buf.ctypes.data_as(_P), cap, C.byref(nbytes))
     else:

@@ -25,8 +25,10 @@
 
 #if defined(__HIPCC__)
 #define JDA_HD __host__ __device__ __forceinline__
+#define JDA_HD_MEMBER __host__ __device__ __forceinline__
 #else
 #define JDA_HD static inline __attribute__((always_inline))
+#define JDA_HD_MEMBER inline __attribute__((always_inline))
 #endif
 
 // ---- tile and LDS layout -------------------------------------------------------------------------
@@ -4384,6 +4386,311 @@ template <class IO> JDA_HD void jda_ho_length(const jda_en_arrays &A, const jda_
     uint32_t bits = 0;
     jda_ho_symbols(A, J, b, io, [&io, &bits, huff](uint32_t index, uint32_t extra) { bits += (io.ld32(huff + index) >> 16) + extra; });
     io.st32(A.code + b, (io.ld32(A.code + b) & 0xffff0000u) | bits);
+}
+
+// ================================================================================================
+// jda_pe_*: the same coefficients written as a PROGRESSIVE file (DESIGN.md 5.13 rules 10 to 14): libjpeg's default scan script and
+// jcphuff.c's four passes.  The work item is a UNIT, one block of one scan; a call's units form one flat list, a job's scans (its
+// SEGMENTS, jda_pe_seg) in file order.  Behind blocks and lengths of jda_en_* (the coefficients; a dummy block's DC) nine launches:
+//   classify lane = unit of an AC scan: does it emit a symbol of its own (JDA_PE_BREAKER: a pending end-of-band run is flushed in front of
+//            it), does its band end in zeros or in correction bits (JDA_PE_JOINS: EOBRUN++), how many correction bits it hands to the
+//            run, and -- a refinement scan -- the last newly nonzero position (no ZRL is written behind it).  DC units: 0.
+//   resolve  lane = unit.  A unit that joins and is the first of its scan, or a breaker, or follows one that does not join, opens a
+//            stretch and walks it (eight records a step) to the unit in front of the next breaker: run after run, each cut at 0x7FFF
+//            units or once more than 937 correction bits are buffered (libjpeg's greedy rule; it does not compose as a prefix function,
+//            hence the walk).  A run's bits belong to its FIRST unit, behind that unit's own
+//            (the units behind it in the run have none): the head's word holds the run's length and its buffered bits, every other
+//            unit's the distance to the head and its own offset in the buffered bits.  Every word is written by exactly one lane.
+//   gather   a workgroup = 256 consecutive units, one histogram of 256 bins in LDS, the segments it meets taken in turn as
+//            jda_huffopt_gather takes jobs: a unit's own symbols and, at a head, the run's EOBn.
+//   lengths  lane = unit: its bits under the scan's own code words -- a head's with the run's symbol, extra bits and buffered bits.
+//   scan     a workgroup = a segment: positions from lengths (jda_en_scan_* as they stand); every scan starts on a byte of its own.
+//            The second launch: a workgroup = a job, the file offsets of its chunks.
+//   emit     lane = unit: its own code at its position; its correction bits at their offset in its run's tail; the scan's last unit
+//            adds the 1-bits to the byte.
+//   count    lane = chunk: a header chunk's bytes, or a data chunk's bytes and 0xFF bytes.
+//   write    lane = chunk: header bytes copied, data bytes stuffed; the job's last chunk adds EOI.
+#define JDA_PE_BREAKER 1u
+#define JDA_PE_JOINS 2u
+#define JDA_PE_INRUN 0x80000000u           // a unit's word of the resolve stage: INRUN | (distance to the head << 10) | offset in the buffered bits,
+#define JDA_PE_HEAD 0x40000000u            // a head's: INRUN | HEAD | (units of the run << 10) | buffered bits
+#define JDA_PE_MAX_RUN 0x7fffu
+#define JDA_PE_MAX_BE 937u                 // MAX_CORR_BITS - DCTSIZE2 + 1
+#define JDA_PE_NO_SYMBOL 0xffffffffu
+struct jda_pe_arrays {
+    jda_en_arrays E;                       // jobs, quant, huff (Annex K: blocks and lengths), coef, meta, code, totals, u, ffcnt, ffend
+    const jda_pe_seg *segs;
+    const jda_pe_job *pjobs;
+    const uint32_t *words;                 // the scans' code words (jda_pe_seg.tab)
+    const uint8_t *hdr;
+    uint32_t *cls, *run, *len;             // a unit
+    uint64_t *end;                         // a unit: the bit behind its bits, from its scan's first
+    uint64_t *sbytes;                      // a segment: the bytes of its unstuffed data
+    uint32_t n_segs;
+};
+template <class IO> JDA_HD uint32_t jda_pe_find(const jda_pe_seg *segs, uint32_t n, uint32_t x, bool chunk, IO &io)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (io.ld32(chunk ? &segs[mid].chunk0 : &segs[mid].unit0) <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// the block (of the call's flat list) of unit r of a segment: a DC scan walks the job's blocks as they lie, a scan of one component that
+// component's own blocks in raster order
+JDA_HD uint32_t jda_pe_block(const jda_pe_seg &S, const jda_encode_dev_job &J, uint32_t r)
+{
+    if (S.comp == JDA_PE_ALL) return J.block0 + r;
+    const uint32_t by = r / S.wbc, bx = r - by * S.wbc;
+    if (S.comp == 0u) {
+        const uint32_t my = by / J.vs, mx = bx / J.hs;
+        return J.block0 + (my * J.cx + mx) * J.bpm + (by - my * J.vs) * J.hs + (bx - mx * J.hs);
+    }
+    return J.block0 + (by * J.cx + bx) * J.bpm + J.hs * J.vs + S.comp - 1u;
+}
+// f(z, value) for the coefficients ss .. se of a block
+template <class IO, class F> JDA_HD void jda_pe_band(const int16_t *blk, uint32_t ss, uint32_t se, IO &io, F &&f)
+{
+    for (uint32_t i = ss >> 3; i <= (se >> 3); i++) {
+        uint32_t w[4];
+        io.ld128(blk + 8u * i, w);
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; j++) {
+            const uint32_t z = i * 8u + j;
+            if (z < ss || z > se) continue;
+            f(z, (int32_t)(int16_t)((w[j >> 1] >> (16u * (j & 1u))) & 0xffffu));
+        }
+    }
+}
+template <class IO> JDA_HD void jda_pe_classify(const jda_pe_arrays &A, const jda_pe_seg &S, const jda_encode_dev_job &J, uint32_t u, IO &io)
+{
+    if (S.ss == 0u) { io.st32(A.cls + u, 0u); return; }
+    const int16_t *blk = A.E.coef + (size_t)jda_pe_block(S, J, u - S.unit0) * 64u;
+    const uint32_t al = S.al;
+    uint32_t any = 0, last = 0, eob = 0, br = 0;
+    jda_pe_band(blk, S.ss, S.se, io, [&](uint32_t z, int32_t v) {
+        const uint32_t t = (uint32_t)(v < 0 ? -v : v) >> al;
+        any |= t; last = t;
+        if (t == 1u) { eob = z; br = 0u; } else if (t > 1u) br++;
+    });
+    if (!S.ah) io.st32(A.cls + u, (any ? JDA_PE_BREAKER : 0u) | (last == 0u ? JDA_PE_JOINS : 0u));
+    else io.st32(A.cls + u, (eob ? JDA_PE_BREAKER : 0u) | (eob < S.se ? JDA_PE_JOINS : 0u) | (br << 8) | (eob << 16));
+}
+template <class IO> JDA_HD void jda_pe_resolve(const jda_pe_arrays &A, const jda_pe_seg &S, uint32_t u, IO &io)
+{
+    const uint32_t c = io.ld32(A.cls + u);
+    if (!(c & JDA_PE_JOINS)) { io.st32(A.run + u, 0u); return; }
+    if (u > S.unit0 && !(c & JDA_PE_BREAKER) && (io.ld32(A.cls + u - 1u) & JDA_PE_JOINS)) return;      // inside a stretch: its first unit's lane writes this word
+    const uint32_t stop = S.unit0 + S.n_units;
+    uint32_t a = u, n = 0, be = 0;
+    bool open = true;
+    for (uint32_t v0 = u; open && v0 < stop; v0 += 8u) {              // eight records a step: their loads are in flight together
+        uint32_t cw[8];
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++) cw[i] = io.ld32(A.cls + (v0 + i < stop ? v0 + i : stop - 1u));
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++) {
+            const uint32_t v = v0 + i, cv = cw[i];
+            if (!open || v >= stop || (v != u && (cv & JDA_PE_BREAKER))) { open = false; continue; }
+            const uint32_t off = be;
+            be += (cv >> 8) & 63u; n++;
+            if (v != a) io.st32(A.run + v, JDA_PE_INRUN | ((v - a) << 10) | off);
+            if (n == JDA_PE_MAX_RUN || be > JDA_PE_MAX_BE) {
+                io.st32(A.run + a, JDA_PE_INRUN | JDA_PE_HEAD | (n << 10) | be);
+                a = v + 1u; n = 0u; be = 0u;
+            }
+        }
+    }
+    if (n) io.st32(A.run + a, JDA_PE_INRUN | JDA_PE_HEAD | (n << 10) | be);
+}
+// a unit's symbols in the order of the file, handed to k.sym(index in the scan's tables or JDA_PE_NO_SYMBOL, extra bits, their number)
+// and k.corr(correction bits, first bit highest, their number); tail: the correction bits it hands to its run
+template <class IO, class K> JDA_HD void jda_pe_unit(const jda_pe_arrays &A, const jda_pe_seg &S, const jda_encode_dev_job &J, uint32_t u, IO &io, K &k, uint64_t &tail, uint32_t &ntail)
+{
+    const uint32_t b = jda_pe_block(S, J, u - S.unit0), al = S.al;
+    const int16_t *blk = A.E.coef + (size_t)b * 64u;
+    tail = 0; ntail = 0;
+    if (S.ss == 0u) {
+        const int32_t dc = (int32_t)(int16_t)(io.ld32((const uint32_t *)blk) & 0xffffu);
+        if (S.ah) { k.sym(JDA_PE_NO_SYMBOL, (uint32_t)(dc >> al) & 1u, 1u); return; }
+        const uint32_t s = b - J.block0, m = s / J.bpm, q = s - m * J.bpm, nl = J.hs * J.vs;
+        int32_t pred = 0;                                              // the block before it of its component, dummies included (they carry a DC)
+        if (q < nl && q > 0u) pred = (int32_t)(int16_t)(io.ld32((const uint32_t *)(blk - 64)) & 0xffffu);
+        else if (m > 0u) pred = (int32_t)(int16_t)(io.ld32((const uint32_t *)(blk - (size_t)(q < nl ? J.bpm - nl + 1u : J.bpm) * 64u)) & 0xffffu);
+        const int32_t diff = (dc >> al) - (pred >> al);
+        const uint32_t cat = jda_en_nbits((uint32_t)(diff < 0 ? -diff : diff));
+        k.sym((q < nl ? 0u : 16u) + cat, (uint32_t)(diff < 0 ? diff - 1 : diff), cat);
+        return;
+    }
+    uint32_t r = 0, nbr = 0;
+    uint64_t br = 0;
+    if (!S.ah) {
+        jda_pe_band(blk, S.ss, S.se, io, [&](uint32_t, int32_t v) {
+            const uint32_t t = (uint32_t)(v < 0 ? -v : v) >> al;
+            if (!t) { r++; return; }
+            for (; r > 15u; r -= 16u) k.sym(0xf0u, 0u, 0u);
+            const uint32_t sz = jda_en_nbits(t);
+            k.sym((r << 4) | sz, v < 0 ? ~t : t, sz);
+            r = 0u;
+        });
+    } else {
+        const uint32_t eob = (io.ld32(A.cls + u) >> 16) & 63u;
+        jda_pe_band(blk, S.ss, S.se, io, [&](uint32_t z, int32_t v) {
+            const uint32_t t = (uint32_t)(v < 0 ? -v : v) >> al;
+            if (!t) { r++; return; }
+            while (r > 15u && z <= eob) {
+                k.sym(0xf0u, 0u, 0u);
+                r -= 16u;
+                if (nbr) { k.corr(br, nbr); br = 0; nbr = 0u; }
+            }
+            if (t > 1u) { br = (br << 1) | (t & 1u); nbr++; return; }
+            k.sym((r << 4) | 1u, v < 0 ? 0u : 1u, 1u);
+            if (nbr) { k.corr(br, nbr); br = 0; nbr = 0u; }
+            r = 0u;
+        });
+    }
+    const uint32_t rn = io.ld32(A.run + u);
+    if (rn & JDA_PE_HEAD) {
+        const uint32_t len = (rn >> 10) & 0x7fffu, n = jda_en_nbits(len) - 1u;
+        k.sym(n << 4, len & ((1u << n) - 1u), n);
+    }
+    tail = br; ntail = nbr;
+}
+template <class IO> struct jda_pe_counter {
+    IO *io;
+    JDA_HD_MEMBER void sym(uint32_t index, uint32_t, uint32_t) { if (index != JDA_PE_NO_SYMBOL) io->lds_add32(index, 1u); }
+    JDA_HD_MEMBER void corr(uint64_t, uint32_t) {}
+};
+template <class IO> struct jda_pe_adder {
+    IO *io; const uint32_t *words; uint32_t bits;
+    JDA_HD_MEMBER void sym(uint32_t index, uint32_t, uint32_t n) { bits += n + (index != JDA_PE_NO_SYMBOL ? io->ld32(words + index) >> 16 : 0u); }
+    JDA_HD_MEMBER void corr(uint64_t, uint32_t n) { bits += n; }
+};
+template <class IO> JDA_HD void jda_pe_put_long(jda_en_bits<IO> &W, uint64_t bits, uint32_t n)      // n <= 63 bits, the first the highest
+{
+    while (n) {
+        const uint32_t take = n > 16u ? 16u : n;
+        jda_en_put(W, (uint32_t)(bits >> (n - take)), take);
+        n -= take;
+    }
+}
+template <class IO> struct jda_pe_writer {
+    IO *io; const uint32_t *words; jda_en_bits<IO> W;
+    JDA_HD_MEMBER void sym(uint32_t index, uint32_t v, uint32_t n)
+    {
+        if (index != JDA_PE_NO_SYMBOL) { const uint32_t h = io->ld32(words + index); jda_en_put(W, h & 0xffffu, h >> 16); }
+        jda_en_put(W, v, n);
+    }
+    JDA_HD_MEMBER void corr(uint64_t bits, uint32_t n) { jda_pe_put_long(W, bits, n); }
+};
+template <class IO> JDA_HD void jda_pe_clear(uint32_t tid, IO &io) { for (uint32_t i = tid; i < JDA_PE_TAB_DWORDS; i += JDA_EN_THREADS) io.lds_st32(i, 0u); }
+template <class IO> JDA_HD void jda_pe_flush(uint32_t *hist, uint32_t tid, IO &io)
+{
+    for (uint32_t i = tid; i < JDA_PE_TAB_DWORDS; i += JDA_EN_THREADS) {
+        const uint32_t v = io.lds_ld32(i);
+        if (v) io.atomic_add(hist + i, v);
+    }
+}
+template <class IO> JDA_HD void jda_pe_count_unit(const jda_pe_arrays &A, const jda_pe_seg &S, const jda_encode_dev_job &J, uint32_t u, IO &io)
+{
+    jda_pe_counter<IO> k; k.io = &io;
+    uint64_t tail; uint32_t ntail;
+    jda_pe_unit(A, S, J, u, io, k, tail, ntail);
+}
+template <class IO> JDA_HD void jda_pe_length(const jda_pe_arrays &A, const jda_pe_seg &S, const jda_encode_dev_job &J, uint32_t u, IO &io)
+{
+    jda_pe_adder<IO> k; k.io = &io; k.words = A.words + S.tab; k.bits = 0u;
+    uint64_t tail; uint32_t ntail;
+    jda_pe_unit(A, S, J, u, io, k, tail, ntail);
+    const uint32_t rn = S.ss ? io.ld32(A.run + u) : 0u;
+    io.st32(A.len + u, k.bits + (rn & JDA_PE_HEAD ? rn & 1023u : 0u));
+}
+template <class IO> JDA_HD void jda_pe_start(jda_en_bits<IO> &W, const jda_pe_arrays &A, const jda_pe_seg &S, uint64_t bit, IO &io)
+{
+    const uint64_t p = S.u_off * 8u + bit;
+    W.acc = 0; W.n = (uint32_t)(p & 31u); W.dw = (uint32_t *)A.E.u + (p >> 5); W.io = &io;
+}
+template <class IO> JDA_HD void jda_pe_emit(const jda_pe_arrays &A, const jda_pe_seg &S, const jda_encode_dev_job &J, uint32_t u, IO &io)
+{
+    jda_pe_writer<IO> k; k.io = &io; k.words = A.words + S.tab;
+    const uint64_t end = io.ld64(A.end + u);
+    jda_pe_start(k.W, A, S, end - io.ld32(A.len + u), io);
+    uint64_t tail; uint32_t ntail;
+    jda_pe_unit(A, S, J, u, io, k, tail, ntail);
+    if (k.W.n) jda_en_flush(k.W);
+    if (ntail) {                                                       // its correction bits, in its run's tail: behind the head's own code and the run's symbol
+        const uint32_t rn = io.ld32(A.run + u), a = rn & JDA_PE_HEAD ? u : u - ((rn >> 10) & 0x7fffu);
+        const uint32_t off = rn & JDA_PE_HEAD ? 0u : rn & 1023u, be = io.ld32(A.run + a) & 1023u;
+        jda_en_bits<IO> T;
+        jda_pe_start(T, A, S, io.ld64(A.end + a) - be + off, io);
+        jda_pe_put_long(T, tail, ntail);
+        if (T.n) jda_en_flush(T);
+    }
+    if (u + 1u == S.unit0 + S.n_units && (end & 7u)) {                 // the scan's 1-bits to the byte
+        jda_en_bits<IO> P;
+        jda_pe_start(P, A, S, end, io);
+        jda_en_put(P, 0xffu, 8u - (uint32_t)(end & 7u));
+        if (P.n) jda_en_flush(P);
+    }
+}
+// a segment's scan of the units' lengths (bytes = false: g = segment) or a job's of its chunks' bytes in the file (g = job)
+template <class IO> JDA_HD void jda_pe_scan(const jda_pe_arrays &A, uint32_t g, bool bytes, bool second, uint32_t tid, IO &io)
+{
+    const uint32_t *vals = bytes ? A.E.ffcnt : A.len;
+    const uint32_t first = io.ld32(bytes ? &A.pjobs[g].chunk0 : &A.segs[g].unit0), n = io.ld32(bytes ? &A.pjobs[g].n_chunks : &A.segs[g].n_units);
+    if (!second) { jda_en_scan_local(vals, 0xffffffffu, first, n, 0u, tid, io); return; }
+    const uint64_t p = jda_en_scan_write(vals, 0xffffffffu, first, n, 0u, bytes ? A.E.ffend : A.end, (uint64_t *)0, tid, io);
+    if (p == ~(uint64_t)0) return;
+    if (!bytes) io.st64(A.sbytes + g, jda_en_ceil8(p) >> 3);
+    else io.st64(&A.E.totals[g].file_bytes, p + 2u);
+}
+// a chunk's bytes in the file: a header chunk's as they are, a data chunk's and a zero behind every 0xFF
+template <class IO> JDA_HD void jda_pe_count(const jda_pe_arrays &A, const jda_pe_seg &S, uint32_t si, uint32_t c, IO &io)
+{
+    const uint32_t local = c - S.chunk0;
+    uint32_t cnt;
+    if (local < S.h_chunks) cnt = S.hdr_len - local * JDA_EN_CHUNK < JDA_EN_CHUNK ? S.hdr_len - local * JDA_EN_CHUNK : JDA_EN_CHUNK;
+    else {
+        const uint64_t p0 = (uint64_t)(local - S.h_chunks) * JDA_EN_CHUNK, left = io.ld64(A.sbytes + si) - p0;
+        cnt = left < JDA_EN_CHUNK ? (uint32_t)left : JDA_EN_CHUNK;
+        const uint8_t *p = A.E.u + S.u_off + p0;
+        for (uint32_t i = 0; i < JDA_EN_CHUNK / 16u; i++) {            // (behind the scan's last byte: zeros)
+            uint32_t w[4];
+            io.ld128(p + 16u * i, w);
+#pragma unroll
+            for (uint32_t j = 0; j < 16u; j++) cnt += ((w[j >> 2] >> (8u * (j & 3u))) & 0xffu) == 0xffu ? 1u : 0u;
+        }
+    }
+    io.st32(A.E.ffcnt + c, cnt);
+}
+template <class IO> JDA_HD void jda_pe_write(const jda_pe_arrays &A, const jda_pe_seg &S, const jda_encode_dev_job &J, uint32_t si, uint32_t c, IO &io)
+{
+    const uint64_t fb = io.ld64(&A.E.totals[S.job].file_bytes);
+    if (fb > J.capacity) return;                                       // the file does not fit: no byte of it is written
+    const uint32_t local = c - S.chunk0;
+    uint8_t *q = J.dst + (io.ld64(A.E.ffend + c) - io.ld32(A.E.ffcnt + c));
+    if (local < S.h_chunks) {
+        const uint32_t o = local * JDA_EN_CHUNK, left = S.hdr_len - o < JDA_EN_CHUNK ? S.hdr_len - o : JDA_EN_CHUNK;
+        for (uint32_t i = 0; i < left; i++) io.st8(q++, io.ld8(A.hdr + S.hdr_off + o + i));
+    } else {
+        const uint64_t p0 = (uint64_t)(local - S.h_chunks) * JDA_EN_CHUNK, sb = io.ld64(A.sbytes + si);
+        const uint8_t *src = A.E.u + S.u_off + p0;
+        for (uint32_t i = 0; i < JDA_EN_CHUNK / 16u; i++) {
+            if (p0 + 16u * i >= sb) break;
+            uint32_t w[4];
+            io.ld128(src + 16u * i, w);
+#pragma unroll
+            for (uint32_t j = 0; j < 16u; j++) {
+                if (p0 + 16u * i + j >= sb) continue;
+                const uint32_t v = (w[j >> 2] >> (8u * (j & 3u))) & 0xffu;
+                io.st8(q++, v);
+                if (v == 0xffu) io.st8(q++, 0u);
+            }
+        }
+    }
+    const uint32_t jc0 = io.ld32(&A.pjobs[S.job].chunk0), jcn = io.ld32(&A.pjobs[S.job].n_chunks);
+    if (c + 1u == jc0 + jcn) { io.st8(J.dst + fb - 2u, 0xffu); io.st8(J.dst + fb - 1u, 0xd9u); }
 }
 
 #endif // JDA_DEVICE_CORE_H

@@ -245,4 +245,26 @@ enum { JDA_EN_STAGE_BLOCKS = 0, JDA_EN_STAGE_LENGTHS, JDA_EN_STAGE_SCAN_BITS, JD
 // the two stages an optimised job adds (jda_huffopt_*): gather runs behind lengths, huffopt_lengths in front of the scan
 enum { JDA_EN_STAGE_GATHER = JDA_EN_STAGES, JDA_EN_STAGE_OPT_LENGTHS, JDA_EN_STAGES_OPT };
 
+// Progressive encode (jda_pe_* in jda_device_core.h, DESIGN.md 5.13 rules 10 to 14).  A SEGMENT is one scan of one job: its units -- a
+// (scan, block) pair each -- are [unit0, unit0 + n_units) of the call's flat unit list, the job's scans in file order.  comp: the scan's
+// component (JDA_PE_ALL: every block of the MCU grid in the job's block order, a DC scan); wbc: the blocks in a row of the component's own
+// extent; ss, se, ah, al as its SOS states them; tab: where the scan's code words -- and its histogram -- lie in the call's tables, in
+// dwords, JDA_PE_TAB_DWORDS a scan ((length << 16) | code: an AC scan's symbol rs at [rs], the first DC scan's category s of table t at
+// [t * 16 + s]).  Known once the lengths are: the scan's header (DHTs and SOS; the first scan's: everything from SOI) at hdr_off of the
+// header blob, [chunk0, chunk0 + n_chunks) of the flat chunk list, the first h_chunks the header's, and u_off, where its unstuffed data lie.
+struct jda_pe_seg {
+    uint64_t u_off;
+    uint32_t unit0, n_units, job, comp, wbc, ss, se, ah, al, tab, hdr_off, hdr_len, chunk0, n_chunks, h_chunks, pad;
+};
+struct jda_pe_job { uint32_t seg0, n_segs, chunk0, n_chunks; };                // a job's segments and chunks in the flat lists
+#define JDA_PE_ALL 3u
+#define JDA_PE_TAB_DWORDS 256u
+#define JDA_PE_MAX_SCANS 10u
+#define JDA_PE_BLOCK_BITS 3928u           // no block adds more to a file, all its scans together (the derivation: DESIGN.md 5.13 rule 14)
+#define JDA_PE_SCAN_HDR 568u              // no scan's DHTs and SOS are longer: two tables of 4 + 17 + 256 bytes, 14 bytes of SOS
+#define JDA_PE_FILE_HDR 200u              // SOI, APP0, two DQTs, SOF2: 2 + 18 + 138 + 19 = 177
+// the stages of a call, in the order they run (blocks and lengths are jda_encode_blocks and jda_encode_lengths as they stand)
+enum { JDA_PE_STAGE_BLOCKS = 0, JDA_PE_STAGE_DC, JDA_PE_STAGE_CLASSIFY, JDA_PE_STAGE_RESOLVE, JDA_PE_STAGE_GATHER, JDA_PE_STAGE_LENGTHS, JDA_PE_STAGE_SCAN_BITS,
+       JDA_PE_STAGE_EMIT, JDA_PE_STAGE_COUNT, JDA_PE_STAGE_SCAN_BYTES, JDA_PE_STAGE_WRITE, JDA_PE_STAGES };
+
 #endif

@@ -2165,6 +2165,121 @@ extern "C" hipError_t jda_launch_huffopt_stage(const jda_en_arrays *A, uint32_t 
     return hipGetLastError();
 }
 
+// jda_progenc_*: the stages a progressive file adds behind jda_encode_blocks and jda_encode_lengths (jda_pe_* in jda_device_core.h; DESIGN.md
+// 5.13 rules 10 to 14).  classify, resolve, lengths and emit run a lane per unit of the call's flat unit list, count and write a lane per
+// chunk (the segment of a lane: bisection over the segment records); gather keeps one histogram of 256 bins in LDS a workgroup and takes
+// the segments its 256 units belong to in turn, the loop's bounds the same in every lane; scan runs a workgroup per segment, then per job.
+// No workgroup waits for another.  Global accesses as in the baseline stages: 16-byte coefficient loads, dword records, dword atomic ORs
+// into the zeroed unstuffed data, byte stores into the file.
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_progenc_classify(jda_pe_arrays A, uint32_t n_units)
+{
+    const uint32_t u = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (u >= n_units) return;
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = nullptr;
+    const jda_pe_seg S = A.segs[jda_pe_find(A.segs, A.n_segs, u, false, io)];
+    jda_pe_classify(A, S, A.E.jobs[S.job], u, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_progenc_resolve(jda_pe_arrays A, uint32_t n_units)
+{
+    const uint32_t u = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (u >= n_units) return;
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = nullptr;
+    const jda_pe_seg S = A.segs[jda_pe_find(A.segs, A.n_segs, u, false, io)];
+    jda_pe_resolve(A, S, u, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_progenc_gather(jda_pe_arrays A, uint32_t n_units, uint32_t *hist)
+{
+    __shared__ uint32_t hist_lds[JDA_PE_TAB_DWORDS];
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = hist_lds;
+    const uint32_t first = blockIdx.x * JDA_EN_THREADS, u = first + threadIdx.x;
+    const uint32_t last = first + JDA_EN_THREADS - 1u < n_units ? first + JDA_EN_THREADS - 1u : n_units - 1u;
+    const uint32_t s0 = jda_pe_find(A.segs, A.n_segs, first, false, io), s1 = jda_pe_find(A.segs, A.n_segs, last, false, io);
+    const uint32_t mine = u < n_units ? jda_pe_find(A.segs, A.n_segs, u, false, io) : ~0u;
+    for (uint32_t s = s0; s <= s1; s++) {
+        const jda_pe_seg S = A.segs[s];
+        if (S.ss == 0u && S.ah != 0u) continue;                          // (a DC refinement scan has no symbols)
+        jda_pe_clear(threadIdx.x, io);
+        __syncthreads();
+        if (mine == s) jda_pe_count_unit(A, S, A.E.jobs[S.job], u, io);
+        __syncthreads();
+        jda_pe_flush(hist + S.tab, threadIdx.x, io);
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_progenc_lengths(jda_pe_arrays A, uint32_t n_units)
+{
+    const uint32_t u = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (u >= n_units) return;
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = nullptr;
+    const jda_pe_seg S = A.segs[jda_pe_find(A.segs, A.n_segs, u, false, io)];
+    jda_pe_length(A, S, A.E.jobs[S.job], u, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_progenc_scan(jda_pe_arrays A, uint32_t bytes)
+{
+    __shared__ uint64_t scan_lds[3 * JDA_EN_THREADS];
+    jda_huffopt_io io; io.lds = scan_lds; io.hist_lds = nullptr;
+    jda_pe_scan(A, blockIdx.x, bytes != 0u, false, threadIdx.x, io);
+    __syncthreads();
+    jda_pe_scan(A, blockIdx.x, bytes != 0u, true, threadIdx.x, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_progenc_emit(jda_pe_arrays A, uint32_t n_units)
+{
+    const uint32_t u = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (u >= n_units) return;
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = nullptr;
+    const jda_pe_seg S = A.segs[jda_pe_find(A.segs, A.n_segs, u, false, io)];
+    jda_pe_emit(A, S, A.E.jobs[S.job], u, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_progenc_count(jda_pe_arrays A, uint32_t n_chunks)
+{
+    const uint32_t c = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (c >= n_chunks) return;
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = nullptr;
+    const uint32_t si = jda_pe_find(A.segs, A.n_segs, c, true, io);
+    jda_pe_count(A, A.segs[si], si, c, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_progenc_write(jda_pe_arrays A, uint32_t n_chunks)
+{
+    const uint32_t c = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (c >= n_chunks) return;
+    jda_huffopt_io io; io.lds = nullptr; io.hist_lds = nullptr;
+    const uint32_t si = jda_pe_find(A.segs, A.n_segs, c, true, io);
+    const jda_pe_seg S = A.segs[si];
+    jda_pe_write(A, S, A.E.jobs[S.job], si, c, io);
+}
+// One stage of a progressive call (JDA_PE_STAGE_*, the order they run in).  hist: the call's zeroed histograms (gather).
+extern "C" hipError_t jda_launch_progenc_stage(const jda_pe_arrays *A, uint32_t stage, uint32_t n_blocks, uint32_t n_units, uint32_t n_jobs, uint32_t n_chunks, uint32_t *hist,
+                                               hipStream_t stream)
+{
+    if (!A || A->n_segs == 0u || n_blocks == 0u || n_units == 0u || n_jobs == 0u || stage >= JDA_PE_STAGES) return hipErrorInvalidValue;
+    if (stage >= JDA_PE_STAGE_EMIT && (n_chunks == 0u || !A->E.u)) return hipErrorInvalidValue;
+    if (stage == JDA_PE_STAGE_GATHER && !hist) return hipErrorInvalidValue;
+    const dim3 block(JDA_EN_THREADS), bgrid((n_blocks + JDA_EN_THREADS - 1u) / JDA_EN_THREADS), ugrid((n_units + JDA_EN_THREADS - 1u) / JDA_EN_THREADS);
+    const dim3 cgrid((n_chunks + JDA_EN_THREADS - 1u) / JDA_EN_THREADS);
+    switch (stage) {
+    case JDA_PE_STAGE_BLOCKS: JDA_LAUNCH(jda_encode_blocks, bgrid, block, 0, stream, A->E, n_blocks); break;
+    case JDA_PE_STAGE_DC: JDA_LAUNCH(jda_encode_lengths, bgrid, block, 0, stream, A->E, n_blocks); break;
+    case JDA_PE_STAGE_CLASSIFY: JDA_LAUNCH(jda_progenc_classify, ugrid, block, 0, stream, *A, n_units); break;
+    case JDA_PE_STAGE_RESOLVE: JDA_LAUNCH(jda_progenc_resolve, ugrid, block, 0, stream, *A, n_units); break;
+    case JDA_PE_STAGE_GATHER: JDA_LAUNCH(jda_progenc_gather, ugrid, block, 0, stream, *A, n_units, hist); break;
+    case JDA_PE_STAGE_LENGTHS: JDA_LAUNCH(jda_progenc_lengths, ugrid, block, 0, stream, *A, n_units); break;
+    case JDA_PE_STAGE_SCAN_BITS: JDA_LAUNCH(jda_progenc_scan, dim3(A->n_segs), block, 0, stream, *A, 0u); break;
+    case JDA_PE_STAGE_EMIT: JDA_LAUNCH(jda_progenc_emit, ugrid, block, 0, stream, *A, n_units); break;
+    case JDA_PE_STAGE_COUNT: JDA_LAUNCH(jda_progenc_count, cgrid, block, 0, stream, *A, n_chunks); break;
+    case JDA_PE_STAGE_SCAN_BYTES: JDA_LAUNCH(jda_progenc_scan, dim3(n_jobs), block, 0, stream, *A, 1u); break;
+    default: JDA_LAUNCH(jda_progenc_write, cgrid, block, 0, stream, *A, n_chunks); break;
+    }
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // jda_coef_tiles<MODE>: tiles decoded from coefficient images (jda_ct_* in jda_device_core.h: the load phase that stands in for
 // P1, then the decode kernel's own list / column / row / colour stages).  A wavefront = a tile of the launch list, four to a

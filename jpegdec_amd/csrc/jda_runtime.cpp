@@ -2017,13 +2017,29 @@ int jda_transcode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
 {
     return jda_transcode_to_host_ex(ctx, jpeg, len, options, rect, out_w, out_h, sampling, quality, restart_interval, 0u, host_file, capacity, file_bytes);
 }
+static int transcode_call(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
+                          int32_t sampling, int32_t quality, int32_t restart_interval, uint32_t encode_flags, bool progressive, void *host_file, int64_t capacity,
+                          int64_t *file_bytes);
 int jda_transcode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
                              int32_t sampling, int32_t quality, int32_t restart_interval, uint32_t encode_flags, void *host_file, int64_t capacity,
                              int64_t *file_bytes)
 {
+    return transcode_call(ctx, jpeg, len, options, rect, out_w, out_h, sampling, quality, restart_interval, encode_flags, false, host_file, capacity, file_bytes);
+}
+int jda_transcode_to_host_progressive(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
+                                      int32_t sampling, int32_t quality, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes)
+{
+    return transcode_call(ctx, jpeg, len, options, rect, out_w, out_h, sampling, quality, restart_interval, 0u, true, host_file, capacity, file_bytes);
+}
+// the encoder: jda_encode_surfaces_ex, or (progressive) jda_encode_surfaces_progressive
+static int transcode_call(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
+                          int32_t sampling, int32_t quality, int32_t restart_interval, uint32_t encode_flags, bool progressive, void *host_file, int64_t capacity,
+                          int64_t *file_bytes)
+{
     if (file_bytes) *file_bytes = 0;
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (encode_flags & ~(uint32_t)JDA_ENCODE_OPTIMIZE) return JDA_INVALID_PARAMETER;
+    if (progressive && restart_interval != 0) return JDA_INVALID_PARAMETER;
     if (!jpeg || !host_file || !file_bytes || capacity < 0 || out_w <= 0 || out_h <= 0) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     int32_t err = JDA_SUCCESS;
@@ -2038,7 +2054,7 @@ int jda_transcode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int
     const int32_t *box = rect ? rect : whole;
     if (rc == JDA_SUCCESS && (box[0] < 0 || box[1] < 0 || box[2] <= 0 || box[3] <= 0 || (int64_t)box[0] + box[2] > ow || (int64_t)box[1] + box[3] > oh)) rc = JDA_INVALID_PARAMETER;
     int64_t bound = 0;
-    if (rc == JDA_SUCCESS) rc = jda_encode_bound_bytes(out_w, out_h, sampling, restart_interval, &bound);
+    if (rc == JDA_SUCCESS) rc = progressive ? jda_encode_bound_progressive(out_w, out_h, sampling, &bound) : jda_encode_bound_bytes(out_w, out_h, sampling, restart_interval, &bound);
     if (rc == JDA_SUCCESS && (quality < 1 || quality > 100 || (sampling == JDA_ENCODE_GRAY) != (bpp == 1))) rc = JDA_INVALID_PARAMETER;
     const bool resized = rc == JDA_SUCCESS && (out_w != box[2] || out_h != box[3]);
     { uint32_t k; if (resized) rc = jda_resize_axis_ksize(box[0], box[0] + box[2], out_w, &k); if (resized && rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[1], box[1] + box[3], out_h, &k); }
@@ -2078,7 +2094,8 @@ int jda_transcode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int
                 const jda_encode_job E = { resized ? 0 : box[0], resized ? 0 : box[1], out_w, out_h, sampling, quality, restart_interval, 0 };
                 void *dfile = dsurf + cbytes + rbytes;
                 int32_t st = JDA_SUCCESS;
-                rc = jda_encode_surfaces_ex(ctx, 1, resized ? &D : &S, bpp, &E, encode_flags ? &encode_flags : NULL, &dfile, &fcap, file_bytes, &st);
+                rc = progressive ? jda_encode_surfaces_progressive(ctx, 1, resized ? &D : &S, bpp, &E, &dfile, &fcap, file_bytes, &st)
+                                 : jda_encode_surfaces_ex(ctx, 1, resized ? &D : &S, bpp, &E, encode_flags ? &encode_flags : NULL, &dfile, &fcap, file_bytes, &st);
                 if (rc == JDA_SUCCESS) rc = st;
                 if (rc == JDA_SUCCESS) {
                     hipError_t e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);

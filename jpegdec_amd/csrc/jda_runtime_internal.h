@@ -145,6 +145,9 @@ extern "C" hipError_t jda_launch_resize(const jda_resize_job *jobs, uint32_t n, 
 extern "C" hipError_t jda_launch_encode_stage(const jda_en_arrays *A, uint32_t stage, uint32_t n_blocks, uint32_t n_chunks, hipStream_t stream);
 // the two more of a call with an optimised job (JDA_EN_STAGE_GATHER into the call's zeroed histograms, JDA_EN_STAGE_OPT_LENGTHS; jda_ho_*)
 extern "C" hipError_t jda_launch_huffopt_stage(const jda_en_arrays *A, uint32_t stage, uint32_t n_blocks, uint32_t *hist, hipStream_t stream);
+// one stage of a progressive call (JDA_PE_STAGE_*; jda_pe_* in jda_device_core.h)
+extern "C" hipError_t jda_launch_progenc_stage(const jda_pe_arrays *A, uint32_t stage, uint32_t n_blocks, uint32_t n_units, uint32_t n_jobs, uint32_t n_chunks, uint32_t *hist,
+                                               hipStream_t stream);
 extern "C" hipError_t jda_launch_segscan_tail(const jda_segscan_params *params, uint32_t n_images, uint32_t max_segs, uint32_t first_round, uint32_t max_round, hipStream_t stream);
 extern "C" hipError_t jda_launch_filter(const jda_filter_params *params, uint32_t n_images, uint32_t max_raw_len, hipStream_t stream);
 extern "C" hipError_t jda_launch_fill_strips(const jda_strips_params *params, uint32_t n_images, uint32_t max_tiles, hipStream_t stream);

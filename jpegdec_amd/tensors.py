@@ -161,13 +161,14 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     return result
 
 
-def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=True, restart_interval=0, optimize=False, resample="bilinear"):
+def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=True, restart_interval=0, optimize=False, resample="bilinear", progressive=False):
     """files (JPEG bytes, all colour or all gray) -> list of JPEG files (bytes), each image -- or crops[k] = (x, y, w, h) of image k, in pixels
     of its visible size -- resized to size = (H, W) and encoded at `quality`; gray files take the gray sampling whatever `sampling` says.
     resample: the filter, as in decode_to_tensors (Pillow's own thumbnail() takes "bicubic").
     One Pipeline batch, one jda_resize_surfaces_ex launch and one jda_encode_surfaces call; only the files are copied back.  prescale (whole
     images only, ignored with crops): as decode_to_tensors.  optimize: every file with Huffman tables of its own (Pillow's optimize=True; a
-    thumbnail loses a few hundred bytes of standard tables).  No torch in here.  A file that fails to decode raises JdaError with its status."""
+    thumbnail loses a few hundred bytes of standard tables).  progressive: progressive files (jda_encode_surfaces_progressive: Pillow's
+    progressive=True; the tables are always the file's own, so optimize changes nothing; restart_interval must be 0).  No torch in here.  A file that fails to decode raises JdaError with its status."""
     files = list(files)
     filt = B.resize_filter(resample)
     size = tuple(int(v) for v in size)
@@ -202,7 +203,7 @@ def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, presc
         total += (p * g["canvas_h"] + 255) & ~255
     rpitch = (size[1] * bpp + 15) & ~15
     rbytes = (rpitch * size[0] + 255) & ~255
-    cap = B.encode_bound(size[1], size[0], samp, restart_interval)
+    cap = B.encode_bound_progressive(size[1], size[0], samp) if progressive else B.encode_bound(size[1], size[0], samp, restart_interval)
     base = ctx.malloc(total + rbytes * n + cap * n)
     try:
         rbase, fbase = base + total, base + total + rbytes * n
@@ -218,8 +219,11 @@ def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, presc
         visible = [(base + offs[k], pitches[k], geos[k]["out_w"], geos[k]["out_h"]) for k in range(n)]
         resized = [(rbase + k * rbytes, rpitch, size[1], size[0]) for k in range(n)]
         B.resize_surfaces(ctx, visible, bpp, resized, crops, filt)
-        nbytes, st = B.encode_surfaces(ctx, resized, bpp, [(0, 0, size[1], size[0], samp, quality, restart_interval)] * n, [fbase + k * cap for k in range(n)], [cap] * n,
-                                       [B.ENCODE_OPTIMIZE] * n if optimize else None)
+        jobs, dsts = [(0, 0, size[1], size[0], samp, quality, restart_interval)] * n, [fbase + k * cap for k in range(n)]
+        if progressive:
+            nbytes, st = B.encode_surfaces_progressive(ctx, resized, bpp, jobs, dsts, [cap] * n)
+        else:
+            nbytes, st = B.encode_surfaces(ctx, resized, bpp, jobs, dsts, [cap] * n, [B.ENCODE_OPTIMIZE] * n if optimize else None)
         if any(st):
             raise B.JdaError(max(st), "jda_encode_surfaces")
         # (the files alone come back: nbytes[k] bytes each)
