@@ -118,6 +118,45 @@ void jda_pool_free(jda_ctx *ctx, void *p)
     (void)hipFree(p);
 }
 
+// The measuring hooks' loop (jda_internal_*_time): launch() reps times, each between the context's two timer events on its stream, ms[k]:
+// repeat k; then the stream drained, the plan's block (may be NULL) released, and HIP's error under the hook's name.
+template <class Launch>
+static int timed_launches(jda_ctx *ctx, int32_t reps, float *ms, void *block, const char *who, Launch launch)
+{
+    int rc = JDA_SUCCESS;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < reps && rc == JDA_SUCCESS && e == hipSuccess; k++) {
+        e = hipEventRecord(ctx->ev_start, ctx->stream);
+        if (e == hipSuccess) rc = launch();
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, block);
+    if (rc != JDA_SUCCESS) return rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, who);
+}
+// The tail of jda_{orient,pack,resize}_surfaces: the launch is queued (launch_rc: what it said); the stream drained, the plan's block
+// released, and HIP's error under the entry point's name.
+static int finish_surfaces(jda_ctx *ctx, int launch_rc, void *block, const char *who)
+{
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, block);
+    if (launch_rc != JDA_SUCCESS) return launch_rc;
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, who);
+}
+// Rows of a device surface to host memory and the wait for them: one piece where neither side has a gap between its rows (and the caller
+// allows it), else a 2-D copy.
+static int copy_rows_back(jda_ctx *ctx, void *host, size_t host_pitch, const void *from, size_t from_pitch, size_t row_bytes, size_t rows, bool one_piece_ok)
+{
+    hipError_t e;
+    if (one_piece_ok && host_pitch == from_pitch && row_bytes == from_pitch) e = hipMemcpyAsync(host, from, row_bytes * rows, hipMemcpyDeviceToHost, ctx->stream);
+    else e = hipMemcpy2DAsync(host, host_pitch, from, from_pitch, row_bytes, rows, hipMemcpyDeviceToHost, ctx->stream);
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }      // (also after an error: the surface goes back to the pool)
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "copy back");
+}
+
 extern "C" {
 
 int jda_device_count(void)
@@ -1100,9 +1139,7 @@ static int progressive_full_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t l
     if (rc == JDA_SUCCESS) { const hipError_t e = jda_coef_plan_launch(plan, blk, ctx->stream); if (e != hipSuccess) rc = jda_set_err(ctx, e, "jda_coef_tiles"); }
     if (rc == JDA_SUCCESS && drows > 0) {
         const size_t row_bytes = (size_t)cw * bpp < (size_t)pitch_bytes ? (size_t)cw * bpp : (size_t)pitch_bytes;
-        hipError_t e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, row_bytes, (size_t)drows, hipMemcpyDeviceToHost, ctx->stream);
-        { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
-        if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+        rc = copy_rows_back(ctx, host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, row_bytes, (size_t)drows, false);
     } else (void)hipStreamSynchronize(ctx->stream);
     if (blk) jda_pool_free(ctx, blk);
     jda_pool_free(ctx, dout);
@@ -1141,6 +1178,105 @@ static int32_t jda_onecall_prepare_flags(int32_t len)
     return len >= dev_from ? JDA_PREPARE_DEVICE_PRESCAN : 0;
 }
 
+// ---- the frame of the one calls: ONE file prepared, uploaded, decoded onto a canvas from the pool, released.  What a
+// call keeps between those steps is in `onecall`; the entry points call oc_open, oc_geometry, oc_upload, oc_plan, oc_run and oc_close in
+// that order, with their own checks, surfaces, uploads and launches between them -- what reaches the context's stream, and in which order,
+// is read off each entry point's own body.
+struct onecall {
+    jda_ctx *ctx; jda_image *img; jda_dev_image *dimg;
+    uint8_t *dsurf; jda_batch *b;                // the pool block (the canvas, the caller's surfaces behind it) and the launch plan
+    jda_image_info I;                            // (by value: the image is freed as soon as it is uploaded)
+    int32_t pixel_type, options;
+    int bpp, ow, oh, cw, ch, mw, mh, cpitch;     // mw x mh: the MCU in canvas pixels
+    size_t cbytes;
+    uint32_t nok; bool complete;
+    jda_output C, S;                             // the canvas, and its visible rectangle
+    double t_mark;
+};
+static bool oc_tracing() { static const bool on = JDA_LAB_ENV("JDA_ONECALL_TRACE") != NULL; return on; }       // stage timings on stderr (diagnostics)
+#define JDA_OC_MARK(F, what) do { if (oc_tracing()) { const double t_ = now_ms(); fprintf(stderr, "jda_decode_to_host: %-24s %7.3f ms\n", what, t_ - (F).t_mark); (F).t_mark = t_; } } while (0)
+// The host's half.  The image stays open: the entry point checks its own parameters against F.I and the geometry and, where it refuses,
+// frees F.img and returns -- nothing has been uploaded or launched by then.
+static int oc_open(onecall &F, jda_ctx *ctx, const uint8_t *jpeg, int32_t len)
+{
+    memset(&F, 0, sizeof(F));
+    F.ctx = ctx;
+    F.t_mark = oc_tracing() ? now_ms() : 0.0;
+    (void)hipSetDevice(ctx->device);
+    int32_t err = JDA_SUCCESS;
+    F.img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
+    if (!F.img) return err;
+    F.I = *jda_image_get_info(F.img);
+    return JDA_SUCCESS;
+}
+static int oc_geometry(onecall &F, int32_t pixel_type, int32_t options)
+{
+    F.pixel_type = pixel_type; F.options = options;
+    const int rc = jda_output_geometry(&F.I, pixel_type, options, &F.bpp, &F.ow, &F.oh, &F.cw, &F.ch);
+    if (rc != JDA_SUCCESS) return rc;
+    F.mw = F.cw / (F.I.mcus_x ? F.I.mcus_x : 1); F.mh = F.ch / (F.I.mcus_y ? F.I.mcus_y : 1);
+    F.cpitch = (int)align16((size_t)F.cw * F.bpp); F.cbytes = (size_t)F.cpitch * F.ch;
+    JDA_OC_MARK(F, "prepare (host)");
+    return JDA_SUCCESS;
+}
+// The file goes up and the host image goes away; a pool block of surf_bytes (F.cbytes and what the caller wants behind the canvas) with the
+// canvas C at its head, S the canvas's visible rectangle.  The index is read only AFTER the upload: where the device makes it
+// (JDA_PREPARE_DEVICE_PRESCAN) it exists, and a bad MCU is known, only then.  On failure nothing is left to release.
+static int oc_upload(onecall &F, size_t surf_bytes, int32_t *mcus_decoded)
+{
+    int32_t err = JDA_SUCCESS;
+    F.dimg = jda_upload(F.ctx, F.img, &err);
+    JDA_OC_MARK(F, "upload + device pre-scan");
+    jda_image_block_index(F.img, &F.nok);
+    F.complete = F.nok == (uint32_t)(F.I.mcus_x * F.I.mcus_y);
+    if (mcus_decoded) *mcus_decoded = (int32_t)F.nok;
+    jda_image_free(F.img);
+    F.img = NULL;
+    if (!F.dimg) return err;
+    if (jda_pool_alloc(F.ctx, (void **)&F.dsurf, surf_bytes) != hipSuccess) { jda_dev_image_free(F.ctx, F.dimg); return JDA_ERROR_MEMORY; }
+    F.C.pixels = F.dsurf; F.C.pitch_bytes = F.cpitch; F.C.width_px = F.cw; F.C.rows = F.ch;
+    F.S = F.C; F.S.width_px = F.ow; F.S.rows = F.oh;
+    return JDA_SUCCESS;
+}
+// the MCUs that hold the canvas pixels reads = { x0, y0, x1, y1 } -> mcu_rect; true: every MCU of the image
+static bool oc_mcu_rect(const onecall &F, const int32_t *reads, int32_t *mcu_rect)
+{
+    mcu_rect[0] = reads[0] / F.mw; mcu_rect[1] = reads[1] / F.mh;
+    mcu_rect[2] = std::min((reads[2] + F.mw - 1) / F.mw, F.I.mcus_x); mcu_rect[3] = std::min((reads[3] + F.mh - 1) / F.mh, F.I.mcus_y);
+    return mcu_rect[0] == 0 && mcu_rect[1] == 0 && mcu_rect[2] == F.I.mcus_x && mcu_rect[3] == F.I.mcus_y;
+}
+// the launch plan over the canvas C: an MCU rectangle or all of the image (NULL), strip-major (strip_mcus) or row-major (NULL)
+static int oc_plan(onecall &F, const int32_t *mcu_rect, const int32_t *strip_mcus, int32_t *tiles)
+{
+    int32_t err = JDA_SUCCESS;
+    F.b = jda_batch_create_strips(F.ctx, 1, &F.dimg, &F.C, &F.pixel_type, &F.options, mcu_rect, strip_mcus, &err);
+    if (F.b && tiles) { tiles[0] = (int32_t)F.b->stats.tiles; tiles[1] = (int32_t)F.b->stats.tiles_whole_images; }
+    JDA_OC_MARK(F, "surface + launch plan");
+    return err;
+}
+// The decode.  What a bad stream does not reach reads zero: clear_bytes of the block from clear_at on are cleared in front of the decode --
+// where the stream has a bad MCU, or (also_complete) whatever it has.
+static int oc_run(onecall &F, size_t clear_at, size_t clear_bytes, bool also_complete)
+{
+    if ((!F.complete || also_complete) && clear_bytes) (void)hipMemsetAsync(F.dsurf + clear_at, 0, clear_bytes, F.ctx->stream);
+    return jda_batch_decode(F.ctx, F.b);
+}
+// The end of every call that got through oc_upload.  A step that failed behind oc_plan may have left work on the stream that reads or
+// writes the blocks going back to the pool (plan_block: the post-process's, may be NULL): the stream is drained first.
+static int oc_close(onecall &F, int rc, void *plan_block)
+{
+    if (F.b && rc != JDA_SUCCESS) (void)hipStreamSynchronize(F.ctx->stream);
+    JDA_OC_MARK(F, "decode + copy back");
+    jda_batch_destroy(F.ctx, F.b);
+    jda_pool_free(F.ctx, plan_block);
+    jda_pool_free(F.ctx, F.dsurf);
+    jda_dev_image_free(F.ctx, F.dimg);
+    JDA_OC_MARK(F, "release");
+    if (rc == JDA_SUCCESS && !F.complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
+    return rc;
+}
+#undef JDA_OC_MARK
+
 // The whole image as the reference's JPEGDRAW strips (jpeg.inl:5300-5336): strip_mcus MCUs wide, one MCU row high, in raster order, every
 // strip's pixels contiguous -- what JPEGDEC::decode hands to the draw callback without touching a pixel (a strip of a row-major canvas is
 // a few hundred bytes from each of 16 rows a pitch apart: 8,192 strips of a 4096x4096 image were 1.5 ms of small strided copies).
@@ -1150,63 +1286,41 @@ int jda_decode_to_host_strips(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
     if (mcus_decoded) *mcus_decoded = 0;
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (!jpeg || !host_pixels || strip_mcus <= 0) return JDA_INVALID_PARAMETER;
-    (void)hipSetDevice(ctx->device);
-    int32_t err = JDA_SUCCESS;
-    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
-    if (!img) return err;
-    const jda_image_info I = *jda_image_get_info(img);
-    int bpp, ow, oh, cw, ch;
-    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
-    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
-    const int mw = cw / I.mcus_x, mh = ch / I.mcus_y;
-    const int n_sx = (I.mcus_x + strip_mcus - 1) / strip_mcus;
-    const size_t strip_bytes = (size_t)strip_mcus * mw * mh * bpp, row_bytes = (size_t)n_sx * strip_bytes, total = row_bytes * I.mcus_y;
-    if (host_bytes < total) { jda_image_free(img); return JDA_INVALID_PARAMETER; }
-    jda_dev_image *dimg = jda_upload(ctx, img, &err);
-    uint32_t nok = 0;
-    jda_image_block_index(img, &nok);
-    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
-    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
-    jda_image_free(img);
-    if (!dimg) return err;
-    void *dout = NULL;
-    const int dpitch = (int)align16((size_t)cw * bpp);
-    const size_t surf = std::max(total, (size_t)dpitch * ch) + 256;
-    if (jda_pool_alloc(ctx, &dout, surf) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
-    jda_output O;
-    O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = cw; O.rows = ch;
-    jda_batch *b = jda_batch_create_strips(ctx, 1, &dimg, &O, &pixel_type, &options, NULL, &strip_mcus, &err);
-    rc = err;
-    if (b) {
-        if (!complete) (void)hipMemsetAsync(dout, 0, total, ctx->stream);       // (callback mode: what a bad stream does not reach reads zero)
-        rc = jda_batch_decode(ctx, b);
-        if (rc == JDA_SUCCESS) {
-            int nb = (band_ready && n_bands > 1) ? (n_bands > JDA_MAX_BANDS ? JDA_MAX_BANDS : n_bands) : 1;
-            if (nb > I.mcus_y) nb = I.mcus_y;
-            const int per = (I.mcus_y + nb - 1) / nb;                            // MCU rows a band
-            hipError_t e = hipSuccess;
-            int made = 0;
-            for (int k = 0; k < nb && e == hipSuccess; k++) {
-                const int y0 = k * per, y1 = std::min(I.mcus_y, y0 + per);
-                if (y0 >= y1) break;
-                if (!ctx->ev_band[k]) e = hipEventCreateWithFlags(&ctx->ev_band[k], hipEventDisableTiming);
-                if (e == hipSuccess) e = hipMemcpyAsync((uint8_t *)host_pixels + (size_t)y0 * row_bytes, (uint8_t *)dout + (size_t)y0 * row_bytes, (size_t)(y1 - y0) * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipEventRecord(ctx->ev_band[k], ctx->stream);
-                if (e == hipSuccess) made++;
-            }
-            for (int k = 0; k < made && e == hipSuccess; k++) {
-                e = hipEventSynchronize(ctx->ev_band[k]);
-                if (e == hipSuccess && band_ready) (*band_ready)(user, k * per * mh, std::min(I.mcus_y, (k + 1) * per) * mh);
-            }
-            { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
-            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+    onecall F;
+    int rc = oc_open(F, ctx, jpeg, len);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = oc_geometry(F, pixel_type, options);
+    const jda_image_info &I = F.I;
+    const int mh = F.mh, n_sx = (I.mcus_x + strip_mcus - 1) / strip_mcus;
+    const size_t strip_bytes = (size_t)strip_mcus * F.mw * mh * F.bpp, row_bytes = (size_t)n_sx * strip_bytes, total = row_bytes * I.mcus_y;
+    if (rc == JDA_SUCCESS && host_bytes < total) rc = JDA_INVALID_PARAMETER;
+    if (rc != JDA_SUCCESS) { jda_image_free(F.img); return rc; }
+    rc = oc_upload(F, std::max(total, F.cbytes) + 256, mcus_decoded);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = oc_plan(F, NULL, &strip_mcus, NULL);
+    if (rc == JDA_SUCCESS) rc = oc_run(F, 0, total, false);                      // (callback mode: what a bad stream does not reach reads zero)
+    if (rc == JDA_SUCCESS) {
+        int nb = (band_ready && n_bands > 1) ? (n_bands > JDA_MAX_BANDS ? JDA_MAX_BANDS : n_bands) : 1;
+        if (nb > I.mcus_y) nb = I.mcus_y;
+        const int per = (I.mcus_y + nb - 1) / nb;                                // MCU rows a band
+        hipError_t e = hipSuccess;
+        int made = 0;
+        for (int k = 0; k < nb && e == hipSuccess; k++) {
+            const int y0 = k * per, y1 = std::min(I.mcus_y, y0 + per);
+            if (y0 >= y1) break;
+            if (!ctx->ev_band[k]) e = hipEventCreateWithFlags(&ctx->ev_band[k], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipMemcpyAsync((uint8_t *)host_pixels + (size_t)y0 * row_bytes, F.dsurf + (size_t)y0 * row_bytes, (size_t)(y1 - y0) * row_bytes, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipEventRecord(ctx->ev_band[k], ctx->stream);
+            if (e == hipSuccess) made++;
         }
-        jda_batch_destroy(ctx, b);
+        for (int k = 0; k < made && e == hipSuccess; k++) {
+            e = hipEventSynchronize(ctx->ev_band[k]);
+            if (e == hipSuccess && band_ready) (*band_ready)(user, k * per * mh, std::min(I.mcus_y, (k + 1) * per) * mh);
+        }
+        { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+        if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
     }
-    jda_pool_free(ctx, dout);
-    jda_dev_image_free(ctx, dimg);
-    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
-    return rc;
+    return oc_close(F, rc, NULL);
 }
 
 int jda_decode_to_host_bands(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *mcu_rect,
@@ -1216,101 +1330,63 @@ int jda_decode_to_host_bands(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int
     if (mcus_decoded) *mcus_decoded = 0;
     if (tiles) tiles[0] = tiles[1] = 0;
     if (!ctx) return JDA_ERROR_NO_DEVICE;
-    int32_t err = JDA_SUCCESS;
-    static const bool trace = JDA_LAB_ENV("JDA_ONECALL_TRACE") != NULL;       // stage timings on stderr (diagnostics)
-    double t_mark = trace ? now_ms() : 0.0;
-#define JDA_OC_MARK(what) do { if (trace) { const double t_ = now_ms(); fprintf(stderr, "jda_decode_to_host: %-24s %7.3f ms\n", what, t_ - t_mark); t_mark = t_; } } while (0)
-    const int32_t prep_flags = jda_onecall_prepare_flags(len);
-    jda_image *img = jda_prepare_ex(jpeg, len, prep_flags, &err);
-    if (!img) return err;
-    const jda_image_info I = *jda_image_get_info(img);       // (by value: the image is freed as soon as it is uploaded)
-    int bpp, ow, oh, cw, ch;
-    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
-    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
-    const int dpitch = (int)align16((size_t)cw * bpp);
-    const int drows = rows < ch ? rows : ch;
-    JDA_OC_MARK("prepare (host)");
-    jda_dev_image *dimg = jda_upload(ctx, img, &err);
-    JDA_OC_MARK("upload + device pre-scan");
-    uint32_t nok = 0;
-    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
-    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
-    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
-    jda_image_free(img);
-    if (!dimg) return err;
-    void *dout = NULL;
-    if (jda_pool_alloc(ctx, &dout, (size_t)dpitch * ch) != hipSuccess) dout = NULL;
-    if (!dout) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
-    jda_output O;
-    O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = cw; O.rows = drows;
-    jda_batch *b = jda_batch_create_rect(ctx, 1, &dimg, &O, &pixel_type, &options, mcu_rect, &err);
-    rc = err;
-    JDA_OC_MARK("surface + launch plan");
-    if (b) {
-        if (tiles) { tiles[0] = (int32_t)b->stats.tiles; tiles[1] = (int32_t)b->stats.tiles_whole_images; }
-        // only the MCU rows of the rectangle are decoded, zeroed where nothing is written, and copied back
-        int r0 = 0, r1 = drows;
-        if (mcu_rect) {
-            const int mh_out = ch / (I.mcus_y ? I.mcus_y : 1);
-            r0 = std::max(0, std::min(drows, mcu_rect[1] * mh_out)); r1 = std::max(r0, std::min(drows, mcu_rect[3] * mh_out));
+    onecall F;
+    int rc = oc_open(F, ctx, jpeg, len);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = oc_geometry(F, pixel_type, options);
+    if (rc != JDA_SUCCESS) { jda_image_free(F.img); return rc; }
+    rc = oc_upload(F, F.cbytes, mcus_decoded);
+    if (rc != JDA_SUCCESS) return rc;
+    const jda_image_info &I = F.I;
+    const int dpitch = F.cpitch, mh_out = F.mh;
+    const int drows = rows < F.ch ? rows : F.ch;
+    const size_t row_bytes = (size_t)F.cw * F.bpp < (size_t)pitch_bytes ? (size_t)F.cw * F.bpp : (size_t)pitch_bytes;
+    uint8_t *const dout = F.dsurf;
+    F.C.rows = drows;
+    // only the MCU rows of the rectangle are decoded, zeroed where nothing is written, and copied back
+    int r0 = 0, r1 = drows;
+    if (mcu_rect) { r0 = std::max(0, std::min(drows, mcu_rect[1] * mh_out)); r1 = std::max(r0, std::min(drows, mcu_rect[3] * mh_out)); }
+    rc = oc_plan(F, mcu_rect, NULL, tiles);
+    if (rc == JDA_SUCCESS) rc = oc_run(F, (size_t)r0 * dpitch, r1 > r0 ? (size_t)dpitch * (r1 - r0) : 0, mcu_rect != NULL);
+    if (rc == JDA_SUCCESS && !F.complete && (flags & JDA_TO_HOST_KEEP_UNDECODED) && !mcu_rect) {
+        // the reference returns at the bad MCU and leaves the rest of the caller's buffer alone (jpeg.inl:5354-5356): copy back the
+        // whole MCU rows in front of it and, of its own row, the MCUs in front of it -- nothing else of the host buffer is touched
+        const int full = (int)(F.nok / (uint32_t)I.mcus_x), part = (int)(F.nok % (uint32_t)I.mcus_x);
+        const int rf = std::min(drows, full * mh_out), rp = std::min(drows, (full + 1) * mh_out);
+        hipError_t e = hipSuccess;
+        if (rf > 0) e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, row_bytes, (size_t)rf, hipMemcpyDeviceToHost, ctx->stream);
+        const size_t part_bytes = std::min(row_bytes, (size_t)part * F.mw * F.bpp);
+        if (e == hipSuccess && part_bytes && rp > rf)
+            e = hipMemcpy2DAsync((uint8_t *)host_pixels + (size_t)rf * pitch_bytes, (size_t)pitch_bytes, dout + (size_t)rf * dpitch, (size_t)dpitch, part_bytes, (size_t)(rp - rf), hipMemcpyDeviceToHost, ctx->stream);
+        { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+        if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+    } else if (rc == JDA_SUCCESS && r1 > r0 && band_ready && n_bands > 1) {
+        // the copy back in bands of whole MCU rows, the caller told as each one lands: what it does with band k (the class replays its
+        // draw callbacks) runs while band k + 1 is still on the bus
+        int nb = n_bands > JDA_MAX_BANDS ? JDA_MAX_BANDS : n_bands;
+        const int mrows = (r1 - r0 + mh_out - 1) / mh_out;
+        if (nb > mrows) nb = mrows;
+        const int per = ((mrows + nb - 1) / nb) * mh_out;
+        hipError_t e = hipSuccess;
+        int made = 0;
+        for (int k = 0; k < nb && e == hipSuccess; k++) {
+            const int b0 = r0 + k * per, b1 = std::min(r1, b0 + per);
+            if (b0 >= b1) break;
+            if (!ctx->ev_band[k]) e = hipEventCreateWithFlags(&ctx->ev_band[k], hipEventDisableTiming);
+            if (e == hipSuccess) e = hipMemcpy2DAsync((uint8_t *)host_pixels + (size_t)b0 * pitch_bytes, (size_t)pitch_bytes, dout + (size_t)b0 * dpitch, (size_t)dpitch, row_bytes, (size_t)(b1 - b0), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipEventRecord(ctx->ev_band[k], ctx->stream);
+            if (e == hipSuccess) made++;
         }
-        if ((!complete || mcu_rect) && r1 > r0) (void)hipMemsetAsync((uint8_t *)dout + (size_t)r0 * dpitch, 0, (size_t)dpitch * (r1 - r0), ctx->stream);
-        rc = jda_batch_decode(ctx, b);
-        if (rc == JDA_SUCCESS && !complete && (flags & JDA_TO_HOST_KEEP_UNDECODED) && !mcu_rect) {
-            // the reference returns at the bad MCU and leaves the rest of the caller's buffer alone (jpeg.inl:5354-5356): copy back the
-            // whole MCU rows in front of it and, of its own row, the MCUs in front of it -- nothing else of the host buffer is touched
-            const int mh_out = ch / (I.mcus_y ? I.mcus_y : 1), mw_out = cw / (I.mcus_x ? I.mcus_x : 1);
-            const int full = (int)(nok / (uint32_t)I.mcus_x), part = (int)(nok % (uint32_t)I.mcus_x);
-            const int rf = std::min(drows, full * mh_out), rp = std::min(drows, (full + 1) * mh_out);
-            const size_t row_bytes = (size_t)cw * bpp < (size_t)pitch_bytes ? (size_t)cw * bpp : (size_t)pitch_bytes;
-            hipError_t e = hipSuccess;
-            if (rf > 0) e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, row_bytes, (size_t)rf, hipMemcpyDeviceToHost, ctx->stream);
-            const size_t part_bytes = std::min(row_bytes, (size_t)part * mw_out * bpp);
-            if (e == hipSuccess && part_bytes && rp > rf)
-                e = hipMemcpy2DAsync((uint8_t *)host_pixels + (size_t)rf * pitch_bytes, (size_t)pitch_bytes, (uint8_t *)dout + (size_t)rf * dpitch, (size_t)dpitch, part_bytes, (size_t)(rp - rf), hipMemcpyDeviceToHost, ctx->stream);
-            { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
-            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
-        } else if (rc == JDA_SUCCESS && r1 > r0 && band_ready && n_bands > 1) {
-            // the copy back in bands of whole MCU rows, the caller told as each one lands: what it does with band k (the class replays its
-            // draw callbacks) runs while band k + 1 is still on the bus
-            const int mh_out = ch / (I.mcus_y ? I.mcus_y : 1);
-            int nb = n_bands > JDA_MAX_BANDS ? JDA_MAX_BANDS : n_bands;
-            const int mrows = (r1 - r0 + mh_out - 1) / mh_out;
-            if (nb > mrows) nb = mrows;
-            const int per = ((mrows + nb - 1) / nb) * mh_out;
-            const size_t row_bytes = (size_t)cw * bpp < (size_t)pitch_bytes ? (size_t)cw * bpp : (size_t)pitch_bytes;
-            hipError_t e = hipSuccess;
-            int made = 0;
-            for (int k = 0; k < nb && e == hipSuccess; k++) {
-                const int b0 = r0 + k * per, b1 = std::min(r1, b0 + per);
-                if (b0 >= b1) break;
-                if (!ctx->ev_band[k]) e = hipEventCreateWithFlags(&ctx->ev_band[k], hipEventDisableTiming);
-                if (e == hipSuccess) e = hipMemcpy2DAsync((uint8_t *)host_pixels + (size_t)b0 * pitch_bytes, (size_t)pitch_bytes, (uint8_t *)dout + (size_t)b0 * dpitch, (size_t)dpitch, row_bytes, (size_t)(b1 - b0), hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipEventRecord(ctx->ev_band[k], ctx->stream);
-                if (e == hipSuccess) made++;
-            }
-            for (int k = 0; k < made && e == hipSuccess; k++) {
-                e = hipEventSynchronize(ctx->ev_band[k]);
-                if (e == hipSuccess) (*band_ready)(user, r0 + k * per, std::min(r1, r0 + (k + 1) * per));
-            }
-            // (also after an error: copies queued before it may still be writing the caller's buffer, and the surface goes back to the pool)
-            { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
-            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
-        } else if (rc == JDA_SUCCESS && r1 > r0) {
-            const size_t row_bytes = (size_t)cw * bpp < (size_t)pitch_bytes ? (size_t)cw * bpp : (size_t)pitch_bytes;
-            hipError_t e = hipMemcpy2DAsync((uint8_t *)host_pixels + (size_t)r0 * pitch_bytes, (size_t)pitch_bytes, (uint8_t *)dout + (size_t)r0 * dpitch, (size_t)dpitch, row_bytes, (size_t)(r1 - r0), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+        for (int k = 0; k < made && e == hipSuccess; k++) {
+            e = hipEventSynchronize(ctx->ev_band[k]);
+            if (e == hipSuccess) (*band_ready)(user, r0 + k * per, std::min(r1, r0 + (k + 1) * per));
         }
-        JDA_OC_MARK("decode + copy back");
-        jda_batch_destroy(ctx, b);
-    }
-    jda_pool_free(ctx, dout);
-    jda_dev_image_free(ctx, dimg);
-    JDA_OC_MARK("release");
-#undef JDA_OC_MARK
-    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
-    return rc;
+        // (also after an error: copies queued before it may still be writing the caller's buffer, and the surface goes back to the pool)
+        { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+        if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+    } else if (rc == JDA_SUCCESS && r1 > r0)
+        rc = copy_rows_back(ctx, (uint8_t *)host_pixels + (size_t)r0 * pitch_bytes, (size_t)pitch_bytes, dout + (size_t)r0 * dpitch, (size_t)dpitch, row_bytes, (size_t)(r1 - r0), false);
+    return oc_close(F, rc, NULL);
 }
 
 // ---- 4 / 2 / 1-bpp output (jda_dither_rows in jda_kernels.hip)
@@ -1362,8 +1438,8 @@ static int dither_launch(jda_ctx *ctx, const dither_plan &plan)
     const hipError_t e = jda_launch_dither((const jda_dither_job *)plan.block, plan.n, plan.max_w, plan.max_h, plan.d_fail, ctx->stream);
     return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_dither_rows");
 }
-// page-locked staging of at least `bytes` (the context's grow-only block; whatever used it before has drained: the stream is synchronised first)
-static uint8_t *dither_staging(jda_ctx *ctx, size_t bytes)
+// the context's grow-only page-locked block, at least `bytes` of it (whatever used it before has drained: the stream is synchronised before it is replaced)
+static uint8_t *ctx_pinned_block(jda_ctx *ctx, size_t bytes)
 {
     if (bytes <= ctx->pinned_cap) return ctx->pinned;
     (void)hipStreamSynchronize(ctx->stream);
@@ -1403,52 +1479,38 @@ int jda_decode_dither_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     const uint32_t bits = dither_bits_of(pixel_type);
     if (!bits || !jpeg || !host_packed) return JDA_INVALID_PARAMETER;
-    (void)hipSetDevice(ctx->device);
-    int32_t err = JDA_SUCCESS;
-    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
-    if (!img) return err;
-    const jda_image_info I = *jda_image_get_info(img);
-    int bpp, ow, oh, cw, ch;
-    int32_t gray_type = JDA_EIGHT_BIT_GRAYSCALE;
-    int rc = jda_output_geometry(&I, gray_type, options, &bpp, &ow, &oh, &cw, &ch);
+    onecall F;
+    int rc = oc_open(F, ctx, jpeg, len);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = oc_geometry(F, JDA_EIGHT_BIT_GRAYSCALE, options);
+    const int cw = F.cw, ch = F.ch;
     int32_t dbits = 0, dpitch = 0;
     int64_t dbytes = 0;
     if (rc == JDA_SUCCESS) rc = jda_dither_geometry(cw, ch, pixel_type, &dbits, &dpitch, &dbytes);
-    if (rc == JDA_SUCCESS && (pitch_bytes < dpitch || I.mcus_y <= 0 || ch % I.mcus_y)) rc = JDA_INVALID_PARAMETER;
-    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
-    jda_dev_image *dimg = jda_upload(ctx, img, &err);
-    uint32_t nok = 0;
-    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
-    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
-    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
-    jda_image_free(img);
-    if (!dimg) return err;
+    if (rc == JDA_SUCCESS && (pitch_bytes < dpitch || F.I.mcus_y <= 0 || ch % F.I.mcus_y)) rc = JDA_INVALID_PARAMETER;
+    if (rc != JDA_SUCCESS) { jda_image_free(F.img); return rc; }
     // (the packed surface at the caller's own pitch where the kernel's dword stores allow it: the copy back then lands where it belongs)
-    const int gpitch = (int)align16((size_t)cw), ppitch = (pitch_bytes == dpitch && !(dpitch & 3)) ? dpitch : (int)align16((size_t)dpitch);
-    const size_t gbytes = (size_t)gpitch * ch;
-    uint8_t *dsurf = NULL;                              // the gray canvas, the packed rows behind it
-    if (jda_pool_alloc(ctx, (void **)&dsurf, gbytes + (size_t)ppitch * ch) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
-    jda_output G, P;
-    G.pixels = dsurf; G.pitch_bytes = gpitch; G.width_px = cw; G.rows = ch;
-    P.pixels = dsurf + gbytes; P.pitch_bytes = ppitch; P.width_px = cw; P.rows = ch;
-    jda_batch *b = jda_batch_create(ctx, 1, &dimg, &G, &gray_type, &options, &err);
-    rc = err;
-    if (b) {
+    const int ppitch = (pitch_bytes == dpitch && !(dpitch & 3)) ? dpitch : (int)align16((size_t)dpitch);
+    rc = oc_upload(F, F.cbytes + (size_t)ppitch * ch, mcus_decoded);              // the gray canvas, the packed rows behind it
+    if (rc != JDA_SUCCESS) return rc;
+    jda_output P;
+    P.pixels = F.dsurf + F.cbytes; P.pitch_bytes = ppitch; P.width_px = cw; P.rows = ch;
+    dither_plan plan;
+    plan.block = NULL;
+    rc = oc_plan(F, NULL, NULL, NULL);
+    if (rc == JDA_SUCCESS) {
         // everything that has to wait for the host -- the job record, the staging block -- first; then decode, dither and the copy back are
         // queued back to back
-        dither_plan plan;
         uint32_t fail = 0;
-        const int32_t strip = ch / I.mcus_y;            // the rows of one MCU row, as scaled (jpeg.inl:5048-5049, :5310)
+        const int32_t strip = F.mh;                     // the rows of one MCU row, as scaled (jpeg.inl:5048-5049, :5310)
         const int drows = rows < ch ? rows : ch;
-        rc = dither_upload(ctx, 1, &G, &strip, &pixel_type, &seed, &P, &plan);
+        rc = dither_upload(ctx, 1, &F.C, &strip, &pixel_type, &seed, &P, &plan);
         // the packed rows come back as ONE copy at the device pitch into page-locked memory and are brought to the caller's pitch here: a
         // 2-D copy of thousands of rows of an odd width into pageable memory goes row by row (3596 x 2840 at 1 bpp: 450-byte rows, +25 ms)
         uint8_t *stage = NULL;
-        if (rc == JDA_SUCCESS && drows > 0 && pitch_bytes != ppitch) { stage = dither_staging(ctx, (size_t)ppitch * drows); if (!stage) rc = JDA_ERROR_MEMORY; }
-        if (rc == JDA_SUCCESS && !complete) (void)hipMemsetAsync(dsurf, 0, gbytes, ctx->stream);
-        if (rc == JDA_SUCCESS) rc = jda_batch_decode(ctx, b);
+        if (rc == JDA_SUCCESS && drows > 0 && pitch_bytes != ppitch) { stage = ctx_pinned_block(ctx, (size_t)ppitch * drows); if (!stage) rc = JDA_ERROR_MEMORY; }
+        if (rc == JDA_SUCCESS) rc = oc_run(F, 0, F.cbytes, false);
         if (rc == JDA_SUCCESS) rc = dither_launch(ctx, plan);
-        void *blk = plan.block;
         if (rc == JDA_SUCCESS) {
             hipError_t e = hipSuccess;
             if (drows > 0) e = hipMemcpyAsync(stage ? (void *)stage : host_packed, P.pixels, (size_t)ppitch * drows, hipMemcpyDeviceToHost, ctx->stream);
@@ -1458,14 +1520,9 @@ int jda_decode_dither_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
                 for (int r = 0; r < drows; r++) memcpy((uint8_t *)host_packed + (size_t)r * pitch_bytes, stage + (size_t)r * ppitch, (size_t)dpitch);
             if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
             else if (fail) { snprintf(ctx->last_error, sizeof(ctx->last_error), "jda_dither_rows: a wavefront gave up waiting for the rows above it"); rc = JDA_ERROR_HIP; }
-        } else (void)hipStreamSynchronize(ctx->stream);
-        if (blk) jda_pool_free(ctx, blk);
-        jda_batch_destroy(ctx, b);
+        }
     }
-    jda_pool_free(ctx, dsurf);
-    jda_dev_image_free(ctx, dimg);
-    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
-    return rc;
+    return oc_close(F, rc, plan.block);
 }
 
 // ---- EXIF orientation (jda_orient_tiles in jda_kernels.hip; the permutation and its tiles: jda_device_core.h)
@@ -1538,11 +1595,7 @@ int jda_orient_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t 
     orient_plan plan;
     int rc = orient_upload(ctx, n, src, bytes_per_pixel, orientations, dst, &plan);
     if (rc != JDA_SUCCESS) return rc;
-    rc = orient_launch(ctx, plan);
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    jda_pool_free(ctx, plan.block);
-    if (rc != JDA_SUCCESS) return rc;
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_orient_surfaces");
+    return finish_surfaces(ctx, orient_launch(ctx, plan), plan.block, "jda_orient_surfaces");
 }
 
 int jda_decode_to_host_oriented(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, int32_t orientation,
@@ -1551,59 +1604,30 @@ int jda_decode_to_host_oriented(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, 
     if (mcus_decoded) *mcus_decoded = 0;
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (!jpeg || !host_pixels || orientation > 8 || pixel_type < 0 || pixel_type > JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
-    (void)hipSetDevice(ctx->device);
-    int32_t err = JDA_SUCCESS;
-    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
-    if (!img) return err;
-    const jda_image_info I = *jda_image_get_info(img);
-    int bpp, ow, oh, cw, ch, tw = 0, th = 0;
-    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
-    if (rc == JDA_SUCCESS) rc = jda_oriented_geometry(&I, pixel_type, options, orientation, NULL, &tw, &th, NULL);
-    if (rc == JDA_SUCCESS && (ow > cw || oh > ch || pitch_bytes < tw * bpp || rows < th)) rc = JDA_INVALID_PARAMETER;
-    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
-    int32_t o = orientation < 0 ? I.orientation : orientation;
+    onecall F;
+    int rc = oc_open(F, ctx, jpeg, len);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = oc_geometry(F, pixel_type, options);
+    int tw = 0, th = 0;
+    if (rc == JDA_SUCCESS) rc = jda_oriented_geometry(&F.I, pixel_type, options, orientation, NULL, &tw, &th, NULL);
+    if (rc == JDA_SUCCESS && (F.ow > F.cw || F.oh > F.ch || pitch_bytes < tw * F.bpp || rows < th)) rc = JDA_INVALID_PARAMETER;
+    if (rc != JDA_SUCCESS) { jda_image_free(F.img); return rc; }
+    int32_t o = orientation < 0 ? F.I.orientation : orientation;
     if (o < 2 || o > 8) o = 0;                          // "as it is": the visible rectangle goes back from the canvas itself
-    jda_dev_image *dimg = jda_upload(ctx, img, &err);
-    uint32_t nok = 0;
-    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
-    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
-    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
-    jda_image_free(img);
-    if (!dimg) return err;
-    const int cpitch = (int)align16((size_t)cw * bpp), opitch = (int)align16((size_t)tw * bpp);
-    const size_t cbytes = (size_t)cpitch * ch;
-    uint8_t *dsurf = NULL;                              // the decoded canvas, the oriented surface behind it
-    if (jda_pool_alloc(ctx, (void **)&dsurf, cbytes + (o ? (size_t)opitch * th : 0)) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
-    jda_output C, S, D;
-    C.pixels = dsurf; C.pitch_bytes = cpitch; C.width_px = cw; C.rows = ch;
-    S = C; S.width_px = ow; S.rows = oh;                // the visible rectangle of the canvas
-    D.pixels = dsurf + cbytes; D.pitch_bytes = opitch; D.width_px = tw; D.rows = th;
-    jda_batch *b = jda_batch_create(ctx, 1, &dimg, &C, &pixel_type, &options, &err);
-    rc = err;
-    if (b) {
-        // what has to wait for the host -- the job record -- first; then decode, orient and the copy back are queued back to back
-        orient_plan plan;
-        plan.block = NULL;
-        if (o) rc = orient_upload(ctx, 1, &S, bpp, &o, &D, &plan);
-        if (rc == JDA_SUCCESS && !complete) (void)hipMemsetAsync(dsurf, 0, cbytes, ctx->stream);       // (the MCUs a bad stream does not reach are zeros before they are turned)
-        if (rc == JDA_SUCCESS) rc = jda_batch_decode(ctx, b);
-        if (rc == JDA_SUCCESS && o) rc = orient_launch(ctx, plan);
-        if (rc == JDA_SUCCESS) {
-            const uint8_t *from = o ? (const uint8_t *)D.pixels : dsurf;
-            const size_t fpitch = (size_t)(o ? opitch : cpitch), row_bytes = (size_t)tw * bpp;
-            hipError_t e;
-            if ((size_t)pitch_bytes == fpitch && row_bytes == fpitch) e = hipMemcpyAsync(host_pixels, from, row_bytes * (size_t)th, hipMemcpyDeviceToHost, ctx->stream);      // (rows without a gap on either side: one piece)
-            else e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, from, fpitch, row_bytes, (size_t)th, hipMemcpyDeviceToHost, ctx->stream);
-            { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
-            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
-        } else (void)hipStreamSynchronize(ctx->stream);
-        if (plan.block) jda_pool_free(ctx, plan.block);
-        jda_batch_destroy(ctx, b);
-    }
-    jda_pool_free(ctx, dsurf);
-    jda_dev_image_free(ctx, dimg);
-    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
-    return rc;
+    const int opitch = (int)align16((size_t)tw * F.bpp);
+    rc = oc_upload(F, F.cbytes + (o ? (size_t)opitch * th : 0), mcus_decoded);    // the decoded canvas, the oriented surface behind it
+    if (rc != JDA_SUCCESS) return rc;
+    jda_output D;
+    D.pixels = F.dsurf + F.cbytes; D.pitch_bytes = opitch; D.width_px = tw; D.rows = th;
+    orient_plan plan;
+    plan.block = NULL;
+    rc = oc_plan(F, NULL, NULL, NULL);
+    // what has to wait for the host -- the job record -- first; then decode, orient and the copy back are queued back to back
+    if (rc == JDA_SUCCESS && o) rc = orient_upload(ctx, 1, &F.S, F.bpp, &o, &D, &plan);
+    if (rc == JDA_SUCCESS) rc = oc_run(F, 0, F.cbytes, false);                    // (the MCUs a bad stream does not reach are zeros before they are turned)
+    if (rc == JDA_SUCCESS && o) rc = orient_launch(ctx, plan);
+    if (rc == JDA_SUCCESS) rc = copy_rows_back(ctx, host_pixels, (size_t)pitch_bytes, o ? D.pixels : F.dsurf, (size_t)(o ? opitch : F.cpitch), (size_t)tw * F.bpp, (size_t)th, true);
+    return oc_close(F, rc, plan.block);
 }
 
 // ---- dense RGB / BGR / planar output (jda_pack_tiles in jda_kernels.hip; runs, vectors and the lane's walk: jda_device_core.h)
@@ -1651,11 +1675,7 @@ int jda_pack_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t sr
     pack_plan plan;
     int rc = pack_upload(ctx, n, src, src_bytes_per_pixel, rects, layout_flags, elem_type, table, dst, &plan);
     if (rc != JDA_SUCCESS) return rc;
-    rc = pack_launch(ctx, plan);
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    jda_pool_free(ctx, plan.block);
-    if (rc != JDA_SUCCESS) return rc;
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_pack_surfaces");
+    return finish_surfaces(ctx, pack_launch(ctx, plan), plan.block, "jda_pack_surfaces");
 }
 
 int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, int32_t layout_flags, int32_t elem_type,
@@ -1666,61 +1686,40 @@ int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
     if (h) *h = 0;
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (!jpeg || !host_out) return JDA_INVALID_PARAMETER;
-    (void)hipSetDevice(ctx->device);
-    int32_t err = JDA_SUCCESS;
-    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
-    if (!img) return err;
-    const jda_image_info I = *jda_image_get_info(img);
-    int32_t pixel_type = (I.ncomp == 1 || (options & JDA_LUMA_ONLY)) ? JDA_EIGHT_BIT_GRAYSCALE : JDA_RGB8888;
-    int bpp, ow, oh, cw, ch;
-    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
+    onecall F;
+    int rc = oc_open(F, ctx, jpeg, len);
+    if (rc != JDA_SUCCESS) return rc;
+    const int32_t pixel_type = (F.I.ncomp == 1 || (options & JDA_LUMA_ONLY)) ? JDA_EIGHT_BIT_GRAYSCALE : JDA_RGB8888;
+    rc = oc_geometry(F, pixel_type, options);
     const uint32_t es = jda_pack_elem_bytes(elem_type), channels = pixel_type == JDA_RGB8888 ? 3u : 1u;
     // (the table is HOST memory here: its alignment does not matter, the device copy's does)
-    if (rc == JDA_SUCCESS) rc = jda_pack_check_format(bpp, layout_flags, elem_type, table ? (const void *)16 : NULL);
-    const size_t dense = rc == JDA_SUCCESS ? jda_pack_bytes(ow, oh, (int32_t)channels, elem_type) : 0;
-    if (rc == JDA_SUCCESS && (ow > cw || oh > ch || out_bytes < dense)) rc = JDA_INVALID_PARAMETER;
-    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
-    if (w) *w = ow;
-    if (h) *h = oh;
-    jda_dev_image *dimg = jda_upload(ctx, img, &err);
-    uint32_t nok = 0;
-    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
-    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
-    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
-    jda_image_free(img);
-    if (!dimg) return err;
-    const int cpitch = (int)align16((size_t)cw * bpp);
-    const size_t cbytes = (size_t)cpitch * ch, tbytes = table ? (size_t)channels * 256u * es : 0;
-    uint8_t *dsurf = NULL;                              // the decoded canvas, the dense result and the table behind it
-    if (jda_pool_alloc(ctx, (void **)&dsurf, cbytes + align16(dense) + tbytes) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
-    uint8_t *ddense = dsurf + cbytes, *dtable = table ? ddense + align16(dense) : NULL;
-    jda_output C, S;
-    C.pixels = dsurf; C.pitch_bytes = cpitch; C.width_px = cw; C.rows = ch;
-    S = C; S.width_px = ow; S.rows = oh;                // the visible rectangle of the canvas
-    jda_batch *b = jda_batch_create(ctx, 1, &dimg, &C, &pixel_type, &options, &err);
-    rc = err;
-    if (b) {
+    if (rc == JDA_SUCCESS) rc = jda_pack_check_format(F.bpp, layout_flags, elem_type, table ? (const void *)16 : NULL);
+    const size_t dense = rc == JDA_SUCCESS ? jda_pack_bytes(F.ow, F.oh, (int32_t)channels, elem_type) : 0;
+    if (rc == JDA_SUCCESS && (F.ow > F.cw || F.oh > F.ch || out_bytes < dense)) rc = JDA_INVALID_PARAMETER;
+    if (rc != JDA_SUCCESS) { jda_image_free(F.img); return rc; }
+    if (w) *w = F.ow;
+    if (h) *h = F.oh;
+    const size_t tbytes = table ? (size_t)channels * 256u * es : 0;
+    rc = oc_upload(F, F.cbytes + align16(dense) + tbytes, mcus_decoded);          // the decoded canvas, the dense result and the table behind it
+    if (rc != JDA_SUCCESS) return rc;
+    uint8_t *ddense = F.dsurf + F.cbytes, *dtable = table ? ddense + align16(dense) : NULL;
+    pack_plan plan;
+    plan.block = NULL;
+    rc = oc_plan(F, NULL, NULL, NULL);
+    if (rc == JDA_SUCCESS) {
         // what has to wait for the host -- the table and the job record -- first; then decode, pack and the copy back are queued back to back
-        pack_plan plan;
-        plan.block = NULL;
         if (table && hipMemcpyAsync(dtable, table, tbytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = JDA_ERROR_HIP;
         void *const dsts[1] = { ddense };
-        if (rc == JDA_SUCCESS) rc = pack_upload(ctx, 1, &S, bpp, NULL, layout_flags, elem_type, dtable, dsts, &plan);
-        if (rc == JDA_SUCCESS && !complete) (void)hipMemsetAsync(dsurf, 0, cbytes, ctx->stream);       // (the MCUs a bad stream does not reach are zeros before they are packed)
-        if (rc == JDA_SUCCESS) rc = jda_batch_decode(ctx, b);
+        if (rc == JDA_SUCCESS) rc = pack_upload(ctx, 1, &F.S, F.bpp, NULL, layout_flags, elem_type, dtable, dsts, &plan);
+        if (rc == JDA_SUCCESS) rc = oc_run(F, 0, F.cbytes, false);                // (the MCUs a bad stream does not reach are zeros before they are packed)
         if (rc == JDA_SUCCESS) rc = pack_launch(ctx, plan);
         if (rc == JDA_SUCCESS) {
             hipError_t e = hipMemcpyAsync(host_out, ddense, dense, hipMemcpyDeviceToHost, ctx->stream);
             { const hipError_t es2 = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es2; }
             if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
-        } else (void)hipStreamSynchronize(ctx->stream);
-        if (plan.block) jda_pool_free(ctx, plan.block);
-        jda_batch_destroy(ctx, b);
+        }
     }
-    jda_pool_free(ctx, dsurf);
-    jda_dev_image_free(ctx, dimg);
-    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
-    return rc;
+    return oc_close(F, rc, plan.block);
 }
 
 // ---- antialiased resize (jda_resize_tiles in jda_kernels.hip; the passes and the tile: jda_device_core.h; checks, taps and tiles: jda_resize_plan.h)
@@ -1770,11 +1769,7 @@ int jda_resize_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32
     resize_plan plan;
     int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL, filter);
     if (rc != JDA_SUCCESS) return rc;
-    rc = resize_launch(ctx, plan);
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    jda_pool_free(ctx, plan.block);
-    if (rc != JDA_SUCCESS) return rc;
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_resize_surfaces");
+    return finish_surfaces(ctx, resize_launch(ctx, plan), plan.block, "jda_resize_surfaces");
 }
 
 int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *rect,
@@ -1792,68 +1787,36 @@ int jda_decode_to_host_resized_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (!jpeg || !host_pixels || out_w <= 0 || out_h <= 0 || filter < 0 || filter >= JDA_RESIZE_FILTERS) return JDA_INVALID_PARAMETER;
     if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
-    (void)hipSetDevice(ctx->device);
-    int32_t err = JDA_SUCCESS;
-    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
-    if (!img) return err;
-    const jda_image_info I = *jda_image_get_info(img);
-    int bpp, ow, oh, cw, ch;
-    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
-    if (rc == JDA_SUCCESS && (ow > cw || oh > ch || (int64_t)pitch_bytes < (int64_t)out_w * bpp || rows < out_h || out_w > (1 << 24) || out_h > (1 << 24))) rc = JDA_INVALID_PARAMETER;
+    onecall F;
+    int rc = oc_open(F, ctx, jpeg, len);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = oc_geometry(F, pixel_type, options);
+    const int bpp = F.bpp, ow = F.ow, oh = F.oh;
+    if (rc == JDA_SUCCESS && (ow > F.cw || oh > F.ch || (int64_t)pitch_bytes < (int64_t)out_w * bpp || rows < out_h || out_w > (1 << 24) || out_h > (1 << 24))) rc = JDA_INVALID_PARAMETER;
     const int32_t whole[4] = { 0, 0, ow, oh };
     const int32_t *box = rect ? rect : whole;
     if (rc == JDA_SUCCESS && (box[0] < 0 || box[1] < 0 || box[2] <= 0 || box[3] <= 0 || (int64_t)box[0] + box[2] > ow || (int64_t)box[1] + box[3] > oh)) rc = JDA_INVALID_PARAMETER;
     // (the limits of the resize before anything is uploaded)
     { uint32_t k; if (rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[0], box[0] + box[2], out_w, &k, filter); if (rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[1], box[1] + box[3], out_h, &k, filter); }
-    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
-    jda_dev_image *dimg = jda_upload(ctx, img, &err);
-    uint32_t nok = 0;
-    jda_image_block_index(img, &nok);                   // (after the upload: a deferred pre-scan has run by now)
-    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
-    if (mcus_decoded) *mcus_decoded = (int32_t)nok;
-    jda_image_free(img);
-    if (!dimg) return err;
-    const int cpitch = (int)align16((size_t)cw * bpp), opitch = (int)align16((size_t)out_w * bpp);
-    const size_t cbytes = (size_t)cpitch * ch;
-    uint8_t *dsurf = NULL;                              // the decoded canvas, the resized surface behind it
-    if (jda_pool_alloc(ctx, (void **)&dsurf, cbytes + (size_t)opitch * out_h) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
-    jda_output C, S, D;
-    C.pixels = dsurf; C.pitch_bytes = cpitch; C.width_px = cw; C.rows = ch;
-    S = C; S.width_px = ow; S.rows = oh;                // the visible rectangle of the canvas
-    D.pixels = dsurf + cbytes; D.pitch_bytes = opitch; D.width_px = out_w; D.rows = out_h;
+    if (rc != JDA_SUCCESS) { jda_image_free(F.img); return rc; }
+    const int opitch = (int)align16((size_t)out_w * bpp);
+    rc = oc_upload(F, F.cbytes + (size_t)opitch * out_h, mcus_decoded);           // the decoded canvas, the resized surface behind it
+    if (rc != JDA_SUCCESS) return rc;
+    jda_output D;
+    D.pixels = F.dsurf + F.cbytes; D.pitch_bytes = opitch; D.width_px = out_w; D.rows = out_h;
     // what has to wait for the host -- the job record and the taps -- first: the taps say which MCUs have to be decoded at all
     resize_plan plan;
-    int32_t reads[4] = { 0, 0, 0, 0 };
-    rc = resize_upload(ctx, 1, &S, bpp, box, &D, &plan, reads, filter);      // (reads: what the chosen filter's taps read, clipped at the visible image)
+    int32_t reads[4] = { 0, 0, 0, 0 }, mcu_rect[4];
+    rc = resize_upload(ctx, 1, &F.S, bpp, box, &D, &plan, reads, filter);        // (reads: what the chosen filter's taps read, clipped at the visible image)
     if (rc == JDA_SUCCESS) {
-        const int mw_out = cw / (I.mcus_x ? I.mcus_x : 1), mh_out = ch / (I.mcus_y ? I.mcus_y : 1);
-        int32_t mcu_rect[4] = { reads[0] / mw_out, reads[1] / mh_out, (reads[2] + mw_out - 1) / mw_out, (reads[3] + mh_out - 1) / mh_out };
-        mcu_rect[2] = std::min(mcu_rect[2], I.mcus_x); mcu_rect[3] = std::min(mcu_rect[3], I.mcus_y);
-        const bool all = mcu_rect[0] == 0 && mcu_rect[1] == 0 && mcu_rect[2] == I.mcus_x && mcu_rect[3] == I.mcus_y;
-        jda_batch *b = jda_batch_create_rect(ctx, 1, &dimg, &C, &pixel_type, &options, all ? NULL : mcu_rect, &err);
-        rc = err;
-        if (b) {
-            if (tiles) { tiles[0] = (int32_t)b->stats.tiles; tiles[1] = (int32_t)b->stats.tiles_whole_images; }
-            // then decode, resize and the copy back are queued back to back (the MCUs a bad stream does not reach are zeros before they are sampled)
-            if (!complete) (void)hipMemsetAsync(dsurf + (size_t)mcu_rect[1] * mh_out * cpitch, 0, (size_t)(mcu_rect[3] - mcu_rect[1]) * mh_out * cpitch, ctx->stream);
-            rc = jda_batch_decode(ctx, b);
-            if (rc == JDA_SUCCESS) rc = resize_launch(ctx, plan);
-            if (rc == JDA_SUCCESS) {
-                const size_t row_bytes = (size_t)out_w * bpp;
-                hipError_t e;
-                if ((size_t)pitch_bytes == (size_t)opitch && row_bytes == (size_t)opitch) e = hipMemcpyAsync(host_pixels, D.pixels, row_bytes * (size_t)out_h, hipMemcpyDeviceToHost, ctx->stream);
-                else e = hipMemcpy2DAsync(host_pixels, (size_t)pitch_bytes, D.pixels, (size_t)opitch, row_bytes, (size_t)out_h, hipMemcpyDeviceToHost, ctx->stream);
-                { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
-                if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
-            } else (void)hipStreamSynchronize(ctx->stream);
-            jda_batch_destroy(ctx, b);
-        }
-        jda_pool_free(ctx, plan.block);
+        const bool all = oc_mcu_rect(F, reads, mcu_rect);
+        rc = oc_plan(F, all ? NULL : mcu_rect, NULL, tiles);
+        // then decode, resize and the copy back are queued back to back (the MCUs a bad stream does not reach are zeros before they are sampled)
+        if (rc == JDA_SUCCESS) rc = oc_run(F, (size_t)mcu_rect[1] * F.mh * F.cpitch, (size_t)(mcu_rect[3] - mcu_rect[1]) * F.mh * F.cpitch, false);
+        if (rc == JDA_SUCCESS) rc = resize_launch(ctx, plan);
+        if (rc == JDA_SUCCESS) rc = copy_rows_back(ctx, host_pixels, (size_t)pitch_bytes, D.pixels, (size_t)opitch, (size_t)out_w * bpp, (size_t)out_h, true);
     }
-    jda_pool_free(ctx, dsurf);
-    jda_dev_image_free(ctx, dimg);
-    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;   // jpeg.inl:5354-5356
-    return rc;
+    return oc_close(F, rc, plan.block);
 }
 
 // ---- baseline encode (jda_encode_* in jda_kernels.hip; the stages: jda_en_* in jda_device_core.h; checks, records and headers: jda_encode_plan.h)
@@ -2041,15 +2004,12 @@ static int transcode_call(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
     if (encode_flags & ~(uint32_t)JDA_ENCODE_OPTIMIZE) return JDA_INVALID_PARAMETER;
     if (progressive && restart_interval != 0) return JDA_INVALID_PARAMETER;
     if (!jpeg || !host_file || !file_bytes || capacity < 0 || out_w <= 0 || out_h <= 0) return JDA_INVALID_PARAMETER;
-    (void)hipSetDevice(ctx->device);
-    int32_t err = JDA_SUCCESS;
-    jda_image *img = jda_prepare_ex(jpeg, len, jda_onecall_prepare_flags(len), &err);
-    if (!img) return err;
-    const jda_image_info I = *jda_image_get_info(img);
-    const int32_t pixel_type = I.ncomp == 1 ? JDA_EIGHT_BIT_GRAYSCALE : JDA_RGB8888;       // a gray file is encoded as it is decoded
-    int bpp, ow, oh, cw, ch;
-    int rc = jda_output_geometry(&I, pixel_type, options, &bpp, &ow, &oh, &cw, &ch);
-    if (rc == JDA_SUCCESS && (ow > cw || oh > ch)) rc = JDA_INVALID_PARAMETER;
+    onecall F;
+    int rc = oc_open(F, ctx, jpeg, len);
+    if (rc != JDA_SUCCESS) return rc;
+    rc = oc_geometry(F, F.I.ncomp == 1 ? JDA_EIGHT_BIT_GRAYSCALE : JDA_RGB8888, options);      // a gray file is encoded as it is decoded
+    const int bpp = F.bpp, ow = F.ow, oh = F.oh;
+    if (rc == JDA_SUCCESS && (ow > F.cw || oh > F.ch)) rc = JDA_INVALID_PARAMETER;
     const int32_t whole[4] = { 0, 0, ow, oh };
     const int32_t *box = rect ? rect : whole;
     if (rc == JDA_SUCCESS && (box[0] < 0 || box[1] < 0 || box[2] <= 0 || box[3] <= 0 || (int64_t)box[0] + box[2] > ow || (int64_t)box[1] + box[3] > oh)) rc = JDA_INVALID_PARAMETER;
@@ -2058,59 +2018,39 @@ static int transcode_call(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
     if (rc == JDA_SUCCESS && (quality < 1 || quality > 100 || (sampling == JDA_ENCODE_GRAY) != (bpp == 1))) rc = JDA_INVALID_PARAMETER;
     const bool resized = rc == JDA_SUCCESS && (out_w != box[2] || out_h != box[3]);
     { uint32_t k; if (resized) rc = jda_resize_axis_ksize(box[0], box[0] + box[2], out_w, &k); if (resized && rc == JDA_SUCCESS) rc = jda_resize_axis_ksize(box[1], box[1] + box[3], out_h, &k); }
-    if (rc != JDA_SUCCESS) { jda_image_free(img); return rc; }
-    jda_dev_image *dimg = jda_upload(ctx, img, &err);
-    uint32_t nok = 0;
-    jda_image_block_index(img, &nok);
-    const bool complete = nok == (uint32_t)(I.mcus_x * I.mcus_y);
-    jda_image_free(img);
-    if (!dimg) return err;
-    const int cpitch = (int)align16((size_t)cw * bpp), opitch = (int)align16((size_t)out_w * bpp);
-    const size_t cbytes = (size_t)cpitch * ch, rbytes = resized ? (size_t)opitch * out_h : 0;
+    if (rc != JDA_SUCCESS) { jda_image_free(F.img); return rc; }
+    const int opitch = (int)align16((size_t)out_w * bpp);
+    const size_t rbytes = resized ? (size_t)opitch * out_h : 0;
     const int64_t fcap = std::min(capacity, bound);                                        // (no file is longer than the bound)
-    uint8_t *dsurf = NULL;                                                                  // the decoded canvas, the resized surface behind it, the file behind that
-    if (jda_pool_alloc(ctx, (void **)&dsurf, cbytes + rbytes + (size_t)fcap + 16) != hipSuccess) { jda_dev_image_free(ctx, dimg); return JDA_ERROR_MEMORY; }
-    jda_output C, S, D;
-    C.pixels = dsurf; C.pitch_bytes = cpitch; C.width_px = cw; C.rows = ch;
-    S = C; S.width_px = ow; S.rows = oh;
-    D.pixels = dsurf + cbytes; D.pitch_bytes = opitch; D.width_px = out_w; D.rows = out_h;
+    rc = oc_upload(F, F.cbytes + rbytes + (size_t)fcap + 16, NULL);                        // the decoded canvas, the resized surface behind it, the file behind that
+    if (rc != JDA_SUCCESS) return rc;
+    jda_output D;
+    D.pixels = F.dsurf + F.cbytes; D.pitch_bytes = opitch; D.width_px = out_w; D.rows = out_h;
     resize_plan plan;
     plan.block = NULL;
-    int32_t reads[4] = { box[0], box[1], box[0] + box[2], box[1] + box[3] };               // without a resize the encoder reads the rectangle itself
-    if (resized) rc = resize_upload(ctx, 1, &S, bpp, box, &D, &plan, reads);
+    int32_t reads[4] = { box[0], box[1], box[0] + box[2], box[1] + box[3] }, mcu_rect[4];  // without a resize the encoder reads the rectangle itself
+    if (resized) rc = resize_upload(ctx, 1, &F.S, bpp, box, &D, &plan, reads);
     if (rc == JDA_SUCCESS) {
-        const int mw_out = cw / (I.mcus_x ? I.mcus_x : 1), mh_out = ch / (I.mcus_y ? I.mcus_y : 1);
-        int32_t mcu_rect[4] = { reads[0] / mw_out, reads[1] / mh_out, (reads[2] + mw_out - 1) / mw_out, (reads[3] + mh_out - 1) / mh_out };
-        mcu_rect[2] = std::min(mcu_rect[2], I.mcus_x); mcu_rect[3] = std::min(mcu_rect[3], I.mcus_y);
-        const bool all = mcu_rect[0] == 0 && mcu_rect[1] == 0 && mcu_rect[2] == I.mcus_x && mcu_rect[3] == I.mcus_y;
-        jda_batch *b = jda_batch_create_rect(ctx, 1, &dimg, &C, &pixel_type, &options, all ? NULL : mcu_rect, &err);
-        rc = err;
-        if (b) {
-            if (!complete) (void)hipMemsetAsync(dsurf + (size_t)mcu_rect[1] * mh_out * cpitch, 0, (size_t)(mcu_rect[3] - mcu_rect[1]) * mh_out * cpitch, ctx->stream);
-            rc = jda_batch_decode(ctx, b);
-            if (rc == JDA_SUCCESS && resized) rc = resize_launch(ctx, plan);
+        const bool all = oc_mcu_rect(F, reads, mcu_rect);
+        rc = oc_plan(F, all ? NULL : mcu_rect, NULL, NULL);
+        if (rc == JDA_SUCCESS) rc = oc_run(F, (size_t)mcu_rect[1] * F.mh * F.cpitch, (size_t)(mcu_rect[3] - mcu_rect[1]) * F.mh * F.cpitch, false);
+        if (rc == JDA_SUCCESS && resized) rc = resize_launch(ctx, plan);
+        if (rc == JDA_SUCCESS) {
+            // the encoder's stages follow on the same stream; its two looks at the sizes are the only waits
+            const jda_encode_job E = { resized ? 0 : box[0], resized ? 0 : box[1], out_w, out_h, sampling, quality, restart_interval, 0 };
+            void *dfile = F.dsurf + F.cbytes + rbytes;
+            int32_t st = JDA_SUCCESS;
+            rc = progressive ? jda_encode_surfaces_progressive(ctx, 1, resized ? &D : &F.S, bpp, &E, &dfile, &fcap, file_bytes, &st)
+                             : jda_encode_surfaces_ex(ctx, 1, resized ? &D : &F.S, bpp, &E, encode_flags ? &encode_flags : NULL, &dfile, &fcap, file_bytes, &st);
+            if (rc == JDA_SUCCESS) rc = st;
             if (rc == JDA_SUCCESS) {
-                // the encoder's stages follow on the same stream; its two looks at the sizes are the only waits
-                const jda_encode_job E = { resized ? 0 : box[0], resized ? 0 : box[1], out_w, out_h, sampling, quality, restart_interval, 0 };
-                void *dfile = dsurf + cbytes + rbytes;
-                int32_t st = JDA_SUCCESS;
-                rc = progressive ? jda_encode_surfaces_progressive(ctx, 1, resized ? &D : &S, bpp, &E, &dfile, &fcap, file_bytes, &st)
-                                 : jda_encode_surfaces_ex(ctx, 1, resized ? &D : &S, bpp, &E, encode_flags ? &encode_flags : NULL, &dfile, &fcap, file_bytes, &st);
-                if (rc == JDA_SUCCESS) rc = st;
-                if (rc == JDA_SUCCESS) {
-                    hipError_t e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);
-                    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
-                    if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
-                }
-            } else (void)hipStreamSynchronize(ctx->stream);
-            jda_batch_destroy(ctx, b);
+                hipError_t e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);
+                { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+                if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+            }
         }
-        if (plan.block) jda_pool_free(ctx, plan.block);
     }
-    jda_pool_free(ctx, dsurf);
-    jda_dev_image_free(ctx, dimg);
-    if (rc == JDA_SUCCESS && !complete) rc = JDA_DECODE_ERROR;
-    return rc;
+    return oc_close(F, rc, plan.block);
 }
 
 // Measuring hook of tools/resize_bench.py (not part of the public header): the resize launch between the context's two timer events on
@@ -2129,20 +2069,9 @@ int jda_internal_resize_time_ex(jda_ctx *ctx, int32_t n, const jda_output *src, 
     if (n <= 0 || reps <= 0 || !ms || !src || !dst) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     resize_plan plan;
-    int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL, filter);
+    const int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL, filter);
     if (rc != JDA_SUCCESS) return rc;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < reps && rc == JDA_SUCCESS && e == hipSuccess; k++) {
-        e = hipEventRecord(ctx->ev_start, ctx->stream);
-        if (e == hipSuccess) rc = resize_launch(ctx, plan);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    jda_pool_free(ctx, plan.block);
-    if (rc != JDA_SUCCESS) return rc;
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_resize_time");
+    return timed_launches(ctx, reps, ms, plan.block, "jda_internal_resize_time", [&]() { return resize_launch(ctx, plan); });
 }
 
 // Measuring hook of tools/pack_bench.py (not part of the public header): the pack launch between the context's two timer events on its
@@ -2154,20 +2083,9 @@ int jda_internal_pack_time(jda_ctx *ctx, int32_t n, const jda_output *src, int32
     if (n <= 0 || reps <= 0 || !ms) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     pack_plan plan;
-    int rc = pack_upload(ctx, n, src, src_bytes_per_pixel, rects, layout_flags, elem_type, table, dst, &plan);
+    const int rc = pack_upload(ctx, n, src, src_bytes_per_pixel, rects, layout_flags, elem_type, table, dst, &plan);
     if (rc != JDA_SUCCESS) return rc;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < reps && rc == JDA_SUCCESS && e == hipSuccess; k++) {
-        e = hipEventRecord(ctx->ev_start, ctx->stream);
-        if (e == hipSuccess) rc = pack_launch(ctx, plan);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    jda_pool_free(ctx, plan.block);
-    if (rc != JDA_SUCCESS) return rc;
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_pack_time");
+    return timed_launches(ctx, reps, ms, plan.block, "jda_internal_pack_time", [&]() { return pack_launch(ctx, plan); });
 }
 
 // Measuring hooks of tools/orient_bench.py (not part of the public header): the orient launch, and a device-to-device copy to hold it
@@ -2179,36 +2097,19 @@ int jda_internal_orient_time(jda_ctx *ctx, int32_t n, const jda_output *src, int
     if (n <= 0 || !src || !orientations || !dst || reps <= 0 || !ms) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     orient_plan plan;
-    int rc = orient_upload(ctx, n, src, bytes_per_pixel, orientations, dst, &plan);
+    const int rc = orient_upload(ctx, n, src, bytes_per_pixel, orientations, dst, &plan);
     if (rc != JDA_SUCCESS) return rc;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < reps && rc == JDA_SUCCESS && e == hipSuccess; k++) {
-        e = hipEventRecord(ctx->ev_start, ctx->stream);
-        if (e == hipSuccess) rc = orient_launch(ctx, plan);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    jda_pool_free(ctx, plan.block);
-    if (rc != JDA_SUCCESS) return rc;
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_orient_time");
+    return timed_launches(ctx, reps, ms, plan.block, "jda_internal_orient_time", [&]() { return orient_launch(ctx, plan); });
 }
 int jda_internal_copy_time(jda_ctx *ctx, void *dst, const void *src, size_t bytes, int32_t reps, float *ms)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (!dst || !src || !bytes || reps <= 0 || !ms) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < reps && e == hipSuccess; k++) {
-        e = hipEventRecord(ctx->ev_start, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev_stop);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms[k], ctx->ev_start, ctx->ev_stop);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_copy_time");
+    return timed_launches(ctx, reps, ms, NULL, "jda_internal_copy_time", [&]() {
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        return e == hipSuccess ? (int)JDA_SUCCESS : jda_set_err(ctx, e, "jda_internal_copy_time");
+    });
 }
 
 } // extern "C"

@@ -358,6 +358,38 @@ def test_one_calls_with_fewer_rows_bad_mcu_and_progressive(gpu_ctx, oracle):
             assert np.array_equal(host, exp), (pt, rows, int(np.count_nonzero(host != exp)))
 
 
+def test_strips_call_on_a_stream_with_a_bad_mcu(gpu_ctx, oracle):
+    """jda_decode_to_host_strips (RGB8888, strips of 4 MCUs, one copy back) on a stream with a bad MCU: JDA_DECODE_ERROR and the MCUs in
+    front of the bad one; every strip in front of it holds the oracle's pixels, every byte behind it is zero"""
+    ctx, lib = gpu_ctx, gpu_ctx.lib
+    jpeg, nbad = U.bad_mcu_jpeg()
+    info = J.parse(jpeg)
+    mx, my = info["mcus_x"], info["mcus_y"]
+    _, canvas, _ = oracle.decode_canvas(jpeg, J.RGB8888, 0)
+    canvas = U.zero_undecoded(canvas, info, nbad)
+    mh, mwb = canvas.shape[0] // my, canvas.shape[1] // mx                  # (rows x bytes of an MCU)
+    per, n_sx = 4, (mx + 3) // 4
+    strip_bytes = per * mwb * mh
+    exp = np.zeros(my * n_sx * strip_bytes, np.uint8)                      # (behind a row's last, narrower strip: zeros too)
+    for y in range(my):
+        for s in range(n_sx):
+            px = canvas[y * mh:(y + 1) * mh, s * per * mwb:min(mx, (s + 1) * per) * mwb]
+            o = (y * n_sx + s) * strip_bytes
+            exp[o:o + px.size] = px.reshape(-1)
+    host = np.full(exp.size + 64, GUARD, np.uint8)
+    nok = C.c_int32(-1)
+    P = C.c_void_p
+    lib.jda_decode_to_host_strips.argtypes = [P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_size_t, P, C.c_int32, P, P]
+    rc = lib.jda_decode_to_host_strips(ctx.handle, jpeg, len(jpeg), J.RGB8888, 0, per, host.ctypes.data, exp.size, C.byref(nok), 1, None, None)
+    assert (rc, nok.value) == (2, nbad)
+    first = (nbad // mx) * n_sx + (nbad % mx) // per                        # the strip that holds the bad MCU
+    assert first > 0 and exp[:first * strip_bytes].any()
+    assert np.array_equal(host[:first * strip_bytes], exp[:first * strip_bytes]), "a strip in front of the bad MCU"
+    assert np.array_equal(host[first * strip_bytes:(first + 1) * strip_bytes], exp[first * strip_bytes:(first + 1) * strip_bytes]), "the bad MCU's strip"
+    assert not host[(first + 1) * strip_bytes:exp.size].any(), "a byte behind the bad MCU's strip"
+    assert np.all(host[exp.size:] == GUARD)
+
+
 def pipeline_entries(oracle):
     """[(Entry, file handed in, file whose oracle canvas is expected)]: two images per layout in mixed modes under different clips, a stream
     with a bad MCU under two clips, a progressive file at full size under a clip, and a clip of (0, 0)"""

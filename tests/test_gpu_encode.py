@@ -12,7 +12,9 @@ import pytest
 
 import jpegdec_amd as J
 from tests import coef_jpeg
+from tests import encode_prog_util as P
 from tests import encode_util as E
+from tests import orient_util as U
 from tests import resize_util as R
 from tests.cases import jpeg_for
 from tests.test_encode_cpu import ALL_EDGES, ZRL_WANT, edge_cases, twin_layout, zrl_symbols
@@ -21,7 +23,7 @@ from tests.test_gpu_resize import visible_pixels
 pytestmark = pytest.mark.gpu
 
 FILL = 0x5A
-INVALID, MEMORY = 1, 5
+INVALID, DECODE_ERROR, MEMORY = 1, 2, 5
 KERNELS = ("jda_encode_blocks", "jda_encode_lengths", "jda_encode_scan", "jda_encode_emit", "jda_encode_count", "jda_encode_write")
 GRID_PICTURES = (("noise", 75), ("smooth", 30), ("pixels", 100), ("blocks", 100))
 FILES = {"gray": "gray_333x217", "4:4:4": "c444_333x217", "4:2:2": "c422_333x217", "4:2:0": "c420_333x217"}
@@ -199,6 +201,21 @@ def test_transcode_to_host(sampling, gpu_ctx, oracle):
         rc, f, n = J.transcode_to_host(gpu_ctx, jpeg, capacity=1 << 16, **args)
         assert rc == INVALID and f is None and n == 0, kw
     assert encode_counts() == before
+
+
+def test_transcode_to_host_bad_mcu(gpu_ctx, oracle):
+    """a stream with a bad MCU: the MCUs from the bad one on are zeros BEFORE the cut or the resize, the file is delivered all the same, and
+    the verdict is JDA_DECODE_ERROR -- cut and resized, the whole image as it is, and the progressive encoder behind the same decode"""
+    bad, nok = U.bad_mcu_jpeg()
+    vis = visible_pixels(oracle, bad, J.RGB8888, 0, zero_from=nok)
+    for rect, size in (((250, 150, 83, 67), (40, 30)), (None, None)):
+        rc, f, n = J.transcode_to_host(gpu_ctx, bad, size, "4:2:0", 75, 0, 0, rect)
+        px = vis if size is None else R.resize(vis, size[0], size[1], rect)
+        want = E.file_bytes(np.ascontiguousarray(px), "4:2:0", 75, 0)
+        assert rc == DECODE_ERROR and n == len(want) and f == want, (rect, size, rc, n)
+    rc, f, n = J.transcode_to_host(gpu_ctx, bad, (40, 30), "4:2:0", 75, 0, 0, (250, 150, 83, 67), progressive=True)
+    want = P.file_bytes_prog(np.ascontiguousarray(R.resize(vis, 40, 30, (250, 150, 83, 67))), "4:2:0", 75)
+    assert rc == DECODE_ERROR and n == len(want) and f == want, (rc, n)
 
 
 def test_thumbnails_over_a_mixed_list(gpu_ctx, oracle):
