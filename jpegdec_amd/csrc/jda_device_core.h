@@ -1069,7 +1069,22 @@ JDA_HD uint32_t jda_output_pixel(const uint8_t *planes, uint32_t px, uint32_t py
 #define JDA_SEG_CHANGED 0x80000000u // entry-state word: "differs from the previous round's" (the walker's own bits are 14:0)
 enum { JDA_SEG_SPEC = 0 /* round 0: the exit state only */, JDA_SEG_RECORD = 4 /* + the segment's sums, one record per block start, truncation candidates (jda_segscan_finalize) */ };
 #define JDA_SEG_SUM_WORDS 8u         // per segment: block starts, DC sums [3], phase map, bad | has-restart | max AC category << 4, lag word at the last block start, round
-#define JDA_ST_NCAND 66u             // result word: truncation candidates appended (RECORD)
+#define JDA_SEG_START_WORDS 5u       // per segment: first block ordinal, DC predictors [3], byte lag j of the reference window at its entry
+// the result words (jda_segscan_params.stats), zeroed by the caller: who writes them is said at jda_segscan_params; what they add up to, in jda_prescan_plan.h
+#define JDA_ST_BAD 0u                // a predictor out of range, a stream read on into its padding, more records or candidates than their arrays hold
+#define JDA_ST_TERMINAL 1u           // closing index entries written: 1 for a good stream
+#define JDA_ST_MAX_AC 2u             // largest AC category
+#define JDA_ST_MAX_DC 3u             // largest |DC|
+#define JDA_ST_TRUNC 4u              // truncated reads (the serial pre-scan's count)
+#define JDA_ST_RST_MISMATCH 5u       // a restart marker is not where the MCU count puts it
+#define JDA_ST_INDEX_OK 6u           // the sums: enough blocks, no bad code before the end
+#define JDA_ST_SETTLED 7u            // the last round left nothing to walk (0: JDA_PRESCAN_MAX_ROUND reached)
+#define JDA_ST_ROUND0 8u             // + r: length of round r's work list (r >= 2; round r - 1 appends to it)
+#define JDA_ST_NCAND 66u             // truncation candidates appended (RECORD)
+#define JDA_ST_WORDS 68u
+#define JDA_PRESCAN_LIST_ROUNDS 4u   // rounds launched one by one (a round with an empty work list returns at once); the rest in one launch (jda_segscan_tail)
+#define JDA_PRESCAN_MAX_ROUND 56u    // no list round has this number or a higher one: the states-first order's recording round takes it
+static_assert(JDA_ST_ROUND0 + JDA_PRESCAN_MAX_ROUND + 1u < JDA_ST_NCAND, "every round's list length has a result word of its own");
 #define JDA_REC_POS_BITS 12u         // a record: bit position of the block's first AC symbol, counted from its segment's first bit (the block's DC symbol starts in the
                                      // segment: <= 2047 + 27) | running DC sum of its component, the block's own difference included, << 12
 #define JDA_SEG_FIRST_RST_SHIFT 8u   // seg_sum word 5, bits 31:8: the ordinal of the segment's first block behind an interval end (its sums count from a restart)
@@ -1077,13 +1092,15 @@ enum { JDA_SEG_SPEC = 0 /* round 0: the exit state only */, JDA_SEG_RECORD = 4 /
 struct jda_segscan_params {          // one per image
     const uint8_t *scan;             // filtered scan (global), zero padded to n_segs * JDA_SEG_BYTES + 16
     const uint8_t *tables;           // table blob (global)
-    uint32_t *entry_cur, *entry_nxt; // n_segs + 1 entry states each; swapped between rounds
-    uint32_t *seg_sum;               // COUNT out, 6 words per segment: block starts, DC sums [3], phase map, bad
-    const uint32_t *seg_start;       // WRITE in, 5 words per segment: first block ordinal, DC predictors [3], byte lag j of the reference window
-    uint32_t *blk_index;             // WRITE out: n_blocks_total + 1
-    int16_t *blk_dc;                 // WRITE out: n_blocks_total
-    uint32_t *stats;                 // [0] bad, [1] terminal entry written, [2] max AC category, [3] max |DC|, [4] truncated reads, [5] a restart marker is not where the MCU count puts it
-    uint32_t scan_len, n_segs, n_blocks_total, first_round;
+    uint32_t *entry_cur, *entry_nxt; // n_segs + 1 entry states, zeroed: the rounds read and replace them in place (entry_cur; entry_nxt is not read)
+    uint32_t *seg_sum;               // every RECORD walk out, JDA_SEG_SUM_WORDS words per segment; the sums, finalize and the candidates in
+    const uint32_t *seg_start;       // the sums out, JDA_SEG_START_WORDS words per segment; finalize and the candidates in
+    uint32_t *blk_index;             // finalize out, flagged entries by the candidates: n_blocks_total + 1
+    int16_t *blk_dc;                 // finalize out: n_blocks_total
+    // JDA_ST_WORDS result words (JDA_ST_*), zeroed: list lengths by the rounds, SETTLED by jda_segscan_tail, NCAND by the RECORD walks, INDEX_OK and
+    // MAX_AC by the sums, BAD / TERMINAL / MAX_DC by finalize, RST_MISMATCH / TRUNC (and BAD: more candidates than cand_cap) by the candidates' pass
+    uint32_t *stats;
+    uint32_t scan_len, n_segs, n_blocks_total, first_round;      // (first_round is not read)
     uint8_t nluma, nblocks, dc_id[3], ac_id[3];
     const uint32_t *filter_result;   // device filter ran (jda_pipeline): [0] = the filtered length; scan_len / n_segs above are upper bounds then
     uint32_t *worklist;              // jda_segscan_fused: two lists of n_segs (upper bound) segment numbers -- who walks in the next round
@@ -1098,18 +1115,18 @@ struct jda_segscan_params {          // one per image
     // copies them (one wait) instead of converting the blob itself
     uint8_t *walk_tables;
     uint32_t walk_tables_shared;      // 1: another image of the batch (same tables, same table ids) builds them
-    // RECORD mode (NULL / 0: the counting walk + WRITE walk of round 2): the counting walk leaves one record per block start --
-    // rec_cap slots per segment (more than its 2,048 bits can start blocks: jda_record_cap), 16-byte groups -- and the rare
-    // magnitude read that SOME entry lag would truncate as a candidate (16 bytes: segment, ordinal + 1 | round << 16, lag word at
+    // RECORD mode (every caller's: finalize and the candidates' pass return at once without records): the walk leaves one record per
+    // block start -- rec_cap slots per segment (more than its 2,048 bits can start blocks: jda_record_cap), 16-byte groups -- and the
+    // rare magnitude read that SOME entry lag would truncate as a candidate (16 bytes: segment, ordinal + 1 | round << 16, lag word at
     // the block's start, the lags that truncate); jda_segscan_finalize turns records into index entries and predictors,
-    // jda_segscan_resolve the candidates of the true lag into flagged entries
+    // jda_segscan_resolve_cands the candidates of the true lag into flagged entries.  Neither array needs clearing.
     uint32_t *records;
     uint32_t rec_cap;
     uint32_t *cands;
     uint32_t cand_cap;
     // RECORD mode with restart intervals: two words per interval start nr = 1 .. n_intervals - 1, zeroed -- the walk that ends the
     // interval in front of it leaves (its segment << 11 | blocks it had started by then + 1, its round): jda_segscan_resolve_cands
-    // checks that every marker ended an interval of a settled walk exactly where the MCU count puts it (what WRITE checks as it goes)
+    // checks that every marker ended an interval of a settled walk exactly where the MCU count puts it (JDA_ST_RST_MISMATCH)
     uint32_t *rst_events;
 };
 #define JDA_RST_SENTINEL 0x1fffffffu      // (a byte position no scan reaches: the index packs positions in 25 bits)
@@ -1610,7 +1627,7 @@ JDA_HD uint32_t jda_resolve_item(const jda_segscan_params &P, uint32_t ci)
     const uint32_t JDA_GLOBAL *sum = JDA_G(const uint32_t, P.seg_sum);
     const uint32_t JDA_GLOBAL *st = JDA_G(const uint32_t, P.seg_start);
     if (seg >= P.n_segs || sum[(size_t)seg * JDA_SEG_SUM_WORDS + 7u] != round) return 0;      // the segment was walked again: not its last walk's candidate
-    const uint32_t g0 = st[(size_t)seg * 5u], j = st[(size_t)seg * 5u + 4u];
+    const uint32_t g0 = st[(size_t)seg * JDA_SEG_START_WORDS], j = st[(size_t)seg * JDA_SEG_START_WORDS + 4u];
     if (g0 >= 0xfffffff0u || !((hit >> (4u + 5u * j)) & 1u)) return 0;
     uint32_t t = seg, i = ord - 1u, lagw = cd[2], jt = j, g = g0 + i;
     if (ord == 0u) {                                                // the block was open at the segment's entry: it started in ..
@@ -1618,7 +1635,7 @@ JDA_HD uint32_t jda_resolve_item(const jda_segscan_params &P, uint32_t ci)
         do { t--; } while (t > 0u && sum[(size_t)t * JDA_SEG_SUM_WORDS] == 0u);              // .. the last segment before that starts a block
         const uint32_t nb = sum[(size_t)t * JDA_SEG_SUM_WORDS];
         if (nb == 0u) return 0;
-        i = nb - 1u; lagw = sum[(size_t)t * JDA_SEG_SUM_WORDS + 6u]; jt = st[(size_t)t * 5u + 4u]; g = g0 - 1u;
+        i = nb - 1u; lagw = sum[(size_t)t * JDA_SEG_SUM_WORDS + 6u]; jt = st[(size_t)t * JDA_SEG_START_WORDS + 4u]; g = g0 - 1u;
     }
     if (g >= P.n_blocks_total || i >= P.rec_cap) return 0;
     const uint32_t rec = JDA_G(const uint32_t, P.records)[(size_t)t * P.rec_cap + i];
@@ -1642,7 +1659,7 @@ JDA_HD uint32_t jda_rst_event_item(const jda_segscan_params &P, uint32_t nr)
     if (e == 0u) return 1u;                                         // nobody ended an interval at this marker
     const uint32_t seg = e >> 11, nb = (e & 2047u) - 1u;
     if (seg >= P.n_segs || JDA_G(const uint32_t, P.seg_sum)[(size_t)seg * JDA_SEG_SUM_WORDS + 7u] != ev[1]) return 1u;      // .. not in its segment's last walk
-    const uint32_t g0 = JDA_G(const uint32_t, P.seg_start)[(size_t)seg * 5u];
+    const uint32_t g0 = JDA_G(const uint32_t, P.seg_start)[(size_t)seg * JDA_SEG_START_WORDS];
     if (g0 >= 0xfffffff0u) return 0u;                               // behind a bad code: the image is rejected for that
     return (uint64_t)g0 + nb == want ? 0u : 1u;
 }

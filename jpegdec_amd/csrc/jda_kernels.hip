@@ -1007,7 +1007,7 @@ __device__ __forceinline__ void jda_fused_item(const jda_segscan_params &P, cons
         if (who) {
             const uint32_t first = (uint32_t)__builtin_ctzll(who);
             uint32_t at0 = 0;
-            if (lane == first) at0 = atomicAdd(&P.stats[8u + round + 1u], (uint32_t)__builtin_popcountll(who));
+            if (lane == first) at0 = atomicAdd(&P.stats[JDA_ST_ROUND0 + round + 1u], (uint32_t)__builtin_popcountll(who));
             at0 = (uint32_t)__builtin_amdgcn_readlane((int)at0, (int)first);
             if (changed) {
                 E[seg + 1u] = x;
@@ -1038,7 +1038,7 @@ void jda_segscan_fused(const jda_segscan_params *__restrict__ params, uint32_t r
     uint32_t JDA_GLOBAL *stats = JDA_G(uint32_t, P.stats);
     const uint32_t round = round_and_flag & ~JDA_ROUND_ALL;
     const bool all = round <= 1u || (round_and_flag & JDA_ROUND_ALL) != 0u;      // rounds 0 and 1 walk every segment (round 1 to make everybody's sums); the closing RECORD round of the states-first order (jda_launch_prescan_passes_ex) too
-    const uint32_t count = all ? P.n_segs : stats[8u + round];
+    const uint32_t count = all ? P.n_segs : stats[JDA_ST_ROUND0 + round];
     if (blockIdx.x * JDA_WALK_THREADS >= count) return;                          // (uniform per workgroup)
     const uint32_t JDA_GLOBAL *wl_in = JDA_G(const uint32_t, P.worklist) + ((round & 1u) ? P.worklist_cap : 0u);
     uint32_t JDA_GLOBAL *wl_out = JDA_G(uint32_t, P.worklist) + ((round & 1u) ? 0u : P.worklist_cap);
@@ -1057,7 +1057,7 @@ void jda_segscan_fused(const jda_segscan_params *__restrict__ params, uint32_t r
 
 // The rounds behind the first few, in ONE launch: one workgroup per image goes round after round (a barrier and a fence between two)
 // until a round leaves its list empty -- lists of a handful of segments by then; a launch per round cost more than its walk, and a
-// fixed number of launches was a limit on the rounds.  stats[7] = 1: settled (0: max_round reached).
+// fixed number of launches was a limit on the rounds.  JDA_ST_SETTLED = 1: settled (0: max_round reached).
 // LDS_TABLES: sixteen wavefronts around the tables in LDS (large images: dozens of segments a round) / four wavefronts, tables through
 // the L2 (batches of small images: see jda_segscan_fused).
 template <bool LDS_TABLES>
@@ -1071,8 +1071,8 @@ void jda_segscan_tail(const jda_segscan_params *__restrict__ params, uint32_t fi
     uint32_t *stats = P.stats;
     const bool states_only = (first_round_and_flag & JDA_ROUND_ALL) != 0u;      // (uniform) the states-first order: these rounds settle the entry states, one RECORD round over every segment follows
     uint32_t round = first_round_and_flag & ~JDA_ROUND_ALL;
-    uint32_t count = __hip_atomic_load(&stats[8u + round], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (count == 0) { if (threadIdx.x == 0) stats[7] = 1; return; }       // (the usual case: nothing is staged)
+    uint32_t count = __hip_atomic_load(&stats[JDA_ST_ROUND0 + round], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (count == 0) { if (threadIdx.x == 0) stats[JDA_ST_SETTLED] = 1; return; }       // (the usual case: nothing is staged)
     uint32_t JDA_GLOBAL *E = JDA_G(uint32_t, P.entry_cur);
     const uint8_t *tab = LDS_TABLES ? (const uint8_t *)lds : (const uint8_t *)JDA_G(const uint8_t, P.walk_tables);
     if (LDS_TABLES) {
@@ -1092,9 +1092,9 @@ void jda_segscan_tail(const jda_segscan_params *__restrict__ params, uint32_t fi
         __threadfence();                                             // this round's entry states, sums and list, for every wavefront of the next
         __syncthreads();
         round++;
-        count = __hip_atomic_load(&stats[8u + round], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        count = __hip_atomic_load(&stats[JDA_ST_ROUND0 + round], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (threadIdx.x == 0) stats[7] = count == 0 ? 1u : 0u;
+    if (threadIdx.x == 0) stats[JDA_ST_SETTLED] = count == 0 ? 1u : 0u;
 }
 
 // batches whose longest scan has at most this many segments (512 KB) take the late rounds without LDS
@@ -1212,10 +1212,10 @@ __device__ __forceinline__ jda_sum_el jda_sum_load_chunk(const jda_segscan_param
 // with the chunk's carry-in and writes seg_start.  (One wavefront walking the segments in order -- 64 serial steps per chunk for
 // the lag, then also for the predictors -- took 0.23-0.49 ms per 64-image batch with nothing beside it on the GPU.)
 // A segment that met an invalid code ends the sums: harmless only behind the image's last block.
-// Result word: stats[6] = 1 when the index can be written (enough blocks, no bad code before the end).
+// Result word: JDA_ST_INDEX_OK = 1 when the index can be written (enough blocks, no bad code before the end).
 #define JDA_SUMS_WAVES 16u
 // (32 MB of scan -- the index packs byte positions in 25 bits --, or what fits the CU's LDS with smaller segments: a longer scan goes
-// to the serial pre-scan, stats[6] = 0)
+// to the serial pre-scan, JDA_ST_INDEX_OK = 0)
 #define JDA_SUMS_MAX_CHUNKS (((1u << 25) / (64u * JDA_SEG_BYTES)) < 6144u ? ((1u << 25) / (64u * JDA_SEG_BYTES)) : 6144u)
 __global__ __launch_bounds__(64 * JDA_SUMS_WAVES)
 void jda_segscan_sums(const jda_segscan_params *__restrict__ params)
@@ -1225,7 +1225,7 @@ void jda_segscan_sums(const jda_segscan_params *__restrict__ params)
     const jda_segscan_params P = jda_segscan_resolve(params[blockIdx.x]);
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t n_chunks = (P.n_segs + 63u) / 64u;
-    if (n_chunks > JDA_SUMS_MAX_CHUNKS) { if (threadIdx.x == 0) P.stats[6] = 0; return; }    // (the front end admits no scan that long)
+    if (n_chunks > JDA_SUMS_MAX_CHUNKS) { if (threadIdx.x == 0) P.stats[JDA_ST_INDEX_OK] = 0; return; }    // (the front end admits no scan that long)
     for (uint32_t c = wave; c < n_chunks; c += JDA_SUMS_WAVES) {    // ---- chunk aggregates
         uint32_t first_bad, mac;
         const jda_sum_el incl = jda_sum_wave_scan(jda_sum_load_chunk(P, c, lane, first_bad, mac), lane);
@@ -1254,7 +1254,7 @@ void jda_segscan_sums(const jda_segscan_params *__restrict__ params)
             carry = jda_sum_combine(carry, last);
             if (bm) ended = true;
         }
-        if (lane == 0) P.stats[6] = carry.nblk >= P.n_blocks_total + 1u ? 1u : 0u;     // else: the scan ends before the image does
+        if (lane == 0) P.stats[JDA_ST_INDEX_OK] = carry.nblk >= P.n_blocks_total + 1u ? 1u : 0u;     // else: the scan ends before the image does
     }
     __syncthreads();
     uint32_t *seg_start = const_cast<uint32_t *>(P.seg_start);
@@ -1267,12 +1267,12 @@ void jda_segscan_sums(const jda_segscan_params *__restrict__ params)
         if (P.records) {                                            // RECORD mode: the largest AC category of the settled walks (WRITE's result word)
             if (in.flag & 4u) mac = 0;
             mac = jda_wave_max_u32(mac);
-            if (lane == 0 && mac) atomicMax(&P.stats[2], mac);
+            if (lane == 0 && mac) atomicMax(&P.stats[JDA_ST_MAX_AC], mac);
         }
         const jda_sum_el pre = jda_sum_combine(in, excl);
         const uint32_t seg = c * 64u + lane;
         if (seg < P.n_segs) {
-            uint32_t *st = seg_start + (size_t)seg * 5;
+            uint32_t *st = seg_start + (size_t)seg * JDA_SEG_START_WORDS;
             const bool dead = (in.flag & 4u) != 0 || lane > first_bad;       // behind a bad code: the write pass skips these
             st[0] = dead ? 0xfffffff0u : (pre.nblk > 0xfffffff0u ? 0xfffffff0u : pre.nblk);
             st[1] = pre.d0; st[2] = pre.d1; st[3] = pre.d2; st[4] = pre.map & 7u;      // (the lag the scan starts with is 0: field 0 of the composed map)
@@ -1291,8 +1291,8 @@ extern "C" hipError_t jda_launch_segscan_sums(const jda_segscan_params *params, 
 }
 
 // RECORD mode, after the sums: the records of every segment -> index entries (canonical) and DC predictors, block-parallel -- a
-// wavefront per segment, sixteen segments one after the other, lane = record: coalesced reads and writes, no walk.  Result words as
-// WRITE left them: [0] bad (a predictor out of range, a stream read on into its padding), [1] closing entry written, [3] max |DC|.
+// wavefront per segment, sixteen segments one after the other, lane = record: coalesced reads and writes, no walk.  Result words:
+// JDA_ST_BAD (a predictor out of range, a stream read on into its padding), JDA_ST_TERMINAL (closing entry written), JDA_ST_MAX_DC.
 #ifndef JDA_FIN_SEGS_PER_WAVE
 #define JDA_FIN_SEGS_PER_WAVE 16u
 #endif
@@ -1309,7 +1309,7 @@ void jda_segscan_finalize(const jda_segscan_params *__restrict__ params)
     // the segments' headers first, one lane each (one round trip for all of them), then segment after segment
     uint32_t h_g0 = 0xffffffffu, h_n = 0, h_p0 = 0, h_p1 = 0, h_p2 = 0, h_b0 = 0, h_rf = 0xffffffffu;
     if (lane < JDA_FIN_SEGS_PER_WAVE && seg0 + lane < P.n_segs) {
-        const uint32_t JDA_GLOBAL *st = JDA_G(const uint32_t, P.seg_start) + (size_t)(seg0 + lane) * 5;
+        const uint32_t JDA_GLOBAL *st = JDA_G(const uint32_t, P.seg_start) + (size_t)(seg0 + lane) * JDA_SEG_START_WORDS;
         h_g0 = st[0]; h_p0 = st[1]; h_p1 = st[2]; h_p2 = st[3];
         h_n = JDA_G(const uint32_t, P.seg_sum)[(size_t)(seg0 + lane) * JDA_SEG_SUM_WORDS];
         h_rf = jda_fin_rst_from(JDA_G(const uint32_t, P.seg_sum)[(size_t)(seg0 + lane) * JDA_SEG_SUM_WORDS + 5u]);
@@ -1336,9 +1336,9 @@ void jda_segscan_finalize(const jda_segscan_params *__restrict__ params)
     const uint32_t m_dc = jda_wave_max_u32(A.max_abs_dc), n_term = jda_wave_sum_u32(A.terminal);
     const bool any_bad = __builtin_amdgcn_ballot_w64(A.bad != 0) != 0;
     if (lane == 0) {
-        if (any_bad) atomicOr(&P.stats[0], 1u);
-        if (n_term) atomicAdd(&P.stats[1], n_term);
-        if (m_dc) atomicMax(&P.stats[3], m_dc);
+        if (any_bad) atomicOr(&P.stats[JDA_ST_BAD], 1u);
+        if (n_term) atomicAdd(&P.stats[JDA_ST_TERMINAL], n_term);
+        if (m_dc) atomicMax(&P.stats[JDA_ST_MAX_DC], m_dc);
     }
 }
 // .. and the candidates: the truncated reads of the true lag flag their blocks (behind jda_segscan_finalize: it overwrites entries)
@@ -1347,18 +1347,18 @@ void jda_segscan_resolve_cands(const jda_segscan_params *__restrict__ params)
 {
     const jda_segscan_params P = jda_segscan_resolve(params[blockIdx.y]);
     if (!P.records) return;
-    if (P.restart_pos) {                                             // every marker where the MCU count puts it?  (result word [5], as WRITE sets it)
+    if (P.restart_pos) {                                             // every marker where the MCU count puts it?  (JDA_ST_RST_MISMATCH)
         bool mis = false;
         for (uint32_t nr = 1u + blockIdx.x * 256u + threadIdx.x; nr < P.n_intervals; nr += gridDim.x * 256u) mis |= jda_rst_event_item(P, nr) != 0u;
-        if (__builtin_amdgcn_ballot_w64(mis) != 0 && (threadIdx.x & 63u) == 0u) atomicOr(&P.stats[5], 1u);
+        if (__builtin_amdgcn_ballot_w64(mis) != 0 && (threadIdx.x & 63u) == 0u) atomicOr(&P.stats[JDA_ST_RST_MISMATCH], 1u);
     }
     const uint32_t n = P.stats[JDA_ST_NCAND];
     if (blockIdx.x * 256u >= n) return;
-    if (n > P.cand_cap) { if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(&P.stats[0], 1u); return; }     // more than the list holds: the serial pre-scan
+    if (n > P.cand_cap) { if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(&P.stats[JDA_ST_BAD], 1u); return; }     // more than the list holds: the serial pre-scan
     uint32_t hits = 0;
     for (uint32_t ci = blockIdx.x * 256u + threadIdx.x; ci < n; ci += gridDim.x * 256u) hits += jda_resolve_item(P, ci);
     hits = jda_wave_sum_u32(hits);
-    if ((threadIdx.x & 63u) == 0u && hits) atomicAdd(&P.stats[4], hits);
+    if ((threadIdx.x & 63u) == 0u && hits) atomicAdd(&P.stats[JDA_ST_TRUNC], hits);
 }
 
 // every pass of the device pre-scan behind the filter, on one stream: round 0 and the counting round over every segment, the

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "jda_runtime_internal.h"
+#include "jda_prescan_plan.h"
 
 extern "C" int jda_front_prepare(const uint8_t *jpeg, int32_t len, uint8_t *tables, jda_front *out);
 extern "C" uint32_t jda_front_fast_mul(const uint8_t *tables, const jda_front *f, uint32_t max_ac_bits, int32_t max_abs_dc);
@@ -67,7 +68,7 @@ inline void copy_to_mirror(uint8_t *dst, const uint8_t *src, size_t n)
     memcpy(dst, src, n);
 }
 
-inline size_t a16(size_t v) { return (v + 15) & ~(size_t)15; }
+inline size_t a16(size_t v) { return jda_a16(v); }
 inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // a few persistent worker threads: run(n, fn) calls fn(0..n-1) across them and the caller.  Items are handed out under the
@@ -150,14 +151,15 @@ struct Img {
     int32_t err;                 // front-end verdict
     bool device;                 // filter + pre-scan + decode were enqueued for it
     bool fast;                   // launched with 24-bit multiplies
-    uint32_t n_segs_ub, n_blocks;
+    uint32_t n_blocks;
+    jda_prescan_sizes z;         // of the unfiltered length: upper bounds (z.n_segs too) of what the filtered scan needs
     size_t off_raw, off_scan, scan_bytes, off_index, off_dc, off_work, off_zero, off_stats;   // arena offsets
-    size_t work_bytes, zero_bytes, off_rpos, off_fwork, off_wt;     // off_rpos / off_fwork: restart positions / the filter's work words inside the work region
+    size_t work_bytes, zero_bytes, off_start, off_wl, off_rpos, off_fwork, off_wt;     // seg_start / work lists / restart positions / the filter's work words / the walk's tables inside the work region
+    size_t off_ev;               // who ended which restart interval, inside the zero region
     bool direct;                 // its bytes go to the GPU from where the caller has them (JDA_SUBMIT_PINNED_INPUT): no copy into the mirror
     uint32_t raw_skip;           // .. keeping their alignment: the stream's first byte is raw_skip bytes behind the 16-byte aligned off_raw
     bool record;                 // the pre-scan runs in RECORD mode (no WRITE walk)
     size_t off_recs, off_cands;  // block records / truncation candidates inside the work region
-    uint32_t cand_cap;
     size_t ctl_tables;           // offset of its tables inside the control blob (images with equal tables and table ids share one copy)
     uint64_t tab_hash;           // of the tables + the components' table ids (what the walk's tables are made from)
     int tab_owner;               // the first image of the batch with the same tables (itself: it owns the copy that travels)
@@ -175,10 +177,14 @@ struct Img {
 
 #define JDA_PIPE_MAX_DEPTH 8
 #ifndef JDA_PIPE_SPEC_ROUNDS
-#define JDA_PIPE_SPEC_ROUNDS 4       // rounds launched one by one (a round with an empty work list returns at once); the rest in one launch (jda_segscan_tail)
+#define JDA_PIPE_SPEC_ROUNDS JDA_PRESCAN_LIST_ROUNDS
 #endif
-#define JDA_PIPE_MAX_ROUNDS 56       // stats[8 + r] = length of round r's list, r <= 57 < 60
-#define JDA_PIPE_STATS_BYTES 288      // per image: filter result (2 words, 16 bytes) | 64 result words of the pre-scan + 16 bytes
+#ifndef JDA_PIPE_MAX_ROUNDS
+#define JDA_PIPE_MAX_ROUNDS JDA_PRESCAN_MAX_ROUND
+#endif
+static_assert(JDA_PIPE_MAX_ROUNDS <= JDA_PRESCAN_MAX_ROUND, "jda_prescan_verdict / jda_prescan_rounds_used: no list round beyond JDA_PRESCAN_MAX_ROUND - 1");
+#define JDA_PIPE_STATS_BYTES 288      // per image: filter result (2 words, 16 bytes) | the result words of the pre-scan
+static_assert(JDA_PIPE_STATS_BYTES == 16 + 4 * JDA_ST_WORDS, "the filter's result, then the pre-scan's");
 
 struct jda_pipeline {
     jda_ctx *ctx;
@@ -467,10 +473,7 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
                                             outputs[i], S.pts[(size_t)i], S.opts[(size_t)i], &bpp);
         if (rc != JDA_SUCCESS) { im.err = rc; continue; }
         if (!im.f.device_ok) continue;                       // valid, but the serial host pre-scan has to make its index (jda_pipeline_wait)
-        // the block records of the device pre-scan are rec_cap slots per 256-byte segment: 6 x the scan with the usual tables, up to
-        // 16 x with a DHT whose shortest codes are one or two bits.  Past 8 x (+ 16 MB of grace) the image takes the serial path: a
-        // batch of such files must not ask for an arena several times what the same files needed before the records existed
-        if ((uint64_t)(im.f.raw_len / JDA_SEG_BYTES + 1u) * im.f.rec_cap * 4u > 8ull * im.f.raw_len + (16ull << 20)) continue;
+        if (!jda_prescan_admits(im.f.raw_len, im.f.rec_cap)) continue;      // record slots out of proportion to the scan: the serial path
         im.device = true; n_dev++;
         const int variant = jda_plain_variant(D);
         // (window size: the filtered length is not known yet; the unfiltered one is at most a few percent larger)
@@ -545,22 +548,23 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
         Img &im = S.imgs[(size_t)i];
         if (!im.device) continue;
         // seg_sum | seg_start | two work lists | where the restart intervals start (+ the sentinel)
-        im.n_segs_ub = im.f.raw_len / JDA_SEG_BYTES + 1u;
-        im.off_rpos = a16((size_t)im.n_segs_ub * 4 * JDA_SEG_SUM_WORDS) + a16((size_t)im.n_segs_ub * 20) + a16((size_t)im.n_segs_ub * 8);
-        im.off_fwork = im.off_rpos + (im.f.n_intervals ? a16(((size_t)im.f.n_intervals + 1) * 4) : 0);          // .. | the filter's chunk functions
+        im.z = jda_prescan_sizes_of(im.f.raw_len, im.f.n_intervals, im.f.rec_cap);
+        im.off_start = im.z.seg_sum;
+        im.off_wl = im.off_start + im.z.seg_start;
+        im.off_rpos = im.off_wl + im.z.worklist;
+        im.off_fwork = im.off_rpos + im.z.restart_pos;                                                             // .. | the filter's chunk functions
         im.off_wt = im.off_fwork + a16(JDA_FILTER_WORK_BYTES(im.f.raw_len + 16u));                                 // .. | the walk's tables
         im.work_bytes = im.off_wt + JDA_WT_BYTES;
         // .. | RECORD mode: the segments' block records, the truncation candidates
         im.record = true;                                    // (device_ok streams have record slots: front_common)
-        im.off_recs = im.off_cands = 0; im.cand_cap = 0;
+        im.off_recs = im.off_cands = 0;
         if (im.record) {
             // (images of one size would put their record regions a constant stride apart: a skew per image keeps the walkers of a
             // batch of like images -- all at the same place of their scans at the same time -- off each other's memory channels)
             static const size_t skew = []() { const char *e = JDA_LAB_ENV("JDA_PIPE_REC_SKEW"); return e ? (size_t)atoi(e) : (size_t)0; }();
             im.off_recs = a256(im.work_bytes) + a256(skew * (size_t)(i % 16));
-            im.off_cands = im.off_recs + a16((size_t)im.n_segs_ub * im.f.rec_cap * 4);
-            im.cand_cap = std::max<uint32_t>(1024u, im.n_segs_ub * 16u);      // (a high-quality photograph: five candidates per segment, most of them of walks that were redone)
-            im.work_bytes = im.off_cands + (size_t)im.cand_cap * 16;
+            im.off_cands = im.off_recs + im.z.records;
+            im.work_bytes = im.off_cands + im.z.cands;
         }
         im.off_work = take(im.work_bytes);
     }
@@ -568,14 +572,15 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
     for (int i = 0; i < n; i++) {
         Img &im = S.imgs[(size_t)i];
         if (!im.device) continue;
-        im.scan_bytes = a16(std::max((size_t)im.f.raw_len + JDA_SCAN_PAD, (size_t)im.n_segs_ub * JDA_SEG_BYTES + 16));
+        im.scan_bytes = im.z.scan;
         im.off_scan = take(im.scan_bytes);
     }
     for (int i = 0; i < n; i++) { Img &im = S.imgs[(size_t)i]; if (im.device) im.off_index = take(((size_t)im.n_blocks + 1) * 4); }
     for (int i = 0; i < n; i++) {
         Img &im = S.imgs[(size_t)i];
         if (!im.device) continue;
-        im.zero_bytes = a16(((size_t)im.n_segs_ub + 1) * 4) + (im.record && im.f.n_intervals ? a16((size_t)im.f.n_intervals * 8) : 0);      // entry states | RECORD mode: who ended which restart interval
+        im.off_ev = im.z.entry;
+        im.zero_bytes = im.off_ev + (im.record ? im.z.rst_events : 0);      // entry states | RECORD mode: who ended which restart interval
         im.off_zero = take(im.zero_bytes);
     }
     S.off_stats_dev = arena;
@@ -708,12 +713,12 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
         memset(&P, 0, sizeof(P));
         P.scan = B + im.off_scan; P.tables = B + im.ctl_tables;
         P.entry_cur = (uint32_t *)(B + im.off_zero); P.entry_nxt = P.entry_cur;
-        P.worklist = (uint32_t *)(B + im.off_work + a16((size_t)im.n_segs_ub * 4 * JDA_SEG_SUM_WORDS) + a16((size_t)im.n_segs_ub * 20)); P.worklist_cap = im.n_segs_ub;
-        P.seg_sum = (uint32_t *)(B + im.off_work); P.seg_start = (const uint32_t *)(B + im.off_work + a16((size_t)im.n_segs_ub * 4 * JDA_SEG_SUM_WORDS));
+        P.worklist = (uint32_t *)(B + im.off_work + im.off_wl); P.worklist_cap = im.z.n_segs;
+        P.seg_sum = (uint32_t *)(B + im.off_work); P.seg_start = (const uint32_t *)(B + im.off_work + im.off_start);
         if (im.record) {
             P.records = (uint32_t *)(B + im.off_work + im.off_recs); P.rec_cap = im.f.rec_cap;
-            P.cands = (uint32_t *)(B + im.off_work + im.off_cands); P.cand_cap = im.cand_cap;
-            if (im.f.n_intervals) P.rst_events = (uint32_t *)(B + im.off_zero + a16(((size_t)im.n_segs_ub + 1) * 4));
+            P.cands = (uint32_t *)(B + im.off_work + im.off_cands); P.cand_cap = im.z.cand_cap;
+            if (im.f.n_intervals) P.rst_events = (uint32_t *)(B + im.off_zero + im.off_ev);
         }
         P.blk_index = (uint32_t *)(B + im.off_index); P.blk_dc = (int16_t *)(B + im.off_dc);
         P.stats = pstats;
@@ -721,17 +726,11 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
         if (wo < 0) wo = i;
         P.walk_tables = B + S.imgs[(size_t)wo].off_work + S.imgs[(size_t)wo].off_wt;
         P.walk_tables_shared = wo != i ? 1u : 0u;
-        P.scan_len = im.f.raw_len; P.n_segs = im.n_segs_ub; P.n_blocks_total = im.n_blocks;
-        P.nblocks = (uint8_t)I.blocks_per_mcu; P.nluma = (uint8_t)(I.blocks_per_mcu - (I.ncomp == 3 ? 2 : 0));
-        for (int c = 0; c < 3; c++) { P.dc_id[c] = im.f.dc_id[c]; P.ac_id[c] = im.f.ac_id[c]; }
+        jda_prescan_fill_geometry(P, I, im.f.dc_id, im.f.ac_id, im.f.raw_len, im.z.n_segs, n_int);
         P.filter_result = fres;
-        if (n_int) {                                                    // the walk ends intervals where the filter found the markers
-            P.restart_pos = F.restart_pos; P.n_intervals = n_int;
-            P.interval_blocks = (uint32_t)I.restart_interval * (uint32_t)I.blocks_per_mcu;
-            P.round_last = ((uint32_t)(I.mcus_x * I.mcus_y) % (uint32_t)I.restart_interval) == 0 ? 1u : 0u;
-        }
+        if (n_int) P.restart_pos = F.restart_pos;                       // the walk ends intervals where the filter found the markers
         sp[k] = P;
-        max_segs = std::max(max_segs, im.n_segs_ub);
+        max_segs = std::max(max_segs, im.z.n_segs);
         jda_strips_params &TP = tp[k];
         TP.dst = (jda_strip *)(B + S.list_off[im.list]) + im.strip_off; TP.n_padded = im.n_tiles; TP.image = (uint32_t)i; TP.ord = im.ord;
         TP.mcus_x = D.mcus_x; TP.mcus_y = D.mcus_y; TP.per = jda_mcus_per_tile(D.mode);
@@ -885,13 +884,12 @@ int jda_pipeline_wait(jda_pipeline *p, int32_t ticket, int32_t *status)
                 uint32_t max_ac = 0, max_dc = 0;
                 // the last round left nothing to walk; enough blocks; no bad code; the closing entry written once; and, with restart
                 // intervals, as many markers as the MCU count asks for, each where the count puts it
-                bool ok = ps[7] == 1 && ps[6] == 1 && ps[0] == 0 && ps[1] == 1;
-                if (im.f.n_intervals && (rb[1] + 1u != im.f.n_intervals || ps[5] != 0)) ok = false;
-                max_ac = ps[2]; max_dc = ps[3];
-                S.st.spec_rounds_max = std::max<int32_t>(S.st.spec_rounds_max, [&]() { int r = 2; while (r <= JDA_PIPE_MAX_ROUNDS + 1 && ps[8 + r]) r++; return r; }());   // rounds that had something to walk
+                bool ok = jda_prescan_verdict(ps, rb, im.f.n_intervals);
+                max_ac = ps[JDA_ST_MAX_AC]; max_dc = ps[JDA_ST_MAX_DC];
+                S.st.spec_rounds_max = std::max<int32_t>(S.st.spec_rounds_max, jda_prescan_rounds_used(ps));   // rounds that had something to walk
                 {
                     static const bool trace_lists = JDA_LAB_ENV("JDA_PIPE_TRACE_LISTS") != NULL;      // (what the rounds behind round 1 had to walk)
-                    if (trace_lists && i == 0) fprintf(stderr, "jda_pipeline: ticket %d image 0: %u segments, work lists of rounds 2.. : %u %u %u %u %u\n", ticket, rb[0] / JDA_SEG_BYTES + 1u, ps[10], ps[11], ps[12], ps[13], ps[14]);
+                    if (trace_lists && i == 0) fprintf(stderr, "jda_pipeline: ticket %d image 0: %u segments, work lists of rounds 2.. : %u %u %u %u %u\n", ticket, rb[0] / JDA_SEG_BYTES + 1u, ps[JDA_ST_ROUND0 + 2], ps[JDA_ST_ROUND0 + 3], ps[JDA_ST_ROUND0 + 4], ps[JDA_ST_ROUND0 + 5], ps[JDA_ST_ROUND0 + 6]);
                 }
                 if (ok && im.fast && !jda_front_fast_mul(S.pin + im.ctl_tables, &im.f, max_ac, (int32_t)max_dc)) ok = false;   // a magnitude no legal stream has
                 redo = !ok;
@@ -899,8 +897,8 @@ int jda_pipeline_wait(jda_pipeline *p, int32_t ticket, int32_t *status)
                 else {
                     static const bool trace = JDA_LAB_ENV("JDA_PIPE_TRACE") != NULL;
                     if (trace) fprintf(stderr, "jda_pipeline: image %d (%dx%d, %u restart intervals) of ticket %d goes to the host path: filter %u bytes / %u markers, result words %u %u %u %u %u, [5] %u [6] %u, settled %u, fast %d\n",
-                                       i, im.f.info.width, im.f.info.height, im.f.n_intervals, ticket, rb[0], rb[1], ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], ps[6],
-                                       ps[7], (int)im.fast);
+                                       i, im.f.info.width, im.f.info.height, im.f.n_intervals, ticket, rb[0], rb[1], ps[JDA_ST_BAD], ps[JDA_ST_TERMINAL], ps[JDA_ST_MAX_AC], ps[JDA_ST_MAX_DC], ps[JDA_ST_TRUNC], ps[JDA_ST_RST_MISMATCH],
+                                       ps[JDA_ST_INDEX_OK], ps[JDA_ST_SETTLED], (int)im.fast);
                 }
             }
             if (redo) { st = slow_path(p, S.jpegs[(size_t)i], S.lens[(size_t)i], S.outs[(size_t)i], S.pts[(size_t)i], S.opts[(size_t)i]); S.st.host_path_images++; }

@@ -25,6 +25,7 @@
 #include "jda_pack_plan.h"
 #include "jda_resize_plan.h"
 #include "jda_encode_plan.h"
+#include "jda_prescan_plan.h"
 
 extern "C" uint32_t jda_image_fast_mul(const jda_image *img);
 extern "C" uint32_t jda_image_general_p1(const jda_image *img);
@@ -81,7 +82,7 @@ int jda_set_err(jda_ctx *ctx, hipError_t e, const char *what)
 
 #define JDA_HIP(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return jda_set_err((ctx), e_, #call); } while (0)
 
-static inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+static inline size_t align16(size_t v) { return jda_a16(v); }
 
 hipError_t jda_pool_alloc(jda_ctx *ctx, void **out, size_t bytes)
 {
@@ -311,7 +312,7 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
         bool seg_mode; uint32_t n_segs; size_t off_ea, off_sum, off_start, off_wl, off_rp, off_wt, off_ev, off_sstats;
         bool record; uint32_t rec_cap, cand_cap; size_t off_recs, off_cands, zero_end;      // RECORD mode of the pre-scan (no restart intervals)
         std::vector<uint32_t> rp;            // restart positions + the sentinel, until their copy has been made
-        uint32_t sst[68];
+        uint32_t sst[JDA_ST_WORDS];
     };
     std::vector<Item> items((size_t)n);
     int rc = JDA_SUCCESS;
@@ -380,11 +381,7 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
         const uint8_t *tables = jda_image_tables(img, &it.tbytes);
         it.n_blocks = (size_t)I.mcus_x * I.mcus_y * I.blocks_per_mcu;
         it.on_device = jda_image_index_on_device(img) != 0;      // index to be made on the device
-        if (it.on_device) {                                      // (the record area's bound: jda_pipeline_submit_ex has the same)
-            uint32_t sl = 0;
-            (void)jda_image_scan(img, &sl);
-            if ((uint64_t)(sl / JDA_SEG_BYTES + 1u) * jda_image_record_cap(img) * 4u > 8ull * sl + (16ull << 20)) { jda_image_run_host_prescan(img); it.on_device = false; }
-        }
+        if (it.on_device && !jda_prescan_admits(scan_len, jda_image_record_cap(img))) { jda_image_run_host_prescan(img); it.on_device = false; }      // (the record area's bound)
         const uint32_t *rpos = jda_image_restart_positions(img, &it.n_int);
         jda_dev_image *d = new (std::nothrow) jda_dev_image;
         if (!d) { rc = JDA_ERROR_MEMORY; break; }
@@ -418,25 +415,26 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
         if (it.seg_mode) {
             // the scan is read in whole 256-byte segments (+ a few bytes): zero padded behind its last byte; then the entry
             // states, the per-segment sums and start values, the two work lists, the restart positions, the result words
-            it.n_segs = scan_len / JDA_SEG_BYTES + 1u;
-            d->bytes = d->off_scan + align16(std::max((size_t)scan_len + JDA_SCAN_PAD, (size_t)it.n_segs * JDA_SEG_BYTES + 16));
+            it.rec_cap = jda_image_record_cap(img);
+            const jda_prescan_sizes Z = jda_prescan_sizes_of(scan_len, I.restart_interval ? it.n_int : 0u, it.rec_cap);
+            it.n_segs = Z.n_segs;
+            d->bytes = d->off_scan + Z.scan;
             it.off_ea = d->bytes;
-            it.off_sum = it.off_ea + align16(((size_t)it.n_segs + 1) * 4);
-            it.off_start = it.off_sum + align16((size_t)it.n_segs * 4 * JDA_SEG_SUM_WORDS);
-            it.off_wl = it.off_start + align16((size_t)it.n_segs * 20);
-            it.off_rp = it.off_wl + align16((size_t)it.n_segs * 8);
-            it.off_wt = it.off_rp + (I.restart_interval ? align16(((size_t)it.n_int + 1) * 4) : 0);
+            it.off_sum = it.off_ea + Z.entry;
+            it.off_start = it.off_sum + Z.seg_sum;
+            it.off_wl = it.off_start + Z.seg_start;
+            it.off_rp = it.off_wl + Z.worklist;
+            it.off_wt = it.off_rp + Z.restart_pos;
             it.off_ev = it.off_wt + JDA_WT_BYTES;                 // RECORD mode: who ended which restart interval (zeroed)
-            it.off_sstats = it.off_ev + (I.restart_interval ? align16((size_t)it.n_int * 8) : 0);
+            it.off_sstats = it.off_ev + Z.rst_events;
             it.alloc = it.off_sstats + 512;
             it.zero_end = it.alloc;                          // (what is memset: everything up to here; records and candidates need none)
-            it.rec_cap = jda_image_record_cap(img);
             it.record = true;                                 // (a stream the device walks has record slots: front_common)
             if (it.record) {
                 it.off_recs = (it.alloc + 255) & ~(size_t)255;
-                it.off_cands = it.off_recs + align16((size_t)it.n_segs * it.rec_cap * 4);
-                it.cand_cap = std::max<uint32_t>(1024u, it.n_segs * 16u);
-                it.alloc = it.off_cands + (size_t)it.cand_cap * 16;
+                it.off_cands = it.off_recs + Z.records;
+                it.cand_cap = Z.cand_cap;
+                it.alloc = it.off_cands + Z.cands;
             }
         }
         e = jda_pool_alloc(ctx, (void **)&d->base, it.alloc);
@@ -467,9 +465,7 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
                 it.rp.assign(rpos, rpos + it.n_int); it.rp.push_back(JDA_RST_SENTINEL);
                 e = hipMemcpyAsync(d->base + it.off_rp, it.rp.data(), it.rp.size() * 4, hipMemcpyHostToDevice, ctx->stream);
                 if (e != hipSuccess) { rc = jda_set_err(ctx, e, "hipMemcpy(restart positions)"); break; }
-                SP.restart_pos = (const uint32_t *)(d->base + it.off_rp); SP.n_intervals = it.n_int;
-                SP.interval_blocks = (uint32_t)I.restart_interval * (uint32_t)I.blocks_per_mcu;
-                SP.round_last = ((uint32_t)(I.mcus_x * I.mcus_y) % (uint32_t)I.restart_interval) == 0 ? 1u : 0u;
+                SP.restart_pos = (const uint32_t *)(d->base + it.off_rp);
             }
             SP.blk_index = (uint32_t *)(d->base + d->off_index); SP.blk_dc = (int16_t *)(d->base + d->off_dc);
             SP.stats = (uint32_t *)(d->base + it.off_sstats);
@@ -479,9 +475,7 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
                 SP.cands = (uint32_t *)(d->base + it.off_cands); SP.cand_cap = it.cand_cap;
                 if (I.restart_interval) SP.rst_events = (uint32_t *)(d->base + it.off_ev);
             }
-            SP.scan_len = scan_len; SP.n_segs = it.n_segs; SP.n_blocks_total = (uint32_t)it.n_blocks;
-            SP.nblocks = (uint8_t)I.blocks_per_mcu; SP.nluma = (uint8_t)(I.blocks_per_mcu - (I.ncomp == 3 ? 2 : 0));
-            for (int c = 0; c < 3; c++) { SP.dc_id[c] = d->dc_id[c]; SP.ac_id[c] = d->ac_id[c]; }
+            jda_prescan_fill_geometry(SP, I, d->dc_id, d->ac_id, scan_len, it.n_segs, I.restart_interval ? it.n_int : 0u);
             seg_params.push_back(SP); seg_owner.push_back(i);
             if (it.n_segs > max_segs) max_segs = it.n_segs;
             continue;
@@ -541,7 +535,7 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
         uint64_t total_segs = 0;
         for (const jda_segscan_params &sp : seg_params) total_segs += sp.n_segs;
         const int states_first = total_segs <= 131072u ? 1 : 0;                 // (two lanes for every SIMD lane of the GPU)
-        if (e == hipSuccess) e = jda_launch_prescan_passes_ex(d_seg, ns, max_segs, 4, 56, 1, states_first, ctx->stream);
+        if (e == hipSuccess) e = jda_launch_prescan_passes_ex(d_seg, ns, max_segs, JDA_PRESCAN_LIST_ROUNDS, JDA_PRESCAN_MAX_ROUND, 1, states_first, ctx->stream);
         for (uint32_t p = 0; p < ns && e == hipSuccess; p++) {
             Item &it = items[seg_owner[p]];
             e = hipMemcpyAsync(it.sst, it.d->base + it.off_sstats, sizeof(it.sst), hipMemcpyDeviceToHost, ctx->stream);
@@ -560,9 +554,9 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
         const int i = seg_owner[p];
         Item &it = items[i];
         const jda_image_info &I = *jda_image_get_info(imgs[i]);
-        { int r = 2; while (r <= 57 && it.sst[8 + r]) r++; if (r > rounds_max) rounds_max = r; }
-        if (it.sst[7] == 1 && it.sst[6] == 1 && it.sst[0] == 0 && it.sst[1] == 1 && it.sst[5] == 0 && it.sst[8 + 57] == 0) {   // (.. and the states-first order's recording round found every exit state as the SPEC rounds had left it)   // states settled, enough blocks, no bad code before the end, the closing index entry written once, every marker where the MCU count puts it
-            jda_image_adopt_prescan(imgs[i], (uint32_t)(I.mcus_x * I.mcus_y), it.sst[2], (int32_t)it.sst[3], it.sst[4]);
+        rounds_max = std::max(rounds_max, jda_prescan_rounds_used(it.sst));
+        if (jda_prescan_verdict(it.sst, NULL, 0)) {                      // (the host filter placed the markers)
+            jda_image_adopt_prescan(imgs[i], (uint32_t)(I.mcus_x * I.mcus_y), it.sst[JDA_ST_MAX_AC], (int32_t)it.sst[JDA_ST_MAX_DC], it.sst[JDA_ST_TRUNC]);
             it.d->prescan_on_device = 1;
         } else {                                                         // corrupt or truncated stream: the serial pre-scan knows what the reference does
             jda_image_run_host_prescan(imgs[i]);

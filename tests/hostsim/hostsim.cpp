@@ -19,6 +19,7 @@ static int g_trace_seg = -1;
 #define JDA_SEG_TRACE_HOOK(OP, seg, p, k, kk, b2, bn, ends, iend, next_bit, nr, nblk, e, inval) do { if ((int)(seg) == g_trace_seg) fprintf(stderr, "  op %d seg %u: p %u (abs %u) k %u kk %u b2 %u bn %u ends %d iend %d next_bit %d nr %u nblk %u e %04x inval %d\n", (int)(OP), (unsigned)(seg), (unsigned)(p), (unsigned)((seg) * 2048u + (p)), (unsigned)(k), (unsigned)(kk), (unsigned)(b2), (unsigned)(bn), (int)(ends), (int)(iend), (int)(next_bit), (unsigned)(nr), (unsigned)(nblk), (unsigned)(e), (int)(inval)); } while (0)
 #include "../../jpegdec_amd/csrc/jda_device_core.h"
 #include "../../jpegdec_amd/csrc/jda_plan.h"
+#include "../../jpegdec_amd/csrc/jda_prescan_plan.h"
 
 static unsigned long long g_chunk_items = 0;      // continuation entries decoded as chunks since the last call of hostsim_chunk_items
 extern "C" unsigned long long hostsim_chunk_items(void) { const unsigned long long n = g_chunk_items; g_chunk_items = 0; return n; }
@@ -222,6 +223,17 @@ extern "C" int hostsim_segscan_rounds(void) { return g_segscan_rounds; }
 static int g_index_equal = -1;       // after a device-pre-scanned decode: 1 if its index == the serial host pre-scan's
 extern "C" int hostsim_index_equal(void) { return g_index_equal; }
 
+// jda_prescan_plan.h as the runtime compiles it (tests/test_prescan_plan_cpu.py).  out: n_segs, cand_cap, then the arrays' bytes in the struct's order
+extern "C" void hostsim_prescan_sizes(uint32_t len, uint32_t n_intervals, uint32_t rec_cap, uint64_t *out)
+{
+    const jda_prescan_sizes Z = jda_prescan_sizes_of(len, n_intervals, rec_cap);
+    const uint64_t v[11] = { Z.n_segs, Z.cand_cap, Z.scan, Z.entry, Z.seg_sum, Z.seg_start, Z.worklist, Z.restart_pos, Z.rst_events, Z.records, Z.cands };
+    memcpy(out, v, sizeof(v));
+}
+extern "C" int hostsim_prescan_admits(uint32_t len, uint32_t rec_cap) { return jda_prescan_admits(len, rec_cap) ? 1 : 0; }
+extern "C" int hostsim_prescan_verdict(const uint32_t *stats, const uint32_t *filter_result, uint32_t n_intervals) { return jda_prescan_verdict(stats, filter_result, n_intervals) ? 1 : 0; }
+extern "C" int hostsim_prescan_rounds_used(const uint32_t *stats) { return jda_prescan_rounds_used(stats); }
+
 extern "C" int hostsim_decode(const uint8_t *jpeg, int len, int pixel_type, int options,
                               uint8_t *out, int pitch_bytes, int width_px, int rows)
 {
@@ -240,38 +252,34 @@ extern "C" int hostsim_decode(const uint8_t *jpeg, int len, int pixel_type, int 
         uint32_t sl = 0, tb = 0;
         const uint8_t *scan = jda_image_scan(img, &sl);
         const uint8_t *tables = jda_image_tables(img, &tb);
-        const uint32_t n_segs = sl / JDA_SEG_BYTES + 1u;
-        std::vector<uint32_t> padded(((size_t)n_segs * JDA_SEG_BYTES + 16) / 4 + 1, 0);
+        uint32_t n_int = 0;                                     // restart intervals: where they start in the filtered scan (+ the sentinel)
+        const uint32_t *r0 = jda_image_restart_positions(img, &n_int);
+        if (!I->restart_interval) n_int = 0;
+        const jda_prescan_sizes Z = jda_prescan_sizes_of(sl, n_int, jda_image_record_cap(img));      // the arrays as large as the device's
+        const uint32_t n_segs = Z.n_segs;
+        std::vector<uint32_t> padded(Z.scan / 4, 0);
         memcpy(padded.data(), scan, sl);
         std::vector<uint64_t> lt_store((JDA_WT_BYTES + 7) / 8);
         uint8_t *lt = (uint8_t *)lt_store.data();
 
-        std::vector<uint32_t> ea(n_segs + 1, 0), eb(n_segs + 1, 0), seg_sum((size_t)n_segs * JDA_SEG_SUM_WORDS), seg_start((size_t)n_segs * 5, 0);
+        std::vector<uint32_t> ea(Z.entry / 4, 0), seg_sum(Z.seg_sum / 4), seg_start(Z.seg_start / 4, 0);
         jda_segscan_params P;
         memset(&P, 0, sizeof(P));
         P.scan = (const uint8_t *)padded.data(); P.tables = tables;
         P.seg_sum = seg_sum.data(); P.seg_start = seg_start.data();
         P.blk_index = dev_index.data(); P.blk_dc = dev_dc.data();
-        P.scan_len = sl; P.n_segs = n_segs; P.n_blocks_total = (uint32_t)nb;
-        P.nblocks = (uint8_t)I->blocks_per_mcu; P.nluma = (uint8_t)(I->blocks_per_mcu - (I->ncomp == 3 ? 2 : 0));
-        uint8_t q_id[3];
-        jda_image_component_ids(img, P.dc_id, P.ac_id, q_id);
-        std::vector<uint32_t> rp;                               // restart intervals: where they start in the filtered scan + the sentinel
-        if (I->restart_interval) {
-            uint32_t n_int = 0;
-            const uint32_t *r0 = jda_image_restart_positions(img, &n_int);
-            rp.assign(r0, r0 + n_int); rp.push_back(JDA_RST_SENTINEL);
-            P.restart_pos = rp.data(); P.n_intervals = n_int; P.interval_blocks = (uint32_t)I->restart_interval * P.nblocks;
-            P.round_last = ((uint32_t)(I->mcus_x * I->mcus_y) % (uint32_t)I->restart_interval) == 0 ? 1u : 0u;
-        }
+        uint8_t dc_id[3], ac_id[3], q_id[3];
+        jda_image_component_ids(img, dc_id, ac_id, q_id);
+        jda_prescan_fill_geometry(P, *I, dc_id, ac_id, sl, n_segs, n_int);
+        std::vector<uint32_t> rp(r0, r0 + n_int);
+        if (n_int) { rp.push_back(JDA_RST_SENTINEL); P.restart_pos = rp.data(); }
         for (uint32_t tid = 0; tid < 256; tid++) jda_walk_tables_from(tables, jda_wt_dc_follow(P), tid, 256, lt);
         const bool rst = P.restart_pos != nullptr;
         // the passes as jda_pipeline / jda_upload_batch run them
-        std::vector<uint32_t> records, cands, stats(80, 0), rst_events;
-        P.rec_cap = jda_image_record_cap(img); P.cand_cap = std::max<uint32_t>(1024u, n_segs * 16u);
-        records.assign((size_t)n_segs * P.rec_cap, 0xdeadbeefu); cands.assign((size_t)P.cand_cap * 4, 0);
+        std::vector<uint32_t> records(Z.records / 4, 0xdeadbeefu), cands(Z.cands / 4, 0), stats(JDA_ST_WORDS, 0), rst_events(Z.rst_events / 4, 0);
+        P.rec_cap = jda_image_record_cap(img); P.cand_cap = Z.cand_cap;
         P.records = records.data(); P.cands = cands.data(); P.stats = stats.data();
-        if (rst) { rst_events.assign((size_t)P.n_intervals * 2 + 2, 0); P.rst_events = rst_events.data(); }
+        if (rst) P.rst_events = rst_events.data();
         jda_seg_sum S;
         jda_seg_stats ST;
         memset(&ST, 0, sizeof(ST));
@@ -288,7 +296,7 @@ extern "C" int hostsim_decode(const uint8_t *jpeg, int len, int pixel_type, int 
             }
             for (uint32_t seg = 0; seg < n_segs; seg++) list.push_back(seg);
             rounds = 1;
-            while (!list.empty() && rounds < 57) {
+            while (!list.empty() && rounds < JDA_PRESCAN_MAX_ROUND + 1u) {
                 const std::vector<uint32_t> snap(E);            // (a round's lanes read what the round before left)
                 next.clear();
                 for (uint32_t seg : list) {
@@ -309,15 +317,16 @@ extern "C" int hostsim_decode(const uint8_t *jpeg, int len, int pixel_type, int 
                 rounds++;
             }
             settled = list.empty();
-            if (g_states_first) {                               // .. and ONE recording round over every segment, from its settled entry state (round number 56)
+            stats[JDA_ST_SETTLED] = settled ? 1u : 0u;          // (jda_segscan_tail)
+            if (g_states_first) {                               // .. and ONE recording round over every segment, from its settled entry state (round number JDA_PRESCAN_MAX_ROUND)
                 for (uint32_t seg = 0; seg < n_segs; seg++) {
                     const uint32_t *slot = padded.data() + (size_t)seg * (JDA_SEG_BYTES / 4);
                     const uint32_t entry = seg == 0 ? 0u : E[seg];
-                    const uint32_t x = rst ? jda_seg_walk<JDA_SEG_RECORD, true>(P, seg, entry, slot, lt, S, ST, 56u) : jda_seg_walk<JDA_SEG_RECORD, false>(P, seg, entry, slot, lt, S, ST, 56u);
+                    const uint32_t x = rst ? jda_seg_walk<JDA_SEG_RECORD, true>(P, seg, entry, slot, lt, S, ST, JDA_PRESCAN_MAX_ROUND) : jda_seg_walk<JDA_SEG_RECORD, false>(P, seg, entry, slot, lt, S, ST, JDA_PRESCAN_MAX_ROUND);
                     uint32_t *o = &seg_sum[(size_t)seg * JDA_SEG_SUM_WORDS];
                     o[0] = S.nblk; o[1] = (uint32_t)S.dcsum[0]; o[2] = (uint32_t)S.dcsum[1]; o[3] = (uint32_t)S.dcsum[2]; o[4] = S.phase_map;
-                    o[5] = S.bad | (S.max_ac << 4); o[6] = S.lag_last; o[7] = 56u;
-                    if (seg + 1 < n_segs && x != E[seg + 1]) settled = false;      // (a recording walk leaves the state a SPEC walk leaves)
+                    o[5] = S.bad | (S.max_ac << 4); o[6] = S.lag_last; o[7] = JDA_PRESCAN_MAX_ROUND;
+                    if (seg + 1 < n_segs && x != E[seg + 1]) stats[JDA_ST_ROUND0 + JDA_PRESCAN_MAX_ROUND + 1u]++;      // (a recording walk leaves the state a SPEC walk leaves: the list behind the last round stays empty, jda_fused_item)
                 }
             }
             for (uint32_t i = 0; i <= n_segs; i++) ea[i] = E[i];
@@ -339,56 +348,52 @@ extern "C" int hostsim_decode(const uint8_t *jpeg, int len, int pixel_type, int 
                 fprintf(stderr, "round %u: %u of %u states true, %u dead\n", r, good, n_segs + 1, dead);
             }
         }
-        bool ok = settled;
-        {   // the host's sums (jda_upload_batch)
+        {   // the sums (jda_segscan_sums)
             uint64_t g = 0;
             int32_t pred[3] = { 0, 0, 0 };
             uint32_t j = 0;
             for (uint32_t i = 0; i < n_segs; i++) {
-                uint32_t *st = &seg_start[(size_t)i * 5];
+                uint32_t *st = &seg_start[(size_t)i * JDA_SEG_START_WORDS];
                 const uint32_t *su = &seg_sum[(size_t)i * JDA_SEG_SUM_WORDS];
                 st[0] = g > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)g; st[1] = (uint32_t)pred[0]; st[2] = (uint32_t)pred[1]; st[3] = (uint32_t)pred[2]; st[4] = j;
                 g += su[0];
                 if (su[5] & 1u) {
-                    if (g < (uint64_t)nb + 1) ok = false;
-                    for (uint32_t r = i + 1; r < n_segs; r++) seg_start[(size_t)r * 5] = 0xfffffff0u;
+                    for (uint32_t r = i + 1; r < n_segs; r++) seg_start[(size_t)r * JDA_SEG_START_WORDS] = 0xfffffff0u;
                     break;
                 }
                 if (su[5] & JDA_SEG_HAS_RESTART) { pred[0] = (int32_t)su[1]; pred[1] = (int32_t)su[2]; pred[2] = (int32_t)su[3]; }   // an interval ended inside: its sums count from there
                 else { pred[0] += (int32_t)su[1]; pred[1] += (int32_t)su[2]; pred[2] += (int32_t)su[3]; }
                 j = (su[4] >> (3u * j)) & 7u;
             }
-            if (g < (uint64_t)nb + 1) ok = false;
+            stats[JDA_ST_INDEX_OK] = g >= (uint64_t)nb + 1 ? 1u : 0u;      // else: the scan ends before the image does
         }
-        memset(&ST, 0, sizeof(ST));
-        uint32_t terminal = 0;
         {                                                       // finalize + candidates (jda_segscan_finalize, jda_segscan_resolve_cands)
             jda_fin_acc A;
             A.bad = 0; A.terminal = 0; A.max_abs_dc = 0;
             for (uint32_t seg = 0; seg < n_segs; seg++) {
-                const uint32_t *st = &seg_start[(size_t)seg * 5];
+                const uint32_t *st = &seg_start[(size_t)seg * JDA_SEG_START_WORDS];
                 if (st[0] > P.n_blocks_total) break;
                 uint32_t nblk = seg_sum[(size_t)seg * JDA_SEG_SUM_WORDS];
                 if (nblk > P.rec_cap) { nblk = P.rec_cap; A.bad = 1; }
                 for (uint32_t i = 0; i < nblk; i++) jda_finalize_item(P, seg, i, st[0], st[0] % P.nblocks, jda_fin_recip(P.nblocks), (int32_t)st[1], (int32_t)st[2], (int32_t)st[3], jda_fin_rst_from(seg_sum[(size_t)seg * JDA_SEG_SUM_WORDS + 5]), A);
                 const uint32_t mac = (seg_sum[(size_t)seg * JDA_SEG_SUM_WORDS + 5] >> 4) & 15u;
-                if (mac > ST.max_ac_bits) ST.max_ac_bits = mac;
+                if (mac > stats[JDA_ST_MAX_AC]) stats[JDA_ST_MAX_AC] = mac;
             }
             g_prescan_cands = stats[JDA_ST_NCAND];
             if (stats[JDA_ST_NCAND] > P.cand_cap) A.bad = 1;
-            else for (uint32_t ci = 0; ci < stats[JDA_ST_NCAND]; ci++) ST.trunc_events += jda_resolve_item(P, ci);
+            else for (uint32_t ci = 0; ci < stats[JDA_ST_NCAND]; ci++) stats[JDA_ST_TRUNC] += jda_resolve_item(P, ci);
             if (rst) for (uint32_t nr = 1; nr < P.n_intervals; nr++) {                                          // every marker where the MCU count puts it
                 const uint32_t mis = jda_rst_event_item(P, nr);
                 if (mis && getenv("HOSTSIM_DEBUG")) fprintf(stderr, "restart event %u of %u: ev %u/%u round %u, seg round %u g0 %u want %u\n", nr, P.n_intervals, rst_events[2 * nr] >> 11, rst_events[2 * nr] & 2047u, rst_events[2 * nr + 1],
-                                                            seg_sum[(size_t)(rst_events[2 * nr] >> 11) * JDA_SEG_SUM_WORDS + 7], seg_start[(size_t)(rst_events[2 * nr] >> 11) * 5], nr * P.interval_blocks);
-                ST.bad |= mis;
+                                                            seg_sum[(size_t)(rst_events[2 * nr] >> 11) * JDA_SEG_SUM_WORDS + 7], seg_start[(size_t)(rst_events[2 * nr] >> 11) * JDA_SEG_START_WORDS], nr * P.interval_blocks);
+                stats[JDA_ST_RST_MISMATCH] |= mis;
             }
             if (getenv("HOSTSIM_DEBUG")) fprintf(stderr, "finalize: bad %u terminal %u cands %u\n", A.bad, A.terminal, stats[JDA_ST_NCAND]);
-            ST.bad |= A.bad; terminal = A.terminal; ST.max_abs_dc = A.max_abs_dc;
+            stats[JDA_ST_BAD] = A.bad; stats[JDA_ST_TERMINAL] = A.terminal; stats[JDA_ST_MAX_DC] = A.max_abs_dc;
         }
-        if (ok && !ST.bad && terminal == 1) {
-            g_prescan_trunc = ST.trunc_events;
-            jda_image_adopt_prescan(img, (uint32_t)(I->mcus_x * I->mcus_y), ST.max_ac_bits, (int32_t)ST.max_abs_dc, ST.trunc_events);
+        if (jda_prescan_verdict(stats.data(), NULL, 0)) {        // (the host filter placed the markers: as jda_upload_batch decides)
+            g_prescan_trunc = stats[JDA_ST_TRUNC];
+            jda_image_adopt_prescan(img, (uint32_t)(I->mcus_x * I->mcus_y), stats[JDA_ST_MAX_AC], (int32_t)stats[JDA_ST_MAX_DC], stats[JDA_ST_TRUNC]);
             g_prescan_used = 2;
             int32_t e2 = 0;
             jda_image *ref = jda_prepare(jpeg, len, &e2);
@@ -408,10 +413,10 @@ extern "C" int hostsim_decode(const uint8_t *jpeg, int len, int pixel_type, int 
                 same_index = pb >= pa && pb <= pa + 41u;
             }
             g_index_equal = same_index && memcmp(jda_image_block_dc(ref), dev_dc.data(), nb * 2) == 0 &&
-                            jda_image_truncation_events(ref) == ST.trunc_events && jda_image_fast_mul(ref) == jda_image_fast_mul(img) ? 1 : 0;
+                            jda_image_truncation_events(ref) == stats[JDA_ST_TRUNC] && jda_image_fast_mul(ref) == jda_image_fast_mul(img) ? 1 : 0;
             if (ref && getenv("HOSTSIM_DEBUG")) {
                 for (size_t i = 0; i <= nb; i++) if (hi[i] != dev_index[i] || (i < nb && jda_image_block_dc(ref)[i] != dev_dc[i])) { fprintf(stderr, "first diff at block %zu of %zu: host %u/%u dc %d, dev %u/%u dc %d\n", i, nb, hi[i] >> 7, hi[i] & 127, i < nb ? jda_image_block_dc(ref)[i] : 0, dev_index[i] >> 7, dev_index[i] & 127, i < nb ? dev_dc[i] : 0); break; }
-                fprintf(stderr, "rounds %u trunc host %u dev %u\n", rounds, jda_image_truncation_events(ref), ST.trunc_events);
+                fprintf(stderr, "rounds %u trunc host %u dev %u\n", rounds, jda_image_truncation_events(ref), stats[JDA_ST_TRUNC]);
                 for (size_t i = 0; i < nb; i++) {                   // the first entry that differs in what counts (position, flag, flagged entry, DC value)
                     const uint32_t a = hi[i], b = dev_index[i];
                     const uint32_t pa = (a >> JDA_INDEX_OFF_BITS) * 8u + (a & (JDA_INDEX_TRUNC - 1u)), pb = (b >> JDA_INDEX_OFF_BITS) * 8u + (b & (JDA_INDEX_TRUNC - 1u));
@@ -421,7 +426,7 @@ extern "C" int hostsim_decode(const uint8_t *jpeg, int len, int pixel_type, int 
             }
             if (ref) jda_image_free(ref);
         } else {                                                // corrupt / truncated: the serial pre-scan, as jda_upload_batch does
-            if (getenv("HOSTSIM_DEBUG")) fprintf(stderr, "segment path rejected: ok %d settled %d rounds %u bad %u terminal %u\n", (int)ok, (int)settled, rounds, ST.bad, terminal);
+            if (getenv("HOSTSIM_DEBUG")) fprintf(stderr, "segment path rejected: index ok %u settled %d rounds %u bad %u mismatch %u terminal %u\n", stats[JDA_ST_INDEX_OK], (int)settled, rounds, stats[JDA_ST_BAD], stats[JDA_ST_RST_MISMATCH], stats[JDA_ST_TERMINAL]);
             jda_image_run_host_prescan(img);
             dev_index.clear(); dev_dc.clear();
         }

@@ -314,8 +314,8 @@ def test_bound_holds_for_optimised_files(sim):
 
 
 def test_refusals(sim):
-    surf = np.zeros((64, 256), dtype=np.uint8)
-    dst = np.zeros(4096, dtype=np.uint8)
+    mem = np.zeros(4096 + 64 * 256, dtype=np.uint8)          # dst in FRONT of surf: the source range `wide` claims below runs 2.6 GB on from surf and must not cover dst
+    dst, surf = mem[:4096], mem[4096:].reshape(64, 256)
 
     def check(flags, n=1, job=(0, 0, 16, 16, 3, 75, 0, 0), out=None, bpp=4):
         o = (Output * max(n, 1))(*[Output(*(out or (surf.ctypes.data, 256, 64, 64)))] * max(n, 1))
