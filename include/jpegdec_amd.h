@@ -184,6 +184,15 @@ int jda_index_equivalent(const uint32_t *a, const uint32_t *b, uint32_t n_blocks
  * into buf (NUL-terminated, truncated at cap); returns the bytes the whole report needs.  (Diagnostics: the GPU test-suite
  * holds itself to every kernel the library ships.) */
 int jda_kernel_launch_counts(char *buf, int cap);
+/* Internal (tests, tools): the decode kernel deals the last quads of a launch that fills the GPU at run time ("the
+ * pool").  jda_internal_set_decode_pool forces the launches' workgroup cap and the pool's share of the quads in 1/1000 (at most
+ * 500), so that a small image runs the pool too -- a forced cap also lifts the rule that a workgroup's run is eight quads and more;
+ * 0, 0 restores the defaults (one workgroup per CU, the built-in share).  Process-wide, for the launches made after it.
+ * jda_internal_decode_pool_last: of the last launch of the decode kernel, once the caller has synchronised with it: out[0] the
+ * quads in its pool (0: it had none), out[1] the claims its workgroups made, out[2] those that found the pool empty (one per
+ * workgroup), out[3] the counter slot it used (-1: none).  JDA_ERROR_HIP if the launch did not leave its counters zeroed. */
+int jda_internal_set_decode_pool(int32_t grid_cap_override, int32_t pool_permille);
+int jda_internal_decode_pool_last(int32_t out[4]);
 /* the table blob uploaded to the GPU: DC LUTs 2x1024 B, AC LUTs 2x2048 uint16, quant 4x64 int16, zigzag 64 B,
  * and (ours) the end-of-block code of each AC table, 2 x uint32 = (32 - length) << 16 | code */
 const uint8_t *jda_image_tables(const jda_image *img, uint32_t *bytes);

@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <mutex>
 
 // A kernel's dynamic-LDS limit is a property of the function ON A DEVICE: set once per device and kernel (a process may drive
 // several GPUs -- JPEGDEC::setDevice, jda_node -- from several threads: the flags are atomic, the attribute call is idempotent).
@@ -195,14 +196,99 @@ __device__ __forceinline__ jda_strip jda_load_record(const jda_strip *tp)
 // image; tiles are drawn in order, so every wavefront meets an image boundary of the run exactly once: all
 // wait at a barrier, the wavefront that drew the new image's first tile restages the tables, second barrier.
 // A wavefront that runs out of tiles still walks the remaining boundaries (the barrier counts every wave).
+//
+// The tail of a launch (the pool): the static split leaves the CUs finishing some per cent apart, and the kernel ends with the
+// slowest.  So a launch that fills the GPU with tiles of ONE table generation keeps its last n_pool quads (groups of n_waves
+// tiles) out of the split; a workgroup that has drawn its own run goes on drawing, and what it draws past the run (a "virtual
+// run") maps, chunk of n_waves draws by chunk, to quads claimed from the pool: one lane's returning atomicAdd on a counter in
+// global memory, made one quad ahead of need by the wavefront that draws the first tile of the quad before.  pool_map[c] in
+// LDS is chunk c's quad (JDA_POOL_UNSET until its claim has returned, JDA_POOL_NONE when the pool was empty).  Nothing else
+// changes: a pool tile goes through the wavefronts' two-ahead draw like an own tile, and its image's first tile starts cold
+// like any first tile of an image (the tables are the staged ones: one generation).
+#define JDA_POOL_CHUNKS 32u                    // pool_map entries: quads a workgroup can take from the pool
+#define JDA_POOL_LDS (16u + 4u * JDA_POOL_CHUNKS)   // behind the draw counter and tab_src: {the pool's first quad, -, -, -}, pool_map
+#define JDA_POOL_UNSET 0xfffffffeu
+#define JDA_POOL_NONE 0xffffffffu
+#define JDA_NO_TILE 0xffffffffu                // what a draw past the run (and past the pool) gives
+#define JDA_POOL_SLOTS_DEV 32
+// {claims, done} of the launch that has the slot, and what the launch before it left: one slot per stream that launches decodes
+// (launches of a stream run one after the other), lent by the host (jda_decode_pool_slot).  done: workgroups that have made
+// their last claim (low half) and, of those, the ones that stopped at pool_map's capacity instead of at an empty pool (high
+// half).  The workgroup whose add to `done` finds all the others there copies both words to last_* (jda_internal_decode_pool_last)
+// and zeroes the pair for the stream's next launch: no memset, no kernel of its own.
+struct __attribute__((aligned(128))) jda_pool_counters { uint32_t claims, done, last_claims, last_done; };
+__device__ jda_pool_counters g_jda_pool[JDA_POOL_SLOTS_DEV];
+
+// one lane, after this workgroup's last claim has returned
+__device__ __forceinline__ void jda_pool_leave(jda_pool_counters *P, uint32_t add)
+{
+    const uint32_t d = __hip_atomic_fetch_add(&P->done, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((d & 0xffffu) != gridDim.x - 1u) return;
+    // every other workgroup added to `done` behind the return of its last claim: `claims` is final
+    __hip_atomic_store(&P->last_claims, __hip_atomic_load(&P->claims, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&P->last_done, d + add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&P->claims, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&P->done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A draw at or past t_claim in the tile loop (rare: the run's last own quad and the virtual run; without a pool the draws past the run).
+// big: bit 0 the window size, bits 1-7 the counter slot, bits 8-31 n_pool.  t_claim: the first tile of the run's last own quad
+// (pool on) or the run's end (no pool).  Returns the tile's index in the list or JDA_NO_TILE.
+template <uint32_t WAVES0, uint32_t WAVES1>
+__device__ __forceinline__ uint32_t jda_pool_resolve(uint32_t v, uint32_t t_claim, uint32_t big, uint32_t *ctr, uint32_t lane)
+{
+    // (nothing of this path is computed ahead of it, in the tile loop's registers: the compiler takes these two for new values here)
+    asm volatile("" : "+s"(big), "+s"(t_claim));
+    const uint32_t n_pool = big >> 8, n_waves = (big & 1u) ? WAVES1 : WAVES0;
+    if (n_pool == 0u) return JDA_NO_TILE;
+    typedef volatile uint32_t __attribute__((address_space(3))) lds_u32;      // (ds_ instructions: a volatile access through the generic pointer is a flat one)
+    lds_u32 *hdr = (lds_u32 *)JDA_LDS_A32(ctr + 4);
+    lds_u32 *pool_map = hdr + 4;
+    const uint32_t t_end = t_claim + n_waves;
+    uint32_t tile = v, c_next = 0u, leave = 0u;                 // the chunk this draw claims, what it adds to `done`
+    bool claim = v == t_claim;                                  // the first tile of the last own quad claims chunk 0
+    if (v >= t_end) {
+        const uint32_t k = v - t_end, c = (big & 1u) ? k / WAVES1 : k / WAVES0, r = k - c * n_waves;
+        if (c >= JDA_POOL_CHUNKS) return JDA_NO_TILE;
+        // Chunk c is published by the wavefront that drew the first tile of the quad before it -- an earlier draw (the counter
+        // in LDS hands the indices out in order), so that wavefront is in this function already, or through it.  The wait
+        // ends: every wavefront of the workgroup is resident (one workgroup per CU, all started together); a publisher waits
+        // at most here, for a chunk BELOW the one it publishes (chunk 0's publisher for nothing), and between its claim and its
+        // publish for no other wavefront, only for its own atomic's return; and a pool launch has one table generation, so no
+        // wavefront waits at a workgroup barrier inside the tile loop while another polls here.
+        __builtin_amdgcn_s_setprio(0);
+        uint32_t quad;
+        while ((quad = jda_uni32(pool_map[c])) == JDA_POOL_UNSET) __builtin_amdgcn_s_sleep(2);
+        tile = quad == JDA_POOL_NONE ? JDA_NO_TILE : quad * n_waves + r;
+        c_next = c + 1u;
+        if (r == 0u) {                                          // the first tile of a chunk sees to the next one
+            if (c_next >= JDA_POOL_CHUNKS) leave = quad != JDA_POOL_NONE ? 0x10001u : 0u;   // no room for it: the workgroup is done with the pool
+            else if (quad != JDA_POOL_NONE) claim = true;
+            else if (lane == 0) pool_map[c_next] = JDA_POOL_NONE;                          // the failing claim has been made: the same for the next chunk
+        }
+    }
+    if ((claim || leave) && lane == 0) {
+        jda_pool_counters *P = &g_jda_pool[(big >> 1) & 127u];
+        if (claim) {                                            // wait for the atomic's return in place, publish at once and whatever it says
+            const uint32_t g = __hip_atomic_fetch_add(&P->claims, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pool_map[c_next] = g < n_pool ? hdr[0] + g : JDA_POOL_NONE;
+            if (g >= n_pool) leave = 1u;                        // this workgroup's one failing claim, its last
+        }
+        if (leave) jda_pool_leave(P, leave);
+    }
+    return tile;
+}
+
+// t_claim: draws below it are own tiles that claim nothing (all draws of a launch without a pool but the ones past the run)
 template <int MODE>
-__device__ __forceinline__ uint32_t jda_draw_tile(uint32_t *ctr, uint32_t lane)
+__device__ __forceinline__ uint32_t jda_draw_tile(uint32_t *ctr, uint32_t lane, uint32_t t_claim, uint32_t big)
 {
     uint32_t v = 0;
     if (lane == 0) v = atomicAdd(ctr, 1u);            // ds_add_rtn_u32
-    return jda_uni32(v);
+    v = jda_uni32(v);
+    if (__builtin_expect(v >= t_claim, 0)) v = jda_pool_resolve<jda_lds_layout<MODE, 0>::WAVES, jda_lds_layout<MODE, 1>::WAVES>(v, t_claim, big, ctr, lane);
+    return v;
 }
-
 // per-lane index / DC entries of a tile + the entry just past it (for the window bounds)
 // CONT: also the block's place in the continuation entries (cf0 .. cf1: jda_p1c_*)
 template <int MODE, int CONT = 0>
@@ -297,19 +383,22 @@ void jda_decode_tiles_persistent(const jda_dev_desc *__restrict__ descs, const j
     typedef jda_lds_layout<MODE, 0> L;
     typedef jda_lds_layout<MODE, 1> LB;
     // (one live SGPR: the three numbers are selects between constants wherever they are used)
-#define n_waves (big ? (uint32_t)LB::WAVES : (uint32_t)L::WAVES)
-#define wave_bytes (big ? (uint32_t)LB::WAVE_BYTES : (uint32_t)L::WAVE_BYTES)
-#define win_bytes (big ? (uint32_t)LB::WIN_BYTES : (uint32_t)L::WIN_BYTES)
+#define n_waves ((big & 1u) ? (uint32_t)LB::WAVES : (uint32_t)L::WAVES)
+#define wave_bytes ((big & 1u) ? (uint32_t)LB::WAVE_BYTES : (uint32_t)L::WAVE_BYTES)
+#define win_bytes ((big & 1u) ? (uint32_t)LB::WIN_BYTES : (uint32_t)L::WIN_BYTES)
     static_assert(jda_lds_layout<MODE, 0>::WIN_CHUNKS == jda_lds_layout<MODE, 1>::WIN_CHUNKS, "both window sizes are staged by the same copy loop");
     typedef jda_chunks<L::WIN_CHUNKS> chunks_t;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     // runs of n_quads / grid groups of tiles, the remainder one more each for the first workgroups (rounding the run length up
     // instead left the last workgroups of a 64-image batch with half a run and none: 0.6 % of the kernel's time)
-    const uint32_t per = n_quads / gridDim.x, rem = n_quads % gridDim.x;
+    // (the last big >> 8 quads are the pool and not part of the split: jda_pool_resolve; the host gives every workgroup a quad of its own then)
+    const uint32_t n_own = n_quads - (big >> 8);
+    const uint32_t per = n_own / gridDim.x, rem = n_own % gridDim.x;
     const uint32_t q0 = blockIdx.x * per + (blockIdx.x < rem ? blockIdx.x : rem);
     const uint32_t q_end = q0 + per + (blockIdx.x < rem ? 1u : 0u);
     if (q0 >= q_end) return;
     const uint32_t t_begin = q0 * n_waves, t_end = q_end * n_waves;                       // this workgroup's run of tiles
+    const uint32_t t_claim = (big >> 8) ? t_end - n_waves : t_end;                        // draws from here on: jda_pool_resolve
     unsigned long long *wgtrace = g_jda_wgtrace;
     if (wgtrace && lane == 0) wgtrace[(blockIdx.x * 16u + wave) * 2u] = wall_clock64();
     uint8_t *tab = lds;
@@ -318,7 +407,10 @@ void jda_decode_tiles_persistent(const jda_dev_desc *__restrict__ descs, const j
     unsigned long long *tab_src = (unsigned long long *)(ctr + 2);                          // where the next image's tables are (JDA_ADVANCE_TABLES)
 
     // ---- prologue: the tables of the run's first image, the counter
-    if (threadIdx.x == 0) *ctr = t_begin;
+    // (a wavefront's first two tiles are not drawn: wavefront w takes tiles w and n_waves + w of the run, the counter starts behind them --
+    // with a pool they lie in front of the run's last own quad, which has the first claim to make: launch_persistent gives a run three quads)
+    if (threadIdx.x == 0) *ctr = t_begin + 2u * n_waves;
+    if ((big >> 8) && threadIdx.x < 4u + JDA_POOL_CHUNKS) ctr[4u + threadIdx.x] = threadIdx.x == 0 ? n_own : JDA_POOL_UNSET;   // the pool's first quad, pool_map
     const jda_strip R0 = jda_load_record(tiles + t_begin);
     uint32_t staged = R0.ord;                                                            // image (ordinal) whose tables are in LDS
     const uint32_t last_ord = jda_load_record(tiles + (t_end - 1u)).ord;
@@ -326,13 +418,14 @@ void jda_decode_tiles_persistent(const jda_dev_desc *__restrict__ descs, const j
     jda_p0_tables(Dc, threadIdx.x, 64u * n_waves, tab, L::LONG_LDS != 0);
     __syncthreads();                                  // tables staged, counter set
 
-    uint32_t i_cur = jda_draw_tile<MODE>(ctr, lane);
-    if (i_cur >= t_end) {                             // more wavefronts than tiles: only keep the barriers company
+    const uint32_t wave_u = jda_uni32(wave);
+    uint32_t i_cur = t_begin + wave_u < t_claim ? t_begin + wave_u : JDA_NO_TILE;
+    if (i_cur == JDA_NO_TILE) {                             // more wavefronts than tiles: only keep the barriers company
         jda_strip none = R0;
         JDA_ADVANCE_TABLES(last_ord, false, none, Dc);
         return;
     }
-    uint32_t i_nxt = jda_draw_tile<MODE>(ctr, lane);
+    uint32_t i_nxt = t_begin + n_waves + wave_u < t_claim ? t_begin + n_waves + wave_u : JDA_NO_TILE;
     jda_strip S = jda_load_record(tiles + i_cur);
     if (S.image != R0.image) Dc = jda_desc_uniform<VARIANT, MODE>(descs + S.image);
     jda_p1_inputs in;
@@ -357,7 +450,7 @@ void jda_decode_tiles_persistent(const jda_dev_desc *__restrict__ descs, const j
     jda_p4_prepare<MODE>(P4, Dc, lane);
     if (lane < 8) ((uint32_t *)(wl + L::CNT_OFF))[lane] = 0;
     jda_strip Sn = S;
-    if (i_nxt < t_end) Sn = jda_load_record(tiles + i_nxt);
+    if (i_nxt != JDA_NO_TILE) Sn = jda_load_record(tiles + i_nxt);
     JDA_ADVANCE_TABLES(S.ord, true, S, Dc);
     jda_lane_pre LP;                                  // the lane's Huffman LUTs / quantiser table / EOB code in this image (reads the staged tables)
     jda_lane_prepare<MODE>(LP, Dc, lane, tab);
@@ -370,16 +463,16 @@ void jda_decode_tiles_persistent(const jda_dev_desc *__restrict__ descs, const j
     for (;;) {
         const jda_dev_desc &D = Dc;
         JDA_PTRACE(0);
-        const bool have_next = i_nxt < t_end;
+        const bool have_next = i_nxt != JDA_NO_TILE;
         // the software pipeline runs inside an image; the first tile of the next image starts cold (below) -- keeping a
         // second descriptor in SGPRs for that one tile cost more (SGPR spills) than the overlap was worth
         const bool pipelined = have_next && Sn.image == S.image;
         // stage A: draw the tile after the next one and start loading its record (wave-uniform 16 bytes, consumed at
         // the bottom of the loop)
-        uint32_t i_nn = t_end;
-        if (have_next) i_nn = jda_draw_tile<MODE>(ctr, lane);
+        uint32_t i_nn = JDA_NO_TILE;
+        if (have_next) i_nn = jda_draw_tile<MODE>(ctr, lane, t_claim, big);
         uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
-        if (i_nn < t_end) { const uint32_t JDA_GLOBAL *w = JDA_G(const uint32_t, tiles + i_nn); r0 = w[0]; r1 = w[1]; r2 = w[2]; r3 = w[3]; }
+        if (i_nn != JDA_NO_TILE) { const uint32_t JDA_GLOBAL *w = JDA_G(const uint32_t, tiles + i_nn); r0 = w[0]; r1 = w[1]; r2 = w[2]; r3 = w[3]; }
         // stage B: per-lane index entries of the next tile; in flight during this tile's entropy phase
         jda_p1_inputs inn;
         uint32_t ixn_end = 0;
@@ -467,16 +560,78 @@ void jda_decode_tiles_persistent(const jda_dev_desc *__restrict__ descs, const j
 #undef win_bytes
 }
 
+// ---- the pool of a launch's last quads (jda_pool_resolve), host side
+#ifndef JDA_POOL_PERMILLE_DEFAULT
+#define JDA_POOL_PERMILLE_DEFAULT 30         // share of a launch's quads that is dealt at run time (profiles/decode_pool_wg_balance.txt)
+#endif
+// the counter slots of g_jda_pool, one per stream that launches decodes (any device: every device has its own copy of the array)
+static std::mutex g_pool_slot_mutex;
+static hipStream_t g_pool_slot_stream[JDA_POOL_SLOTS_DEV];
+static bool g_pool_slot_used[JDA_POOL_SLOTS_DEV];
+static int jda_decode_pool_slot(hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lock(g_pool_slot_mutex);
+    int free_slot = -1;
+    for (int i = 0; i < JDA_POOL_SLOTS_DEV; i++) {
+        if (g_pool_slot_used[i] && g_pool_slot_stream[i] == stream) return i;
+        if (!g_pool_slot_used[i] && free_slot < 0) free_slot = i;
+    }
+    if (free_slot >= 0) { g_pool_slot_used[free_slot] = true; g_pool_slot_stream[free_slot] = stream; }
+    return free_slot;
+}
+// the stream is about to be destroyed (its work is done): its slot is free again
+extern "C" void jda_decode_pool_release(hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lock(g_pool_slot_mutex);
+    for (int i = 0; i < JDA_POOL_SLOTS_DEV; i++) if (g_pool_slot_used[i] && g_pool_slot_stream[i] == stream) g_pool_slot_used[i] = false;
+}
+// test hooks (include/jpegdec_amd.h): a forced grid cap and pool share, so that small images run the pool; the last launch's pool
+static std::atomic<int> g_pool_grid_cap_override(0), g_pool_permille_override(0);
+static std::atomic<int> g_pool_last_n(0), g_pool_last_slot(-1), g_pool_last_device(0);
+extern "C" int jda_internal_set_decode_pool(int32_t grid_cap_override, int32_t pool_permille)
+{
+    if (grid_cap_override < 0 || grid_cap_override > 65535 || pool_permille < 0 || pool_permille > 500) return JDA_INVALID_PARAMETER;
+    g_pool_grid_cap_override.store(grid_cap_override, std::memory_order_relaxed);
+    g_pool_permille_override.store(pool_permille, std::memory_order_relaxed);
+    return JDA_SUCCESS;
+}
+// out: n_pool of the last persistent decode launch, the claims it made, the failing ones among them, its counter slot (-1: no pool).
+// The caller has synchronised with the launch.
+extern "C" int jda_internal_decode_pool_last(int32_t out[4])
+{
+    if (!out) return JDA_INVALID_PARAMETER;
+    out[0] = g_pool_last_n.load(std::memory_order_relaxed); out[1] = out[2] = 0; out[3] = g_pool_last_slot.load(std::memory_order_relaxed);
+    if (out[0] <= 0 || out[3] < 0) { out[0] = 0; out[3] = -1; return JDA_SUCCESS; }
+    jda_pool_counters c;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipSetDevice(g_pool_last_device.load(std::memory_order_relaxed));
+    const hipError_t e = hipMemcpyFromSymbol(&c, HIP_SYMBOL(g_jda_pool), sizeof(c), (size_t)out[3] * sizeof(jda_pool_counters), hipMemcpyDeviceToHost);
+    (void)hipSetDevice(dev);
+    if (e != hipSuccess) return JDA_ERROR_HIP;
+    if (c.claims != 0u || c.done != 0u) return JDA_ERROR_HIP;           // the pair was not reset
+    out[1] = (int32_t)c.last_claims;
+    out[2] = (int32_t)((c.last_done & 0xffffu) - (c.last_done >> 16));   // workgroups that left at an empty pool (one failing claim each)
+    return JDA_SUCCESS;
+}
+
+// pool_ok: the list's records are one table generation (the planner knows), and the caller's launches on `stream` run in order
 template <int MODE, int FAST, int VARIANT, int CONT = 0>
-static hipError_t launch_persistent(int big, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+static hipError_t launch_persistent(int big, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, int pool_ok, hipStream_t stream)
 {
     typedef jda_lds_layout<MODE, 0> L0;
     typedef jda_lds_layout<MODE, 1> L1;
     static_assert(L0::TAB_BYTES + L0::WAVES * L0::WAVE_BYTES + 16 <= 160 * 1024 && L1::TAB_BYTES + L1::WAVES * L1::WAVE_BYTES + 16 <= 160 * 1024, "one workgroup must fit the CU's LDS");
     static_assert(L0::WIN_BYTES >= L0::COLLIST_ENTRIES * 2 + 16 && L0::WIN_BYTES % 16 == 0 && L1::WIN_BYTES % 16 == 0 && L0::WIN_OFF % 16 == 0, "the window covers the column list and its overrun");
     const uint32_t n_waves = big ? L1::WAVES : L0::WAVES, wave_bytes = big ? L1::WAVE_BYTES : L0::WAVE_BYTES, win_bytes = big ? L1::WIN_BYTES : L0::WIN_BYTES;
-    const int lds_max = (L0::WAVES * L0::WAVE_BYTES > L1::WAVES * L1::WAVE_BYTES ? L0::WAVES * L0::WAVE_BYTES : L1::WAVES * L1::WAVE_BYTES) + L0::TAB_BYTES + 16;
-    const int lds_bytes = L0::TAB_BYTES + (int)(n_waves * wave_bytes) + 16;      // + the draw counter
+    // pool_map and the pool's first quad go behind the draw counter where the window size leaves room (4:2:0: 163,632 + 144 of 163,840 bytes)
+    constexpr int pool_lds = (int)JDA_POOL_LDS, body0 = L0::WAVES * L0::WAVE_BYTES, body1 = L1::WAVES * L1::WAVE_BYTES;
+    constexpr bool pool_room0 = L0::TAB_BYTES + body0 + 16 + pool_lds <= 160 * 1024, pool_room1 = L1::TAB_BYTES + body1 + 16 + pool_lds <= 160 * 1024;
+    constexpr int wg0 = body0 + (pool_room0 ? pool_lds : 0), wg1 = body1 + (pool_room1 ? pool_lds : 0);      // (a layout without room launches without a pool)
+    static_assert(pool_lds % 16 == 0 && L0::TAB_BYTES + wg0 + 16 <= 160 * 1024 && L1::TAB_BYTES + wg1 + 16 <= 160 * 1024, "one workgroup with the pool's map must fit the CU's LDS");
+    static_assert(MODE != JDA_MODE_420 || (pool_room0 && pool_room1), "both 4:2:0 layouts have room for the pool's map");
+    const bool pool_room = big ? pool_room1 : pool_room0;
+    const int lds_max = (wg0 > wg1 ? wg0 : wg1) + L0::TAB_BYTES + 16;
     static std::atomic<unsigned long long> attr_done(0);
     { const hipError_t e = jda_ensure_lds_limit((const void *)jda_decode_tiles_persistent<MODE, FAST, VARIANT, CONT>, lds_max, attr_done); if (e != hipSuccess) return e; }
     static std::atomic<int> grid_cap_once(0);                   // (the GPUs of a node are alike: the first device's CU count)
@@ -494,10 +649,28 @@ static hipError_t launch_persistent(int big, const jda_dev_desc *descs, const jd
         grid_cap = cus * (per_cu > 0 ? per_cu : 1) * mult;
         grid_cap_once.store(grid_cap, std::memory_order_relaxed);
     }
+    const int cap_forced = g_pool_grid_cap_override.load(std::memory_order_relaxed), permille_forced = g_pool_permille_override.load(std::memory_order_relaxed);
+    if (cap_forced) grid_cap = cap_forced;
     const uint32_t n_quads = n_tiles / n_waves;
     const uint32_t grid = n_quads < (uint32_t)grid_cap ? n_quads : (uint32_t)grid_cap;
+    // The pool: only where the launch fills the GPU with runs of eight quads and more (a forced grid cap lifts that floor: the
+    // tests' images are small), every workgroup keeps three quads of its own (its wavefronts' first two tiles each
+    // lie in front of the last own quad), and the workgroups' maps together hold the pool twice
+    uint32_t n_pool = 0;
+    int slot = -1;
+    if (pool_ok && pool_room && grid == (uint32_t)grid_cap && grid < 65536u && (cap_forced || n_quads >= 8u * grid)) {
+        n_pool = (uint32_t)((uint64_t)n_quads * (uint32_t)(permille_forced ? permille_forced : JDA_POOL_PERMILLE_DEFAULT) / 1000u);
+        if (n_pool > JDA_POOL_CHUNKS / 2u * grid) n_pool = JDA_POOL_CHUNKS / 2u * grid;
+        if (n_pool + 3u * grid > n_quads) n_pool = n_quads > 3u * grid ? n_quads - 3u * grid : 0u;
+        if (n_pool >= (1u << 24)) n_pool = (1u << 24) - 1u;
+        if (n_pool && (slot = jda_decode_pool_slot(stream)) < 0) n_pool = 0;       // no counter slot free: the static split
+    }
+    const int lds_bytes = L0::TAB_BYTES + (int)(n_waves * wave_bytes) + 16 + (n_pool ? (int)JDA_POOL_LDS : 0);      // + the draw counter (+ the pool's map)
+    g_pool_last_n.store((int)n_pool, std::memory_order_relaxed);
+    g_pool_last_slot.store(n_pool ? slot : -1, std::memory_order_relaxed);
+    if (n_pool) { int dev = 0; (void)hipGetDevice(&dev); g_pool_last_device.store(dev, std::memory_order_relaxed); }
     JDA_LAUNCH((jda_decode_tiles_persistent<MODE, FAST, VARIANT, CONT>), dim3(grid), dim3(64 * n_waves), lds_bytes, stream,
-               descs, tiles, n_quads, (uint32_t)(big ? 1 : 0));
+               descs, tiles, n_quads, (uint32_t)(big ? 1 : 0) | (n_pool ? ((uint32_t)slot << 1) | (n_pool << 8) : 0u));
     (void)win_bytes;
     return hipGetLastError();
 }
@@ -2443,7 +2616,7 @@ extern "C" hipError_t jda_internal_set_trace(unsigned long long *dev_buf)
 
 // Launch entry used by jda_runtime.cpp.  n_tiles is a multiple of jda_lds_layout<MODE>::WAVES (padded per image).
 extern "C" hipError_t jda_launch_decode(int mode, int fast_mul, int variant, int big, int cont, const jda_dev_desc *descs, const jda_strip *tiles,
-                                        uint32_t n_tiles, uint32_t aux, hipStream_t stream)
+                                        uint32_t n_tiles, uint32_t aux, int pool_ok, hipStream_t stream)
 {
     if (n_tiles == 0) return hipSuccess;
     if (cont && !fast_mul && variant == 3) {          // JDA_LIST_THUMB_FLAT: whole gray / 4:2:0 images at 1/8, a record per image
@@ -2454,8 +2627,8 @@ extern "C" hipError_t jda_launch_decode(int mode, int fast_mul, int variant, int
     if (cont) {                                       // P1 in chunks (jda_use_cont decides who gets here): the RGB8888 plain case of 4:2:0 and 4:4:4
         if (!fast_mul || variant != 1) return hipErrorInvalidValue;
         switch (mode) {
-        case JDA_MODE_444: return launch_persistent<JDA_MODE_444, 1, 1, 1>(big, descs, tiles, n_tiles, stream);
-        case JDA_MODE_420: return launch_persistent<JDA_MODE_420, 1, 1, 1>(big, descs, tiles, n_tiles, stream);
+        case JDA_MODE_444: return launch_persistent<JDA_MODE_444, 1, 1, 1>(big, descs, tiles, n_tiles, pool_ok, stream);
+        case JDA_MODE_420: return launch_persistent<JDA_MODE_420, 1, 1, 1>(big, descs, tiles, n_tiles, pool_ok, stream);
         default: return hipErrorInvalidValue;
         }
     }
@@ -2482,23 +2655,23 @@ extern "C" hipError_t jda_launch_decode(int mode, int fast_mul, int variant, int
     // big: the larger scan window for high-bitrate images, one wavefront less per workgroup (jda_big_window in jda_runtime.cpp decides)
     if (variant >= 1 && fast_mul) {                   // the plain-case kernels (jda_plain_variant decides who gets here)
         switch (mode * 4 + variant) {
-        case JDA_MODE_444 * 4 + 1: return launch_persistent<JDA_MODE_444, 1, 1>(big, descs, tiles, n_tiles, stream);
-        case JDA_MODE_420 * 4 + 1: return launch_persistent<JDA_MODE_420, 1, 1>(big, descs, tiles, n_tiles, stream);
-        case JDA_MODE_422 * 4 + 1: return launch_persistent<JDA_MODE_422, 1, 1>(big, descs, tiles, n_tiles, stream);
-        case JDA_MODE_444 * 4 + 2: return launch_persistent<JDA_MODE_444, 1, 2>(big, descs, tiles, n_tiles, stream);
-        case JDA_MODE_420 * 4 + 2: return launch_persistent<JDA_MODE_420, 1, 2>(big, descs, tiles, n_tiles, stream);
-        case JDA_MODE_420 * 4 + 3: return launch_persistent<JDA_MODE_420, 1, 3>(big, descs, tiles, n_tiles, stream);
-        case JDA_MODE_GRAY * 4 + 3: return launch_persistent<JDA_MODE_GRAY, 1, 3>(big, descs, tiles, n_tiles, stream);
+        case JDA_MODE_444 * 4 + 1: return launch_persistent<JDA_MODE_444, 1, 1>(big, descs, tiles, n_tiles, pool_ok, stream);
+        case JDA_MODE_420 * 4 + 1: return launch_persistent<JDA_MODE_420, 1, 1>(big, descs, tiles, n_tiles, pool_ok, stream);
+        case JDA_MODE_422 * 4 + 1: return launch_persistent<JDA_MODE_422, 1, 1>(big, descs, tiles, n_tiles, pool_ok, stream);
+        case JDA_MODE_444 * 4 + 2: return launch_persistent<JDA_MODE_444, 1, 2>(big, descs, tiles, n_tiles, pool_ok, stream);
+        case JDA_MODE_420 * 4 + 2: return launch_persistent<JDA_MODE_420, 1, 2>(big, descs, tiles, n_tiles, pool_ok, stream);
+        case JDA_MODE_420 * 4 + 3: return launch_persistent<JDA_MODE_420, 1, 3>(big, descs, tiles, n_tiles, pool_ok, stream);
+        case JDA_MODE_GRAY * 4 + 3: return launch_persistent<JDA_MODE_GRAY, 1, 3>(big, descs, tiles, n_tiles, pool_ok, stream);
         default: return hipErrorInvalidValue;
         }
     }
     if (variant != 0) return hipErrorInvalidValue;
     switch (mode) {                                   // the general kernels: 24- or 32-bit multiplies as the image's descriptor says
-    case JDA_MODE_GRAY: return launch_persistent<JDA_MODE_GRAY, -1, 0>(big, descs, tiles, n_tiles, stream);
-    case JDA_MODE_444: return launch_persistent<JDA_MODE_444, -1, 0>(big, descs, tiles, n_tiles, stream);
-    case JDA_MODE_420: return launch_persistent<JDA_MODE_420, -1, 0>(big, descs, tiles, n_tiles, stream);
-    case JDA_MODE_422: return launch_persistent<JDA_MODE_422, -1, 0>(big, descs, tiles, n_tiles, stream);
-    case JDA_MODE_440: return launch_persistent<JDA_MODE_440, -1, 0>(big, descs, tiles, n_tiles, stream);
+    case JDA_MODE_GRAY: return launch_persistent<JDA_MODE_GRAY, -1, 0>(big, descs, tiles, n_tiles, pool_ok, stream);
+    case JDA_MODE_444: return launch_persistent<JDA_MODE_444, -1, 0>(big, descs, tiles, n_tiles, pool_ok, stream);
+    case JDA_MODE_420: return launch_persistent<JDA_MODE_420, -1, 0>(big, descs, tiles, n_tiles, pool_ok, stream);
+    case JDA_MODE_422: return launch_persistent<JDA_MODE_422, -1, 0>(big, descs, tiles, n_tiles, pool_ok, stream);
+    case JDA_MODE_440: return launch_persistent<JDA_MODE_440, -1, 0>(big, descs, tiles, n_tiles, pool_ok, stream);
     default: return hipErrorInvalidValue;
     }
 }

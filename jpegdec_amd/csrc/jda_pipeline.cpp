@@ -801,7 +801,7 @@ int jda_pipeline_submit_ex(jda_pipeline *p, int32_t n, const uint8_t *const *jpe
     for (int m = 0; m < JDA_N_LISTS && e == hipSuccess && n_dev; m++) {
         if (!S.list_n[m]) continue;
         e = jda_launch_decode(JDA_LIST_MODE(m), JDA_LIST_FAST(m), JDA_LIST_VARIANT(m), JDA_LIST_BIG(m), JDA_LIST_CONT(m), (const jda_dev_desc *)(B + S.off_descs), (const jda_strip *)(B + S.list_off[m]), S.list_n[m],
-                              JDA_LIST_IS_THUMB_FLAT(m) ? S.flat_max_items : 0u, ctx->stream);
+                              JDA_LIST_IS_THUMB_FLAT(m) ? S.flat_max_items : 0u, 0 /* the static split: these lists go out before the pre-scan's verdict */, ctx->stream);
         S.st.launches++;
     }
     // .. and the coefficient launches, one per (form, layout) present, behind the batch's decode and in front of its event: the stream

@@ -196,6 +196,7 @@ void jda_destroy(jda_ctx *ctx)
     (void)hipEventDestroy(ctx->ev_start);
     (void)hipEventDestroy(ctx->ev_stop);
     for (int i = 0; i < JDA_MAX_BANDS; i++) if (ctx->ev_band[i]) (void)hipEventDestroy(ctx->ev_band[i]);
+    jda_decode_pool_release(ctx->stream);
     (void)hipStreamDestroy(ctx->stream);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     for (int i = 0; i < JDA_POOL_SLOTS; i++) if (ctx->pool[i].p) (void)hipFree(ctx->pool[i].p);
@@ -737,7 +738,8 @@ jda_batch *jda_batch_create_strips(jda_ctx *ctx, int32_t n, jda_dev_image *const
     // consecutive images of a list with equal tables and table ids use ONE copy of them (the first one's: it is part of this plan) and are
     // one table generation to the decode kernel -- its workgroups pass from one to the next without restaging (jda_strip::ord)
     int list_owner[JDA_N_LISTS];
-    for (int m = 0; m < JDA_N_LISTS; m++) list_owner[m] = -1;
+    uint32_t list_images[JDA_N_LISTS];
+    for (int m = 0; m < JDA_N_LISTS; m++) { list_owner[m] = -1; list_images[m] = 0; }
     for (int i = 0; i < n; i++) {
         const jda_dev_image *im = images[i];
         jda_dev_desc &D = descs[(size_t)i];
@@ -762,6 +764,7 @@ jda_batch *jda_batch_create_strips(jda_ctx *ctx, int32_t n, jda_dev_image *const
         {
             const int li = jda_list_index(D, variant, big, cont, mcu_rects == NULL);
             std::vector<jda_strip> &lst = strips[li];
+            list_images[li]++;
             bool same_tables = false;
             if (list_owner[li] >= 0) {
                 const jda_dev_image *om = images[list_owner[li]];
@@ -803,6 +806,9 @@ jda_batch *jda_batch_create_strips(jda_ctx *ctx, int32_t n, jda_dev_image *const
     for (int m = 0; m < JDA_N_LISTS && e == hipSuccess; m++) {
         b->n_strips[m] = (uint32_t)strips[m].size();
         if (!b->n_strips[m]) continue;
+        if (!JDA_LIST_IS_THUMB_FLAT(m))
+            b->pool_ok[m] = strips[m].front().ord == strips[m].back().ord &&
+                            strips[m].size() / jda_tiles_per_wg(JDA_LIST_MODE(m), JDA_LIST_BIG(m)) >= (size_t)JDA_POOL_MIN_QUADS_PER_IMAGE * list_images[m];
         e = jda_pool_alloc(ctx, (void **)&b->d_strips[m], strips[m].size() * sizeof(jda_strip));
         if (e == hipSuccess) e = hipMemcpyAsync(b->d_strips[m], strips[m].data(), strips[m].size() * sizeof(jda_strip), hipMemcpyHostToDevice, ctx->stream);
         st.n_launches++;
@@ -837,7 +843,7 @@ int jda_batch_decode(jda_ctx *ctx, jda_batch *b)
     for (int m = 0; m < JDA_N_LISTS; m++) {
         if (!b->n_strips[m]) continue;
         JDA_HIP(ctx, jda_launch_decode(JDA_LIST_MODE(m), JDA_LIST_FAST(m), JDA_LIST_VARIANT(m), JDA_LIST_BIG(m), JDA_LIST_CONT(m), b->d_descs, b->d_strips[m], b->n_strips[m],
-                                       JDA_LIST_IS_THUMB_FLAT(m) ? b->flat_max_items : 0u, ctx->stream));
+                                       JDA_LIST_IS_THUMB_FLAT(m) ? b->flat_max_items : 0u, b->pool_ok[m], ctx->stream));
     }
     return JDA_SUCCESS;
 }

@@ -17,6 +17,10 @@
 #define JDA_LIST_CONT(m) ((m) & 1)
 
 #define JDA_POOL_SLOTS 192
+// A tile taken from the decode kernel's pool starts cold when its image is not the one of the wavefront's tile before, and quads claimed one
+// by one rarely are of one image when the images are small: the photographs leg (8 quads an image) ran 2.4 % slower with the pool than without,
+// 1280x720 images (23 quads) 1.2 % faster (profiles/decode_pool_ab.txt).  So only lists whose images average this many quads run the pool.
+#define JDA_POOL_MIN_QUADS_PER_IMAGE 16
 #define JDA_POOL_IDLE_MAX ((size_t)2 << 30)      // idle bytes kept at most
 #define JDA_MAX_BANDS 8
 struct jda_ctx {
@@ -86,6 +90,7 @@ struct jda_batch {
     uint32_t n_strips[JDA_N_LISTS];
     jda_batch_stats stats;
     uint32_t flat_max_items;    // JDA_LIST_THUMB_FLAT: the launch's width
+    uint8_t pool_ok[JDA_N_LISTS];   // the list's launch may deal its last quads at run time (jda_launch_decode): one table generation, JDA_POOL_MIN_QUADS_PER_IMAGE
     int32_t *status;            // per image: JDA_SUCCESS / JDA_DECODE_ERROR (bad MCU) / JDA_INVALID_PARAMETER (hole)
 };
 
@@ -159,8 +164,12 @@ extern "C" hipError_t jda_launch_prescan_passes(const jda_segscan_params *params
 extern "C" hipError_t jda_launch_prescan_passes_ex(const jda_segscan_params *params, uint32_t n_images, uint32_t max_segs, uint32_t list_rounds, uint32_t max_round,
                                                    int any_record, int states_first, hipStream_t stream);
 // aux: JDA_LIST_THUMB_FLAT: the most items an image of the batch's flat lists has (jda_flat_items); 0 otherwise
+// pool_ok: every record of the list has one table generation (jda_strip::ord) and the launches on `stream` run one after the other: the
+// persistent kernel may deal the launch's last quads at run time (jda_pool_resolve in jda_kernels.hip); 0: the static split
 extern "C" hipError_t jda_launch_decode(int mode, int fast_mul, int variant, int big, int cont, const jda_dev_desc *descs, const jda_strip *strips,
-                                        uint32_t n_strips, uint32_t aux, hipStream_t stream);
+                                        uint32_t n_strips, uint32_t aux, int pool_ok, hipStream_t stream);
+// a stream that launched decodes is about to be destroyed: its counter slot of the pool is free again
+extern "C" void jda_decode_pool_release(hipStream_t stream);
 // tiles of coefficient images of one MCU layout (descs[i].scan: coefficients, .tables: JDA_CT_QUANT_BYTES of quantisers): jda_coef_tiles<mode>
 extern "C" hipError_t jda_launch_coef_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
 // the same from the sparse form (descs[i].tables: quantisers | first[], .scan: entries): jda_sparse_tiles<mode>

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Profiling aid: when does every wave of the persistent decode kernel start and finish (100 MHz wall clock)?
-Shows how evenly the static split of the batch's tiles loads the CUs.  Usage (GPU box): python tools/wg_balance.py [batch]"""
+Shows how evenly the split of the batch's tiles loads the CUs.  Usage (GPU box): python tools/wg_balance.py [batch [pool_permille]]
+(pool_permille: the share of the launch's quads dealt at run time, jda_internal_set_decode_pool; default: the library's)"""
 import ctypes as C
 import os
 import sys
@@ -14,6 +15,9 @@ import jpegdec_amd as J  # noqa: E402
 nb = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 ctx = J.Context(0)
 lib = ctx.lib
+if len(sys.argv) > 2:
+    lib.jda_internal_set_decode_pool.argtypes = [C.c_int32, C.c_int32]
+    assert lib.jda_internal_set_decode_pool(0, int(sys.argv[2])) == 0
 jp = [bench.cached_jpeg(4096, 4096, "4:2:0", 1234 + i) for i in range(2)]
 prep = [J.PreparedImage(j) for j in jp]
 g = prep[0].geometry(J.RGB8888, 0)
