@@ -11,7 +11,7 @@ EXTRA ?=
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared -fwrapv -pthread -Wall -Wno-unused-function -Xarch_host -ffp-contract=off -Iinclude $(EXTRA)
 LIB = jpegdec_amd/libjpegdec_amd.so
 LIB_SRCS = $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp $(CSRC)/jda_runtime.cpp $(CSRC)/jda_encode_progressive.cpp $(CSRC)/jda_pipeline.cpp $(CSRC)/jda_node.cpp $(CSRC)/jda_kernels.hip $(CSRC)/JPEGDEC.cpp
-LIB_DEPS = $(LIB_SRCS) $(CSRC)/jda_runtime_internal.h $(CSRC)/jda_internal.h $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_pack_plan.h $(CSRC)/jda_resize_plan.h $(CSRC)/jda_encode_plan.h $(CSRC)/jda_encode_prog_plan.h $(CSRC)/jda_prescan_plan.h include/jpegdec_amd.h include/JPEGDEC.h
+LIB_DEPS = $(LIB_SRCS) $(CSRC)/jda_runtime_internal.h $(CSRC)/jda_internal.h $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_pack_plan.h $(CSRC)/jda_resize_plan.h $(CSRC)/jda_encode_plan.h $(CSRC)/jda_encode_prog_plan.h $(CSRC)/jda_recode_plan.h $(CSRC)/jda_prescan_plan.h include/jpegdec_amd.h include/JPEGDEC.h
 
 all: lib oracle hostsim classshim
 
@@ -22,7 +22,7 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so tests/hostsim/libjda_encodeprogsim.so
+hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so tests/hostsim/libjda_encodeprogsim.so tests/hostsim/libjda_recodesim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_prescan_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
@@ -95,6 +95,16 @@ encodeprogasan: tests/hostsim/encode_prog_asan
 tests/hostsim/encode_prog_asan: tests/hostsim/encode_prog_main.cpp $(ENCODEPROGSIM_DEPS)
 	$(CXX) -O1 -g -std=c++17 -fwrapv -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/encode_prog_main.cpp tests/hostsim/encode_prog_sim.cpp
 
+# the recode plan and its two stages (jda_recode_plan.h, jda_rc_* of jda_device_core.h) over sources the product's front end prepares, as a
+# library for the CPU tests (tests/test_recode_cpu.py) and as a program of its own under ASan + UBSan -- test infrastructure
+RECODESIM_SRCS = tests/hostsim/recode_sim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp
+RECODESIM_DEPS = $(RECODESIM_SRCS) $(CSRC)/jda_recode_plan.h $(CSRC)/jda_encode_prog_plan.h $(CSRC)/jda_plan.h $(ENCODESIM_DEPS)
+tests/hostsim/libjda_recodesim.so: $(RECODESIM_DEPS)
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ $(RECODESIM_SRCS)
+recodeasan: tests/hostsim/recode_asan
+tests/hostsim/recode_asan: tests/hostsim/recode_main.cpp $(RECODESIM_DEPS)
+	$(CXX) -O1 -g -std=c++17 -fwrapv -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/recode_main.cpp $(RECODESIM_SRCS)
+
 # the reference-API driver (oracle/ref_shim.cpp) built against the product's JPEGDEC class -- test infrastructure
 classshim: tests/libjpegdec_class_shim.so
 tests/libjpegdec_class_shim.so: oracle/ref_shim.cpp include/JPEGDEC.h $(LIB)
@@ -157,10 +167,10 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
+	rm -f tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan resizefiltersasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
+.PHONY: all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan resizefiltersasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
 
 # jda_node.cpp (host code above the C-ABI) over eight pretend devices -- test infrastructure, no GPU (tests/test_c_api.py)
 nodestub: tests/node_stub/node_stub_user

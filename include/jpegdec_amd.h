@@ -747,6 +747,43 @@ size_t jda_dev_coef_bytes(const jda_dev_coef *d);  /* of the device allocation, 
 int jda_coef_decode_surfaces_rect(jda_ctx *ctx, int32_t n, const jda_dev_coef *const *imgs, const jda_output *outputs, const int32_t *pixel_types,
                                   const int32_t *options, const int32_t *mcu_rects);
 
+/* ------------------------------------------------------------------ lossless recode
+ * A JPEG's own quantised coefficients to a file with another entropy coding -- what jpegtran -optimize / -progressive -copy none do: no
+ * IDCT, no colour conversion, no FDCT, no quantisation; every coefficient and every quantiser of the source is in the file that comes out
+ * -- with ONE exception, which the format makes: a JDA_RECODE_PROGRESSIVE file holds no AC coefficient of the MCU grid's padding blocks
+ * (blocks of a component that lie outside its own extent of ceil(w_c / 8) x ceil(h_c / 8): its AC scans visit that extent only, T.81 A.2.2;
+ * jpegtran drops them too).  Their DC values are kept, no pixel inside the image depends on them, and a baseline or optimised target keeps all.
+ * The source is resident: a baseline image (jda_upload*, its index from the host pre-scan or from JDA_PREPARE_DEVICE_PRESCAN: the same file
+ * either way) or a dense coefficient image (jda_coef_upload, e.g. of jda_progressive_prepare: a progressive file made baseline).  Exactly
+ * one of jda_recode_source's two pointers is set.  form: JDA_RECODE_BASELINE (the Annex K tables, as jda_encode_surfaces writes them),
+ * JDA_RECODE_OPTIMIZE (tables of the file's own, as JDA_ENCODE_OPTIMIZE), JDA_RECODE_PROGRESSIVE (libjpeg's simple progression, as
+ * jda_encode_surfaces_progressive).  restart_interval: -1 the source's own (dropped in a progressive file), 0 none, 1..65535 MCUs.
+ * dst, dst_capacity, dst_bytes, status: as in jda_encode_surfaces -- a file that does not fit is reported with the size it needs and
+ * JDA_ERROR_MEMORY, and no byte of it is written.  jda_recode_bound: a capacity no recoded file of that source passes (jda_encode_bound /
+ * jda_encode_bound_progressive of its shape and what its own DQT segments can add: a third table, 16-bit entries).
+ * The file: SOI, JFIF APP0, one DQT segment per distinct table id of the source in the order Y, Cb, Cr first name it, under the source's id,
+ * 8-bit unless an entry passes 255 (libjpeg's emit_dqt); the frame header with component ids 1..3; the encoder's Huffman table assignment.
+ * No APPn or COM segment of the source is carried over.
+ * Launches: one of jda_rc_extract where a job's source is a baseline image and one of jda_rc_from_coef where a job's is a coefficient image,
+ * in the place of the blocks stage; then the stages of the form as they stand: 6 more (BASELINE), 8 more (OPTIMIZE), 10 more (PROGRESSIVE).
+ * Per job, in status[i], the rest of the call going on: JDA_UNSUPPORTED_FEATURE -- a 4:4:0 source (the encoder has no such sampling), a
+ * source file with an Adobe APP14 segment (dropping it would change how the components are read), a sparse coefficient image, a block with
+ * an |AC| above 1023 or a DC outside -1024 .. 1023 (stricter than libjpeg, which refuses only a DC DIFFERENCE beyond category 11: the
+ * target's restart interval may differ from the source's, and a difference is not local to a block; no byte of such a job's file is
+ * written); JDA_DECODE_ERROR -- a baseline source whose pre-scan validated fewer MCUs than the image has.  From the call,
+ * JDA_INVALID_PARAMETER: progressive jobs mixed with others, gray and colour mixed in a progressive call, JDA_RECODE_PROGRESSIVE with a
+ * positive restart_interval, a source with both or neither pointer set, a destination that overlaps another.
+ * jda_recode_to_host: file in, file out -- a baseline file through jda_prepare + jda_upload, a progressive one through
+ * jda_progressive_prepare + jda_coef_upload; only files cross the bus. */
+enum { JDA_RECODE_BASELINE = 0, JDA_RECODE_OPTIMIZE = 1, JDA_RECODE_PROGRESSIVE = 2 };
+typedef struct jda_recode_source { const jda_dev_image *image; const jda_dev_coef *coef; } jda_recode_source;   /* exactly one is set */
+typedef struct jda_recode_job { int32_t form, restart_interval, reserved0, reserved1; } jda_recode_job;         /* restart_interval: -1 the source's, 0 none, 1..65535 */
+int jda_recode_bound(const jda_image_info *info, int32_t form, int32_t restart_interval, int64_t *bytes);
+int jda_recode_images(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs,
+                      void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status);
+int jda_recode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t form, int32_t restart_interval,
+                       void *host_file, int64_t capacity, int64_t *file_bytes);
+
 const char *jda_version(void);
 
 #ifdef __cplusplus

@@ -51,6 +51,18 @@ class EncodeJob(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("x", "y", "w", "h", "sampling", "quality", "restart_interval", "reserved")]
 
 
+class RecodeSource(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("coef", C.c_void_p)]
+
+
+class RecodeJob(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("form", "restart_interval", "reserved0", "reserved1")]
+
+
+RECODE_BASELINE, RECODE_OPTIMIZE, RECODE_PROGRESSIVE = 0, 1, 2
+RECODE_FORMS = {"baseline": RECODE_BASELINE, "optimize": RECODE_OPTIMIZE, "progressive": RECODE_PROGRESSIVE}
+
+
 class PipelineStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("images", "device_images", "host_path_images", "failed_images", "source_pixels",
                                           "compressed_bytes", "h2d_bytes")] + [("launches", C.c_int32), ("spec_rounds_max", C.c_int32)]
@@ -192,6 +204,10 @@ _PROTOTYPES = [
     ("jda_coef_decode_surfaces_rect", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("jda_dev_coef_free", None, [_P, _P]),
     ("jda_coef_decode_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("jda_recode_bound", C.c_int, [C.POINTER(ImageInfo), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("jda_recode_images", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(RecodeJob), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int32)]),
+    ("jda_recode_to_host", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
 ]
 
 
@@ -748,6 +764,24 @@ class CoefImage:
             pass
 
 
+class DeviceCoef:
+    """A coefficient image resident in HBM (jda_coef_upload_ex): form COEF_DENSE / COEF_SPARSE / COEF_AUTO."""
+
+    def __init__(self, ctx: Context, image: CoefImage, form=COEF_DENSE):
+        self.ctx = ctx
+        err = C.c_int32(0)
+        self.handle = ctx.lib.jda_coef_upload_ex(ctx.handle, image.handle, form, C.byref(err))
+        if not self.handle:
+            raise JdaError(err.value, "jda_coef_upload_ex")
+        self.info = ImageInfo.from_buffer_copy(image.info)
+        self.form = int(ctx.lib.jda_dev_coef_form(self.handle))
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.jda_dev_coef_free(self.ctx.handle, self.handle)
+            self.handle = None
+
+
 def coef_decode(ctx: Context, images, pixel_types, options=None, form=COEF_DENSE, rects=None):
     """jda_coef_upload_ex + ONE jda_coef_decode_surfaces_rect over all the images: [(canvas, geometry)] in MCU-padded host canvases.
     form: COEF_DENSE / COEF_SPARSE / COEF_AUTO for all images, or one per image (dense and sparse images may share the call).
@@ -1024,6 +1058,85 @@ def transcode_to_host(ctx: Context, jpeg: bytes, size=None, sampling="4:2:0", qu
         rc = ctx.lib.jda_transcode_to_host(ctx.handle, jpeg, len(jpeg), options, r, size[0], size[1], _sampling(sampling), quality, restart_interval,
                                            buf.ctypes.data_as(_P), cap, C.byref(nbytes))
     return rc, (buf[:nbytes.value].tobytes() if rc in (0, 2) and nbytes.value <= cap else None), nbytes.value
+
+
+def _recode_form(f):
+    return RECODE_FORMS[f] if isinstance(f, str) else int(f)
+
+
+def recode_bound(info: ImageInfo, form="optimize", restart_interval=None) -> int:
+    """jda_recode_bound: a capacity no recoded file of a source with this header passes (restart_interval None: the source's own)"""
+    b = C.c_int64()
+    rc = load_library().jda_recode_bound(C.byref(info), _recode_form(form), -1 if restart_interval is None else restart_interval, C.byref(b))
+    if rc != 0:
+        raise JdaError(rc, "jda_recode_bound")
+    return b.value
+
+
+def recode_images(ctx: Context, sources, jobs, dst, capacities):
+    """jda_recode_images: sources = DeviceImage (a resident baseline image) or DeviceCoef (a resident coefficient image) each; jobs = a
+    (form, restart_interval) each -- form "baseline" / "optimize" / "progressive" or RECODE_*, restart_interval None (the source's own), 0 or
+    1..65535; dst = device pointers, capacities = their bytes.  -> (file sizes, statuses): the source's own coefficients and quantisers under
+    the entropy coding asked for, written where the file lies in HBM."""
+    n = len(sources)
+    s = (RecodeSource * max(n, 1))(*[RecodeSource(q.handle, None) if isinstance(q, DeviceImage) else RecodeSource(None, q.handle) for q in sources])
+    j = (RecodeJob * max(n, 1))(*[RecodeJob(_recode_form(q[0]), -1 if q[1] is None else q[1], 0, 0) for q in jobs])
+    d = (C.c_void_p * max(n, 1))(*dst)
+    c = (C.c_int64 * max(n, 1))(*capacities)
+    nbytes, status = (C.c_int64 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+    ctx.check(ctx.lib.jda_recode_images(ctx.handle, n, s, j, d, c, nbytes, status), "jda_recode_images")
+    return list(nbytes)[:n], list(status)[:n]
+
+
+def recode_to_host(ctx: Context, jpeg: bytes, form="optimize", restart_interval=None, capacity=None):
+    """jda_recode_to_host: a baseline or progressive file in, the same coefficients under another entropy coding out; -> (rc, the file's bytes
+    or None, the size the file has or needs).  capacity: the host buffer's bytes (default: the bound)."""
+    if capacity is not None:
+        cap = capacity
+    else:
+        info = ImageInfo()
+        rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
+        if rc != 0:
+            raise JdaError(rc, "jda_parse")
+        try:
+            cap = recode_bound(info, form, restart_interval)
+        except JdaError as e:              # (a form, an interval or a layout the call refuses: its code, as the call itself gives it)
+            return e.code, None, 0
+    buf = np.zeros(max(cap, 1), dtype=np.uint8)
+    nbytes = C.c_int64(0)
+    rc = ctx.lib.jda_recode_to_host(ctx.handle, jpeg, len(jpeg), _recode_form(form), -1 if restart_interval is None else restart_interval, buf.ctypes.data_as(_P), cap,
+                                    C.byref(nbytes))
+    return rc, (buf[:nbytes.value].tobytes() if rc == 0 and nbytes.value <= cap else None), nbytes.value
+
+
+def recode(ctx: Context, files, form="optimize"):
+    """Baseline files in, a list of bytes out: prepare_batch with the device pre-scan, upload_batch and ONE recode_images call (a file the
+    call refuses raises JdaError with its status)."""
+    prepared = prepare_batch(list(files), device_prescan=True)
+    images = []
+    base = None
+    try:
+        images = upload_batch(ctx, prepared)
+        caps = [recode_bound(im.info, form) for im in images]
+        offs, total = [], 0
+        for c in caps:
+            offs.append(total)
+            total += (c + 255) & ~255
+        base = ctx.malloc(max(total, 256))
+        nbytes, status = recode_images(ctx, images, [(form, None)] * len(images), [base + o for o in offs], caps)
+        for st in status:
+            if st != 0:
+                raise JdaError(st, "jda_recode_images")
+        return [ctx.to_host(base + o, nb).tobytes() for o, nb in zip(offs, nbytes)]
+    finally:
+        if base is not None:
+            ctx.free(base)
+        for im in images:
+            if im is not None:
+                im.close()
+        for p in prepared:
+            if p is not None:
+                p.close()
 
 
 def decode_resized_to_host(ctx: Context, jpeg: bytes, size, pixel_type=RGB8888, options=0, rect=None, out=None, filter=0):

@@ -4710,4 +4710,128 @@ template <class IO> JDA_HD void jda_pe_write(const jda_pe_arrays &A, const jda_p
     if (c + 1u == jc0 + jcn) { io.st8(J.dst + fb - 2u, 0xffu); io.st8(J.dst + fb - 1u, 0xd9u); }
 }
 
+// ================================================================================================
+// jda_rc_*: the coefficients of a compressed file in the place of the blocks stage (lossless recode).  A lane = a block
+// of the call's flat list, which is the source's own block order (the order of its scan).  Two stages, a kernel each:
+//   extract    the source is a resident baseline image: the lane reads the block's index entry and DC value (index format 2) and walks the
+//              AC symbols from the entry's BIT POSITION through the image's AC LUT for the block's component (the table blob's layout in
+//              HBM: (length << 8) | RS, found by an 11-bit key) into its slot in LDS: 64 x int16, unscaled, in zig-zag order.  The values
+//              are T.81's EXTEND of whole magnitudes -- the reader peeks 32 bits at any bit position, so the reference's un-refilled window
+//              (JDA_INDEX_TRUNC) has no part in it and the entry's phase is not looked at.  The wavefront then stores its
+//              slots with whole 128-bit stores, 64 lanes 8 consecutive blocks an instruction (jda_rc_store).
+//   from_coef  the source is a resident dense coefficient image: natural order -> zig-zag in registers, the indices constants.
+// Both leave what jda_en_block leaves: the coefficients and the block's word (AC code bits under the Annex K table of its class << 16 | DC).
+// No block of a source is a dummy: every block of the MCU grid carries the source's own coefficients.  A block with an |AC| above 1023 or
+// a DC outside -1024 .. 1023 raises its job's word in `bad` (the job is refused) and is clamped, so that the stages behind see legal values.
+// A slot is JDA_COEF_STRIDE bytes, the decode kernel's padding: lanes l and l + 32 share a bank where a stride of 128 would put all 64 on one.
+#define JDA_RC_SLOT_VALID 128u             // byte offset in a slot: != 0: the lane decoded a block into it
+template <class IO> JDA_HD uint32_t jda_rc_peek(const jda_rc_src &S, uint32_t p, IO &io)      // the 32 bits of the scan from bit p on
+{
+    // (the scan section is scan_len + JDA_SCAN_PAD bytes: both dwords stay inside whatever an entry says)
+    const uint32_t a_max = (S.scan_len + JDA_SCAN_PAD - 8u) >> 2;
+    uint32_t a = p >> 5;
+    a = a < a_max ? a : a_max;
+    const uint32_t *w = (const uint32_t *)S.scan + a;
+    const uint32_t d0 = __builtin_bswap32(io.ld32(w)), d1 = __builtin_bswap32(io.ld32(w + 1u)), sh = p & 31u;
+    return sh ? (d0 << sh) | (d1 >> (32u - sh)) : d0;
+}
+JDA_HD uint32_t jda_rc_comp(const jda_encode_dev_job &J, uint32_t s)      // the component of block s of a job
+{
+    const uint32_t k = s % J.bpm, nl = J.hs * J.vs;
+    return k < nl ? 0u : 1u + k - nl;
+}
+// the code bits of an AC value behind `run` zeros, as jda_en_block counts them
+template <class IO> JDA_HD uint32_t jda_rc_ac_bits(const uint32_t *ac, uint32_t run, uint32_t a, IO &io)
+{
+    return (run >> 4) * (io.ld32(ac + 0xf0u) >> 16) + (io.ld32(ac + (((run & 15u) << 4) | jda_en_nbits(a))) >> 16) + jda_en_nbits(a);
+}
+template <class IO> JDA_HD void jda_rc_extract_block(const jda_en_arrays &A, const jda_encode_dev_job &J, const jda_rc_src &S, uint32_t job, uint32_t b, uint8_t *slot,
+                                                     uint32_t *bad, IO &io)
+{
+    const uint32_t s = b - J.block0, c = jda_rc_comp(J, s), t = c ? 1u : 0u;
+    int16_t *coef = (int16_t *)slot;
+    jda_u64_alias *z8 = (jda_u64_alias *)slot;
+#pragma unroll
+    for (int i = 0; i < 16; i++) z8[i] = 0;
+    const uint32_t ix = io.ld32(S.blk_index + s);
+    const uint32_t dcw = io.ld32((const uint32_t *)S.blk_dc + (s >> 1));
+    int32_t dc = (int32_t)(int16_t)((s & 1u) ? dcw >> 16 : dcw & 0xffffu);
+    bool wrong = dc < JDA_RC_MIN_DC || dc > JDA_RC_MAX_DC;
+    dc = dc < JDA_RC_MIN_DC ? JDA_RC_MIN_DC : dc > JDA_RC_MAX_DC ? JDA_RC_MAX_DC : dc;
+    coef[0] = (int16_t)dc;
+    uint32_t p = (ix >> JDA_INDEX_OFF_BITS) * 8u + (ix & (JDA_INDEX_TRUNC - 1u));
+    const uint32_t *lut = (const uint32_t *)(S.tables + JDA_TB_AC + (S.ac_id[c] & 1u) * 4096u);
+    const uint32_t *ac = A.huff + t * 256u;
+    uint32_t bits = 0, z = 1, last = 0;
+    while (z < 64u) {
+        const uint32_t w = jda_rc_peek(S, p, io);
+        const uint32_t key = w >= 0xfc000000u ? 1024u + ((w >> 16) & 0x3ffu) : w >> 22;
+        const uint32_t pair = io.ld32(lut + (key >> 1)), raw = (key & 1u) ? pair >> 16 : pair & 0xffffu;
+        const uint32_t len = raw >> 8, rs = raw & 0xffu, sz = rs & 15u;
+        if (len == 0u || rs == 0u) break;                                // no such code, or EOB
+        z += rs >> 4;
+        if (sz && z < 64u) {
+            const uint32_t m = w << len, v = m >> (32u - sz);
+            int32_t val = (m & 0x80000000u) ? (int32_t)v : (int32_t)v - (int32_t)((1u << sz) - 1u);       // T.81 F.2.2.1 EXTEND
+            uint32_t a = (uint32_t)(val < 0 ? -val : val);
+            if (a > (uint32_t)JDA_RC_MAX_AC) { wrong = true; a = JDA_RC_MAX_AC; val = val < 0 ? -JDA_RC_MAX_AC : JDA_RC_MAX_AC; }
+            coef[z] = (int16_t)val;
+            bits += jda_rc_ac_bits(ac, z - last - 1u, a, io);
+            last = z;
+        }
+        p += len + sz;
+        z++;
+    }
+    if (last < 63u) bits += io.ld32(ac) >> 16;
+    io.st32(A.meta + b, (bits << 16) | ((uint32_t)dc & 0xffffu));
+    if (wrong) io.atomic_or(bad + job, 1u);
+}
+// the wavefront's slots (its first block: b0) to the call's coefficients: chunk i * 64 + lane of the 512 16-byte chunks of 64 blocks
+template <class IO> JDA_HD void jda_rc_store(const jda_en_arrays &A, uint32_t b0, const uint8_t *slots, uint32_t lane, IO &io)
+{
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) {
+        const uint32_t ch = i * 64u + lane, blk = ch >> 3, part = ch & 7u;
+        const uint8_t *slot = slots + blk * JDA_COEF_STRIDE;
+        if (*(const jda_u32_alias *)(slot + JDA_RC_SLOT_VALID) == 0u) continue;
+        const jda_u64_alias *q = (const jda_u64_alias *)(slot + part * 16u);
+        const uint64_t lo = q[0], hi = q[1];
+        const uint32_t w[4] = { (uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32) };
+        io.st128(A.coef + (size_t)(b0 + blk) * 64u + part * 8u, w);
+    }
+}
+template <class IO> JDA_HD void jda_rc_coef_block(const jda_en_arrays &A, const jda_encode_dev_job &J, const jda_rc_src &S, uint32_t job, uint32_t b, uint32_t *bad, IO &io)
+{
+    const uint32_t s = b - J.block0, t = jda_rc_comp(J, s) ? 1u : 0u;
+    const int16_t *in = S.coef + (size_t)s * 64u;
+    uint32_t n[32], w[32];
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) io.ld128(in + 8u * i, n + 4u * i);
+    const uint32_t *ac = A.huff + t * 256u;
+    uint32_t bits = 0, run = 0, dcw = 0;
+    bool wrong = false;
+#pragma unroll
+    for (uint32_t z = 0; z < 64u; z++) {
+        const uint32_t k = jda_en_zigzag(z);
+        int32_t v = (int32_t)(int16_t)((k & 1u) ? n[k >> 1] >> 16 : n[k >> 1] & 0xffffu);
+        if (z == 0u) {
+            if (v < JDA_RC_MIN_DC || v > JDA_RC_MAX_DC) { wrong = true; v = v < JDA_RC_MIN_DC ? JDA_RC_MIN_DC : JDA_RC_MAX_DC; }
+            dcw = (uint32_t)v & 0xffffu;
+        } else {
+            uint32_t a = (uint32_t)(v < 0 ? -v : v);
+            if (a > (uint32_t)JDA_RC_MAX_AC) { wrong = true; a = JDA_RC_MAX_AC; v = v < 0 ? -JDA_RC_MAX_AC : JDA_RC_MAX_AC; }
+            if (a == 0u) run++;
+            else { bits += jda_rc_ac_bits(ac, run, a, io); run = 0; }
+        }
+        const uint32_t val = (uint32_t)v & 0xffffu;
+        if (z & 1u) w[z >> 1] |= val << 16; else w[z >> 1] = val;
+    }
+    if (run) bits += io.ld32(ac) >> 16;
+    int16_t *out = A.coef + (size_t)b * 64u;
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) io.st128(out + 8u * i, w + 4u * i);
+    io.st32(A.meta + b, (bits << 16) | dcw);
+    if (wrong) io.atomic_or(bad + job, 1u);
+}
+
 #endif // JDA_DEVICE_CORE_H

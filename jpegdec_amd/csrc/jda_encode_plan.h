@@ -43,6 +43,11 @@ struct jda_encode_plan_out {
     uint64_t u_total;                        // bytes of all unstuffed scans, each rounded up to a chunk (after jda_encode_plan_place)
     std::vector<int32_t> quality;            // a job (its header is written twice where it is optimised)
     uint32_t n_opt;                          // optimised jobs: JDA_EN_HUFF_DWORDS of histogram each
+    // a call whose jobs bring quantisers of their own (jda_recode_plan.h; empty in a call over pixels): a job's DQT segments as they go into
+    // its file, the table ids of Y, Cb, Cr, and the room kept for an optimised job's header
+    std::vector<std::vector<uint8_t>> dqt;
+    std::vector<uint8_t> tq;                 // 3 a job
+    std::vector<uint32_t> hdr_room;
 };
 // one Huffman table as a DHT segment lists it
 struct jda_encode_table { uint8_t bits[16]; uint8_t vals[256]; uint32_t n_vals; };
@@ -145,11 +150,9 @@ static inline void jda_encode_put_seg(std::vector<uint8_t> &o, uint8_t marker, c
 // SOI, JFIF APP0, DQT per table, SOF0, the DHTs, DRI (ri != 0), SOS: everything in front of the entropy-coded data.  tables == NULL: the
 // Annex K DHTs, DC 0, DC 1, AC 0, AC 1 as libjpeg writes the standard ones; else the job's own (DC 0, AC 0, DC 1, AC 1 in tables[], the
 // last two unused for gray), a segment per table in that order, as libjpeg writes them behind its statistics pass.
-static inline void jda_encode_header_tables(int32_t w, int32_t h, int32_t sampling, int32_t quality, int32_t ri, const jda_encode_table *tables, std::vector<uint8_t> &o)
+// the DQT segments of a file at `quality`: table 0, and table 1 where there is chroma
+static inline void jda_encode_quality_dqt(int32_t quality, int nc, std::vector<uint8_t> &o)
 {
-    const int nc = sampling == JDA_ENCODE_GRAY ? 1 : 3, hs = sampling >= JDA_ENCODE_422 ? 2 : 1, vs = sampling == JDA_ENCODE_420 ? 2 : 1;
-    o.push_back(0xff); o.push_back(0xd8);
-    jda_encode_put_seg(o, 0xe0, { 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0 });
     for (int t = 0; t < (nc == 1 ? 1 : 2); t++) {
         uint8_t nat[64];
         jda_encode_quantiser(quality, t, nat);
@@ -158,9 +161,23 @@ static inline void jda_encode_header_tables(int32_t w, int32_t h, int32_t sampli
         for (int z = 0; z < 64; z++) p[1 + z] = nat[jda_en_zigzag((uint32_t)z)];
         jda_encode_put_seg(o, 0xdb, p);
     }
-    std::vector<uint8_t> sof = { 8, (uint8_t)(h >> 8), (uint8_t)h, (uint8_t)(w >> 8), (uint8_t)w, (uint8_t)nc, 1, (uint8_t)((hs << 4) | vs), 0 };
-    for (int c = 1; c < nc; c++) { sof.push_back((uint8_t)(1 + c)); sof.push_back(0x11); sof.push_back(1); }
-    jda_encode_put_seg(o, 0xc0, sof);
+}
+// SOI, JFIF APP0, the DQT segments as handed in, the frame header (marker: 0xc0 or 0xc2) with tq[c] the quantiser of component c
+static inline void jda_encode_header_front(int32_t w, int32_t h, int nc, int hs, int vs, const uint8_t *dqt, size_t dqt_bytes, const uint8_t tq[3], uint8_t marker, std::vector<uint8_t> &o)
+{
+    o.push_back(0xff); o.push_back(0xd8);
+    jda_encode_put_seg(o, 0xe0, { 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0 });
+    o.insert(o.end(), dqt, dqt + dqt_bytes);
+    std::vector<uint8_t> sof = { 8, (uint8_t)(h >> 8), (uint8_t)h, (uint8_t)(w >> 8), (uint8_t)w, (uint8_t)nc, 1, (uint8_t)((hs << 4) | vs), tq[0] };
+    for (int c = 1; c < nc; c++) { sof.push_back((uint8_t)(1 + c)); sof.push_back(0x11); sof.push_back(tq[c]); }
+    jda_encode_put_seg(o, marker, sof);
+}
+// the same with explicit quantisers (a recode: the source's own): dqt = its DQT segments, tq[c] = the table id of component c
+static inline void jda_encode_header_explicit(int32_t w, int32_t h, int32_t sampling, const uint8_t *dqt, size_t dqt_bytes, const uint8_t tq[3], int32_t ri,
+                                              const jda_encode_table *tables, std::vector<uint8_t> &o)
+{
+    const int nc = sampling == JDA_ENCODE_GRAY ? 1 : 3, hs = sampling >= JDA_ENCODE_422 ? 2 : 1, vs = sampling == JDA_ENCODE_420 ? 2 : 1;
+    jda_encode_header_front(w, h, nc, hs, vs, dqt, dqt_bytes, tq, 0xc0, o);
     for (int k = 0; k < (nc == 1 ? 2 : 4); k++) {
         const int cls = tables ? k & 1 : (nc == 1 ? k : k >> 1), t = tables ? k >> 1 : (nc == 1 ? 0 : k & 1);
         const uint8_t *bits = tables ? tables[k].bits : cls ? jda_en_k_ac_bits[t] : jda_en_k_dc_bits[t];
@@ -176,6 +193,13 @@ static inline void jda_encode_header_tables(int32_t w, int32_t h, int32_t sampli
     for (int c = 1; c < nc; c++) { sos.push_back((uint8_t)(1 + c)); sos.push_back(0x11); }
     sos.push_back(0); sos.push_back(63); sos.push_back(0);
     jda_encode_put_seg(o, 0xda, sos);
+}
+static inline void jda_encode_header_tables(int32_t w, int32_t h, int32_t sampling, int32_t quality, int32_t ri, const jda_encode_table *tables, std::vector<uint8_t> &o)
+{
+    const uint8_t tq[3] = { 0, 1, 1 };
+    std::vector<uint8_t> dqt;
+    jda_encode_quality_dqt(quality, sampling == JDA_ENCODE_GRAY ? 1 : 3, dqt);
+    jda_encode_header_explicit(w, h, sampling, dqt.data(), dqt.size(), tq, ri, tables, o);
 }
 static inline void jda_encode_header(int32_t w, int32_t h, int32_t sampling, int32_t quality, int32_t ri, std::vector<uint8_t> &o)
 {
@@ -221,7 +245,7 @@ static inline int jda_encode_plan_jobs_ex(int32_t n, const jda_output *src, int3
                                           const int64_t *dst_capacity, jda_encode_plan_out *plan)
 {
     plan->jobs.clear(); plan->quant.clear(); plan->huff.clear(); plan->hdr.clear(); plan->n_blocks = plan->n_int = plan->n_chunks = 0; plan->u_total = 0;
-    plan->quality.clear(); plan->n_opt = 0;
+    plan->quality.clear(); plan->n_opt = 0; plan->dqt.clear(); plan->tq.clear(); plan->hdr_room.clear();
     if (bytes_per_pixel != 1 && bytes_per_pixel != 4) return JDA_INVALID_PARAMETER;
     if (n <= 0 || !src || !jobs || !dst || !dst_capacity) return JDA_INVALID_PARAMETER;
     const uint32_t bpp = (uint32_t)bytes_per_pixel;
@@ -317,8 +341,9 @@ static inline int jda_encode_plan_tables(jda_encode_plan_out *plan, const uint32
         jda_encode_huff_words_from(bits4, vals4, plan->huff.data() + J.huff_off);
         const int32_t sampling = J.nc == 1u ? JDA_ENCODE_GRAY : J.vs == 2u ? JDA_ENCODE_420 : J.hs == 2u ? JDA_ENCODE_422 : JDA_ENCODE_444;
         std::vector<uint8_t> h;
-        jda_encode_header_tables((int32_t)J.w, (int32_t)J.h, sampling, plan->quality[i], (int32_t)J.ri, T, h);
-        if (h.size() > jda_encode_header_bytes(sampling, (int32_t)J.ri)) return JDA_ERROR_MEMORY;      // (never: at most 12 + 162 symbols)
+        if (plan->dqt.empty()) jda_encode_header_tables((int32_t)J.w, (int32_t)J.h, sampling, plan->quality[i], (int32_t)J.ri, T, h);
+        else jda_encode_header_explicit((int32_t)J.w, (int32_t)J.h, sampling, plan->dqt[i].data(), plan->dqt[i].size(), plan->tq.data() + 3 * i, (int32_t)J.ri, T, h);
+        if (h.size() > (plan->hdr_room.empty() ? jda_encode_header_bytes(sampling, (int32_t)J.ri) : plan->hdr_room[i])) return JDA_ERROR_MEMORY;      // (never: at most 12 + 162 symbols)
         memcpy(plan->hdr.data() + J.hdr_off, h.data(), h.size());
         J.hdr_len = (uint32_t)h.size();
     }

@@ -22,10 +22,16 @@ struct jda_pe_plan_out {
     std::vector<uint8_t> hdr;                // every segment's header bytes, back to back (jda_pe_plan_tables)
     uint32_t n_units, n_chunks;              // n_chunks: after jda_pe_plan_place
     uint64_t u_total;
+    std::vector<uint32_t> hdr_grow;          // a job (empty in a call over pixels): the bytes its own DQT segments add to JDA_PE_FILE_HDR (jda_recode_plan.h)
 };
 static inline uint32_t jda_pe_scans(int32_t sampling) { return sampling == JDA_ENCODE_GRAY ? 6u : 10u; }
 // the room the headers of a call can take
-static inline size_t jda_pe_hdr_room(const jda_pe_plan_out &P) { return P.segs.size() * JDA_PE_SCAN_HDR + P.pjobs.size() * JDA_PE_FILE_HDR; }
+static inline size_t jda_pe_hdr_room(const jda_pe_plan_out &P)
+{
+    size_t grow = 0;
+    for (uint32_t g : P.hdr_grow) grow += g;
+    return P.segs.size() * JDA_PE_SCAN_HDR + P.pjobs.size() * JDA_PE_FILE_HDR + grow;
+}
 
 // The largest file the image can become (DESIGN.md 5.13 rule 14): every block at JDA_PE_BLOCK_BITS over all its scans, every byte
 // stuffed, every scan padded to a byte, every scan's header at JDA_PE_SCAN_HDR.
@@ -41,15 +47,22 @@ static inline int jda_pe_bound_bytes(int32_t w, int32_t h, int32_t sampling, int
     return JDA_SUCCESS;
 }
 
+static inline int jda_pe_plan_segments(jda_pe_plan_out *plan);
 // n >= 1 jobs: the baseline plan's checks and records, then a segment per scan.  A restart interval is refused (JDA_INVALID_PARAMETER), a
 // job of more than JDA_EN_OPT_MAX_BLOCKS blocks too (JDA_UNSUPPORTED_FEATURE: a symbol count could pass libjpeg's 10^9).
 static inline int jda_pe_plan_jobs(int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs, void *const *dst, const int64_t *dst_capacity,
                                    jda_pe_plan_out *plan)
 {
-    plan->segs.clear(); plan->pjobs.clear(); plan->words.clear(); plan->hdr.clear(); plan->n_units = plan->n_chunks = 0; plan->u_total = 0;
+    plan->segs.clear(); plan->pjobs.clear(); plan->words.clear(); plan->hdr.clear(); plan->n_units = plan->n_chunks = 0; plan->u_total = 0; plan->hdr_grow.clear();
     if (n > 0 && jobs) for (int i = 0; i < n; i++) if (jobs[i].restart_interval != 0) return JDA_INVALID_PARAMETER;
     const int rc = jda_encode_plan_jobs_ex(n, src, bytes_per_pixel, jobs, NULL, dst, dst_capacity, &plan->B);
     if (rc != JDA_SUCCESS) return rc;
+    return jda_pe_plan_segments(plan);
+}
+// a segment per scan of every job of plan->B (the job records are made: by jda_encode_plan_jobs_ex, or by a recode's plan)
+static inline int jda_pe_plan_segments(jda_pe_plan_out *plan)
+{
+    plan->segs.clear(); plan->pjobs.clear(); plan->words.clear(); plan->hdr.clear(); plan->n_units = plan->n_chunks = 0; plan->u_total = 0;
     uint64_t units = 0;
     for (size_t i = 0; i < plan->B.jobs.size(); i++) {
         const jda_encode_dev_job &J = plan->B.jobs[i];
@@ -93,20 +106,10 @@ static inline void jda_pe_table_words(const jda_encode_table &T, uint32_t *w)
 // everything in front of the first scan's DHTs: SOI, JFIF APP0, a DQT per table, SOF2
 static inline void jda_pe_file_header(int32_t w, int32_t h, const jda_encode_dev_job &J, int32_t quality, std::vector<uint8_t> &o)
 {
-    const int nc = (int)J.nc;
-    o.push_back(0xff); o.push_back(0xd8);
-    jda_encode_put_seg(o, 0xe0, { 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0 });
-    for (int t = 0; t < (nc == 1 ? 1 : 2); t++) {
-        uint8_t nat[64];
-        jda_encode_quantiser(quality, t, nat);
-        std::vector<uint8_t> p(65);
-        p[0] = (uint8_t)t;
-        for (int z = 0; z < 64; z++) p[1 + z] = nat[jda_en_zigzag((uint32_t)z)];
-        jda_encode_put_seg(o, 0xdb, p);
-    }
-    std::vector<uint8_t> sof = { 8, (uint8_t)(h >> 8), (uint8_t)h, (uint8_t)(w >> 8), (uint8_t)w, (uint8_t)nc, 1, (uint8_t)((J.hs << 4) | J.vs), 0 };
-    for (int c = 1; c < nc; c++) { sof.push_back((uint8_t)(1 + c)); sof.push_back(0x11); sof.push_back(1); }
-    jda_encode_put_seg(o, 0xc2, sof);
+    const uint8_t tq[3] = { 0, 1, 1 };
+    std::vector<uint8_t> dqt;
+    jda_encode_quality_dqt(quality, (int)J.nc, dqt);
+    jda_encode_header_front(w, h, (int)J.nc, (int)J.hs, (int)J.vs, dqt.data(), dqt.size(), tq, 0xc2, o);
 }
 // between gather and lengths: hist = the call's histograms as the device counted them (the word tables' layout).  Every scan gets the
 // table(s) of its own counts (libjpeg's jpeg_gen_optimal_table), its code words and its header: a DHT segment per table, then its SOS.
@@ -121,7 +124,10 @@ static inline int jda_pe_plan_tables(jda_pe_plan_out *plan, const uint32_t *hist
         const uint32_t *H = hist + S.tab;
         uint32_t *W = plan->words.data() + S.tab;
         std::vector<uint8_t> o;
-        if (si == plan->pjobs[S.job].seg0) jda_pe_file_header((int32_t)J.w, (int32_t)J.h, J, plan->B.quality[S.job], o);
+        const bool first = si == plan->pjobs[S.job].seg0;
+        if (first && plan->B.dqt.empty()) jda_pe_file_header((int32_t)J.w, (int32_t)J.h, J, plan->B.quality[S.job], o);
+        else if (first) jda_encode_header_front((int32_t)J.w, (int32_t)J.h, (int)J.nc, (int)J.hs, (int)J.vs, plan->B.dqt[S.job].data(), plan->B.dqt[S.job].size(),
+                                                plan->B.tq.data() + 3 * S.job, 0xc2, o);
         if (S.ss == 0u && S.ah == 0u) {
             for (uint32_t t = 0; t < (J.nc == 1u ? 1u : 2u); t++) {
                 uint32_t freq[256];
@@ -145,7 +151,7 @@ static inline int jda_pe_plan_tables(jda_pe_plan_out *plan, const uint32_t *hist
         } else { sos.push_back(1); sos.push_back((uint8_t)(1u + S.comp)); sos.push_back((uint8_t)(S.comp ? 0x01 : 0x00)); }
         sos.push_back((uint8_t)S.ss); sos.push_back((uint8_t)S.se); sos.push_back((uint8_t)((S.ah << 4) | S.al));
         jda_encode_put_seg(o, 0xda, sos);
-        if (o.size() > JDA_PE_SCAN_HDR + (si == plan->pjobs[S.job].seg0 ? JDA_PE_FILE_HDR : 0u)) return JDA_ERROR_MEMORY;      // (never: at most 256 symbols a table)
+        if (o.size() > JDA_PE_SCAN_HDR + (first ? JDA_PE_FILE_HDR + (plan->hdr_grow.empty() ? 0u : plan->hdr_grow[S.job]) : 0u)) return JDA_ERROR_MEMORY;      // (never: at most 256 symbols a table)
         S.hdr_off = (uint32_t)plan->hdr.size(); S.hdr_len = (uint32_t)o.size();
         plan->hdr.insert(plan->hdr.end(), o.begin(), o.end());
     }

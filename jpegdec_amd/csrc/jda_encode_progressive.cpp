@@ -18,13 +18,20 @@
 struct progenc_run {
     uint8_t *a, *b; jda_pe_arrays A; jda_pe_plan_out P; uint32_t *hist; std::vector<jda_encode_totals> totals;
     float *stage_ms;                              // (the measuring hook: stage_ms[JDA_PE_STAGES + 1], the host's two steps last)
+    jda_rc_hook *rc;                              // a recode call (jda_recode_images): its sources in the place of the blocks stage; NULL: pixels
 };
 static hipError_t progenc_stages(jda_ctx *ctx, progenc_run &R, uint32_t s0, uint32_t s1)
 {
     hipError_t e = hipSuccess;
     for (uint32_t s = s0; s < s1 && e == hipSuccess; s++) {
         if (R.stage_ms) e = hipEventRecord(ctx->ev_start, ctx->stream);
-        if (e == hipSuccess) e = jda_launch_progenc_stage(&R.A, s, R.P.B.n_blocks, R.P.n_units, (uint32_t)R.P.pjobs.size(), R.P.n_chunks, R.hist, ctx->stream);
+        if (e == hipSuccess) {
+            if (s == JDA_PE_STAGE_BLOCKS && R.rc) {
+                e = jda_launch_recode_blocks(&R.A.E, R.rc->d_src, R.rc->d_bad, R.P.B.n_blocks, R.rc->any_image, R.rc->any_coef, ctx->stream);
+            } else {
+                e = jda_launch_progenc_stage(&R.A, s, R.P.B.n_blocks, R.P.n_units, (uint32_t)R.P.pjobs.size(), R.P.n_chunks, R.hist, ctx->stream);
+            }
+        }
         if (R.stage_ms) {
             float ms = 0.f;
             if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
@@ -45,6 +52,7 @@ static int progenc_run_call(jda_ctx *ctx, progenc_run &R)
     const size_t o_coef = take(nb * 128), o_meta = take(nb * 4), o_code = take(nb * 4), o_tot = take(n * sizeof(jda_encode_totals));
     const size_t o_segs = take(ns * sizeof(jda_pe_seg)), o_pjobs = take(n * sizeof(jda_pe_job)), o_words = take(ns * JDA_PE_TAB_DWORDS * 4), o_hist = take(ns * JDA_PE_TAB_DWORDS * 4);
     const size_t o_cls = take(nu * 4), o_run = take(nu * 4), o_len = take(nu * 4), o_end = take(nu * 8), o_sb = take(ns * 8), o_hdr = take(jda_pe_hdr_room(P));
+    const size_t o_rsrc = take(R.rc ? n * sizeof(jda_rc_src) : 0), o_bad = take(R.rc ? n * 4 : 0);
     hipError_t e = jda_pool_alloc(ctx, (void **)&R.a, off);
     if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(progressive encode scratch)"); return JDA_ERROR_MEMORY; }
     jda_pe_arrays &A = R.A;
@@ -62,12 +70,24 @@ static int progenc_run_call(jda_ctx *ctx, progenc_run &R)
     if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_segs, P.segs.data(), ns * sizeof(jda_pe_seg), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_pjobs, P.pjobs.data(), n * sizeof(jda_pe_job), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(R.hist, 0, ns * JDA_PE_TAB_DWORDS * 4, ctx->stream);      // (the pool hands out what earlier calls left in it)
+    if (R.rc) {
+        R.rc->d_src = (jda_rc_src *)(R.a + o_rsrc); R.rc->d_bad = (uint32_t *)(R.a + o_bad);
+        if (e == hipSuccess) e = hipMemcpyAsync(R.rc->d_src, R.rc->src.data(), n * sizeof(jda_rc_src), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(R.rc->d_bad, 0, n * 4, ctx->stream);
+    }
     if (e == hipSuccess) e = progenc_stages(ctx, R, JDA_PE_STAGE_BLOCKS, JDA_PE_STAGE_LENGTHS);
     std::vector<uint32_t> hist(ns * JDA_PE_TAB_DWORDS);
     auto t0 = std::chrono::steady_clock::now();
     if (e == hipSuccess) e = hipMemcpyAsync(hist.data(), R.hist, hist.size() * 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (R.rc) { R.rc->bad.assign(n, 0u); if (e == hipSuccess) e = hipMemcpyAsync(R.rc->bad.data(), R.rc->d_bad, n * 4, hipMemcpyDeviceToHost, ctx->stream); }
     { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
     if (e != hipSuccess) return jda_set_err(ctx, e, "jda_encode_surfaces_progressive (counts)");
+    if (R.rc) {                                   // a job with a block out of range: no byte of its file is written
+        bool any = false;
+        for (size_t i = 0; i < n; i++) if (R.rc->bad[i]) { P.B.jobs[i].capacity = 0; any = true; }
+        if (any) e = hipMemcpyAsync(R.a + o_jobs, P.B.jobs.data(), n * sizeof(jda_encode_dev_job), hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return jda_set_err(ctx, e, "jda_recode_images (job records)");
+    }
     int rc = jda_pe_plan_tables(&P, hist.data());
     if (rc != JDA_SUCCESS) return rc;
     e = hipMemcpyAsync(R.a + o_words, P.words.data(), P.words.size() * 4, hipMemcpyHostToDevice, ctx->stream);
@@ -105,7 +125,7 @@ static int progenc_call(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t 
     if (!src || !jobs || !dst || !dst_capacity || !dst_bytes || !status) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     progenc_run R;
-    R.a = R.b = NULL; R.hist = NULL; R.stage_ms = stage_ms;
+    R.a = R.b = NULL; R.hist = NULL; R.stage_ms = stage_ms; R.rc = NULL;
     int rc = jda_pe_plan_jobs(n, src, bytes_per_pixel, jobs, dst, dst_capacity, &R.P);
     if (rc != JDA_SUCCESS) return rc;
     rc = progenc_run_call(ctx, R);
@@ -118,6 +138,20 @@ static int progenc_call(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t 
         status[i] = R.totals[(size_t)i].file_bytes > (uint64_t)dst_capacity[i] ? JDA_ERROR_MEMORY : JDA_SUCCESS;
     }
     return JDA_SUCCESS;
+}
+// a recode call's progressive jobs (jda_recode_images): the plan is made (jda_recode_plan.h), the hook stands in for the blocks stage
+int jda_progenc_recode(jda_ctx *ctx, jda_pe_plan_out &P, jda_rc_hook &hook, std::vector<jda_encode_totals> &totals)
+{
+    progenc_run R;
+    R.a = R.b = NULL; R.hist = NULL; R.stage_ms = NULL; R.rc = &hook;
+    R.P = std::move(P);
+    int rc = progenc_run_call(ctx, R);
+    if (rc != JDA_SUCCESS) (void)hipStreamSynchronize(ctx->stream);
+    if (R.b) jda_pool_free(ctx, R.b);
+    if (R.a) jda_pool_free(ctx, R.a);
+    totals = R.totals;
+    P = std::move(R.P);
+    return rc;
 }
 int jda_encode_bound_progressive(int32_t w, int32_t h, int32_t sampling, int64_t *bytes) { return jda_pe_bound_bytes(w, h, sampling, bytes); }
 int jda_encode_surfaces_progressive(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const jda_encode_job *jobs,

@@ -179,6 +179,8 @@ struct jda_front {
     uint32_t raw_off, raw_len;   // the entropy-coded segment inside the file (unfiltered)
     uint32_t n_intervals;        // restart intervals (0: no DRI)
     uint32_t rec_cap;            // jda_record_cap of the image's tables
+    uint8_t raw_q_id[3], adobe;  // the frame header's quantiser ids as they stand; the file has an Adobe APP14 segment
+    uint16_t quant_zz[4][64];    // the DQT entries as the file lists them, by table id (zigzag order)
 };
 
 // One image of a dither launch (device pointers): gray = canvas_w x canvas_h bytes at gray_pitch (16-byte aligned rows), out = packed
@@ -244,6 +246,23 @@ struct jda_encode_totals { uint64_t u_bytes, file_bytes; };                    /
 enum { JDA_EN_STAGE_BLOCKS = 0, JDA_EN_STAGE_LENGTHS, JDA_EN_STAGE_SCAN_BITS, JDA_EN_STAGE_EMIT, JDA_EN_STAGE_COUNT, JDA_EN_STAGE_SCAN_BYTES, JDA_EN_STAGE_WRITE, JDA_EN_STAGES };
 // the two stages an optimised job adds (jda_huffopt_*): gather runs behind lengths, huffopt_lengths in front of the scan
 enum { JDA_EN_STAGE_GATHER = JDA_EN_STAGES, JDA_EN_STAGE_OPT_LENGTHS, JDA_EN_STAGES_OPT };
+
+// The source of one job of a recode call (jda_rc_* in jda_device_core.h; device pointers): a resident baseline image --
+// its filtered scan (scan_len bytes and JDA_SCAN_PAD zeros), block index and DC values (index format 2) and table blob, ac_id[c] the AC
+// table of component c -- or a resident dense coefficient image (coef: 64 x int16 a block, natural order).  The job's record in the
+// call's jda_encode_dev_job list carries the shape; its src is NULL.
+enum { JDA_RC_IMAGE = 0, JDA_RC_COEF = 1 };
+struct jda_rc_src {
+    const uint8_t *scan;
+    const uint32_t *blk_index;
+    const int16_t *blk_dc;
+    const uint8_t *tables;
+    const int16_t *coef;
+    uint32_t scan_len, kind, ac_id[3], pad_;
+};
+#define JDA_RC_MAX_AC 1023                // a recoded block: |AC| <= 1023 and -1024 <= DC <= 1023, else its job is refused
+#define JDA_RC_MIN_DC (-1024)
+#define JDA_RC_MAX_DC 1023
 
 // Progressive encode (jda_pe_* in jda_device_core.h, DESIGN.md 5.13 rules 10 to 14).  A SEGMENT is one scan of one job: its units -- a
 // (scan, block) pair each -- are [unit0, unit0 + n_units) of the call's flat unit list, the job's scans in file order.  comp: the scan's

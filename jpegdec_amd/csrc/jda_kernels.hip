@@ -2453,6 +2453,55 @@ extern "C" hipError_t jda_launch_progenc_stage(const jda_pe_arrays *A, uint32_t 
     return hipGetLastError();
 }
 
+// jda_rc_*: the two stages that stand in for jda_encode_blocks in a recode call (jda_rc_* in jda_device_core.h).  A lane
+// per block of the call's flat block list; a lane whose job has the other kind of source does nothing.  extract: 34 KiB of LDS, a slot of
+// JDA_COEF_STRIDE bytes a lane; dword loads of the scan and the LUT from HBM; after the barrier every wavefront writes its 64 slots with
+// 128-bit stores, consecutive lanes consecutive 16 bytes.  Every lane meets the barrier.
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_rc_extract(jda_en_arrays A, const jda_rc_src *src, uint32_t *bad, uint32_t n_blocks)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t slots[JDA_EN_THREADS * JDA_COEF_STRIDE];
+    const uint32_t b = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    jda_encode_io io; io.lds = nullptr;
+    uint8_t *slot = slots + threadIdx.x * JDA_COEF_STRIDE;
+    uint32_t valid = 0u;
+    if (b < n_blocks) {
+        const uint32_t job = jda_en_find_block(A.jobs, A.n_jobs, b, io);
+        const jda_rc_src S = JDA_G(const jda_rc_src, src)[job];
+        if (S.kind == JDA_RC_IMAGE) {
+            const jda_encode_dev_job J = A.jobs[job];
+            jda_rc_extract_block(A, J, S, job, b, slot, bad, io);
+            valid = 1u;
+        }
+    }
+    *(jda_u32_alias *)(slot + JDA_RC_SLOT_VALID) = valid;
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6;
+    jda_rc_store(A, blockIdx.x * JDA_EN_THREADS + wave * 64u, slots + wave * 64u * JDA_COEF_STRIDE, threadIdx.x & 63u, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_rc_from_coef(jda_en_arrays A, const jda_rc_src *src, uint32_t *bad, uint32_t n_blocks)
+{
+    const uint32_t b = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (b >= n_blocks) return;
+    jda_encode_io io; io.lds = nullptr;
+    const uint32_t job = jda_en_find_block(A.jobs, A.n_jobs, b, io);
+    const jda_rc_src S = JDA_G(const jda_rc_src, src)[job];
+    if (S.kind != JDA_RC_COEF) return;
+    const jda_encode_dev_job J = A.jobs[job];
+    jda_rc_coef_block(A, J, S, job, b, bad, io);
+}
+// the launches of a recode call in the place of JDA_EN_STAGE_BLOCKS: one of jda_rc_extract where a job's source is a baseline image, one of
+// jda_rc_from_coef where a job's is a coefficient image; bad: a zeroed dword a job
+extern "C" hipError_t jda_launch_recode_blocks(const jda_en_arrays *A, const jda_rc_src *src, uint32_t *bad, uint32_t n_blocks, int any_image, int any_coef, hipStream_t stream)
+{
+    if (!A || A->n_jobs == 0u || n_blocks == 0u || !src || !bad || (!any_image && !any_coef)) return hipErrorInvalidValue;
+    const dim3 block(JDA_EN_THREADS), bgrid((n_blocks + JDA_EN_THREADS - 1u) / JDA_EN_THREADS);
+    if (any_image) JDA_LAUNCH(jda_rc_extract, bgrid, block, 0, stream, *A, src, bad, n_blocks);
+    if (any_coef) JDA_LAUNCH(jda_rc_from_coef, bgrid, block, 0, stream, *A, src, bad, n_blocks);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // jda_coef_tiles<MODE>: tiles decoded from coefficient images (jda_ct_* in jda_device_core.h: the load phase that stands in for
 // P1, then the decode kernel's own list / column / row / colour stages).  A wavefront = a tile of the launch list, four to a

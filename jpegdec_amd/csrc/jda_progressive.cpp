@@ -23,6 +23,8 @@ extern "C" void jda_front_prescale_quant(const uint16_t *zz, int convert, int16_
 struct jda_coef_image {
     jda_image_info info;
     uint8_t q_id[3];
+    uint8_t raw_qid[3], adobe;               // the frame header's table id of component c; the file has an Adobe APP14 segment
+    uint16_t raw_quant[3][64];               // component c's DQT entries as the file lists them (zigzag order): a recode writes them back
     alignas(16) int16_t quant[4 * 64];      // prescaled (JPEGFixQuantD, jpeg.inl:1789-1811), natural order: JDA_TB_QUANT of the table blob
     int16_t *coefs;                          // n_blocks x int16[64], natural order, MCU-interleaved scan order; 16-byte aligned
     uint32_t n_blocks;
@@ -135,6 +137,7 @@ struct Decoder {
     bool quant_defined[4], latched[3];
     int tq[3];
     int16_t *quant_out;
+    uint16_t (*raw_out)[64];
 
     bool read_dqt(int at, int seglen)
     {
@@ -154,6 +157,7 @@ struct Decoder {
         if (latched[c]) return true;
         if (!quant_defined[tq[c]]) return false;
         jda_front_prescale_quant(quant_zz[tq[c]], tq[c] < I.ncomp, quant_out + 64 * c);      // (the conversion rule of the baseline path)
+        memcpy(raw_out[c], quant_zz[tq[c]], sizeof(quant_zz[0]));
         latched[c] = true;
         return true;
     }
@@ -344,6 +348,9 @@ jda_coef_image *coef_image_new(const uint8_t *jpeg, int32_t len, int want_progre
     img->info = F.info;
     memcpy(img->q_id, F.q_id, 3);
     memcpy(img->quant, tables + JDA_TB_QUANT, sizeof(img->quant));
+    memset(img->raw_quant, 0, sizeof(img->raw_quant));
+    for (int c = 0; c < 3; c++) { img->raw_qid[c] = F.raw_q_id[c]; memcpy(img->raw_quant[c], F.quant_zz[F.raw_q_id[c] & 3], sizeof(img->raw_quant[0])); }
+    img->adobe = F.adobe;
     img->n_blocks = (uint32_t)(F.info.mcus_x * F.info.mcus_y * F.info.blocks_per_mcu);
     img->coefs = NULL;
     img->sp_first = img->sp_entries = NULL; img->sp_n_entries = 0; img->sp_status = JDA_SUCCESS;
@@ -409,7 +416,7 @@ jda_coef_image *jda_progressive_prepare(const uint8_t *jpeg, int32_t len, int32_
     Decoder *D = new (std::nothrow) Decoder;
     if (!D) { jda_coef_image_free(img); *err = JDA_ERROR_MEMORY; return NULL; }
     memset(D, 0, sizeof(*D));
-    D->d = jpeg; D->len = len; D->I = I; D->coefs = img->coefs; D->quant_out = img->quant;
+    D->d = jpeg; D->len = len; D->I = I; D->coefs = img->coefs; D->quant_out = img->quant; D->raw_out = img->raw_quant;
     D->restart_interval = 0;
     const int lh = (I.subsample == 0x22 || I.subsample == 0x21) ? 2 : 1, lv = (I.subsample == 0x22 || I.subsample == 0x12) ? 2 : 1;
     D->hmax = lh; D->vmax = lv;
@@ -427,6 +434,7 @@ jda_coef_image *jda_progressive_prepare(const uint8_t *jpeg, int32_t len, int32_
                 Comp &C = D->comp[c];
                 C.id = jpeg[at + 10 + 3 * c];
                 D->tq[c] = jpeg[at + 12 + 3 * c] & 3;
+                img->raw_qid[c] = (uint8_t)D->tq[c];
                 C.h = c == 0 ? lh : 1; C.v = c == 0 ? lv : 1;
                 const int wc = (I.width * C.h + lh - 1) / lh, hc = (I.height * C.v + lv - 1) / lv;      // the component's own extent (A.1.1)
                 C.blocks_w = (wc + 7) / 8; C.blocks_h = (hc + 7) / 8;
@@ -434,6 +442,7 @@ jda_coef_image *jda_progressive_prepare(const uint8_t *jpeg, int32_t len, int32_
             }
         } else if (m == 0xc4) { if (!D->read_dht(at + 2, seglen)) { rc = JDA_DECODE_ERROR; break; } }
         else if (m == 0xdb) { if (!D->read_dqt(at + 2, seglen)) { rc = JDA_DECODE_ERROR; break; } }
+        else if (m == 0xee) { if (seglen >= 7 && at + 9 <= len && !memcmp(jpeg + at + 4, "Adobe", 5)) img->adobe = 1; }
         else if (m == 0xdd) { if (seglen == 4 && at + 6 <= len) D->restart_interval = (jpeg[at + 4] << 8) | jpeg[at + 5]; }
         else if (m == 0xda) { first_sos = at; break; }
         at += 2 + seglen;
@@ -480,6 +489,15 @@ const int16_t *jda_coef_image_quant(const jda_coef_image *img, uint8_t *q_id)
     if (!img) return NULL;
     if (q_id) memcpy(q_id, img->q_id, 3);
     return img->quant;
+}
+
+// the quantisers of Y, Cb, Cr as the file's DQT segments list them (3 x 64, zigzag order), the table ids its frame header gives them, and
+// whether it carries an Adobe APP14 segment: what a lossless recode writes back, and what it refuses (jda_recode_plan.h)
+void jda_coef_image_raw_quant(const jda_coef_image *img, uint16_t *quant_zz, uint8_t *q_id, int32_t *adobe)
+{
+    if (quant_zz) memcpy(quant_zz, img->raw_quant, sizeof(img->raw_quant));
+    if (q_id) memcpy(q_id, img->raw_qid, 3);
+    if (adobe) *adobe = img->adobe;
 }
 
 const uint32_t *jda_coef_image_sparse(const jda_coef_image *img, const uint32_t **first, uint32_t *n_entries)

@@ -25,6 +25,7 @@
 #include "jda_pack_plan.h"
 #include "jda_resize_plan.h"
 #include "jda_encode_plan.h"
+#include "jda_recode_plan.h"
 #include "jda_prescan_plan.h"
 
 extern "C" uint32_t jda_image_fast_mul(const jda_image *img);
@@ -391,6 +392,7 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
         d->info = I;
         d->scan_len = scan_len;
         jda_image_component_ids(img, d->dc_id, d->ac_id, d->q_id);
+        { int32_t adobe = 0; jda_image_raw_quant(img, &d->quant_zz[0][0], &adobe); d->adobe = (uint8_t)adobe; }
         d->general_p1 = (uint8_t)jda_image_general_p1(img);
         d->tables_host = (uint8_t *)malloc(JDA_TABLE_BYTES);
         if (d->tables_host) { uint32_t tb_ = 0; memcpy(d->tables_host, jda_image_tables(img, &tb_), JDA_TABLE_BYTES); }
@@ -988,6 +990,7 @@ jda_dev_coef *jda_coef_upload_ex(jda_ctx *ctx, const jda_coef_image *img, int32_
     d->info = *jda_coef_image_get_info(img);
     const int16_t *coefs = jda_coef_image_coefficients(img, &d->n_blocks);
     const int16_t *quant = jda_coef_image_quant(img, d->q_id);
+    { int32_t adobe = 0; jda_coef_image_raw_quant(img, &d->raw_quant[0][0], d->raw_qid, &adobe); d->adobe = (uint8_t)adobe; }
     d->form = picked;
     d->bytes = JDA_CT_QUANT_BYTES + payload;
     hipError_t e = jda_pool_alloc(ctx, (void **)&d->base, d->bytes);
@@ -1833,6 +1836,7 @@ struct encode_run {
     uint8_t *a, *b; jda_en_arrays A; jda_encode_plan_out P; std::vector<jda_encode_totals> totals;
     float *stage_ms; uint32_t timed_stages;      // (the measuring hooks: stage_ms[timed_stages], and behind it the host's step between gather and the second lengths pass)
     uint32_t *hist;
+    jda_rc_hook *rc;                             // a recode call (jda_recode_images): its sources in the place of the blocks stage; NULL: pixels
 };
 // stages [s0, s1) queued back to back; with stage_ms (the measuring hook) each between the context's two timer events, its time added to stage_ms[stage]
 static hipError_t encode_stages(jda_ctx *ctx, encode_run &R, uint32_t s0, uint32_t s1)
@@ -1840,8 +1844,14 @@ static hipError_t encode_stages(jda_ctx *ctx, encode_run &R, uint32_t s0, uint32
     hipError_t e = hipSuccess;
     for (uint32_t s = s0; s < s1 && e == hipSuccess; s++) {
         if (R.stage_ms) e = hipEventRecord(ctx->ev_start, ctx->stream);
-        if (e == hipSuccess) e = s < JDA_EN_STAGES ? jda_launch_encode_stage(&R.A, s, R.P.n_blocks, R.P.n_chunks, ctx->stream)
-                                                   : jda_launch_huffopt_stage(&R.A, s, R.P.n_blocks, R.hist, ctx->stream);
+        if (e == hipSuccess) {
+            if (s == JDA_EN_STAGE_BLOCKS && R.rc) {
+                e = jda_launch_recode_blocks(&R.A, R.rc->d_src, R.rc->d_bad, R.P.n_blocks, R.rc->any_image, R.rc->any_coef, ctx->stream);
+            } else {
+                e = s < JDA_EN_STAGES ? jda_launch_encode_stage(&R.A, s, R.P.n_blocks, R.P.n_chunks, ctx->stream)
+                                      : jda_launch_huffopt_stage(&R.A, s, R.P.n_blocks, R.hist, ctx->stream);
+            }
+        }
         if (R.stage_ms) {
             float ms = 0.f;
             if (e == hipSuccess) e = hipEventRecord(ctx->ev_stop, ctx->stream);
@@ -1879,6 +1889,7 @@ static int encode_lengths(jda_ctx *ctx, encode_run &R)
     const size_t o_jobs = take(n * sizeof(jda_encode_dev_job)), o_quant = take(P.quant.size() * sizeof(jda_encode_quant)), o_huff = take(P.huff.size() * 4), o_hdr = take(P.hdr.size());
     const size_t o_coef = take(nb * 128), o_meta = take(nb * 4), o_code = take(nb * 4), o_end = take(nb * 8), o_ist = take((size_t)P.n_int * 8), o_tot = take(n * sizeof(jda_encode_totals));
     const size_t o_hist = take((size_t)P.n_opt * JDA_EN_HUFF_DWORDS * 4);
+    const size_t o_rsrc = take(R.rc ? n * sizeof(jda_rc_src) : 0), o_bad = take(R.rc ? n * 4 : 0);
     hipError_t e = jda_pool_alloc(ctx, (void **)&R.a, off);
     if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(encode scratch)"); return JDA_ERROR_MEMORY; }
     jda_en_arrays &A = R.A;
@@ -1891,6 +1902,11 @@ static int encode_lengths(jda_ctx *ctx, encode_run &R)
     if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_quant, P.quant.data(), P.quant.size() * sizeof(jda_encode_quant), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_huff, P.huff.data(), P.huff.size() * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(R.a + o_hdr, P.hdr.data(), P.hdr.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (R.rc) {
+        R.rc->d_src = (jda_rc_src *)(R.a + o_rsrc); R.rc->d_bad = (uint32_t *)(R.a + o_bad);
+        if (e == hipSuccess) e = hipMemcpyAsync(R.rc->d_src, R.rc->src.data(), n * sizeof(jda_rc_src), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(R.rc->d_bad, 0, n * 4, ctx->stream);
+    }
     { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }      // (the records are on the stack of this call)
     if (P.n_opt) {                                                                                     // (the pool hands out what earlier calls left in it)
         if (e == hipSuccess) e = hipMemsetAsync(R.hist, 0, (size_t)P.n_opt * JDA_EN_HUFF_DWORDS * 4, ctx->stream);
@@ -1902,7 +1918,9 @@ static int encode_lengths(jda_ctx *ctx, encode_run &R)
     } else if (e == hipSuccess) e = encode_stages(ctx, R, JDA_EN_STAGE_BLOCKS, JDA_EN_STAGE_EMIT);
     R.totals.resize(n);
     if (e == hipSuccess) e = hipMemcpyAsync(R.totals.data(), A.totals, n * sizeof(jda_encode_totals), hipMemcpyDeviceToHost, ctx->stream);
+    if (R.rc) { R.rc->bad.assign(n, 0u); if (e == hipSuccess) e = hipMemcpyAsync(R.rc->bad.data(), R.rc->d_bad, n * 4, hipMemcpyDeviceToHost, ctx->stream); }
     { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+    if (R.rc) for (size_t i = 0; i < n; i++) if (R.rc->bad[i]) P.jobs[i].capacity = 0;      // a block out of range: no byte of the job's file is written (encode_files sends the records up again)
     return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_encode_lengths");
 }
 static int encode_files(jda_ctx *ctx, encode_run &R)
@@ -1934,7 +1952,7 @@ static int encode_call(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t b
     if (!src || !jobs || !dst || !dst_capacity || !dst_bytes || !status) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     encode_run R;
-    R.a = R.b = NULL; R.stage_ms = stage_ms; R.timed_stages = timed_stages; R.hist = NULL;
+    R.a = R.b = NULL; R.stage_ms = stage_ms; R.timed_stages = timed_stages; R.hist = NULL; R.rc = NULL;
     int rc = jda_encode_plan_jobs_ex(n, src, bytes_per_pixel, jobs, job_flags, dst, dst_capacity, &R.P);
     if (rc != JDA_SUCCESS) return rc;
     rc = encode_lengths(ctx, R);
@@ -1973,6 +1991,136 @@ int jda_internal_encode_time_ex(jda_ctx *ctx, int32_t n, const jda_output *src, 
 {
     if (!stage_ms) return JDA_INVALID_PARAMETER;
     return encode_call(ctx, n, src, bytes_per_pixel, jobs, job_flags, dst, dst_capacity, dst_bytes, status, stage_ms, JDA_EN_STAGES_OPT);
+}
+
+// ---- lossless recode (jda_rc_* in jda_kernels.hip and jda_device_core.h; checks, records and headers: jda_recode_plan.h): the
+// encoder's calls as they stand with the sources' own coefficients in the place of the blocks stage.  The jobs' range words come back with
+// the totals (a progressive call: with the symbol counts); a job whose word is set is refused and its record sent up again with capacity 0.
+int jda_recode_bound(const jda_image_info *info, int32_t form, int32_t restart_interval, int64_t *bytes)
+{
+    return jda_recode_bound_bytes(info, form, restart_interval, bytes);
+}
+static void recode_host_of(const jda_recode_source &S, jda_recode_src_host *H)
+{
+    memset(H, 0, sizeof(*H));
+    if (S.image) {
+        const jda_dev_image *d = S.image;
+        H->kind = JDA_RC_IMAGE; H->info = d->info; H->adobe = d->adobe; H->n_mcus_ok = d->n_mcus_ok;
+        for (int c = 0; c < 3; c++) { H->q_id[c] = d->q_id[c]; memcpy(H->quant[c], d->quant_zz[d->q_id[c] & 3], sizeof(H->quant[c])); }
+        H->dev.scan = d->base + d->off_scan; H->dev.blk_index = (const uint32_t *)(d->base + d->off_index); H->dev.blk_dc = (const int16_t *)(d->base + d->off_dc);
+        H->dev.tables = d->base + d->off_tables; H->dev.scan_len = d->scan_len;
+        for (int c = 0; c < 3; c++) H->dev.ac_id[c] = d->ac_id[c];
+    } else {
+        const jda_dev_coef *d = S.coef;
+        H->kind = d->form == JDA_COEF_DENSE ? JDA_RC_COEF : JDA_RC_SPARSE; H->info = d->info; H->adobe = d->adobe;
+        memcpy(H->quant, d->raw_quant, sizeof(H->quant)); memcpy(H->q_id, d->raw_qid, 3);
+        H->dev.coef = (const int16_t *)(d->base + d->off_entries);
+    }
+}
+static int recode_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs,
+                       void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    if (!src || !jobs || !dst || !dst_capacity || !dst_bytes || !status) return JDA_INVALID_PARAMETER;
+    for (int i = 0; i < n; i++) if ((src[i].image != NULL) == (src[i].coef != NULL)) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    std::vector<jda_recode_src_host> hosts((size_t)n);
+    for (int i = 0; i < n; i++) recode_host_of(src[i], &hosts[(size_t)i]);
+    jda_recode_plan_out plan;
+    for (int i = 0; i < n; i++) dst_bytes[i] = 0;
+    int rc = jda_recode_plan_jobs(n, hosts.data(), jobs, dst, dst_capacity, status, &plan);
+    if (rc != JDA_SUCCESS || plan.src.empty()) return rc;
+    jda_rc_hook hook;
+    hook.src = plan.src; hook.any_image = plan.any_image; hook.any_coef = plan.any_coef; hook.d_src = NULL; hook.d_bad = NULL;
+    std::vector<jda_encode_totals> totals;
+    if (plan.progressive) rc = stage_ms ? JDA_INVALID_PARAMETER : jda_progenc_recode(ctx, plan.P, hook, totals);
+    else {
+        encode_run R;
+        R.a = R.b = NULL; R.stage_ms = stage_ms; R.timed_stages = stage_ms ? JDA_EN_STAGES_OPT : 0u; R.hist = NULL; R.rc = &hook;
+        R.P = std::move(plan.P.B);
+        rc = encode_lengths(ctx, R);
+        if (rc == JDA_SUCCESS) rc = encode_files(ctx, R);
+        if (rc != JDA_SUCCESS) (void)hipStreamSynchronize(ctx->stream);
+        if (R.b) jda_pool_free(ctx, R.b);
+        if (R.a) jda_pool_free(ctx, R.a);
+        totals = R.totals;
+    }
+    if (rc != JDA_SUCCESS) return rc;
+    for (size_t k = 0; k < plan.job_of.size(); k++) {
+        const int i = plan.job_of[k];
+        if (hook.bad[k]) { status[i] = JDA_UNSUPPORTED_FEATURE; continue; }
+        dst_bytes[i] = (int64_t)totals[k].file_bytes;
+        status[i] = totals[k].file_bytes > (uint64_t)dst_capacity[i] ? JDA_ERROR_MEMORY : JDA_SUCCESS;
+    }
+    return JDA_SUCCESS;
+}
+int jda_recode_images(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs,
+                      void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status)
+{
+    return recode_call(ctx, n, src, jobs, dst, dst_capacity, dst_bytes, status, NULL);
+}
+// Measuring hook of tools/recode_bench.py (not part of the public header): a call of baseline or optimised jobs with every one of its launches
+// between the context's two timer events; stage_ms[JDA_EN_STAGES_OPT + 1] as jda_internal_encode_time_ex fills it -- entry 0, the blocks stage's,
+// is the recode stage's here (jda_rc_extract and / or jda_rc_from_coef) -- is ADDED to, so the caller zeroes it.
+int jda_internal_recode_time(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs,
+                             void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
+{
+    if (!stage_ms) return JDA_INVALID_PARAMETER;
+    return recode_call(ctx, n, src, jobs, dst, dst_capacity, dst_bytes, status, stage_ms);
+}
+int jda_recode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t form, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes)
+{
+    if (file_bytes) *file_bytes = 0;
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!jpeg || !host_file || !file_bytes || capacity < 0) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    jda_image_info I;
+    int rc = jda_parse(jpeg, len, &I);
+    if (rc != JDA_SUCCESS) return rc;
+    int64_t bound = 0;
+    rc = jda_recode_bound_bytes(&I, form, restart_interval, &bound);
+    if (rc != JDA_SUCCESS) return rc;
+    jda_image *img = NULL;
+    jda_coef_image *cimg = NULL;
+    jda_recode_source S = { NULL, NULL };
+    int32_t err = JDA_SUCCESS;
+    jda_dev_image *dimg = NULL;
+    jda_dev_coef *dcoef = NULL;
+    if (I.jpeg_type == 1) {
+        cimg = jda_progressive_prepare(jpeg, len, &err);
+        if (cimg) dcoef = jda_coef_upload(ctx, cimg, &err);
+        S.coef = dcoef;
+    } else {
+        img = jda_prepare(jpeg, len, &err);
+        if (img) dimg = jda_upload(ctx, img, &err);
+        S.image = dimg;
+    }
+    rc = (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
+    const int64_t fcap = std::min(capacity, bound);                                        // (no file is longer than the bound)
+    void *dfile = NULL;
+    if (rc == JDA_SUCCESS) {
+        const hipError_t e = jda_pool_alloc(ctx, &dfile, (size_t)fcap + 16);
+        if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(recoded file)"); rc = JDA_ERROR_MEMORY; }
+    }
+    if (rc == JDA_SUCCESS) {
+        const jda_recode_job J = { form, restart_interval, 0, 0 };
+        int32_t st = JDA_SUCCESS;
+        rc = jda_recode_images(ctx, 1, &S, &J, &dfile, &fcap, file_bytes, &st);
+        if (rc == JDA_SUCCESS) rc = st;
+        if (rc == JDA_SUCCESS) {
+            hipError_t e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);
+            { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+        }
+    }
+    if (dfile) jda_pool_free(ctx, dfile);
+    if (dimg) jda_dev_image_free(ctx, dimg);
+    if (dcoef) jda_dev_coef_free(ctx, dcoef);
+    if (img) jda_image_free(img);
+    if (cimg) jda_coef_image_free(cimg);
+    return rc;
 }
 
 int jda_transcode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,

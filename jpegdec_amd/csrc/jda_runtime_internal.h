@@ -54,7 +54,11 @@ struct jda_dev_image {
     uint32_t n_cont;
     uint32_t tiles_total, tiles_over_small;   // host index known: tiles, and those whose scan slice exceeds the 16-wave kernel's window (0 / 0: unknown)
     uint8_t *tables_host;     // a host copy of the tables (JDA_TABLE_BYTES): a launch plan lets consecutive images with equal tables share the first one's copy
+    uint16_t quant_zz[4][64]; // the file's DQT entries by table id (zigzag order) and whether it has an Adobe APP14 segment: a recode's header (jda_recode_plan.h)
+    uint8_t adobe;
 };
+extern "C" void jda_image_raw_quant(const jda_image *img, uint16_t *quant_zz, int32_t *adobe);
+extern "C" void jda_coef_image_raw_quant(const jda_coef_image *img, uint16_t *quant_zz, uint8_t *q_id, int32_t *adobe);
 
 struct jda_dev_coef {
     uint8_t *base;            // one allocation: quantisers (JDA_CT_QUANT_BYTES) | coefficients (n_blocks x 128 bytes)  -- JDA_COEF_DENSE
@@ -65,6 +69,8 @@ struct jda_dev_coef {
     int form;                 // what is resident
     uint32_t n_entries;
     size_t off_entries;       // the coefficients (dense) / the entries (sparse)
+    uint16_t raw_quant[3][64]; // the DQT entries of Y, Cb, Cr as the file lists them, the ids its frame header gives them, its Adobe APP14 flag (a recode's header)
+    uint8_t raw_qid[3], adobe;
 };
 
 // launch plan of a call over coefficient images: descs | tile lists of (form, layout), in one host blob that goes to the device as it is
@@ -153,6 +159,22 @@ extern "C" hipError_t jda_launch_huffopt_stage(const jda_en_arrays *A, uint32_t 
 // one stage of a progressive call (JDA_PE_STAGE_*; jda_pe_* in jda_device_core.h)
 extern "C" hipError_t jda_launch_progenc_stage(const jda_pe_arrays *A, uint32_t stage, uint32_t n_blocks, uint32_t n_units, uint32_t n_jobs, uint32_t n_chunks, uint32_t *hist,
                                                hipStream_t stream);
+// the launches of a recode call in the place of the blocks stage (jda_rc_extract and / or jda_rc_from_coef; jda_rc_* in jda_device_core.h)
+extern "C" hipError_t jda_launch_recode_blocks(const jda_en_arrays *A, const jda_rc_src *src, uint32_t *bad, uint32_t n_blocks, int any_image, int any_coef,
+                                               hipStream_t stream);
+// What a recode call hands the encoder's host code (jda_runtime.cpp, jda_encode_progressive.cpp) in the place of pixels: the source records
+// of its jobs; d_src / d_bad: their place, and that of the jobs' range words, in the call's scratch (the encoder's code sets them); bad: the
+// words as they came back at the call's first wait -- a job whose word is set gets capacity 0 before the write stage, so no byte of it is written
+struct jda_rc_hook {
+    std::vector<jda_rc_src> src;
+    int any_image, any_coef;
+    jda_rc_src *d_src;
+    uint32_t *d_bad;
+    std::vector<uint32_t> bad;
+};
+struct jda_pe_plan_out;
+// the progressive encoder's three parts over a plan that is made (jda_recode_plan.h), its blocks stage the hook's; totals: a job each
+int jda_progenc_recode(jda_ctx *ctx, jda_pe_plan_out &P, jda_rc_hook &hook, std::vector<jda_encode_totals> &totals);
 extern "C" hipError_t jda_launch_segscan_tail(const jda_segscan_params *params, uint32_t n_images, uint32_t max_segs, uint32_t first_round, uint32_t max_round, hipStream_t stream);
 extern "C" hipError_t jda_launch_filter(const jda_filter_params *params, uint32_t n_images, uint32_t max_raw_len, hipStream_t stream);
 extern "C" hipError_t jda_launch_fill_strips(const jda_strips_params *params, uint32_t n_images, uint32_t max_tiles, hipStream_t stream);
