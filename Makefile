@@ -22,7 +22,7 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so tests/hostsim/libjda_encodeprogsim.so tests/hostsim/libjda_recodesim.so
+hostsim: tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so tests/hostsim/libjda_encodeprogsim.so tests/hostsim/libjda_recodesim.so tests/hostsim/libjda_recodexfsim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_prescan_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
@@ -105,6 +105,17 @@ recodeasan: tests/hostsim/recode_asan
 tests/hostsim/recode_asan: tests/hostsim/recode_main.cpp $(RECODESIM_DEPS)
 	$(CXX) -O1 -g -std=c++17 -fwrapv -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/recode_main.cpp $(RECODESIM_SRCS)
 
+# the same with a flip, a turn, a transposition or an MCU crop a job (jda_recode_images_ex's plan, jda_rc_*_xf of jda_device_core.h), as a
+# library for the CPU tests (tests/test_recode_xf_cpu.py) and as a program of its own under ASan + UBSan -- test infrastructure;
+# recode_xf_sim.cpp includes recode_sim.cpp for its sources, its memory policy and the stages behind
+RECODEXFSIM_SRCS = tests/hostsim/recode_xf_sim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp
+RECODEXFSIM_DEPS = $(RECODEXFSIM_SRCS) $(RECODESIM_DEPS)
+tests/hostsim/libjda_recodexfsim.so: $(RECODEXFSIM_DEPS)
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ $(RECODEXFSIM_SRCS)
+recodexfasan: tests/hostsim/recode_xf_asan
+tests/hostsim/recode_xf_asan: tests/hostsim/recode_xf_main.cpp $(RECODEXFSIM_DEPS)
+	$(CXX) -O1 -g -std=c++17 -fwrapv -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/recode_xf_main.cpp $(RECODEXFSIM_SRCS)
+
 # the reference-API driver (oracle/ref_shim.cpp) built against the product's JPEGDEC class -- test infrastructure
 classshim: tests/libjpegdec_class_shim.so
 tests/libjpegdec_class_shim.so: oracle/ref_shim.cpp include/JPEGDEC.h $(LIB)
@@ -167,10 +178,10 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
+	rm -f tests/hostsim/libjda_recodexfsim.so tests/hostsim/recode_xf_asan tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan resizefiltersasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
+.PHONY: all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan recodexfasan resizefiltersasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
 
 # jda_node.cpp (host code above the C-ABI) over eight pretend devices -- test infrastructure, no GPU (tests/test_c_api.py)
 nodestub: tests/node_stub/node_stub_user

@@ -784,6 +784,35 @@ int jda_recode_images(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
 int jda_recode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t form, int32_t restart_interval,
                        void *host_file, int64_t capacity, int64_t *file_bytes);
 
+/* ---- lossless flip, rotate, transpose and MCU crop: the other half of jpegtran.  Per component the coefficients are a
+ * grid C[by, bx, v, u] over the whole MCU grid (v: vertical frequency, u: horizontal).  FLIP_H: C[:, ::-1] * (-1)^u.  FLIP_V: C[::-1] *
+ * (-1)^v.  TRANSPOSE: C.transpose(1, 0, 3, 2).  ROT_90 (clockwise): TRANSPOSE then FLIP_H.  ROT_270: TRANSPOSE then FLIP_V.  ROT_180:
+ * FLIP_H then FLIP_V.  TRANSVERSE: TRANSPOSE then ROT_180.  DC never changes.  The transposing operations swap width and height, transpose
+ * every quantiser table, and need a sampling whose transpose the encoder has: gray, 4:4:4, 4:2:0 (a 4:2:2 source: JDA_UNSUPPORTED_FEATURE
+ * for the job).  JDA_XF_EXIF: the operation jda_image_info.orientation names (0, 1: none, 2 FLIP_H, 3 ROT_180, 4 FLIP_V, 5 TRANSPOSE,
+ * 6 ROT_90, 7 TRANSVERSE, 8 ROT_270 -- the turn JPEG_AUTO_ROTATE makes); no APPn segment is carried over, so the file has no tag.
+ * mcu_rect = { x, y, w, h } in source MCUs, applied BEFORE the operation; all zero: the whole image.  The cropped size in pixels on an
+ * axis: min(w * mcu_w, width - x * mcu_w), likewise the height.
+ * A source axis that is mirrored (x: FLIP_H, ROT_270; y: FLIP_V, ROT_90; both: ROT_180, TRANSVERSE; none: TRANSPOSE) must be a whole
+ * number of MCUs after the crop: without JDA_XF_TRIM the job gets JDA_UNSUPPORTED_FEATURE (jpegtran -perfect); with it the partial last
+ * MCU column or row is dropped (jpegtran -trim), and a job of which nothing is left is refused.  An unmirrored ragged edge travels with
+ * its blocks.  jpegtran's default (an untransformed edge strip) is not offered.
+ * jda_recode_geometry: the shape of the file that comes out (width, height, mcus_x, mcus_y, orientation 0; the rest as the source's), or
+ * the job's refusal.  jda_recode_bound_ex: jda_recode_bound of that shape.  jda_recode_images_ex: xforms NULL, or every entry NONE (EXIF
+ * over orientation 0 or 1 included) with a zero rectangle: jda_recode_images, launch for launch and byte for byte.  As soon as one job has
+ * an operation or a rectangle, the stage in the place of the blocks stage is jda_rc_extract_xf and / or jda_rc_from_coef_xf for every job
+ * of the call.  JDA_INVALID_PARAMETER from the call: an unknown op or flag, a rectangle with a negative member, one outside the MCU grid,
+ * w or h of 0 with another member non-zero.  Everything else is jda_recode_images': range rule, refusals, forms, restart intervals. */
+enum { JDA_XF_NONE = 0, JDA_XF_FLIP_H, JDA_XF_FLIP_V, JDA_XF_TRANSPOSE, JDA_XF_TRANSVERSE, JDA_XF_ROT_90, JDA_XF_ROT_180, JDA_XF_ROT_270, JDA_XF_EXIF };
+#define JDA_XF_TRIM 1
+typedef struct jda_recode_xform { int32_t op, flags, mcu_rect[4]; } jda_recode_xform;
+int jda_recode_geometry(const jda_image_info *info, const jda_recode_xform *xform, jda_image_info *out);
+int jda_recode_bound_ex(const jda_image_info *info, const jda_recode_xform *xform, int32_t form, int32_t restart_interval, int64_t *bytes);
+int jda_recode_images_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs, const jda_recode_xform *xforms,
+                         void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status);
+int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t form, int32_t restart_interval, const jda_recode_xform *xform,
+                          void *host_file, int64_t capacity, int64_t *file_bytes);
+
 const char *jda_version(void);
 
 #ifdef __cplusplus

@@ -59,7 +59,15 @@ class RecodeJob(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("form", "restart_interval", "reserved0", "reserved1")]
 
 
+class RecodeXform(C.Structure):
+    _fields_ = [("op", C.c_int32), ("flags", C.c_int32), ("mcu_rect", C.c_int32 * 4)]
+
+
 RECODE_BASELINE, RECODE_OPTIMIZE, RECODE_PROGRESSIVE = 0, 1, 2
+XF_NONE, XF_FLIP_H, XF_FLIP_V, XF_TRANSPOSE, XF_TRANSVERSE, XF_ROT_90, XF_ROT_180, XF_ROT_270, XF_EXIF = range(9)
+XF_TRIM = 1
+RECODE_TRANSFORMS = {None: XF_NONE, "none": XF_NONE, "flip_h": XF_FLIP_H, "flip_v": XF_FLIP_V, "transpose": XF_TRANSPOSE, "transverse": XF_TRANSVERSE, "rot90": XF_ROT_90,
+                     "rot180": XF_ROT_180, "rot270": XF_ROT_270, "exif": XF_EXIF}
 RECODE_FORMS = {"baseline": RECODE_BASELINE, "optimize": RECODE_OPTIMIZE, "progressive": RECODE_PROGRESSIVE}
 
 
@@ -208,6 +216,11 @@ _PROTOTYPES = [
     ("jda_recode_images", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(RecodeJob), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int32)]),
     ("jda_recode_to_host", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("jda_recode_geometry", C.c_int, [C.POINTER(ImageInfo), C.POINTER(RecodeXform), C.POINTER(ImageInfo)]),
+    ("jda_recode_bound_ex", C.c_int, [C.POINTER(ImageInfo), C.POINTER(RecodeXform), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("jda_recode_images_ex", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(RecodeJob), C.POINTER(RecodeXform), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("jda_recode_to_host_ex", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RecodeXform), _P, C.c_int64, C.POINTER(C.c_int64)]),
 ]
 
 
@@ -1064,33 +1077,72 @@ def _recode_form(f):
     return RECODE_FORMS[f] if isinstance(f, str) else int(f)
 
 
-def recode_bound(info: ImageInfo, form="optimize", restart_interval=None) -> int:
-    """jda_recode_bound: a capacity no recoded file of a source with this header passes (restart_interval None: the source's own)"""
+def recode_xform(transform=None, crop=None, trim=False) -> RecodeXform:
+    """a jda_recode_xform: transform None / "flip_h" / "flip_v" / "transpose" / "transverse" / "rot90" / "rot180" / "rot270" / "exif" or XF_*; crop
+    (x, y, w, h) in source MCUs, applied before the operation (None: the whole image); trim: drop a partial MCU column or row of a mirrored
+    axis (jpegtran -trim) where the job is refused without (jpegtran -perfect).  A RecodeXform or its six words pass through."""
+    if isinstance(transform, RecodeXform):
+        return transform
+    x = RecodeXform()
+    if isinstance(transform, (tuple, list)):
+        x.op, x.flags = int(transform[0]), int(transform[1])
+        crop = transform[2:6]
+    else:
+        x.op = RECODE_TRANSFORMS[transform] if transform is None or isinstance(transform, str) else int(transform)
+        x.flags = XF_TRIM if trim else 0
+    for k in range(4):
+        x.mcu_rect[k] = int(crop[k]) if crop is not None else 0
+    return x
+
+
+def recode_geometry(info: ImageInfo, transform=None, crop=None, trim=False) -> ImageInfo:
+    """jda_recode_geometry: the header of the file a recode with this transform writes (width, height and MCU grid of the turned region;
+    orientation 0); JdaError with the job's refusal"""
+    out = ImageInfo()
+    rc = load_library().jda_recode_geometry(C.byref(info), C.byref(recode_xform(transform, crop, trim)), C.byref(out))
+    if rc != 0:
+        raise JdaError(rc, "jda_recode_geometry")
+    return out
+
+
+def recode_bound(info: ImageInfo, form="optimize", restart_interval=None, xform=None) -> int:
+    """jda_recode_bound[_ex]: a capacity no recoded file of a source with this header passes (restart_interval None: the source's own);
+    xform: what recode_xform takes -- the bound of the turned region's file"""
     b = C.c_int64()
-    rc = load_library().jda_recode_bound(C.byref(info), _recode_form(form), -1 if restart_interval is None else restart_interval, C.byref(b))
+    ri = -1 if restart_interval is None else restart_interval
+    if xform is None:
+        rc = load_library().jda_recode_bound(C.byref(info), _recode_form(form), ri, C.byref(b))
+    else:
+        rc = load_library().jda_recode_bound_ex(C.byref(info), C.byref(recode_xform(xform)), _recode_form(form), ri, C.byref(b))
     if rc != 0:
         raise JdaError(rc, "jda_recode_bound")
     return b.value
 
 
-def recode_images(ctx: Context, sources, jobs, dst, capacities):
+def recode_images(ctx: Context, sources, jobs, dst, capacities, xforms=None):
     """jda_recode_images: sources = DeviceImage (a resident baseline image) or DeviceCoef (a resident coefficient image) each; jobs = a
     (form, restart_interval) each -- form "baseline" / "optimize" / "progressive" or RECODE_*, restart_interval None (the source's own), 0 or
     1..65535; dst = device pointers, capacities = their bytes.  -> (file sizes, statuses): the source's own coefficients and quantisers under
-    the entropy coding asked for, written where the file lies in HBM."""
+    the entropy coding asked for, written where the file lies in HBM.  xforms: None, or what recode_xform takes a job (jda_recode_images_ex):
+    the file of the job's region flipped, turned or transposed, still without a pixel in between."""
     n = len(sources)
     s = (RecodeSource * max(n, 1))(*[RecodeSource(q.handle, None) if isinstance(q, DeviceImage) else RecodeSource(None, q.handle) for q in sources])
     j = (RecodeJob * max(n, 1))(*[RecodeJob(_recode_form(q[0]), -1 if q[1] is None else q[1], 0, 0) for q in jobs])
     d = (C.c_void_p * max(n, 1))(*dst)
     c = (C.c_int64 * max(n, 1))(*capacities)
     nbytes, status = (C.c_int64 * max(n, 1))(), (C.c_int32 * max(n, 1))()
-    ctx.check(ctx.lib.jda_recode_images(ctx.handle, n, s, j, d, c, nbytes, status), "jda_recode_images")
+    if xforms is None:
+        ctx.check(ctx.lib.jda_recode_images(ctx.handle, n, s, j, d, c, nbytes, status), "jda_recode_images")
+    else:
+        x = xforms if isinstance(xforms, C.Array) else (RecodeXform * max(n, 1))(*[recode_xform(q) for q in xforms])      # (an array made before: no marshalling a call)
+        ctx.check(ctx.lib.jda_recode_images_ex(ctx.handle, n, s, j, x, d, c, nbytes, status), "jda_recode_images_ex")
     return list(nbytes)[:n], list(status)[:n]
 
 
-def recode_to_host(ctx: Context, jpeg: bytes, form="optimize", restart_interval=None, capacity=None):
-    """jda_recode_to_host: a baseline or progressive file in, the same coefficients under another entropy coding out; -> (rc, the file's bytes
-    or None, the size the file has or needs).  capacity: the host buffer's bytes (default: the bound)."""
+def recode_to_host(ctx: Context, jpeg: bytes, form="optimize", restart_interval=None, capacity=None, transform=None, crop=None, trim=False):
+    """jda_recode_to_host[_ex]: a baseline or progressive file in, the same coefficients under another entropy coding out; -> (rc, the file's bytes
+    or None, the size the file has or needs).  capacity: the host buffer's bytes (default: the bound).  transform, crop, trim: recode_xform's."""
+    xf = None if transform is None and crop is None and not trim else recode_xform(transform, crop, trim)
     if capacity is not None:
         cap = capacity
     else:
@@ -1099,31 +1151,37 @@ def recode_to_host(ctx: Context, jpeg: bytes, form="optimize", restart_interval=
         if rc != 0:
             raise JdaError(rc, "jda_parse")
         try:
-            cap = recode_bound(info, form, restart_interval)
+            cap = recode_bound(info, form, restart_interval, xf)
         except JdaError as e:              # (a form, an interval or a layout the call refuses: its code, as the call itself gives it)
             return e.code, None, 0
     buf = np.zeros(max(cap, 1), dtype=np.uint8)
     nbytes = C.c_int64(0)
-    rc = ctx.lib.jda_recode_to_host(ctx.handle, jpeg, len(jpeg), _recode_form(form), -1 if restart_interval is None else restart_interval, buf.ctypes.data_as(_P), cap,
-                                    C.byref(nbytes))
+    if xf is None:
+        rc = ctx.lib.jda_recode_to_host(ctx.handle, jpeg, len(jpeg), _recode_form(form), -1 if restart_interval is None else restart_interval, buf.ctypes.data_as(_P), cap,
+                                        C.byref(nbytes))
+    else:
+        rc = ctx.lib.jda_recode_to_host_ex(ctx.handle, jpeg, len(jpeg), _recode_form(form), -1 if restart_interval is None else restart_interval, C.byref(xf),
+                                           buf.ctypes.data_as(_P), cap, C.byref(nbytes))
     return rc, (buf[:nbytes.value].tobytes() if rc == 0 and nbytes.value <= cap else None), nbytes.value
 
 
-def recode(ctx: Context, files, form="optimize"):
+def recode(ctx: Context, files, form="optimize", transform=None, crop=None, trim=False):
     """Baseline files in, a list of bytes out: prepare_batch with the device pre-scan, upload_batch and ONE recode_images call (a file the
-    call refuses raises JdaError with its status)."""
+    call refuses raises JdaError with its status).  transform, crop, trim: recode_xform's, the same for every file -- transform="exif" turns
+    each file by its own orientation tag, so a mixed list comes out upright."""
+    xf = None if transform is None and crop is None and not trim else recode_xform(transform, crop, trim)
     prepared = prepare_batch(list(files), device_prescan=True)
     images = []
     base = None
     try:
         images = upload_batch(ctx, prepared)
-        caps = [recode_bound(im.info, form) for im in images]
+        caps = [recode_bound(im.info, form, None, xf) for im in images]
         offs, total = [], 0
         for c in caps:
             offs.append(total)
             total += (c + 255) & ~255
         base = ctx.malloc(max(total, 256))
-        nbytes, status = recode_images(ctx, images, [(form, None)] * len(images), [base + o for o in offs], caps)
+        nbytes, status = recode_images(ctx, images, [(form, None)] * len(images), [base + o for o in offs], caps, None if xf is None else [xf] * len(images))
         for st in status:
             if st != 0:
                 raise JdaError(st, "jda_recode_images")

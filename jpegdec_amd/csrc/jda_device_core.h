@@ -4834,4 +4834,162 @@ template <class IO> JDA_HD void jda_rc_coef_block(const jda_en_arrays &A, const 
     if (wrong) io.atomic_or(bad + job, 1u);
 }
 
+// ------------------------------------------------------------------------------------------------
+// jda_rc_*_xf: the same two stages with every block put at another place, its coefficients permuted and sign-flipped (lossless flip,
+// rotate, transpose and MCU crop).  A lane = a block of the job's REGION (jda_rc_xf) in the SOURCE's scan order, so the
+// index, DC and scan reads are as local as in jda_rc_extract; the lane works out where its block goes in the target's scan order
+// (jda_rc_xf_map) and the block -- 128 bytes, a cache line -- is written there whole.  In zig-zag order a transposition keeps a coefficient
+// on its anti-diagonal and reverses its place there (jda_rc_tz); a mirrored target axis negates the coefficients of odd frequency along it,
+// which are fixed zig-zag positions of the SOURCE block (JDA_RC_ODD_U / _V: bit z).  DC never changes.
+#define JDA_RC_ODD_U 0xB56AAD55554AA952ull  // zig-zag positions of odd horizontal frequency
+#define JDA_RC_ODD_V 0xD6AB555AA5552A94ull  // .. of odd vertical frequency: JDA_RC_ODD_U under jda_rc_tz
+JDA_HD uint32_t jda_rc_tz(uint32_t z)       // the zig-zag position of the transposed coefficient of zig-zag position z
+{
+    constexpr uint8_t tz[64] = { 0, 2, 1, 5, 4, 3, 9, 8, 7, 6, 14, 13, 12, 11, 10, 20, 19, 18, 17, 16, 15, 27, 26, 25, 24, 23, 22, 21, 35, 34, 33, 32,
+                                 31, 30, 29, 28, 42, 41, 40, 39, 38, 37, 36, 48, 47, 46, 45, 44, 43, 53, 52, 51, 50, 49, 57, 56, 55, 54, 60, 59, 58, 62, 61, 63 };
+    return tz[z];
+}
+// the zig-zag positions of a SOURCE block whose coefficients a job negates
+JDA_HD uint64_t jda_rc_xf_neg(uint32_t bits)
+{
+    const bool t = (bits & JDA_RC_XF_T) != 0u, mx = (bits & JDA_RC_XF_MX) != 0u, my = (bits & JDA_RC_XF_MY) != 0u;
+    return ((t ? my : mx) ? JDA_RC_ODD_U : 0ull) ^ ((t ? mx : my) ? JDA_RC_ODD_V : 0ull);       // (transposed: the target's x is the source's y)
+}
+// block r of a job's region: *s = its index in the source's scan order, the return value its index in the target's
+JDA_HD uint32_t jda_rc_xf_map(const jda_encode_dev_job &J, const jda_rc_xf &X, uint32_t r, uint32_t *s)
+{
+    const uint32_t m = r / J.bpm, k = r - m * J.bpm, nl = J.hs * J.vs;
+    const uint32_t my = m / X.rw, mx = m - my * X.rw;
+    *s = ((X.y0 + my) * X.scx + X.x0 + mx) * J.bpm + k;
+    const bool luma = k < nl;
+    uint32_t tx = mx, ty = my, kx = luma ? k % J.hs : 0u, ky = luma ? k / J.hs : 0u;
+    if (X.bits & JDA_RC_XF_T) { uint32_t q = tx; tx = ty; ty = q; q = kx; kx = ky; ky = q; }
+    if (X.bits & JDA_RC_XF_MX) { tx = J.cx - 1u - tx; if (luma) kx = J.hs - 1u - kx; }
+    if (X.bits & JDA_RC_XF_MY) { ty = J.cy - 1u - ty; if (luma) ky = J.vs - 1u - ky; }
+    return (ty * J.cx + tx) * J.bpm + (luma ? ky * J.hs + kx : k);
+}
+// the AC code bits of a finished block in the lane's slot, in the target's zig-zag order, four coefficients a read
+template <class IO> JDA_HD uint32_t jda_rc_slot_bits(const uint32_t *ac, const uint8_t *slot, IO &io)
+{
+    const jda_u64_alias *z8 = (const jda_u64_alias *)slot;
+    uint32_t bits = 0, run = 0;
+    for (uint32_t q = 0; q < 16u; q++) {
+        uint64_t w = z8[q];
+        if (q == 0u) w &= ~0xffffull;                                     // (the DC value is no part of a run)
+        if (w == 0ull) { run += q ? 4u : 3u; continue; }
+        for (uint32_t j = q ? 0u : 1u; j < 4u; j++) {
+            const int32_t v = (int32_t)(int16_t)(w >> (16u * j));
+            if (v == 0) { run++; continue; }
+            bits += jda_rc_ac_bits(ac, run, (uint32_t)(v < 0 ? -v : v), io);
+            run = 0;
+        }
+    }
+    if (run) bits += io.ld32(ac) >> 16;
+    return bits;
+}
+// the lane's block into its slot, as jda_rc_extract_block; the return value: the block's index in the call's flat list
+template <class IO> JDA_HD uint32_t jda_rc_extract_block_xf(const jda_en_arrays &A, const jda_encode_dev_job &J, const jda_rc_src &S, const jda_rc_xf &X, uint32_t job, uint32_t b,
+                                                            uint8_t *slot, uint32_t *bad, IO &io)
+{
+    uint32_t s;
+    const uint32_t d = J.block0 + jda_rc_xf_map(J, X, b - J.block0, &s), c = jda_rc_comp(J, s), t = c ? 1u : 0u;
+    const bool tr = (X.bits & JDA_RC_XF_T) != 0u;
+    const uint64_t neg = jda_rc_xf_neg(X.bits);
+    int16_t *coef = (int16_t *)slot;
+    jda_u64_alias *z8 = (jda_u64_alias *)slot;
+#pragma unroll
+    for (int i = 0; i < 16; i++) z8[i] = 0;
+    const uint32_t ix = io.ld32(S.blk_index + s);
+    const uint32_t dcw = io.ld32((const uint32_t *)S.blk_dc + (s >> 1));
+    int32_t dc = (int32_t)(int16_t)((s & 1u) ? dcw >> 16 : dcw & 0xffffu);
+    bool wrong = dc < JDA_RC_MIN_DC || dc > JDA_RC_MAX_DC;
+    dc = dc < JDA_RC_MIN_DC ? JDA_RC_MIN_DC : dc > JDA_RC_MAX_DC ? JDA_RC_MAX_DC : dc;
+    coef[0] = (int16_t)dc;
+    uint32_t p = (ix >> JDA_INDEX_OFF_BITS) * 8u + (ix & (JDA_INDEX_TRUNC - 1u));
+    const uint32_t *lut = (const uint32_t *)(S.tables + JDA_TB_AC + (S.ac_id[c] & 1u) * 4096u);
+    uint32_t z = 1;
+    while (z < 64u) {
+        const uint32_t w = jda_rc_peek(S, p, io);
+        const uint32_t key = w >= 0xfc000000u ? 1024u + ((w >> 16) & 0x3ffu) : w >> 22;
+        const uint32_t pair = io.ld32(lut + (key >> 1)), raw = (key & 1u) ? pair >> 16 : pair & 0xffffu;
+        const uint32_t len = raw >> 8, rs = raw & 0xffu, sz = rs & 15u;
+        if (len == 0u || rs == 0u) break;                                // no such code, or EOB
+        z += rs >> 4;
+        if (sz && z < 64u) {
+            const uint32_t m = w << len, v = m >> (32u - sz);
+            int32_t val = (m & 0x80000000u) ? (int32_t)v : (int32_t)v - (int32_t)((1u << sz) - 1u);       // T.81 F.2.2.1 EXTEND
+            if (val > JDA_RC_MAX_AC || val < -JDA_RC_MAX_AC) { wrong = true; val = val < 0 ? -JDA_RC_MAX_AC : JDA_RC_MAX_AC; }
+            if ((neg >> z) & 1ull) val = -val;
+            coef[tr ? jda_rc_tz(z) : z] = (int16_t)val;
+        }
+        p += len + sz;
+        z++;
+    }
+    const uint32_t bits = jda_rc_slot_bits(A.huff + t * 256u, slot, io);
+    io.st32(A.meta + d, (bits << 16) | ((uint32_t)dc & 0xffffu));
+    if (wrong) io.atomic_or(bad + job, 1u);
+    return d;
+}
+// the wavefront's slots to the call's coefficients, as jda_rc_store: a slot's word at JDA_RC_SLOT_VALID is its block's index in the flat
+// list + 1 (0: no block), and eight consecutive lanes write the block's line
+template <class IO> JDA_HD void jda_rc_store_xf(const jda_en_arrays &A, const uint8_t *slots, uint32_t lane, IO &io)
+{
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) {
+        const uint32_t ch = i * 64u + lane, blk = ch >> 3, part = ch & 7u;
+        const uint8_t *slot = slots + blk * JDA_COEF_STRIDE;
+        const uint32_t tag = *(const jda_u32_alias *)(slot + JDA_RC_SLOT_VALID);
+        if (tag == 0u) continue;
+        const jda_u64_alias *q = (const jda_u64_alias *)(slot + part * 16u);
+        const uint64_t lo = q[0], hi = q[1];
+        const uint32_t w[4] = { (uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32) };
+        io.st128(A.coef + (size_t)(tag - 1u) * 64u + part * 8u, w);
+    }
+}
+template <bool TR, class IO> JDA_HD void jda_rc_coef_block_xf_t(const jda_en_arrays &A, const jda_encode_dev_job &J, const jda_rc_src &S, const jda_rc_xf &X, uint32_t job, uint32_t b,
+                                                                uint32_t *bad, IO &io)
+{
+    uint32_t s;
+    const uint32_t d = J.block0 + jda_rc_xf_map(J, X, b - J.block0, &s), t = jda_rc_comp(J, s) ? 1u : 0u;
+    const bool mx = (X.bits & JDA_RC_XF_MX) != 0u, my = (X.bits & JDA_RC_XF_MY) != 0u;
+    const bool su = TR ? my : mx, sv = TR ? mx : my;                      // the SOURCE's odd u / odd v are negated
+    const int16_t *in = S.coef + (size_t)s * 64u;
+    uint32_t n[32], w[32];
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) io.ld128(in + 8u * i, n + 4u * i);
+    const uint32_t *ac = A.huff + t * 256u;
+    uint32_t bits = 0, run = 0, dcw = 0;
+    bool wrong = false;
+#pragma unroll
+    for (uint32_t z = 0; z < 64u; z++) {
+        const uint32_t kt = jda_en_zigzag(z), k = TR ? ((kt & 7u) << 3) | (kt >> 3) : kt;      // target natural index, source natural index
+        int32_t v = (int32_t)(int16_t)((k & 1u) ? n[k >> 1] >> 16 : n[k >> 1] & 0xffffu);
+        if (z == 0u) {
+            if (v < JDA_RC_MIN_DC || v > JDA_RC_MAX_DC) { wrong = true; v = v < JDA_RC_MIN_DC ? JDA_RC_MIN_DC : JDA_RC_MAX_DC; }
+            dcw = (uint32_t)v & 0xffffu;
+        } else {
+            uint32_t a = (uint32_t)(v < 0 ? -v : v);
+            if (a > (uint32_t)JDA_RC_MAX_AC) { wrong = true; a = JDA_RC_MAX_AC; v = v < 0 ? -JDA_RC_MAX_AC : JDA_RC_MAX_AC; }
+            if ((k & 1u) && su) v = -v;
+            if ((k & 8u) && sv) v = -v;
+            if (a == 0u) run++;
+            else { bits += jda_rc_ac_bits(ac, run, a, io); run = 0; }
+        }
+        const uint32_t val = (uint32_t)v & 0xffffu;
+        if (z & 1u) w[z >> 1] |= val << 16; else w[z >> 1] = val;
+    }
+    if (run) bits += io.ld32(ac) >> 16;
+    int16_t *out = A.coef + (size_t)d * 64u;
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; i++) io.st128(out + 8u * i, w + 4u * i);
+    io.st32(A.meta + d, (bits << 16) | dcw);
+    if (wrong) io.atomic_or(bad + job, 1u);
+}
+template <class IO> JDA_HD void jda_rc_coef_block_xf(const jda_en_arrays &A, const jda_encode_dev_job &J, const jda_rc_src &S, const jda_rc_xf &X, uint32_t job, uint32_t b,
+                                                     uint32_t *bad, IO &io)
+{
+    if (X.bits & JDA_RC_XF_T) jda_rc_coef_block_xf_t<true>(A, J, S, X, job, b, bad, io);
+    else jda_rc_coef_block_xf_t<false>(A, J, S, X, job, b, bad, io);
+}
+
 #endif // JDA_DEVICE_CORE_H

@@ -27,7 +27,7 @@ static hipError_t progenc_stages(jda_ctx *ctx, progenc_run &R, uint32_t s0, uint
         if (R.stage_ms) e = hipEventRecord(ctx->ev_start, ctx->stream);
         if (e == hipSuccess) {
             if (s == JDA_PE_STAGE_BLOCKS && R.rc) {
-                e = jda_launch_recode_blocks(&R.A.E, R.rc->d_src, R.rc->d_bad, R.P.B.n_blocks, R.rc->any_image, R.rc->any_coef, ctx->stream);
+                e = jda_rc_hook_launch(&R.A.E, *R.rc, R.P.B.n_blocks, ctx->stream);
             } else {
                 e = jda_launch_progenc_stage(&R.A, s, R.P.B.n_blocks, R.P.n_units, (uint32_t)R.P.pjobs.size(), R.P.n_chunks, R.hist, ctx->stream);
             }
@@ -52,7 +52,7 @@ static int progenc_run_call(jda_ctx *ctx, progenc_run &R)
     const size_t o_coef = take(nb * 128), o_meta = take(nb * 4), o_code = take(nb * 4), o_tot = take(n * sizeof(jda_encode_totals));
     const size_t o_segs = take(ns * sizeof(jda_pe_seg)), o_pjobs = take(n * sizeof(jda_pe_job)), o_words = take(ns * JDA_PE_TAB_DWORDS * 4), o_hist = take(ns * JDA_PE_TAB_DWORDS * 4);
     const size_t o_cls = take(nu * 4), o_run = take(nu * 4), o_len = take(nu * 4), o_end = take(nu * 8), o_sb = take(ns * 8), o_hdr = take(jda_pe_hdr_room(P));
-    const size_t o_rsrc = take(R.rc ? n * sizeof(jda_rc_src) : 0), o_bad = take(R.rc ? n * 4 : 0);
+    const size_t o_rsrc = take(R.rc ? n * sizeof(jda_rc_src) : 0), o_bad = take(R.rc ? n * 4 : 0), o_xf = take(R.rc ? R.rc->xf.size() * sizeof(jda_rc_xf) : 0);
     hipError_t e = jda_pool_alloc(ctx, (void **)&R.a, off);
     if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(progressive encode scratch)"); return JDA_ERROR_MEMORY; }
     jda_pe_arrays &A = R.A;
@@ -74,6 +74,8 @@ static int progenc_run_call(jda_ctx *ctx, progenc_run &R)
         R.rc->d_src = (jda_rc_src *)(R.a + o_rsrc); R.rc->d_bad = (uint32_t *)(R.a + o_bad);
         if (e == hipSuccess) e = hipMemcpyAsync(R.rc->d_src, R.rc->src.data(), n * sizeof(jda_rc_src), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(R.rc->d_bad, 0, n * 4, ctx->stream);
+        R.rc->d_xf = (jda_rc_xf *)(R.a + o_xf);
+        if (e == hipSuccess && !R.rc->xf.empty()) e = hipMemcpyAsync(R.rc->d_xf, R.rc->xf.data(), R.rc->xf.size() * sizeof(jda_rc_xf), hipMemcpyHostToDevice, ctx->stream);
     }
     if (e == hipSuccess) e = progenc_stages(ctx, R, JDA_PE_STAGE_BLOCKS, JDA_PE_STAGE_LENGTHS);
     std::vector<uint32_t> hist(ns * JDA_PE_TAB_DWORDS);

@@ -260,6 +260,14 @@ struct jda_rc_src {
     const int16_t *coef;
     uint32_t scan_len, kind, ac_id[3], pad_;
 };
+// The transform of one job of a recode call whose stage is jda_rc_extract_xf / jda_rc_from_coef_xf.  The job's REGION is
+// rw x rh MCUs of the source's grid (scx MCUs across) from MCU (x0, y0): what the crop and the trim leave.  bits: JDA_RC_XF_T the blocks and
+// their coefficients are transposed, then JDA_RC_XF_MX / _MY the TARGET's x / y axis is mirrored.  The job's record in the call's
+// jda_encode_dev_job list carries the target's shape: cx x cy = rw x rh, or rh x rw where transposed (then hs == vs).
+#define JDA_RC_XF_T 1u
+#define JDA_RC_XF_MX 2u
+#define JDA_RC_XF_MY 4u
+struct jda_rc_xf { uint32_t bits, scx, x0, y0, rw, rh, pad_[2]; };
 #define JDA_RC_MAX_AC 1023                // a recoded block: |AC| <= 1023 and -1024 <= DC <= 1023, else its job is refused
 #define JDA_RC_MIN_DC (-1024)
 #define JDA_RC_MAX_DC 1023

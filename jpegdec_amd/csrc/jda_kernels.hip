@@ -2501,6 +2501,55 @@ extern "C" hipError_t jda_launch_recode_blocks(const jda_en_arrays *A, const jda
     if (any_coef) JDA_LAUNCH(jda_rc_from_coef, bgrid, block, 0, stream, *A, src, bad, n_blocks);
     return hipGetLastError();
 }
+// jda_rc_*_xf: the same two stages of a call in which a job flips, turns, transposes or crops (jda_rc_*_xf in jda_device_core.h; DESIGN.md
+// 5.15).  A lane per block of the flat list, which is a block of its job's region in the SOURCE's scan order; the lane's slot carries the
+// index of the block's place in the target's scan order, and every eight lanes of a wavefront write one block's whole 128-byte line there.
+// The same 34 KiB of LDS; every lane meets the barrier.
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_rc_extract_xf(jda_en_arrays A, const jda_rc_src *src, const jda_rc_xf *xf, uint32_t *bad, uint32_t n_blocks)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t slots[JDA_EN_THREADS * JDA_COEF_STRIDE];
+    const uint32_t b = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    jda_encode_io io; io.lds = nullptr;
+    uint8_t *slot = slots + threadIdx.x * JDA_COEF_STRIDE;
+    uint32_t tag = 0u;
+    if (b < n_blocks) {
+        const uint32_t job = jda_en_find_block(A.jobs, A.n_jobs, b, io);
+        const jda_rc_src S = JDA_G(const jda_rc_src, src)[job];
+        if (S.kind == JDA_RC_IMAGE) {
+            const jda_encode_dev_job J = A.jobs[job];
+            const jda_rc_xf X = JDA_G(const jda_rc_xf, xf)[job];
+            tag = 1u + jda_rc_extract_block_xf(A, J, S, X, job, b, slot, bad, io);
+        }
+    }
+    *(jda_u32_alias *)(slot + JDA_RC_SLOT_VALID) = tag;
+    __syncthreads();
+    const uint32_t wave = threadIdx.x >> 6;
+    jda_rc_store_xf(A, slots + wave * 64u * JDA_COEF_STRIDE, threadIdx.x & 63u, io);
+}
+__global__ __launch_bounds__(JDA_EN_THREADS)
+void jda_rc_from_coef_xf(jda_en_arrays A, const jda_rc_src *src, const jda_rc_xf *xf, uint32_t *bad, uint32_t n_blocks)
+{
+    const uint32_t b = blockIdx.x * JDA_EN_THREADS + threadIdx.x;
+    if (b >= n_blocks) return;
+    jda_encode_io io; io.lds = nullptr;
+    const uint32_t job = jda_en_find_block(A.jobs, A.n_jobs, b, io);
+    const jda_rc_src S = JDA_G(const jda_rc_src, src)[job];
+    if (S.kind != JDA_RC_COEF) return;
+    const jda_encode_dev_job J = A.jobs[job];
+    const jda_rc_xf X = JDA_G(const jda_rc_xf, xf)[job];
+    jda_rc_coef_block_xf(A, J, S, X, job, b, bad, io);
+}
+// .. and their launches: xf = a record a job (an untouched job's: no bits, its whole grid)
+extern "C" hipError_t jda_launch_recode_blocks_xf(const jda_en_arrays *A, const jda_rc_src *src, const jda_rc_xf *xf, uint32_t *bad, uint32_t n_blocks, int any_image, int any_coef,
+                                                  hipStream_t stream)
+{
+    if (!A || A->n_jobs == 0u || n_blocks == 0u || !src || !xf || !bad || (!any_image && !any_coef)) return hipErrorInvalidValue;
+    const dim3 block(JDA_EN_THREADS), bgrid((n_blocks + JDA_EN_THREADS - 1u) / JDA_EN_THREADS);
+    if (any_image) JDA_LAUNCH(jda_rc_extract_xf, bgrid, block, 0, stream, *A, src, xf, bad, n_blocks);
+    if (any_coef) JDA_LAUNCH(jda_rc_from_coef_xf, bgrid, block, 0, stream, *A, src, xf, bad, n_blocks);
+    return hipGetLastError();
+}
 
 // ------------------------------------------------------------------------------------------------
 // jda_coef_tiles<MODE>: tiles decoded from coefficient images (jda_ct_* in jda_device_core.h: the load phase that stands in for

@@ -1846,7 +1846,7 @@ static hipError_t encode_stages(jda_ctx *ctx, encode_run &R, uint32_t s0, uint32
         if (R.stage_ms) e = hipEventRecord(ctx->ev_start, ctx->stream);
         if (e == hipSuccess) {
             if (s == JDA_EN_STAGE_BLOCKS && R.rc) {
-                e = jda_launch_recode_blocks(&R.A, R.rc->d_src, R.rc->d_bad, R.P.n_blocks, R.rc->any_image, R.rc->any_coef, ctx->stream);
+                e = jda_rc_hook_launch(&R.A, *R.rc, R.P.n_blocks, ctx->stream);
             } else {
                 e = s < JDA_EN_STAGES ? jda_launch_encode_stage(&R.A, s, R.P.n_blocks, R.P.n_chunks, ctx->stream)
                                       : jda_launch_huffopt_stage(&R.A, s, R.P.n_blocks, R.hist, ctx->stream);
@@ -1889,7 +1889,7 @@ static int encode_lengths(jda_ctx *ctx, encode_run &R)
     const size_t o_jobs = take(n * sizeof(jda_encode_dev_job)), o_quant = take(P.quant.size() * sizeof(jda_encode_quant)), o_huff = take(P.huff.size() * 4), o_hdr = take(P.hdr.size());
     const size_t o_coef = take(nb * 128), o_meta = take(nb * 4), o_code = take(nb * 4), o_end = take(nb * 8), o_ist = take((size_t)P.n_int * 8), o_tot = take(n * sizeof(jda_encode_totals));
     const size_t o_hist = take((size_t)P.n_opt * JDA_EN_HUFF_DWORDS * 4);
-    const size_t o_rsrc = take(R.rc ? n * sizeof(jda_rc_src) : 0), o_bad = take(R.rc ? n * 4 : 0);
+    const size_t o_rsrc = take(R.rc ? n * sizeof(jda_rc_src) : 0), o_bad = take(R.rc ? n * 4 : 0), o_xf = take(R.rc ? R.rc->xf.size() * sizeof(jda_rc_xf) : 0);
     hipError_t e = jda_pool_alloc(ctx, (void **)&R.a, off);
     if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(encode scratch)"); return JDA_ERROR_MEMORY; }
     jda_en_arrays &A = R.A;
@@ -1906,6 +1906,8 @@ static int encode_lengths(jda_ctx *ctx, encode_run &R)
         R.rc->d_src = (jda_rc_src *)(R.a + o_rsrc); R.rc->d_bad = (uint32_t *)(R.a + o_bad);
         if (e == hipSuccess) e = hipMemcpyAsync(R.rc->d_src, R.rc->src.data(), n * sizeof(jda_rc_src), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(R.rc->d_bad, 0, n * 4, ctx->stream);
+        R.rc->d_xf = (jda_rc_xf *)(R.a + o_xf);
+        if (e == hipSuccess && !R.rc->xf.empty()) e = hipMemcpyAsync(R.rc->d_xf, R.rc->xf.data(), R.rc->xf.size() * sizeof(jda_rc_xf), hipMemcpyHostToDevice, ctx->stream);
     }
     { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }      // (the records are on the stack of this call)
     if (P.n_opt) {                                                                                     // (the pool hands out what earlier calls left in it)
@@ -2017,7 +2019,7 @@ static void recode_host_of(const jda_recode_source &S, jda_recode_src_host *H)
         H->dev.coef = (const int16_t *)(d->base + d->off_entries);
     }
 }
-static int recode_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs,
+static int recode_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs, const jda_recode_xform *xforms,
                        void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
@@ -2030,9 +2032,10 @@ static int recode_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, co
     for (int i = 0; i < n; i++) recode_host_of(src[i], &hosts[(size_t)i]);
     jda_recode_plan_out plan;
     for (int i = 0; i < n; i++) dst_bytes[i] = 0;
-    int rc = jda_recode_plan_jobs(n, hosts.data(), jobs, dst, dst_capacity, status, &plan);
+    int rc = jda_recode_plan_jobs_ex(n, hosts.data(), jobs, xforms, dst, dst_capacity, status, &plan);
     if (rc != JDA_SUCCESS || plan.src.empty()) return rc;
     jda_rc_hook hook;
+    hook.xf = plan.xf; hook.d_xf = NULL;
     hook.src = plan.src; hook.any_image = plan.any_image; hook.any_coef = plan.any_coef; hook.d_src = NULL; hook.d_bad = NULL;
     std::vector<jda_encode_totals> totals;
     if (plan.progressive) rc = stage_ms ? JDA_INVALID_PARAMETER : jda_progenc_recode(ctx, plan.P, hook, totals);
@@ -2059,7 +2062,26 @@ static int recode_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, co
 int jda_recode_images(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs,
                       void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status)
 {
-    return recode_call(ctx, n, src, jobs, dst, dst_capacity, dst_bytes, status, NULL);
+    return recode_call(ctx, n, src, jobs, NULL, dst, dst_capacity, dst_bytes, status, NULL);
+}
+// ---- .. with a flip, a turn, a transposition or an MCU crop a job: the plan resolves every job's jda_recode_xform into a
+// record for jda_rc_extract_xf / jda_rc_from_coef_xf and writes the headers of the turned shape; a call without any runs as above
+int jda_recode_geometry(const jda_image_info *info, const jda_recode_xform *xform, jda_image_info *out) { return jda_recode_geometry_of(info, xform, out); }
+int jda_recode_bound_ex(const jda_image_info *info, const jda_recode_xform *xform, int32_t form, int32_t restart_interval, int64_t *bytes)
+{
+    return jda_recode_bound_bytes_ex(info, xform, form, restart_interval, bytes);
+}
+int jda_recode_images_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs, const jda_recode_xform *xforms,
+                         void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status)
+{
+    return recode_call(ctx, n, src, jobs, xforms, dst, dst_capacity, dst_bytes, status, NULL);
+}
+// Measuring hook of tools/recode_bench.py --transform: jda_internal_recode_time with a jda_recode_xform a job
+int jda_internal_recode_time_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_recode_job *jobs, const jda_recode_xform *xforms,
+                                void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
+{
+    if (!stage_ms) return JDA_INVALID_PARAMETER;
+    return recode_call(ctx, n, src, jobs, xforms, dst, dst_capacity, dst_bytes, status, stage_ms);
 }
 // Measuring hook of tools/recode_bench.py (not part of the public header): a call of baseline or optimised jobs with every one of its launches
 // between the context's two timer events; stage_ms[JDA_EN_STAGES_OPT + 1] as jda_internal_encode_time_ex fills it -- entry 0, the blocks stage's,
@@ -2068,9 +2090,14 @@ int jda_internal_recode_time(jda_ctx *ctx, int32_t n, const jda_recode_source *s
                              void *const *dst, const int64_t *dst_capacity, int64_t *dst_bytes, int32_t *status, float *stage_ms)
 {
     if (!stage_ms) return JDA_INVALID_PARAMETER;
-    return recode_call(ctx, n, src, jobs, dst, dst_capacity, dst_bytes, status, stage_ms);
+    return recode_call(ctx, n, src, jobs, NULL, dst, dst_capacity, dst_bytes, status, stage_ms);
 }
 int jda_recode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t form, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes)
+{
+    return jda_recode_to_host_ex(ctx, jpeg, len, form, restart_interval, NULL, host_file, capacity, file_bytes);
+}
+int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t form, int32_t restart_interval, const jda_recode_xform *xform, void *host_file, int64_t capacity,
+                          int64_t *file_bytes)
 {
     if (file_bytes) *file_bytes = 0;
     if (!ctx) return JDA_ERROR_NO_DEVICE;
@@ -2080,7 +2107,7 @@ int jda_recode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t f
     int rc = jda_parse(jpeg, len, &I);
     if (rc != JDA_SUCCESS) return rc;
     int64_t bound = 0;
-    rc = jda_recode_bound_bytes(&I, form, restart_interval, &bound);
+    rc = jda_recode_bound_bytes_ex(&I, xform, form, restart_interval, &bound);
     if (rc != JDA_SUCCESS) return rc;
     jda_image *img = NULL;
     jda_coef_image *cimg = NULL;
@@ -2107,7 +2134,7 @@ int jda_recode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t f
     if (rc == JDA_SUCCESS) {
         const jda_recode_job J = { form, restart_interval, 0, 0 };
         int32_t st = JDA_SUCCESS;
-        rc = jda_recode_images(ctx, 1, &S, &J, &dfile, &fcap, file_bytes, &st);
+        rc = jda_recode_images_ex(ctx, 1, &S, &J, xform, &dfile, &fcap, file_bytes, &st);
         if (rc == JDA_SUCCESS) rc = st;
         if (rc == JDA_SUCCESS) {
             hipError_t e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);

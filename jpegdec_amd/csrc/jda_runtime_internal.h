@@ -162,6 +162,9 @@ extern "C" hipError_t jda_launch_progenc_stage(const jda_pe_arrays *A, uint32_t 
 // the launches of a recode call in the place of the blocks stage (jda_rc_extract and / or jda_rc_from_coef; jda_rc_* in jda_device_core.h)
 extern "C" hipError_t jda_launch_recode_blocks(const jda_en_arrays *A, const jda_rc_src *src, uint32_t *bad, uint32_t n_blocks, int any_image, int any_coef,
                                                hipStream_t stream);
+// .. and of one in which a job flips, turns, transposes or crops (jda_rc_extract_xf and / or jda_rc_from_coef_xf): a transform record a job
+extern "C" hipError_t jda_launch_recode_blocks_xf(const jda_en_arrays *A, const jda_rc_src *src, const jda_rc_xf *xf, uint32_t *bad, uint32_t n_blocks, int any_image,
+                                                  int any_coef, hipStream_t stream);
 // What a recode call hands the encoder's host code (jda_runtime.cpp, jda_encode_progressive.cpp) in the place of pixels: the source records
 // of its jobs; d_src / d_bad: their place, and that of the jobs' range words, in the call's scratch (the encoder's code sets them); bad: the
 // words as they came back at the call's first wait -- a job whose word is set gets capacity 0 before the write stage, so no byte of it is written
@@ -171,7 +174,15 @@ struct jda_rc_hook {
     jda_rc_src *d_src;
     uint32_t *d_bad;
     std::vector<uint32_t> bad;
+    std::vector<jda_rc_xf> xf;      // empty: no job of the call has a transform; else a record a job, d_xf their place in the scratch
+    jda_rc_xf *d_xf;
 };
+// the hook's launches in the place of the blocks stage
+static inline hipError_t jda_rc_hook_launch(const jda_en_arrays *A, const jda_rc_hook &H, uint32_t n_blocks, hipStream_t stream)
+{
+    if (!H.xf.empty()) return jda_launch_recode_blocks_xf(A, H.d_src, H.d_xf, H.d_bad, n_blocks, H.any_image, H.any_coef, stream);
+    return jda_launch_recode_blocks(A, H.d_src, H.d_bad, n_blocks, H.any_image, H.any_coef, stream);
+}
 struct jda_pe_plan_out;
 // the progressive encoder's three parts over a plan that is made (jda_recode_plan.h), its blocks stage the hook's; totals: a job each
 int jda_progenc_recode(jda_ctx *ctx, jda_pe_plan_out &P, jda_rc_hook &hook, std::vector<jda_encode_totals> &totals);

@@ -12,7 +12,14 @@ Warm-up rounds first, every figure the median of --repeat rounds with min and ma
   stages        the optimised recode through jda_internal_recode_time and the optimised encode through jda_internal_encode_time_ex, every
                 launch on its own: `extract` (jda_rc_extract) beside `blocks` (jda_encode_blocks), the stage it replaces.
 The output sizes ride along: the recoded files are the source's coefficients, the pixel road's are not (it quantises again).
-One JSON line on stdout and, with --out FILE (profiles/recode_bench.json is the place for a run on an MI355X), in a file.  Fails without a GPU."""
+One JSON line on stdout and, with --out FILE (profiles/recode_bench.json is the place for a run on an MI355X), in a file.  Fails without a GPU.
+
+--transform measures the lossless flip / rotate (jda_recode_images_ex) on the same two workloads instead
+(profiles/recode_xf_bench.json is the place for its --out):
+  stage         the launch in the place of the blocks stage, through jda_internal_recode_time[_ex]: jda_rc_extract (no transform) beside
+                jda_rc_extract_xf under NONE (asked for with the whole grid as the rectangle), FLIP_H and ROT_90;
+  call          the whole optimised call as a caller sees it: jda_recode_images beside jda_recode_images_ex under NONE, FLIP_H and ROT_90;
+  pixel_road    jda_batch_decode + jda_orient_surfaces (orientation 2 / 6) + jda_encode_surfaces_ex (JDA_ENCODE_OPTIMIZE) of the turned surfaces."""
 import argparse
 import ctypes as C
 import io
@@ -112,11 +119,97 @@ def workload(J, ctx, n, w, h, warmup, repeat):
     return res
 
 
+XF_CASES = (("none", None), ("flip_h", 2), ("rot90", 6))      # (operation, the EXIF orientation that makes the same turn on the pixel road)
+
+
+def xf_workload(J, ctx, n, w, h, warmup, repeat):
+    from jpegdec_amd.binding import RecodeJob, RecodeSource, RecodeXform
+    jpeg = source_file(w, h)
+    prepared = J.prepare_batch([jpeg] * n, device_prescan=True)
+    images = J.upload_batch(ctx, prepared)
+    info = images[0].info
+    g = prepared[0].geometry(J.RGB8888, 0)
+    pitch = g["canvas_w"] * 4
+    surf = (pitch * g["canvas_h"] + 255) & ~255
+    cap = 2 * len(jpeg) + 65536
+    canvases, turned, dst = ctx.malloc(surf * n), ctx.malloc(surf * n), ctx.malloc(cap * n)
+    res = {"images": n, "width": w, "height": h, "source_file_bytes": len(jpeg) * n, "index_on_device": all(im.prescan_on_device for im in images)}
+    try:
+        outs = [(canvases + k * surf, pitch, g["canvas_w"], g["canvas_h"]) for k in range(n)]
+        batch = J.Batch(ctx, images, outs, [J.RGB8888] * n, [0] * n)
+        dsts, caps = [dst + k * cap for k in range(n)], [cap] * n
+        jobs = [("optimize", 0)] * n
+        whole = (0, 0, info.mcus_x, info.mcus_y)
+        lib = ctx.lib
+        head = [C.c_void_p, C.c_int32, C.POINTER(RecodeSource), C.POINTER(RecodeJob)]
+        tail = [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        lib.jda_internal_recode_time.argtypes = head + tail
+        lib.jda_internal_recode_time_ex.argtypes = head + [C.POINTER(RecodeXform)] + tail
+        rs = (RecodeSource * n)(*[RecodeSource(im.handle, None) for im in images])
+        rj = (RecodeJob * n)(*[RecodeJob(J.RECODE_OPTIMIZE, 0, 0, 0)] * n)
+        sd, sc, sb, ss = (C.c_void_p * n)(*dsts), (C.c_int64 * n)(*caps), (C.c_int64 * n)(), (C.c_int32 * n)()
+        cases = [("plain", None, None)] + [(op, J.recode_xform(op, whole if op == "none" else None), o) for op, o in XF_CASES]
+        stage, call, road, sizes = {}, {}, {}, {}
+        setup = []
+        for name, xf, orientation in cases:
+            xs = None if xf is None else (RecodeXform * n)(*[xf] * n)
+            tsrc = tdst = ejobs = None
+            if orientation is not None:
+                tw, th = (h, w) if orientation >= 5 else (w, h)
+                tsrc = [(canvases + k * surf, pitch, w, h) for k in range(n)]
+                tdst = [(turned + k * surf, ((tw * 4 + 15) & ~15), tw, th) for k in range(n)]
+                ejobs = [(0, 0, tw, th, "4:2:0", 75, 0)] * n
+            setup.append((name, xs, orientation, tsrc, tdst, ejobs))
+            stage[name], call[name], road[name] = [], [], []
+        for r in range(warmup + repeat):                    # the cases take turns inside a round, the first one another each round: drift hits all alike
+            for name, xs, orientation, tsrc, tdst, ejobs in setup[r % len(setup):] + setup[:r % len(setup)]:
+                a = (C.c_float * len(OPT_STAGES))()
+                if xs is None:
+                    ctx.check(lib.jda_internal_recode_time(ctx.handle, n, rs, rj, sd, sc, sb, ss, a), "jda_internal_recode_time")
+                else:
+                    ctx.check(lib.jda_internal_recode_time_ex(ctx.handle, n, rs, rj, xs, sd, sc, sb, ss, a), "jda_internal_recode_time_ex")
+                assert not any(ss), list(ss)[:4]
+                ctx.timer_start()
+                nbytes, status = J.recode_images(ctx, images, jobs, dsts, caps, xs)
+                ctx.timer_stop()
+                assert not any(status), status[:4]
+                t_call = ctx.timer_elapsed_ms()
+                sizes[name] = int(sum(nbytes))
+                if orientation is not None:
+                    ctx.timer_start()
+                    batch.decode()
+                    J.orient_surfaces(ctx, tsrc, 4, [orientation] * n, tdst)
+                    px_bytes, status = J.encode_surfaces(ctx, tdst, 4, ejobs, dsts, caps, [J.ENCODE_OPTIMIZE] * n)
+                    ctx.timer_stop()
+                    assert not any(status), status[:4]
+                    if r >= warmup:
+                        road[name].append(ctx.timer_elapsed_ms())
+                if r >= warmup:
+                    stage[name].append(a[0])
+                    call[name].append(t_call)
+        stage, call, road = {k: stats(v) for k, v in stage.items()}, {k: stats(v) for k, v in call.items()}, {k: stats(v) for k, v in road.items() if v}
+        res["stage"], res["call_optimize"], res["pixel_road_optimize"], res["file_bytes"] = stage, call, road, sizes
+        res["stage_over_plain_extract"] = {k: round(stage[k]["median_ms"] / stage["plain"]["median_ms"], 4) for k, _ in XF_CASES}
+        res["call_over_plain_recode"] = {k: round(call[k]["median_ms"] / call["plain"]["median_ms"], 4) for k, _ in XF_CASES}
+        res["call_over_pixel_road"] = {k: round(call[k]["median_ms"] / road[k]["median_ms"], 4) for k in road}
+        batch.close()
+    finally:
+        ctx.free(canvases)
+        ctx.free(turned)
+        ctx.free(dst)
+        for im in images:
+            im.close()
+        for p in prepared:
+            p.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--small", action="store_true", help="an eighth of the images (a first look)")
+    ap.add_argument("--transform", action="store_true", help="the lossless flip / rotate against the plain recode and the pixel road")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     div = 8 if args.small else 1
@@ -124,9 +217,9 @@ def main():
     import jpegdec_amd as J
     ctx = J.Context(0)
     try:
-        res = {"tool": "tools/recode_bench.py --repeat %d" % args.repeat, "sampling": "4:2:0", "quality": 75, "warmup": args.warmup}
+        res = {"tool": "tools/recode_bench.py %s--repeat %d" % ("--transform " if args.transform else "", args.repeat), "sampling": "4:2:0", "quality": 75, "warmup": args.warmup}
         for name, (n, w, h) in shapes.items():
-            res[name] = workload(J, ctx, n, w, h, args.warmup, args.repeat)
+            res[name] = (xf_workload if args.transform else workload)(J, ctx, n, w, h, args.warmup, args.repeat)
     finally:
         ctx.close()
     line = json.dumps(res)
