@@ -404,6 +404,28 @@ size_t jda_pack_bytes(int32_t w, int32_t h, int32_t channels, int32_t elem_type)
 int jda_pack_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t src_bytes_per_pixel, const int32_t *rects,
                       int32_t layout_flags, int32_t elem_type, const void *table, void *const *dst);
 
+/* ---- The inverse: dense tensors in HBM turned into surfaces the encoders, the resizer and the orienter read
+ * src[i] = DENSE, dst[i].width_px x dst[i].rows pixels of C channels: JDA_PACK_HWC pixel-major or JDA_PACK_CHW planes, elements JDA_PACK_U8 /
+ * _F16 / _F32, aligned to its ELEMENT and to nothing else (image n of a uint8 [N,3,H,W] tensor begins n * 3 * H * W bytes into it).
+ * dst[i] = the surface: JDA_RGB8888 (dst_bytes_per_pixel 4, C = 3: bytes R, G, B, then A = 0xFF) or JDA_EIGHT_BIT_GRAYSCALE (1, C = 1);
+ * pixels 16-byte aligned, pitch_bytes a multiple of 16 and >= width_px * dst_bytes_per_pixel.  Tensor channel c is surface channel c, or
+ * 2 - c with JDA_PACK_BGR.  Exactly the width_px * dst_bytes_per_pixel bytes of each of the rows are written: not the padding up to the
+ * pitch, nothing behind the last row.
+ * JDA_PACK_U8: the byte itself, scale_bias == NULL.  JDA_PACK_F16 / _F32: byte = clamp(rint(x * scale[c] + bias[c]), 0, 255), c = the TENSOR
+ * channel -- x converted exactly to float32 (subnormals kept), the product rounded to float32, the sum rounded to float32 again (never a
+ * fused multiply-add), rint = round half to even, NaN -> 0, +inf -> 255, -inf -> 0: numpy's np.rint(x.astype(np.float32) * s + b) in float32.
+ * scale_bias: HOST memory, scale[0..C-1] then bias[0..C-1]; NULL: scale 255, bias 0.  For a tensor normalised as (v / 255 - mean) / std
+ * that is scale = 255 * std, bias = 255 * mean.
+ * ONE launch on the context's stream, synchronous.  n == 0 succeeds and launches nothing.  The caller makes sure that whatever wrote the
+ * tensors (another stream, another library) is done before the call.
+ * JDA_INVALID_PARAMETER: a null pointer or array; n < 0; a pixel size other than 1 or 4; unknown layout bits or element type; JDA_PACK_BGR
+ * with one channel; scale_bias with U8; a scale or bias that is not finite; a source misaligned for its element; a destination not 16-byte
+ * aligned; a pitch too small or not a multiple of 16; a size that is not positive; a dense source larger than JDA_PACK_MAX_BYTES; a
+ * destination whose written bytes share a byte with any source or with another destination's. */
+int jda_unpack_surfaces(jda_ctx *ctx, int32_t n, const void *const *src, int32_t layout_flags, int32_t elem_type,
+                        const float *scale_bias,      /* HOST: scale[0..C-1], bias[0..C-1]; NULL = 255, 0; must be NULL with U8 */
+                        const jda_output *dst, int32_t dst_bytes_per_pixel);
+
 /* ---- Decoded surfaces resized on the GPU: Pillow's Image.resize((ow, oh), Image.BILINEAR, box=(x, y, x + w, y + h)), bit for bit
  * src[i] = a decoded surface resident in HBM, JDA_RGB8888 (bytes_per_pixel 4) or JDA_EIGHT_BIT_GRAYSCALE (1); dst[i] = the result,
  * dst[i].width_px x dst[i].rows pixels of the same format: that IS the output size.  Both: pixels 16-byte aligned, pitch_bytes a multiple
@@ -562,6 +584,15 @@ int jda_transcode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int
 /* jda_transcode_to_host with jda_encode_surfaces_progressive as its encoder: a progressive file out (restart_interval must be 0) */
 int jda_transcode_to_host_progressive(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t options, const int32_t *rect, int32_t out_w, int32_t out_h,
                                       int32_t sampling, int32_t quality, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes);
+/* A dense image in HOST memory (w x h pixels of channels = 3 or 1; layout_flags, elem_type, scale_bias as jda_unpack_surfaces) to a JPEG file
+ * in host memory: the image goes up, jda_unpack_surfaces makes a surface of it, one of the encoders makes the file -- form JDA_RECODE_BASELINE
+ * (jda_encode_surfaces), JDA_RECODE_OPTIMIZE (JDA_ENCODE_OPTIMIZE) or JDA_RECODE_PROGRESSIVE (jda_encode_surfaces_progressive; restart_interval
+ * must be 0) -- and only the file comes back; the stages are queued back to back on the context's stream.  sampling, quality,
+ * restart_interval as jda_encode_job; a gray image (channels 1) takes JDA_ENCODE_GRAY and a colour image must not (JDA_INVALID_PARAMETER).
+ * host_file, capacity, *file_bytes and a file that does not fit: as jda_transcode_to_host. */
+int jda_encode_dense_to_host(jda_ctx *ctx, const void *host_dense, int32_t w, int32_t h, int32_t channels, int32_t layout_flags, int32_t elem_type,
+                             const float *scale_bias, int32_t sampling, int32_t quality, int32_t restart_interval, int32_t form,
+                             void *host_file, int64_t capacity, int64_t *file_bytes);
 /* jda_decode_to_host_ex followed by the orientation: prepare, upload, decode to a device canvas, orient its visible rectangle into a second
  * device surface (jda_orient_surfaces) and copy back only the W' * bpp x H' bytes of jda_oriented_geometry: row r at host_pixels + r * pitch_bytes,
  * pitch_bytes >= W' * bpp (any value), rows >= H'.  orientation < 0: the file's; 0..8 as given (0, 1: the visible rectangle as it is); above

@@ -163,6 +163,8 @@ _PROTOTYPES = [
     ("jda_decode_to_host_oriented", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     ("jda_pack_bytes", C.c_size_t, [C.c_int32] * 4),
     ("jda_pack_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    ("jda_unpack_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(_P), C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(Output), C.c_int32]),
+    ("jda_encode_dense_to_host", C.c_int, [_P, _P] + [C.c_int32] * 5 + [C.POINTER(C.c_float)] + [C.c_int32] * 4 + [_P, C.c_int64, C.POINTER(C.c_int64)]),
     ("jda_decode_to_host_packed", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t] + [C.POINTER(C.c_int32)] * 3),
     ("jda_resize_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output)]),
     ("jda_resize_surfaces_ex", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output), C.c_int32]),
@@ -956,6 +958,53 @@ def decode_packed_to_host(ctx: Context, jpeg: bytes, options=0, layout=PACK_HWC,
         return rc, None, g
     shape = (channels, h.value, w.value) if layout & PACK_CHW else (h.value, w.value, channels)
     return rc, flat[:w.value * h.value * channels].reshape(shape), g
+
+
+def _scale_bias(scale_bias, channels):
+    """None, or (scale, bias) / an array of 2 x channels values -> a ctypes float array: scale[0..C-1], bias[0..C-1]"""
+    if scale_bias is None:
+        return None
+    v = np.ascontiguousarray(np.asarray(scale_bias, np.float32).reshape(-1))
+    if v.size != 2 * channels:
+        raise ValueError("scale_bias: %d scales and %d biases" % (channels, channels))
+    return (C.c_float * v.size)(*[float(x) for x in v])
+
+
+def unpack_surfaces(ctx: Context, src_ptrs, dst, bytes_per_pixel, layout=PACK_HWC, elem_type=PACK_U8, scale_bias=None):
+    """jda_unpack_surfaces, the inverse of pack_surfaces: src_ptrs = device pointers of dense images (HWC / CHW, uint8 / float16 / float32),
+    dst = list of (device_ptr, pitch_bytes, width_px, rows) of the RGB8888 (4: A = 0xFF) or GRAY8 (1) surfaces they become -- width_px x rows
+    is the image's size.  scale_bias: None (255, 0), or (scale[C], bias[C]) for float elements (denormalise_params).  One launch."""
+    n = len(src_ptrs)
+    s = (_P * max(n, 1))(*src_ptrs)
+    d = (Output * max(n, 1))(*[Output(*o) for o in dst])
+    sb = _scale_bias(scale_bias, 3 if bytes_per_pixel == 4 else 1)
+    ctx.check(ctx.lib.jda_unpack_surfaces(ctx.handle, n, s, layout, elem_type, sb, d, bytes_per_pixel), "jda_unpack_surfaces")
+
+
+def encode_dense_to_host(ctx: Context, array, layout=PACK_HWC, sampling="4:2:0", quality=75, restart_interval=0, form="baseline", scale_bias=None, capacity=None):
+    """jda_encode_dense_to_host: array = a numpy image [h, w, C] (PACK_HWC, | PACK_BGR) or [C, h, w] (PACK_CHW), or [h, w] gray; uint8, float16
+    or float32; -> (rc, the file's bytes or None, the size the file has or needs).  form: "baseline", "optimize" or "progressive" (RECODE_*).
+    A gray image takes the gray sampling whatever `sampling` says.  capacity: the host buffer's bytes (default: the bound)."""
+    a = np.ascontiguousarray(array)
+    if a.ndim == 2:
+        a = a[None] if layout & PACK_CHW else a[..., None]
+    if a.ndim != 3:
+        raise ValueError("array: [h, w, C], [C, h, w] or [h, w]")
+    channels, h, w = a.shape if layout & PACK_CHW else (a.shape[2], a.shape[0], a.shape[1])
+    elem = {np.dtype(v): k for k, v in PACK_DTYPES.items()}.get(a.dtype)
+    if elem is None:
+        raise ValueError("array: uint8, float16 or float32")
+    samp = ENCODE_GRAY if channels == 1 else _sampling(sampling)
+    f = _recode_form(form)
+    if capacity is not None:
+        cap = capacity
+    else:
+        cap = encode_bound_progressive(w, h, samp) if f == RECODE_PROGRESSIVE else encode_bound(w, h, samp, restart_interval)
+    buf = np.zeros(max(cap, 1), dtype=np.uint8)
+    nbytes = C.c_int64(0)
+    rc = ctx.lib.jda_encode_dense_to_host(ctx.handle, a.ctypes.data_as(_P), w, h, channels, layout, elem, _scale_bias(scale_bias, channels), samp, quality,
+                                          restart_interval, f, buf.ctypes.data_as(_P), cap, C.byref(nbytes))
+    return rc, (buf[:nbytes.value].tobytes() if rc == 0 and nbytes.value <= cap else None), nbytes.value
 
 
 def resize_filter(resample) -> int:

@@ -3616,6 +3616,177 @@ template <int HWC, int ES, class IO> JDA_HD void jda_pack_tile(const jda_pack_ge
     for (uint32_t r = 0; r < runs; r++) jda_pack_planar<ES>(G, r, vec, io);
 }
 
+// ---- jda_unpack_*: dense tensors turned back into surfaces, the inverse of jda_pack_*  ---------------------------------
+// src = DENSE: h * w * C elements pixel-major (JDA_PACK_HWC) or C planes of h * w elements (JDA_PACK_CHW), aligned to its element and to
+// nothing else; C = 3 (tensor channel c is surface byte c, 2 - c with JDA_PACK_BGR) or 1 (gray).  dst = a surface: RGB8888 (bytes R, G, B
+// and A = 0xFF) or EIGHT_BIT_GRAYSCALE, 16-byte aligned, at a pitch that is a multiple of 16.  An element is the byte itself (ES = 1) or a
+// float16 / float32 x that becomes clamp(rint(x * scale[c] + bias[c]), 0, 255): the product rounded to float32, the sum rounded again
+// (never one fused multiply-add), round-half-to-even, NaN -> 0.
+// The schedule is laid on the DESTINATION, the aligned side here: a lane makes one aligned 16-byte vector of a surface row (4 RGBX
+// pixels or 16 gray ones), a tile = JDA_UNPACK_THREADS consecutive vectors, row-major over the job's ceil(w * bpp / 16) vectors a row.
+// A lane finds its (row, vector) with one division, loads the aligned dwords that hold its source elements (12 HWC bytes: at most 4; a
+// plane's 4 bytes: at most 2; F32 elements are dwords), realigns them (v_alignbyte), cuts the bytes out (v_perm_b32) or converts, and
+// stores once; only the last vector of a row may be partial and goes out as the dwords, the half and the byte inside the row.  Every
+// load is unconditional: a dword behind the image is the image's last dword again.  Neighbouring lanes load neighbouring bytes in every
+// format.  Memory goes through an IO policy: the kernel (jda_kernels.hip) and the lane-by-lane run on the CPU
+// (tests/hostsim/unpack_sim.cpp) are the same code.
+#define JDA_UNPACK_THREADS 256
+struct jda_unpack_params { float scale[3], bias[3]; };      // per TENSOR channel (kernel arguments)
+struct jda_unpack_geo {                      // a job and the launch's format, wave-uniform
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t dst_pitch, w, h, bpp, bgr;
+    jda_unpack_params p;
+};
+JDA_HD uint32_t jda_unpack_row_vectors(uint32_t w, uint32_t bpp) { return (w * bpp + 15u) >> 4; }
+JDA_HD uint32_t jda_unpack_tiles_of(uint32_t w, uint32_t h, uint32_t bpp) { return (jda_unpack_row_vectors(w, bpp) * h + JDA_UNPACK_THREADS - 1u) / JDA_UNPACK_THREADS; }
+// the job a tile of the flat list belongs to (as jda_pack_find_job)
+JDA_HD uint32_t jda_unpack_find_job(const jda_unpack_job *jobs, uint32_t n, uint32_t tile)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (JDA_G(const jda_unpack_job, jobs)[mid].tile0 <= tile) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// a float16's bits -> float32, exactly (subnormals kept)
+JDA_HD float jda_unpack_half(uint32_t h16)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)h16);
+#else
+    const uint32_t sign = (h16 & 0x8000u) << 16, e = (h16 >> 10) & 31u, m = h16 & 0x3ffu;
+    uint32_t bits;
+    if (e == 31u) bits = sign | 0x7f800000u | (m << 13);
+    else if (e) bits = sign | ((e + 112u) << 23) | (m << 13);
+    else if (!m) bits = sign;
+    else {
+        uint32_t k = 0, mm = m;
+        while (!(mm & 0x400u)) { mm <<= 1; k++; }
+        bits = sign | ((113u - k) << 23) | ((mm & 0x3ffu) << 13);
+    }
+    float f;
+    __builtin_memcpy(&f, &bits, 4);
+    return f;
+#endif
+}
+JDA_HD float jda_unpack_f32(uint32_t bits)
+{
+    float f;
+    __builtin_memcpy(&f, &bits, 4);
+    return f;
+}
+// clamp(rint(x * s + b), 0, 255): two roundings (v_mul_f32, v_add_f32), then v_rndne_f32; NaN -> 0
+JDA_HD uint32_t jda_unpack_byte(float x, float s, float b)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float p = x * s;
+    const float t = p + b;
+    float r = __builtin_rintf(t);
+    r = r >= 0.f ? r : 0.f;
+    r = r > 255.f ? 255.f : r;
+    return (uint32_t)r;
+}
+// K elements from element e0 on of the job's nbytes dense bytes -> the K * ES / 4 dwords that hold them, realigned: the aligned dwords
+// from the one that holds e0's first byte on, one more than the elements fill where they may straddle (ES < 4)
+template <int ES, int K, class IO> JDA_HD void jda_unpack_gather(IO &io, const jda_unpack_geo &G, uint32_t nbytes, uint32_t e0, uint32_t *r)
+{
+    const int NW = K * ES / 4, NL = ES == 4 ? NW : NW + 1;
+    const uint32_t lead = (uint32_t)((uintptr_t)G.src & 3u);
+    const uint8_t *base = G.src - lead;
+    const uint32_t last = (lead + nbytes - 1u) & ~3u, o = lead + e0 * (uint32_t)ES, a0 = o & ~3u;
+    uint32_t d[NL];
+#pragma unroll
+    for (int j = 0; j < NL; j++) {
+        const uint32_t a = a0 + 4u * (uint32_t)j;
+        d[j] = io.ld32(base + (a < last ? a : last));
+    }
+#pragma unroll
+    for (int j = 0; j < NW; j++) r[j] = ES == 4 ? d[j] : jda_alignbyte(d[j + 1 < NL ? j + 1 : j], d[j], o & 3u);
+}
+// element k of a gathered stream as a surface byte; c: its TENSOR channel
+template <int ES> JDA_HD uint32_t jda_unpack_element(const jda_unpack_geo &G, const uint32_t *r, uint32_t k, uint32_t c)
+{
+    if (ES == 1) return (r[k >> 2] >> (8u * (k & 3u))) & 0xffu;
+    const float x = ES == 2 ? jda_unpack_half((r[k >> 1] >> (16u * (k & 1u))) & 0xffffu) : jda_unpack_f32(r[k]);
+    return jda_unpack_byte(x, G.p.scale[c], G.p.bias[c]);
+}
+// the vector at p, `left` bytes of its row from p on: one store where the row holds all of it, else the dwords, the half and the byte inside
+template <class IO> JDA_HD void jda_unpack_store(IO &io, uint8_t *p, uint32_t left, const uint32_t *out)
+{
+    if (left >= 16u) { io.st128(p, out); return; }
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) {
+        if (4u * j + 4u <= left) { io.st32(p + 4u * j, out[j]); continue; }
+        if (4u * j >= left) continue;
+        const uint32_t rem = left - 4u * j;                       // 1 .. 3 (gray rows only)
+        if (rem & 2u) io.st16(p + 4u * j, out[j] & 0xffffu);
+        if (rem & 1u) io.st8(p + 4u * j + (rem & 2u), (out[j] >> (8u * (rem & 2u))) & 0xffu);
+    }
+}
+// vector `vec` of a job.  HWC = 1: a pixel-major source of three channels; HWC = 0: planes -- three (bpp 4) or the one of a gray image
+template <int HWC, int ES, class IO> JDA_HD void jda_unpack_vector(const jda_unpack_geo &G, uint32_t vec, IO &io)
+{
+    const uint32_t vpr = jda_unpack_row_vectors(G.w, G.bpp);
+    const uint32_t row = vec / vpr, col = vec - row * vpr;
+    if (row >= G.h) return;
+    const uint32_t npx = G.w * G.h;
+    uint32_t out[4];
+    if (HWC) {
+        uint32_t r[3 * ES];
+        jda_unpack_gather<ES, 12>(io, G, npx * 3u * (uint32_t)ES, (row * G.w + col * 4u) * 3u, r);
+        if (ES == 1) {
+            // twelve bytes R G B R G B .. in r[0..2]: pixel p is bytes 3 p .. 3 p + 2
+            out[0] = jda_perm(r[1], r[0], G.bgr ? 0x0d000102u : 0x0d020100u);
+            out[1] = jda_perm(r[1], r[0], G.bgr ? 0x0d030405u : 0x0d050403u);
+            out[2] = jda_perm(r[2], r[1], G.bgr ? 0x0d020304u : 0x0d040302u);
+            out[3] = jda_perm(r[2], r[2], G.bgr ? 0x0d010203u : 0x0d030201u);
+        } else {
+#pragma unroll
+            for (uint32_t p = 0; p < 4u; p++) {
+                out[p] = 0xff000000u;
+#pragma unroll
+                for (uint32_t c = 0; c < 3u; c++) out[p] |= jda_unpack_element<ES>(G, r, 3u * p + c, c) << (8u * (G.bgr ? 2u - c : c));
+            }
+        }
+    } else if (G.bpp == 4u) {
+        uint32_t pl[3][ES];
+#pragma unroll
+        for (uint32_t c = 0; c < 3u; c++) jda_unpack_gather<ES, 4>(io, G, npx * 3u * (uint32_t)ES, c * npx + row * G.w + col * 4u, pl[c]);
+        if (ES == 1) {
+            const uint32_t rr = G.bgr ? pl[2][0] : pl[0][0], gg = pl[1][0], bb = G.bgr ? pl[0][0] : pl[2][0];
+#pragma unroll
+            for (uint32_t p = 0; p < 4u; p++) out[p] = jda_perm(bb, jda_perm(gg, rr, 0x0c0c0400u + p * 0x0101u), 0x0d040100u + (p << 16));
+        } else {
+#pragma unroll
+            for (uint32_t p = 0; p < 4u; p++) {
+                out[p] = 0xff000000u;
+#pragma unroll
+                for (uint32_t c = 0; c < 3u; c++) out[p] |= jda_unpack_element<ES>(G, pl[c], p, c) << (8u * (G.bgr ? 2u - c : c));
+            }
+        }
+    } else {
+        uint32_t r[4 * ES];
+        jda_unpack_gather<ES, 16>(io, G, npx * (uint32_t)ES, row * G.w + col * 16u, r);
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) {
+            if (ES == 1) { out[j] = r[j]; continue; }
+            out[j] = 0u;
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) out[j] |= jda_unpack_element<ES>(G, r, 4u * j + k, 0u) << (8u * k);
+        }
+    }
+    jda_unpack_store(io, G.dst + (size_t)row * G.dst_pitch + (size_t)col * 16u, G.w * G.bpp - col * 16u, out);
+}
+// tile `tile` of a job, lane tid
+template <int HWC, int ES, class IO> JDA_HD void jda_unpack_tile(const jda_unpack_geo &G, uint32_t tile, uint32_t tid, IO &io)
+{
+    jda_unpack_vector<HWC, ES>(G, tile * JDA_UNPACK_THREADS + tid, io);
+}
+
 // ---- jda_rs_*: decoded surfaces resized with one of Pillow's antialiased convolution filters -------------------------
 // The result is Pillow's resize(F, box): a horizontal pass into 8-bit intermediates, then a vertical pass, both
 //   out = clip8((2^21 + sum_x in[min + x] * k[x]) >> 22)     per byte of a pixel, 32-bit sum, sum(k) ~ 2^22

@@ -210,6 +210,15 @@ struct jda_pack_job {
     uint32_t src_pitch, x, y, w, h, tile0;
 };
 
+// One image of an unpack launch (device pointers): src = the dense image (w * h * C elements, aligned to its element), dst = the surface
+// it becomes (16-byte aligned, dst_pitch a multiple of 16) of the launch's pixel size, w x h pixels.  tile0: the index of the job's
+// first tile in the launch's flat tile list.
+struct jda_unpack_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t dst_pitch, w, h, tile0;
+};
+
 // One image of a resize launch (device pointers): src = a decoded surface of the launch's pixel size (16-byte aligned, src_pitch a
 // multiple of 16), dst = out_w x out_h pixels at dst_pitch, the same.  htab / vtab: where the job's tap tables of the two axes begin in
 // the launch's table block, in dwords (the layout of a table: jda_rs_* in jda_device_core.h; the rectangle is in the taps' coordinates,

@@ -2116,6 +2116,58 @@ extern "C" hipError_t jda_launch_pack(const jda_pack_job *jobs, uint32_t n, uint
 }
 
 // ------------------------------------------------------------------------------------------------
+// jda_unpack_tiles<HWC, ES>: dense three-channel / planar tensors turned into RGB8888 / gray surfaces, the inverse of jda_pack_tiles (the
+// vectors and the lane's gather: jda_unpack_* in jda_device_core.h).  grid = the flat list of every job's tiles, a
+// workgroup finds its job by bisection (scalar loads) and keeps it in SGPRs.  HWC = 1: a pixel-major source; HWC = 0: planes (three, or
+// the one of a gray image; bpp wave-uniform).  ES = bytes of an element: 1 = the byte; 2 / 4 = float16 / float32 through scale and bias,
+// which are kernel arguments.  Global accesses: aligned dword loads, one aligned 16-byte store a lane; narrower stores only in the last
+// vector of a row.  No LDS, no atomics, nothing shared between tiles.
+typedef uint32_t jda_unpack_v4 __attribute__((ext_vector_type(4)));      // (a native vector: its assignment stays in the global address space)
+struct jda_unpack_io {
+    __device__ __forceinline__ uint32_t ld32(const uint8_t *p) const { return *(const jda_u32_alias JDA_GLOBAL *)JDA_G(const uint8_t, p); }
+    __device__ __forceinline__ void st128(uint8_t *p, const uint32_t *v) const { const jda_unpack_v4 q = { v[0], v[1], v[2], v[3] }; *(jda_unpack_v4 JDA_GLOBAL *)JDA_G(uint8_t, p) = q; }
+    __device__ __forceinline__ void st32(uint8_t *p, uint32_t v) const { *(jda_u32_alias JDA_GLOBAL *)JDA_G(uint8_t, p) = v; }
+    __device__ __forceinline__ void st16(uint8_t *p, uint32_t v) const { *(uint16_t JDA_GLOBAL *)JDA_G(uint8_t, p) = (uint16_t)v; }
+    __device__ __forceinline__ void st8(uint8_t *p, uint32_t v) const { *JDA_G(uint8_t, p) = (uint8_t)v; }
+};
+template <int HWC, int ES>
+__global__ __launch_bounds__(JDA_UNPACK_THREADS)
+void jda_unpack_tiles(const jda_unpack_job *__restrict__ jobs, uint32_t n_jobs, jda_unpack_params params, uint32_t bpp, uint32_t bgr)
+{
+    const uint32_t tile = blockIdx.x;
+    const jda_unpack_job JDA_GLOBAL *job = JDA_G(const jda_unpack_job, jobs) + jda_uni32(jda_unpack_find_job(jobs, n_jobs, tile));
+    jda_unpack_geo G;
+    G.src = jda_uni_ptr(job->src); G.dst = jda_uni_ptr(job->dst);
+    G.dst_pitch = jda_uni32(job->dst_pitch);
+    G.w = jda_uni32(job->w); G.h = jda_uni32(job->h);
+    G.bpp = HWC ? 4u : bpp; G.bgr = bgr; G.p = params;
+    const uint32_t local = tile - jda_uni32(job->tile0);
+    if (G.w == 0u || G.h == 0u) return;
+    jda_unpack_io io;
+    jda_unpack_tile<HWC, ES>(G, local, threadIdx.x, io);
+}
+template <int HWC>
+static hipError_t launch_unpack(uint32_t es, const jda_unpack_job *jobs, uint32_t n, uint32_t n_tiles, const jda_unpack_params &params, uint32_t bpp, uint32_t bgr, hipStream_t stream)
+{
+    if (es == 1u) JDA_LAUNCH((jda_unpack_tiles<HWC, 1>), dim3(n_tiles), dim3(JDA_UNPACK_THREADS), 0, stream, jobs, n, params, bpp, bgr);
+    else if (es == 2u) JDA_LAUNCH((jda_unpack_tiles<HWC, 2>), dim3(n_tiles), dim3(JDA_UNPACK_THREADS), 0, stream, jobs, n, params, bpp, bgr);
+    else if (es == 4u) JDA_LAUNCH((jda_unpack_tiles<HWC, 4>), dim3(n_tiles), dim3(JDA_UNPACK_THREADS), 0, stream, jobs, n, params, bpp, bgr);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// n jobs of one destination pixel size, layout and element size; n_tiles = the sum of their tiles (the jobs carry where each one's begin);
+// scale_bias: scale[0..2], bias[0..2] per tensor channel (HOST; read only where es > 1)
+extern "C" hipError_t jda_launch_unpack(const jda_unpack_job *jobs, uint32_t n, uint32_t n_tiles, int hwc, uint32_t es, const float *scale_bias,
+                                        uint32_t bpp, uint32_t bgr, hipStream_t stream)
+{
+    if (n == 0 || n_tiles == 0) return hipSuccess;
+    if ((bpp != 1u && bpp != 4u) || (hwc && bpp != 4u) || !scale_bias) return hipErrorInvalidValue;
+    jda_unpack_params params;
+    for (int c = 0; c < 3; c++) { params.scale[c] = scale_bias[c]; params.bias[c] = scale_bias[3 + c]; }
+    return hwc ? launch_unpack<1>(es, jobs, n, n_tiles, params, bpp, bgr, stream) : launch_unpack<0>(es, jobs, n, n_tiles, params, bpp, bgr, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
 // jda_resize_tiles<BPP> / jda_resize_tiles_signed<BPP>: decoded surfaces resized with one of Pillow's antialiased filters (the passes, the tile and its LDS image:
 // jda_rs_* in jda_device_core.h).  grid = the flat list of every job's tiles, a workgroup finds its job by bisection
 // (scalar loads) and keeps it in SGPRs.  A workgroup resamples the source rows its tile needs horizontally into LDS (8-bit pixels), and

@@ -23,6 +23,7 @@
 
 #include "jda_runtime_internal.h"
 #include "jda_pack_plan.h"
+#include "jda_unpack_plan.h"
 #include "jda_resize_plan.h"
 #include "jda_encode_plan.h"
 #include "jda_recode_plan.h"
@@ -2226,6 +2227,118 @@ static int transcode_call(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
         }
     }
     return oc_close(F, rc, plan.block);
+}
+
+// ---- dense tensors back into surfaces (jda_unpack_tiles in jda_kernels.hip; vectors and the lane's gather: jda_device_core.h)
+// Check n jobs (jda_unpack_plan.h) and upload their records, and wait for them as pack_upload does; unpack_launch then queues the kernel.
+struct unpack_plan { void *block; uint32_t n, n_tiles, es, hwc, bpp, bgr; float scale_bias[6]; };
+static int unpack_upload(jda_ctx *ctx, int32_t n, const void *const *src, int32_t layout_flags, int32_t elem_type, const float *scale_bias,
+                         const jda_output *dst, int32_t dst_bytes_per_pixel, unpack_plan *plan)
+{
+    plan->block = NULL; plan->n = (uint32_t)n; plan->n_tiles = 0;
+    jda_unpack_plan_out P;
+    const int rc = jda_unpack_plan_jobs(n, src, layout_flags, elem_type, scale_bias, dst, dst_bytes_per_pixel, &P);
+    if (rc != JDA_SUCCESS) return rc;
+    plan->es = P.es; plan->hwc = P.hwc; plan->bpp = (uint32_t)dst_bytes_per_pixel; plan->bgr = (layout_flags & JDA_PACK_BGR) ? 1u : 0u;
+    memcpy(plan->scale_bias, P.scale_bias, sizeof(plan->scale_bias));
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, align16(P.jobs.size() * sizeof(jda_unpack_job)));
+    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(unpack jobs)");
+    e = hipMemcpyAsync(blk, P.jobs.data(), P.jobs.size() * sizeof(jda_unpack_job), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { jda_pool_free(ctx, blk); return jda_set_err(ctx, e, "unpack jobs"); }
+    plan->block = blk; plan->n_tiles = P.n_tiles;
+    return JDA_SUCCESS;
+}
+static int unpack_launch(jda_ctx *ctx, const unpack_plan &plan)
+{
+    const hipError_t e = jda_launch_unpack((const jda_unpack_job *)plan.block, plan.n, plan.n_tiles, (int)plan.hwc, plan.es, plan.scale_bias, plan.bpp, plan.bgr, ctx->stream);
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_unpack_tiles");
+}
+
+int jda_unpack_surfaces(jda_ctx *ctx, int32_t n, const void *const *src, int32_t layout_flags, int32_t elem_type, const float *scale_bias,
+                        const jda_output *dst, int32_t dst_bytes_per_pixel)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0) return JDA_INVALID_PARAMETER;
+    { const int frc = jda_unpack_check_format(dst_bytes_per_pixel, layout_flags, elem_type, scale_bias); if (frc != JDA_SUCCESS) return frc; }
+    if (n == 0) return JDA_SUCCESS;
+    (void)hipSetDevice(ctx->device);
+    unpack_plan plan;
+    int rc = unpack_upload(ctx, n, src, layout_flags, elem_type, scale_bias, dst, dst_bytes_per_pixel, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    return finish_surfaces(ctx, unpack_launch(ctx, plan), plan.block, "jda_unpack_surfaces");
+}
+
+int jda_encode_dense_to_host(jda_ctx *ctx, const void *host_dense, int32_t w, int32_t h, int32_t channels, int32_t layout_flags, int32_t elem_type,
+                             const float *scale_bias, int32_t sampling, int32_t quality, int32_t restart_interval, int32_t form,
+                             void *host_file, int64_t capacity, int64_t *file_bytes)
+{
+    if (file_bytes) *file_bytes = 0;
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!host_dense || !host_file || !file_bytes || capacity < 0 || w <= 0 || h <= 0 || (channels != 1 && channels != 3)) return JDA_INVALID_PARAMETER;
+    if (form != JDA_RECODE_BASELINE && form != JDA_RECODE_OPTIMIZE && form != JDA_RECODE_PROGRESSIVE) return JDA_INVALID_PARAMETER;
+    const bool progressive = form == JDA_RECODE_PROGRESSIVE;
+    if (progressive && restart_interval != 0) return JDA_INVALID_PARAMETER;
+    const int bpp = channels == 3 ? 4 : 1;
+    int rc = jda_unpack_check_format(bpp, layout_flags, elem_type, scale_bias);
+    if (rc != JDA_SUCCESS) return rc;
+    if (quality < 1 || quality > 100 || (sampling == JDA_ENCODE_GRAY) != (bpp == 1)) return JDA_INVALID_PARAMETER;
+    const uint64_t dense = (uint64_t)w * (uint64_t)h * (uint64_t)channels * jda_pack_elem_bytes(elem_type);
+    if (dense > JDA_PACK_MAX_BYTES) return JDA_INVALID_PARAMETER;
+    int64_t bound = 0;
+    rc = progressive ? jda_encode_bound_progressive(w, h, sampling, &bound) : jda_encode_bound_bytes(w, h, sampling, restart_interval, &bound);
+    if (rc != JDA_SUCCESS) return rc;
+    (void)hipSetDevice(ctx->device);
+    const size_t pitch = align16((size_t)w * bpp), sbytes = pitch * (size_t)h;
+    const int64_t fcap = std::min(capacity, bound);                                        // (no file is longer than the bound)
+    uint8_t *blk = NULL;                                                                   // the surface, the dense image behind it, the file behind that
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, sbytes + align16((size_t)dense) + (size_t)fcap + 16);
+    if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(dense image)"); return JDA_ERROR_MEMORY; }
+    uint8_t *ddense = blk + sbytes;
+    void *dfile = ddense + align16((size_t)dense);
+    jda_output S;
+    S.pixels = blk; S.pitch_bytes = (int32_t)pitch; S.width_px = w; S.rows = h;
+    unpack_plan plan;
+    plan.block = NULL;
+    // the image and the job record go up; then unpack and the encoder's stages are queued back to back on the one stream, and its two looks
+    // at the sizes are the only waits
+    e = hipMemcpyAsync(ddense, host_dense, (size_t)dense, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) rc = jda_set_err(ctx, e, "upload");
+    const void *const srcs[1] = { ddense };
+    if (rc == JDA_SUCCESS) rc = unpack_upload(ctx, 1, srcs, layout_flags, elem_type, scale_bias, &S, bpp, &plan);
+    if (rc == JDA_SUCCESS) rc = unpack_launch(ctx, plan);
+    if (rc == JDA_SUCCESS) {
+        const jda_encode_job E = { 0, 0, w, h, sampling, quality, restart_interval, 0 };
+        const uint32_t flags = form == JDA_RECODE_OPTIMIZE ? (uint32_t)JDA_ENCODE_OPTIMIZE : 0u;
+        int32_t st = JDA_SUCCESS;
+        rc = progressive ? jda_encode_surfaces_progressive(ctx, 1, &S, bpp, &E, &dfile, &fcap, file_bytes, &st)
+                         : jda_encode_surfaces_ex(ctx, 1, &S, bpp, &E, flags ? &flags : NULL, &dfile, &fcap, file_bytes, &st);
+        if (rc == JDA_SUCCESS) rc = st;
+        if (rc == JDA_SUCCESS) {
+            e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);
+            { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+            if (e != hipSuccess) rc = jda_set_err(ctx, e, "copy back");
+        }
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    jda_pool_free(ctx, plan.block);
+    jda_pool_free(ctx, blk);
+    return rc;
+}
+
+// Measuring hook of tools/unpack_bench.py (not part of the public header): the unpack launch between the context's two timer events on
+// its stream -- the job records go up before the first event.  ms[k]: repeat k.
+int jda_internal_unpack_time(jda_ctx *ctx, int32_t n, const void *const *src, int32_t layout_flags, int32_t elem_type, const float *scale_bias,
+                             const jda_output *dst, int32_t dst_bytes_per_pixel, int32_t reps, float *ms)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n <= 0 || reps <= 0 || !ms) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    unpack_plan plan;
+    const int rc = unpack_upload(ctx, n, src, layout_flags, elem_type, scale_bias, dst, dst_bytes_per_pixel, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    return timed_launches(ctx, reps, ms, plan.block, "jda_internal_unpack_time", [&]() { return unpack_launch(ctx, plan); });
 }
 
 // Measuring hook of tools/resize_bench.py (not part of the public header): the resize launch between the context's two timer events on

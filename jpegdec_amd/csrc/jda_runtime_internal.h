@@ -147,6 +147,11 @@ extern "C" hipError_t jda_launch_orient(const jda_orient_job *jobs, uint32_t n, 
 // `table`, device memory), one workgroup a tile of 4 KiB of destination; n_tiles: the length of the flat tile list
 extern "C" hipError_t jda_launch_pack(const jda_pack_job *jobs, uint32_t n, uint32_t n_tiles, int hwc, uint32_t es, const uint8_t *table,
                                       uint32_t bpp, uint32_t bgr, hipStream_t stream);
+// n jobs of one destination pixel size (bpp 1 or 4), layout (hwc: pixel-major, RGB8888 destinations only) and element size (es 1: bytes,
+// 2 / 4: float16 / float32 through scale_bias = scale[0..2], bias[0..2] per tensor channel, HOST memory: they travel as kernel arguments),
+// one workgroup a tile of 256 destination vectors; n_tiles: the length of the flat tile list
+extern "C" hipError_t jda_launch_unpack(const jda_unpack_job *jobs, uint32_t n, uint32_t n_tiles, int hwc, uint32_t es, const float *scale_bias,
+                                        uint32_t bpp, uint32_t bgr, hipStream_t stream);
 // n jobs of one pixel size (1 or 4) resized through the tap tables in `tables` (device memory; the jobs carry where theirs begin), one
 // workgroup a tile of 64 output dwords x the job's tile rows; n_tiles: the length of the flat tile list, lds_bytes: the largest tile's LDS;
 // signed_taps: the tables of a filter with negative taps (BICUBIC, LANCZOS), run by jda_resize_tiles_signed

@@ -1,7 +1,8 @@
 """Decoded images as torch tensors on the GPU that decoded them: a Pipeline batch into scratch canvases, then ONE jda_pack_surfaces launch
 straight into the tensors' memory (include/jpegdec_amd.h: dense RGB / BGR or planar CHW, uint8 or float through a lookup table).  With
 size=(H, W) ONE jda_resize_surfaces launch (Pillow's antialiased BILINEAR, bit for bit) stands between the two, and the result is one batch.
-torch is imported when decode_to_tensors runs, not when the package is.  One process, one HIP runtime: a torch build that ships its own
+encode_tensors is the way back: ONE jda_unpack_surfaces launch from the tensors' own memory into scratch surfaces, one encode call, JPEG files out.
+torch is imported when decode_to_tensors or encode_tensors runs, not when the package is.  One process, one HIP runtime: a torch build that ships its own
 (a wheel does) must be imported BEFORE libjpegdec_amd.so is loaded (before the first Context), so that the library binds to the runtime
 torch already brought; the other way round the process holds two runtimes, torch finds no GPU, and decode_to_tensors says so."""
 import ctypes as C
@@ -29,6 +30,96 @@ def normalise_table(mean, std, dtype=np.float32):
         raise ValueError("mean and std: one value per channel each")
     t = (np.arange(256, dtype=np.float64)[None, :] / 255.0 - mean[:, None]) / std[:, None]
     return np.ascontiguousarray(t.astype(_np_dtype(dtype)))
+
+
+def denormalise_params(mean, std):
+    """The inverse of normalise_table for unpack_surfaces / encode_dense_to_host / encode_tensors: a float32 array [2, C] = (scale, bias) with
+    scale[c] = 255 * std[c], bias[c] = 255 * mean[c], worked out in float64 and cast to float32 -- a tensor normalised as (v / 255 - mean) /
+    std becomes bytes again as clamp(rint(x * scale + bias), 0, 255).  The channel is the TENSOR channel: with BGR tensors, mean[0] is blue's."""
+    mean, std = np.atleast_1d(np.asarray(mean, np.float64)), np.atleast_1d(np.asarray(std, np.float64))
+    if mean.shape != std.shape or mean.ndim != 1:
+        raise ValueError("mean and std: one value per channel each")
+    return np.ascontiguousarray(np.stack([255.0 * std, 255.0 * mean]).astype(np.float32))
+
+
+def encode_tensors(ctx, images, quality=75, sampling="4:2:0", restart_interval=0, optimize=False, progressive=False, layout="CHW", bgr=False, scale_bias=None):
+    """images -> list of JPEG files (bytes).  images: ONE [N,C,H,W] / [N,H,W,C] tensor, or a list of [C,H,W] / [H,W,C] tensors of any sizes
+    (layout "CHW" or "HWC"; bgr: channel 0 is blue) -- all on cuda:<ctx.device>, all of one dtype (torch.uint8, float16 or float32), all of
+    one C (3, or 1: gray, which takes the gray sampling whatever `sampling` says); anything else is a ValueError before the GPU is touched.
+    uint8: the bytes themselves.  float: byte = clamp(rint(x * scale[c] + bias[c]), 0, 255), scale_bias = (scale[C], bias[C]) -- None: (255,
+    0), for values in [0, 1]; denormalise_params(mean, std) for a normalised tensor.  optimize / progressive / restart_interval: as
+    thumbnails().  One jda_unpack_surfaces launch from the tensors' own memory into scratch surfaces, one encode call; only the files are
+    copied back.  The tensors must be complete on torch's side: the call synchronises the device before its first launch."""
+    import torch
+
+    if layout not in ("CHW", "HWC"):
+        raise ValueError("layout: 'CHW' or 'HWC'")
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise ValueError("images: one [N,C,H,W] / [N,H,W,C] tensor, or a list of [C,H,W] / [H,W,C] tensors")
+        images = [images[k] for k in range(images.shape[0])]
+    else:
+        images = list(images)
+        if any(not isinstance(t, torch.Tensor) or t.dim() != 3 for t in images):
+            raise ValueError("images: one [N,C,H,W] / [N,H,W,C] tensor, or a list of [C,H,W] / [H,W,C] tensors")
+    n = len(images)
+    if n == 0:
+        return []
+    device = torch.device("cuda", ctx.device)
+    if any(t.device != device for t in images):
+        raise ValueError("images: all on %s" % device)
+    if any(t.dtype != images[0].dtype for t in images):
+        raise ValueError("images: all of one dtype")
+    npdt = _np_dtype(images[0].dtype)
+    elem = {np.uint8: B.PACK_U8, np.float16: B.PACK_F16, np.float32: B.PACK_F32}[npdt]
+    dims = [(t.shape[0], t.shape[1], t.shape[2]) if layout == "CHW" else (t.shape[2], t.shape[0], t.shape[1]) for t in images]      # (C, H, W)
+    channels = dims[0][0]
+    if channels not in (1, 3) or any(d[0] != channels for d in dims):
+        raise ValueError("images: all of 3 channels or all of 1")
+    if any(d[1] <= 0 or d[2] <= 0 for d in dims):
+        raise ValueError("images: empty")
+    if bgr and channels == 1:
+        raise ValueError("bgr: not with one channel")
+    if elem == B.PACK_U8 and scale_bias is not None:
+        raise ValueError("scale_bias: with float16 / float32 tensors")
+    if scale_bias is not None:
+        scale_bias = np.asarray(scale_bias.detach().cpu().numpy() if isinstance(scale_bias, torch.Tensor) else scale_bias, np.float32).reshape(-1)
+        if scale_bias.size != 2 * channels or not np.all(np.isfinite(scale_bias)):
+            raise ValueError("scale_bias: %d finite scales and %d finite biases" % (channels, channels))
+    if progressive and restart_interval != 0:
+        raise ValueError("progressive: restart_interval must be 0")
+    bpp = 4 if channels == 3 else 1
+    if isinstance(sampling, str) and sampling not in B.ENCODE_SAMPLINGS:
+        raise ValueError("sampling: one of %s" % ", ".join(repr(k) for k in B.ENCODE_SAMPLINGS))
+    samp = B.ENCODE_GRAY if channels == 1 else B.ENCODE_SAMPLINGS[sampling] if isinstance(sampling, str) else int(sampling)
+    flags = (B.PACK_CHW if layout == "CHW" else B.PACK_HWC) | (B.PACK_BGR if bgr else 0)
+    dense = [t.contiguous() for t in images]                              # (the copies live until this function returns: behind the encode call)
+    pitches = [(w * bpp + 15) & ~15 for _, h, w in dims]
+    caps = [B.encode_bound_progressive(w, h, samp) if progressive else B.encode_bound(w, h, samp, restart_interval) for _, h, w in dims]
+    soffs, total = [], 0
+    for p, (_, h, w) in zip(pitches, dims):
+        soffs.append(total)
+        total += (p * h + 255) & ~255
+    foffs = []
+    for c in caps:
+        foffs.append(total)
+        total += (c + 255) & ~255
+    torch.cuda.synchronize(device)                                        # (the tensors were written on torch's stream)
+    base = ctx.malloc(total)
+    try:
+        surfaces = [(base + soffs[k], pitches[k], dims[k][2], dims[k][1]) for k in range(n)]
+        B.unpack_surfaces(ctx, [t.data_ptr() for t in dense], surfaces, bpp, flags, elem, scale_bias)
+        jobs, dsts = [(0, 0, dims[k][2], dims[k][1], samp, quality, restart_interval) for k in range(n)], [base + foffs[k] for k in range(n)]
+        if progressive:
+            nbytes, st = B.encode_surfaces_progressive(ctx, surfaces, bpp, jobs, dsts, caps)
+        else:
+            nbytes, st = B.encode_surfaces(ctx, surfaces, bpp, jobs, dsts, caps, [B.ENCODE_OPTIMIZE] * n if optimize else None)
+        if any(st):
+            raise B.JdaError(max(st), "jda_encode_surfaces")
+        # (the files alone come back: nbytes[k] bytes each)
+        return [ctx.to_host(base + foffs[k], nbytes[k]).tobytes() for k in range(n)]
+    finally:
+        ctx.free(base)
 
 
 def prescale_option(info, pixel_type, options, size):
