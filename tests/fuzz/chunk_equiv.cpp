@@ -3,7 +3,7 @@
 // exposes the chunk size as a variable: the product library has no such switch -- there the size follows from the scan and the threads).
 // For every file given: chunks of 512 .. 16 K bytes, the file as it is and corrupted copies (bytes of the entropy-coded data changed):
 // the same verdict as the serial pre-scan and, where both index the whole image, the same index in the sense of jda_index_equivalent,
-// DC values, truncation count and continuation entries.  usage: chunk_equiv iterations seed file.jpg..
+// DC values, truncation count, continuation entries and fast-multiply verdict.  usage: chunk_equiv iterations seed file.jpg..
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +17,7 @@
 extern uint32_t jda_test_chunk_bytes;            // jda_frontend.cpp under JDA_TEST_CHUNK_BYTES_HOOK (0: the product's rule)
 extern uint32_t jda_test_chunk_taken;            // counts the images host_prescan_chunks indexed
 extern std::atomic<int> jda_test_throw_countdown;   // the n-th allocation point a pre-scan worker passes throws std::bad_alloc (0: never)
+extern "C" uint32_t jda_image_fast_mul(const jda_image *img);   // the summary the kernels' 24-bit multiplies hang on (jda_frontend.cpp; not in the public header)
 extern "C" int jda_host_prescan_threads(void);   // the caller + the helper threads (1: a machine with fewer than four CPUs -- nothing runs in chunks there)
 
 static uint32_t rng_state = 1;
@@ -38,7 +39,7 @@ static bool same(const std::vector<uint8_t> &b, int32_t flags, const char *what)
         const uint32_t *xa = jda_image_block_cont(a, &fa, &ca), *xp = jda_image_block_cont(p, &fp, &cp);
         ok = na == np && jda_image_truncation_events(a) == jda_image_truncation_events(p) && ca == cp &&
              !memcmp(jda_image_block_dc(a), jda_image_block_dc(p), (size_t)nb * 2) && !memcmp(fa, fp, ((size_t)nb + 1) * 4) && (ca == 0 || !memcmp(xa, xp, (size_t)ca * 4));
-        if (ok) ok = na == (uint32_t)(I->mcus_x * I->mcus_y) ? jda_index_equivalent(ia, ip, nb) != 0 : !memcmp(ia, ip, ((size_t)nb + 1) * 4);
+        if (ok) ok = na == (uint32_t)(I->mcus_x * I->mcus_y) ? jda_index_equivalent(ia, ip, nb) != 0 && jda_image_fast_mul(a) == jda_image_fast_mul(p) : !memcmp(ia, ip, ((size_t)nb + 1) * 4);
     }
     if (!ok) fprintf(stderr, "chunk_equiv: %s differs (chunk bytes %u, flags %d)\n", what, jda_test_chunk_bytes, flags);
     if (a) jda_image_free(a);
