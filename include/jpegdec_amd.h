@@ -844,6 +844,33 @@ int jda_recode_images_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *src, 
 int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t form, int32_t restart_interval, const jda_recode_xform *xform,
                           void *host_file, int64_t capacity, int64_t *file_bytes);
 
+/* ------------------------------------------------------------------ libjpeg-exact decode
+ * The decode stages above reproduce the reference, an embedded decoder.  These calls decode with libjpeg's own arithmetic instead, so that
+ * the pixels are those of Pillow / libjpeg-turbo (Image.open(f).convert("RGB")): T.81's quantised coefficients times the RAW DQT entries,
+ * jidctint.c's 8x8 islow IDCT (32-bit integers, the range-limit table's wrap-around included), "fancy" chroma upsampling over each component's
+ * own extent with the edge sample replicated, jdcolor.c's 16-bit colour constants.  The definition is stated in numpy in tests/exact_util.py.
+ * Where a pre-limit IDCT result leaves -512 .. 511 libjpeg-turbo's SIMD IDCT saturates and the C code wraps: these calls wrap.
+ * Sources as in jda_recode_images -- exactly one pointer set (else JDA_INVALID_PARAMETER from the call): a resident baseline image (its
+ * index from the host pre-scan or from JDA_PREPARE_DEVICE_PRESCAN) or a resident coefficient image, dense or sparse.  pixel_types (NULL:
+ * RGB8888): JDA_RGB8888 (R, G, B, A = 0xFF; a gray file: R = G = B = Y) or JDA_EIGHT_BIT_GRAYSCALE (the Y plane, Image.draft("L")).
+ * outputs: base and pitch as jda_batch_create; exactly the min(width, width_px) x min(height, rows) visible pixels are written -- the
+ * image's own size, not the MCU grid's -- and no other byte.  Launches, whatever n: one of jda_exact_planes per (layout, dense | sparse |
+ * baseline image) present, one of jda_exact_colour per
+ * layout present.  Synchronous, like jda_coef_decode_surfaces.  Per image, in status[i], the rest of the call going on:
+ * JDA_INVALID_PARAMETER -- another pixel type, a surface jda_batch_create would refuse; JDA_UNSUPPORTED_FEATURE -- a file with an Adobe
+ * APP14 segment, a resident image of a progressive file (its first scan only: pass the coefficient image); JDA_DECODE_ERROR -- a baseline
+ * source whose pre-scan validated fewer MCUs than the image has.  A call in which every image is refused launches nothing.
+ * jda_exact_decode_planes: the first stage alone, libjpeg's raw-data output: planes[3 i + c] (c: Y, Cb, Cr; a gray image: Y only) receives
+ * min(width_px, extent) x min(rows, extent) samples of the component's own extent -- width x height for Y, ceil(width / hs) x
+ * ceil(height / vs) for Cb and Cr -- at any base and pitch.
+ * jda_decode_to_host_exact: file in, pixels out -- a baseline file through jda_prepare + jda_upload, a progressive one (every scan, no
+ * option bit) through jda_progressive_prepare + jda_coef_upload_ex(JDA_COEF_AUTO); host_pixels: width x height pixels at pitch_bytes (a pitch
+ * below the width's bytes: JDA_INVALID_PARAMETER), of which min(rows, height) rows are written. */
+int jda_exact_decode_surfaces(jda_ctx *ctx, int32_t n, const jda_recode_source *sources, const jda_output *outputs, const int32_t *pixel_types,
+                              int32_t *status);
+int jda_exact_decode_planes(jda_ctx *ctx, int32_t n, const jda_recode_source *sources, const jda_output *planes, int32_t *status);
+int jda_decode_to_host_exact(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, void *host_pixels, int32_t pitch_bytes, int32_t rows);
+
 const char *jda_version(void);
 
 #ifdef __cplusplus

@@ -223,6 +223,9 @@ _PROTOTYPES = [
     ("jda_recode_images_ex", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(RecodeJob), C.POINTER(RecodeXform), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("jda_recode_to_host_ex", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RecodeXform), _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("jda_exact_decode_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("jda_exact_decode_planes", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32)]),
+    ("jda_decode_to_host_exact", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
 ]
 
 
@@ -1244,6 +1247,47 @@ def recode(ctx: Context, files, form="optimize", transform=None, crop=None, trim
         for p in prepared:
             if p is not None:
                 p.close()
+
+
+def _recode_sources(sources):
+    n = len(sources)
+    return (RecodeSource * max(n, 1))(*[RecodeSource(q.handle, None) if isinstance(q, DeviceImage) else RecodeSource(None, q.handle) for q in sources])
+
+
+def exact_decode(ctx: Context, sources, outputs, pixel_types=None):
+    """jda_exact_decode_surfaces: the libjpeg-exact decode (Pillow's pixels, not the reference's) of resident sources -- DeviceImage (a
+    baseline file) or DeviceCoef (dense or sparse) each -- into surfaces.  outputs = (device pointer, pitch, width_px, rows) each;
+    pixel_types: RGB8888 (the default) or GRAY8 each.  Exactly min(width, width_px) x min(height, rows) pixels of an image are written.
+    -> the statuses; the call's own refusals raise JdaError."""
+    n = len(sources)
+    o = (Output * max(n, 1))(*[Output(*q) for q in outputs])
+    pt = None if pixel_types is None else (C.c_int32 * max(n, 1))(*pixel_types)
+    status = (C.c_int32 * max(n, 1))()
+    ctx.check(ctx.lib.jda_exact_decode_surfaces(ctx.handle, n, _recode_sources(sources), o, pt, status), "jda_exact_decode_surfaces")
+    return list(status)[:n]
+
+
+def exact_planes(ctx: Context, sources, planes):
+    """jda_exact_decode_planes: the 8-bit component planes at their own extents (libjpeg's raw-data output).  planes = per source three
+    (device pointer, pitch, width, rows) -- Y, Cb, Cr; a gray image's last two are not looked at.  -> the statuses."""
+    n = len(sources)
+    flat = [Output(*q) for three in planes for q in three]
+    status = (C.c_int32 * max(n, 1))()
+    ctx.check(ctx.lib.jda_exact_decode_planes(ctx.handle, n, _recode_sources(sources), (Output * max(3 * n, 1))(*flat), status), "jda_exact_decode_planes")
+    return list(status)[:n]
+
+
+def decode_to_host_exact(ctx: Context, jpeg: bytes, pixel_type=RGB8888):
+    """jda_decode_to_host_exact: one file, baseline or progressive, to the pixels Pillow gives -- (rc, height x width x 4 RGBA bytes or
+    height x width gray)."""
+    info = ImageInfo()
+    rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
+    if rc != 0:
+        raise JdaError(rc, "jda_parse")
+    bpp = 4 if pixel_type == RGB8888 else 1
+    canvas = np.zeros((info.height, info.width * bpp), dtype=np.uint8)
+    rc = ctx.lib.jda_decode_to_host_exact(ctx.handle, jpeg, len(jpeg), pixel_type, canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0])
+    return rc, (canvas.reshape(info.height, info.width, 4) if bpp == 4 else canvas)
 
 
 def decode_resized_to_host(ctx: Context, jpeg: bytes, size, pixel_type=RGB8888, options=0, rect=None, out=None, filter=0):

@@ -5163,4 +5163,241 @@ template <class IO> JDA_HD void jda_rc_coef_block_xf(const jda_en_arrays &A, con
     else jda_rc_coef_block_xf_t<false>(A, J, S, X, job, b, bad, io);
 }
 
+// ================================================================================================
+// jda_ex_*: the libjpeg-exact decode: the coefficients of a coefficient image through libjpeg's own arithmetic -- the
+// RAW DQT entries, jidctint.c's islow IDCT, "fancy" chroma upsampling, jdcolor.c's constants -- so that the pixels are Pillow's, not the
+// reference's.  The definition is stated once more in numpy (tests/exact_util.py).  Two stages, a kernel each:
+//   planes   the decode's tile (one wave64, <= 64 consecutive blocks of an MCU row) behind a load phase by source: the coefficient kernels'
+//            (jda_ct_load, or jda_cs_zero + jda_cs_scatter, as they stand; the chunk words they leave are not looked at), or, for a
+//            resident baseline image, jda_ex_load_baseline (below).  lane = block:
+//            its 64 coefficients from its LDS slot (sixteen 8-byte reads: a slot is 8-byte aligned), times the raw quantisers of its component (the wavefront's copy
+//            in LDS: JDA_EX_QUANT_BYTES), the column pass into a workspace of 64 registers, the row pass, the range limit, eight 8-byte
+//            stores into the component's plane in the call's scratch.  Every multiply by an IDCT constant is a full 32-bit one: the
+//            arithmetic is defined modulo 2^32 for ANY int16 coefficients (a coefficient image's are the caller's), where a 24-bit
+//            multiplier would need a bound on them that nothing checks.  The dequantisation (int16 x uint16) is exact in 24 bits.
+//   colour   lane = four output pixels of a row = one 16-byte store (RGB8888; four bytes of a gray surface): the Y bytes and the chroma
+//            neighbours the upsampling formulas name, read from the planes in HBM with the indices clamped to the component's OWN extent
+//            -- the edge sample replicated, the MCU padding never read --, then the colour conversion.  A tile is a record of the same
+//            list as the planes stage's: count MCUs of an MCU row, its rows walked 64 quads at a time.
+// IO: ld128 / ld32u as the coefficient kernels'; ld32(base, byte offset), ld8(base, byte offset); st64 / st128 / st32 / st8(base, byte
+// offset, ..) -- global memory, the offsets below 2^32 (jda_exact_plan.h checks the planes, jda_fill_launch_desc the surface).
+#define JDA_EX_QUANT_BYTES 384u             // 3 x 64 uint16, natural order
+template <int MODE> struct jda_ex_layout {
+    enum { WAVE_BYTES = (JDA_EX_QUANT_BYTES + jda_lds_layout<MODE>::BASE_BYTES + 15) / 16 * 16,
+           HS = (MODE == JDA_MODE_420 || MODE == JDA_MODE_422) ? 2 : 1, VS = (MODE == JDA_MODE_420 || MODE == JDA_MODE_440) ? 2 : 1 };
+};
+
+// the wavefront's copy of the image's raw quantisers: 96 dwords
+template <class IO> JDA_HD void jda_ex_tables(IO &io, const jda_ex_desc *X, uint32_t lane, uint8_t *qt)
+{
+    jda_u32_alias *dst = (jda_u32_alias *)qt;
+    dst[lane] = io.ld32(&X->quant[0][0], 4u * lane);
+    if (lane < JDA_EX_QUANT_BYTES / 4u - 64u) dst[64u + lane] = io.ld32(&X->quant[0][0], 4u * (64u + lane));
+}
+
+// one pass of jidctint.c's jpeg_idct_islow over eight values, in place: DESCALE by SHIFT (CONST_BITS - PASS1_BITS = 11 for the columns,
+// CONST_BITS + PASS1_BITS + 3 = 18 for the rows); unsigned arithmetic where a sum may wrap, as the definition's 32-bit integers do
+template <int SHIFT> JDA_HD void jda_ex_idct8(int32_t &d0, int32_t &d1, int32_t &d2, int32_t &d3, int32_t &d4, int32_t &d5, int32_t &d6, int32_t &d7)
+{
+    typedef uint32_t U;
+    const U R = 1u << (SHIFT - 1);
+    const U z1e = ((U)d2 + (U)d6) * 4433u;
+    const U t2e = z1e - (U)d6 * 15137u, t3e = z1e + (U)d2 * 6270u;
+    const U t0e = ((U)d0 + (U)d4) << 13, t1e = ((U)d0 - (U)d4) << 13;
+    const U t10 = t0e + t3e, t13 = t0e - t3e, t11 = t1e + t2e, t12 = t1e - t2e;
+    const U z1 = (U)d7 + (U)d1, z2 = (U)d5 + (U)d3, z3 = (U)d7 + (U)d3, z4 = (U)d5 + (U)d1;
+    const U z5 = (z3 + z4) * 9633u;
+    const U m1 = 0u - z1 * 7373u, m2 = 0u - z2 * 20995u, m3 = z5 - z3 * 16069u, m4 = z5 - z4 * 3196u;
+    const U t0 = (U)d7 * 2446u + m1 + m3, t1 = (U)d5 * 16819u + m2 + m4, t2 = (U)d3 * 25172u + m2 + m3, t3 = (U)d1 * 12299u + m1 + m4;
+    d0 = (int32_t)(t10 + t3 + R) >> SHIFT; d7 = (int32_t)(t10 - t3 + R) >> SHIFT;
+    d1 = (int32_t)(t11 + t2 + R) >> SHIFT; d6 = (int32_t)(t11 - t2 + R) >> SHIFT;
+    d2 = (int32_t)(t12 + t1 + R) >> SHIFT; d5 = (int32_t)(t12 - t1 + R) >> SHIFT;
+    d3 = (int32_t)(t13 + t0 + R) >> SHIFT; d4 = (int32_t)(t13 - t0 + R) >> SHIFT;
+}
+// libjpeg's range limit behind the IDCT: the table's index is x & 1023 -- clamp(x + 128) for x in -512 .. 511, wrapping outside
+JDA_HD uint32_t jda_ex_limit(int32_t x)
+{
+    const uint32_t i = (uint32_t)x & 1023u;
+    return i < 128u ? i + 128u : i < 512u ? 255u : i < 896u ? 0u : i - 896u;
+}
+
+// lane = block of the tile, behind the load phase.  wl: the wavefront's slots, qt: its quantisers
+template <int MODE, class IO>
+JDA_HD void jda_ex_block(IO &io, const jda_ex_desc &X, const jda_strip &S, const jda_tile_ctx &C, uint32_t lane, const uint8_t *wl, const uint8_t *qt)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_lds_layout<MODE> L;
+    typedef jda_ex_layout<MODE> E;
+    if (lane >= C.count * (uint32_t)T::NBLK) return;
+    const uint32_t k = lane % (uint32_t)T::NBLK, m = lane / (uint32_t)T::NBLK;
+    const uint32_t c = k < (uint32_t)T::NLUMA ? 0u : k - (uint32_t)T::NLUMA + 1u;
+    if (c && X.luma_only) return;
+    const jda_u64_alias *src = (const jda_u64_alias *)(wl + L::COEF_OFF + lane * JDA_COEF_STRIDE);
+    const jda_u64_alias *qs = (const jda_u64_alias *)(qt + c * 128u);
+    int32_t ws[64];
+#pragma unroll
+    for (uint32_t i = 0; i < 16u; i++) {                     // four coefficients and their quantisers a step
+        const uint64_t v = src[i], q = qs[i];
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++)
+            ws[4u * i + j] = jda_mulc<true>((int32_t)(int16_t)(uint16_t)(v >> (16u * j)), (int32_t)(uint16_t)(q >> (16u * j)));
+    }
+#pragma unroll
+    for (uint32_t x = 0; x < 8u; x++)
+        jda_ex_idct8<11>(ws[x], ws[8 + x], ws[16 + x], ws[24 + x], ws[32 + x], ws[40 + x], ws[48 + x], ws[56 + x]);
+    uint32_t bx, by, pitch;
+    if (c == 0u) { bx = (S.mcu_x0 + m) * (uint32_t)E::HS + k % (uint32_t)E::HS; by = S.mcu_y * (uint32_t)E::VS + k / (uint32_t)E::HS; pitch = X.pitch_y; }
+    else { bx = S.mcu_x0 + m; by = S.mcu_y; pitch = X.pitch_c; }
+    uint8_t *plane = c == 0u ? X.plane[0] : c == 1u ? X.plane[1] : X.plane[2];
+    uint32_t off = by * 8u * pitch + bx * 8u;
+#pragma unroll
+    for (uint32_t y = 0; y < 8u; y++) {
+        jda_ex_idct8<18>(ws[8 * y], ws[8 * y + 1], ws[8 * y + 2], ws[8 * y + 3], ws[8 * y + 4], ws[8 * y + 5], ws[8 * y + 6], ws[8 * y + 7]);
+        const uint32_t lo = jda_ex_limit(ws[8 * y]) | (jda_ex_limit(ws[8 * y + 1]) << 8) | (jda_ex_limit(ws[8 * y + 2]) << 16) | (jda_ex_limit(ws[8 * y + 3]) << 24);
+        const uint32_t hi = jda_ex_limit(ws[8 * y + 4]) | (jda_ex_limit(ws[8 * y + 5]) << 8) | (jda_ex_limit(ws[8 * y + 6]) << 16) | (jda_ex_limit(ws[8 * y + 7]) << 24);
+        io.st64(plane, off, lo, hi);
+        off += pitch;
+    }
+}
+
+// jdcolor.c, SCALEBITS 16: the pixel as a dword, R in the lowest byte, A = 0xFF
+JDA_HD uint32_t jda_ex_rgba(uint32_t y, uint32_t cbs, uint32_t crs)
+{
+    const int32_t cb = (int32_t)cbs - 128, cr = (int32_t)crs - 128, Y = (int32_t)y;
+    int32_t r = Y + ((91881 * cr + 32768) >> 16);
+    int32_t g = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
+    int32_t b = Y + ((116130 * cb + 32768) >> 16);
+    r = r < 0 ? 0 : r > 255 ? 255 : r; g = g < 0 ? 0 : g > 255 ? 255 : g; b = b < 0 ? 0 : b > 255 ? 255 : b;
+    return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16) | 0xff000000u;
+}
+// the four upsampled samples of a chroma plane under the output pixels x0 .. x0 + 3 (x0 a multiple of 4) of output row y
+template <int MODE, class IO> JDA_HD void jda_ex_chroma4(IO &io, const jda_ex_desc &X, const uint8_t *plane, uint32_t x0, uint32_t y, uint32_t *out)
+{
+    typedef jda_ex_layout<MODE> E;
+    const uint32_t j = E::VS == 2 ? y >> 1 : y;
+    // the second row of a vertical pair: the one above for an even output row, the one below for an odd one, inside the component's extent
+    const uint32_t jn = E::VS == 2 ? ((y & 1u) ? (j + 1u < X.ch ? j + 1u : j) : (j ? j - 1u : 0u)) : j;
+    if (E::HS == 1) {
+        const uint32_t a = io.ld32(plane, j * X.pitch_c + x0);
+        if (E::VS == 1) { for (uint32_t k = 0; k < 4u; k++) out[k] = (a >> (8u * k)) & 255u; return; }
+        const uint32_t b = io.ld32(plane, jn * X.pitch_c + x0), bias = 1u + (y & 1u);
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) out[k] = (3u * ((a >> (8u * k)) & 255u) + ((b >> (8u * k)) & 255u) + bias) >> 2;
+        return;
+    }
+    const uint32_t i0 = x0 >> 1, last = X.cw - 1u;
+    uint32_t t[4];                                           // s[i0 - 1 .. i0 + 2], clamped; for 4:2:0: 3 s[j] + s[jn]
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        uint32_t i = i0 + k;
+        i = i ? i - 1u : 0u;
+        i = i < last ? i : last;
+        const uint32_t a = io.ld8(plane, j * X.pitch_c + i);
+        t[k] = E::VS == 2 ? 3u * a + io.ld8(plane, jn * X.pitch_c + i) : a;
+    }
+    if (E::VS == 2) {
+        out[0] = (3u * t[1] + t[0] + 8u) >> 4; out[1] = (3u * t[1] + t[2] + 7u) >> 4;
+        out[2] = (3u * t[2] + t[1] + 8u) >> 4; out[3] = (3u * t[2] + t[3] + 7u) >> 4;
+    } else {
+        out[0] = (3u * t[1] + t[0] + 1u) >> 2; out[1] = (3u * t[1] + t[2] + 2u) >> 2;
+        out[2] = (3u * t[2] + t[1] + 1u) >> 2; out[3] = (3u * t[2] + t[3] + 2u) >> 2;
+    }
+}
+// lane = the output pixels x0 .. x0 + 3 of row y: nothing outside out_w x out_rows is written
+template <int MODE, class IO> JDA_HD void jda_ex_quad(IO &io, const jda_ex_desc &X, uint32_t x0, uint32_t y)
+{
+    if (y >= X.out_rows || x0 >= X.out_w) return;
+    const uint32_t n = X.out_w - x0 < 4u ? X.out_w - x0 : 4u;
+    const uint32_t yw = io.ld32(X.plane[0], y * X.pitch_y + x0);
+    if (X.gray_out) {
+        const uint32_t o = y * X.out_pitch + x0;
+        if (n == 4u) io.st32(X.out, o, yw);
+        else for (uint32_t k = 0; k < n; k++) io.st8(X.out, o + k, (yw >> (8u * k)) & 255u);
+        return;
+    }
+    uint32_t cb[4] = { 128u, 128u, 128u, 128u }, cr[4] = { 128u, 128u, 128u, 128u }, px[4];
+    if (MODE != JDA_MODE_GRAY) {
+        jda_ex_chroma4<MODE>(io, X, X.plane[1], x0, y, cb);
+        jda_ex_chroma4<MODE>(io, X, X.plane[2], x0, y, cr);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) px[k] = jda_ex_rgba((yw >> (8u * k)) & 255u, cb[k], cr[k]);
+    const uint32_t o = y * X.out_pitch + x0 * 4u;
+    if (n == 4u) io.st128(X.out, o, px);
+    else for (uint32_t k = 0; k < n; k++) io.st32(X.out, o + 4u * k, px[k]);
+}
+// a wavefront = a tile record: count MCUs of MCU row mcu_y from MCU mcu_x0
+template <int MODE, class IO> JDA_HD void jda_ex_colour_tile(IO &io, const jda_ex_desc &X, const jda_strip &S, uint32_t lane)
+{
+    typedef jda_mode_traits<MODE> T;
+    const uint32_t quads = (uint32_t)S.count * ((uint32_t)T::MCU_W / 4u), items = quads * (uint32_t)T::MCU_H;
+    const uint32_t px0 = (uint32_t)S.mcu_x0 * (uint32_t)T::MCU_W, py0 = (uint32_t)S.mcu_y * (uint32_t)T::MCU_H;
+    if (py0 >= X.out_rows || px0 >= X.out_w) return;         // (wave-uniform)
+    for (uint32_t it = lane; it < items; it += 64u) {
+        const uint32_t r = it / quads, q = it - r * quads;
+        jda_ex_quad<MODE>(io, X, px0 + 4u * q, py0 + r);
+    }
+}
+
+// baseline load phase: a resident BASELINE image as the third source of the planes stage, beside jda_ct_load and jda_cs_zero / _scatter.
+// lane = block of the tile: T.81's reader -- a 32-bit peek of the scan at any bit position from the index entry's own, the AC LUT of the
+// image's table blob (the layout jda_rc_extract_block reads), EXTEND of WHOLE magnitudes, never the reference's truncated reads -- into the
+// lane's LDS slot in NATURAL order (the blob's cZigZag2), the block's DC value from the index.  The slot then holds what the dense load
+// phase would have put there for the same coefficients; no coefficient touches HBM.  The reader is written out here a third time (after
+// jda_rc_extract_block and its _xf twin): those two store zig-zag order, clamp to the encoder's range and count its code bits as they go,
+// and they are kernels of their own features, which this one leaves as they stand.
+// what a lane needs of its block's jda_ex_src, field by field (no array: a copy of the whole record, indexed by component, would live in scratch)
+struct jda_ex_walk { const uint8_t *scan, *tables; const uint32_t *blk_index; const int16_t *blk_dc; uint32_t scan_len, ac_ids, bpm, nluma; };
+template <class IO> JDA_HD jda_ex_walk jda_ex_walk_of(const jda_ex_src *J, IO &io)
+{
+    jda_ex_walk W;
+    W.scan = (const uint8_t *)io.ldptr(&J->S.scan); W.tables = (const uint8_t *)io.ldptr(&J->S.tables);
+    W.blk_index = (const uint32_t *)io.ldptr(&J->S.blk_index); W.blk_dc = (const int16_t *)io.ldptr(&J->S.blk_dc);
+    W.scan_len = io.ld32(&J->S.scan_len); W.bpm = io.ld32(&J->bpm); W.nluma = io.ld32(&J->nluma);
+    W.ac_ids = (io.ld32(&J->S.ac_id[0]) & 1u) | ((io.ld32(&J->S.ac_id[1]) & 1u) << 1) | ((io.ld32(&J->S.ac_id[2]) & 1u) << 2);
+    return W;
+}
+template <class IO> JDA_HD void jda_ex_extract_block(const jda_ex_walk &W, uint32_t s, uint8_t *slot, IO &io)
+{
+    const uint32_t k = s % W.bpm, c = k < W.nluma ? 0u : 1u + k - W.nluma;
+    int16_t *coef = (int16_t *)slot;
+    jda_u64_alias *z8 = (jda_u64_alias *)slot;
+#pragma unroll
+    for (int i = 0; i < 16; i++) z8[i] = 0;
+    const uint32_t ix = io.ld32(W.blk_index + s);
+    const uint32_t dcw = io.ld32((const uint32_t *)W.blk_dc + (s >> 1));
+    coef[0] = (int16_t)((s & 1u) ? dcw >> 16 : dcw & 0xffffu);
+    uint32_t p = (ix >> JDA_INDEX_OFF_BITS) * 8u + (ix & (JDA_INDEX_TRUNC - 1u));
+    const uint32_t *lut = (const uint32_t *)(W.tables + JDA_TB_AC + ((W.ac_ids >> c) & 1u) * 4096u);
+    // (the scan section is scan_len + JDA_SCAN_PAD bytes: both dwords of a peek stay inside whatever an entry says, as jda_rc_peek's)
+    const uint32_t a_max = (W.scan_len + JDA_SCAN_PAD - 8u) >> 2;
+    uint32_t z = 1;
+    while (z < 64u) {
+        uint32_t a = p >> 5;
+        a = a < a_max ? a : a_max;
+        const uint32_t d0 = __builtin_bswap32(io.ld32((const uint32_t *)W.scan + a)), d1 = __builtin_bswap32(io.ld32((const uint32_t *)W.scan + a + 1u)), sh = p & 31u;
+        const uint32_t w = sh ? (d0 << sh) | (d1 >> (32u - sh)) : d0;
+        const uint32_t key = w >= 0xfc000000u ? 1024u + ((w >> 16) & 0x3ffu) : w >> 22;
+        const uint32_t pair = io.ld32(lut + (key >> 1)), raw = (key & 1u) ? pair >> 16 : pair & 0xffffu;
+        const uint32_t len = raw >> 8, rs = raw & 0xffu, sz = rs & 15u;
+        if (len == 0u || rs == 0u) break;                                // no such code, or EOB
+        z += rs >> 4;
+        if (sz && z < 64u) {
+            const uint32_t m = w << len, v = m >> (32u - sz);
+            const int32_t val = (m & 0x80000000u) ? (int32_t)v : (int32_t)v - (int32_t)((1u << sz) - 1u);       // T.81 F.2.2.1 EXTEND
+            coef[io.ld8(W.tables, JDA_TB_ZIGZAG + z) & 63u] = (int16_t)val;      // (the blob's cZigZag2: zig-zag position -> natural index)
+        }
+        p += len + sz;
+        z++;
+    }
+}
+// the load phase: lane = block of the tile; src: the image's record
+template <int MODE, class IO> JDA_HD void jda_ex_load_baseline(IO &io, const jda_ex_src *src, const jda_tile_ctx &C, uint32_t lane, uint8_t *wl)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_lds_layout<MODE> L;
+    if (lane >= C.count * (uint32_t)T::NBLK) return;
+    jda_ex_extract_block(jda_ex_walk_of(src, io), C.first_block + lane, wl + L::COEF_OFF + lane * JDA_COEF_STRIDE, io);
+}
+
 #endif // JDA_DEVICE_CORE_H

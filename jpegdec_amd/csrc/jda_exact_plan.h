@@ -1,0 +1,74 @@
+// jda_exact_plan.h -- the host side of the libjpeg-exact decode (jda_exact_decode_surfaces / _planes): what is refused,
+// the component planes of an image in the call's scratch, and its record for the kernels.  Host work only, no HIP: the runtime and
+// tests/hostsim/exact_sim.cpp share it.
+#ifndef JDA_EXACT_PLAN_H
+#define JDA_EXACT_PLAN_H
+
+#include <string.h>
+
+#include "jda_device_core.h"
+#include "jda_plan.h"
+
+// What the exact road takes: a gray or YCbCr file as libjpeg would read it (no Adobe APP14 segment: its transform flag changes how the
+// components are read), an RGB8888 or 8-bit gray surface.  baseline_image: the source is a resident baseline image, whose pre-scan
+// validated n_mcus_ok MCUs -- all of them, or the reader would walk index entries nothing stands behind (JDA_DECODE_ERROR, the recode's
+// rule) -- and which is no progressive file's (its first scan only: the whole file comes as a coefficient image).
+inline int jda_exact_check(const jda_image_info &I, int adobe, int pixel_type, int baseline_image, uint32_t n_mcus_ok)
+{
+    if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
+    if ((I.ncomp != 1 && I.ncomp != 3) || adobe) return JDA_UNSUPPORTED_FEATURE;
+    if (I.width <= 0 || I.height <= 0 || I.mcus_x <= 0 || I.mcus_y <= 0) return JDA_INVALID_PARAMETER;
+    if (baseline_image && I.jpeg_type != 0) return JDA_UNSUPPORTED_FEATURE;
+    if (baseline_image && n_mcus_ok < (uint32_t)I.mcus_x * (uint32_t)I.mcus_y) return JDA_DECODE_ERROR;
+    return JDA_SUCCESS;
+}
+
+// The planes of one image: Y over the whole MCU grid, Cb and Cr (a colour file decoded in colour) over theirs, the rows a multiple of
+// 16 bytes apart, each plane's start a multiple of 256 from the image's.  cw x ch: a chroma component's own extent.
+struct jda_exact_geo {
+    uint32_t hs, vs, pitch_y, pitch_c, rows_y, rows_c, cw, ch;
+    size_t off[3], bytes;
+};
+inline int jda_exact_geometry(const jda_image_info &I, bool luma_only, jda_exact_geo *G)
+{
+    const int mode = jda_mode_of(I);
+    memset(G, 0, sizeof(*G));
+    G->hs = (mode == JDA_MODE_420 || mode == JDA_MODE_422) ? 2u : 1u;
+    G->vs = (mode == JDA_MODE_420 || mode == JDA_MODE_440) ? 2u : 1u;
+    G->pitch_y = ((uint32_t)I.mcus_x * 8u * G->hs + 15u) & ~15u;
+    G->rows_y = (uint32_t)I.mcus_y * 8u * G->vs;
+    G->cw = ((uint32_t)I.width + G->hs - 1u) / G->hs;
+    G->ch = ((uint32_t)I.height + G->vs - 1u) / G->vs;
+    // the kernels address a plane with 32-bit byte offsets
+    if ((uint64_t)G->pitch_y * G->rows_y >= (1ull << 32)) return JDA_UNSUPPORTED_FEATURE;
+    size_t at = ((size_t)G->pitch_y * G->rows_y + 255u) & ~(size_t)255u;
+    if (mode != JDA_MODE_GRAY && !luma_only) {
+        G->pitch_c = ((uint32_t)I.mcus_x * 8u + 15u) & ~15u;
+        G->rows_c = (uint32_t)I.mcus_y * 8u;
+        for (int c = 1; c < 3; c++) { G->off[c] = at; at += ((size_t)G->pitch_c * G->rows_c + 255u) & ~(size_t)255u; }
+    }
+    G->bytes = at;
+    return JDA_SUCCESS;
+}
+
+// The image's record.  quant_zz: the DQT entries of Y, Cb, Cr as the file lists them (zig-zag order); scratch: where the image's planes
+// begin (device); out == NULL: no surface (jda_exact_decode_planes runs the first stage only).
+inline void jda_exact_fill(jda_ex_desc &X, const jda_image_info &I, const uint16_t (*quant_zz)[64], const jda_exact_geo &G, uint8_t *scratch, const jda_output *out,
+                           int pixel_type, bool luma_only)
+{
+    memset(&X, 0, sizeof(X));
+    for (int c = 0; c < 3; c++) X.plane[c] = scratch + G.off[c];
+    X.pitch_y = G.pitch_y; X.pitch_c = G.pitch_c;
+    X.w = (uint32_t)I.width; X.h = (uint32_t)I.height; X.cw = G.cw; X.ch = G.ch;
+    X.luma_only = luma_only ? 1u : 0u;
+    X.gray_out = pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1u : 0u;
+    if (out) {
+        X.out = (uint8_t *)out->pixels; X.out_pitch = (uint32_t)out->pitch_bytes;
+        X.out_w = out->width_px < I.width ? (uint32_t)(out->width_px < 0 ? 0 : out->width_px) : (uint32_t)I.width;
+        X.out_rows = out->rows < I.height ? (uint32_t)(out->rows < 0 ? 0 : out->rows) : (uint32_t)I.height;
+    }
+    for (int c = 0; c < 3; c++)
+        for (uint32_t z = 0; z < 64u; z++) X.quant[c][jda_en_zigzag(z)] = quant_zz[c][z];
+}
+
+#endif

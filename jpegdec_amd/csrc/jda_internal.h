@@ -281,6 +281,26 @@ struct jda_rc_xf { uint32_t bits, scx, x0, y0, rw, rh, pad_[2]; };
 #define JDA_RC_MIN_DC (-1024)
 #define JDA_RC_MAX_DC 1023
 
+// One image of a libjpeg-exact decode call (jda_ex_* in jda_device_core.h; device pointers), beside its jda_dev_desc in the
+// call's blob.  plane[c]: the 8-bit samples of Y, Cb, Cr in the call's scratch, each padded to the MCU grid, the rows pitch_y / pitch_c
+// bytes apart (multiples of 16); w x h: the image, cw x ch: a chroma component's own extent (ceil(w / hs) x ceil(h / vs)).  out: the
+// surface, of which out_w x out_rows pixels are written (the clip to the image included); gray_out: it is 8-bit gray (the Y plane), else
+// RGB8888.  luma_only: the chroma blocks are not decoded (a gray surface of a colour file).  quant: the RAW DQT entries of Y, Cb, Cr in
+// NATURAL order -- not the prescaled quantisers of the coefficient image's own blob.
+struct jda_ex_desc {
+    uint8_t *plane[3];
+    uint8_t *out;
+    uint32_t pitch_y, pitch_c, w, h, cw, ch, out_pitch, out_w, out_rows, gray_out, luma_only, pad_;
+    uint16_t quant[3][64];
+};
+// A resident baseline image as the source of an exact call, beside its jda_dev_desc and jda_ex_desc in the call's blob (a record an image
+// of the call; zeros for a coefficient image): what the planes stage's baseline load phase reads -- S as a recode source's; bpm blocks an
+// MCU, the first nluma of them luma.
+struct jda_ex_src {
+    jda_rc_src S;
+    uint32_t bpm, nluma, pad_[2];
+};
+
 // Progressive encode (jda_pe_* in jda_device_core.h, DESIGN.md 5.13 rules 10 to 14).  A SEGMENT is one scan of one job: its units -- a
 // (scan, block) pair each -- are [unit0, unit0 + n_units) of the call's flat unit list, the job's scans in file order.  comp: the scan's
 // component (JDA_PE_ALL: every block of the MCU grid in the job's block order, a DC scan); wbc: the blocks in a row of the component's own

@@ -2754,6 +2754,119 @@ extern "C" hipError_t jda_launch_sparse_tiles(int mode, const jda_dev_desc *desc
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// jda_exact_planes<MODE, SOURCE> / jda_exact_colour<MODE>: the libjpeg-exact decode (jda_ex_* in jda_device_core.h).
+// planes: a wavefront = a tile of the launch list, four to a workgroup, each with its own share of the LDS (the tile's slots and its
+// image's raw quantisers), no workgroup barrier; the load phase is jda_coef_tiles' (SOURCE 0: a dense coefficient image), jda_sparse_tiles'
+// (1: a sparse one) or the T.81 reader over a resident baseline image (2: jda_ex_load_baseline).
+// colour: a wavefront = a record of the same kind of list; it reads the planes the first kernel wrote (the launches are on one stream).
+struct jda_exact_io {
+    __device__ __forceinline__ void ld128(const uint8_t *base, uint32_t i, uint32_t *v) const
+    {
+        const uint4 q = ((const uint4 JDA_GLOBAL *)JDA_G(const uint8_t, base))[i];
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+    __device__ __forceinline__ uint32_t ld32u(const uint8_t *base, uint32_t i) const { return jda_uni32(((const uint32_t JDA_GLOBAL *)JDA_G(const uint8_t, base))[i]); }
+    __device__ __forceinline__ uint32_t ld32(const void *base, uint32_t off) const { return *(const uint32_t JDA_GLOBAL *)(JDA_G(const uint8_t, base) + off); }
+    __device__ __forceinline__ uint32_t ld32(const uint32_t *p) const { return *JDA_G(const uint32_t, p); }
+    template <class P> __device__ __forceinline__ const void *ldptr(P const *p) const { return (const void *)*JDA_G(P const, p); }
+    __device__ __forceinline__ uint32_t ld8(const uint8_t *base, uint32_t off) const { return JDA_G(const uint8_t, base)[off]; }
+    __device__ __forceinline__ void st64(uint8_t *base, uint32_t off, uint32_t lo, uint32_t hi) const { *(uint2 JDA_GLOBAL *)(JDA_G(uint8_t, base) + off) = make_uint2(lo, hi); }
+    __device__ __forceinline__ void st128(uint8_t *base, uint32_t off, const uint32_t *w) const { *(uint4 JDA_GLOBAL *)(JDA_G(uint8_t, base) + off) = make_uint4(w[0], w[1], w[2], w[3]); }
+    __device__ __forceinline__ void st32(uint8_t *base, uint32_t off, uint32_t v) const { *(uint32_t JDA_GLOBAL *)(JDA_G(uint8_t, base) + off) = v; }
+    __device__ __forceinline__ void st8(uint8_t *base, uint32_t off, uint32_t v) const { JDA_G(uint8_t, base)[off] = (uint8_t)v; }
+};
+// the record of an image, wave-uniform (quant stays in memory: jda_ex_tables copies it)
+__device__ __forceinline__ void jda_ex_desc_uniform(jda_ex_desc &L, const jda_ex_desc *p)
+{
+    const jda_ex_desc JDA_GLOBAL *g = JDA_G(const jda_ex_desc, p);
+    L.plane[0] = jda_uni_ptr(g->plane[0]); L.plane[1] = jda_uni_ptr(g->plane[1]); L.plane[2] = jda_uni_ptr(g->plane[2]); L.out = jda_uni_ptr(g->out);
+    L.pitch_y = jda_uni32(g->pitch_y); L.pitch_c = jda_uni32(g->pitch_c); L.w = jda_uni32(g->w); L.h = jda_uni32(g->h);
+    L.cw = jda_uni32(g->cw); L.ch = jda_uni32(g->ch); L.out_pitch = jda_uni32(g->out_pitch); L.out_w = jda_uni32(g->out_w);
+    L.out_rows = jda_uni32(g->out_rows); L.gray_out = jda_uni32(g->gray_out); L.luma_only = jda_uni32(g->luma_only);
+}
+template <int MODE, int SOURCE>
+__global__ __launch_bounds__(64 * JDA_CT_WAVES)
+void jda_exact_planes(const jda_dev_desc *__restrict__ descs, const jda_ex_desc *__restrict__ ex, const jda_ex_src *__restrict__ src, const jda_strip *__restrict__ tiles,
+                      uint32_t n_tiles)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    typedef jda_mode_traits<MODE> T;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_CT_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;                                              // a padding record of the list
+    uint8_t *qt = lds + wave * (uint32_t)jda_ex_layout<MODE>::WAVE_BYTES;
+    uint8_t *wl = qt + JDA_EX_QUANT_BYTES;
+    const jda_dev_desc D = jda_desc_uniform<0, MODE>(descs + S.image);
+    jda_ex_desc X;
+    jda_ex_desc_uniform(X, ex + S.image);
+    jda_tile_ctx C;
+    C.first_mcu = S.mcu_y * D.mcus_x + S.mcu_x0;
+    C.count = S.count;
+    C.first_block = C.first_mcu * (uint32_t)T::NBLK;
+    C.win_lo = C.win_len = C.win_need = 0;
+    jda_exact_io io;
+    jda_ex_tables(io, ex + S.image, lane, qt);
+    if (SOURCE == 2) {
+        jda_ex_load_baseline<MODE>(io, src + S.image, C, lane, wl);
+    } else if (SOURCE == 1) {
+        uint32_t e0, e1;
+        jda_cs_range<MODE>(io, D, C, &e0, &e1);
+        jda_cs_zero<MODE>(C, lane, wl);
+        JDA_WAVE_SYNC();                                                   // (the zeros lie in LDS before the first entry lands)
+        jda_cs_scatter<MODE>(io, D, C, lane, e0, e1, wl);
+    } else {
+        jda_ct_load<MODE>(io, D, C, lane, wl);
+    }
+    JDA_WAVE_SYNC();
+    jda_ex_block<MODE>(io, X, S, C, lane, wl, qt);
+}
+template <int MODE>
+__global__ __launch_bounds__(64 * JDA_CT_WAVES)
+void jda_exact_colour(const jda_ex_desc *__restrict__ ex, const jda_strip *__restrict__ tiles, uint32_t n_tiles)
+{
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_CT_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;
+    jda_ex_desc X;
+    jda_ex_desc_uniform(X, ex + S.image);
+    jda_exact_io io;
+    jda_ex_colour_tile<MODE>(io, X, S, lane);
+}
+template <int MODE>
+static hipError_t launch_exact(int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    const uint32_t lds_bytes = JDA_CT_WAVES * (uint32_t)jda_ex_layout<MODE>::WAVE_BYTES;
+    static_assert(JDA_CT_WAVES * jda_ex_layout<MODE>::WAVE_BYTES <= 64 * 1024, "a workgroup's LDS stays under the default limit");
+    const dim3 grid((n_tiles + JDA_CT_WAVES - 1u) / JDA_CT_WAVES), block(64u * JDA_CT_WAVES);
+    const auto dense = jda_exact_planes<MODE, 0>, sparse = jda_exact_planes<MODE, 1>, baseline = jda_exact_planes<MODE, 2>;
+    if (stage == 0) JDA_LAUNCH(dense, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else if (stage == 1) JDA_LAUNCH(sparse, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else if (stage == 2) JDA_LAUNCH(baseline, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else JDA_LAUNCH(jda_exact_colour<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
+    return hipGetLastError();
+}
+// stage 0 / 1 / 2: jda_exact_planes over tiles of dense coefficient images / sparse ones / resident baseline images of ONE mode (descs as
+// jda_launch_coef_tiles / _sparse_tiles; src: a record an image, read for baseline images); stage 3: jda_exact_colour over tile records of that mode
+extern "C" hipError_t jda_launch_exact(int mode, int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
+                                       hipStream_t stream)
+{
+    if (n_tiles == 0) return hipSuccess;
+    if (stage < 0 || stage > 3) return hipErrorInvalidValue;
+    switch (mode) {
+    case JDA_MODE_GRAY: return launch_exact<JDA_MODE_GRAY>(stage, descs, ex, src, tiles, n_tiles, stream);
+    case JDA_MODE_444: return launch_exact<JDA_MODE_444>(stage, descs, ex, src, tiles, n_tiles, stream);
+    case JDA_MODE_420: return launch_exact<JDA_MODE_420>(stage, descs, ex, src, tiles, n_tiles, stream);
+    case JDA_MODE_422: return launch_exact<JDA_MODE_422>(stage, descs, ex, src, tiles, n_tiles, stream);
+    case JDA_MODE_440: return launch_exact<JDA_MODE_440>(stage, descs, ex, src, tiles, n_tiles, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 extern "C" hipError_t jda_internal_set_wgtrace(unsigned long long *dev_buf)
 {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_jda_wgtrace), &dev_buf, sizeof(dev_buf));

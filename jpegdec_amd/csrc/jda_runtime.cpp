@@ -27,6 +27,7 @@
 #include "jda_resize_plan.h"
 #include "jda_encode_plan.h"
 #include "jda_recode_plan.h"
+#include "jda_exact_plan.h"
 #include "jda_prescan_plan.h"
 
 extern "C" uint32_t jda_image_fast_mul(const jda_image *img);
@@ -2144,6 +2145,200 @@ int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
         }
     }
     if (dfile) jda_pool_free(ctx, dfile);
+    if (dimg) jda_dev_image_free(ctx, dimg);
+    if (dcoef) jda_dev_coef_free(ctx, dcoef);
+    if (img) jda_image_free(img);
+    if (cimg) jda_coef_image_free(cimg);
+    return rc;
+}
+
+// ---- libjpeg-exact decode (jda_exact_* in jda_kernels.hip, jda_ex_* in jda_device_core.h; checks, planes and records: jda_exact_plan.h;
+// DESIGN.md 5.17).  One pool block a call: the blob (descs | records | baseline sources, one of each an image | tile lists) and behind it
+// the scratch -- every planned image's component planes.  The lists of a layout lie dense, sparse, baseline, back to back, so that the
+// colour stage takes all three in one launch.
+struct exact_image { int kind; jda_image_info info; uint16_t quant[3][64]; jda_exact_geo G; size_t plane_at; bool luma_only; };
+// stage_ms (the measuring hook's, else NULL): [0] the jda_exact_planes launches, [1] the jda_exact_colour launches
+static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const jda_output *planes,
+                      int32_t *status, float *stage_ms = NULL)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    if (!src || !status || (!outputs && !planes)) return JDA_INVALID_PARAMETER;
+    for (int i = 0; i < n; i++) if ((src[i].image != NULL) == (src[i].coef != NULL)) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    std::vector<jda_dev_desc> descs((size_t)n);
+    std::vector<jda_ex_desc> ex((size_t)n);
+    std::vector<jda_ex_src> esrc((size_t)n);
+    std::vector<exact_image> im((size_t)n);
+    std::vector<jda_strip> strips[JDA_N_MODES][3];
+    size_t scratch = 0;
+    int planned = 0;
+    for (int i = 0; i < n; i++) {
+        exact_image &M = im[(size_t)i];
+        jda_dev_desc &D = descs[(size_t)i];
+        memset(&D, 0, sizeof(D)); memset(&ex[(size_t)i], 0, sizeof(jda_ex_desc)); memset(&esrc[(size_t)i], 0, sizeof(jda_ex_src));
+        int adobe = 0;
+        uint32_t n_ok = 0;
+        if (src[i].image) {
+            const jda_dev_image *d = src[i].image;
+            M.kind = 2; M.info = d->info; adobe = d->adobe; n_ok = d->n_mcus_ok;
+            for (int c = 0; c < 3; c++) memcpy(M.quant[c], d->quant_zz[d->q_id[c] & 3], sizeof(M.quant[c]));
+        } else {
+            const jda_dev_coef *d = src[i].coef;
+            M.kind = d->form == JDA_COEF_SPARSE ? 1 : 0; M.info = d->info; adobe = d->adobe;
+            memcpy(M.quant, d->raw_quant, sizeof(M.quant));
+        }
+        const jda_image_info &I = M.info;
+        const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
+        int rc = jda_exact_check(I, adobe, pt, M.kind == 2, n_ok);
+        M.luma_only = outputs && pt == JDA_EIGHT_BIT_GRAYSCALE && I.ncomp == 3;
+        if (rc == JDA_SUCCESS) rc = jda_exact_geometry(I, M.luma_only, &M.G);
+        if (rc == JDA_SUCCESS && outputs) {
+            jda_image_info B = I;
+            B.jpeg_type = 0;
+            const uint8_t none[3] = { 0, 0, 0 };
+            rc = jda_fill_launch_desc(D, B, none, none, none, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, outputs[i], pt, 0, NULL);
+        } else if (rc == JDA_SUCCESS) {
+            D.mode = (uint8_t)jda_mode_of(I); D.ncomp = (uint8_t)I.ncomp; D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
+            for (int c = 0; c < (I.ncomp == 3 ? 3 : 1) && rc == JDA_SUCCESS; c++) {
+                const jda_output &P = planes[3 * i + c];
+                const int32_t ew = c ? (int32_t)M.G.cw : I.width;
+                if (!P.pixels || P.width_px < 0 || P.rows < 0 || P.pitch_bytes < (P.width_px < ew ? P.width_px : ew)) rc = JDA_INVALID_PARAMETER;
+            }
+        }
+        if (rc != JDA_SUCCESS) { status[i] = rc; memset(&D, 0, sizeof(D)); M.kind = -1; continue; }
+        status[i] = JDA_SUCCESS;
+        planned++;
+        M.plane_at = scratch; scratch += M.G.bytes;
+        if (M.kind == 2) {
+            jda_ex_src &J = esrc[(size_t)i];
+            const jda_dev_image *d = src[i].image;
+            J.S.scan = d->base + d->off_scan; J.S.blk_index = (const uint32_t *)(d->base + d->off_index); J.S.blk_dc = (const int16_t *)(d->base + d->off_dc);
+            J.S.tables = d->base + d->off_tables; J.S.scan_len = d->scan_len; J.S.kind = JDA_RC_IMAGE;
+            for (int c = 0; c < 3; c++) J.S.ac_id[c] = d->ac_id[c];
+            J.bpm = (uint32_t)I.blocks_per_mcu; J.nluma = I.ncomp == 3 ? J.bpm - 2u : 1u;
+        } else {
+            D.tables = src[i].coef->base; D.scan = src[i].coef->base + src[i].coef->off_entries;
+        }
+        jda_append_strips(strips[D.mode][M.kind], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+    }
+    if (!planned) return JDA_SUCCESS;
+    const size_t o_ex = align16(descs.size() * sizeof(jda_dev_desc)), o_src = o_ex + align16(ex.size() * sizeof(jda_ex_desc));
+    size_t bytes = o_src + align16(esrc.size() * sizeof(jda_ex_src));
+    size_t off[JDA_N_MODES][3];
+    for (int m = 0; m < JDA_N_MODES; m++)
+        for (int f = 0; f < 3; f++) { off[m][f] = bytes; bytes += strips[m][f].size() * sizeof(jda_strip); }
+    const size_t o_scratch = (bytes + 255u) & ~(size_t)255u;
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, o_scratch + scratch);
+    if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(exact decode)"); return JDA_ERROR_MEMORY; }
+    for (int i = 0; i < n; i++) {
+        const exact_image &M = im[(size_t)i];
+        if (M.kind < 0) continue;
+        const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
+        jda_exact_fill(ex[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt, M.luma_only);
+    }
+    std::vector<uint8_t> blob(bytes, 0);
+    memcpy(blob.data(), descs.data(), descs.size() * sizeof(jda_dev_desc));
+    memcpy(blob.data() + o_ex, ex.data(), ex.size() * sizeof(jda_ex_desc));
+    memcpy(blob.data() + o_src, esrc.data(), esrc.size() * sizeof(jda_ex_src));
+    for (int m = 0; m < JDA_N_MODES; m++)
+        for (int f = 0; f < 3; f++)
+            if (!strips[m][f].empty()) memcpy(blob.data() + off[m][f], strips[m][f].data(), strips[m][f].size() * sizeof(jda_strip));
+    e = hipMemcpyAsync(blk, blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    const jda_dev_desc *d_descs = (const jda_dev_desc *)blk;
+    const jda_ex_desc *d_ex = (const jda_ex_desc *)(blk + o_ex);
+    const jda_ex_src *d_src = (const jda_ex_src *)(blk + o_src);
+    hipEvent_t ev[3] = { NULL, NULL, NULL };
+    for (int k = 0; k < 3 && stage_ms && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
+    if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess; m++)
+        for (int f = 0; f < 3 && e == hipSuccess; f++)
+            e = jda_launch_exact(m, f, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][f]), (uint32_t)strips[m][f].size(), ctx->stream);
+    if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs; m++)
+        e = jda_launch_exact(m, 3, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][0]),
+                             (uint32_t)(strips[m][0].size() + strips[m][1].size() + strips[m][2].size()), ctx->stream);
+    if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
+    for (int i = 0; i < n && e == hipSuccess && planes; i++) {
+        const exact_image &M = im[(size_t)i];
+        if (M.kind < 0) continue;
+        for (int c = 0; c < (M.info.ncomp == 3 ? 3 : 1) && e == hipSuccess; c++) {
+            const jda_output &P = planes[3 * i + c];
+            const int32_t ew = c ? (int32_t)M.G.cw : M.info.width, eh = c ? (int32_t)M.G.ch : M.info.height;
+            const size_t cw = (size_t)(P.width_px < ew ? P.width_px : ew), crows = (size_t)(P.rows < eh ? P.rows : eh);
+            if (cw && crows)
+                e = hipMemcpy2DAsync(P.pixels, (size_t)P.pitch_bytes, blk + o_scratch + M.plane_at + M.G.off[c], c ? M.G.pitch_c : M.G.pitch_y, cw, crows,
+                                     hipMemcpyDeviceToDevice, ctx->stream);
+        }
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);     // (the blob leaves pageable memory that goes away with this frame)
+    for (int k = 0; k < 2 && stage_ms && e == hipSuccess && es == hipSuccess; k++) e = hipEventElapsedTime(&stage_ms[k], ev[k], ev[k + 1]);
+    for (int k = 0; k < 3; k++) if (ev[k]) (void)hipEventDestroy(ev[k]);
+    jda_pool_free(ctx, blk);
+    if (e != hipSuccess) return jda_set_err(ctx, e, "jda_exact_decode");
+    return es == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, es, "jda_exact_decode");
+}
+int jda_exact_decode_surfaces(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, int32_t *status)
+{
+    if (ctx && n > 0 && !outputs) return JDA_INVALID_PARAMETER;
+    return exact_call(ctx, n, src, outputs, pixel_types, NULL, status);
+}
+// Measuring hook of tools/exact_bench.py (not part of the public header): jda_exact_decode_surfaces with its launches between events of the
+// call's own; stage_ms[2]: the jda_exact_planes launches, the jda_exact_colour launches
+int jda_internal_exact_time(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, int32_t *status, float *stage_ms)
+{
+    if (!stage_ms || (ctx && n > 0 && !outputs)) return JDA_INVALID_PARAMETER;
+    stage_ms[0] = stage_ms[1] = 0.f;
+    return exact_call(ctx, n, src, outputs, pixel_types, NULL, status, stage_ms);
+}
+int jda_exact_decode_planes(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *planes, int32_t *status)
+{
+    if (ctx && n > 0 && !planes) return JDA_INVALID_PARAMETER;
+    return exact_call(ctx, n, src, NULL, NULL, planes, status);
+}
+int jda_decode_to_host_exact(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, void *host_pixels, int32_t pitch_bytes, int32_t rows)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!jpeg || !host_pixels || pitch_bytes < 0 || rows < 0) return JDA_INVALID_PARAMETER;
+    if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    jda_image_info I;
+    int rc = jda_parse(jpeg, len, &I);
+    if (rc != JDA_SUCCESS) return rc;
+    if ((int64_t)pitch_bytes < (int64_t)I.width * (pixel_type == JDA_RGB8888 ? 4 : 1)) return JDA_INVALID_PARAMETER;      // (a row holds the image's width, as a surface's does)
+    jda_image *img = NULL;
+    jda_coef_image *cimg = NULL;
+    jda_recode_source S = { NULL, NULL };
+    int32_t err = JDA_SUCCESS;
+    jda_dev_image *dimg = NULL;
+    jda_dev_coef *dcoef = NULL;
+    if (I.jpeg_type == 1) {                                // (every scan is what libjpeg decodes: no option bit)
+        cimg = jda_progressive_prepare(jpeg, len, &err);
+        if (cimg) dcoef = jda_coef_upload_ex(ctx, cimg, JDA_COEF_AUTO, &err);
+        S.coef = dcoef;
+    } else {
+        img = jda_prepare(jpeg, len, &err);
+        if (img) dimg = jda_upload(ctx, img, &err);
+        S.image = dimg;
+    }
+    rc = (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
+    const int bpp = pixel_type == JDA_RGB8888 ? 4 : 1;
+    const int dpitch = (int)align16((size_t)I.width * bpp), drows = rows < I.height ? rows : I.height;
+    void *dout = NULL;
+    if (rc == JDA_SUCCESS && jda_pool_alloc(ctx, &dout, (size_t)dpitch * (size_t)I.height + 16) != hipSuccess) rc = JDA_ERROR_MEMORY;
+    if (rc == JDA_SUCCESS) {
+        jda_output O;
+        O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = I.width; O.rows = drows;
+        int32_t st = JDA_SUCCESS;
+        rc = exact_call(ctx, 1, &S, &O, &pixel_type, NULL, &st);
+        if (rc == JDA_SUCCESS) rc = st;
+    }
+    if (rc == JDA_SUCCESS && drows > 0) {
+        rc = copy_rows_back(ctx, host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, (size_t)I.width * bpp, (size_t)drows, false);
+    }
+    if (dout) jda_pool_free(ctx, dout);
     if (dimg) jda_dev_image_free(ctx, dimg);
     if (dcoef) jda_dev_coef_free(ctx, dcoef);
     if (img) jda_image_free(img);

@@ -212,6 +212,11 @@ extern "C" void jda_decode_pool_release(hipStream_t stream);
 extern "C" hipError_t jda_launch_coef_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
 // the same from the sparse form (descs[i].tables: quantisers | first[], .scan: entries): jda_sparse_tiles<mode>
 extern "C" hipError_t jda_launch_sparse_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
+// the libjpeg-exact decode (jda_ex_* in jda_device_core.h): stage 0 / 1 / 2 jda_exact_planes<mode> over tiles of dense coefficient images /
+// sparse ones / resident baseline images (descs as for the two launches above, ex and src: a record an image), stage 3 jda_exact_colour<mode>
+// over tile records of that mode
+extern "C" hipError_t jda_launch_exact(int mode, int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
+                                       hipStream_t stream);
 inline uint32_t jda_flat_items(const jda_dev_desc &D) { return (D.mode == JDA_MODE_GRAY ? (D.mcus_x + 3u) >> 2 : D.mcus_x) * D.mcus_y; }      // quads of blocks (gray) / MCUs
 
 #endif

@@ -131,7 +131,32 @@ def prescale_option(info, pixel_type, options, size):
     return 0
 
 
-def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False, progressive="thumbnail", resample=None):
+def _exact_batch(ctx, files, infos, outs, pt):
+    """decode_to_tensors(decoder="libjpeg"): the files resident -- baseline ones with the device pre-scan's index, progressive ones as
+    coefficient images in whichever form is smaller -- and ONE exact_decode call into the surfaces `outs`; -> the statuses"""
+    n = len(files)
+    base_ix = [k for k in range(n) if infos[k].jpeg_type != 1]
+    prepared, sources, hosts = [], [None] * n, []
+    try:
+        prepared = B.prepare_batch([files[k] for k in base_ix], device_prescan=True) if base_ix else []
+        for k, d in zip(base_ix, B.upload_batch(ctx, prepared) if base_ix else []):
+            sources[k] = d
+        for k in range(n):
+            if infos[k].jpeg_type == 1:
+                hosts.append(B.CoefImage(files[k]))
+                sources[k] = B.DeviceCoef(ctx, hosts[-1], B.COEF_AUTO)
+        return B.exact_decode(ctx, sources, outs, [pt] * n)
+    finally:
+        for d in sources:
+            if d is not None:
+                d.close()
+        for p in list(prepared) + hosts:
+            if p is not None:
+                p.close()
+
+
+def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False, progressive="thumbnail", resample=None,
+                      decoder="reference"):
     """files (JPEG bytes, all colour or all gray) -> tensors on cuda:<ctx.device>.  layout "CHW" or "HWC"; dtype torch.uint8 (default), or
     torch.float16 / torch.float32 with table = [C, 256] values of that type (normalise_table; numpy or torch).  options: the decode option
     bits of every file (a JDA_SCALE_* bit, JDA_LUMA_ONLY: one channel).  Returns a list of [C,H,W] / [H,W,C] tensors, or, when all images
@@ -145,8 +170,21 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     progressive="full": every file whose header says progressive gets PROGRESSIVE_FULL in its options and the batch is submitted with
     SUBMIT_PROGRESSIVE_FULL -- every scan, full size, so a batch that mixes baseline and progressive files of one size is still ONE
     tensor; size= and crops= work as for any file.  There is no DCT-domain scale for such a file: with prescale=True it is decoded at full
-    size and resized from there, and a JDA_SCALE_* bit in options is refused for it (JdaError 3)."""
+    size and resized from there, and a JDA_SCALE_* bit in options is refused for it (JdaError 3).
+    decoder="reference" (the default): the decode stages that reproduce the reference decoder, through a Pipeline batch.  decoder="libjpeg":
+    libjpeg's own arithmetic (jda_exact_decode_surfaces: islow IDCT, fancy upsampling, 16-bit colour constants), so that the pixels in
+    front of the resize are Image.open(f).convert("RGB")'s and, with size= and resample=, the tensor is Pillow's resize() of them bit for
+    bit.  Baseline files go through prepare_batch(device_prescan=True) + upload_batch, progressive ones -- every scan, whatever
+    progressive= says -- through CoefImage + jda_coef_upload_ex(COEF_AUTO), then ONE exact_decode call into the scratch surfaces.  libjpeg's
+    reduced-size IDCTs are not built: prescale=True or a JDA_SCALE_* bit in options is a ValueError, and so is every other option bit but
+    JDA_LUMA_ONLY (one channel: the Y plane, Pillow's draft("L")) -- none is silently dropped."""
     files = list(files)
+    if decoder not in ("reference", "libjpeg"):
+        raise ValueError("decoder: 'reference' or 'libjpeg'")
+    if decoder == "libjpeg" and (prescale or options & (B.SCALE_HALF | B.SCALE_QUARTER | B.SCALE_EIGHTH)):
+        raise ValueError("decoder='libjpeg' decodes at full size: no prescale, no JDA_SCALE_* bit in options")
+    if decoder == "libjpeg" and options & ~B.LUMA_ONLY:
+        raise ValueError("decoder='libjpeg': the only option bit it honours is JDA_LUMA_ONLY (the Y plane)")
     if progressive not in ("thumbnail", "full"):
         raise ValueError("progressive: 'thumbnail' or 'full'")
     if layout not in ("CHW", "HWC"):
@@ -192,7 +230,7 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     if any(gray) != all(gray):
         raise ValueError("gray and colour files in one call: one jda_pack_surfaces launch takes one source format")
     pt, channels = (B.GRAY8, 1) if gray[0] else (B.RGB8888, 3)
-    full = [progressive == "full" and i.jpeg_type == 1 for i in infos]
+    full = [(progressive == "full" or decoder == "libjpeg") and i.jpeg_type == 1 for i in infos]
     opts = [options | B.PROGRESSIVE_FULL if fl else options | (prescale_option(i, pt, options, size) if prescale else 0) for i, fl in zip(infos, full)]
     geos = [B.output_geometry(i, pt, o) for i, o in zip(infos, opts)]
     bpp = geos[0]["bpp"]
@@ -229,12 +267,15 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     try:
         if size is not None:
             rbase = ctx.malloc(rbytes * n)
-        pipe = B.Pipeline(ctx, max_images=n, depth=1)
-        try:
-            outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
-            status = pipe.wait(pipe.submit(files, outs, [pt] * n, opts, B.SUBMIT_PROGRESSIVE_FULL if any(full) else 0))
-        finally:
-            pipe.close()
+        outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
+        if decoder == "libjpeg":
+            status = _exact_batch(ctx, files, infos, outs, pt)
+        else:
+            pipe = B.Pipeline(ctx, max_images=n, depth=1)
+            try:
+                status = pipe.wait(pipe.submit(files, outs, [pt] * n, opts, B.SUBMIT_PROGRESSIVE_FULL if any(full) else 0))
+            finally:
+                pipe.close()
         for k, st in enumerate(status):
             if st != 0:
                 raise B.JdaError(st, "file %d of the batch" % k)

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Times of the libjpeg-exact decode (jda_exact_decode_surfaces) on the GPU beside jda_batch_decode of the same resident
+images, in one process: 64 files of 4096 x 4096, 4:2:0 at quality 75, to RGB8888 surfaces.
+
+The source is Pillow's baseline file of one smooth-plus-noise picture (tools/encode_bench.picture), prepared with the device pre-scan and
+uploaded n times; and Pillow's progressive file of the same picture as a coefficient image (jda_progressive_prepare), uploaded n times in the
+form JDA_COEF_AUTO picks.  Warm-up rounds first, every figure the median of --repeat rounds with min and max beside it:
+  exact_call      jda_exact_decode_surfaces as a caller sees it, between the context's two timer events (plan, blob copy, launches, wait);
+  stages          the same call through jda_internal_exact_time, its launches between events of their own: planes, colour;
+  batch_decode    jda_batch_decode of the baseline images to the same surfaces (the launch plan made before the first event).
+By bytes the exact road moves about 7 B a pixel (planes written 1.5, read 1.5, RGB8888 written 4) where the decode kernel writes 4.
+Nothing here is a gate.
+One JSON line on stdout and, with --out FILE (profiles/exact_bench.json is the place for a run on an MI355X), in a file.  Fails without a GPU."""
+import argparse
+import ctypes as C
+import io
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tools.encode_bench import picture, stats      # noqa: E402
+
+
+def files(w, h):
+    from PIL import Image
+    im = Image.fromarray(np.ascontiguousarray(picture(w, h)[..., :3]))
+    out = []
+    for kw in ({}, dict(progressive=True)):
+        b = io.BytesIO()
+        im.save(b, "JPEG", quality=75, subsampling=2, **kw)
+        out.append(b.getvalue())
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=64)
+    ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    import jpegdec_amd as J
+    from jpegdec_amd.binding import Output, RecodeSource
+    ctx = J.Context(0)
+    n, w, h = a.images, a.size, a.size
+    base_file, prog_file = files(w, h)
+    prepared = J.prepare_batch([base_file] * n, device_prescan=True)
+    images = J.upload_batch(ctx, prepared)
+    host = J.CoefImage(prog_file)
+    coefs = [J.DeviceCoef(ctx, host, J.COEF_AUTO) for _ in range(n)]
+    g = prepared[0].geometry(J.RGB8888, 0)
+    pitch = g["canvas_w"] * 4
+    surf = (pitch * g["canvas_h"] + 255) & ~255
+    canvases = ctx.malloc(surf * n)
+    res = {"images": n, "width": w, "height": h, "pixels": n * w * h, "index_on_device": all(im.prescan_on_device for im in images),
+           "coef_form": "sparse" if coefs[0].form == J.COEF_SPARSE else "dense"}
+    try:
+        outs = [(canvases + k * surf, pitch, g["canvas_w"], g["canvas_h"]) for k in range(n)]
+        batch = J.Batch(ctx, images, outs, [J.RGB8888] * n, [0] * n)
+        lib = ctx.lib
+        lib.jda_internal_exact_time.restype = C.c_int
+        lib.jda_internal_exact_time.argtypes = [C.c_void_p, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        so = (Output * n)(*[Output(*o) for o in outs])
+        st = (C.c_int32 * n)()
+        roads = {"baseline": (images, (RecodeSource * n)(*[RecodeSource(im.handle, None) for im in images])),
+                 "coefficients": (coefs, (RecodeSource * n)(*[RecodeSource(None, d.handle) for d in coefs]))}
+        call = {k: [] for k in roads}
+        stages = {k: [] for k in roads}
+        dec = []
+        for r in range(a.warmup + a.repeat):
+            for name, (items, rs) in roads.items():
+                ctx.timer_start()
+                status = J.exact_decode(ctx, items, outs)
+                ctx.timer_stop()
+                assert not any(status), status[:4]
+                t_call = ctx.timer_elapsed_ms()
+                ms = (C.c_float * 2)()
+                ctx.check(lib.jda_internal_exact_time(ctx.handle, n, rs, so, None, st, ms), "jda_internal_exact_time")
+                assert not any(st)
+                if r >= a.warmup:
+                    call[name].append(t_call)
+                    stages[name].append(list(ms))
+            ctx.timer_start()
+            batch.decode()
+            ctx.timer_stop()
+            if r >= a.warmup:
+                dec.append(ctx.timer_elapsed_ms())
+        res["batch_decode"] = stats(dec)
+        for name in roads:
+            res[name] = {"exact_call": stats(call[name]),
+                         "stages": {s: stats([row[k] for row in stages[name]]) for k, s in enumerate(("planes", "colour"))},
+                         "exact_call_over_batch_decode": round(statistics.median(call[name]) / statistics.median(dec), 3)}
+            med = {s: res[name]["stages"][s]["median_ms"] for s in ("planes", "colour")}
+            res[name]["gpixels_per_s_kernels"] = round(n * w * h / (sum(med.values()) * 1e6), 2)
+        batch.close()
+    finally:
+        ctx.free(canvases)
+        for d in coefs:
+            d.close()
+        host.close()
+        for im in images:
+            im.close()
+        for p in prepared:
+            p.close()
+        ctx.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
