@@ -871,6 +871,33 @@ int jda_exact_decode_surfaces(jda_ctx *ctx, int32_t n, const jda_recode_source *
 int jda_exact_decode_planes(jda_ctx *ctx, int32_t n, const jda_recode_source *sources, const jda_output *planes, int32_t *status);
 int jda_decode_to_host_exact(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, void *host_pixels, int32_t pitch_bytes, int32_t rows);
 
+/* ------------------------------------------------------------------ libjpeg-exact decode at 1/2, 1/4, 1/8
+ * libjpeg's scaled decode as Pillow's Image.draft() drives it, bit for bit: scale s in {1, 2, 4, 8}, the output ceil(width / s) x
+ * ceil(height / s); every component through a reduced IDCT of its own size (jdmaster.c: 8 / s for luma and for every chroma but 4:2:0's,
+ * which takes 16 / s and then needs no upsampling; jidctred.c's 4x4, 2x2 and 1x1, jidctint.c's 8x8); fancy upsampling only above 1/8, h2v1
+ * fancy only where the component's own width is above 2, replication otherwise; dequantisation, range limit and colour as at full size.
+ * The definition is stated in numpy in tests/exact_scaled_util.py; the window rule of the full-size calls carries over.
+ * jda_exact_scaled_geometry: the output size and the own extents of Y, Cb, Cr at that scale (comp_w / comp_h: three entries each, zeros for
+ * the components a gray file lacks; any pointer may be NULL).  info: a header jda_parse accepted.  JDA_INVALID_PARAMETER for a scale outside
+ * {1, 2, 4, 8} or an empty image, JDA_UNSUPPORTED_FEATURE for a header the decode calls refuse by its layout (not one or three components).
+ * jda_exact_draft_scale: the scale Pillow's draft(mode, (req_w, req_h)) chooses: the largest of 8, 4, 2, 1 that does not exceed
+ * min(width / req_w, height / req_h) (integer divisions); 1 for a request that is not positive.
+ * jda_exact_decode_surfaces_scaled: jda_exact_decode_surfaces with a scale per image (scales == NULL: all 1); the surface receives
+ * min(ceil(width / s), width_px) x min(ceil(height / s), rows) pixels and no other byte.  Scales may be mixed in one call.  An image at
+ * scale 1 goes through jda_exact_decode_surfaces' own kernels and gets its bytes; launches: one of jda_exact_planes[_scaled] per (layout,
+ * dense | sparse | baseline image, scale) present, one of jda_exact_colour[_scaled] per (layout, scale) present.  A scale outside {1, 2, 4, 8}:
+ * JDA_INVALID_PARAMETER in status[i]; everything jda_exact_decode_surfaces refuses stays refused.  At 1/8 a resident baseline image whose
+ * components all decode to one sample a block (every layout but 4:2:0) is decoded from the DC values of its index alone: its scan is not read.
+ * jda_exact_decode_planes_scaled: the planes at their own scaled extents (jda_exact_scaled_geometry's).
+ * jda_decode_to_host_exact_scaled: the one call at a scale; host_pixels: ceil(width / s) x ceil(height / s) pixels at pitch_bytes. */
+int jda_exact_scaled_geometry(const jda_image_info *info, int32_t scale, int32_t *out_w, int32_t *out_h, int32_t *comp_w, int32_t *comp_h);
+int jda_exact_draft_scale(const jda_image_info *info, int32_t req_w, int32_t req_h);
+int jda_exact_decode_surfaces_scaled(jda_ctx *ctx, int32_t n, const jda_recode_source *sources, const jda_output *outputs, const int32_t *pixel_types,
+                                     const int32_t *scales, int32_t *status);
+int jda_exact_decode_planes_scaled(jda_ctx *ctx, int32_t n, const jda_recode_source *sources, const jda_output *planes, const int32_t *scales, int32_t *status);
+int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, void *host_pixels, int32_t pitch_bytes,
+                                    int32_t rows);
+
 const char *jda_version(void);
 
 #ifdef __cplusplus

@@ -226,6 +226,11 @@ _PROTOTYPES = [
     ("jda_exact_decode_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("jda_exact_decode_planes", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32)]),
     ("jda_decode_to_host_exact", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
+    ("jda_exact_scaled_geometry", C.c_int, [C.POINTER(ImageInfo), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("jda_exact_draft_scale", C.c_int, [C.POINTER(ImageInfo), C.c_int32, C.c_int32]),
+    ("jda_exact_decode_surfaces_scaled", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("jda_exact_decode_planes_scaled", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("jda_decode_to_host_exact_scaled", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
 ]
 
 
@@ -1254,40 +1259,83 @@ def _recode_sources(sources):
     return (RecodeSource * max(n, 1))(*[RecodeSource(q.handle, None) if isinstance(q, DeviceImage) else RecodeSource(None, q.handle) for q in sources])
 
 
-def exact_decode(ctx: Context, sources, outputs, pixel_types=None):
+def exact_decode(ctx: Context, sources, outputs, pixel_types=None, scales=None):
     """jda_exact_decode_surfaces: the libjpeg-exact decode (Pillow's pixels, not the reference's) of resident sources -- DeviceImage (a
     baseline file) or DeviceCoef (dense or sparse) each -- into surfaces.  outputs = (device pointer, pitch, width_px, rows) each;
     pixel_types: RGB8888 (the default) or GRAY8 each.  Exactly min(width, width_px) x min(height, rows) pixels of an image are written.
-    -> the statuses; the call's own refusals raise JdaError."""
+    scales (jda_exact_decode_surfaces_scaled): 1, 2, 4 or 8 each -- libjpeg's scaled decode, Pillow's draft(); the image is then
+    ceil(width / s) x ceil(height / s).  -> the statuses; the call's own refusals raise JdaError."""
     n = len(sources)
     o = (Output * max(n, 1))(*[Output(*q) for q in outputs])
     pt = None if pixel_types is None else (C.c_int32 * max(n, 1))(*pixel_types)
     status = (C.c_int32 * max(n, 1))()
-    ctx.check(ctx.lib.jda_exact_decode_surfaces(ctx.handle, n, _recode_sources(sources), o, pt, status), "jda_exact_decode_surfaces")
+    if scales is None:
+        ctx.check(ctx.lib.jda_exact_decode_surfaces(ctx.handle, n, _recode_sources(sources), o, pt, status), "jda_exact_decode_surfaces")
+    else:
+        sc = (C.c_int32 * max(n, 1))(*scales)
+        ctx.check(ctx.lib.jda_exact_decode_surfaces_scaled(ctx.handle, n, _recode_sources(sources), o, pt, sc, status), "jda_exact_decode_surfaces_scaled")
     return list(status)[:n]
 
 
-def exact_planes(ctx: Context, sources, planes):
+def exact_planes(ctx: Context, sources, planes, scales=None):
     """jda_exact_decode_planes: the 8-bit component planes at their own extents (libjpeg's raw-data output).  planes = per source three
-    (device pointer, pitch, width, rows) -- Y, Cb, Cr; a gray image's last two are not looked at.  -> the statuses."""
+    (device pointer, pitch, width, rows) -- Y, Cb, Cr; a gray image's last two are not looked at.  scales (jda_exact_decode_planes_scaled):
+    1, 2, 4 or 8 each, the extents then exact_scaled_geometry's.  -> the statuses."""
     n = len(sources)
     flat = [Output(*q) for three in planes for q in three]
     status = (C.c_int32 * max(n, 1))()
-    ctx.check(ctx.lib.jda_exact_decode_planes(ctx.handle, n, _recode_sources(sources), (Output * max(3 * n, 1))(*flat), status), "jda_exact_decode_planes")
+    if scales is None:
+        ctx.check(ctx.lib.jda_exact_decode_planes(ctx.handle, n, _recode_sources(sources), (Output * max(3 * n, 1))(*flat), status), "jda_exact_decode_planes")
+    else:
+        sc = (C.c_int32 * max(n, 1))(*scales)
+        ctx.check(ctx.lib.jda_exact_decode_planes_scaled(ctx.handle, n, _recode_sources(sources), (Output * max(3 * n, 1))(*flat), sc, status), "jda_exact_decode_planes_scaled")
     return list(status)[:n]
 
 
-def decode_to_host_exact(ctx: Context, jpeg: bytes, pixel_type=RGB8888):
-    """jda_decode_to_host_exact: one file, baseline or progressive, to the pixels Pillow gives -- (rc, height x width x 4 RGBA bytes or
-    height x width gray)."""
+def _info_of(jpeg_or_info):
+    if isinstance(jpeg_or_info, ImageInfo):
+        return jpeg_or_info
+    info = ImageInfo()
+    rc = load_library().jda_parse(jpeg_or_info, len(jpeg_or_info), C.byref(info))
+    if rc != 0:
+        raise JdaError(rc, "jda_parse")
+    return info
+
+
+def exact_scaled_geometry(jpeg_or_info, scale):
+    """jda_exact_scaled_geometry of a file (bytes) or an ImageInfo: {"width", "height": the output at that scale, "components": [(w, h)] the own
+    extents of Y, Cb, Cr}; a scale outside 1, 2, 4, 8 raises JdaError."""
+    info = _info_of(jpeg_or_info)
+    w, h, cw, ch = C.c_int32(), C.c_int32(), (C.c_int32 * 3)(), (C.c_int32 * 3)()
+    rc = load_library().jda_exact_scaled_geometry(C.byref(info), scale, C.byref(w), C.byref(h), cw, ch)
+    if rc != 0:
+        raise JdaError(rc, "jda_exact_scaled_geometry")
+    return dict(width=w.value, height=h.value, components=[(cw[c], ch[c]) for c in range(info.ncomp)])
+
+
+def exact_draft_scale(jpeg_or_info, size):
+    """jda_exact_draft_scale: the scale Pillow's Image.draft(mode, size) chooses for the file; size = (width, height) as Pillow's"""
+    info = _info_of(jpeg_or_info)
+    return load_library().jda_exact_draft_scale(C.byref(info), int(size[0]), int(size[1]))
+
+
+def decode_to_host_exact(ctx: Context, jpeg: bytes, pixel_type=RGB8888, scale=1):
+    """jda_decode_to_host_exact[_scaled]: one file, baseline or progressive, to the pixels Pillow gives (at scale 2, 4, 8: after
+    draft()) -- (rc, height x width x 4 RGBA bytes or height x width gray)."""
     info = ImageInfo()
     rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
     if rc != 0:
         raise JdaError(rc, "jda_parse")
     bpp = 4 if pixel_type == RGB8888 else 1
-    canvas = np.zeros((info.height, info.width * bpp), dtype=np.uint8)
-    rc = ctx.lib.jda_decode_to_host_exact(ctx.handle, jpeg, len(jpeg), pixel_type, canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0])
-    return rc, (canvas.reshape(info.height, info.width, 4) if bpp == 4 else canvas)
+    if scale == 1:
+        canvas = np.zeros((info.height, info.width * bpp), dtype=np.uint8)
+        rc = ctx.lib.jda_decode_to_host_exact(ctx.handle, jpeg, len(jpeg), pixel_type, canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0])
+        return rc, (canvas.reshape(info.height, info.width, 4) if bpp == 4 else canvas)
+    s = scale if scale in (2, 4, 8) else 1                          # (a scale the call refuses: a canvas of the file's size, left untouched)
+    w, h = -(-info.width // s), -(-info.height // s)
+    canvas = np.zeros((h, w * bpp), dtype=np.uint8)
+    rc = ctx.lib.jda_decode_to_host_exact_scaled(ctx.handle, jpeg, len(jpeg), pixel_type, scale, canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0])
+    return rc, (canvas.reshape(h, w, 4) if bpp == 4 else canvas)
 
 
 def decode_resized_to_host(ctx: Context, jpeg: bytes, size, pixel_type=RGB8888, options=0, rect=None, out=None, filter=0):

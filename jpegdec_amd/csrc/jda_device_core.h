@@ -5400,4 +5400,281 @@ template <int MODE, class IO> JDA_HD void jda_ex_load_baseline(IO &io, const jda
     jda_ex_extract_block(jda_ex_walk_of(src, io), C.first_block + lane, wl + L::COEF_OFF + lane * JDA_COEF_STRIDE, io);
 }
 
+// ================================================================================================
+// jda_exs_*: the libjpeg-exact decode at 1/2, 1/4 and 1/8: libjpeg's scaled decode as Pillow's draft() drives it, stated
+// in numpy in tests/exact_scaled_util.py.  SCALE = 2, 4, 8; MIN = 8 / SCALE.  A component's blocks go through an IDCT of its own size ss
+// (jdmaster.c): MIN for luma and for every chroma but 4:2:0's, whose ss is 2 MIN -- at 1/2 the full islow IDCT above -- and which then
+// needs no upsampling.  jidctred.c's 4x4 reads 49 coefficients (no row or column 4), its 2x2 reads 25 (frequencies 0, 1, 3, 5, 7), 1x1 the
+// DC.  Multiplies by IDCT constants are full 32-bit ones, as at full size.
+//   planes   lane = block behind the same three load phases.  A lane takes the coefficients its IDCT reads out of its slot into
+//            registers and leaves ss rows of ss bytes packed in px[]; once every lane has read (a wave sync), the slots are free and the
+//            tile is assembled over them: per component ROWS rows of the tile's samples, each byte where its plane address says modulo 4
+//            (jda_exs_stage).  After another sync the lanes share the rows out dword by dword (jda_exs_store): 4-byte stores wherever
+//            all four bytes are the tile's, single bytes at its unaligned ends (a 20-MCU 4:4:4 tile at 1/8 is 20 bytes wide, a 4:2:2 one
+//            at 1/8 is 32 luma and 16 chroma bytes).  Neighbouring tiles never write the same byte.
+//            A baseline image's 1x1 lanes take the DC value from the index and never touch the scan: jda_exs_load_baseline walks only
+//            lanes whose ss is above 1 (4:2:0's chroma at 1/8) -- at 1/8 gray, 4:4:4, 4:2:2 and 4:4:0 have no walk at all.
+//   colour   lane = four output pixels at a multiple of 4 (one 16-byte store; single pixels where a tile begins or ends inside the quad),
+//            over the tile's own pixels: count x MCU_W / SCALE by MCU_H / SCALE.  X.up names what jdsample.c does at this scale: nothing,
+//            h2v1 or h1v2, fancy or replicated; the indices are clamped to the component's own scaled extent (X.cw x X.ch).
+#define JDA_EX_UP_NONE 0u
+#define JDA_EX_UP_H2V1_FANCY 1u
+#define JDA_EX_UP_H2V1_REPLICATE 2u
+#define JDA_EX_UP_H1V2_FANCY 3u
+#define JDA_EX_UP_H1V2_REPLICATE 4u
+template <int MODE, int SCALE> struct jda_exs_layout {
+    enum { MIN = 8 / SCALE, SS_Y = MIN, SS_C = MODE == JDA_MODE_420 ? 2 * MIN : MIN,
+           HS = jda_ex_layout<MODE>::HS, VS = jda_ex_layout<MODE>::VS, MCUS = jda_lds_layout<MODE>::MCUS,
+           // the tile over the slots: a row holds the tile's bytes behind up to three of misalignment, dwords of it up to three more
+           PITCH_Y = (MCUS * HS * SS_Y + 6) / 4 * 4, ROWS_Y = VS * SS_Y, PITCH_C = (MCUS * SS_C + 6) / 4 * 4, ROWS_C = SS_C,
+           OFF_C = PITCH_Y * ROWS_Y, STAGE_BYTES = OFF_C + 2 * PITCH_C * ROWS_C };
+    static_assert(SCALE == 2 || SCALE == 4 || SCALE == 8, "the reduced sizes");
+    static_assert(STAGE_BYTES <= jda_lds_layout<MODE>::BLOCKS * JDA_COEF_STRIDE, "the assembled tile fits over the slots");
+};
+
+// one pass of jidctred.c's jpeg_idct_4x4 (DESCALE by 12 for the columns, 19 for the rows) and of jpeg_idct_2x2 (13, 20)
+template <int SHIFT> JDA_HD void jda_exs_idct4(int32_t d0, int32_t d1, int32_t d2, int32_t d3, int32_t d5, int32_t d6, int32_t d7, int32_t *o, int stride)
+{
+    typedef uint32_t U;
+    const U R = 1u << (SHIFT - 1);
+    const U t0 = (U)d0 << 14, t2 = (U)d2 * 15137u - (U)d6 * 6270u;
+    const U t10 = t0 + t2, t12 = t0 - t2;
+    const U a = (U)d5 * 11893u + (U)d1 * 8697u - (U)d7 * 1730u - (U)d3 * 17799u;
+    const U c = (U)d3 * 7373u + (U)d1 * 20995u - (U)d7 * 4176u - (U)d5 * 4926u;
+    o[0] = (int32_t)(t10 + c + R) >> SHIFT; o[3 * stride] = (int32_t)(t10 - c + R) >> SHIFT;
+    o[stride] = (int32_t)(t12 + a + R) >> SHIFT; o[2 * stride] = (int32_t)(t12 - a + R) >> SHIFT;
+}
+template <int SHIFT> JDA_HD void jda_exs_idct2(int32_t d0, int32_t d1, int32_t d3, int32_t d5, int32_t d7, int32_t *o, int stride)
+{
+    typedef uint32_t U;
+    const U R = 1u << (SHIFT - 1);
+    const U t10 = (U)d0 << 15, t0 = (U)d5 * 6967u + (U)d1 * 29692u - (U)d7 * 5906u - (U)d3 * 10426u;
+    o[0] = (int32_t)(t10 + t0 + R) >> SHIFT; o[stride] = (int32_t)(t10 - t0 + R) >> SHIFT;
+}
+// row r of a slot, dequantised: eight coefficients times the raw quantisers
+JDA_HD void jda_exs_row(const jda_u64_alias *src, const jda_u64_alias *qs, uint32_t r, int32_t *d)
+{
+#pragma unroll
+    for (uint32_t h = 0; h < 2u; h++) {
+        const uint64_t v = src[2u * r + h], q = qs[2u * r + h];
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) d[4u * h + j] = jda_mulc<true>((int32_t)(int16_t)(uint16_t)(v >> (16u * j)), (int32_t)(uint16_t)(q >> (16u * j)));
+    }
+}
+// the SS x SS samples of one block: row y in px[y * SS / 4 ..] (SS = 8: two dwords a row, 4: one; SS = 2: both rows in px[0], 1: a byte)
+template <int SS> JDA_HD void jda_exs_idct(const uint8_t *slot, const uint8_t *q, uint32_t *px)
+{
+    const jda_u64_alias *src = (const jda_u64_alias *)slot, *qs = (const jda_u64_alias *)q;
+    if (SS == 8) {
+        int32_t ws[64];
+#pragma unroll
+        for (uint32_t r = 0; r < 8u; r++) jda_exs_row(src, qs, r, ws + 8u * r);
+#pragma unroll
+        for (uint32_t x = 0; x < 8u; x++) jda_ex_idct8<11>(ws[x], ws[8 + x], ws[16 + x], ws[24 + x], ws[32 + x], ws[40 + x], ws[48 + x], ws[56 + x]);
+#pragma unroll
+        for (uint32_t y = 0; y < 8u; y++) {
+            jda_ex_idct8<18>(ws[8 * y], ws[8 * y + 1], ws[8 * y + 2], ws[8 * y + 3], ws[8 * y + 4], ws[8 * y + 5], ws[8 * y + 6], ws[8 * y + 7]);
+            px[2 * y] = jda_ex_limit(ws[8 * y]) | (jda_ex_limit(ws[8 * y + 1]) << 8) | (jda_ex_limit(ws[8 * y + 2]) << 16) | (jda_ex_limit(ws[8 * y + 3]) << 24);
+            px[2 * y + 1] = jda_ex_limit(ws[8 * y + 4]) | (jda_ex_limit(ws[8 * y + 5]) << 8) | (jda_ex_limit(ws[8 * y + 6]) << 16) | (jda_ex_limit(ws[8 * y + 7]) << 24);
+        }
+    } else if (SS == 4) {
+        int32_t d[64], ws[32], o[4];
+#pragma unroll
+        for (uint32_t r = 0; r < 8u; r++) if (r != 4u) jda_exs_row(src, qs, r, d + 8u * r);
+#pragma unroll
+        for (uint32_t x = 0; x < 8u; x++) if (x != 4u) jda_exs_idct4<12>(d[x], d[8 + x], d[16 + x], d[24 + x], d[40 + x], d[48 + x], d[56 + x], ws + x, 8);
+#pragma unroll
+        for (uint32_t y = 0; y < 4u; y++) {
+            jda_exs_idct4<19>(ws[8 * y], ws[8 * y + 1], ws[8 * y + 2], ws[8 * y + 3], ws[8 * y + 5], ws[8 * y + 6], ws[8 * y + 7], o, 1);
+            px[y] = jda_ex_limit(o[0]) | (jda_ex_limit(o[1]) << 8) | (jda_ex_limit(o[2]) << 16) | (jda_ex_limit(o[3]) << 24);
+        }
+    } else if (SS == 2) {
+        int32_t d[64], ws[16], o[2];
+#pragma unroll
+        for (uint32_t r = 0; r < 8u; r++) if (r < 2u || (r & 1u)) jda_exs_row(src, qs, r, d + 8u * r);
+#pragma unroll
+        for (uint32_t x = 0; x < 8u; x++) if (x < 2u || (x & 1u)) jda_exs_idct2<13>(d[x], d[8 + x], d[24 + x], d[40 + x], d[56 + x], ws + x, 8);
+        px[0] = 0;
+#pragma unroll
+        for (uint32_t y = 0; y < 2u; y++) {
+            jda_exs_idct2<20>(ws[8 * y], ws[8 * y + 1], ws[8 * y + 3], ws[8 * y + 5], ws[8 * y + 7], o, 1);
+            px[0] |= (jda_ex_limit(o[0]) | (jda_ex_limit(o[1]) << 8)) << (16u * y);
+        }
+    } else {
+        const int32_t dc = jda_mulc<true>((int32_t)(int16_t)(uint16_t)src[0], (int32_t)(uint16_t)qs[0]);
+        px[0] = jda_ex_limit((int32_t)((uint32_t)dc + 4u) >> 3);                     // DESCALE(d0, 3)
+    }
+}
+// where a lane's block lies: its component, its place in the tile in blocks of the component
+template <int MODE> JDA_HD void jda_exs_place(uint32_t lane, uint32_t *c, uint32_t *bx, uint32_t *by)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_ex_layout<MODE> E;
+    const uint32_t k = lane % (uint32_t)T::NBLK, m = lane / (uint32_t)T::NBLK;
+    *c = k < (uint32_t)T::NLUMA ? 0u : k - (uint32_t)T::NLUMA + 1u;
+    *bx = *c ? m : m * (uint32_t)E::HS + k % (uint32_t)E::HS;
+    *by = *c ? 0u : k / (uint32_t)E::HS;
+}
+// the load phase over a resident baseline image: only the lanes whose IDCT reads more than the DC walk the scan
+template <int MODE, int SCALE, class IO>
+JDA_HD void jda_exs_load_baseline(IO &io, const jda_ex_desc &X, const jda_ex_src *src, const jda_tile_ctx &C, uint32_t lane, uint8_t *wl)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_lds_layout<MODE> L;
+    typedef jda_exs_layout<MODE, SCALE> Z;
+    if ((int)Z::SS_Y == 1 && (int)Z::SS_C == 1) return;
+    if (lane >= C.count * (uint32_t)T::NBLK) return;
+    uint32_t c, bx, by;
+    jda_exs_place<MODE>(lane, &c, &bx, &by);
+    if ((c ? (int)Z::SS_C : (int)Z::SS_Y) == 1 || (c && X.luma_only)) return;
+    jda_ex_extract_block(jda_ex_walk_of(src, io), C.first_block + lane, wl + L::COEF_OFF + lane * JDA_COEF_STRIDE, io);
+}
+// phase 1, lane = block: the block's samples into px[16] (what the lane's ss needs of it)
+template <int MODE, int SCALE, int SOURCE, class IO>
+JDA_HD void jda_exs_block(IO &io, const jda_ex_desc &X, const jda_ex_src *src, const jda_tile_ctx &C, uint32_t lane, const uint8_t *wl, const uint8_t *qt, uint32_t *px)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_lds_layout<MODE> L;
+    typedef jda_exs_layout<MODE, SCALE> Z;
+    if (lane >= C.count * (uint32_t)T::NBLK) return;
+    uint32_t c, bx, by;
+    jda_exs_place<MODE>(lane, &c, &bx, &by);
+    if (c && X.luma_only) return;
+    const uint8_t *slot = wl + L::COEF_OFF + lane * JDA_COEF_STRIDE, *q = qt + c * 128u;
+    if (c == 0u || (int)Z::SS_C == (int)Z::SS_Y) {
+        if ((int)Z::SS_Y == 1 && SOURCE == 2) {                  // the DC value from the index: the slot was never filled
+            const uint32_t s = C.first_block + lane;
+            const uint32_t dcw = io.ld32((const uint32_t *)io.ldptr(&src->S.blk_dc) + (s >> 1));
+            const int32_t dc = jda_mulc<true>((int32_t)(int16_t)(uint16_t)((s & 1u) ? dcw >> 16 : dcw & 0xffffu), (int32_t)(uint16_t)*(const jda_u64_alias *)q);
+            px[0] = jda_ex_limit((int32_t)((uint32_t)dc + 4u) >> 3);
+        } else jda_exs_idct<(int)Z::SS_Y>(slot, q, px);
+    } else jda_exs_idct<(int)Z::SS_C>(slot, q, px);
+}
+// phase 2, lane = block: its rows into the assembled tile (stage: the wavefront's slots, free by now)
+template <int MODE, int SCALE>
+JDA_HD void jda_exs_stage(const jda_ex_desc &X, const jda_strip &S, const jda_tile_ctx &C, uint32_t lane, uint8_t *stage, const uint32_t *px)
+{
+    typedef jda_mode_traits<MODE> T;
+    typedef jda_exs_layout<MODE, SCALE> Z;
+    if (lane >= C.count * (uint32_t)T::NBLK) return;
+    uint32_t c, bx, by;
+    jda_exs_place<MODE>(lane, &c, &bx, &by);
+    if (c && X.luma_only) return;
+    const uint32_t ss = c ? (uint32_t)Z::SS_C : (uint32_t)Z::SS_Y, pitch = c ? (uint32_t)Z::PITCH_C : (uint32_t)Z::PITCH_Y;
+    const uint32_t x0 = (uint32_t)S.mcu_x0 * (c ? 1u : (uint32_t)Z::HS) * ss;              // the tile's first sample of a row of the plane
+    uint8_t *p = stage + (c ? (uint32_t)Z::OFF_C + (c - 1u) * (uint32_t)(Z::PITCH_C * Z::ROWS_C) : 0u) + by * ss * pitch + (x0 & 3u) + bx * ss;
+    if (ss == 8u) {
+#pragma unroll
+        for (uint32_t y = 0; y < 8u; y++) { ((jda_u32_alias *)(p + y * pitch))[0] = px[2 * y]; ((jda_u32_alias *)(p + y * pitch))[1] = px[2 * y + 1]; }
+    } else if (ss == 4u) {
+#pragma unroll
+        for (uint32_t y = 0; y < 4u; y++) *(jda_u32_alias *)(p + y * pitch) = px[y];
+    } else if (ss == 2u) {
+        p[0] = (uint8_t)px[0]; p[1] = (uint8_t)(px[0] >> 8); p[pitch] = (uint8_t)(px[0] >> 16); p[pitch + 1u] = (uint8_t)(px[0] >> 24);
+    } else p[0] = (uint8_t)px[0];
+}
+// phase 3: the rows of the assembled tile, shared out dword by dword over the lanes
+template <int MODE, int SCALE, class IO>
+JDA_HD void jda_exs_store(IO &io, const jda_ex_desc &X, const jda_strip &S, uint32_t lane, const uint8_t *stage)
+{
+    typedef jda_exs_layout<MODE, SCALE> Z;
+    const uint32_t ncomp = (MODE == JDA_MODE_GRAY || X.luma_only) ? 1u : 3u;
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; c++) {                      // (unrolled: the plane pointers stay in registers)
+        if (c >= ncomp) break;
+        const uint32_t ss = c ? (uint32_t)Z::SS_C : (uint32_t)Z::SS_Y, spitch = c ? (uint32_t)Z::PITCH_C : (uint32_t)Z::PITCH_Y;
+        const uint32_t rows = c ? (uint32_t)Z::ROWS_C : (uint32_t)Z::ROWS_Y, hs = c ? 1u : (uint32_t)Z::HS;
+        const uint32_t x0 = (uint32_t)S.mcu_x0 * hs * ss, wb = (uint32_t)S.count * hs * ss, a = x0 & 3u, nd = (a + wb + 3u) >> 2;
+        const uint32_t pitch = c ? X.pitch_c : X.pitch_y, y0 = (uint32_t)S.mcu_y * rows;
+        uint8_t *plane = c == 0u ? X.plane[0] : c == 1u ? X.plane[1] : X.plane[2];
+        const uint8_t *st = stage + (c ? (uint32_t)Z::OFF_C + (c - 1u) * (uint32_t)(Z::PITCH_C * Z::ROWS_C) : 0u);
+        for (uint32_t it = lane; it < rows * nd; it += 64u) {
+            const uint32_t r = it / nd, j = it - r * nd;
+            const uint32_t v = *(const jda_u32_alias *)(st + r * spitch + 4u * j);
+            const uint32_t lo = j ? 0u : a, hi = a + wb - 4u * j < 4u ? a + wb - 4u * j : 4u;
+            const uint32_t off = (y0 + r) * pitch + (x0 - a) + 4u * j;
+            if (lo == 0u && hi == 4u) io.st32(plane, off, v);
+            else for (uint32_t b = lo; b < hi; b++) io.st8(plane, off + b, (v >> (8u * b)) & 255u);
+        }
+    }
+}
+
+// the four upsampled samples of a chroma plane under the output pixels x0 .. x0 + 3 (x0 a multiple of 4) of output row y
+template <class IO> JDA_HD void jda_exs_chroma4(IO &io, const jda_ex_desc &X, const uint8_t *plane, uint32_t x0, uint32_t y, uint32_t *out)
+{
+    const uint32_t up = X.up;
+    if (up == JDA_EX_UP_NONE || up == JDA_EX_UP_H1V2_REPLICATE || up == JDA_EX_UP_H1V2_FANCY) {
+        const uint32_t j = up == JDA_EX_UP_NONE ? y : y >> 1;
+        const uint32_t a = io.ld32(plane, j * X.pitch_c + x0);
+        if (up != JDA_EX_UP_H1V2_FANCY) {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) out[k] = (a >> (8u * k)) & 255u;
+            return;
+        }
+        const uint32_t jn = (y & 1u) ? (j + 1u < X.ch ? j + 1u : j) : (j ? j - 1u : 0u);
+        const uint32_t b = io.ld32(plane, jn * X.pitch_c + x0), bias = 1u + (y & 1u);
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) out[k] = (3u * ((a >> (8u * k)) & 255u) + ((b >> (8u * k)) & 255u) + bias) >> 2;
+        return;
+    }
+    const uint32_t i0 = x0 >> 1, last = X.cw - 1u, row = y * X.pitch_c;
+    if (up == JDA_EX_UP_H2V1_REPLICATE) {
+        const uint32_t s0 = io.ld8(plane, row + (i0 < last ? i0 : last)), s1 = io.ld8(plane, row + (i0 + 1u < last ? i0 + 1u : last));
+        out[0] = out[1] = s0; out[2] = out[3] = s1;
+        return;
+    }
+    uint32_t t[4];                                           // s[i0 - 1 .. i0 + 2], clamped
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        uint32_t i = i0 + k;
+        i = i ? i - 1u : 0u;
+        t[k] = io.ld8(plane, row + (i < last ? i : last));
+    }
+    out[0] = (3u * t[1] + t[0] + 1u) >> 2; out[1] = (3u * t[1] + t[2] + 2u) >> 2;
+    out[2] = (3u * t[2] + t[1] + 1u) >> 2; out[3] = (3u * t[2] + t[3] + 2u) >> 2;
+}
+// lane = the output pixels x0 + lo .. x0 + hi - 1 of row y (x0 a multiple of 4): nothing outside out_w x out_rows is written
+template <int MODE, class IO> JDA_HD void jda_exs_quad(IO &io, const jda_ex_desc &X, uint32_t x0, uint32_t y, uint32_t lo, uint32_t hi)
+{
+    if (y >= X.out_rows || x0 + lo >= X.out_w) return;
+    if (X.out_w - x0 < hi) hi = X.out_w - x0;
+    const uint32_t yw = io.ld32(X.plane[0], y * X.pitch_y + x0);
+    if (X.gray_out) {
+        const uint32_t o = y * X.out_pitch + x0;
+        if (lo == 0u && hi == 4u) io.st32(X.out, o, yw);
+        else {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) if (k >= lo && k < hi) io.st8(X.out, o + k, (yw >> (8u * k)) & 255u);
+        }
+        return;
+    }
+    uint32_t cb[4] = { 128u, 128u, 128u, 128u }, cr[4] = { 128u, 128u, 128u, 128u }, px[4];
+    if (MODE != JDA_MODE_GRAY) {
+        jda_exs_chroma4(io, X, X.plane[1], x0, y, cb);
+        jda_exs_chroma4(io, X, X.plane[2], x0, y, cr);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) px[k] = jda_ex_rgba((yw >> (8u * k)) & 255u, cb[k], cr[k]);
+    const uint32_t o = y * X.out_pitch + x0 * 4u;
+    if (lo == 0u && hi == 4u) io.st128(X.out, o, px);
+    else {
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) if (k >= lo && k < hi) io.st32(X.out, o + 4u * k, px[k]);
+    }
+}
+// a wavefront = a tile record: the pixels of count MCUs of MCU row mcu_y from MCU mcu_x0 at the record's scale (X.scale: 2, 4, 8)
+template <int MODE, class IO> JDA_HD void jda_exs_colour_tile(IO &io, const jda_ex_desc &X, const jda_strip &S, uint32_t lane)
+{
+    typedef jda_mode_traits<MODE> T;
+    const uint32_t sh = X.scale == 8u ? 3u : X.scale == 4u ? 2u : 1u;
+    const uint32_t mw = (uint32_t)T::MCU_W >> sh, mh = (uint32_t)T::MCU_H >> sh;
+    const uint32_t px0 = (uint32_t)S.mcu_x0 * mw, px1 = px0 + (uint32_t)S.count * mw, py0 = (uint32_t)S.mcu_y * mh;
+    if (py0 >= X.out_rows || px0 >= X.out_w) return;         // (wave-uniform)
+    const uint32_t xa = px0 & ~3u, quads = (px1 - xa + 3u) >> 2, items = quads * mh;
+    for (uint32_t it = lane; it < items; it += 64u) {
+        const uint32_t r = it / quads, q = it - r * quads, x0 = xa + 4u * q;
+        jda_exs_quad<MODE>(io, X, x0, py0 + r, x0 < px0 ? px0 - x0 : 0u, px1 - x0 < 4u ? px1 - x0 : 4u);
+    }
+}
+
 #endif // JDA_DEVICE_CORE_H

@@ -28,6 +28,7 @@ inline int jda_exact_check(const jda_image_info &I, int adobe, int pixel_type, i
 struct jda_exact_geo {
     uint32_t hs, vs, pitch_y, pitch_c, rows_y, rows_c, cw, ch;
     size_t off[3], bytes;
+    uint32_t scale, ss_y, ss_c, w, h, up;                    // jda_exact_geometry_scaled's (zeros from jda_exact_geometry)
 };
 inline int jda_exact_geometry(const jda_image_info &I, bool luma_only, jda_exact_geo *G)
 {
@@ -69,6 +70,77 @@ inline void jda_exact_fill(jda_ex_desc &X, const jda_image_info &I, const uint16
     }
     for (int c = 0; c < 3; c++)
         for (uint32_t z = 0; z < 64u; z++) X.quant[c][jda_en_zigzag(z)] = quant_zz[c][z];
+}
+
+// ---- the scaled decode: libjpeg's 1/2, 1/4 and 1/8 as Pillow's draft() drives them
+inline bool jda_exact_scale_ok(int scale) { return scale == 1 || scale == 2 || scale == 4 || scale == 8; }
+// Pillow's choice for a requested req_w x req_h: the largest of 8, 4, 2, 1 that does not exceed min(W / req_w, H / req_h)
+inline int jda_exact_draft(const jda_image_info &I, int req_w, int req_h)
+{
+    if (req_w <= 0 || req_h <= 0 || I.width <= 0 || I.height <= 0) return 1;
+    const int a = I.width / req_w, b = I.height / req_h, k = a < b ? a : b;
+    return k >= 8 ? 8 : k >= 4 ? 4 : k >= 2 ? 2 : 1;
+}
+// jdmaster.c: the IDCT size of a component of h_c x v_c blocks an MCU: from min = 8 / scale, doubled while it stays below 8 and the
+// component still divides the MCU's scaled extent both ways
+inline uint32_t jda_exact_idct_size(uint32_t scale, uint32_t hmax, uint32_t vmax, uint32_t h_c, uint32_t v_c)
+{
+    const uint32_t mn = 8u / scale;
+    uint32_t ss = mn;
+    while (ss < 8u && (hmax * mn) % (h_c * ss * 2u) == 0u && (vmax * mn) % (v_c * ss * 2u) == 0u) ss *= 2u;
+    return ss;
+}
+// The planes of one image at `scale`: as jda_exact_geometry, every block ss_y x ss_y (luma) or ss_c x ss_c (chroma) samples; w x h: the
+// output, ceil(width / scale) x ceil(height / scale); cw x ch: a chroma component's own scaled extent; up: jdsample.c's choice.  Scale 1:
+// jda_exact_geometry's numbers, field for field.
+inline int jda_exact_geometry_scaled(const jda_image_info &I, bool luma_only, int scale, jda_exact_geo *G)
+{
+    if (!jda_exact_scale_ok(scale)) { memset(G, 0, sizeof(*G)); return JDA_INVALID_PARAMETER; }
+    if (scale == 1) {
+        const int rc = jda_exact_geometry(I, luma_only, G);
+        G->scale = 1u; G->ss_y = G->ss_c = 8u; G->w = (uint32_t)I.width; G->h = (uint32_t)I.height;
+        return rc;
+    }
+    const int mode = jda_mode_of(I);
+    memset(G, 0, sizeof(*G));
+    const uint32_t s = (uint32_t)scale, mn = 8u / s;
+    G->hs = (mode == JDA_MODE_420 || mode == JDA_MODE_422) ? 2u : 1u;
+    G->vs = (mode == JDA_MODE_420 || mode == JDA_MODE_440) ? 2u : 1u;
+    G->scale = s;
+    G->ss_y = jda_exact_idct_size(s, G->hs, G->vs, G->hs, G->vs);
+    G->ss_c = jda_exact_idct_size(s, G->hs, G->vs, 1u, 1u);
+    G->w = ((uint32_t)I.width + s - 1u) / s; G->h = ((uint32_t)I.height + s - 1u) / s;
+    G->pitch_y = ((uint32_t)I.mcus_x * G->ss_y * G->hs + 15u) & ~15u;
+    G->rows_y = (uint32_t)I.mcus_y * G->ss_y * G->vs;
+    G->cw = (uint32_t)(((uint64_t)I.width * G->ss_c + G->hs * 8u - 1u) / (G->hs * 8u));
+    G->ch = (uint32_t)(((uint64_t)I.height * G->ss_c + G->vs * 8u - 1u) / (G->vs * 8u));
+    // (the upsampling factors that are left: hs min / ss_c by vs min / ss_c -- 4:2:0's chroma needs none below full size)
+    const bool fancy = mn > 1u;
+    if (mode == JDA_MODE_422) G->up = fancy && G->cw > 2u ? JDA_EX_UP_H2V1_FANCY : JDA_EX_UP_H2V1_REPLICATE;
+    else if (mode == JDA_MODE_440) G->up = fancy ? JDA_EX_UP_H1V2_FANCY : JDA_EX_UP_H1V2_REPLICATE;
+    else G->up = JDA_EX_UP_NONE;
+    if ((uint64_t)G->pitch_y * G->rows_y >= (1ull << 32)) return JDA_UNSUPPORTED_FEATURE;
+    size_t at = ((size_t)G->pitch_y * G->rows_y + 255u) & ~(size_t)255u;
+    if (mode != JDA_MODE_GRAY && !luma_only) {
+        G->pitch_c = ((uint32_t)I.mcus_x * G->ss_c + 15u) & ~15u;
+        G->rows_c = (uint32_t)I.mcus_y * G->ss_c;
+        if ((uint64_t)G->pitch_c * G->rows_c >= (1ull << 32)) return JDA_UNSUPPORTED_FEATURE;
+        for (int c = 1; c < 3; c++) { G->off[c] = at; at += ((size_t)G->pitch_c * G->rows_c + 255u) & ~(size_t)255u; }
+    }
+    G->bytes = at;
+    return JDA_SUCCESS;
+}
+// The image's record at G's scale.  Scale 1: jda_exact_fill's record (scale and up stay 0: the full-size kernels' record as it was).
+inline void jda_exact_fill_scaled(jda_ex_desc &X, const jda_image_info &I, const uint16_t (*quant_zz)[64], const jda_exact_geo &G, uint8_t *scratch, const jda_output *out,
+                                  int pixel_type, bool luma_only)
+{
+    jda_exact_fill(X, I, quant_zz, G, scratch, out, pixel_type, luma_only);
+    if (G.scale <= 1u) return;
+    X.w = G.w; X.h = G.h; X.scale = G.scale; X.up = G.up;
+    if (out) {
+        X.out_w = out->width_px < (int32_t)G.w ? (uint32_t)(out->width_px < 0 ? 0 : out->width_px) : G.w;
+        X.out_rows = out->rows < (int32_t)G.h ? (uint32_t)(out->rows < 0 ? 0 : out->rows) : G.h;
+    }
 }
 
 #endif

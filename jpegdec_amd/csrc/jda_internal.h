@@ -292,6 +292,9 @@ struct jda_ex_desc {
     uint8_t *out;
     uint32_t pitch_y, pitch_c, w, h, cw, ch, out_pitch, out_w, out_rows, gray_out, luma_only, pad_;
     uint16_t quant[3][64];
+    // a scaled decode (jda_exs_*; zeros in a record of the full-size kernels): scale 2, 4 or 8 -- w x h, cw x ch, the pitches
+    // and the clip are then the scaled ones, a plane's blocks ss x ss samples each --, up: what jdsample.c does to the chroma planes (JDA_EX_UP_*)
+    uint32_t scale, up, pad2_[2];
 };
 // A resident baseline image as the source of an exact call, beside its jda_dev_desc and jda_ex_desc in the call's blob (a record an image
 // of the call; zeros for a coefficient image): what the planes stage's baseline load phase reads -- S as a recode source's; bpm blocks an

@@ -39,17 +39,21 @@ static hipError_t jda_ensure_lds_limit(const void *fn, int bytes, std::atomic<un
 // Launches per kernel function of this library, counted where they are made (an atomic add per launch): jda_kernel_launch_counts
 // reports which kernels of the code object a process has used -- tests/test_gpu_zz_kernel_coverage.py holds the suite to all of them.
 struct jda_launch_slot { std::atomic<const void *> fn; std::atomic<unsigned long long> n; };
-#define JDA_LAUNCH_SLOTS 128
+// 512 slots, a power of two well above the 320 kernels of the code object (the hash below gives nine bits).  A launch that finds the table
+// full is NOT counted: it says so once on stderr, so that the coverage test's report cannot be short without a word.
+#define JDA_LAUNCH_SLOTS 512
 static jda_launch_slot g_launch_slots[JDA_LAUNCH_SLOTS];
 static void jda_count_launch(const void *fn)
 {
-    const uint32_t h = (uint32_t)((((uintptr_t)fn >> 3) * 0x9E3779B97F4A7C15ull) >> 57);
+    const uint32_t h = (uint32_t)((((uintptr_t)fn >> 3) * 0x9E3779B97F4A7C15ull) >> 55);
     for (uint32_t i = 0; i < JDA_LAUNCH_SLOTS; i++) {
         jda_launch_slot &S = g_launch_slots[(h + i) % JDA_LAUNCH_SLOTS];
         const void *cur = S.fn.load(std::memory_order_acquire);
         if (cur == nullptr && S.fn.compare_exchange_strong(cur, fn, std::memory_order_acq_rel)) cur = fn;
         if (cur == fn) { S.n.fetch_add(1, std::memory_order_relaxed); return; }
     }
+    static std::atomic<bool> said(false);
+    if (!said.exchange(true)) fprintf(stderr, "jpegdec_amd: the launch-count table (%d slots) is full; further kernels are not counted\n", JDA_LAUNCH_SLOTS);
 }
 #define JDA_LAUNCH(kernel, grid, block, lds, stream, ...) do { jda_count_launch((const void *)(kernel)); hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); } while (0)
 // "<kernel symbol> <launches>\n" for every kernel launched so far; returns the bytes the whole report needs (cap too small: truncated)
@@ -2863,6 +2867,113 @@ extern "C" hipError_t jda_launch_exact(int mode, int stage, const jda_dev_desc *
     case JDA_MODE_420: return launch_exact<JDA_MODE_420>(stage, descs, ex, src, tiles, n_tiles, stream);
     case JDA_MODE_422: return launch_exact<JDA_MODE_422>(stage, descs, ex, src, tiles, n_tiles, stream);
     case JDA_MODE_440: return launch_exact<JDA_MODE_440>(stage, descs, ex, src, tiles, n_tiles, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// jda_exact_planes_scaled<MODE, SOURCE, SCALE> / jda_exact_colour_scaled<MODE>: the libjpeg-exact decode at 1/2, 1/4 and 1/8 (jda_exs_* in
+// jda_device_core.h).  The launch shapes, the LDS share and the load phases are jda_exact_planes'; behind the IDCT the
+// wavefront assembles its tile over the slots and stores it in dwords.  The colour kernel takes the scale from the image's record.
+__device__ __forceinline__ void jda_exs_desc_uniform(jda_ex_desc &L, const jda_ex_desc *p)
+{
+    jda_ex_desc_uniform(L, p);
+    const jda_ex_desc JDA_GLOBAL *g = JDA_G(const jda_ex_desc, p);
+    L.scale = jda_uni32(g->scale); L.up = jda_uni32(g->up);
+}
+template <int MODE, int SOURCE, int SCALE>
+__global__ __launch_bounds__(64 * JDA_CT_WAVES)
+void jda_exact_planes_scaled(const jda_dev_desc *__restrict__ descs, const jda_ex_desc *__restrict__ ex, const jda_ex_src *__restrict__ src, const jda_strip *__restrict__ tiles,
+                             uint32_t n_tiles)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    typedef jda_mode_traits<MODE> T;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_CT_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;                                              // a padding record of the list
+    uint8_t *qt = lds + wave * (uint32_t)jda_ex_layout<MODE>::WAVE_BYTES;
+    uint8_t *wl = qt + JDA_EX_QUANT_BYTES;
+    const jda_dev_desc D = jda_desc_uniform<0, MODE>(descs + S.image);
+    jda_ex_desc X;
+    jda_exs_desc_uniform(X, ex + S.image);
+    jda_tile_ctx C;
+    C.first_mcu = S.mcu_y * D.mcus_x + S.mcu_x0;
+    C.count = S.count;
+    C.first_block = C.first_mcu * (uint32_t)T::NBLK;
+    C.win_lo = C.win_len = C.win_need = 0;
+    jda_exact_io io;
+    jda_ex_tables(io, ex + S.image, lane, qt);
+    if (SOURCE == 2) {
+        jda_exs_load_baseline<MODE, SCALE>(io, X, src + S.image, C, lane, wl);
+    } else if (SOURCE == 1) {
+        uint32_t e0, e1;
+        jda_cs_range<MODE>(io, D, C, &e0, &e1);
+        jda_cs_zero<MODE>(C, lane, wl);
+        JDA_WAVE_SYNC();                                                   // (the zeros lie in LDS before the first entry lands)
+        jda_cs_scatter<MODE>(io, D, C, lane, e0, e1, wl);
+    } else {
+        jda_ct_load<MODE>(io, D, C, lane, wl);
+    }
+    JDA_WAVE_SYNC();
+    uint32_t px[16];
+    jda_exs_block<MODE, SCALE, SOURCE>(io, X, src + S.image, C, lane, wl, qt, px);
+    JDA_WAVE_SYNC();                                                       // (every lane has read its slot: the tile is assembled over them)
+    jda_exs_stage<MODE, SCALE>(X, S, C, lane, wl + jda_lds_layout<MODE>::COEF_OFF, px);
+    JDA_WAVE_SYNC();
+    jda_exs_store<MODE, SCALE>(io, X, S, lane, wl + jda_lds_layout<MODE>::COEF_OFF);
+}
+template <int MODE>
+__global__ __launch_bounds__(64 * JDA_CT_WAVES)
+void jda_exact_colour_scaled(const jda_ex_desc *__restrict__ ex, const jda_strip *__restrict__ tiles, uint32_t n_tiles)
+{
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_CT_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;
+    jda_ex_desc X;
+    jda_exs_desc_uniform(X, ex + S.image);
+    jda_exact_io io;
+    jda_exs_colour_tile<MODE>(io, X, S, lane);
+}
+template <int MODE, int SCALE>
+static hipError_t launch_exact_scaled(int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    const uint32_t lds_bytes = JDA_CT_WAVES * (uint32_t)jda_ex_layout<MODE>::WAVE_BYTES;
+    const dim3 grid((n_tiles + JDA_CT_WAVES - 1u) / JDA_CT_WAVES), block(64u * JDA_CT_WAVES);
+    const auto dense = jda_exact_planes_scaled<MODE, 0, SCALE>, sparse = jda_exact_planes_scaled<MODE, 1, SCALE>, baseline = jda_exact_planes_scaled<MODE, 2, SCALE>;
+    if (stage == 0) JDA_LAUNCH(dense, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else if (stage == 1) JDA_LAUNCH(sparse, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else if (stage == 2) JDA_LAUNCH(baseline, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else JDA_LAUNCH(jda_exact_colour_scaled<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
+    return hipGetLastError();
+}
+template <int MODE>
+static hipError_t launch_exact_scaled_mode(int stage, int scale, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
+                                           hipStream_t stream)
+{
+    switch (scale) {
+    case 2: return launch_exact_scaled<MODE, 2>(stage, descs, ex, src, tiles, n_tiles, stream);
+    case 4: return launch_exact_scaled<MODE, 4>(stage, descs, ex, src, tiles, n_tiles, stream);
+    case 8: return launch_exact_scaled<MODE, 8>(stage, descs, ex, src, tiles, n_tiles, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+// as jda_launch_exact, the tiles those of images decoded at `scale`: 1 -- jda_launch_exact itself, the full-size kernels --, 2, 4 or 8
+extern "C" hipError_t jda_launch_exact_scaled(int mode, int stage, int scale, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles,
+                                              uint32_t n_tiles, hipStream_t stream)
+{
+    if (scale == 1) return jda_launch_exact(mode, stage, descs, ex, src, tiles, n_tiles, stream);
+    if (n_tiles == 0) return hipSuccess;
+    if (stage < 0 || stage > 3) return hipErrorInvalidValue;
+    switch (mode) {
+    case JDA_MODE_GRAY: return launch_exact_scaled_mode<JDA_MODE_GRAY>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
+    case JDA_MODE_444: return launch_exact_scaled_mode<JDA_MODE_444>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
+    case JDA_MODE_420: return launch_exact_scaled_mode<JDA_MODE_420>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
+    case JDA_MODE_422: return launch_exact_scaled_mode<JDA_MODE_422>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
+    case JDA_MODE_440: return launch_exact_scaled_mode<JDA_MODE_440>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
     default: return hipErrorInvalidValue;
     }
 }

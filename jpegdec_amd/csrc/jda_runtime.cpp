@@ -2155,11 +2155,12 @@ int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
 // ---- libjpeg-exact decode (jda_exact_* in jda_kernels.hip, jda_ex_* in jda_device_core.h; checks, planes and records: jda_exact_plan.h;
 // DESIGN.md 5.17).  One pool block a call: the blob (descs | records | baseline sources, one of each an image | tile lists) and behind it
 // the scratch -- every planned image's component planes.  The lists of a layout lie dense, sparse, baseline, back to back, so that the
-// colour stage takes all three in one launch.
+// colour stage takes all three in one launch.  scales (NULL: all 1): the lists are then per (layout, scale), and a scale
+// above 1 launches the _scaled kernels.
 struct exact_image { int kind; jda_image_info info; uint16_t quant[3][64]; jda_exact_geo G; size_t plane_at; bool luma_only; };
 // stage_ms (the measuring hook's, else NULL): [0] the jda_exact_planes launches, [1] the jda_exact_colour launches
 static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const jda_output *planes,
-                      int32_t *status, float *stage_ms = NULL)
+                      int32_t *status, float *stage_ms = NULL, const int32_t *scales = NULL)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (n < 0) return JDA_INVALID_PARAMETER;
@@ -2171,7 +2172,7 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
     std::vector<jda_ex_desc> ex((size_t)n);
     std::vector<jda_ex_src> esrc((size_t)n);
     std::vector<exact_image> im((size_t)n);
-    std::vector<jda_strip> strips[JDA_N_MODES][3];
+    std::vector<jda_strip> strips[JDA_N_MODES][4][3];           // [layout][log2 scale][dense | sparse | baseline]
     size_t scratch = 0;
     int planned = 0;
     for (int i = 0; i < n; i++) {
@@ -2193,17 +2194,21 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
         const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
         int rc = jda_exact_check(I, adobe, pt, M.kind == 2, n_ok);
         M.luma_only = outputs && pt == JDA_EIGHT_BIT_GRAYSCALE && I.ncomp == 3;
-        if (rc == JDA_SUCCESS) rc = jda_exact_geometry(I, M.luma_only, &M.G);
+        const int scale = scales ? scales[i] : 1;
+        if (rc == JDA_SUCCESS) rc = jda_exact_geometry_scaled(I, M.luma_only, scale, &M.G);
         if (rc == JDA_SUCCESS && outputs) {
             jda_image_info B = I;
             B.jpeg_type = 0;
             const uint8_t none[3] = { 0, 0, 0 };
-            rc = jda_fill_launch_desc(D, B, none, none, none, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, outputs[i], pt, 0, NULL);
+            jda_output O = outputs[i];                         // (a scaled image: the surface is held to the scaled size, not to the file's)
+            if (scale > 1 && O.width_px > (int32_t)M.G.w) O.width_px = (int32_t)M.G.w;
+            if (scale > 1 && O.rows > (int32_t)M.G.h) O.rows = (int32_t)M.G.h;
+            rc = jda_fill_launch_desc(D, B, none, none, none, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, O, pt, 0, NULL);
         } else if (rc == JDA_SUCCESS) {
             D.mode = (uint8_t)jda_mode_of(I); D.ncomp = (uint8_t)I.ncomp; D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
             for (int c = 0; c < (I.ncomp == 3 ? 3 : 1) && rc == JDA_SUCCESS; c++) {
                 const jda_output &P = planes[3 * i + c];
-                const int32_t ew = c ? (int32_t)M.G.cw : I.width;
+                const int32_t ew = c ? (int32_t)M.G.cw : (int32_t)M.G.w;
                 if (!P.pixels || P.width_px < 0 || P.rows < 0 || P.pitch_bytes < (P.width_px < ew ? P.width_px : ew)) rc = JDA_INVALID_PARAMETER;
             }
         }
@@ -2221,14 +2226,15 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
         } else {
             D.tables = src[i].coef->base; D.scan = src[i].coef->base + src[i].coef->off_entries;
         }
-        jda_append_strips(strips[D.mode][M.kind], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        jda_append_strips(strips[D.mode][M.G.scale == 8u ? 3 : M.G.scale == 4u ? 2 : M.G.scale == 2u ? 1 : 0][M.kind], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
     }
     if (!planned) return JDA_SUCCESS;
     const size_t o_ex = align16(descs.size() * sizeof(jda_dev_desc)), o_src = o_ex + align16(ex.size() * sizeof(jda_ex_desc));
     size_t bytes = o_src + align16(esrc.size() * sizeof(jda_ex_src));
-    size_t off[JDA_N_MODES][3];
+    size_t off[JDA_N_MODES][4][3];
     for (int m = 0; m < JDA_N_MODES; m++)
-        for (int f = 0; f < 3; f++) { off[m][f] = bytes; bytes += strips[m][f].size() * sizeof(jda_strip); }
+        for (int g = 0; g < 4; g++)
+            for (int f = 0; f < 3; f++) { off[m][g][f] = bytes; bytes += strips[m][g][f].size() * sizeof(jda_strip); }
     const size_t o_scratch = (bytes + 255u) & ~(size_t)255u;
     uint8_t *blk = NULL;
     hipError_t e = jda_pool_alloc(ctx, (void **)&blk, o_scratch + scratch);
@@ -2237,15 +2243,16 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
         const exact_image &M = im[(size_t)i];
         if (M.kind < 0) continue;
         const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
-        jda_exact_fill(ex[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt, M.luma_only);
+        jda_exact_fill_scaled(ex[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt, M.luma_only);
     }
     std::vector<uint8_t> blob(bytes, 0);
     memcpy(blob.data(), descs.data(), descs.size() * sizeof(jda_dev_desc));
     memcpy(blob.data() + o_ex, ex.data(), ex.size() * sizeof(jda_ex_desc));
     memcpy(blob.data() + o_src, esrc.data(), esrc.size() * sizeof(jda_ex_src));
     for (int m = 0; m < JDA_N_MODES; m++)
-        for (int f = 0; f < 3; f++)
-            if (!strips[m][f].empty()) memcpy(blob.data() + off[m][f], strips[m][f].data(), strips[m][f].size() * sizeof(jda_strip));
+        for (int g = 0; g < 4; g++)
+            for (int f = 0; f < 3; f++)
+                if (!strips[m][g][f].empty()) memcpy(blob.data() + off[m][g][f], strips[m][g][f].data(), strips[m][g][f].size() * sizeof(jda_strip));
     e = hipMemcpyAsync(blk, blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
     const jda_dev_desc *d_descs = (const jda_dev_desc *)blk;
     const jda_ex_desc *d_ex = (const jda_ex_desc *)(blk + o_ex);
@@ -2254,19 +2261,21 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
     for (int k = 0; k < 3 && stage_ms && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
     for (int m = 0; m < JDA_N_MODES && e == hipSuccess; m++)
-        for (int f = 0; f < 3 && e == hipSuccess; f++)
-            e = jda_launch_exact(m, f, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][f]), (uint32_t)strips[m][f].size(), ctx->stream);
+        for (int g = 0; g < 4 && e == hipSuccess; g++)
+            for (int f = 0; f < 3 && e == hipSuccess; f++)
+                e = jda_launch_exact_scaled(m, f, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][g][f]), (uint32_t)strips[m][g][f].size(), ctx->stream);
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
     for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs; m++)
-        e = jda_launch_exact(m, 3, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][0]),
-                             (uint32_t)(strips[m][0].size() + strips[m][1].size() + strips[m][2].size()), ctx->stream);
+        for (int g = 0; g < 4 && e == hipSuccess; g++)
+            e = jda_launch_exact_scaled(m, 3, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][g][0]),
+                                        (uint32_t)(strips[m][g][0].size() + strips[m][g][1].size() + strips[m][g][2].size()), ctx->stream);
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
     for (int i = 0; i < n && e == hipSuccess && planes; i++) {
         const exact_image &M = im[(size_t)i];
         if (M.kind < 0) continue;
         for (int c = 0; c < (M.info.ncomp == 3 ? 3 : 1) && e == hipSuccess; c++) {
             const jda_output &P = planes[3 * i + c];
-            const int32_t ew = c ? (int32_t)M.G.cw : M.info.width, eh = c ? (int32_t)M.G.ch : M.info.height;
+            const int32_t ew = c ? (int32_t)M.G.cw : (int32_t)M.G.w, eh = c ? (int32_t)M.G.ch : (int32_t)M.G.h;
             const size_t cw = (size_t)(P.width_px < ew ? P.width_px : ew), crows = (size_t)(P.rows < eh ? P.rows : eh);
             if (cw && crows)
                 e = hipMemcpy2DAsync(P.pixels, (size_t)P.pitch_bytes, blk + o_scratch + M.plane_at + M.G.off[c], c ? M.G.pitch_c : M.G.pitch_y, cw, crows,
@@ -2298,16 +2307,64 @@ int jda_exact_decode_planes(jda_ctx *ctx, int32_t n, const jda_recode_source *sr
     if (ctx && n > 0 && !planes) return JDA_INVALID_PARAMETER;
     return exact_call(ctx, n, src, NULL, NULL, planes, status);
 }
+// ---- the same at 1/2, 1/4 and 1/8
+int jda_exact_scaled_geometry(const jda_image_info *info, int32_t scale, int32_t *out_w, int32_t *out_h, int32_t *comp_w, int32_t *comp_h)
+{
+    if (!info) return JDA_INVALID_PARAMETER;
+    // (the layout checks of the decode calls: what they refuse has no geometry here either -- four components: JDA_UNSUPPORTED_FEATURE)
+    int rc = jda_exact_check(*info, 0, JDA_RGB8888, 0, 0);
+    if (rc != JDA_SUCCESS) return rc;
+    jda_exact_geo G;
+    rc = jda_exact_geometry_scaled(*info, false, scale, &G);
+    if (rc != JDA_SUCCESS) return rc;
+    if (out_w) *out_w = (int32_t)G.w;
+    if (out_h) *out_h = (int32_t)G.h;
+    for (int c = 0; c < 3; c++) {
+        const bool there = c < info->ncomp;
+        if (comp_w) comp_w[c] = there ? (int32_t)(c ? G.cw : G.w) : 0;
+        if (comp_h) comp_h[c] = there ? (int32_t)(c ? G.ch : G.h) : 0;
+    }
+    return JDA_SUCCESS;
+}
+int jda_exact_draft_scale(const jda_image_info *info, int32_t req_w, int32_t req_h)
+{
+    return info ? jda_exact_draft(*info, req_w, req_h) : 1;
+}
+int jda_exact_decode_surfaces_scaled(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const int32_t *scales,
+                                     int32_t *status)
+{
+    if (ctx && n > 0 && !outputs) return JDA_INVALID_PARAMETER;
+    return exact_call(ctx, n, src, outputs, pixel_types, NULL, status, NULL, scales);
+}
+int jda_exact_decode_planes_scaled(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *planes, const int32_t *scales, int32_t *status)
+{
+    if (ctx && n > 0 && !planes) return JDA_INVALID_PARAMETER;
+    return exact_call(ctx, n, src, NULL, NULL, planes, status, NULL, scales);
+}
+// the measuring hook with a scale an image (tools/exact_bench.py --scale)
+int jda_internal_exact_time_scaled(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const int32_t *scales,
+                                   int32_t *status, float *stage_ms)
+{
+    if (!stage_ms || (ctx && n > 0 && !outputs)) return JDA_INVALID_PARAMETER;
+    stage_ms[0] = stage_ms[1] = 0.f;
+    return exact_call(ctx, n, src, outputs, pixel_types, NULL, status, stage_ms, scales);
+}
 int jda_decode_to_host_exact(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, void *host_pixels, int32_t pitch_bytes, int32_t rows)
+{
+    return jda_decode_to_host_exact_scaled(ctx, jpeg, len, pixel_type, 1, host_pixels, pitch_bytes, rows);
+}
+int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, void *host_pixels, int32_t pitch_bytes, int32_t rows)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (!jpeg || !host_pixels || pitch_bytes < 0 || rows < 0) return JDA_INVALID_PARAMETER;
     if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
+    if (!jda_exact_scale_ok(scale)) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     jda_image_info I;
     int rc = jda_parse(jpeg, len, &I);
     if (rc != JDA_SUCCESS) return rc;
-    if ((int64_t)pitch_bytes < (int64_t)I.width * (pixel_type == JDA_RGB8888 ? 4 : 1)) return JDA_INVALID_PARAMETER;      // (a row holds the image's width, as a surface's does)
+    const int32_t ow = (I.width + scale - 1) / scale, oh = (I.height + scale - 1) / scale;      // (at scale 1 the file's own size)
+    if ((int64_t)pitch_bytes < (int64_t)ow * (pixel_type == JDA_RGB8888 ? 4 : 1)) return JDA_INVALID_PARAMETER;      // (a row holds the image's width, as a surface's does)
     jda_image *img = NULL;
     jda_coef_image *cimg = NULL;
     jda_recode_source S = { NULL, NULL };
@@ -2325,18 +2382,18 @@ int jda_decode_to_host_exact(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int
     }
     rc = (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
     const int bpp = pixel_type == JDA_RGB8888 ? 4 : 1;
-    const int dpitch = (int)align16((size_t)I.width * bpp), drows = rows < I.height ? rows : I.height;
+    const int dpitch = (int)align16((size_t)ow * bpp), drows = rows < oh ? rows : oh;
     void *dout = NULL;
-    if (rc == JDA_SUCCESS && jda_pool_alloc(ctx, &dout, (size_t)dpitch * (size_t)I.height + 16) != hipSuccess) rc = JDA_ERROR_MEMORY;
+    if (rc == JDA_SUCCESS && jda_pool_alloc(ctx, &dout, (size_t)dpitch * (size_t)oh + 16) != hipSuccess) rc = JDA_ERROR_MEMORY;
     if (rc == JDA_SUCCESS) {
         jda_output O;
-        O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = I.width; O.rows = drows;
+        O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = ow; O.rows = drows;
         int32_t st = JDA_SUCCESS;
-        rc = exact_call(ctx, 1, &S, &O, &pixel_type, NULL, &st);
+        rc = exact_call(ctx, 1, &S, &O, &pixel_type, NULL, &st, NULL, &scale);
         if (rc == JDA_SUCCESS) rc = st;
     }
     if (rc == JDA_SUCCESS && drows > 0) {
-        rc = copy_rows_back(ctx, host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, (size_t)I.width * bpp, (size_t)drows, false);
+        rc = copy_rows_back(ctx, host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, (size_t)ow * bpp, (size_t)drows, false);
     }
     if (dout) jda_pool_free(ctx, dout);
     if (dimg) jda_dev_image_free(ctx, dimg);

@@ -217,6 +217,10 @@ extern "C" hipError_t jda_launch_sparse_tiles(int mode, const jda_dev_desc *desc
 // over tile records of that mode
 extern "C" hipError_t jda_launch_exact(int mode, int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
                                        hipStream_t stream);
+// the same over tiles of images decoded at `scale`: 1 -- jda_launch_exact itself --, or 2, 4, 8: jda_exact_planes_scaled<mode,
+// stage, scale> (stage 0 / 1 / 2), jda_exact_colour_scaled<mode> (stage 3)
+extern "C" hipError_t jda_launch_exact_scaled(int mode, int stage, int scale, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles,
+                                              uint32_t n_tiles, hipStream_t stream);
 inline uint32_t jda_flat_items(const jda_dev_desc &D) { return (D.mode == JDA_MODE_GRAY ? (D.mcus_x + 3u) >> 2 : D.mcus_x) * D.mcus_y; }      // quads of blocks (gray) / MCUs
 
 #endif

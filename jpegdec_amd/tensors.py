@@ -131,9 +131,10 @@ def prescale_option(info, pixel_type, options, size):
     return 0
 
 
-def _exact_batch(ctx, files, infos, outs, pt):
+def _exact_batch(ctx, files, infos, outs, pt, scales=None):
     """decode_to_tensors(decoder="libjpeg"): the files resident -- baseline ones with the device pre-scan's index, progressive ones as
-    coefficient images in whichever form is smaller -- and ONE exact_decode call into the surfaces `outs`; -> the statuses"""
+    coefficient images in whichever form is smaller -- and ONE exact_decode call into the surfaces `outs` (scales: file k at 1 / scales[k],
+    libjpeg's scaled decode); -> the statuses"""
     n = len(files)
     base_ix = [k for k in range(n) if infos[k].jpeg_type != 1]
     prepared, sources, hosts = [], [None] * n, []
@@ -145,7 +146,7 @@ def _exact_batch(ctx, files, infos, outs, pt):
             if infos[k].jpeg_type == 1:
                 hosts.append(B.CoefImage(files[k]))
                 sources[k] = B.DeviceCoef(ctx, hosts[-1], B.COEF_AUTO)
-        return B.exact_decode(ctx, sources, outs, [pt] * n)
+        return B.exact_decode(ctx, sources, outs, [pt] * n, scales)
     finally:
         for d in sources:
             if d is not None:
@@ -156,7 +157,7 @@ def _exact_batch(ctx, files, infos, outs, pt):
 
 
 def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False, progressive="thumbnail", resample=None,
-                      decoder="reference"):
+                      decoder="reference", draft=None):
     """files (JPEG bytes, all colour or all gray) -> tensors on cuda:<ctx.device>.  layout "CHW" or "HWC"; dtype torch.uint8 (default), or
     torch.float16 / torch.float32 with table = [C, 256] values of that type (normalise_table; numpy or torch).  options: the decode option
     bits of every file (a JDA_SCALE_* bit, JDA_LUMA_ONLY: one channel).  Returns a list of [C,H,W] / [H,W,C] tensors, or, when all images
@@ -175,14 +176,29 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     libjpeg's own arithmetic (jda_exact_decode_surfaces: islow IDCT, fancy upsampling, 16-bit colour constants), so that the pixels in
     front of the resize are Image.open(f).convert("RGB")'s and, with size= and resample=, the tensor is Pillow's resize() of them bit for
     bit.  Baseline files go through prepare_batch(device_prescan=True) + upload_batch, progressive ones -- every scan, whatever
-    progressive= says -- through CoefImage + jda_coef_upload_ex(COEF_AUTO), then ONE exact_decode call into the scratch surfaces.  libjpeg's
-    reduced-size IDCTs are not built: prescale=True or a JDA_SCALE_* bit in options is a ValueError, and so is every other option bit but
-    JDA_LUMA_ONLY (one channel: the Y plane, Pillow's draft("L")) -- none is silently dropped."""
+    progressive= says -- through CoefImage + jda_coef_upload_ex(COEF_AUTO), then ONE exact_decode call into the scratch surfaces.  The
+    reference road's scales are not libjpeg's: prescale=True or a JDA_SCALE_* bit in options is a ValueError (libjpeg's own reduced-size
+    decode is draft=, below), and so is every other option bit but
+    JDA_LUMA_ONLY (one channel: the Y plane, Pillow's draft("L")) -- none is silently dropped.
+    draft (decoder="libjpeg" with size=, whole images): Pillow's Image.draft() in front of the resize.  draft=True requests `size` itself,
+    draft=(h, w) any other size; each file is decoded at the scale Pillow would choose for that request (exact_draft_scale: the largest of
+    1/8, 1/4, 1/2, 1 that keeps both sides at or above it) by libjpeg's reduced-size IDCTs (jda_exact_decode_surfaces_scaled) and resized
+    from there, so that the tensor is Pillow's draft() -> convert("RGB") -> resize() bit for bit.  With decoder="reference", with crops= or
+    without size= it is a ValueError."""
     files = list(files)
     if decoder not in ("reference", "libjpeg"):
         raise ValueError("decoder: 'reference' or 'libjpeg'")
+    if draft is not None and draft is not False:
+        if decoder != "libjpeg" or size is None or crops is not None:
+            raise ValueError("draft goes with decoder='libjpeg' and size=(H, W), whole images only")
+        if draft is not True:
+            draft = tuple(int(v) for v in draft)
+            if len(draft) != 2 or draft[0] <= 0 or draft[1] <= 0:
+                raise ValueError("draft: True or (h, w), both positive")
+    else:
+        draft = None
     if decoder == "libjpeg" and (prescale or options & (B.SCALE_HALF | B.SCALE_QUARTER | B.SCALE_EIGHTH)):
-        raise ValueError("decoder='libjpeg' decodes at full size: no prescale, no JDA_SCALE_* bit in options")
+        raise ValueError("decoder='libjpeg': no prescale, no JDA_SCALE_* bit in options (the reference road's scales); libjpeg's scaled decode is draft=")
     if decoder == "libjpeg" and options & ~B.LUMA_ONLY:
         raise ValueError("decoder='libjpeg': the only option bit it honours is JDA_LUMA_ONLY (the Y plane)")
     if progressive not in ("thumbnail", "full"):
@@ -233,6 +249,13 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     full = [(progressive == "full" or decoder == "libjpeg") and i.jpeg_type == 1 for i in infos]
     opts = [options | B.PROGRESSIVE_FULL if fl else options | (prescale_option(i, pt, options, size) if prescale else 0) for i, fl in zip(infos, full)]
     geos = [B.output_geometry(i, pt, o) for i, o in zip(infos, opts)]
+    scales = None
+    if draft is not None:                                               # (the surfaces are then the scaled images, nothing around them)
+        req = size if draft is True else draft
+        scales = [B.exact_draft_scale(i, (req[1], req[0])) for i in infos]
+        for k, (i, s) in enumerate(zip(infos, scales)):
+            w, h = -(-i.width // s), -(-i.height // s)
+            geos[k] = dict(geos[k], canvas_w=w, canvas_h=h, out_w=w, out_h=h)
     bpp = geos[0]["bpp"]
     pitches = [(g["canvas_w"] * bpp + 15) & ~15 for g in geos]
     offs, total = [], 0
@@ -269,7 +292,7 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
             rbase = ctx.malloc(rbytes * n)
         outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
         if decoder == "libjpeg":
-            status = _exact_batch(ctx, files, infos, outs, pt)
+            status = _exact_batch(ctx, files, infos, outs, pt, scales)
         else:
             pipe = B.Pipeline(ctx, max_images=n, depth=1)
             try:

@@ -9,6 +9,9 @@ form JDA_COEF_AUTO picks.  Warm-up rounds first, every figure the median of --re
   stages          the same call through jda_internal_exact_time, its launches between events of their own: planes, colour;
   batch_decode    jda_batch_decode of the baseline images to the same surfaces (the launch plan made before the first event).
 By bytes the exact road moves about 7 B a pixel (planes written 1.5, read 1.5, RGB8888 written 4) where the decode kernel writes 4.
+--scale 2,4,8: the scaled decode instead -- jda_exact_decode_surfaces_scaled of the same resident images at each scale named
+and at scale 1, all in the same rounds: the call, and its planes / colour launches through jda_internal_exact_time_scaled; no batch_decode
+leg.  profiles/exact_scaled_bench.json is the place for that run.
 Nothing here is a gate.
 One JSON line on stdout and, with --out FILE (profiles/exact_bench.json is the place for a run on an MI355X), in a file.  Fails without a GPU."""
 import argparse
@@ -38,12 +41,49 @@ def files(w, h):
     return out
 
 
+def scaled(ctx, J, a, n, w, h, images, coefs, outs, res):
+    """--scale: every scale of a.scale and scale 1 in the same rounds, per road: the call and its two stages"""
+    from jpegdec_amd.binding import Output, RecodeSource
+    lib = ctx.lib
+    lib.jda_internal_exact_time_scaled.restype = C.c_int
+    lib.jda_internal_exact_time_scaled.argtypes = [C.c_void_p, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    so = (Output * n)(*[Output(*o) for o in outs])
+    st = (C.c_int32 * n)()
+    roads = {"baseline": (images, (RecodeSource * n)(*[RecodeSource(im.handle, None) for im in images])),
+             "coefficients": (coefs, (RecodeSource * n)(*[RecodeSource(None, d.handle) for d in coefs]))}
+    scales = [1] + [s for s in a.scale if s != 1]
+    call = {(k, s): [] for k in roads for s in scales}
+    stages = {(k, s): [] for k in roads for s in scales}
+    for r in range(a.warmup + a.repeat):
+        for name, (items, rs) in roads.items():
+            for s in scales:
+                ctx.timer_start()
+                status = J.exact_decode(ctx, items, outs, None, [s] * n)
+                ctx.timer_stop()
+                assert not any(status), status[:4]
+                t_call = ctx.timer_elapsed_ms()
+                ms = (C.c_float * 2)()
+                ctx.check(lib.jda_internal_exact_time_scaled(ctx.handle, n, rs, so, None, (C.c_int32 * n)(*[s] * n), st, ms), "jda_internal_exact_time_scaled")
+                assert not any(st)
+                if r >= a.warmup:
+                    call[name, s].append(t_call)
+                    stages[name, s].append(list(ms))
+    for name in roads:
+        res[name] = {}
+        for s in scales:
+            row = {"exact_call": stats(call[name, s]), "stages": {k: stats([x[i] for x in stages[name, s]]) for i, k in enumerate(("planes", "colour"))}}
+            row["call_over_scale_1"] = round(statistics.median(call[name, s]) / statistics.median(call[name, 1]), 3)
+            res[name]["scale_%d" % s] = row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--scale", type=lambda v: [int(x) for x in v.split(",")], help="e.g. 2,4,8: the scaled decode at these scales beside scale 1")
     ap.add_argument("--out")
     a = ap.parse_args()
     import jpegdec_amd as J
@@ -63,6 +103,15 @@ def main():
            "coef_form": "sparse" if coefs[0].form == J.COEF_SPARSE else "dense"}
     try:
         outs = [(canvases + k * surf, pitch, g["canvas_w"], g["canvas_h"]) for k in range(n)]
+        if a.scale:
+            res["scales"] = a.scale
+            scaled(ctx, J, a, n, w, h, images, coefs, outs, res)
+            line = json.dumps(res)
+            print(line)
+            if a.out:
+                with open(a.out, "w") as f:
+                    f.write(line + "\n")
+            return
         batch = J.Batch(ctx, images, outs, [J.RGB8888] * n, [0] * n)
         lib = ctx.lib
         lib.jda_internal_exact_time.restype = C.c_int
