@@ -898,6 +898,72 @@ int jda_exact_decode_planes_scaled(jda_ctx *ctx, int32_t n, const jda_recode_sou
 int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, void *host_pixels, int32_t pitch_bytes,
                                     int32_t rows);
 
+/* ------------------------------------------------------------------ libjpeg-exact decode: the file's colour model
+ * libjpeg does not read every three-component file as YCbCr.  jdapimin.c's rule, as jda_exact_probe resolves it:
+ *   1 component                                                   JDA_CS_GRAY
+ *   3 components, a JFIF APP0 segment (it beats an Adobe one)     JDA_CS_YCBCR
+ *   3, no JFIF, Adobe APP14 with transform 0                      JDA_CS_RGB     the components ARE R, G, B
+ *   3, no JFIF, Adobe with transform 1 or anything else           JDA_CS_YCBCR
+ *   3, neither marker, component ids 'R', 'G', 'B'                JDA_CS_RGB
+ *   3, neither marker, any other ids                              JDA_CS_YCBCR
+ *   4, Adobe transform 0, or no Adobe segment                     JDA_CS_CMYK
+ *   4, Adobe transform 2 or anything else                         JDA_CS_YCCK
+ * jda_exact_probe: header in, the model out -- with the number of components, the layout of components 0..2 (layout: 0 gray, 1 4:4:4,
+ * 2 4:2:0, 3 4:2:2, 4 4:4:0, -1 none of them), the sampling byte of component 3 (k_sampling, 0 without one), the size and the SOF
+ * type (jpeg_type: 0 sequential, 1 progressive), and what the rule read.  Four components are taken with components 1 and 2 at 1x1,
+ * component 0 at 1x1, 2x1, 1x2 or 2x2 and component 3 at 1x1 or at component 0's factors (Pillow's own CMYK files: 22,11,11,11;
+ * Photoshop's YCCK: 22,11,11,22).  Returns jda_parse's code for a header it refuses (an SOF1 frame is let through), and
+ * JDA_UNSUPPORTED_FEATURE, the fields filled and decodable 0, for a layout the decode calls below do not take.
+ * jda_coef_prepare: every scan of a Huffman-coded 8-bit file on the host -- SOF0 / SOF1 (whole blocks) or SOF2 (jda_progressive_prepare's
+ * decoder), interleaved scans or one a component, restart intervals -- into a coefficient image.  One or three components: the image
+ * jda_progressive_prepare makes of a progressive file.  Four: the handle holds components 0..2 exactly as a three-component image of their
+ * layout (jda_coef_image_coefficients, n_blocks) and component 3 as a gray coefficient image over its own MCU-padded block grid, row-major
+ * (jda_coef_image_component3: the parent's, freed with it; NULL for every other image); jda_coef_image_get_info says ncomp 4, and every
+ * consumer of coefficient images but the calls below answers JDA_UNSUPPORTED_FEATURE for it: jda_coef_decode_surfaces*, the recode calls,
+ * the exact calls without the flag; jda_coef_image_sparse gives none (dense only: JDA_COEF_AUTO picks dense, JDA_COEF_SPARSE is refused).
+ * jda_exact_decode_surfaces_ex / _planes_ex: jda_exact_decode_surfaces_scaled / _planes_scaled with flags.  flags 0: those calls to the byte,
+ * every refusal included.  JDA_EXACT_COLOUR_MODELS: the file's model decides.  A YCbCr file with an Adobe segment (Photoshop's transform 1,
+ * JFIF + Adobe) goes through the kernels of the plain calls.  An RGB-coded one through jda_exact_colour_rgb / jda_exact_colour_scaled_rgb,
+ * which write the three upsampled planes as R, G, B (fancy upsampling applies to components 1 and 2 as to chroma), A = 0xFF, at every
+ * scale.  A four-component one (a dense coefficient image of jda_coef_prepare, scale 1) through jda_exact_colour4: every component through
+ * the islow IDCT with its own raw quantiser and fancy upsampling over its own extent, then Pillow's reading of it ("CMYK;I": a CMYK file's
+ * samples s as 255 - s; a YCCK file's components 0..2 through jdcolor.c's YCbCr -> RGB, the bytes R, G, B, 255 - s3), written as
+ * JDA_CMYK8888 -- those four bytes, np.asarray(Image.open(f)) -- or as JDA_RGB8888 -- Pillow's convert("RGB") of them: nk = 255 - K,
+ * clip8(nk - muldiv255(C, nk)), muldiv255(a, b) = ((t >> 8) + t) >> 8 with t = a b + 128; A = 0xFF.  In these stages a component at most
+ * two samples wide is replicated, not interpolated, as jdsample.c does.  Per image, JDA_UNSUPPORTED_FEATURE: JDA_EIGHT_BIT_GRAYSCALE of a
+ * four-component or RGB-coded source; a four-component source at a scale other than 1, as a sparse or a baseline image, or of another
+ * layout; JDA_INVALID_PARAMETER: JDA_CMYK8888 for another source or without the flag.  Launches: as the scaled calls -- one of
+ * jda_exact_planes[_scaled] per (layout, source kind, scale) present, a four-component image's K tiles counted under gray --, then one
+ * colour launch per (layout, scale) for the gray / YCbCr images, one for the RGB-coded ones, and one of jda_exact_colour4 per layout;
+ * a call that refuses everything launches nothing and writes nothing.  The planes call takes planes[4 i + c] with the flag (three entries
+ * an image without it): c = 3 a four-component image's K -- libjpeg's raw-data output, un-inverted, each at its own extent.
+ * jda_decode_to_host_exact_ex: jda_decode_to_host_exact_scaled with those flags; a four-component file of any SOF type goes through
+ * jda_coef_prepare + jda_coef_upload_ex, a progressive file as ever through jda_progressive_prepare, everything else through the resident
+ * baseline image. */
+enum { JDA_CS_GRAY = 0, JDA_CS_YCBCR = 1, JDA_CS_RGB = 2, JDA_CS_CMYK = 3, JDA_CS_YCCK = 4 };
+enum { JDA_EXACT_COLOUR_MODELS = 1 };
+enum { JDA_CMYK8888 = 16 };     /* a pixel type of the _ex calls with the flag, for four-component sources: bytes C, M, Y, K as Pillow's mode "CMYK" */
+jda_coef_image *jda_coef_prepare(const uint8_t *jpeg, int32_t len, int32_t *err);
+const jda_coef_image *jda_coef_image_component3(const jda_coef_image *img);
+typedef struct jda_exact_file {
+    int32_t colour_model;       /* JDA_CS_* */
+    int32_t ncomp;
+    int32_t layout;             /* of components 0..2 */
+    int32_t k_sampling;         /* component 3's sampling byte (0x11, 0x22, ..), 0 without one */
+    int32_t width, height;
+    int32_t jpeg_type;          /* 0 baseline, 1 progressive */
+    int32_t decodable;          /* the _ex calls take it with JDA_EXACT_COLOUR_MODELS */
+    int32_t jfif, adobe, adobe_transform;   /* what the rule read: APP0 JFIF seen, APP14 Adobe seen, its transform byte (-1 without one) */
+    int32_t component_id[4];
+} jda_exact_file;
+int jda_exact_probe(const uint8_t *jpeg, int32_t len, jda_exact_file *out);
+int jda_exact_decode_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *sources, const jda_output *outputs, const int32_t *pixel_types,
+                                 const int32_t *scales, uint32_t flags, int32_t *status);
+int jda_exact_decode_planes_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *sources, const jda_output *planes, const int32_t *scales, uint32_t flags,
+                               int32_t *status);
+int jda_decode_to_host_exact_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, void *host_pixels,
+                                int32_t pitch_bytes, int32_t rows);
+
 const char *jda_version(void);
 
 #ifdef __cplusplus

@@ -231,6 +231,12 @@ _PROTOTYPES = [
     ("jda_exact_decode_surfaces_scaled", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("jda_exact_decode_planes_scaled", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("jda_decode_to_host_exact_scaled", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
+    ("jda_exact_probe", C.c_int, [C.c_char_p, C.c_int32, _P]),
+    ("jda_coef_prepare", _P, [C.c_char_p, C.c_int32, C.POINTER(C.c_int32)]),
+    ("jda_coef_image_component3", _P, [_P]),
+    ("jda_exact_decode_surfaces_ex", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32)]),
+    ("jda_exact_decode_planes_ex", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32)]),
+    ("jda_decode_to_host_exact_ex", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P, C.c_int32, C.c_int32]),
 ]
 
 
@@ -728,17 +734,37 @@ class CoefImage:
     """A coefficient image (host): every scan of a progressive file decoded by jda_progressive_prepare, or -- coefs given -- the
     caller's own coefficients under the headers of any supported file (jda_coef_image_from_coefficients).  coefs: int16,
     (blocks, 64), natural order, blocks in MCU-interleaved scan order."""
-    def __init__(self, jpeg: bytes, coefs=None):
+    def __init__(self, jpeg: bytes, coefs=None, any_file=False):
         self.lib = load_library()
+        self.owned = True
         err = C.c_int32(0)
-        if coefs is None:
+        if any_file:
+            self.handle = self.lib.jda_coef_prepare(jpeg, len(jpeg), C.byref(err))
+        elif coefs is None:
             self.handle = self.lib.jda_progressive_prepare(jpeg, len(jpeg), C.byref(err))
         else:
             a = np.ascontiguousarray(coefs, dtype=np.int16).reshape(-1, 64)
             self.handle = self.lib.jda_coef_image_from_coefficients(jpeg, len(jpeg), a.ctypes.data_as(_P), a.shape[0], C.byref(err))
         if not self.handle:
-            raise JdaError(err.value, "jda_progressive_prepare" if coefs is None else "jda_coef_image_from_coefficients")
+            raise JdaError(err.value, "jda_coef_prepare" if any_file else "jda_progressive_prepare" if coefs is None else "jda_coef_image_from_coefficients")
         self.info = self.lib.jda_coef_image_get_info(self.handle).contents
+
+    @classmethod
+    def from_file(cls, jpeg: bytes):
+        """jda_coef_prepare: every scan of a Huffman-coded 8-bit file of one, three or four components, sequential or progressive.  A
+        four-component image holds components 0..2 as a three-component image (coefficients(), info.ncomp == 4) and component 3 as
+        component3(), a gray image; only the exact decode with colour_models=True takes it."""
+        return cls(jpeg, any_file=True)
+
+    def component3(self):
+        """component 3 of a four-component image as the gray coefficient image it is stored as (a view: it lives as long as this one), or None"""
+        h = self.lib.jda_coef_image_component3(self.handle)
+        if not h:
+            return None
+        k = object.__new__(CoefImage)
+        k.lib, k.handle, k.owned, k.parent = self.lib, h, False, self
+        k.info = self.lib.jda_coef_image_get_info(h).contents
+        return k
 
     def coefficients(self) -> np.ndarray:
         n = C.c_uint32(0)
@@ -777,7 +803,8 @@ class CoefImage:
 
     def close(self):
         if self.handle:
-            self.lib.jda_coef_image_free(self.handle)
+            if self.owned:
+                self.lib.jda_coef_image_free(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -1259,17 +1286,49 @@ def _recode_sources(sources):
     return (RecodeSource * max(n, 1))(*[RecodeSource(q.handle, None) if isinstance(q, DeviceImage) else RecodeSource(None, q.handle) for q in sources])
 
 
-def exact_decode(ctx: Context, sources, outputs, pixel_types=None, scales=None):
+# the colour models of jda_exact_probe (jdapimin.c's rule) and the flag of the _ex calls that makes them decide
+CMYK8888 = 16                                     # JDA_CMYK8888: Pillow's mode-"CMYK" bytes of a four-component source (the exact decode with colour_models=True)
+CS_GRAY, CS_YCBCR, CS_RGB, CS_CMYK, CS_YCCK = 0, 1, 2, 3, 4
+CS_NAMES = {CS_GRAY: "gray", CS_YCBCR: "ycbcr", CS_RGB: "rgb", CS_CMYK: "cmyk", CS_YCCK: "ycck"}
+EXACT_COLOUR_MODELS = 1
+
+
+class ExactFile(C.Structure):
+    _fields_ = [("colour_model", C.c_int32), ("ncomp", C.c_int32), ("layout", C.c_int32), ("k_sampling", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("jpeg_type", C.c_int32), ("decodable", C.c_int32), ("jfif", C.c_int32), ("adobe", C.c_int32), ("adobe_transform", C.c_int32),
+                ("component_id", C.c_int32 * 4)]
+
+
+def exact_probe(jpeg: bytes):
+    """jda_exact_probe: how libjpeg reads the file's components -- {"colour_model": CS_*, "model": its name, "ncomp", "layout" (0 gray, 1 4:4:4,
+    2 4:2:0, 3 4:2:2, 4 4:4:0, -1 another), "k_sampling", "width", "height", "progressive", "decodable" (by the exact calls with
+    colour_models=True), "jfif", "adobe", "adobe_transform", "component_ids"}; a header jda_parse refuses raises JdaError."""
+    f = ExactFile()
+    rc = load_library().jda_exact_probe(jpeg, len(jpeg), C.byref(f))
+    if rc != 0 and (rc != 3 or f.colour_model < 0):          # (JDA_UNSUPPORTED_FEATURE behind a header that parsed: the fields stand, decodable is False)
+        raise JdaError(rc, "jda_exact_probe")
+    return dict(colour_model=f.colour_model, model=CS_NAMES.get(f.colour_model), ncomp=f.ncomp, layout=f.layout, k_sampling=f.k_sampling, width=f.width,
+                height=f.height, progressive=bool(f.jpeg_type), decodable=bool(f.decodable), jfif=bool(f.jfif), adobe=bool(f.adobe),
+                adobe_transform=f.adobe_transform, component_ids=list(f.component_id)[:f.ncomp])
+
+
+def exact_decode(ctx: Context, sources, outputs, pixel_types=None, scales=None, colour_models=False):
     """jda_exact_decode_surfaces: the libjpeg-exact decode (Pillow's pixels, not the reference's) of resident sources -- DeviceImage (a
     baseline file) or DeviceCoef (dense or sparse) each -- into surfaces.  outputs = (device pointer, pitch, width_px, rows) each;
     pixel_types: RGB8888 (the default) or GRAY8 each.  Exactly min(width, width_px) x min(height, rows) pixels of an image are written.
     scales (jda_exact_decode_surfaces_scaled): 1, 2, 4 or 8 each -- libjpeg's scaled decode, Pillow's draft(); the image is then
-    ceil(width / s) x ceil(height / s).  -> the statuses; the call's own refusals raise JdaError."""
+    ceil(width / s) x ceil(height / s).  colour_models (jda_exact_decode_surfaces_ex with JDA_EXACT_COLOUR_MODELS): a file with an Adobe
+    segment is taken, an RGB-coded one (exact_probe) is written as R, G, B, and a four-component DeviceCoef of CoefImage.from_file (CMYK,
+    YCCK; scale 1) as Pillow's convert("RGB") of it, or, pixel type CMYK8888, as Pillow's mode-"CMYK" bytes.  -> the statuses; the call's
+    own refusals raise JdaError."""
     n = len(sources)
     o = (Output * max(n, 1))(*[Output(*q) for q in outputs])
     pt = None if pixel_types is None else (C.c_int32 * max(n, 1))(*pixel_types)
     status = (C.c_int32 * max(n, 1))()
-    if scales is None:
+    if colour_models:
+        sc = None if scales is None else (C.c_int32 * max(n, 1))(*scales)
+        ctx.check(ctx.lib.jda_exact_decode_surfaces_ex(ctx.handle, n, _recode_sources(sources), o, pt, sc, EXACT_COLOUR_MODELS, status), "jda_exact_decode_surfaces_ex")
+    elif scales is None:
         ctx.check(ctx.lib.jda_exact_decode_surfaces(ctx.handle, n, _recode_sources(sources), o, pt, status), "jda_exact_decode_surfaces")
     else:
         sc = (C.c_int32 * max(n, 1))(*scales)
@@ -1277,13 +1336,21 @@ def exact_decode(ctx: Context, sources, outputs, pixel_types=None, scales=None):
     return list(status)[:n]
 
 
-def exact_planes(ctx: Context, sources, planes, scales=None):
+def exact_planes(ctx: Context, sources, planes, scales=None, colour_models=False):
     """jda_exact_decode_planes: the 8-bit component planes at their own extents (libjpeg's raw-data output).  planes = per source three
     (device pointer, pitch, width, rows) -- Y, Cb, Cr; a gray image's last two are not looked at.  scales (jda_exact_decode_planes_scaled):
-    1, 2, 4 or 8 each, the extents then exact_scaled_geometry's.  -> the statuses."""
+    1, 2, 4 or 8 each, the extents then exact_scaled_geometry's.  colour_models (jda_exact_decode_planes_ex): as exact_decode's -- an RGB-coded
+    file's planes are R, G, B, and a four-component source takes FOUR entries (the fourth: K at its own extent, un-inverted; the call's
+    array holds four an image, a shorter list here is padded).  -> the statuses."""
     n = len(sources)
-    flat = [Output(*q) for three in planes for q in three]
     status = (C.c_int32 * max(n, 1))()
+    if colour_models:                                        # (four entries a source: a three-tuple is padded with an entry nobody looks at)
+        flat = [Output(*q) for some in planes for q in (list(some) + [(None, 0, 0, 0)])[:4]]
+        sc = None if scales is None else (C.c_int32 * max(n, 1))(*scales)
+        ctx.check(ctx.lib.jda_exact_decode_planes_ex(ctx.handle, n, _recode_sources(sources), (Output * max(4 * n, 1))(*flat), sc, EXACT_COLOUR_MODELS, status),
+                  "jda_exact_decode_planes_ex")
+        return list(status)[:n]
+    flat = [Output(*q) for three in planes for q in three]
     if scales is None:
         ctx.check(ctx.lib.jda_exact_decode_planes(ctx.handle, n, _recode_sources(sources), (Output * max(3 * n, 1))(*flat), status), "jda_exact_decode_planes")
     else:
@@ -1319,14 +1386,22 @@ def exact_draft_scale(jpeg_or_info, size):
     return load_library().jda_exact_draft_scale(C.byref(info), int(size[0]), int(size[1]))
 
 
-def decode_to_host_exact(ctx: Context, jpeg: bytes, pixel_type=RGB8888, scale=1):
+def decode_to_host_exact(ctx: Context, jpeg: bytes, pixel_type=RGB8888, scale=1, colour_models=False):
     """jda_decode_to_host_exact[_scaled]: one file, baseline or progressive, to the pixels Pillow gives (at scale 2, 4, 8: after
-    draft()) -- (rc, height x width x 4 RGBA bytes or height x width gray)."""
+    draft()) -- (rc, height x width x 4 RGBA bytes or height x width gray).  colour_models (jda_decode_to_host_exact_ex): as exact_decode's."""
+    bpp = 4 if pixel_type in (RGB8888, CMYK8888) else 1
+    if colour_models:
+        p = exact_probe(jpeg)                                     # (jda_parse refuses an extended-sequential frame, which this road takes)
+        s = scale if scale in (1, 2, 4, 8) else 1
+        w, h = -(-p["width"] // s), -(-p["height"] // s)
+        canvas = np.zeros((h, w * bpp), dtype=np.uint8)
+        rc = ctx.lib.jda_decode_to_host_exact_ex(ctx.handle, jpeg, len(jpeg), pixel_type, scale, EXACT_COLOUR_MODELS, canvas.ctypes.data_as(_P), canvas.shape[1],
+                                                 canvas.shape[0])
+        return rc, (canvas.reshape(h, w, 4) if bpp == 4 else canvas)
     info = ImageInfo()
     rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
     if rc != 0:
         raise JdaError(rc, "jda_parse")
-    bpp = 4 if pixel_type == RGB8888 else 1
     if scale == 1:
         canvas = np.zeros((info.height, info.width * bpp), dtype=np.uint8)
         rc = ctx.lib.jda_decode_to_host_exact(ctx.handle, jpeg, len(jpeg), pixel_type, canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0])

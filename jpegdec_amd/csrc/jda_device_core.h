@@ -5303,8 +5303,26 @@ template <int MODE, class IO> JDA_HD void jda_ex_chroma4(IO &io, const jda_ex_de
         out[2] = (3u * t[2] + t[1] + 1u) >> 2; out[3] = (3u * t[2] + t[3] + 2u) >> 2;
     }
 }
-// lane = the output pixels x0 .. x0 + 3 of row y: nothing outside out_w x out_rows is written
-template <int MODE, class IO> JDA_HD void jda_ex_quad(IO &io, const jda_ex_desc &X, uint32_t x0, uint32_t y)
+// jdsample.c takes the fancy h2v1 / h2v2 upsamplers only for a component MORE than two samples wide (downsampled_width > 2): a narrower one
+// -- an image of at most four pixels across -- is replicated, both ways.  What the colour stages of DESIGN.md 5.19 call in the place of
+// jda_ex_chroma4 (jda_exact_colour itself keeps calling that one: its instances stay the code they were).
+template <int MODE, class IO> JDA_HD void jda_ex_chroma4_any(IO &io, const jda_ex_desc &X, const uint8_t *plane, uint32_t x0, uint32_t y, uint32_t *out)
+{
+    typedef jda_ex_layout<MODE> E;
+    if (E::HS == 2 && X.cw <= 2u) {                          // (wave-uniform)
+        const uint32_t row = (E::VS == 2 ? y >> 1 : y) * X.pitch_c, last = X.cw - 1u;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t i = (x0 + k) >> 1;
+            out[k] = io.ld8(plane, row + (i < last ? i : last));
+        }
+        return;
+    }
+    jda_ex_chroma4<MODE>(io, X, plane, x0, y, out);
+}
+// lane = the output pixels x0 .. x0 + 3 of row y: nothing outside out_w x out_rows is written.  RGB: the file's three
+// components ARE R, G, B (jdapimin.c's rule, jda_colour_model): the upsampled samples go out as they stand, no conversion
+template <int MODE, bool RGB = false, class IO> JDA_HD void jda_ex_quad(IO &io, const jda_ex_desc &X, uint32_t x0, uint32_t y)
 {
     if (y >= X.out_rows || x0 >= X.out_w) return;
     const uint32_t n = X.out_w - x0 < 4u ? X.out_w - x0 : 4u;
@@ -5316,18 +5334,22 @@ template <int MODE, class IO> JDA_HD void jda_ex_quad(IO &io, const jda_ex_desc 
         return;
     }
     uint32_t cb[4] = { 128u, 128u, 128u, 128u }, cr[4] = { 128u, 128u, 128u, 128u }, px[4];
-    if (MODE != JDA_MODE_GRAY) {
+    if (MODE != JDA_MODE_GRAY && RGB) {
+        jda_ex_chroma4_any<MODE>(io, X, X.plane[1], x0, y, cb);
+        jda_ex_chroma4_any<MODE>(io, X, X.plane[2], x0, y, cr);
+    } else if (MODE != JDA_MODE_GRAY) {
         jda_ex_chroma4<MODE>(io, X, X.plane[1], x0, y, cb);
         jda_ex_chroma4<MODE>(io, X, X.plane[2], x0, y, cr);
     }
 #pragma unroll
-    for (uint32_t k = 0; k < 4u; k++) px[k] = jda_ex_rgba((yw >> (8u * k)) & 255u, cb[k], cr[k]);
+    for (uint32_t k = 0; k < 4u; k++)
+        px[k] = RGB ? ((yw >> (8u * k)) & 255u) | (cb[k] << 8) | (cr[k] << 16) | 0xff000000u : jda_ex_rgba((yw >> (8u * k)) & 255u, cb[k], cr[k]);
     const uint32_t o = y * X.out_pitch + x0 * 4u;
     if (n == 4u) io.st128(X.out, o, px);
     else for (uint32_t k = 0; k < n; k++) io.st32(X.out, o + 4u * k, px[k]);
 }
 // a wavefront = a tile record: count MCUs of MCU row mcu_y from MCU mcu_x0
-template <int MODE, class IO> JDA_HD void jda_ex_colour_tile(IO &io, const jda_ex_desc &X, const jda_strip &S, uint32_t lane)
+template <int MODE, bool RGB = false, class IO> JDA_HD void jda_ex_colour_tile(IO &io, const jda_ex_desc &X, const jda_strip &S, uint32_t lane)
 {
     typedef jda_mode_traits<MODE> T;
     const uint32_t quads = (uint32_t)S.count * ((uint32_t)T::MCU_W / 4u), items = quads * (uint32_t)T::MCU_H;
@@ -5335,7 +5357,71 @@ template <int MODE, class IO> JDA_HD void jda_ex_colour_tile(IO &io, const jda_e
     if (py0 >= X.out_rows || px0 >= X.out_w) return;         // (wave-uniform)
     for (uint32_t it = lane; it < items; it += 64u) {
         const uint32_t r = it / quads, q = it - r * quads;
-        jda_ex_quad<MODE>(io, X, px0 + 4u * q, py0 + r);
+        jda_ex_quad<MODE, RGB>(io, X, px0 + 4u * q, py0 + r);
+    }
+}
+
+// jda_ex4_*: the colour stage of a four-component image (CMYK or YCCK).  The planes stage has left four planes: components
+// 0..2 as a three-component image of layout MODE, component 3 ("K") decoded as a gray image into X.plane3 -- at component 0's sampling
+// (JDA_EX4_K_FULL: pitch_y, w x h) or at 1x1 (a chroma plane's pitch and extent).  lane = four output pixels of a row = one 16-byte store,
+// over jda_ex_colour_tile's tile records and clip: component 0 and a full-size K as a dword each, every 1x1 component through
+// jda_ex_chroma4_any<MODE> (fancy upsampling over its own extent, the MCU padding never read).  Then the model -- Pillow reads every
+// four-component file as "CMYK;I", each byte of libjpeg's output inverted: a CMYK file's samples s give 255 - s; of a YCCK file libjpeg
+// makes 255 - R, 255 - G, 255 - B (jdcolor.c's conversion, jda_ex_rgba) and passes K, so the bytes are R, G, B, 255 - s3 -- and the
+// pixel type: those four bytes (JDA_CMYK8888), or Pillow's convert("RGB") of them, A = 0xFF.
+// Pillow's MULDIV255 (ImagingUtils.h): a * b / 255, rounded
+JDA_HD uint32_t jda_ex4_muldiv255(uint32_t a, uint32_t b)
+{
+    const uint32_t t = a * b + 128u;
+    return ((t >> 8) + t) >> 8;
+}
+// Convert.c's cmyk2rgb on the bytes (C, M, Y, K) packed as a dword, C lowest: nk = 255 - K, clip8(nk - muldiv255(C, nk)), ..
+JDA_HD uint32_t jda_ex4_cmyk2rgb(uint32_t cmyk)
+{
+    const int32_t nk = 255 - (int32_t)(cmyk >> 24);
+    uint32_t px = 0xff000000u;
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; c++) {
+        int32_t v = nk - (int32_t)jda_ex4_muldiv255((cmyk >> (8u * c)) & 255u, (uint32_t)nk);
+        v = v < 0 ? 0 : v > 255 ? 255 : v;
+        px |= (uint32_t)v << (8u * c);
+    }
+    return px;
+}
+template <int MODE, class IO> JDA_HD void jda_ex4_quad(IO &io, const jda_ex_desc &X, uint32_t x0, uint32_t y)
+{
+    if (y >= X.out_rows || x0 >= X.out_w) return;
+    const uint32_t n = X.out_w - x0 < 4u ? X.out_w - x0 : 4u;
+    const uint32_t s0 = io.ld32(X.plane[0], y * X.pitch_y + x0);
+    uint32_t s1[4], s2[4], k[4], px[4];
+    jda_ex_chroma4_any<MODE>(io, X, X.plane[1], x0, y, s1);
+    jda_ex_chroma4_any<MODE>(io, X, X.plane[2], x0, y, s2);
+    if (MODE == JDA_MODE_444 || (X.cs4 & JDA_EX4_K_FULL)) {                // (wave-uniform)
+        const uint32_t kw = io.ld32(X.plane3, y * X.pitch_y + x0);
+#pragma unroll
+        for (uint32_t i = 0; i < 4u; i++) k[i] = (kw >> (8u * i)) & 255u;
+    } else jda_ex_chroma4_any<MODE>(io, X, X.plane3, x0, y, k);
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; i++) {
+        const uint32_t a = (s0 >> (8u * i)) & 255u;
+        const uint32_t cmy = (X.cs4 & JDA_EX4_YCCK) ? jda_ex_rgba(a, s1[i], s2[i]) & 0xffffffu : (255u - a) | ((255u - s1[i]) << 8) | ((255u - s2[i]) << 16);
+        const uint32_t cmyk = cmy | ((255u - k[i]) << 24);
+        px[i] = (X.cs4 & JDA_EX4_CMYK_OUT) ? cmyk : jda_ex4_cmyk2rgb(cmyk);
+    }
+    const uint32_t o = y * X.out_pitch + x0 * 4u;
+    if (n == 4u) io.st128(X.out, o, px);
+    else for (uint32_t i = 0; i < n; i++) io.st32(X.out, o + 4u * i, px[i]);
+}
+// a wavefront = a tile record of the image's components 0..2: count MCUs of MCU row mcu_y from MCU mcu_x0 (jda_ex_colour_tile's walk)
+template <int MODE, class IO> JDA_HD void jda_ex4_colour_tile(IO &io, const jda_ex_desc &X, const jda_strip &S, uint32_t lane)
+{
+    typedef jda_mode_traits<MODE> T;
+    const uint32_t quads = (uint32_t)S.count * ((uint32_t)T::MCU_W / 4u), items = quads * (uint32_t)T::MCU_H;
+    const uint32_t px0 = (uint32_t)S.mcu_x0 * (uint32_t)T::MCU_W, py0 = (uint32_t)S.mcu_y * (uint32_t)T::MCU_H;
+    if (py0 >= X.out_rows || px0 >= X.out_w) return;         // (wave-uniform)
+    for (uint32_t it = lane; it < items; it += 64u) {
+        const uint32_t r = it / quads, q = it - r * quads;
+        jda_ex4_quad<MODE>(io, X, px0 + 4u * q, py0 + r);
     }
 }
 
@@ -5634,7 +5720,8 @@ template <class IO> JDA_HD void jda_exs_chroma4(IO &io, const jda_ex_desc &X, co
     out[2] = (3u * t[2] + t[1] + 1u) >> 2; out[3] = (3u * t[2] + t[3] + 2u) >> 2;
 }
 // lane = the output pixels x0 + lo .. x0 + hi - 1 of row y (x0 a multiple of 4): nothing outside out_w x out_rows is written
-template <int MODE, class IO> JDA_HD void jda_exs_quad(IO &io, const jda_ex_desc &X, uint32_t x0, uint32_t y, uint32_t lo, uint32_t hi)
+// (RGB: as jda_ex_quad's)
+template <int MODE, bool RGB = false, class IO> JDA_HD void jda_exs_quad(IO &io, const jda_ex_desc &X, uint32_t x0, uint32_t y, uint32_t lo, uint32_t hi)
 {
     if (y >= X.out_rows || x0 + lo >= X.out_w) return;
     if (X.out_w - x0 < hi) hi = X.out_w - x0;
@@ -5654,7 +5741,8 @@ template <int MODE, class IO> JDA_HD void jda_exs_quad(IO &io, const jda_ex_desc
         jda_exs_chroma4(io, X, X.plane[2], x0, y, cr);
     }
 #pragma unroll
-    for (uint32_t k = 0; k < 4u; k++) px[k] = jda_ex_rgba((yw >> (8u * k)) & 255u, cb[k], cr[k]);
+    for (uint32_t k = 0; k < 4u; k++)
+        px[k] = RGB ? ((yw >> (8u * k)) & 255u) | (cb[k] << 8) | (cr[k] << 16) | 0xff000000u : jda_ex_rgba((yw >> (8u * k)) & 255u, cb[k], cr[k]);
     const uint32_t o = y * X.out_pitch + x0 * 4u;
     if (lo == 0u && hi == 4u) io.st128(X.out, o, px);
     else {
@@ -5663,7 +5751,7 @@ template <int MODE, class IO> JDA_HD void jda_exs_quad(IO &io, const jda_ex_desc
     }
 }
 // a wavefront = a tile record: the pixels of count MCUs of MCU row mcu_y from MCU mcu_x0 at the record's scale (X.scale: 2, 4, 8)
-template <int MODE, class IO> JDA_HD void jda_exs_colour_tile(IO &io, const jda_ex_desc &X, const jda_strip &S, uint32_t lane)
+template <int MODE, bool RGB = false, class IO> JDA_HD void jda_exs_colour_tile(IO &io, const jda_ex_desc &X, const jda_strip &S, uint32_t lane)
 {
     typedef jda_mode_traits<MODE> T;
     const uint32_t sh = X.scale == 8u ? 3u : X.scale == 4u ? 2u : 1u;
@@ -5673,7 +5761,7 @@ template <int MODE, class IO> JDA_HD void jda_exs_colour_tile(IO &io, const jda_
     const uint32_t xa = px0 & ~3u, quads = (px1 - xa + 3u) >> 2, items = quads * mh;
     for (uint32_t it = lane; it < items; it += 64u) {
         const uint32_t r = it / quads, q = it - r * quads, x0 = xa + 4u * q;
-        jda_exs_quad<MODE>(io, X, x0, py0 + r, x0 < px0 ? px0 - x0 : 0u, px1 - x0 < 4u ? px1 - x0 : 4u);
+        jda_exs_quad<MODE, RGB>(io, X, x0, py0 + r, x0 < px0 ? px0 - x0 : 0u, px1 - x0 < 4u ? px1 - x0 : 4u);
     }
 }
 

@@ -23,12 +23,40 @@ inline int jda_exact_check(const jda_image_info &I, int adobe, int pixel_type, i
     return JDA_SUCCESS;
 }
 
+// The same with the file's resolved colour model (JDA_CS_*, jda_colour_model) in the place of the Adobe flag: what the _ex calls take with
+// JDA_EXACT_COLOUR_MODELS.  An Adobe segment refuses nothing by itself; gray and YCbCr go the kernels' way as ever, an
+// RGB-coded file (three components of a colour layout) to an RGB8888 surface only -- its component 0 is red, not luma.  Four components
+// (CMYK, YCCK; I as the file's header has it, k_hv component 3's sampling byte): a coefficient image only, at full size only, components
+// 0..2 of a colour layout, component 3 at 1x1 or at component 0's factors, to an RGB8888 or a CMYK8888 surface.  JDA_CMYK8888 is a
+// pixel type of four-component sources alone.
+inline int jda_exact_check_cs(const jda_image_info &I, int colour, int pixel_type, int baseline_image, uint32_t n_mcus_ok, int scale = 1, int k_hv = 0)
+{
+    if (I.ncomp == 4) {
+        if (pixel_type == JDA_EIGHT_BIT_GRAYSCALE) return JDA_UNSUPPORTED_FEATURE;      // (Pillow's draft("L") does nothing for CMYK)
+        if (pixel_type != JDA_RGB8888 && pixel_type != JDA_CMYK8888) return JDA_INVALID_PARAMETER;
+        if (I.width <= 0 || I.height <= 0 || I.mcus_x <= 0 || I.mcus_y <= 0) return JDA_INVALID_PARAMETER;
+        if (colour != JDA_CS_CMYK && colour != JDA_CS_YCCK) return JDA_UNSUPPORTED_FEATURE;
+        if (baseline_image || jda_mode_of(I) == JDA_MODE_GRAY || (k_hv != 0x11 && k_hv != I.subsample)) return JDA_UNSUPPORTED_FEATURE;
+        if (scale == 2 || scale == 4 || scale == 8) return JDA_UNSUPPORTED_FEATURE;
+        return JDA_SUCCESS;
+    }
+    const int rc = jda_exact_check(I, 0, pixel_type, baseline_image, n_mcus_ok);
+    if (rc != JDA_SUCCESS) return rc;
+    if (I.ncomp == 1 ? colour != JDA_CS_GRAY : (colour != JDA_CS_YCBCR && colour != JDA_CS_RGB)) return JDA_UNSUPPORTED_FEATURE;
+    if (colour == JDA_CS_RGB && (pixel_type == JDA_EIGHT_BIT_GRAYSCALE || jda_mode_of(I) == JDA_MODE_GRAY)) return JDA_UNSUPPORTED_FEATURE;
+    return JDA_SUCCESS;
+}
+
 // The planes of one image: Y over the whole MCU grid, Cb and Cr (a colour file decoded in colour) over theirs, the rows a multiple of
 // 16 bytes apart, each plane's start a multiple of 256 from the image's.  cw x ch: a chroma component's own extent.
 struct jda_exact_geo {
     uint32_t hs, vs, pitch_y, pitch_c, rows_y, rows_c, cw, ch;
     size_t off[3], bytes;
     uint32_t scale, ss_y, ss_c, w, h, up;                    // jda_exact_geometry_scaled's (zeros from jda_exact_geometry)
+    // jda_exact_geometry4's (zeros from the others): component 3's plane -- component 0's pitch, rows and extent where it has its
+    // sampling (k_full), a chroma plane's otherwise
+    size_t off_k;
+    uint32_t k_full, pitch_k, rows_k, kw, kh;
 };
 inline int jda_exact_geometry(const jda_image_info &I, bool luma_only, jda_exact_geo *G)
 {
@@ -70,6 +98,37 @@ inline void jda_exact_fill(jda_ex_desc &X, const jda_image_info &I, const uint16
     }
     for (int c = 0; c < 3; c++)
         for (uint32_t z = 0; z < 64u; z++) X.quant[c][jda_en_zigzag(z)] = quant_zz[c][z];
+}
+
+// ---- four components.  I3: the header with components 0..2 alone (ncomp 3); k_full: component 3 has component 0's sampling.
+// The three planes are jda_exact_geometry's, field for field; component 3's follows them, its start a multiple of 256 like theirs.
+inline int jda_exact_geometry4(const jda_image_info &I3, bool k_full, jda_exact_geo *G)
+{
+    const int rc = jda_exact_geometry(I3, false, G);
+    if (rc != JDA_SUCCESS) return rc;
+    G->scale = 1u; G->ss_y = G->ss_c = 8u; G->w = (uint32_t)I3.width; G->h = (uint32_t)I3.height;
+    G->k_full = k_full || jda_mode_of(I3) == JDA_MODE_444 ? 1u : 0u;
+    G->pitch_k = G->k_full ? G->pitch_y : G->pitch_c;
+    G->rows_k = G->k_full ? G->rows_y : G->rows_c;
+    G->kw = G->k_full ? G->w : G->cw; G->kh = G->k_full ? G->h : G->ch;
+    if ((uint64_t)G->pitch_k * G->rows_k >= (1ull << 32)) return JDA_UNSUPPORTED_FEATURE;
+    G->off_k = G->bytes;
+    G->bytes += ((size_t)G->pitch_k * G->rows_k + 255u) & ~(size_t)255u;
+    return JDA_SUCCESS;
+}
+// The records of a four-component image: X for its components 0..2 (jda_exact_fill's for a three-component image of their layout, with
+// the colour word and component 3's plane: what jda_exact_colour4 reads) and XK for component 3's gray tiles in the planes stage (its
+// plane as plane[0], quant_k_zz its DQT entries).  pixel_type: JDA_RGB8888 or JDA_CMYK8888.
+inline void jda_exact_fill4(jda_ex_desc &X, jda_ex_desc &XK, const jda_image_info &I3, const uint16_t (*quant_zz)[64], const uint16_t *quant_k_zz, const jda_exact_geo &G,
+                            uint8_t *scratch, const jda_output *out, int pixel_type, bool ycck)
+{
+    jda_exact_fill(X, I3, quant_zz, G, scratch, out, JDA_RGB8888, false);
+    X.cs4 = (ycck ? JDA_EX4_YCCK : 0u) | (G.k_full ? JDA_EX4_K_FULL : 0u) | (pixel_type == JDA_CMYK8888 ? JDA_EX4_CMYK_OUT : 0u);
+    X.plane3 = scratch + G.off_k;
+    memset(&XK, 0, sizeof(XK));
+    XK.plane[0] = scratch + G.off_k;
+    XK.pitch_y = G.pitch_k; XK.w = G.kw; XK.h = G.kh;
+    for (uint32_t z = 0; z < 64u; z++) XK.quant[0][jda_en_zigzag(z)] = quant_k_zz[z];
 }
 
 // ---- the scaled decode: libjpeg's 1/2, 1/4 and 1/8 as Pillow's draft() drives them

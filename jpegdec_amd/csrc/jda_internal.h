@@ -2,6 +2,7 @@
 #ifndef JDA_INTERNAL_H
 #define JDA_INTERNAL_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/jpegdec_amd.h"
@@ -181,7 +182,22 @@ struct jda_front {
     uint32_t rec_cap;            // jda_record_cap of the image's tables
     uint8_t raw_q_id[3], adobe;  // the frame header's quantiser ids as they stand; the file has an Adobe APP14 segment
     uint16_t quant_zz[4][64];    // the DQT entries as the file lists them, by table id (zigzag order)
+    uint8_t colour;              // JDA_CS_*: how libjpeg reads the components (jda_colour_model)
 };
+
+// jdapimin.c's default_decompress_parms: the colour model libjpeg gives a file.  jfif: an APP0 "JFIF" segment was seen;
+// adobe: an APP14 "Adobe" one, transform its flag byte; ids: the frame header's component ids.
+static inline int jda_colour_model(int ncomp, int jfif, int adobe, int transform, const int *ids)
+{
+    if (ncomp == 1) return JDA_CS_GRAY;
+    if (ncomp == 3) {
+        if (jfif) return JDA_CS_YCBCR;
+        if (adobe) return transform == 0 ? JDA_CS_RGB : JDA_CS_YCBCR;
+        return ids[0] == 0x52 && ids[1] == 0x47 && ids[2] == 0x42 ? JDA_CS_RGB : JDA_CS_YCBCR;
+    }
+    if (ncomp == 4) return adobe && transform != 0 ? JDA_CS_YCCK : JDA_CS_CMYK;
+    return -1;
+}
 
 // One image of a dither launch (device pointers): gray = canvas_w x canvas_h bytes at gray_pitch (16-byte aligned rows), out = packed
 // rows at out_pitch (a multiple of 4, >= jda_dither_pitch)
@@ -290,12 +306,22 @@ struct jda_rc_xf { uint32_t bits, scx, x0, y0, rw, rh, pad_[2]; };
 struct jda_ex_desc {
     uint8_t *plane[3];
     uint8_t *out;
-    uint32_t pitch_y, pitch_c, w, h, cw, ch, out_pitch, out_w, out_rows, gray_out, luma_only, pad_;
+    uint32_t pitch_y, pitch_c, w, h, cw, ch, out_pitch, out_w, out_rows, gray_out, luma_only;
+    // a four-component image (jda_exact_colour4; zero in every other record, where the word was padding): JDA_EX4_* bits
+    uint32_t cs4;
     uint16_t quant[3][64];
     // a scaled decode (jda_exs_*; zeros in a record of the full-size kernels): scale 2, 4 or 8 -- w x h, cw x ch, the pitches
     // and the clip are then the scaled ones, a plane's blocks ss x ss samples each --, up: what jdsample.c does to the chroma planes (JDA_EX_UP_*)
-    uint32_t scale, up, pad2_[2];
+    uint32_t scale, up;
+    // a four-component image: component 3's samples (in the place of eight bytes of padding: a record of the other calls is what it was,
+    // byte for byte) -- rows pitch_y apart and w x h samples where JDA_EX4_K_FULL says component 0's sampling, else pitch_c and cw x ch.
+    // Its quantisers are in the record of its own gray tiles (the planes stage decodes it as a gray image into this plane).
+    uint8_t *plane3;
 };
+static_assert(sizeof(jda_ex_desc) == 480 && offsetof(jda_ex_desc, plane3) == 472 && offsetof(jda_ex_desc, quant) == 80, "the record the exact kernels read stays as it was");
+#define JDA_EX4_YCCK 1u          // components 0..2 are YCbCr (jdcolor.c's conversion in front of the inversion), else C, M, Y as they stand
+#define JDA_EX4_K_FULL 2u        // component 3 has component 0's sampling, else 1x1 (a chroma plane's geometry)
+#define JDA_EX4_CMYK_OUT 4u      // the surface is JDA_CMYK8888 (Pillow's mode-"CMYK" bytes), else JDA_RGB8888 (its convert("RGB"))
 // A resident baseline image as the source of an exact call, beside its jda_dev_desc and jda_ex_desc in the call's blob (a record an image
 // of the call; zeros for a coefficient image): what the planes stage's baseline load phase reads -- S as a recode source's; bpm blocks an
 // MCU, the first nluma of them luma.

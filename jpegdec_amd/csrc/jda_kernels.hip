@@ -2841,6 +2841,54 @@ void jda_exact_colour(const jda_ex_desc *__restrict__ ex, const jda_strip *__res
     jda_exact_io io;
     jda_ex_colour_tile<MODE>(io, X, S, lane);
 }
+// the colour stage of an RGB-coded file (three components that ARE R, G, B: jda_colour_model): jda_exact_colour's tile
+// walk, reads and stores, the samples written as they stand.  A kernel of its own: jda_exact_colour stays the code it was.
+template <int MODE>
+__global__ __launch_bounds__(64 * JDA_CT_WAVES)
+void jda_exact_colour_rgb(const jda_ex_desc *__restrict__ ex, const jda_strip *__restrict__ tiles, uint32_t n_tiles)
+{
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_CT_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;
+    jda_ex_desc X;
+    jda_ex_desc_uniform(X, ex + S.image);
+    jda_exact_io io;
+    jda_ex_colour_tile<MODE, true>(io, X, S, lane);
+}
+template <int MODE>
+static hipError_t launch_exact_rgb(const jda_ex_desc *ex, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    const dim3 grid((n_tiles + JDA_CT_WAVES - 1u) / JDA_CT_WAVES), block(64u * JDA_CT_WAVES);
+    JDA_LAUNCH(jda_exact_colour_rgb<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
+    return hipGetLastError();
+}
+// the colour stage of a four-component image (CMYK, YCCK: jda_ex4_* in jda_device_core.h): a wavefront = a tile record of
+// the image's components 0..2; it reads the four planes the planes launches wrote (K's by the gray launch) and stores 16 bytes a lane
+template <int MODE>
+__global__ __launch_bounds__(64 * JDA_CT_WAVES)
+void jda_exact_colour4(const jda_ex_desc *__restrict__ ex, const jda_strip *__restrict__ tiles, uint32_t n_tiles)
+{
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_CT_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;
+    jda_ex_desc X;
+    jda_ex_desc_uniform(X, ex + S.image);
+    const jda_ex_desc JDA_GLOBAL *g = JDA_G(const jda_ex_desc, ex + S.image);
+    X.cs4 = jda_uni32(g->cs4); X.plane3 = jda_uni_ptr(g->plane3);
+    jda_exact_io io;
+    jda_ex4_colour_tile<MODE>(io, X, S, lane);
+}
+template <int MODE>
+static hipError_t launch_exact_colour4(const jda_ex_desc *ex, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    const dim3 grid((n_tiles + JDA_CT_WAVES - 1u) / JDA_CT_WAVES), block(64u * JDA_CT_WAVES);
+    JDA_LAUNCH(jda_exact_colour4<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
+    return hipGetLastError();
+}
 template <int MODE>
 static hipError_t launch_exact(int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
 {
@@ -2855,12 +2903,32 @@ static hipError_t launch_exact(int stage, const jda_dev_desc *descs, const jda_e
     return hipGetLastError();
 }
 // stage 0 / 1 / 2: jda_exact_planes over tiles of dense coefficient images / sparse ones / resident baseline images of ONE mode (descs as
-// jda_launch_coef_tiles / _sparse_tiles; src: a record an image, read for baseline images); stage 3: jda_exact_colour over tile records of that mode
+// jda_launch_coef_tiles / _sparse_tiles; src: a record an image, read for baseline images); stage 3: jda_exact_colour over tile records of that mode;
+// stage 4: jda_exact_colour_rgb over tile records of RGB-coded images of that mode (a colour layout); stage 5: jda_exact_colour4 over tile
+// records of four-component images whose components 0..2 have that layout
 extern "C" hipError_t jda_launch_exact(int mode, int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
                                        hipStream_t stream)
 {
     if (n_tiles == 0) return hipSuccess;
-    if (stage < 0 || stage > 3) return hipErrorInvalidValue;
+    if (stage < 0 || stage > 5) return hipErrorInvalidValue;
+    if (stage == 5) {
+        switch (mode) {
+        case JDA_MODE_444: return launch_exact_colour4<JDA_MODE_444>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_420: return launch_exact_colour4<JDA_MODE_420>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_422: return launch_exact_colour4<JDA_MODE_422>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_440: return launch_exact_colour4<JDA_MODE_440>(ex, tiles, n_tiles, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
+    if (stage == 4) {
+        switch (mode) {
+        case JDA_MODE_444: return launch_exact_rgb<JDA_MODE_444>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_420: return launch_exact_rgb<JDA_MODE_420>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_422: return launch_exact_rgb<JDA_MODE_422>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_440: return launch_exact_rgb<JDA_MODE_440>(ex, tiles, n_tiles, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
     switch (mode) {
     case JDA_MODE_GRAY: return launch_exact<JDA_MODE_GRAY>(stage, descs, ex, src, tiles, n_tiles, stream);
     case JDA_MODE_444: return launch_exact<JDA_MODE_444>(stage, descs, ex, src, tiles, n_tiles, stream);
@@ -2938,6 +3006,28 @@ void jda_exact_colour_scaled(const jda_ex_desc *__restrict__ ex, const jda_strip
     jda_exact_io io;
     jda_exs_colour_tile<MODE>(io, X, S, lane);
 }
+// .. and of an RGB-coded file at 1/2, 1/4, 1/8 (as jda_exact_colour_rgb beside jda_exact_colour)
+template <int MODE>
+__global__ __launch_bounds__(64 * JDA_CT_WAVES)
+void jda_exact_colour_scaled_rgb(const jda_ex_desc *__restrict__ ex, const jda_strip *__restrict__ tiles, uint32_t n_tiles)
+{
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_CT_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;
+    jda_ex_desc X;
+    jda_exs_desc_uniform(X, ex + S.image);
+    jda_exact_io io;
+    jda_exs_colour_tile<MODE, true>(io, X, S, lane);
+}
+template <int MODE>
+static hipError_t launch_exact_scaled_rgb(const jda_ex_desc *ex, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    const dim3 grid((n_tiles + JDA_CT_WAVES - 1u) / JDA_CT_WAVES), block(64u * JDA_CT_WAVES);
+    JDA_LAUNCH(jda_exact_colour_scaled_rgb<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
+    return hipGetLastError();
+}
 template <int MODE, int SCALE>
 static hipError_t launch_exact_scaled(int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
 {
@@ -2967,7 +3057,17 @@ extern "C" hipError_t jda_launch_exact_scaled(int mode, int stage, int scale, co
 {
     if (scale == 1) return jda_launch_exact(mode, stage, descs, ex, src, tiles, n_tiles, stream);
     if (n_tiles == 0) return hipSuccess;
-    if (stage < 0 || stage > 3) return hipErrorInvalidValue;
+    if (stage < 0 || stage > 4) return hipErrorInvalidValue;
+    if (stage == 4) {                                                      // (the colour kernels take the scale from the record)
+        if (scale != 2 && scale != 4 && scale != 8) return hipErrorInvalidValue;
+        switch (mode) {
+        case JDA_MODE_444: return launch_exact_scaled_rgb<JDA_MODE_444>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_420: return launch_exact_scaled_rgb<JDA_MODE_420>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_422: return launch_exact_scaled_rgb<JDA_MODE_422>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_440: return launch_exact_scaled_rgb<JDA_MODE_440>(ex, tiles, n_tiles, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
     switch (mode) {
     case JDA_MODE_GRAY: return launch_exact_scaled_mode<JDA_MODE_GRAY>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
     case JDA_MODE_444: return launch_exact_scaled_mode<JDA_MODE_444>(stage, scale, descs, ex, src, tiles, n_tiles, stream);

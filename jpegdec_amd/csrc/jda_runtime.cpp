@@ -394,7 +394,7 @@ int jda_upload_batch(jda_ctx *ctx, int32_t n, jda_image *const *imgs, jda_dev_im
         d->info = I;
         d->scan_len = scan_len;
         jda_image_component_ids(img, d->dc_id, d->ac_id, d->q_id);
-        { int32_t adobe = 0; jda_image_raw_quant(img, &d->quant_zz[0][0], &adobe); d->adobe = (uint8_t)adobe; }
+        { int32_t adobe = 0; jda_image_raw_quant(img, &d->quant_zz[0][0], &adobe); d->adobe = (uint8_t)adobe; d->colour = (uint8_t)jda_image_colour_model(img); }
         d->general_p1 = (uint8_t)jda_image_general_p1(img);
         d->tables_host = (uint8_t *)malloc(JDA_TABLE_BYTES);
         if (d->tables_host) { uint32_t tb_ = 0; memcpy(d->tables_host, jda_image_tables(img, &tb_), JDA_TABLE_BYTES); }
@@ -992,7 +992,7 @@ jda_dev_coef *jda_coef_upload_ex(jda_ctx *ctx, const jda_coef_image *img, int32_
     d->info = *jda_coef_image_get_info(img);
     const int16_t *coefs = jda_coef_image_coefficients(img, &d->n_blocks);
     const int16_t *quant = jda_coef_image_quant(img, d->q_id);
-    { int32_t adobe = 0; jda_coef_image_raw_quant(img, &d->raw_quant[0][0], d->raw_qid, &adobe); d->adobe = (uint8_t)adobe; }
+    { int32_t adobe = 0; jda_coef_image_raw_quant(img, &d->raw_quant[0][0], d->raw_qid, &adobe); d->adobe = (uint8_t)adobe; d->colour = (uint8_t)jda_coef_image_colour_model(img); }
     d->form = picked;
     d->bytes = JDA_CT_QUANT_BYTES + payload;
     hipError_t e = jda_pool_alloc(ctx, (void **)&d->base, d->bytes);
@@ -1011,16 +1011,21 @@ jda_dev_coef *jda_coef_upload_ex(jda_ctx *ctx, const jda_coef_image *img, int32_
     }
     { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }      // (the image's host memory is the caller's again)
     if (e != hipSuccess) { jda_pool_free(ctx, d->base); delete d; jda_set_err(ctx, e, "jda_coef_upload"); *err = JDA_ERROR_HIP; return NULL; }
+    if (const jda_coef_image *k = jda_coef_image_component3(img)) {      // (a four-component image: component 3 beside it, dense)
+        d->k = jda_coef_upload_ex(ctx, k, JDA_COEF_DENSE, err);
+        if (!d->k) { jda_pool_free(ctx, d->base); delete d; return NULL; }
+    }
     *err = JDA_SUCCESS;
     return d;
 }
 
 int jda_dev_coef_form(const jda_dev_coef *d) { return d ? d->form : JDA_COEF_DENSE; }
-size_t jda_dev_coef_bytes(const jda_dev_coef *d) { return d ? d->bytes : 0; }
+size_t jda_dev_coef_bytes(const jda_dev_coef *d) { return d ? d->bytes + (d->k ? d->k->bytes : 0) : 0; }
 
 void jda_dev_coef_free(jda_ctx *ctx, jda_dev_coef *d)
 {
     if (!d) return;
+    if (d->k) jda_dev_coef_free(ctx, d->k);
     if (d->base) { if (ctx) { (void)hipSetDevice(ctx->device); jda_pool_free(ctx, d->base); } else (void)hipFree(d->base); }
     delete d;
 }
@@ -1045,6 +1050,7 @@ int jda_coef_plan_build(int32_t n, const jda_dev_coef *const *imgs, const jda_ou
         const int opt = (options ? options[i] : 0) & ~JDA_PROGRESSIVE_FULL;
         const uint8_t no_huff[3] = { 0, 0, 0 };
         int rc = (opt & (JDA_SCALE_HALF | JDA_SCALE_QUARTER | JDA_SCALE_EIGHTH)) ? JDA_UNSUPPORTED_FEATURE : JDA_SUCCESS;      // full size only
+        if (I.ncomp != 1 && I.ncomp != 3) rc = JDA_UNSUPPORTED_FEATURE;       // (a four-component image of jda_coef_prepare: the exact decode's _ex calls alone take it)
         if (rc == JDA_SUCCESS) rc = jda_fill_launch_desc(D, I, no_huff, no_huff, im->q_id, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, outputs[i],
                                                          pixel_types ? pixel_types[i] : JDA_RGB8888, opt, NULL);
         if (rc != JDA_SUCCESS) {
@@ -2157,10 +2163,16 @@ int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
 // the scratch -- every planned image's component planes.  The lists of a layout lie dense, sparse, baseline, back to back, so that the
 // colour stage takes all three in one launch.  scales (NULL: all 1): the lists are then per (layout, scale), and a scale
 // above 1 launches the _scaled kernels.
-struct exact_image { int kind; jda_image_info info; uint16_t quant[3][64]; jda_exact_geo G; size_t plane_at; bool luma_only; };
+// flags (the _ex calls'; 0: the calls as they were): JDA_EXACT_COLOUR_MODELS -- the file's colour model decides (jda_exact_check_cs; DESIGN.md
+// 5.19), and the lists gain a fourth column a (layout, scale): the RGB-coded images' tiles, whatever their source, for their own colour launch
+// A four-component image (a coefficient image of jda_coef_prepare) is two images to the planes stage: its components 0..2 as a
+// three-component image of their layout (record i), component 3 as a gray image (record n + i: the records are 2 n with the flag) whose
+// tiles join the call's gray launch and write the fourth plane; jda_exact_colour4 then takes the tiles of record i.  planes: four entries
+// an image with the flag (planes[4 i + c]), three without.
+struct exact_image { int kind; jda_image_info info; uint16_t quant[3][64]; jda_exact_geo G; size_t plane_at; bool luma_only; bool rgb; bool four; int colour; };
 // stage_ms (the measuring hook's, else NULL): [0] the jda_exact_planes launches, [1] the jda_exact_colour launches
 static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const jda_output *planes,
-                      int32_t *status, float *stage_ms = NULL, const int32_t *scales = NULL)
+                      int32_t *status, float *stage_ms = NULL, const int32_t *scales = NULL, uint32_t flags = 0)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (n < 0) return JDA_INVALID_PARAMETER;
@@ -2168,34 +2180,49 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
     if (!src || !status || (!outputs && !planes)) return JDA_INVALID_PARAMETER;
     for (int i = 0; i < n; i++) if ((src[i].image != NULL) == (src[i].coef != NULL)) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
-    std::vector<jda_dev_desc> descs((size_t)n);
-    std::vector<jda_ex_desc> ex((size_t)n);
-    std::vector<jda_ex_src> esrc((size_t)n);
+    const size_t nrec = flags ? 2u * (size_t)n : (size_t)n;
+    const int ps = flags ? 4 : 3;                                // entries an image in planes
+    std::vector<jda_dev_desc> descs(nrec);
+    std::vector<jda_ex_desc> ex(nrec);
+    std::vector<jda_ex_src> esrc(nrec);
     std::vector<exact_image> im((size_t)n);
+    if (flags) { memset(descs.data(), 0, nrec * sizeof(jda_dev_desc)); memset(ex.data(), 0, nrec * sizeof(jda_ex_desc)); memset(esrc.data(), 0, nrec * sizeof(jda_ex_src)); }
+    std::vector<jda_strip> c4_strips[JDA_N_MODES];              // [layout]: the four-component images' tiles for their colour stage
     std::vector<jda_strip> strips[JDA_N_MODES][4][3];           // [layout][log2 scale][dense | sparse | baseline]
+    // with JDA_EXACT_COLOUR_MODELS the colour stage has lists of its own, [layout][log2 scale][YCbCr or gray | RGB-coded]: the images' tiles
+    // once more, by what the stage does with the planes and whatever their source
+    std::vector<jda_strip> cs_strips[JDA_N_MODES][4][2];
     size_t scratch = 0;
     int planned = 0;
     for (int i = 0; i < n; i++) {
         exact_image &M = im[(size_t)i];
         jda_dev_desc &D = descs[(size_t)i];
         memset(&D, 0, sizeof(D)); memset(&ex[(size_t)i], 0, sizeof(jda_ex_desc)); memset(&esrc[(size_t)i], 0, sizeof(jda_ex_src));
-        int adobe = 0;
+        int adobe = 0, colour = JDA_CS_YCBCR;
         uint32_t n_ok = 0;
         if (src[i].image) {
             const jda_dev_image *d = src[i].image;
-            M.kind = 2; M.info = d->info; adobe = d->adobe; n_ok = d->n_mcus_ok;
+            M.kind = 2; M.info = d->info; adobe = d->adobe; n_ok = d->n_mcus_ok; colour = d->colour;
             for (int c = 0; c < 3; c++) memcpy(M.quant[c], d->quant_zz[d->q_id[c] & 3], sizeof(M.quant[c]));
         } else {
             const jda_dev_coef *d = src[i].coef;
-            M.kind = d->form == JDA_COEF_SPARSE ? 1 : 0; M.info = d->info; adobe = d->adobe;
+            M.kind = d->form == JDA_COEF_SPARSE ? 1 : 0; M.info = d->info; adobe = d->adobe; colour = d->colour;
             memcpy(M.quant, d->raw_quant, sizeof(M.quant));
         }
         const jda_image_info &I = M.info;
         const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
-        int rc = jda_exact_check(I, adobe, pt, M.kind == 2, n_ok);
-        M.luma_only = outputs && pt == JDA_EIGHT_BIT_GRAYSCALE && I.ncomp == 3;
         const int scale = scales ? scales[i] : 1;
-        if (rc == JDA_SUCCESS) rc = jda_exact_geometry_scaled(I, M.luma_only, scale, &M.G);
+        const jda_dev_coef *kd = src[i].coef ? src[i].coef->k : NULL;
+        int rc = (flags & JDA_EXACT_COLOUR_MODELS) ? jda_exact_check_cs(I, colour, pt, M.kind == 2, n_ok, scale, kd ? (kd->info.mcus_x == I.mcus_x && kd->info.mcus_y == I.mcus_y ? 0x11 : I.subsample) : 0)
+                                                   : jda_exact_check(I, adobe, pt, M.kind == 2, n_ok);
+        M.rgb = (flags & JDA_EXACT_COLOUR_MODELS) && colour == JDA_CS_RGB;
+        M.four = (flags & JDA_EXACT_COLOUR_MODELS) && I.ncomp == 4;
+        M.colour = colour;
+        M.luma_only = outputs && pt == JDA_EIGHT_BIT_GRAYSCALE && I.ncomp == 3;
+        if (rc == JDA_SUCCESS && M.four && (!kd || M.kind != 0)) rc = JDA_UNSUPPORTED_FEATURE;      // (dense, with component 3 beside it)
+        if (M.four) { M.info.ncomp = 3; M.info.bpp = 24; }     // (components 0..2 from here on: I is M.info)
+        if (rc == JDA_SUCCESS && !jda_exact_scale_ok(scale)) rc = JDA_INVALID_PARAMETER;
+        if (rc == JDA_SUCCESS) rc = M.four ? jda_exact_geometry4(I, kd->info.mcus_x != I.mcus_x || kd->info.mcus_y != I.mcus_y, &M.G) : jda_exact_geometry_scaled(I, M.luma_only, scale, &M.G);
         if (rc == JDA_SUCCESS && outputs) {
             jda_image_info B = I;
             B.jpeg_type = 0;
@@ -2203,12 +2230,12 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
             jda_output O = outputs[i];                         // (a scaled image: the surface is held to the scaled size, not to the file's)
             if (scale > 1 && O.width_px > (int32_t)M.G.w) O.width_px = (int32_t)M.G.w;
             if (scale > 1 && O.rows > (int32_t)M.G.h) O.rows = (int32_t)M.G.h;
-            rc = jda_fill_launch_desc(D, B, none, none, none, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, O, pt, 0, NULL);
+            rc = jda_fill_launch_desc(D, B, none, none, none, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, O, pt == JDA_CMYK8888 ? JDA_RGB8888 : pt, 0, NULL);      // (four bytes a pixel either way)
         } else if (rc == JDA_SUCCESS) {
             D.mode = (uint8_t)jda_mode_of(I); D.ncomp = (uint8_t)I.ncomp; D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
-            for (int c = 0; c < (I.ncomp == 3 ? 3 : 1) && rc == JDA_SUCCESS; c++) {
-                const jda_output &P = planes[3 * i + c];
-                const int32_t ew = c ? (int32_t)M.G.cw : (int32_t)M.G.w;
+            for (int c = 0; c < (M.four ? 4 : I.ncomp == 3 ? 3 : 1) && rc == JDA_SUCCESS; c++) {
+                const jda_output &P = planes[ps * i + c];
+                const int32_t ew = c == 3 ? (int32_t)M.G.kw : c ? (int32_t)M.G.cw : (int32_t)M.G.w;
                 if (!P.pixels || P.width_px < 0 || P.rows < 0 || P.pitch_bytes < (P.width_px < ew ? P.width_px : ew)) rc = JDA_INVALID_PARAMETER;
             }
         }
@@ -2226,7 +2253,15 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
         } else {
             D.tables = src[i].coef->base; D.scan = src[i].coef->base + src[i].coef->off_entries;
         }
-        jda_append_strips(strips[D.mode][M.G.scale == 8u ? 3 : M.G.scale == 4u ? 2 : M.G.scale == 2u ? 1 : 0][M.kind], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        const int g = M.G.scale == 8u ? 3 : M.G.scale == 4u ? 2 : M.G.scale == 2u ? 1 : 0;
+        jda_append_strips(strips[D.mode][g][M.kind], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        if (M.four) {
+            jda_dev_desc &DK = descs[(size_t)n + (size_t)i];
+            DK.mode = (uint8_t)JDA_MODE_GRAY; DK.ncomp = 1; DK.mcus_x = (uint32_t)kd->info.mcus_x; DK.mcus_y = (uint32_t)kd->info.mcus_y;
+            DK.tables = kd->base; DK.scan = kd->base + kd->off_entries;
+            jda_append_strips(strips[JDA_MODE_GRAY][0][0], (uint32_t)(n + i), DK.mcus_x, DK.mcus_y, JDA_MODE_GRAY);
+            if (outputs) jda_append_strips(c4_strips[D.mode], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        } else if (flags && outputs) jda_append_strips(cs_strips[D.mode][g][M.rgb ? 1 : 0], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
     }
     if (!planned) return JDA_SUCCESS;
     const size_t o_ex = align16(descs.size() * sizeof(jda_dev_desc)), o_src = o_ex + align16(ex.size() * sizeof(jda_ex_desc));
@@ -2235,6 +2270,12 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
     for (int m = 0; m < JDA_N_MODES; m++)
         for (int g = 0; g < 4; g++)
             for (int f = 0; f < 3; f++) { off[m][g][f] = bytes; bytes += strips[m][g][f].size() * sizeof(jda_strip); }
+    size_t cs_off[JDA_N_MODES][4][2];
+    for (int m = 0; m < JDA_N_MODES; m++)
+        for (int g = 0; g < 4; g++)
+            for (int f = 0; f < 2; f++) { cs_off[m][g][f] = bytes; bytes += cs_strips[m][g][f].size() * sizeof(jda_strip); }
+    size_t c4_off[JDA_N_MODES];
+    for (int m = 0; m < JDA_N_MODES; m++) { c4_off[m] = bytes; bytes += c4_strips[m].size() * sizeof(jda_strip); }
     const size_t o_scratch = (bytes + 255u) & ~(size_t)255u;
     uint8_t *blk = NULL;
     hipError_t e = jda_pool_alloc(ctx, (void **)&blk, o_scratch + scratch);
@@ -2243,7 +2284,10 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
         const exact_image &M = im[(size_t)i];
         if (M.kind < 0) continue;
         const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
-        jda_exact_fill_scaled(ex[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt, M.luma_only);
+        if (M.four)
+            jda_exact_fill4(ex[(size_t)i], ex[(size_t)n + (size_t)i], M.info, M.quant, src[i].coef->k->raw_quant[0], M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt,
+                            M.colour == JDA_CS_YCCK);
+        else jda_exact_fill_scaled(ex[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt, M.luma_only);
     }
     std::vector<uint8_t> blob(bytes, 0);
     memcpy(blob.data(), descs.data(), descs.size() * sizeof(jda_dev_desc));
@@ -2253,6 +2297,12 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
         for (int g = 0; g < 4; g++)
             for (int f = 0; f < 3; f++)
                 if (!strips[m][g][f].empty()) memcpy(blob.data() + off[m][g][f], strips[m][g][f].data(), strips[m][g][f].size() * sizeof(jda_strip));
+    for (int m = 0; m < JDA_N_MODES; m++)
+        for (int g = 0; g < 4; g++)
+            for (int f = 0; f < 2; f++)
+                if (!cs_strips[m][g][f].empty()) memcpy(blob.data() + cs_off[m][g][f], cs_strips[m][g][f].data(), cs_strips[m][g][f].size() * sizeof(jda_strip));
+    for (int m = 0; m < JDA_N_MODES; m++)
+        if (!c4_strips[m].empty()) memcpy(blob.data() + c4_off[m], c4_strips[m].data(), c4_strips[m].size() * sizeof(jda_strip));
     e = hipMemcpyAsync(blk, blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
     const jda_dev_desc *d_descs = (const jda_dev_desc *)blk;
     const jda_ex_desc *d_ex = (const jda_ex_desc *)(blk + o_ex);
@@ -2265,20 +2315,26 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
             for (int f = 0; f < 3 && e == hipSuccess; f++)
                 e = jda_launch_exact_scaled(m, f, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][g][f]), (uint32_t)strips[m][g][f].size(), ctx->stream);
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs; m++)
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && !flags; m++)
         for (int g = 0; g < 4 && e == hipSuccess; g++)
             e = jda_launch_exact_scaled(m, 3, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][g][0]),
                                         (uint32_t)(strips[m][g][0].size() + strips[m][g][1].size() + strips[m][g][2].size()), ctx->stream);
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && flags; m++)
+        for (int g = 0; g < 4 && e == hipSuccess; g++)
+            for (int f = 0; f < 2 && e == hipSuccess; f++)
+                e = jda_launch_exact_scaled(m, 3 + f, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + cs_off[m][g][f]), (uint32_t)cs_strips[m][g][f].size(), ctx->stream);
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && flags; m++)
+        e = jda_launch_exact_scaled(m, 5, 1, d_descs, d_ex, d_src, (const jda_strip *)(blk + c4_off[m]), (uint32_t)c4_strips[m].size(), ctx->stream);
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
     for (int i = 0; i < n && e == hipSuccess && planes; i++) {
         const exact_image &M = im[(size_t)i];
         if (M.kind < 0) continue;
-        for (int c = 0; c < (M.info.ncomp == 3 ? 3 : 1) && e == hipSuccess; c++) {
-            const jda_output &P = planes[3 * i + c];
-            const int32_t ew = c ? (int32_t)M.G.cw : (int32_t)M.G.w, eh = c ? (int32_t)M.G.ch : (int32_t)M.G.h;
+        for (int c = 0; c < (M.four ? 4 : M.info.ncomp == 3 ? 3 : 1) && e == hipSuccess; c++) {
+            const jda_output &P = planes[ps * i + c];
+            const int32_t ew = c == 3 ? (int32_t)M.G.kw : c ? (int32_t)M.G.cw : (int32_t)M.G.w, eh = c == 3 ? (int32_t)M.G.kh : c ? (int32_t)M.G.ch : (int32_t)M.G.h;
             const size_t cw = (size_t)(P.width_px < ew ? P.width_px : ew), crows = (size_t)(P.rows < eh ? P.rows : eh);
             if (cw && crows)
-                e = hipMemcpy2DAsync(P.pixels, (size_t)P.pitch_bytes, blk + o_scratch + M.plane_at + M.G.off[c], c ? M.G.pitch_c : M.G.pitch_y, cw, crows,
+                e = hipMemcpy2DAsync(P.pixels, (size_t)P.pitch_bytes, blk + o_scratch + M.plane_at + (c == 3 ? M.G.off_k : M.G.off[c]), c == 3 ? M.G.pitch_k : c ? M.G.pitch_c : M.G.pitch_y, cw, crows,
                                      hipMemcpyDeviceToDevice, ctx->stream);
         }
     }
@@ -2341,6 +2397,28 @@ int jda_exact_decode_planes_scaled(jda_ctx *ctx, int32_t n, const jda_recode_sou
     if (ctx && n > 0 && !planes) return JDA_INVALID_PARAMETER;
     return exact_call(ctx, n, src, NULL, NULL, planes, status, NULL, scales);
 }
+int jda_exact_decode_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const int32_t *scales,
+                                 uint32_t flags, int32_t *status)
+{
+    if (flags & ~(uint32_t)JDA_EXACT_COLOUR_MODELS) return JDA_INVALID_PARAMETER;
+    if (ctx && n > 0 && !outputs) return JDA_INVALID_PARAMETER;
+    return exact_call(ctx, n, src, outputs, pixel_types, NULL, status, NULL, scales, flags);
+}
+int jda_exact_decode_planes_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *planes, const int32_t *scales, uint32_t flags, int32_t *status)
+{
+    if (flags & ~(uint32_t)JDA_EXACT_COLOUR_MODELS) return JDA_INVALID_PARAMETER;
+    if (ctx && n > 0 && !planes) return JDA_INVALID_PARAMETER;
+    return exact_call(ctx, n, src, NULL, NULL, planes, status, NULL, scales, flags);
+}
+// the measuring hook of the _ex calls (tools/exact_adobe_bench.py): stage_ms[0] the planes launches (K's gray tiles among them), stage_ms[1]
+// the colour launches (jda_exact_colour4, the RGB instances)
+int jda_internal_exact_time_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const int32_t *scales,
+                               uint32_t flags, int32_t *status, float *stage_ms)
+{
+    if (!stage_ms || (flags & ~(uint32_t)JDA_EXACT_COLOUR_MODELS) || (ctx && n > 0 && !outputs)) return JDA_INVALID_PARAMETER;
+    stage_ms[0] = stage_ms[1] = 0.f;
+    return exact_call(ctx, n, src, outputs, pixel_types, NULL, status, stage_ms, scales, flags);
+}
 // the measuring hook with a scale an image (tools/exact_bench.py --scale)
 int jda_internal_exact_time_scaled(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const int32_t *scales,
                                    int32_t *status, float *stage_ms)
@@ -2355,24 +2433,44 @@ int jda_decode_to_host_exact(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int
 }
 int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, void *host_pixels, int32_t pitch_bytes, int32_t rows)
 {
+    return jda_decode_to_host_exact_ex(ctx, jpeg, len, pixel_type, scale, 0u, host_pixels, pitch_bytes, rows);
+}
+int jda_decode_to_host_exact_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, void *host_pixels, int32_t pitch_bytes,
+                                int32_t rows)
+{
     if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (flags & ~(uint32_t)JDA_EXACT_COLOUR_MODELS) return JDA_INVALID_PARAMETER;
     if (!jpeg || !host_pixels || pitch_bytes < 0 || rows < 0) return JDA_INVALID_PARAMETER;
-    if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
+    if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE && !(flags && pixel_type == JDA_CMYK8888)) return JDA_INVALID_PARAMETER;
     if (!jda_exact_scale_ok(scale)) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
     jda_image_info I;
     int rc = jda_parse(jpeg, len, &I);
+    // with the flag a four-component file of any SOF type goes the progressive files' way, through jda_coef_prepare (which takes SOF1 too)
+    bool four = false;
+    if (flags) {
+        jda_exact_file E;
+        const int prc = jda_exact_probe(jpeg, len, &E);
+        if (E.ncomp == 4) {
+            if (prc != JDA_SUCCESS) return prc;
+            four = true;
+            if (rc != JDA_SUCCESS) { memset(&I, 0, sizeof(I)); I.width = E.width; I.height = E.height; I.ncomp = 4; rc = JDA_SUCCESS; }
+            if (scale != 1) return JDA_UNSUPPORTED_FEATURE;
+            if (pixel_type == JDA_EIGHT_BIT_GRAYSCALE) return JDA_UNSUPPORTED_FEATURE;
+        }
+    }
     if (rc != JDA_SUCCESS) return rc;
+    if (pixel_type == JDA_CMYK8888 && !four) return JDA_INVALID_PARAMETER;
     const int32_t ow = (I.width + scale - 1) / scale, oh = (I.height + scale - 1) / scale;      // (at scale 1 the file's own size)
-    if ((int64_t)pitch_bytes < (int64_t)ow * (pixel_type == JDA_RGB8888 ? 4 : 1)) return JDA_INVALID_PARAMETER;      // (a row holds the image's width, as a surface's does)
+    if ((int64_t)pitch_bytes < (int64_t)ow * (pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4)) return JDA_INVALID_PARAMETER;      // (a row holds the image's width, as a surface's does)
     jda_image *img = NULL;
     jda_coef_image *cimg = NULL;
     jda_recode_source S = { NULL, NULL };
     int32_t err = JDA_SUCCESS;
     jda_dev_image *dimg = NULL;
     jda_dev_coef *dcoef = NULL;
-    if (I.jpeg_type == 1) {                                // (every scan is what libjpeg decodes: no option bit)
-        cimg = jda_progressive_prepare(jpeg, len, &err);
+    if (I.jpeg_type == 1 || four) {                        // (every scan is what libjpeg decodes: no option bit)
+        cimg = four ? jda_coef_prepare(jpeg, len, &err) : jda_progressive_prepare(jpeg, len, &err);
         if (cimg) dcoef = jda_coef_upload_ex(ctx, cimg, JDA_COEF_AUTO, &err);
         S.coef = dcoef;
     } else {
@@ -2381,7 +2479,7 @@ int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t l
         S.image = dimg;
     }
     rc = (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
-    const int bpp = pixel_type == JDA_RGB8888 ? 4 : 1;
+    const int bpp = pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4;
     const int dpitch = (int)align16((size_t)ow * bpp), drows = rows < oh ? rows : oh;
     void *dout = NULL;
     if (rc == JDA_SUCCESS && jda_pool_alloc(ctx, &dout, (size_t)dpitch * (size_t)oh + 16) != hipSuccess) rc = JDA_ERROR_MEMORY;
@@ -2389,7 +2487,7 @@ int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t l
         jda_output O;
         O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = ow; O.rows = drows;
         int32_t st = JDA_SUCCESS;
-        rc = exact_call(ctx, 1, &S, &O, &pixel_type, NULL, &st, NULL, &scale);
+        rc = exact_call(ctx, 1, &S, &O, &pixel_type, NULL, &st, NULL, &scale, flags);
         if (rc == JDA_SUCCESS) rc = st;
     }
     if (rc == JDA_SUCCESS && drows > 0) {

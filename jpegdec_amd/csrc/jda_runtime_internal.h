@@ -56,9 +56,13 @@ struct jda_dev_image {
     uint8_t *tables_host;     // a host copy of the tables (JDA_TABLE_BYTES): a launch plan lets consecutive images with equal tables share the first one's copy
     uint16_t quant_zz[4][64]; // the file's DQT entries by table id (zigzag order) and whether it has an Adobe APP14 segment: a recode's header (jda_recode_plan.h)
     uint8_t adobe;
+    uint8_t colour;           // JDA_CS_* (jda_colour_model): what the exact decode's _ex calls read the components as
 };
 extern "C" void jda_image_raw_quant(const jda_image *img, uint16_t *quant_zz, int32_t *adobe);
 extern "C" void jda_coef_image_raw_quant(const jda_coef_image *img, uint16_t *quant_zz, uint8_t *q_id, int32_t *adobe);
+// JDA_CS_*: how libjpeg reads the file's components (jda_colour_model; the exact decode's _ex calls)
+extern "C" int jda_image_colour_model(const jda_image *img);
+extern "C" int jda_coef_image_colour_model(const jda_coef_image *img);
 
 struct jda_dev_coef {
     uint8_t *base;            // one allocation: quantisers (JDA_CT_QUANT_BYTES) | coefficients (n_blocks x 128 bytes)  -- JDA_COEF_DENSE
@@ -71,6 +75,10 @@ struct jda_dev_coef {
     size_t off_entries;       // the coefficients (dense) / the entries (sparse)
     uint16_t raw_quant[3][64]; // the DQT entries of Y, Cb, Cr as the file lists them, the ids its frame header gives them, its Adobe APP14 flag (a recode's header)
     uint8_t raw_qid[3], adobe;
+    uint8_t colour;           // JDA_CS_* (jda_colour_model)
+    // a four-component image (jda_coef_prepare; info.ncomp == 4): everything above is components 0..2 as a three-component image, and
+    // component 3 is this gray image over its own MCU-padded block grid, uploaded and freed with this one.  NULL otherwise.
+    jda_dev_coef *k;
 };
 
 // launch plan of a call over coefficient images: descs | tile lists of (form, layout), in one host blob that goes to the device as it is

@@ -131,22 +131,24 @@ def prescale_option(info, pixel_type, options, size):
     return 0
 
 
-def _exact_batch(ctx, files, infos, outs, pt, scales=None):
+def _exact_batch(ctx, files, infos, outs, pt, scales=None, colour_models=False):
     """decode_to_tensors(decoder="libjpeg"): the files resident -- baseline ones with the device pre-scan's index, progressive ones as
     coefficient images in whichever form is smaller -- and ONE exact_decode call into the surfaces `outs` (scales: file k at 1 / scales[k],
-    libjpeg's scaled decode); -> the statuses"""
+    libjpeg's scaled decode; colour_models: exact_decode's); -> the statuses"""
     n = len(files)
-    base_ix = [k for k in range(n) if infos[k].jpeg_type != 1]
+    # (CMYK, YCCK, and an extended-sequential frame, which jda_prepare does not take: a coefficient image whatever the SOF type)
+    four = [colour_models and (infos[k].ncomp == 4 or getattr(infos[k], "via_coef_prepare", False)) for k in range(n)]
+    base_ix = [k for k in range(n) if infos[k].jpeg_type != 1 and not four[k]]
     prepared, sources, hosts = [], [None] * n, []
     try:
         prepared = B.prepare_batch([files[k] for k in base_ix], device_prescan=True) if base_ix else []
         for k, d in zip(base_ix, B.upload_batch(ctx, prepared) if base_ix else []):
             sources[k] = d
         for k in range(n):
-            if infos[k].jpeg_type == 1:
-                hosts.append(B.CoefImage(files[k]))
+            if infos[k].jpeg_type == 1 or four[k]:
+                hosts.append(B.CoefImage.from_file(files[k]) if four[k] else B.CoefImage(files[k]))
                 sources[k] = B.DeviceCoef(ctx, hosts[-1], B.COEF_AUTO)
-        return B.exact_decode(ctx, sources, outs, [pt] * n, scales)
+        return B.exact_decode(ctx, sources, outs, [pt] * n, scales, colour_models)
     finally:
         for d in sources:
             if d is not None:
@@ -157,7 +159,7 @@ def _exact_batch(ctx, files, infos, outs, pt, scales=None):
 
 
 def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=0, bgr=False, size=None, crops=None, prescale=False, progressive="thumbnail", resample=None,
-                      decoder="reference", draft=None):
+                      decoder="reference", draft=None, colour_models=False):
     """files (JPEG bytes, all colour or all gray) -> tensors on cuda:<ctx.device>.  layout "CHW" or "HWC"; dtype torch.uint8 (default), or
     torch.float16 / torch.float32 with table = [C, 256] values of that type (normalise_table; numpy or torch).  options: the decode option
     bits of every file (a JDA_SCALE_* bit, JDA_LUMA_ONLY: one channel).  Returns a list of [C,H,W] / [H,W,C] tensors, or, when all images
@@ -184,7 +186,14 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     draft=(h, w) any other size; each file is decoded at the scale Pillow would choose for that request (exact_draft_scale: the largest of
     1/8, 1/4, 1/2, 1 that keeps both sides at or above it) by libjpeg's reduced-size IDCTs (jda_exact_decode_surfaces_scaled) and resized
     from there, so that the tensor is Pillow's draft() -> convert("RGB") -> resize() bit for bit.  With decoder="reference", with crops= or
-    without size= it is a ValueError."""
+    without size= it is a ValueError.
+    colour_models (decoder="libjpeg"; jda_exact_decode_surfaces_ex with JDA_EXACT_COLOUR_MODELS): True takes files with an Adobe APP14 segment
+    and reads every one- or three-component file by libjpeg's own rule (exact_probe) -- Photoshop's YCbCr files (transform 1) as any YCbCr
+    file, RGB-coded ones (Adobe transform 0 without JFIF, or component ids 'R', 'G', 'B' without either marker) as the R, G, B they hold.
+    Without it such files are refused (JdaError 3) or, the RGB-coded ones without a segment, converted as if they were YCbCr.  Four-component
+    files (CMYK, YCCK; baseline or progressive) go through CoefImage.from_file and come out as Pillow's convert("RGB") of them; draft= leaves
+    them at full size only where Pillow's scale would be 1 (a reduced-size decode of four components is JdaError 3).  With
+    decoder="reference" it is a ValueError."""
     files = list(files)
     if decoder not in ("reference", "libjpeg"):
         raise ValueError("decoder: 'reference' or 'libjpeg'")
@@ -201,6 +210,8 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
         raise ValueError("decoder='libjpeg': no prescale, no JDA_SCALE_* bit in options (the reference road's scales); libjpeg's scaled decode is draft=")
     if decoder == "libjpeg" and options & ~B.LUMA_ONLY:
         raise ValueError("decoder='libjpeg': the only option bit it honours is JDA_LUMA_ONLY (the Y plane)")
+    if colour_models and decoder != "libjpeg":
+        raise ValueError("colour_models goes with decoder='libjpeg'")
     if progressive not in ("thumbnail", "full"):
         raise ValueError("progressive: 'thumbnail' or 'full'")
     if layout not in ("CHW", "HWC"):
@@ -239,13 +250,19 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     for f in files:
         info = B.ImageInfo()
         rc = ctx.lib.jda_parse(f, len(f), C.byref(info))
-        if rc != 0:
+        if rc == 3 and colour_models:                                    # (an SOF1 frame, perhaps: jda_coef_prepare reads those, and keeps the header)
+            host = B.CoefImage.from_file(f)
+            info = B.ImageInfo.from_buffer_copy(host.info)
+            info.via_coef_prepare = True
+            host.close()
+        elif rc != 0:
             raise B.JdaError(rc, "jda_parse")
         infos.append(info)
     gray = [i.ncomp == 1 or bool(options & B.LUMA_ONLY) for i in infos]
-    if any(gray) != all(gray):
+    if any(gray) != all(gray) and not (colour_models and not options & B.LUMA_ONLY):
         raise ValueError("gray and colour files in one call: one jda_pack_surfaces launch takes one source format")
-    pt, channels = (B.GRAY8, 1) if gray[0] else (B.RGB8888, 3)
+    # (colour_models: a gray file among colour ones comes out as Pillow's convert("RGB") of it, R = G = B = Y)
+    pt, channels = (B.GRAY8, 1) if all(gray) else (B.RGB8888, 3)
     full = [(progressive == "full" or decoder == "libjpeg") and i.jpeg_type == 1 for i in infos]
     opts = [options | B.PROGRESSIVE_FULL if fl else options | (prescale_option(i, pt, options, size) if prescale else 0) for i, fl in zip(infos, full)]
     geos = [B.output_geometry(i, pt, o) for i, o in zip(infos, opts)]
@@ -256,7 +273,7 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
         for k, (i, s) in enumerate(zip(infos, scales)):
             w, h = -(-i.width // s), -(-i.height // s)
             geos[k] = dict(geos[k], canvas_w=w, canvas_h=h, out_w=w, out_h=h)
-    bpp = geos[0]["bpp"]
+    bpp = 4 if (decoder == "libjpeg" and pt == B.RGB8888) else geos[0]["bpp"]
     pitches = [(g["canvas_w"] * bpp + 15) & ~15 for g in geos]
     offs, total = [], 0
     for g, p in zip(geos, pitches):
@@ -292,7 +309,7 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
             rbase = ctx.malloc(rbytes * n)
         outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
         if decoder == "libjpeg":
-            status = _exact_batch(ctx, files, infos, outs, pt, scales)
+            status = _exact_batch(ctx, files, infos, outs, pt, scales, bool(colour_models))
         else:
             pipe = B.Pipeline(ctx, max_images=n, depth=1)
             try:
