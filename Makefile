@@ -22,7 +22,7 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_exactadobesim.so tests/hostsim/libjda_exactscaledsim.so tests/hostsim/libjda_exactsim.so tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so tests/hostsim/libjda_encodeprogsim.so tests/hostsim/libjda_recodesim.so tests/hostsim/libjda_recodexfsim.so tests/hostsim/libjda_unpacksim.so
+hostsim: tests/hostsim/libjda_exactrectsim.so tests/hostsim/libjda_exactadobesim.so tests/hostsim/libjda_exactscaledsim.so tests/hostsim/libjda_exactsim.so tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so tests/hostsim/libjda_encodeprogsim.so tests/hostsim/libjda_recodesim.so tests/hostsim/libjda_recodexfsim.so tests/hostsim/libjda_unpacksim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_prescan_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
@@ -92,6 +92,17 @@ tests/hostsim/libjda_exactadobesim.so: $(EXACTADOBESIM_DEPS)
 exactadobeasan: tests/hostsim/exact_adobe_asan
 tests/hostsim/exact_adobe_asan: tests/hostsim/exact_adobe_main.cpp $(EXACTADOBESIM_DEPS)
 	$(CXX) -O1 -g -std=c++17 -fwrapv -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/exact_adobe_main.cpp $(EXACTADOBESIM_SRCS)
+
+# the exact decode of a pixel rectangle: the plan, the existing planes lanes over the rectangle's tiles into a poisoned scratch and the new
+# colour lanes (jda_exr_*) lane by lane on the CPU (tests/test_exact_rect_cpu.py) -- test infrastructure
+EXACTRECTSIM_SRCS = tests/hostsim/exact_rect_sim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp
+EXACTRECTSIM_DEPS = $(EXACTRECTSIM_SRCS) tests/hostsim/exact_scaled_twin.h tests/hostsim/exact_twin.h $(CSRC)/jda_exact_plan.h $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
+tests/hostsim/libjda_exactrectsim.so: $(EXACTRECTSIM_DEPS)
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ $(EXACTRECTSIM_SRCS)
+# .. and the same with a main of its own under AddressSanitizer + UBSan: a program, nothing loaded into an interpreter
+exactrectasan: tests/hostsim/exact_rect_asan
+tests/hostsim/exact_rect_asan: tests/hostsim/exact_rect_main.cpp $(EXACTRECTSIM_DEPS)
+	$(CXX) -O1 -g -std=c++17 -fwrapv -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/exact_rect_main.cpp $(EXACTRECTSIM_SRCS)
 
 # the resize kernel's two passes, lane by lane, its row-major twin, the host's tap tables and the argument checks of jda_resize_surfaces on
 # the CPU (tests/test_resize_cpu.py) -- test infrastructure.  -ffp-contract=off: the taps are Pillow's only in Pillow's order of operations
@@ -219,10 +230,10 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/hostsim/libjda_exactadobesim.so tests/hostsim/exact_adobe_asan tests/hostsim/libjda_exactscaledsim.so tests/hostsim/exact_scaled_asan tests/hostsim/libjda_exactsim.so tests/hostsim/exact_asan tests/hostsim/libjda_unpacksim.so tests/hostsim/unpack_asan tests/hostsim/libjda_recodexfsim.so tests/hostsim/recode_xf_asan tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
+	rm -f tests/hostsim/libjda_exactrectsim.so tests/hostsim/exact_rect_asan tests/hostsim/libjda_exactadobesim.so tests/hostsim/exact_adobe_asan tests/hostsim/libjda_exactscaledsim.so tests/hostsim/exact_scaled_asan tests/hostsim/libjda_exactsim.so tests/hostsim/exact_asan tests/hostsim/libjda_unpacksim.so tests/hostsim/unpack_asan tests/hostsim/libjda_recodexfsim.so tests/hostsim/recode_xf_asan tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
-.PHONY: exactadobeasan exactscaledasan exactasan all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan recodexfasan resizefiltersasan unpackasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
+.PHONY: exactrectasan exactadobeasan exactscaledasan exactasan all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan recodexfasan resizefiltersasan unpackasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
 
 # jda_node.cpp (host code above the C-ABI) over eight pretend devices -- test infrastructure, no GPU (tests/test_c_api.py)
 nodestub: tests/node_stub/node_stub_user

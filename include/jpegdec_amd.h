@@ -964,6 +964,25 @@ int jda_exact_decode_planes_ex(jda_ctx *ctx, int32_t n, const jda_recode_source 
 int jda_decode_to_host_exact_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, void *host_pixels,
                                 int32_t pitch_bytes, int32_t rows);
 
+/* The source rectangle {x0, y0, x1, y1} (half open) that resizing rect = {x, y, w, h} of a src_w x src_h image to out_w x out_h reads with
+ * `filter` (JDA_RESIZE_*), clipped at the image: what a caller decodes of a file before it resizes a crop.  Host work only. */
+int jda_resize_reads(int32_t src_w, int32_t src_h, const int32_t *rect, int32_t out_w, int32_t out_h, int32_t filter, int32_t *reads);
+
+/* ---- libjpeg-exact decode of a pixel rectangle: only the MCUs the rectangle's pixels read are decoded, and the surface
+ * holds the rectangle -- its pixels are the whole decode's, cropped (a horizontally subsampled chroma plane at most two samples wide is
+ * replicated at full size too, libjpeg's rule: such a rectangle is Pillow's, where jda_exact_decode_surfaces interpolates).
+ * rects: {x, y, w, h} per image, pixels of the image at its scale; NULL: jda_exact_decode_surfaces_ex, launch for launch and byte for byte.
+ * An all-zero rectangle: that image whole, through the kernels of the _ex call (whole and cropped images mix in one call).
+ * status[i]: JDA_INVALID_PARAMETER for an empty rectangle, a negative origin or one that leaves the image; JDA_UNSUPPORTED_FEATURE for a
+ * four-component source with a rectangle; everything jda_exact_decode_surfaces_ex refuses stays refused. */
+int jda_exact_decode_surfaces_rect(jda_ctx *ctx, int32_t n, const jda_recode_source *sources, const jda_output *outputs, const int32_t *pixel_types,
+                                   const int32_t *scales, uint32_t flags, const int32_t *rects, int32_t *status);
+/* the MCU rectangle {mx0, my0, mx1, my1} that call decodes for rect (pixel_type decides whether chroma is decoded at all) */
+int jda_exact_rect_mcus(const jda_image_info *info, int32_t scale, int32_t pixel_type, const int32_t *rect, int32_t *mcu_rect);
+/* file in, the rectangle's pixels out: w x h pixels at pitch_bytes; tiles (may be NULL): [0] planes-stage tiles launched, [1] those of the whole image */
+int jda_decode_to_host_exact_rect(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect,
+                                  void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *tiles);
+
 const char *jda_version(void);
 
 #ifdef __cplusplus

@@ -237,6 +237,11 @@ _PROTOTYPES = [
     ("jda_exact_decode_surfaces_ex", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32)]),
     ("jda_exact_decode_planes_ex", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32)]),
     ("jda_decode_to_host_exact_ex", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P, C.c_int32, C.c_int32]),
+    ("jda_exact_decode_surfaces_rect", C.c_int, [_P, C.c_int32, C.POINTER(RecodeSource), C.POINTER(Output), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32,
+                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("jda_exact_rect_mcus", C.c_int, [C.POINTER(ImageInfo), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("jda_decode_to_host_exact_rect", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_int32), _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    ("jda_resize_reads", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
 ]
 
 
@@ -1312,19 +1317,27 @@ def exact_probe(jpeg: bytes):
                 adobe_transform=f.adobe_transform, component_ids=list(f.component_id)[:f.ncomp])
 
 
-def exact_decode(ctx: Context, sources, outputs, pixel_types=None, scales=None, colour_models=False):
+def exact_decode(ctx: Context, sources, outputs, pixel_types=None, scales=None, colour_models=False, rects=None):
     """jda_exact_decode_surfaces: the libjpeg-exact decode (Pillow's pixels, not the reference's) of resident sources -- DeviceImage (a
     baseline file) or DeviceCoef (dense or sparse) each -- into surfaces.  outputs = (device pointer, pitch, width_px, rows) each;
     pixel_types: RGB8888 (the default) or GRAY8 each.  Exactly min(width, width_px) x min(height, rows) pixels of an image are written.
     scales (jda_exact_decode_surfaces_scaled): 1, 2, 4 or 8 each -- libjpeg's scaled decode, Pillow's draft(); the image is then
     ceil(width / s) x ceil(height / s).  colour_models (jda_exact_decode_surfaces_ex with JDA_EXACT_COLOUR_MODELS): a file with an Adobe
     segment is taken, an RGB-coded one (exact_probe) is written as R, G, B, and a four-component DeviceCoef of CoefImage.from_file (CMYK,
-    YCCK; scale 1) as Pillow's convert("RGB") of it, or, pixel type CMYK8888, as Pillow's mode-"CMYK" bytes.  -> the statuses; the call's
-    own refusals raise JdaError."""
+    YCCK; scale 1) as Pillow's convert("RGB") of it, or, pixel type CMYK8888, as Pillow's mode-"CMYK" bytes.
+    rects (jda_exact_decode_surfaces_rect): (x, y, w, h) each, in pixels of the image at its scale, or None / (0, 0, 0, 0) for that image
+    whole -- only the MCUs the rectangle's pixels read are decoded (exact_rect_mcus) and the surface holds the rectangle: exactly
+    min(w, width_px) x min(h, rows) pixels are written.  -> the statuses; the call's own refusals raise JdaError."""
     n = len(sources)
     o = (Output * max(n, 1))(*[Output(*q) for q in outputs])
     pt = None if pixel_types is None else (C.c_int32 * max(n, 1))(*pixel_types)
     status = (C.c_int32 * max(n, 1))()
+    if rects is not None:
+        flat = [int(v) for r in rects for v in (r if r is not None else (0, 0, 0, 0))]
+        sc = None if scales is None else (C.c_int32 * max(n, 1))(*scales)
+        ctx.check(ctx.lib.jda_exact_decode_surfaces_rect(ctx.handle, n, _recode_sources(sources), o, pt, sc, EXACT_COLOUR_MODELS if colour_models else 0,
+                                                         (C.c_int32 * max(4 * n, 1))(*flat), status), "jda_exact_decode_surfaces_rect")
+        return list(status)[:n]
     if colour_models:
         sc = None if scales is None else (C.c_int32 * max(n, 1))(*scales)
         ctx.check(ctx.lib.jda_exact_decode_surfaces_ex(ctx.handle, n, _recode_sources(sources), o, pt, sc, EXACT_COLOUR_MODELS, status), "jda_exact_decode_surfaces_ex")
@@ -1386,10 +1399,40 @@ def exact_draft_scale(jpeg_or_info, size):
     return load_library().jda_exact_draft_scale(C.byref(info), int(size[0]), int(size[1]))
 
 
-def decode_to_host_exact(ctx: Context, jpeg: bytes, pixel_type=RGB8888, scale=1, colour_models=False):
+def exact_rect_mcus(jpeg_or_info, rect, scale=1, pixel_type=RGB8888):
+    """jda_exact_rect_mcus: the half-open MCU rectangle (mx0, my0, mx1, my1) exact_decode(.., rects=) decodes for rect = (x, y, w, h), pixels of
+    the image at `scale` (a gray surface of a colour file decodes no chroma); a rectangle the decode refuses raises JdaError."""
+    info = _info_of(jpeg_or_info)
+    out = (C.c_int32 * 4)()
+    rc = load_library().jda_exact_rect_mcus(C.byref(info), scale, pixel_type, (C.c_int32 * 4)(*[int(v) for v in rect]), out)
+    if rc != 0:
+        raise JdaError(rc, "jda_exact_rect_mcus")
+    return tuple(out)
+
+
+def resize_reads(src_size, rect, out_size, filter=0):
+    """jda_resize_reads: the source rectangle (x0, y0, x1, y1), half open, that resizing rect = (x, y, w, h) of a src_size = (w, h) image to
+    out_size = (w, h) reads with `filter` (RESIZE_*), clipped at the image"""
+    out = (C.c_int32 * 4)()
+    rc = load_library().jda_resize_reads(int(src_size[0]), int(src_size[1]), (C.c_int32 * 4)(*[int(v) for v in rect]), int(out_size[0]), int(out_size[1]), filter, out)
+    if rc != 0:
+        raise JdaError(rc, "jda_resize_reads")
+    return tuple(out)
+
+
+def decode_to_host_exact(ctx: Context, jpeg: bytes, pixel_type=RGB8888, scale=1, colour_models=False, rect=None):
     """jda_decode_to_host_exact[_scaled]: one file, baseline or progressive, to the pixels Pillow gives (at scale 2, 4, 8: after
-    draft()) -- (rc, height x width x 4 RGBA bytes or height x width gray).  colour_models (jda_decode_to_host_exact_ex): as exact_decode's."""
+    draft()) -- (rc, height x width x 4 RGBA bytes or height x width gray).  colour_models (jda_decode_to_host_exact_ex): as exact_decode's.
+    rect = (x, y, w, h) (jda_decode_to_host_exact_rect): that rectangle of the image at its scale alone -- (rc, h x w [x 4] pixels,
+    (planes-stage tiles launched, those of the whole image))."""
     bpp = 4 if pixel_type in (RGB8888, CMYK8888) else 1
+    if rect is not None:
+        x, y, w, h = [int(v) for v in rect]
+        canvas = np.zeros((max(h, 1), max(w, 1) * bpp), dtype=np.uint8)
+        tiles = (C.c_int32 * 2)()
+        rc = ctx.lib.jda_decode_to_host_exact_rect(ctx.handle, jpeg, len(jpeg), pixel_type, scale, EXACT_COLOUR_MODELS if colour_models else 0, (C.c_int32 * 4)(x, y, w, h),
+                                                   canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0], tiles)
+        return rc, (canvas.reshape(canvas.shape[0], -1, 4) if bpp == 4 else canvas), tuple(tiles)
     if colour_models:
         p = exact_probe(jpeg)                                     # (jda_parse refuses an extended-sequential frame, which this road takes)
         s = scale if scale in (1, 2, 4, 8) else 1

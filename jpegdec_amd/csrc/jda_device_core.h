@@ -5765,4 +5765,153 @@ template <int MODE, bool RGB = false, class IO> JDA_HD void jda_exs_colour_tile(
     }
 }
 
+// ================================================================================================
+// jda_exr_*: the colour stage of a pixel rectangle (jda_exact_colour_rect).  The planes stage has written the MCUs the
+// rectangle's formulas read (jda_exact_rect_plan) at the whole image's geometry; a lane makes four DESTINATION pixels dx .. dx + 3 (dx a
+// multiple of 4) of destination row dy -- one 16-byte store, or four bytes of a gray surface -- from the source pixels R.x + dx .., row
+// R.y + dy: any alignment of the Y bytes, either chroma parity.  The upsampling is named an axis (JDA_EXR_*), from the layout, the record's
+// scale and up and libjpeg's rule for a narrow plane, so that one function serves every scale; the formulas, the clamps to the
+// component's own extent and the biases are jda_ex_chroma4_any's and jda_exs_chroma4's.  No byte outside the samples the definition
+// names for the rectangle's pixels is loaded: a dword only where all four bytes are the rectangle's.
+struct jda_exr_rec { uint32_t x, y, w, h; };                 // the rectangle in pixels of the image at its scale; beside jda_ex_desc in the call's blob
+#define JDA_EXR_NONE 0u
+#define JDA_EXR_REPLICATE 1u
+#define JDA_EXR_FANCY 2u
+#define JDA_EXR_TILE_QUADS 64u                               // a tile record of the destination: up to 64 quads of a row ..
+#define JDA_EXR_TILE_ROWS 32u                                // .. times 32 rows (mcu_x0, mcu_y: the tile's place in units of these; count 1)
+#define JDA_EXR_WAVES 4u                                     // wavefronts (tile records) a workgroup of jda_exact_colour_rect
+// what each axis of a chroma plane gets: hs, vs the layout's factors, scale / up / cw the record's (scale 0 or 1: full size)
+JDA_HD void jda_exr_kinds(uint32_t hs, uint32_t vs, uint32_t scale, uint32_t up, uint32_t cw, uint32_t *kh, uint32_t *kv)
+{
+    *kh = *kv = JDA_EXR_NONE;
+    if (scale <= 1u) {
+        const bool narrow = hs == 2u && cw <= 2u;            // jdsample.c: no fancy h2v1 / h2v2 for a component at most two samples wide
+        if (hs == 2u) *kh = narrow ? JDA_EXR_REPLICATE : JDA_EXR_FANCY;
+        if (vs == 2u) *kv = narrow ? JDA_EXR_REPLICATE : JDA_EXR_FANCY;
+        return;
+    }
+    if (up == JDA_EX_UP_H2V1_FANCY) *kh = JDA_EXR_FANCY;
+    else if (up == JDA_EX_UP_H2V1_REPLICATE) *kh = JDA_EXR_REPLICATE;
+    else if (up == JDA_EX_UP_H1V2_FANCY) *kv = JDA_EXR_FANCY;
+    else if (up == JDA_EX_UP_H1V2_REPLICATE) *kv = JDA_EXR_REPLICATE;
+}
+// the samples one axis reads for the pixels [p0, p1] (inclusive) of a component `ext` samples long: [*lo, *hi]
+JDA_HD void jda_exr_reads(uint32_t kind, uint32_t p0, uint32_t p1, uint32_t ext, uint32_t *lo, uint32_t *hi)
+{
+    if (kind == JDA_EXR_NONE) { *lo = p0; *hi = p1; return; }
+    uint32_t a = p0 >> 1, b = p1 >> 1;
+    if (kind == JDA_EXR_FANCY) {
+        if (!(p0 & 1u) && a) a--;
+        if ((p1 & 1u) && b + 1u < ext) b++;
+    }
+    *lo = a; *hi = b < ext ? b : ext - 1u;
+}
+// the bytes sx .. sx + 3 of a plane's row (row: its byte offset) as a dword, of which the first n are asked for; [x_lo, x_hi): the
+// samples of the row the rectangle reads -- a dword load only inside them
+template <class IO> JDA_HD uint32_t jda_exr_row4(IO &io, const uint8_t *plane, uint32_t row, uint32_t sx, uint32_t n, uint32_t x_lo, uint32_t x_hi)
+{
+    const uint32_t a = sx & 3u, b = sx - a;
+    if (a == 0u) { if (sx + 4u <= x_hi) return io.ld32(plane, row + sx); }
+    else if (b >= x_lo && b + 8u <= x_hi) {
+        const uint32_t lo = io.ld32(plane, row + b), hi = io.ld32(plane, row + b + 4u);
+        return (lo >> (8u * a)) | (hi << (32u - 8u * a));
+    }
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) if (k < n) v |= io.ld8(plane, row + sx + k) << (8u * k);
+    return v;
+}
+// the upsampled samples of a chroma plane under the source pixels sx .. sx + n - 1 of source row sy (out[n ..] are not meaningful)
+template <class IO>
+JDA_HD void jda_exr_chroma4(IO &io, const jda_ex_desc &X, const jda_exr_rec &R, const uint8_t *plane, uint32_t kh, uint32_t kv, uint32_t sx, uint32_t sy, uint32_t n, uint32_t *out)
+{
+    const uint32_t j = kv == JDA_EXR_NONE ? sy : sy >> 1;
+    const uint32_t jn = kv == JDA_EXR_FANCY ? ((sy & 1u) ? (j + 1u < X.ch ? j + 1u : j) : (j ? j - 1u : 0u)) : j;
+    const uint32_t row = j * X.pitch_c, rown = jn * X.pitch_c;
+    if (kh == JDA_EXR_NONE) {
+        const uint32_t a = jda_exr_row4(io, plane, row, sx, n, R.x, R.x + R.w);
+        if (kv != JDA_EXR_FANCY) {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) out[k] = (a >> (8u * k)) & 255u;
+            return;
+        }
+        const uint32_t b = jda_exr_row4(io, plane, rown, sx, n, R.x, R.x + R.w), bias = 1u + (sy & 1u);
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) out[k] = (3u * ((a >> (8u * k)) & 255u) + ((b >> (8u * k)) & 255u) + bias) >> 2;
+        return;
+    }
+    const uint32_t i0 = sx >> 1, p = sx & 1u, last = X.cw - 1u;
+    if (kh == JDA_EXR_REPLICATE) {
+        const uint32_t ie = (sx + n - 1u) >> 1;              // the last sample a pixel of the quad lies over
+        uint32_t s[3];
+#pragma unroll
+        for (uint32_t k = 0; k < 3u; k++) {
+            const uint32_t i = i0 + k <= ie ? i0 + k : i0;
+            s[k] = io.ld8(plane, row + (i < last ? i : last));
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) out[k] = s[(p + k) >> 1];
+        return;
+    }
+    // fancy: s[i0 - 1 .. i0 + 2], clamped, of which a quad that begins on an odd pixel does not read the first, a short one not the last
+    uint32_t t[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        const bool need = k == 0u ? p == 0u : k == 1u ? true : k == 2u ? n + p >= 2u : n + p >= 4u;
+        uint32_t i = need ? i0 + k : i0 + 1u;
+        i = i ? i - 1u : 0u;
+        i = i < last ? i : last;
+        const uint32_t a = io.ld8(plane, row + i);
+        t[k] = kv == JDA_EXR_FANCY ? 3u * a + io.ld8(plane, rown + i) : a;
+    }
+    const uint32_t be = kv == JDA_EXR_FANCY ? 8u : 1u, bo = kv == JDA_EXR_FANCY ? 7u : 2u, sh = kv == JDA_EXR_FANCY ? 4u : 2u;
+    if (p == 0u) {
+        out[0] = (3u * t[1] + t[0] + be) >> sh; out[1] = (3u * t[1] + t[2] + bo) >> sh;
+        out[2] = (3u * t[2] + t[1] + be) >> sh; out[3] = (3u * t[2] + t[3] + bo) >> sh;
+    } else {
+        out[0] = (3u * t[1] + t[2] + bo) >> sh; out[1] = (3u * t[2] + t[1] + be) >> sh;
+        out[2] = (3u * t[2] + t[3] + bo) >> sh; out[3] = (3u * t[3] + t[2] + be) >> sh;
+    }
+}
+// lane = the destination pixels dx .. dx + 3 of destination row dy: nothing outside out_w x out_rows (the clip to the rectangle included)
+template <int MODE, bool RGB, class IO>
+JDA_HD void jda_exr_quad(IO &io, const jda_ex_desc &X, const jda_exr_rec &R, uint32_t kh, uint32_t kv, uint32_t dx, uint32_t dy)
+{
+    if (dy >= X.out_rows || dx >= X.out_w) return;
+    const uint32_t n = X.out_w - dx < 4u ? X.out_w - dx : 4u, sx = R.x + dx, sy = R.y + dy;
+    const uint32_t yw = jda_exr_row4(io, X.plane[0], sy * X.pitch_y, sx, n, R.x, R.x + R.w);
+    if (X.gray_out) {
+        const uint32_t o = dy * X.out_pitch + dx;
+        if (n == 4u) io.st32(X.out, o, yw);
+        else for (uint32_t k = 0; k < n; k++) io.st8(X.out, o + k, (yw >> (8u * k)) & 255u);
+        return;
+    }
+    uint32_t cb[4] = { 128u, 128u, 128u, 128u }, cr[4] = { 128u, 128u, 128u, 128u }, px[4];
+    if (MODE != JDA_MODE_GRAY) {
+        jda_exr_chroma4(io, X, R, X.plane[1], kh, kv, sx, sy, n, cb);
+        jda_exr_chroma4(io, X, R, X.plane[2], kh, kv, sx, sy, n, cr);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++)
+        px[k] = RGB ? ((yw >> (8u * k)) & 255u) | ((cb[k] & 255u) << 8) | ((cr[k] & 255u) << 16) | 0xff000000u : jda_ex_rgba((yw >> (8u * k)) & 255u, cb[k] & 255u, cr[k] & 255u);
+    const uint32_t o = dy * X.out_pitch + dx * 4u;
+    if (n == 4u) io.st128(X.out, o, px);
+    else for (uint32_t k = 0; k < n; k++) io.st32(X.out, o + 4u * k, px[k]);
+}
+// a wavefront = a tile record of the destination rectangle: the quads 64 mcu_x0 .. of the rows 32 mcu_y .., inside the clip
+template <int MODE, bool RGB, class IO> JDA_HD void jda_exr_colour_tile(IO &io, const jda_ex_desc &X, const jda_exr_rec &R, const jda_strip &S, uint32_t lane)
+{
+    typedef jda_ex_layout<MODE> E;
+    const uint32_t q0 = (uint32_t)S.mcu_x0 * JDA_EXR_TILE_QUADS, dy0 = (uint32_t)S.mcu_y * JDA_EXR_TILE_ROWS, all = (X.out_w + 3u) >> 2;
+    if (dy0 >= X.out_rows || q0 >= all) return;                  // (wave-uniform)
+    const uint32_t quads = all - q0 < JDA_EXR_TILE_QUADS ? all - q0 : JDA_EXR_TILE_QUADS;
+    const uint32_t rows = X.out_rows - dy0 < JDA_EXR_TILE_ROWS ? X.out_rows - dy0 : JDA_EXR_TILE_ROWS, items = quads * rows;
+    uint32_t kh, kv;
+    jda_exr_kinds((uint32_t)E::HS, (uint32_t)E::VS, X.scale, X.up, X.cw, &kh, &kv);
+    for (uint32_t it = lane; it < items; it += 64u) {
+        const uint32_t r = it / quads, q = it - r * quads;
+        jda_exr_quad<MODE, RGB>(io, X, R, kh, kv, 4u * (q0 + q), dy0 + r);
+    }
+}
+
 #endif // JDA_DEVICE_CORE_H

@@ -202,4 +202,60 @@ inline void jda_exact_fill_scaled(jda_ex_desc &X, const jda_image_info &I, const
     }
 }
 
+// ---- a pixel rectangle.  rect = {x, y, w, h} in pixels of the image at G's scale (G.w x G.h); mcu = {mx0, my0, mx1, my1}:
+// the smallest half-open MCU rectangle that holds every plane sample the definition reads for those pixels -- luma the pixels' own
+// samples, a chroma component what its upsampling reads an axis (jda_exr_kinds / jda_exr_reads, the functions the colour stage runs),
+// clamped to its own extent; luma_only: chroma adds nothing.  Refused (JDA_INVALID_PARAMETER): an empty rectangle, a negative origin,
+// one that leaves the image.
+inline int jda_exact_rect_plan(const jda_image_info &I, const jda_exact_geo &G, bool luma_only, const int32_t *rect, int32_t *mcu)
+{
+    if (!rect || rect[2] < 1 || rect[3] < 1 || rect[0] < 0 || rect[1] < 0) return JDA_INVALID_PARAMETER;
+    if ((int64_t)rect[0] + rect[2] > (int64_t)G.w || (int64_t)rect[1] + rect[3] > (int64_t)G.h) return JDA_INVALID_PARAMETER;
+    const uint32_t x0 = (uint32_t)rect[0], x1 = x0 + (uint32_t)rect[2] - 1u, y0 = (uint32_t)rect[1], y1 = y0 + (uint32_t)rect[3] - 1u;
+    const uint32_t lw = G.hs * G.ss_y, lh = G.vs * G.ss_y;       // luma samples an MCU
+    uint32_t mx0 = x0 / lw, mx1 = x1 / lw, my0 = y0 / lh, my1 = y1 / lh;
+    if (jda_mode_of(I) != JDA_MODE_GRAY && !luma_only) {
+        uint32_t kh, kv, a, b;
+        jda_exr_kinds(G.hs, G.vs, G.scale, G.up, G.cw, &kh, &kv);
+        jda_exr_reads(kh, x0, x1, G.cw, &a, &b);
+        if (a / G.ss_c < mx0) mx0 = a / G.ss_c;
+        if (b / G.ss_c > mx1) mx1 = b / G.ss_c;
+        jda_exr_reads(kv, y0, y1, G.ch, &a, &b);
+        if (a / G.ss_c < my0) my0 = a / G.ss_c;
+        if (b / G.ss_c > my1) my1 = b / G.ss_c;
+    }
+    mcu[0] = (int32_t)mx0; mcu[1] = (int32_t)my0;
+    mcu[2] = (int32_t)(mx1 + 1u < (uint32_t)I.mcus_x ? mx1 + 1u : (uint32_t)I.mcus_x); mcu[3] = (int32_t)(my1 + 1u < (uint32_t)I.mcus_y ? my1 + 1u : (uint32_t)I.mcus_y);
+    return JDA_SUCCESS;
+}
+// The colour stage's tile list over the destination rectangle: out_w x out_rows pixels (the clip), a record per JDA_EXR_TILE_QUADS quads
+// of JDA_EXR_TILE_ROWS rows (mcu_x0, mcu_y: the tile's place in those units; count 1), padded to whole workgroups as jda_append_strips pads.
+inline void jda_exact_rect_tiles(std::vector<jda_strip> &v, uint32_t image, uint32_t out_w, uint32_t out_rows)
+{
+    const uint32_t tx = ((out_w + 3u) / 4u + JDA_EXR_TILE_QUADS - 1u) / JDA_EXR_TILE_QUADS, ty = (out_rows + JDA_EXR_TILE_ROWS - 1u) / JDA_EXR_TILE_ROWS;
+    for (uint32_t y = 0; y < ty; y++)
+        for (uint32_t x = 0; x < tx; x++) {
+            jda_strip s;
+            memset(&s, 0, sizeof(s));
+            s.image = image; s.mcu_y = (uint16_t)y; s.mcu_x0 = (uint16_t)x; s.count = 1;
+            v.push_back(s);
+        }
+    while (v.size() % JDA_EXR_WAVES) {
+        jda_strip s;
+        memset(&s, 0, sizeof(s));
+        s.image = image;
+        v.push_back(s);
+    }
+}
+// The image's record of a rectangle decode: jda_exact_fill_scaled's, the clip that of the RECTANGLE (the surface holds it, not the image),
+// and the rectangle beside it.  At scale 1 the record's scale and up stay 0, as ever.
+inline void jda_exact_fill_rect(jda_ex_desc &X, jda_exr_rec &R, const jda_image_info &I, const uint16_t (*quant_zz)[64], const jda_exact_geo &G, uint8_t *scratch,
+                                const jda_output *out, int pixel_type, bool luma_only, const int32_t *rect)
+{
+    jda_exact_fill_scaled(X, I, quant_zz, G, scratch, out, pixel_type, luma_only);
+    R.x = (uint32_t)rect[0]; R.y = (uint32_t)rect[1]; R.w = (uint32_t)rect[2]; R.h = (uint32_t)rect[3];
+    X.out_w = out->width_px < rect[2] ? (uint32_t)(out->width_px < 0 ? 0 : out->width_px) : R.w;
+    X.out_rows = out->rows < rect[3] ? (uint32_t)(out->rows < 0 ? 0 : out->rows) : R.h;
+}
+
 #endif

@@ -3078,6 +3078,56 @@ extern "C" hipError_t jda_launch_exact_scaled(int mode, int stage, int scale, co
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// jda_exact_colour_rect<MODE, RGB>: the colour stage of a pixel rectangle (jda_exr_* in jda_device_core.h).  A wavefront = a
+// tile record of the DESTINATION rectangle (jda_exact_rect_tiles); the scale and the upsampling kind come from the image's record, the
+// rectangle from the record beside it, all wave-uniform.  No LDS, no scratch.
+template <int MODE, bool RGB>
+__global__ __launch_bounds__(64 * JDA_EXR_WAVES)
+void jda_exact_colour_rect(const jda_ex_desc *__restrict__ ex, const jda_exr_rec *__restrict__ rects, const jda_strip *__restrict__ tiles, uint32_t n_tiles)
+{
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ti = jda_uni32(blockIdx.x * JDA_EXR_WAVES + wave);
+    if (ti >= n_tiles) return;                                             // (wave-uniform)
+    const jda_strip S = jda_load_record(tiles + ti);
+    if (S.count == 0) return;
+    jda_ex_desc X;
+    jda_exs_desc_uniform(X, ex + S.image);
+    const jda_exr_rec JDA_GLOBAL *g = JDA_G(const jda_exr_rec, rects + S.image);
+    jda_exr_rec R;
+    R.x = jda_uni32(g->x); R.y = jda_uni32(g->y); R.w = jda_uni32(g->w); R.h = jda_uni32(g->h);
+    jda_exact_io io;
+    jda_exr_colour_tile<MODE, RGB>(io, X, R, S, lane);
+}
+template <int MODE, bool RGB>
+static hipError_t launch_exact_rect(const jda_ex_desc *ex, const jda_exr_rec *rects, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    const dim3 grid((n_tiles + JDA_EXR_WAVES - 1u) / JDA_EXR_WAVES), block(64u * JDA_EXR_WAVES);
+    JDA_LAUNCH((jda_exact_colour_rect<MODE, RGB>), grid, block, 0, stream, ex, rects, tiles, n_tiles);
+    return hipGetLastError();
+}
+extern "C" hipError_t jda_launch_exact_rect(int mode, int rgb, const jda_ex_desc *ex, const jda_exr_rec *rects, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+{
+    if (n_tiles == 0) return hipSuccess;
+    if (rgb) {
+        switch (mode) {
+        case JDA_MODE_444: return launch_exact_rect<JDA_MODE_444, true>(ex, rects, tiles, n_tiles, stream);
+        case JDA_MODE_420: return launch_exact_rect<JDA_MODE_420, true>(ex, rects, tiles, n_tiles, stream);
+        case JDA_MODE_422: return launch_exact_rect<JDA_MODE_422, true>(ex, rects, tiles, n_tiles, stream);
+        case JDA_MODE_440: return launch_exact_rect<JDA_MODE_440, true>(ex, rects, tiles, n_tiles, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
+    switch (mode) {
+    case JDA_MODE_GRAY: return launch_exact_rect<JDA_MODE_GRAY, false>(ex, rects, tiles, n_tiles, stream);
+    case JDA_MODE_444: return launch_exact_rect<JDA_MODE_444, false>(ex, rects, tiles, n_tiles, stream);
+    case JDA_MODE_420: return launch_exact_rect<JDA_MODE_420, false>(ex, rects, tiles, n_tiles, stream);
+    case JDA_MODE_422: return launch_exact_rect<JDA_MODE_422, false>(ex, rects, tiles, n_tiles, stream);
+    case JDA_MODE_440: return launch_exact_rect<JDA_MODE_440, false>(ex, rects, tiles, n_tiles, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
 extern "C" hipError_t jda_internal_set_wgtrace(unsigned long long *dev_buf)
 {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_jda_wgtrace), &dev_buf, sizeof(dev_buf));

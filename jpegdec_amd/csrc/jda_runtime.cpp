@@ -2169,10 +2169,14 @@ int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
 // three-component image of their layout (record i), component 3 as a gray image (record n + i: the records are 2 n with the flag) whose
 // tiles join the call's gray launch and write the fourth plane; jda_exact_colour4 then takes the tiles of record i.  planes: four entries
 // an image with the flag (planes[4 i + c]), three without.
-struct exact_image { int kind; jda_image_info info; uint16_t quant[3][64]; jda_exact_geo G; size_t plane_at; bool luma_only; bool rgb; bool four; int colour; };
+// rects (jda_exact_decode_surfaces_rect; NULL: none): {x, y, w, h} an image, all zero: that image whole.  A rectangle image's
+// planes tiles are those of its MCU rectangle (jda_exact_rect_plan) in the same lists; its colour stage is jda_exact_colour_rect over tile
+// records of its destination, a list a (layout, RGB-coded or not).  A call with a rectangle keeps colour lists of its own for its whole
+// images, as a call with flags does: the planes lists then hold tiles the whole-image colour kernels must not walk.
+struct exact_image { int kind; jda_image_info info; uint16_t quant[3][64]; jda_exact_geo G; size_t plane_at; bool luma_only; bool rgb; bool four; int colour; bool rect; int32_t mcu[4]; };
 // stage_ms (the measuring hook's, else NULL): [0] the jda_exact_planes launches, [1] the jda_exact_colour launches
 static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const jda_output *planes,
-                      int32_t *status, float *stage_ms = NULL, const int32_t *scales = NULL, uint32_t flags = 0)
+                      int32_t *status, float *stage_ms = NULL, const int32_t *scales = NULL, uint32_t flags = 0, const int32_t *rects = NULL)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (n < 0) return JDA_INVALID_PARAMETER;
@@ -2192,6 +2196,12 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
     // with JDA_EXACT_COLOUR_MODELS the colour stage has lists of its own, [layout][log2 scale][YCbCr or gray | RGB-coded]: the images' tiles
     // once more, by what the stage does with the planes and whatever their source
     std::vector<jda_strip> cs_strips[JDA_N_MODES][4][2];
+    bool any_rect = false;
+    for (int i = 0; i < n && rects && outputs; i++) any_rect = any_rect || rects[4 * i] || rects[4 * i + 1] || rects[4 * i + 2] || rects[4 * i + 3];
+    const bool own_cs = flags || any_rect;                       // the colour stage has lists of its own
+    std::vector<jda_strip> rect_strips[JDA_N_MODES][2];         // [layout][YCbCr or gray | RGB-coded]: the rectangles' destination tiles
+    std::vector<jda_exr_rec> rrec(any_rect ? (size_t)n : 0u);
+    if (any_rect) memset(rrec.data(), 0, rrec.size() * sizeof(jda_exr_rec));
     size_t scratch = 0;
     int planned = 0;
     for (int i = 0; i < n; i++) {
@@ -2223,6 +2233,9 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
         if (M.four) { M.info.ncomp = 3; M.info.bpp = 24; }     // (components 0..2 from here on: I is M.info)
         if (rc == JDA_SUCCESS && !jda_exact_scale_ok(scale)) rc = JDA_INVALID_PARAMETER;
         if (rc == JDA_SUCCESS) rc = M.four ? jda_exact_geometry4(I, kd->info.mcus_x != I.mcus_x || kd->info.mcus_y != I.mcus_y, &M.G) : jda_exact_geometry_scaled(I, M.luma_only, scale, &M.G);
+        const int32_t *rq = any_rect ? rects + 4 * i : NULL;
+        M.rect = rq && (rq[0] || rq[1] || rq[2] || rq[3]);
+        if (rc == JDA_SUCCESS && M.rect) rc = M.four ? JDA_UNSUPPORTED_FEATURE : jda_exact_rect_plan(I, M.G, M.luma_only, rq, M.mcu);
         if (rc == JDA_SUCCESS && outputs) {
             jda_image_info B = I;
             B.jpeg_type = 0;
@@ -2230,6 +2243,8 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
             jda_output O = outputs[i];                         // (a scaled image: the surface is held to the scaled size, not to the file's)
             if (scale > 1 && O.width_px > (int32_t)M.G.w) O.width_px = (int32_t)M.G.w;
             if (scale > 1 && O.rows > (int32_t)M.G.h) O.rows = (int32_t)M.G.h;
+            if (M.rect && O.width_px > rq[2]) O.width_px = rq[2];      // (a rectangle: the surface holds it, not the image)
+            if (M.rect && O.rows > rq[3]) O.rows = rq[3];
             rc = jda_fill_launch_desc(D, B, none, none, none, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, O, pt == JDA_CMYK8888 ? JDA_RGB8888 : pt, 0, NULL);      // (four bytes a pixel either way)
         } else if (rc == JDA_SUCCESS) {
             D.mode = (uint8_t)jda_mode_of(I); D.ncomp = (uint8_t)I.ncomp; D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
@@ -2254,14 +2269,18 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
             D.tables = src[i].coef->base; D.scan = src[i].coef->base + src[i].coef->off_entries;
         }
         const int g = M.G.scale == 8u ? 3 : M.G.scale == 4u ? 2 : M.G.scale == 2u ? 1 : 0;
-        jda_append_strips(strips[D.mode][g][M.kind], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        jda_append_strips(strips[D.mode][g][M.kind], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode, 0, M.rect ? M.mcu : NULL);
         if (M.four) {
             jda_dev_desc &DK = descs[(size_t)n + (size_t)i];
             DK.mode = (uint8_t)JDA_MODE_GRAY; DK.ncomp = 1; DK.mcus_x = (uint32_t)kd->info.mcus_x; DK.mcus_y = (uint32_t)kd->info.mcus_y;
             DK.tables = kd->base; DK.scan = kd->base + kd->off_entries;
             jda_append_strips(strips[JDA_MODE_GRAY][0][0], (uint32_t)(n + i), DK.mcus_x, DK.mcus_y, JDA_MODE_GRAY);
             if (outputs) jda_append_strips(c4_strips[D.mode], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
-        } else if (flags && outputs) jda_append_strips(cs_strips[D.mode][g][M.rgb ? 1 : 0], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        } else if (M.rect) {
+            const jda_output &O = outputs[i];
+            jda_exact_rect_tiles(rect_strips[D.mode][M.rgb ? 1 : 0], (uint32_t)i, (uint32_t)(O.width_px < rq[2] ? (O.width_px < 0 ? 0 : O.width_px) : rq[2]),
+                                 (uint32_t)(O.rows < rq[3] ? (O.rows < 0 ? 0 : O.rows) : rq[3]));
+        } else if (own_cs && outputs) jda_append_strips(cs_strips[D.mode][g][M.rgb ? 1 : 0], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
     }
     if (!planned) return JDA_SUCCESS;
     const size_t o_ex = align16(descs.size() * sizeof(jda_dev_desc)), o_src = o_ex + align16(ex.size() * sizeof(jda_ex_desc));
@@ -2276,6 +2295,11 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
             for (int f = 0; f < 2; f++) { cs_off[m][g][f] = bytes; bytes += cs_strips[m][g][f].size() * sizeof(jda_strip); }
     size_t c4_off[JDA_N_MODES];
     for (int m = 0; m < JDA_N_MODES; m++) { c4_off[m] = bytes; bytes += c4_strips[m].size() * sizeof(jda_strip); }
+    size_t rect_off[JDA_N_MODES][2];
+    for (int m = 0; m < JDA_N_MODES; m++)
+        for (int f = 0; f < 2; f++) { rect_off[m][f] = bytes; bytes += rect_strips[m][f].size() * sizeof(jda_strip); }
+    const size_t o_rect = bytes;
+    bytes += rrec.size() * sizeof(jda_exr_rec);
     const size_t o_scratch = (bytes + 255u) & ~(size_t)255u;
     uint8_t *blk = NULL;
     hipError_t e = jda_pool_alloc(ctx, (void **)&blk, o_scratch + scratch);
@@ -2287,6 +2311,7 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
         if (M.four)
             jda_exact_fill4(ex[(size_t)i], ex[(size_t)n + (size_t)i], M.info, M.quant, src[i].coef->k->raw_quant[0], M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt,
                             M.colour == JDA_CS_YCCK);
+        else if (M.rect) jda_exact_fill_rect(ex[(size_t)i], rrec[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, &outputs[i], pt, M.luma_only, rects + 4 * i);
         else jda_exact_fill_scaled(ex[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt, M.luma_only);
     }
     std::vector<uint8_t> blob(bytes, 0);
@@ -2303,6 +2328,10 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
                 if (!cs_strips[m][g][f].empty()) memcpy(blob.data() + cs_off[m][g][f], cs_strips[m][g][f].data(), cs_strips[m][g][f].size() * sizeof(jda_strip));
     for (int m = 0; m < JDA_N_MODES; m++)
         if (!c4_strips[m].empty()) memcpy(blob.data() + c4_off[m], c4_strips[m].data(), c4_strips[m].size() * sizeof(jda_strip));
+    for (int m = 0; m < JDA_N_MODES; m++)
+        for (int f = 0; f < 2; f++)
+            if (!rect_strips[m][f].empty()) memcpy(blob.data() + rect_off[m][f], rect_strips[m][f].data(), rect_strips[m][f].size() * sizeof(jda_strip));
+    if (!rrec.empty()) memcpy(blob.data() + o_rect, rrec.data(), rrec.size() * sizeof(jda_exr_rec));
     e = hipMemcpyAsync(blk, blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
     const jda_dev_desc *d_descs = (const jda_dev_desc *)blk;
     const jda_ex_desc *d_ex = (const jda_ex_desc *)(blk + o_ex);
@@ -2315,16 +2344,19 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
             for (int f = 0; f < 3 && e == hipSuccess; f++)
                 e = jda_launch_exact_scaled(m, f, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][g][f]), (uint32_t)strips[m][g][f].size(), ctx->stream);
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && !flags; m++)
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && !own_cs; m++)
         for (int g = 0; g < 4 && e == hipSuccess; g++)
             e = jda_launch_exact_scaled(m, 3, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][g][0]),
                                         (uint32_t)(strips[m][g][0].size() + strips[m][g][1].size() + strips[m][g][2].size()), ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && flags; m++)
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && own_cs; m++)
         for (int g = 0; g < 4 && e == hipSuccess; g++)
             for (int f = 0; f < 2 && e == hipSuccess; f++)
                 e = jda_launch_exact_scaled(m, 3 + f, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + cs_off[m][g][f]), (uint32_t)cs_strips[m][g][f].size(), ctx->stream);
     for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && flags; m++)
         e = jda_launch_exact_scaled(m, 5, 1, d_descs, d_ex, d_src, (const jda_strip *)(blk + c4_off[m]), (uint32_t)c4_strips[m].size(), ctx->stream);
+    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && any_rect; m++)
+        for (int f = 0; f < 2 && e == hipSuccess; f++)
+            e = jda_launch_exact_rect(m, f, d_ex, (const jda_exr_rec *)(blk + o_rect), (const jda_strip *)(blk + rect_off[m][f]), (uint32_t)rect_strips[m][f].size(), ctx->stream);
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
     for (int i = 0; i < n && e == hipSuccess && planes; i++) {
         const exact_image &M = im[(size_t)i];
@@ -2410,6 +2442,51 @@ int jda_exact_decode_planes_ex(jda_ctx *ctx, int32_t n, const jda_recode_source 
     if (ctx && n > 0 && !planes) return JDA_INVALID_PARAMETER;
     return exact_call(ctx, n, src, NULL, NULL, planes, status, NULL, scales, flags);
 }
+// The source rectangle {x0, y0, x1, y1} (half open) the taps of `filter` read when rect = {x, y, w, h} of a src_w x src_h image is resized
+// to out_w x out_h, clipped at the image: resize_upload's `reads`, host work only (what decode_to_tensors decodes of a cropped file)
+int jda_resize_reads(int32_t src_w, int32_t src_h, const int32_t *rect, int32_t out_w, int32_t out_h, int32_t filter, int32_t *reads)
+{
+    if (!rect || !reads || src_w <= 0 || src_h <= 0 || out_w <= 0 || out_h <= 0 || out_w > (1 << 24) || out_h > (1 << 24)) return JDA_INVALID_PARAMETER;
+    if (rect[0] < 0 || rect[1] < 0 || rect[2] <= 0 || rect[3] <= 0 || (int64_t)rect[0] + rect[2] > src_w || (int64_t)rect[1] + rect[3] > src_h) return JDA_INVALID_PARAMETER;
+    for (int a = 0; a < 2; a++) {
+        const int32_t in_size = a ? src_h : src_w, in0 = rect[a], in1 = rect[a] + rect[2 + a], out = a ? out_h : out_w;
+        uint32_t ksize = 0;
+        int rc = jda_resize_axis_ksize(in0, in1, out, &ksize, filter);
+        if (rc != JDA_SUCCESS) return rc;
+        std::vector<int32_t> tab((size_t)out * (2u + ksize));
+        rc = jda_resize_axis_taps(in_size, in0, in1, out, ksize, tab.data(), filter);
+        if (rc != JDA_SUCCESS) return rc;
+        reads[a] = tab[0]; reads[2 + a] = tab[2 * (size_t)(out - 1)] + tab[2 * (size_t)(out - 1) + 1];
+    }
+    return JDA_SUCCESS;
+}
+// ---- a pixel rectangle an image
+int jda_exact_decode_surfaces_rect(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const int32_t *scales,
+                                   uint32_t flags, const int32_t *rects, int32_t *status)
+{
+    if (flags & ~(uint32_t)JDA_EXACT_COLOUR_MODELS) return JDA_INVALID_PARAMETER;
+    if (ctx && n > 0 && !outputs) return JDA_INVALID_PARAMETER;
+    return exact_call(ctx, n, src, outputs, pixel_types, NULL, status, NULL, scales, flags, rects);
+}
+// the measuring hook with rectangles (tools/exact_bench.py --rect): stage_ms[1] holds every colour launch, jda_exact_colour_rect among them
+int jda_internal_exact_time_rect(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const int32_t *scales,
+                                 uint32_t flags, const int32_t *rects, int32_t *status, float *stage_ms)
+{
+    if (!stage_ms || (flags & ~(uint32_t)JDA_EXACT_COLOUR_MODELS) || (ctx && n > 0 && !outputs)) return JDA_INVALID_PARAMETER;
+    stage_ms[0] = stage_ms[1] = 0.f;
+    return exact_call(ctx, n, src, outputs, pixel_types, NULL, status, stage_ms, scales, flags, rects);
+}
+int jda_exact_rect_mcus(const jda_image_info *info, int32_t scale, int32_t pixel_type, const int32_t *rect, int32_t *mcu_rect)
+{
+    if (!info || !rect || !mcu_rect) return JDA_INVALID_PARAMETER;
+    int rc = jda_exact_check(*info, 0, pixel_type, 0, 0);
+    if (rc != JDA_SUCCESS) return rc;
+    jda_exact_geo G;
+    const bool luma_only = pixel_type == JDA_EIGHT_BIT_GRAYSCALE && info->ncomp == 3;
+    rc = jda_exact_geometry_scaled(*info, luma_only, scale, &G);
+    if (rc != JDA_SUCCESS) return rc;
+    return jda_exact_rect_plan(*info, G, luma_only, rect, mcu_rect);
+}
 // the measuring hook of the _ex calls (tools/exact_adobe_bench.py): stage_ms[0] the planes launches (K's gray tiles among them), stage_ms[1]
 // the colour launches (jda_exact_colour4, the RGB instances)
 int jda_internal_exact_time_ex(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const int32_t *scales,
@@ -2435,8 +2512,22 @@ int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t l
 {
     return jda_decode_to_host_exact_ex(ctx, jpeg, len, pixel_type, scale, 0u, host_pixels, pitch_bytes, rows);
 }
+static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect, void *host_pixels,
+                         int32_t pitch_bytes, int32_t rows, int32_t *tiles);
 int jda_decode_to_host_exact_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, void *host_pixels, int32_t pitch_bytes,
                                 int32_t rows)
+{
+    return exact_to_host(ctx, jpeg, len, pixel_type, scale, flags, NULL, host_pixels, pitch_bytes, rows, NULL);
+}
+int jda_decode_to_host_exact_rect(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect, void *host_pixels,
+                                  int32_t pitch_bytes, int32_t rows, int32_t *tiles)
+{
+    return exact_to_host(ctx, jpeg, len, pixel_type, scale, flags, rect, host_pixels, pitch_bytes, rows, tiles);
+}
+// rect (NULL or all zero: the whole image): the surface and the host rows hold the rectangle; tiles (may be NULL): [0] the planes-stage tiles
+// launched, [1] those of the whole image
+static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect, void *host_pixels,
+                         int32_t pitch_bytes, int32_t rows, int32_t *tiles)
 {
     if (!ctx) return JDA_ERROR_NO_DEVICE;
     if (flags & ~(uint32_t)JDA_EXACT_COLOUR_MODELS) return JDA_INVALID_PARAMETER;
@@ -2461,7 +2552,26 @@ int jda_decode_to_host_exact_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, 
     }
     if (rc != JDA_SUCCESS) return rc;
     if (pixel_type == JDA_CMYK8888 && !four) return JDA_INVALID_PARAMETER;
-    const int32_t ow = (I.width + scale - 1) / scale, oh = (I.height + scale - 1) / scale;      // (at scale 1 the file's own size)
+    int32_t ow = (I.width + scale - 1) / scale, oh = (I.height + scale - 1) / scale;      // (at scale 1 the file's own size)
+    const bool has_rect = rect && (rect[0] || rect[1] || rect[2] || rect[3]);
+    if (has_rect) {
+        if (four) return JDA_UNSUPPORTED_FEATURE;
+        if (rect[0] < 0 || rect[1] < 0 || rect[2] < 1 || rect[3] < 1 || (int64_t)rect[0] + rect[2] > ow || (int64_t)rect[1] + rect[3] > oh) return JDA_INVALID_PARAMETER;
+        ow = rect[2]; oh = rect[3];
+    }
+    if (tiles) {
+        tiles[0] = tiles[1] = 0;
+        jda_exact_geo G;
+        int32_t mcu[4];
+        const bool luma_only = pixel_type == JDA_EIGHT_BIT_GRAYSCALE && I.ncomp == 3;
+        if (!four && jda_exact_geometry_scaled(I, luma_only, scale, &G) == JDA_SUCCESS && (!has_rect || jda_exact_rect_plan(I, G, luma_only, rect, mcu) == JDA_SUCCESS)) {
+            std::vector<jda_strip> part, whole;
+            jda_append_strips(part, 0, (uint32_t)I.mcus_x, (uint32_t)I.mcus_y, jda_mode_of(I), 0, has_rect ? mcu : NULL);
+            jda_append_strips(whole, 0, (uint32_t)I.mcus_x, (uint32_t)I.mcus_y, jda_mode_of(I));
+            for (const jda_strip &t : part) tiles[0] += t.count ? 1 : 0;
+            for (const jda_strip &t : whole) tiles[1] += t.count ? 1 : 0;
+        }
+    }
     if ((int64_t)pitch_bytes < (int64_t)ow * (pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4)) return JDA_INVALID_PARAMETER;      // (a row holds the image's width, as a surface's does)
     jda_image *img = NULL;
     jda_coef_image *cimg = NULL;
@@ -2487,7 +2597,7 @@ int jda_decode_to_host_exact_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, 
         jda_output O;
         O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = ow; O.rows = drows;
         int32_t st = JDA_SUCCESS;
-        rc = exact_call(ctx, 1, &S, &O, &pixel_type, NULL, &st, NULL, &scale, flags);
+        rc = exact_call(ctx, 1, &S, &O, &pixel_type, NULL, &st, NULL, &scale, flags, has_rect ? rect : NULL);
         if (rc == JDA_SUCCESS) rc = st;
     }
     if (rc == JDA_SUCCESS && drows > 0) {

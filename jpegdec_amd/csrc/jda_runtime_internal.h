@@ -229,6 +229,9 @@ extern "C" hipError_t jda_launch_exact(int mode, int stage, const jda_dev_desc *
 // stage, scale> (stage 0 / 1 / 2), jda_exact_colour_scaled<mode> (stage 3)
 extern "C" hipError_t jda_launch_exact_scaled(int mode, int stage, int scale, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles,
                                               uint32_t n_tiles, hipStream_t stream);
+// the colour stage of pixel rectangles: jda_exact_colour_rect<mode, rgb> over tile records of the destination rectangles
+// (jda_exact_rect_tiles) of images of ONE layout, whatever their scales; rects: a record an image, beside ex
+extern "C" hipError_t jda_launch_exact_rect(int mode, int rgb, const jda_ex_desc *ex, const jda_exr_rec *rects, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
 inline uint32_t jda_flat_items(const jda_dev_desc &D) { return (D.mode == JDA_MODE_GRAY ? (D.mcus_x + 3u) >> 2 : D.mcus_x) * D.mcus_y; }      // quads of blocks (gray) / MCUs
 
 #endif

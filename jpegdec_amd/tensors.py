@@ -131,10 +131,10 @@ def prescale_option(info, pixel_type, options, size):
     return 0
 
 
-def _exact_batch(ctx, files, infos, outs, pt, scales=None, colour_models=False):
+def _exact_batch(ctx, files, infos, outs, pt, scales=None, colour_models=False, rects=None):
     """decode_to_tensors(decoder="libjpeg"): the files resident -- baseline ones with the device pre-scan's index, progressive ones as
     coefficient images in whichever form is smaller -- and ONE exact_decode call into the surfaces `outs` (scales: file k at 1 / scales[k],
-    libjpeg's scaled decode; colour_models: exact_decode's); -> the statuses"""
+    libjpeg's scaled decode; colour_models: exact_decode's; rects: exact_decode's -- the surfaces then hold the rectangles); -> the statuses"""
     n = len(files)
     # (CMYK, YCCK, and an extended-sequential frame, which jda_prepare does not take: a coefficient image whatever the SOF type)
     four = [colour_models and (infos[k].ncomp == 4 or getattr(infos[k], "via_coef_prepare", False)) for k in range(n)]
@@ -148,7 +148,7 @@ def _exact_batch(ctx, files, infos, outs, pt, scales=None, colour_models=False):
             if infos[k].jpeg_type == 1 or four[k]:
                 hosts.append(B.CoefImage.from_file(files[k]) if four[k] else B.CoefImage(files[k]))
                 sources[k] = B.DeviceCoef(ctx, hosts[-1], B.COEF_AUTO)
-        return B.exact_decode(ctx, sources, outs, [pt] * n, scales, colour_models)
+        return B.exact_decode(ctx, sources, outs, [pt] * n, scales, colour_models, rects)
     finally:
         for d in sources:
             if d is not None:
@@ -186,7 +186,8 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     draft=(h, w) any other size; each file is decoded at the scale Pillow would choose for that request (exact_draft_scale: the largest of
     1/8, 1/4, 1/2, 1 that keeps both sides at or above it) by libjpeg's reduced-size IDCTs (jda_exact_decode_surfaces_scaled) and resized
     from there, so that the tensor is Pillow's draft() -> convert("RGB") -> resize() bit for bit.  With decoder="reference", with crops= or
-    without size= it is a ValueError.
+    without size= it is a ValueError.  With crops= this road decodes of each file only the MCUs the resize of its crop reads
+    (jda_exact_decode_surfaces_rect, into a surface of that rectangle's size); the tensor is the one a whole decode gives.
     colour_models (decoder="libjpeg"; jda_exact_decode_surfaces_ex with JDA_EXACT_COLOUR_MODELS): True takes files with an Adobe APP14 segment
     and reads every one- or three-component file by libjpeg's own rule (exact_probe) -- Photoshop's YCbCr files (transform 1) as any YCbCr
     file, RGB-coded ones (Adobe transform 0 without JFIF, or component ids 'R', 'G', 'B' without either marker) as the R, G, B they hold.
@@ -273,6 +274,19 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
         for k, (i, s) in enumerate(zip(infos, scales)):
             w, h = -(-i.width // s), -(-i.height // s)
             geos[k] = dict(geos[k], canvas_w=w, canvas_h=h, out_w=w, out_h=h)
+    rects = None
+    if decoder == "libjpeg" and crops is not None:
+        # only what the resize reads of each file is decoded (jda_exact_decode_surfaces_rect): the source rectangle of the filter's taps for
+        # the crop, clipped at the image, into a surface of that size; the crop moves by the rectangle's origin.  (A four-component file has
+        # no rectangle decode: it stays whole.)
+        rects, crops = [None] * n, list(crops)
+        for k, i in enumerate(infos):
+            if i.ncomp == 4:
+                continue
+            x0, y0, x1, y1 = B.resize_reads((i.width, i.height), crops[k], (size[1], size[0]), filt)
+            rects[k] = (x0, y0, x1 - x0, y1 - y0)
+            crops[k] = (crops[k][0] - x0, crops[k][1] - y0, crops[k][2], crops[k][3])
+            geos[k] = dict(geos[k], canvas_w=x1 - x0, canvas_h=y1 - y0, out_w=x1 - x0, out_h=y1 - y0)
     bpp = 4 if (decoder == "libjpeg" and pt == B.RGB8888) else geos[0]["bpp"]
     pitches = [(g["canvas_w"] * bpp + 15) & ~15 for g in geos]
     offs, total = [], 0
@@ -309,7 +323,7 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
             rbase = ctx.malloc(rbytes * n)
         outs = [(base + offs[k], pitches[k], geos[k]["canvas_w"], geos[k]["canvas_h"]) for k in range(n)]
         if decoder == "libjpeg":
-            status = _exact_batch(ctx, files, infos, outs, pt, scales, bool(colour_models))
+            status = _exact_batch(ctx, files, infos, outs, pt, scales, bool(colour_models), rects)
         else:
             pipe = B.Pipeline(ctx, max_images=n, depth=1)
             try:
