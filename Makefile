@@ -11,7 +11,7 @@ EXTRA ?=
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -shared -fwrapv -pthread -Wall -Wno-unused-function -Xarch_host -ffp-contract=off -Iinclude $(EXTRA)
 LIB = jpegdec_amd/libjpegdec_amd.so
 LIB_SRCS = $(CSRC)/jda_frontend.cpp $(CSRC)/jda_progressive.cpp $(CSRC)/jda_runtime.cpp $(CSRC)/jda_encode_progressive.cpp $(CSRC)/jda_pipeline.cpp $(CSRC)/jda_node.cpp $(CSRC)/jda_kernels.hip $(CSRC)/JPEGDEC.cpp
-LIB_DEPS = $(LIB_SRCS) $(CSRC)/jda_runtime_internal.h $(CSRC)/jda_internal.h $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_pack_plan.h $(CSRC)/jda_unpack_plan.h $(CSRC)/jda_exact_plan.h $(CSRC)/jda_resize_plan.h $(CSRC)/jda_encode_plan.h $(CSRC)/jda_encode_prog_plan.h $(CSRC)/jda_recode_plan.h $(CSRC)/jda_prescan_plan.h include/jpegdec_amd.h include/JPEGDEC.h
+LIB_DEPS = $(LIB_SRCS) $(CSRC)/jda_runtime_internal.h $(CSRC)/jda_internal.h $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_pack_plan.h $(CSRC)/jda_unpack_plan.h $(CSRC)/jda_exact_plan.h $(CSRC)/jda_resize_plan.h $(CSRC)/jda_reduce_plan.h $(CSRC)/jda_thumbnail_plan.h $(CSRC)/jda_encode_plan.h $(CSRC)/jda_encode_prog_plan.h $(CSRC)/jda_recode_plan.h $(CSRC)/jda_prescan_plan.h include/jpegdec_amd.h include/JPEGDEC.h
 
 all: lib oracle hostsim classshim
 
@@ -22,7 +22,7 @@ $(LIB): $(LIB_DEPS)
 oracle:
 	$(MAKE) -C oracle all
 
-hostsim: tests/hostsim/libjda_exactrectsim.so tests/hostsim/libjda_exactadobesim.so tests/hostsim/libjda_exactscaledsim.so tests/hostsim/libjda_exactsim.so tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so tests/hostsim/libjda_encodeprogsim.so tests/hostsim/libjda_recodesim.so tests/hostsim/libjda_recodexfsim.so tests/hostsim/libjda_unpacksim.so
+hostsim: tests/hostsim/libjda_reducesim.so tests/hostsim/libjda_exactrectsim.so tests/hostsim/libjda_exactadobesim.so tests/hostsim/libjda_exactscaledsim.so tests/hostsim/libjda_exactsim.so tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/libjda_encodesim.so tests/hostsim/libjda_huffoptsim.so tests/hostsim/libjda_resizefilterssim.so tests/hostsim/libjda_encodeprogsim.so tests/hostsim/libjda_recodesim.so tests/hostsim/libjda_recodexfsim.so tests/hostsim/libjda_unpacksim.so
 tests/hostsim/libjda_hostsim.so: tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp $(CSRC)/jda_device_core.h $(CSRC)/jda_plan.h $(CSRC)/jda_prescan_plan.h $(CSRC)/jda_internal.h
 	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -Wall -Wno-unused-function -Wno-unknown-pragmas -Iinclude -pthread -o $@ tests/hostsim/hostsim.cpp $(CSRC)/jda_frontend.cpp
 
@@ -118,6 +118,17 @@ tests/hostsim/libjda_resizefilterssim.so: $(RESIZEFSIM_DEPS)
 resizefiltersasan: tests/hostsim/resize_filters_asan
 tests/hostsim/resize_filters_asan: tests/hostsim/resize_filters_main.cpp $(RESIZEFSIM_DEPS)
 	$(CXX) -O1 -g -std=c++17 -fwrapv -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/resize_filters_main.cpp tests/hostsim/resize_filters_sim.cpp
+
+# the reduce kernel's two phases, lane by lane, the argument checks of jda_reduce_surfaces and jda_resize_surfaces_box, the tap tables of
+# fractional boxes and the thumbnail plan on the CPU (tests/test_thumbnail_cpu.py) -- test infrastructure.  -ffp-contract=off: the taps and
+# the plan are Pillow's only in Pillow's order of operations
+REDUCESIM_DEPS = tests/hostsim/reduce_sim.cpp $(CSRC)/jda_thumbnail_plan.h $(CSRC)/jda_reduce_plan.h $(CSRC)/jda_resize_plan.h $(CSRC)/jda_device_core.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
+tests/hostsim/libjda_reducesim.so: $(REDUCESIM_DEPS)
+	$(CXX) -O2 -std=c++17 -fPIC -shared -fwrapv -ffp-contract=off -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/reduce_sim.cpp
+# .. and the same with a main of its own under AddressSanitizer + UBSan: a program, nothing loaded into an interpreter
+thumbasan: tests/hostsim/thumb_asan
+tests/hostsim/thumb_asan: tests/hostsim/thumb_main.cpp $(REDUCESIM_DEPS)
+	$(CXX) -O1 -g -std=c++17 -fwrapv -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/thumb_main.cpp tests/hostsim/reduce_sim.cpp
 
 # the encode kernels' six stages, lane by lane, the header builder and the argument checks of jda_encode_surfaces on the CPU
 # (tests/test_encode_cpu.py) -- test infrastructure
@@ -230,10 +241,10 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/hostsim/libjda_exactrectsim.so tests/hostsim/exact_rect_asan tests/hostsim/libjda_exactadobesim.so tests/hostsim/exact_adobe_asan tests/hostsim/libjda_exactscaledsim.so tests/hostsim/exact_scaled_asan tests/hostsim/libjda_exactsim.so tests/hostsim/exact_asan tests/hostsim/libjda_unpacksim.so tests/hostsim/unpack_asan tests/hostsim/libjda_recodexfsim.so tests/hostsim/recode_xf_asan tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
+	rm -f tests/hostsim/libjda_reducesim.so tests/hostsim/thumb_asan tests/hostsim/libjda_exactrectsim.so tests/hostsim/exact_rect_asan tests/hostsim/libjda_exactadobesim.so tests/hostsim/exact_adobe_asan tests/hostsim/libjda_exactscaledsim.so tests/hostsim/exact_scaled_asan tests/hostsim/libjda_exactsim.so tests/hostsim/exact_asan tests/hostsim/libjda_unpacksim.so tests/hostsim/unpack_asan tests/hostsim/libjda_recodexfsim.so tests/hostsim/recode_xf_asan tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
-.PHONY: exactrectasan exactadobeasan exactscaledasan exactasan all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan recodexfasan resizefiltersasan unpackasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
+.PHONY: thumbasan exactrectasan exactadobeasan exactscaledasan exactasan all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan recodexfasan resizefiltersasan unpackasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
 
 # jda_node.cpp (host code above the C-ABI) over eight pretend devices -- test infrastructure, no GPU (tests/test_c_api.py)
 nodestub: tests/node_stub/node_stub_user

@@ -983,6 +983,58 @@ int jda_exact_rect_mcus(const jda_image_info *info, int32_t scale, int32_t pixel
 int jda_decode_to_host_exact_rect(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect,
                                   void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *tiles);
 
+/* ---- Pillow's Image.thumbnail(): draft, reduce, float-box resize
+ * im = Image.open(f); im.thumbnail((req_w, req_h), F, reducing_gap) is four steps, each Pillow's bit for bit: (1) the aspect-preserving
+ * final size, (2) draft(): the libjpeg-exact decode at 1/1, 1/2, 1/4 or 1/8, chosen from (int(req_w gap), int(req_h gap)), (3) inside
+ * resize(reducing_gap=): Image.reduce((fx, fy), box) when a whole factor >= 2 fits an axis, (4) the convolution resize of a FRACTIONAL box.
+ *
+ * jda_reduce_surfaces: Image.reduce((fx, fy), box) of n surfaces of one pixel size (1 or 4 bytes) in ONE launch of jda_reduce_tiles.
+ * factors: {fx, fy} per job, 1 .. JDA_REDUCE_MAX_FACTOR each (beyond: JDA_UNSUPPORTED_FEATURE; below 1: JDA_INVALID_PARAMETER).  boxes:
+ * {x0, y0, x1, y1} per job, half open, inside the source, not empty; NULL: every source whole.  An output pixel is the average of its cell
+ * of fx x fy source pixels (n of them; fewer in the box's last column and row), per byte ((sum + n / 2) * floor(2^24 / n)) >> 24 in
+ * unsigned 32-bit arithmetic -- Pillow's rule, which is not the rounded mean.  All four bytes of an RGB8888 pixel are averaged (A = 0xFF
+ * stays 0xFF).  dst[i].width_px x rows must be ceil(box_w / fx) x ceil(box_h / fy) (jda_reduce_geometry), else JDA_INVALID_PARAMETER;
+ * exactly those pixels are written.  Pointers and pitches as jda_resize_surfaces: 16-byte aligned, a destination may share no byte with a
+ * source or another destination.  fx = fy = 1 copies the box.  n == 0: JDA_SUCCESS, nothing launched.
+ *
+ * jda_resize_surfaces_box: jda_resize_surfaces_ex with Pillow's resize(size, F, box = (x0, y0, x1, y1)) for FLOAT boxes, four per job (not
+ * NULL).  Pillow's conditions, else JDA_INVALID_PARAMETER: 0 <= x0 < x1 <= width_px, 0 <= y0 < y1 <= rows.  The box is held as float32,
+ * its length is x1 - x0 rounded to float32, and from there the taps are worked out in double, as Pillow does.  Same kernels, same limits.
+ *
+ * jda_thumbnail_plan (host only): what Image.thumbnail((req_w, req_h), F, reducing_gap) does to a src_w x src_h JPEG file.  reducing_gap >=
+ * 1.0, or 0: Pillow's None (no draft, no reduce).  JDA_INVALID_PARAMETER: 0 < gap < 1 (or not a number), a size that is not positive, a
+ * filter id that is none.  JDA_UNSUPPORTED_FEATURE, the plan filled in all the same: a factor beyond JDA_REDUCE_MAX_FACTOR, a resize
+ * beyond JDA_RESIZE_MAX_KSIZE, or an image before the final resize more than 100 times as tall as wide whose height shrinks (Pillow
+ * then runs the vertical pass first, with other intermediates).
+ *
+ * jda_decode_to_host_thumbnail: parse, plan, the libjpeg-exact decode at the plan's scale (baseline and progressive files, as
+ * jda_decode_to_host_exact_scaled; four-component and RGB-coded files are refused as there), reduce, resize, copy back:
+ * np.asarray(im) after im.thumbnail((req_w, req_h), F, reducing_gap).  pixel_type: JDA_RGB8888 (bytes R, G, B, 0xFF) or
+ * JDA_EIGHT_BIT_GRAYSCALE (a gray file as Pillow's mode "L"; of a colour file the luma plane through the same steps, which no single
+ * Pillow call makes).  host_pixels: pitch_bytes >= out_w * bpp, rows >= out_h
+ * of the plan (a caller sizes it with jda_thumbnail_plan), else JDA_INVALID_PARAMETER and nothing launched.  out_w / out_h may be NULL.
+ * launches (may be NULL): [0] reduce launches, [1] resize launches of the call (0 or 1 each). */
+#define JDA_REDUCE_MAX_FACTOR 32
+typedef struct jda_thumbnail_steps {
+    int32_t out_w, out_h;           /* the final size (the source's when the request holds it: then no step at all) */
+    int32_t scale;                  /* draft(): 1, 2, 4 or 8 */
+    int32_t draft_w, draft_h;       /* im.size after draft(): ceil(src / scale) */
+    int32_t fx, fy;                 /* the reduce step's factors; 1, 1: there is none */
+    int32_t reduce_box[4];          /* its box {x0, y0, x1, y1} in the draft image (_get_safe_box) */
+    int32_t reduced_w, reduced_h;   /* the image the resize reads: the reduce step's output, the draft image without one */
+    int32_t resize;                 /* 1: a resize of `box` to out_w x out_h follows; 0: the draft image is the result */
+    float box[4];                   /* {x0, y0, x1, y1} in the image the resize reads */
+} jda_thumbnail_steps;
+int jda_reduce_geometry(int32_t box_w, int32_t box_h, int32_t fx, int32_t fy, int32_t *out_w, int32_t *out_h);
+int jda_reduce_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *factors, const int32_t *boxes,
+                        const jda_output *dst);
+int jda_resize_surfaces_box(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const float *boxes, const jda_output *dst,
+                            int32_t filter);
+int jda_thumbnail_plan(int32_t src_w, int32_t src_h, int32_t req_w, int32_t req_h, int32_t filter, double reducing_gap, jda_thumbnail_steps *plan);
+int jda_decode_to_host_thumbnail(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t req_w, int32_t req_h, int32_t filter, double reducing_gap,
+                                 int32_t pixel_type, void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *out_w, int32_t *out_h,
+                                 int32_t *launches);
+
 const char *jda_version(void);
 
 #ifdef __cplusplus

@@ -42,6 +42,12 @@ class ImageInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class ThumbnailSteps(C.Structure):
+    """jda_thumbnail_steps"""
+    _fields_ = [("out_w", C.c_int32), ("out_h", C.c_int32), ("scale", C.c_int32), ("draft_w", C.c_int32), ("draft_h", C.c_int32), ("fx", C.c_int32), ("fy", C.c_int32),
+                ("reduce_box", C.c_int32 * 4), ("reduced_w", C.c_int32), ("reduced_h", C.c_int32), ("resize", C.c_int32), ("box", C.c_float * 4)]
+
+
 class Output(C.Structure):
     _fields_ = [("pixels", C.c_void_p), ("pitch_bytes", C.c_int32), ("width_px", C.c_int32),
                 ("rows", C.c_int32)]
@@ -168,6 +174,12 @@ _PROTOTYPES = [
     ("jda_decode_to_host_packed", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_size_t] + [C.POINTER(C.c_int32)] * 3),
     ("jda_resize_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output)]),
     ("jda_resize_surfaces_ex", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(Output), C.c_int32]),
+    ("jda_resize_surfaces_box", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_float), C.POINTER(Output), C.c_int32]),
+    ("jda_reduce_geometry", C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_int32)] * 2),
+    ("jda_reduce_surfaces", C.c_int, [_P, C.c_int32, C.POINTER(Output), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Output)]),
+    ("jda_thumbnail_plan", C.c_int, [C.c_int32] * 5 + [C.c_double, C.POINTER(ThumbnailSteps)]),
+    ("jda_decode_to_host_thumbnail", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, C.c_int32, C.c_int32,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("jda_transcode_to_host", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
                                         C.c_int64, C.POINTER(C.c_int64)]),
     ("jda_transcode_to_host_ex", C.c_int, [_P, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
@@ -1069,6 +1081,77 @@ def resize_surfaces(ctx: Context, src, bytes_per_pixel, dst, rects=None, filter=
         ctx.check(ctx.lib.jda_resize_surfaces(ctx.handle, n, s, bytes_per_pixel, r, d), "jda_resize_surfaces")
     else:
         ctx.check(ctx.lib.jda_resize_surfaces_ex(ctx.handle, n, s, bytes_per_pixel, r, d, filter), "jda_resize_surfaces_ex")
+
+
+def resize_surfaces_box(ctx: Context, src, bytes_per_pixel, dst, boxes, filter=0):
+    """jda_resize_surfaces_box: resize_surfaces with Pillow's resize(size, F, box) for FLOAT boxes: boxes = list of (x0, y0, x1, y1), one a
+    job, 0 <= x0 < x1 <= width_px and the same for y.  The ends are held as float32, as Pillow's C side holds them."""
+    n = len(src)
+    s = (Output * max(n, 1))(*[Output(*o) for o in src])
+    d = (Output * max(n, 1))(*[Output(*o) for o in dst])
+    b = None if boxes is None else (C.c_float * max(4 * n, 1))(*[float(v) for q in boxes for v in q])
+    ctx.check(ctx.lib.jda_resize_surfaces_box(ctx.handle, n, s, bytes_per_pixel, b, d, filter), "jda_resize_surfaces_box")
+
+
+REDUCE_MAX_FACTOR = 32
+
+
+def reduce_geometry(box_w, box_h, fx, fy):
+    """jda_reduce_geometry: (out_w, out_h) = (ceil(box_w / fx), ceil(box_h / fy)), Pillow's size of Image.reduce((fx, fy), box); JdaError
+    for a size or a factor below 1 or a factor beyond REDUCE_MAX_FACTOR"""
+    ow, oh = C.c_int32(0), C.c_int32(0)
+    rc = load_library().jda_reduce_geometry(int(box_w), int(box_h), int(fx), int(fy), C.byref(ow), C.byref(oh))
+    if rc != 0:
+        raise JdaError(rc, "jda_reduce_geometry")
+    return ow.value, oh.value
+
+
+def reduce_surfaces(ctx: Context, src, bytes_per_pixel, factors, dst, boxes=None):
+    """jda_reduce_surfaces: Pillow's Image.reduce((fx, fy), box), bit for bit, of every job in one launch.  src / dst = lists of (device_ptr,
+    pitch_bytes, width_px, rows) of RGB8888 (4) or GRAY8 (1) surfaces -- a destination's width_px x rows must be reduce_geometry's --,
+    factors = list of (fx, fy), boxes = list of (x0, y0, x1, y1) or None: every source whole."""
+    n = len(src)
+    s = (Output * max(n, 1))(*[Output(*o) for o in src])
+    d = (Output * max(n, 1))(*[Output(*o) for o in dst])
+    f = None if factors is None else (C.c_int32 * max(2 * n, 1))(*[int(v) for q in factors for v in q])
+    b = None if boxes is None else (C.c_int32 * max(4 * n, 1))(*[int(v) for q in boxes for v in q])
+    ctx.check(ctx.lib.jda_reduce_surfaces(ctx.handle, n, s, bytes_per_pixel, f, b, d), "jda_reduce_surfaces")
+
+
+def thumbnail_plan(src_w, src_h, size, filter=RESIZE_BICUBIC, reducing_gap=2.0) -> dict:
+    """jda_thumbnail_plan: what Image.thumbnail(size, F, reducing_gap) does to a src_w x src_h JPEG file -- out (w, h): the final size;
+    scale: draft()'s; draft (w, h): the decoded size; factors (fx, fy) and reduce_box (x0, y0, x1, y1): the reduce step, (1, 1) without
+    one; reduced (w, h): the image the resize reads; resize: whether there is one; box: its float box.  reducing_gap None (or 0): Pillow's
+    None.  JdaError for what the call refuses (a plan it cannot run is never handed out)."""
+    t = ThumbnailSteps()
+    rc = load_library().jda_thumbnail_plan(int(src_w), int(src_h), int(size[0]), int(size[1]), int(filter), float(reducing_gap or 0.0), C.byref(t))
+    if rc != 0:
+        raise JdaError(rc, "jda_thumbnail_plan")
+    return dict(out=(t.out_w, t.out_h), scale=t.scale, draft=(t.draft_w, t.draft_h), factors=(t.fx, t.fy), reduce_box=tuple(t.reduce_box),
+                reduced=(t.reduced_w, t.reduced_h), resize=bool(t.resize), box=tuple(t.box))
+
+
+def decode_to_host_thumbnail(ctx: Context, jpeg: bytes, size, filter=RESIZE_BICUBIC, reducing_gap=2.0, pixel_type=RGB8888):
+    """jda_decode_to_host_thumbnail: np.asarray(im) after im = Image.open(file); im.thumbnail(size, F, reducing_gap) -- (rc, out_h x out_w x 4
+    RGBA bytes (A = 0xFF) or out_h x out_w gray, (reduce launches, resize launches)); the pixels are None when the call refuses."""
+    info = ImageInfo()
+    rc = ctx.lib.jda_parse(jpeg, len(jpeg), C.byref(info))
+    if rc != 0:
+        raise JdaError(rc, "jda_parse")
+    bpp = 1 if pixel_type == GRAY8 else 4
+    t = ThumbnailSteps()
+    rc = ctx.lib.jda_thumbnail_plan(info.width, info.height, int(size[0]), int(size[1]), int(filter), float(reducing_gap or 0.0), C.byref(t))
+    launches = (C.c_int32 * 2)()
+    if rc != 0:
+        return rc, None, tuple(launches)
+    canvas = np.zeros((t.out_h, t.out_w * bpp), dtype=np.uint8)
+    ow, oh = C.c_int32(0), C.c_int32(0)
+    rc = ctx.lib.jda_decode_to_host_thumbnail(ctx.handle, jpeg, len(jpeg), int(size[0]), int(size[1]), int(filter), float(reducing_gap or 0.0), pixel_type,
+                                              canvas.ctypes.data_as(_P), canvas.shape[1], canvas.shape[0], C.byref(ow), C.byref(oh), launches)
+    if rc != 0:
+        return rc, None, tuple(launches)
+    assert (ow.value, oh.value) == (t.out_w, t.out_h)
+    return rc, (canvas.reshape(t.out_h, t.out_w, 4) if bpp == 4 else canvas), tuple(launches)
 
 
 def _sampling(s):

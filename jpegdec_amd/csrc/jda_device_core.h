@@ -3950,6 +3950,124 @@ template <int BPP, bool SIGNED = false, class IO> JDA_HD void jda_rs_vertical(co
     }
 }
 
+// ---- jda_rd_*: decoded surfaces shrunk by whole factors, Pillow's Image.reduce((fx, fy), box) -------------------------
+// An output pixel is the average of its cell of the box: fx x fy source pixels, fewer in the last column and the last row when the box is
+// no multiple of the factors.  Per byte of a pixel, with n the pixels of the cell, in unsigned 32-bit arithmetic
+//   out = ((sum + n / 2) * floor(2^24 / n)) >> 24          ((255 n + n / 2) * floor(2^24 / n) <= 255.5 * 2^24 < 2^32 for every n)
+// which is NOT the rounded mean (sum + n / 2) / n: about a cell in ten differs by one.  The multipliers of the four kinds of cell a box
+// has come from the host (jda_reduce_job::mul).
+// A workgroup owns one output TILE: JDA_RD_TILE_BYTES bytes (64 RGB8888 pixels, 256 gray ones) of th <= JDA_RD_TILE_ROWS output rows.
+//   1. load (jda_rd_load): the source bytes of the tile are, per source row, one run of bytes; a0, the aligned dword its first byte lies
+//      in, is column 0.  The items (output row r of the tile, dword column c) are dealt to the lanes in order: neighbouring lanes load
+//      neighbouring dwords of one row whatever the factors, a wave-instruction reads 256 contiguous bytes.  A lane adds the <= fy rows of
+//      its column in two registers (bytes 0 and 2, bytes 1 and 3, 16 bits each: fy * 255 < 2^16) and writes the four 16-bit column sums
+//      as ONE 8-byte LDS entry; entry c of a row lies at c + (c >> 5), see below.
+//   2. the workgroup barrier
+//   3. store (jda_rd_store): a lane = one aligned 16-byte vector (tid & 15) of one output row (tid >> 4), as in the resize: it adds the
+//      <= fx entries of each of its 4 pixels (RGB8888, ds_read_b64) or the <= fx 16-bit sums of each of its 16 bytes (gray), applies the
+//      rule and stores the vector; only a row's last vector may be partial, it goes out as the dwords and bytes in front of out_w * bpp.
+//      Neighbouring lanes read 4 fx entries apart; the one spare entry behind every 32 moves each group of 32 by one bank pair, so the 32
+//      lanes of a ds_read_b64 group lie on 32 different slots for fx = 1, 2, 4, 8 (the bare stride would put them on 8, 4, 2, 1).
+// The host picks th per job so that th rows of entries fit JDA_RD_LDS_BYTES.  Memory goes through an IO policy: the kernel
+// (jda_kernels.hip) and the lane-by-lane run on the CPU (tests/hostsim/reduce_sim.cpp) are the same code.
+#define JDA_RD_THREADS 256
+#define JDA_RD_TILE_BYTES 256u
+#define JDA_RD_TILE_ROWS 16u
+#define JDA_RD_LDS_BYTES (32u << 10)
+// LDS entries of one tile row: the dwords that hold fx * JDA_RD_TILE_BYTES bytes beginning anywhere in a dword, spread as above
+JDA_HD uint32_t jda_rd_row_entries(uint32_t fx)
+{
+    const uint32_t cols = fx * (JDA_RD_TILE_BYTES / 4u) + 1u;
+    return cols + (cols >> 5) + 1u;
+}
+struct jda_rd_geo {                          // a job, wave-uniform
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t src_pitch, dst_pitch, x0, y0, bw, bh, fx, fy, out_w, out_h, th, row_entries;
+    uint32_t mul_whole, mul_right, mul_bottom, mul_corner;      // jda_reduce_job::mul[0 .. 3]
+};
+// the job a tile of the flat list belongs to (as jda_rs_find_job)
+JDA_HD uint32_t jda_rd_find_job(const jda_reduce_job *jobs, uint32_t n, uint32_t tile)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (JDA_G(const jda_reduce_job, jobs)[mid].tile0 <= tile) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// a ? b : c of VALUES (of two members of the job, the bare operator is a choice between their addresses and keeps the job in memory)
+JDA_HD uint32_t jda_rd_pick(bool a, uint32_t b, uint32_t c) { return a ? b : c; }
+// the rule, for one byte's sum over a cell of n pixels
+JDA_HD uint32_t jda_rd_mean(uint32_t sum, uint32_t n, uint32_t mul) { return ((sum + (n >> 1)) * mul) >> 24; }
+template <int BPP, class IO> JDA_HD void jda_rd_load(const jda_rd_geo &G, uint32_t tx, uint32_t ty, uint32_t tid, IO &io)
+{
+    const uint32_t tile_px = JDA_RD_TILE_BYTES / (uint32_t)BPP, opx0 = tx * tile_px;
+    const uint32_t npx = G.out_w - opx0 < tile_px ? G.out_w - opx0 : tile_px;
+    const uint32_t sx0 = G.x0 + opx0 * G.fx, sx1 = opx0 * G.fx + npx * G.fx < G.bw ? sx0 + npx * G.fx : G.x0 + G.bw;
+    const uint32_t a0 = (sx0 * (uint32_t)BPP) & ~3u, cols = (sx1 * (uint32_t)BPP - a0 + 3u) >> 2;
+    const uint32_t oy0 = ty * G.th, rows = G.out_h - oy0 < G.th ? G.out_h - oy0 : G.th;
+    const uint32_t items = rows * cols;
+    for (uint32_t w = tid; w < items; w += JDA_RD_THREADS) {
+        const uint32_t r = w / cols, c = w - r * cols;
+        const uint32_t sy = (oy0 + r) * G.fy, ny = G.bh - sy < G.fy ? G.bh - sy : G.fy;
+        const uint8_t *p = G.src + (size_t)(G.y0 + sy) * G.src_pitch + a0 + 4u * c;
+        uint32_t lo = 0, hi = 0;
+#pragma unroll 4
+        for (uint32_t y = 0; y < ny; y++) {
+            const uint32_t d = io.ld32(p + (size_t)y * G.src_pitch);
+            lo += d & 0x00ff00ffu;
+            hi += (d >> 8) & 0x00ff00ffu;
+        }
+        io.lds_wr64(r * G.row_entries + c + (c >> 5), (lo & 0xffffu) | (hi << 16), (lo >> 16) | (hi & 0xffff0000u));
+    }
+}
+template <int BPP, class IO> JDA_HD void jda_rd_store(const jda_rd_geo &G, uint32_t tx, uint32_t ty, uint32_t tid, IO &io)
+{
+    const uint32_t PX = 16u / (uint32_t)BPP;                                // pixels of a vector
+    const uint32_t vc = tid & 15u, orow = tid >> 4, oy = ty * G.th + orow, row_bytes = G.out_w * (uint32_t)BPP;
+    const uint32_t b0 = tx * JDA_RD_TILE_BYTES + vc * 16u;                  // the vector's first byte in its destination row
+    if (orow >= G.th || oy >= G.out_h || b0 >= row_bytes) return;
+    const uint32_t sy = oy * G.fy, ny = G.bh - sy < G.fy ? G.bh - sy : G.fy;
+    const uint32_t opx0 = tx * (JDA_RD_TILE_BYTES / (uint32_t)BPP), shift = ((G.x0 + opx0 * G.fx) * (uint32_t)BPP) & 3u;
+    const uint32_t base = orow * G.row_entries;
+    uint32_t out[4] = { 0u, 0u, 0u, 0u };
+#pragma unroll
+    for (uint32_t j = 0; j < PX; j++) {
+        const uint32_t px = vc * PX + j, ox = opx0 + px;                    // the pixel in its tile, in its row
+        if (ox >= G.out_w) continue;
+        const uint32_t sx = ox * G.fx, nx = G.bw - sx < G.fx ? G.bw - sx : G.fx;
+        const uint32_t n = nx * ny, mul = jda_rd_pick(nx < G.fx, jda_rd_pick(ny < G.fy, G.mul_corner, G.mul_right), jda_rd_pick(ny < G.fy, G.mul_bottom, G.mul_whole));
+        if (BPP == 4) {
+            uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+            for (uint32_t i = 0; i < nx; i++) {
+                const uint32_t e = px * G.fx + i;
+                uint32_t q[2];
+                io.lds_rd64(base + e + (e >> 5), q);
+                s0 += q[0] & 0xffffu; s1 += q[0] >> 16; s2 += q[1] & 0xffffu; s3 += q[1] >> 16;
+            }
+            out[j & 3u] = jda_rd_mean(s0, n, mul) | (jda_rd_mean(s1, n, mul) << 8) | (jda_rd_mean(s2, n, mul) << 16) | (jda_rd_mean(s3, n, mul) << 24);
+        } else {
+            uint32_t s = 0;
+            for (uint32_t i = 0; i < nx; i++) {
+                const uint32_t h = shift + px * G.fx + i, e = h >> 2;
+                s += io.lds_rd16((base + e + (e >> 5)) * 4u + (h & 3u));
+            }
+            out[j >> 2] |= jda_rd_mean(s, n, mul) << (8u * (j & 3u));
+        }
+    }
+    uint8_t *p = G.dst + (size_t)oy * G.dst_pitch + b0;
+    const uint32_t left = row_bytes - b0;
+    if (left >= 16u) { io.st128(p, out); return; }
+#pragma unroll
+    for (uint32_t d = 0; d < 4u; d++) {
+        if (4u * d + 4u <= left) { io.st32(p + 4u * d, out[d]); continue; }
+#pragma unroll
+        for (uint32_t b = 0; b < 4u; b++)
+            if (4u * d + b < left) io.st8(p + 4u * d + b, (out[d] >> (8u * b)) & 0xffu);
+    }
+}
+
 // ================================================================================================
 // jda_coef_tiles: a tile decoded from COEFFICIENTS (a coefficient image: every scan of a progressive file decoded on the host, or a
 // DCT-domain caller's own).  The tile is the decode kernel's -- one wave64, <= 64 consecutive blocks of an MCU row,

@@ -246,6 +246,19 @@ struct jda_resize_job {
     uint32_t src_pitch, dst_pitch, out_w, out_h, htab, vtab, hk, vk, tile0, tiles_x, th, pad_;
 };
 
+// One image of a reduce launch (device pointers; jda_rd_* in jda_device_core.h): the box {x0, y0, bw, bh} (pixels) of the
+// surface at src (16-byte aligned, src_pitch a multiple of 16) averaged over cells of fx x fy pixels into out_w x out_h =
+// ceil(bw / fx) x ceil(bh / fy) pixels at dst, the same alignment.  tile0: the index of the job's first tile in the launch's flat tile
+// list, tiles_x: tiles across the destination, th: output rows of a tile, row_entries: the LDS entries (8 bytes) of one of them.
+// mul[e]: floor(2^24 / n) of a cell of n pixels -- e = 0: a whole cell, 1: the narrower cells of the last column, 2: the lower cells of
+// the last row, 3: the corner cell of both (the values of a kind the box has none of are never read).
+struct jda_reduce_job {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t src_pitch, dst_pitch, x0, y0, bw, bh, fx, fy, out_w, out_h, tile0, tiles_x, th, row_entries;
+    uint32_t mul[4];
+};
+
 // One image of an encode call (device pointers; jda_en_* in jda_device_core.h): the rectangle {x, y, w, h} of the surface
 // at src becomes a baseline file at dst.  hs x vs: luma blocks of an MCU (1 x 1 with nc = 1: gray); cx x cy MCUs of bpm blocks; wb x hb:
 // the luma blocks that hold a pixel (the others of the MCU grid are dummies); ri: the restart interval in MCUs.  The job's blocks are

@@ -2244,6 +2244,60 @@ extern "C" hipError_t jda_launch_resize(const jda_resize_job *jobs, uint32_t n, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// jda_reduce_tiles<BPP>: decoded surfaces shrunk by whole factors, Pillow's Image.reduce (the rule, the tile and its LDS image: jda_rd_* in
+// jda_device_core.h).  grid = the flat list of every job's tiles, a workgroup finds its job by bisection (scalar loads)
+// and keeps it in SGPRs.  The lanes load the tile's source rows as contiguous dwords and add the rows of a cell in registers, the column
+// sums cross to the storing lanes through LDS behind ONE barrier.  LDS is sized by the launch (the largest tile of its jobs).  Global
+// accesses: aligned dword loads, aligned 16-byte stores (narrower only at a row's end).  No atomics, nothing shared between tiles.
+struct jda_reduce_io {
+    uint32_t *lds;
+    __device__ __forceinline__ uint32_t ld32(const uint8_t *p) const { return *(const jda_u32_alias JDA_GLOBAL *)JDA_G(const uint8_t, p); }
+    __device__ __forceinline__ void st128(uint8_t *p, const uint32_t *v) const { *(uint4 JDA_GLOBAL *)JDA_G(uint8_t, p) = make_uint4(v[0], v[1], v[2], v[3]); }
+    __device__ __forceinline__ void st32(uint8_t *p, uint32_t v) const { *(jda_u32_alias JDA_GLOBAL *)JDA_G(uint8_t, p) = v; }
+    __device__ __forceinline__ void st8(uint8_t *p, uint32_t v) const { *JDA_G(uint8_t, p) = (uint8_t)v; }
+    __device__ __forceinline__ void lds_wr64(uint32_t e, uint32_t w0, uint32_t w1) const { *(uint2 *)(lds + 2u * e) = make_uint2(w0, w1); }
+    __device__ __forceinline__ void lds_rd64(uint32_t e, uint32_t *v) const
+    {
+        const uint2 q = *(const uint2 *)(lds + 2u * e);
+        v[0] = q.x; v[1] = q.y;
+    }
+    __device__ __forceinline__ uint32_t lds_rd16(uint32_t h) const { return ((const uint16_t *)lds)[h]; }
+};
+template <int BPP>
+__global__ __launch_bounds__(JDA_RD_THREADS)
+void jda_reduce_tiles(const jda_reduce_job *__restrict__ jobs, uint32_t n_jobs)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t reduce_lds[];
+    const uint32_t tile = blockIdx.x;
+    const jda_reduce_job JDA_GLOBAL *job = JDA_G(const jda_reduce_job, jobs) + jda_uni32(jda_rd_find_job(jobs, n_jobs, tile));
+    jda_rd_geo G;
+    G.src = jda_uni_ptr(job->src); G.dst = jda_uni_ptr(job->dst);
+    G.src_pitch = jda_uni32(job->src_pitch); G.dst_pitch = jda_uni32(job->dst_pitch);
+    G.x0 = jda_uni32(job->x0); G.y0 = jda_uni32(job->y0); G.bw = jda_uni32(job->bw); G.bh = jda_uni32(job->bh);
+    G.fx = jda_uni32(job->fx); G.fy = jda_uni32(job->fy); G.out_w = jda_uni32(job->out_w); G.out_h = jda_uni32(job->out_h);
+    G.th = jda_uni32(job->th); G.row_entries = jda_uni32(job->row_entries);
+    G.mul_whole = jda_uni32(job->mul[0]); G.mul_right = jda_uni32(job->mul[1]); G.mul_bottom = jda_uni32(job->mul[2]); G.mul_corner = jda_uni32(job->mul[3]);
+    const uint32_t local = tile - jda_uni32(job->tile0), tiles_x = jda_uni32(job->tiles_x);
+    if (tiles_x == 0u || G.th == 0u || G.fx == 0u || G.fy == 0u) return;
+    const uint32_t ty = local / tiles_x, tx = local - ty * tiles_x;
+    jda_reduce_io io;
+    io.lds = reduce_lds;
+    jda_rd_load<BPP>(G, tx, ty, threadIdx.x, io);
+    __syncthreads();
+    jda_rd_store<BPP>(G, tx, ty, threadIdx.x, io);
+}
+// n jobs of one pixel size (1 or 4); n_tiles = the sum of their tiles, lds_bytes = what the largest of them needs (<= JDA_RD_LDS_BYTES)
+extern "C" hipError_t jda_launch_reduce(const jda_reduce_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, uint32_t lds_bytes, hipStream_t stream)
+{
+    if (n == 0 || n_tiles == 0) return hipSuccess;
+    if (!jobs || lds_bytes == 0u || lds_bytes > JDA_RD_LDS_BYTES) return hipErrorInvalidValue;
+    if (bytes_per_pixel == 4u) JDA_LAUNCH(jda_reduce_tiles<4>, dim3(n_tiles), dim3(JDA_RD_THREADS), lds_bytes, stream, jobs, n);
+    else if (bytes_per_pixel == 1u) JDA_LAUNCH(jda_reduce_tiles<1>, dim3(n_tiles), dim3(JDA_RD_THREADS), lds_bytes, stream, jobs, n);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // jda_encode_*: decoded surfaces encoded as baseline JPEG files (the stages and what a lane of each does: jda_en_* in jda_device_core.h;
 // DESIGN.md 5.13).  blocks, lengths and emit run a lane per block of the call's flat block list, count and write a lane per 64-byte chunk
 // of its flat chunk list (the job of a lane: bisection over the job records); scan runs a workgroup per job, twice in a call.  The

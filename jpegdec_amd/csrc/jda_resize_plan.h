@@ -10,6 +10,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <array>
@@ -80,16 +81,33 @@ static inline double jda_resize_filter_weight(int32_t filter, double x)
 
 // coefficients per output coordinate of an axis that takes [in0, in1) to out_size; JDA_UNSUPPORTED_FEATURE past JDA_RESIZE_MAX_KSIZE,
 // JDA_INVALID_PARAMETER for a filter id that is none
-static inline int jda_resize_axis_ksize(int32_t in0, int32_t in1, int32_t out_size, uint32_t *ksize, int32_t filter = JDA_RESIZE_BILINEAR)
+static inline int jda_resize_scale_ksize(double scale, uint32_t *ksize, int32_t filter)
 {
     *ksize = 0;
     if (filter < 0 || filter >= JDA_RESIZE_FILTERS) return JDA_INVALID_PARAMETER;
-    const double scale = (double)(in1 - in0) / (double)out_size;
     const double support = jda_resize_filter_support(filter) * (scale < 1.0 ? 1.0 : scale);
     const double c = ceil(support);
     if (c * 2.0 + 1.0 > (double)JDA_RESIZE_MAX_KSIZE) return JDA_UNSUPPORTED_FEATURE;
     *ksize = (uint32_t)((int)c * 2 + 1);
     return JDA_SUCCESS;
+}
+static inline int jda_resize_axis_ksize(int32_t in0, int32_t in1, int32_t out_size, uint32_t *ksize, int32_t filter = JDA_RESIZE_BILINEAR)
+{
+    return jda_resize_scale_ksize((double)(in1 - in0) / (double)out_size, ksize, filter);
+}
+// A FRACTIONAL [in0, in1), Pillow's resize(box = a float box): Pillow's C side holds the box as `float`, so both ends are float32 values
+// (a caller's double is rounded when it becomes the argument) and the box's length is their difference ROUNDED TO FLOAT32 (in1 - in0 of two
+// floats); only then everything is double: scale = (double)(in1 - in0) / out_size, center = in0 + (xx + 0.5) * scale.  A box kept in
+// double, or a length taken in double, moves a tap by one in about a case in a hundred.  Whole numbers below 2^24 give the integer
+// entry points' values.
+static inline double jda_resize_box_scale(float in0, float in1, int32_t out_size)
+{
+    const volatile float len = in1 - in0;            // (volatile: rounded to float32 whatever precision the compiler evaluates in)
+    return (double)len / (double)out_size;
+}
+static inline int jda_resize_axis_ksize(float in0, float in1, int32_t out_size, uint32_t *ksize, int32_t filter = JDA_RESIZE_BILINEAR)
+{
+    return jda_resize_scale_ksize(jda_resize_box_scale(in0, in1, out_size), ksize, filter);
 }
 
 // what the kernel's arithmetic leans on, checked on every table made for a filter other than BILINEAR (whose taps are 0 .. 2^22 by
@@ -113,16 +131,14 @@ static inline int jda_resize_axis_guard(int32_t filter, const int32_t *tab, int3
 }
 
 // the table of one axis: tab[2 i] = min, tab[2 i + 1] = cnt, tab[2 out_size + i ksize + x] = k[x] (zero behind cnt); the guard's answer
-static inline int jda_resize_axis_taps(int32_t in_size, int32_t in0, int32_t in1, int32_t out_size, uint32_t ksize, int32_t *tab,
-                                       int32_t filter = JDA_RESIZE_BILINEAR)
+static inline int jda_resize_scale_taps(int32_t in_size, double in0, double scale, int32_t out_size, uint32_t ksize, int32_t *tab, int32_t filter)
 {
-    const double scale = (double)(in1 - in0) / (double)out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
     const double support = jda_resize_filter_support(filter) * fs, ss = 1.0 / fs;
     std::vector<double> w((size_t)ksize);
     int32_t *k = tab + 2 * (size_t)out_size;
     for (int32_t xx = 0; xx < out_size; xx++, k += ksize) {
-        const double center = (double)in0 + ((double)xx + 0.5) * scale;
+        const double center = in0 + ((double)xx + 0.5) * scale;
         int32_t xmin = (int32_t)(center - support + 0.5), xmax = (int32_t)(center + support + 0.5);
         if (xmin < 0) xmin = 0;
         if (xmax > in_size) xmax = in_size;
@@ -141,6 +157,17 @@ static inline int jda_resize_axis_taps(int32_t in_size, int32_t in0, int32_t in1
     }
     return jda_resize_axis_guard(filter, tab, out_size, ksize);
 }
+static inline int jda_resize_axis_taps(int32_t in_size, int32_t in0, int32_t in1, int32_t out_size, uint32_t ksize, int32_t *tab,
+                                       int32_t filter = JDA_RESIZE_BILINEAR)
+{
+    return jda_resize_scale_taps(in_size, (double)in0, (double)(in1 - in0) / (double)out_size, out_size, ksize, tab, filter);
+}
+// .. of a fractional [in0, in1) (see jda_resize_axis_ksize's)
+static inline int jda_resize_axis_taps(int32_t in_size, float in0, float in1, int32_t out_size, uint32_t ksize, int32_t *tab,
+                                       int32_t filter = JDA_RESIZE_BILINEAR)
+{
+    return jda_resize_scale_taps(in_size, (double)in0, jda_resize_box_scale(in0, in1, out_size), out_size, ksize, tab, filter);
+}
 
 // output rows of a tile: the most (<= JDA_RS_TILE_ROWS) with which every tile's source rows fit the LDS budget (one at the ksize cap)
 static inline uint32_t jda_resize_tile_rows(const int32_t *vtab, uint32_t out_h, uint32_t *max_span)
@@ -158,15 +185,18 @@ static inline uint32_t jda_resize_tile_rows(const int32_t *vtab, uint32_t out_h,
 }
 
 // n >= 1 jobs, one filter for all of them.  rects: {x, y, w, h} per job, or NULL: the whole width_px x rows of every source.  dst[i].width_px x rows is the output size.
-static inline int jda_resize_plan_jobs(int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
-                                       jda_resize_plan_out *plan, int32_t filter = JDA_RESIZE_BILINEAR)
+// fboxes (jda_resize_surfaces_box; rects is then NULL): {x0, y0, x1, y1} per job, fractional, Pillow's conditions on them: 0 <= x0 < x1 <=
+// width_px and the same for y (a NaN fails them).  An axis table is shared by the jobs whose key -- source size, the two ends (the
+// floats' bits, and a mark that they are floats) and output size -- is the same.
+static inline int jda_resize_plan_jobs_any(int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const float *fboxes,
+                                           const jda_output *dst, jda_resize_plan_out *plan, int32_t filter)
 {
     plan->jobs.clear(); plan->tables.clear(); plan->reads.clear(); plan->ranges.clear(); plan->n_tiles = 0; plan->lds_bytes = 0;
     if (bytes_per_pixel != 1 && bytes_per_pixel != 4) return JDA_INVALID_PARAMETER;
     if (n <= 0 || !src || !dst || filter < 0 || filter >= JDA_RESIZE_FILTERS) return JDA_INVALID_PARAMETER;
     const uint32_t bpp = (uint32_t)bytes_per_pixel;
     struct axis { uint32_t off, ksize, th, span; int32_t r0, r1; };
-    std::map<std::array<int32_t, 4>, axis> axes;
+    std::map<std::array<int32_t, 5>, axis> axes;
     plan->jobs.resize((size_t)n);
     plan->reads.resize((size_t)n * 4);
     plan->ranges.reserve((size_t)n * 2);
@@ -179,21 +209,27 @@ static inline int jda_resize_plan_jobs(int32_t n, const jda_output *src, int32_t
         if (((uintptr_t)S.pixels & 15u) || ((uintptr_t)D.pixels & 15u) || (S.pitch_bytes & 15) || (D.pitch_bytes & 15)) return JDA_INVALID_PARAMETER;
         if ((int64_t)S.pitch_bytes < (int64_t)S.width_px * bpp || (int64_t)D.pitch_bytes < (int64_t)D.width_px * bpp) return JDA_INVALID_PARAMETER;
         const int64_t x = rects ? rects[4 * i] : 0, y = rects ? rects[4 * i + 1] : 0, w = rects ? rects[4 * i + 2] : S.width_px, h = rects ? rects[4 * i + 3] : S.rows;
-        if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > S.width_px || y + h > S.rows) return JDA_INVALID_PARAMETER;
-        const std::array<int32_t, 4> keys[2] = { { S.width_px, (int32_t)x, (int32_t)(x + w), D.width_px }, { S.rows, (int32_t)y, (int32_t)(y + h), D.rows } };
+        if (!fboxes && (x < 0 || y < 0 || w <= 0 || h <= 0 || x + w > S.width_px || y + h > S.rows)) return JDA_INVALID_PARAMETER;
+        std::array<int32_t, 5> keys[2] = { { S.width_px, (int32_t)x, (int32_t)(x + w), D.width_px, 0 }, { S.rows, (int32_t)y, (int32_t)(y + h), D.rows, 0 } };
+        const float *fb = fboxes ? fboxes + 4 * (size_t)i : NULL;
+        if (fb) {
+            if (!(fb[0] >= 0.0f && fb[0] < fb[2] && fb[2] <= (float)S.width_px && fb[1] >= 0.0f && fb[1] < fb[3] && fb[3] <= (float)S.rows)) return JDA_INVALID_PARAMETER;
+            for (int a = 0; a < 2; a++) { memcpy(&keys[a][1], &fb[a], 4); memcpy(&keys[a][2], &fb[2 + a], 4); keys[a][4] = 1; }
+        }
         const axis *A[2];
         for (int a = 0; a < 2; a++) {
             auto it = axes.find(keys[a]);
             if (it == axes.end()) {
                 axis N;
-                const int krc = jda_resize_axis_ksize(keys[a][1], keys[a][2], keys[a][3], &N.ksize, filter);
+                const int krc = fb ? jda_resize_axis_ksize(fb[a], fb[2 + a], keys[a][3], &N.ksize, filter) : jda_resize_axis_ksize(keys[a][1], keys[a][2], keys[a][3], &N.ksize, filter);
                 if (krc != JDA_SUCCESS) return krc;
                 const uint64_t dwords = (uint64_t)keys[a][3] * (2u + N.ksize);
                 if ((plan->tables.size() + dwords) * 4u > (uint64_t)JDA_RESIZE_MAX_TABLE_BYTES) return JDA_UNSUPPORTED_FEATURE;
                 N.off = (uint32_t)plan->tables.size();
                 plan->tables.resize(plan->tables.size() + (size_t)dwords);
                 int32_t *tab = plan->tables.data() + N.off;
-                const int grc = jda_resize_axis_taps(keys[a][0], keys[a][1], keys[a][2], keys[a][3], N.ksize, tab, filter);
+                const int grc = fb ? jda_resize_axis_taps(keys[a][0], fb[a], fb[2 + a], keys[a][3], N.ksize, tab, filter)
+                                   : jda_resize_axis_taps(keys[a][0], keys[a][1], keys[a][2], keys[a][3], N.ksize, tab, filter);
                 if (grc != JDA_SUCCESS) return grc;
                 const int32_t last = keys[a][3] - 1;
                 N.r0 = tab[0]; N.r1 = tab[2 * last] + tab[2 * last + 1];
@@ -234,6 +270,19 @@ static inline int jda_resize_plan_jobs(int32_t n, const jda_output *src, int32_t
     plan->n_tiles = (uint32_t)tiles;
     plan->lds_bytes = max_span * JDA_RS_TILE_DWORDS * 4u;
     return JDA_SUCCESS;
+}
+
+static inline int jda_resize_plan_jobs(int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst,
+                                       jda_resize_plan_out *plan, int32_t filter = JDA_RESIZE_BILINEAR)
+{
+    return jda_resize_plan_jobs_any(n, src, bytes_per_pixel, rects, NULL, dst, plan, filter);
+}
+// Pillow's resize(size, F, box = a float box) per job: boxes = {x0, y0, x1, y1} (NULL is an error: jda_resize_surfaces takes whole sources)
+static inline int jda_resize_plan_jobs_box(int32_t n, const jda_output *src, int32_t bytes_per_pixel, const float *boxes, const jda_output *dst,
+                                           jda_resize_plan_out *plan, int32_t filter)
+{
+    if (!boxes) { plan->jobs.clear(); plan->tables.clear(); plan->reads.clear(); plan->ranges.clear(); plan->n_tiles = 0; plan->lds_bytes = 0; return JDA_INVALID_PARAMETER; }
+    return jda_resize_plan_jobs_any(n, src, bytes_per_pixel, NULL, boxes, dst, plan, filter);
 }
 
 // .. nor with the launch's tables, once it is known where they lie: [tables_at, tables_at + 4 * tables.size())

@@ -25,6 +25,8 @@
 #include "jda_pack_plan.h"
 #include "jda_unpack_plan.h"
 #include "jda_resize_plan.h"
+#include "jda_reduce_plan.h"
+#include "jda_thumbnail_plan.h"
 #include "jda_encode_plan.h"
 #include "jda_recode_plan.h"
 #include "jda_exact_plan.h"
@@ -1738,12 +1740,12 @@ int jda_decode_to_host_packed(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, in
 // orient_upload does; resize_launch then queues the kernel.  reads (may be NULL): per job the source pixels {x0, y0, x1, y1} its taps read.
 struct resize_plan { void *block; uint32_t n, n_tiles, bpp, lds_bytes, signed_taps; const int32_t *tables; };
 static int resize_upload(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *rects, const jda_output *dst, resize_plan *plan,
-                         int32_t *reads, int32_t filter = JDA_RESIZE_BILINEAR)
+                         int32_t *reads, int32_t filter = JDA_RESIZE_BILINEAR, const float *fboxes = NULL)
 {
     plan->signed_taps = jda_resize_filter_signed(filter) ? 1u : 0u;      // (the signed instances: BICUBIC, LANCZOS)
     plan->block = NULL; plan->n = (uint32_t)n; plan->n_tiles = 0; plan->bpp = (uint32_t)bytes_per_pixel; plan->lds_bytes = 0; plan->tables = NULL;
     jda_resize_plan_out P;
-    int rc = jda_resize_plan_jobs(n, src, bytes_per_pixel, rects, dst, &P, filter);
+    int rc = fboxes ? jda_resize_plan_jobs_box(n, src, bytes_per_pixel, fboxes, dst, &P, filter) : jda_resize_plan_jobs(n, src, bytes_per_pixel, rects, dst, &P, filter);
     if (rc != JDA_SUCCESS) return rc;
     const size_t jbytes = align16(P.jobs.size() * sizeof(jda_resize_job)), tbytes = P.tables.size() * sizeof(int32_t);
     uint8_t *blk = NULL;
@@ -1781,6 +1783,67 @@ int jda_resize_surfaces_ex(jda_ctx *ctx, int32_t n, const jda_output *src, int32
     int rc = resize_upload(ctx, n, src, bytes_per_pixel, rects, dst, &plan, NULL, filter);
     if (rc != JDA_SUCCESS) return rc;
     return finish_surfaces(ctx, resize_launch(ctx, plan), plan.block, "jda_resize_surfaces");
+}
+
+// Pillow's resize(size, F, box = a float box): the same launch over tables made from fractional ends (jda_resize_plan_jobs_box)
+int jda_resize_surfaces_box(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const float *boxes, const jda_output *dst, int32_t filter)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0 || (bytes_per_pixel != 1 && bytes_per_pixel != 4) || filter < 0 || filter >= JDA_RESIZE_FILTERS) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    if (!src || !dst || !boxes) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    resize_plan plan;
+    int rc = resize_upload(ctx, n, src, bytes_per_pixel, NULL, dst, &plan, NULL, filter, boxes);
+    if (rc != JDA_SUCCESS) return rc;
+    return finish_surfaces(ctx, resize_launch(ctx, plan), plan.block, "jda_resize_surfaces_box");
+}
+
+// ---- Pillow's Image.reduce (jda_reduce_tiles in jda_kernels.hip; the rule and the tile: jda_rd_* in jda_device_core.h; checks and tiles: jda_reduce_plan.h)
+// Check n jobs and upload their records, and wait for them as resize_upload does; reduce_launch then queues the kernel.
+struct reduce_plan { void *block; uint32_t n, n_tiles, bpp, lds_bytes; };
+static int reduce_upload(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *factors, const int32_t *boxes, const jda_output *dst,
+                         reduce_plan *plan)
+{
+    plan->block = NULL; plan->n = (uint32_t)n; plan->n_tiles = 0; plan->bpp = (uint32_t)bytes_per_pixel; plan->lds_bytes = 0;
+    jda_reduce_plan_out P;
+    const int rc = jda_reduce_plan_jobs(n, src, bytes_per_pixel, factors, boxes, dst, &P);
+    if (rc != JDA_SUCCESS) return rc;
+    const size_t jbytes = P.jobs.size() * sizeof(jda_reduce_job);
+    uint8_t *blk = NULL;
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, align16(jbytes));
+    if (e != hipSuccess) return jda_set_err(ctx, e, "hipMalloc(reduce jobs)");
+    // (the records may share no byte with a destination either: the pool hands out what no surface of the caller's holds)
+    e = hipMemcpyAsync(blk, P.jobs.data(), jbytes, hipMemcpyHostToDevice, ctx->stream);
+    { const hipError_t es = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) e = es; }
+    if (e != hipSuccess) { jda_pool_free(ctx, blk); return jda_set_err(ctx, e, "reduce jobs"); }
+    plan->block = blk; plan->n_tiles = P.n_tiles; plan->lds_bytes = P.lds_bytes;
+    return JDA_SUCCESS;
+}
+static int reduce_launch(jda_ctx *ctx, const reduce_plan &plan)
+{
+    const hipError_t e = jda_launch_reduce((const jda_reduce_job *)plan.block, plan.n, plan.n_tiles, plan.bpp, plan.lds_bytes, ctx->stream);
+    return e == hipSuccess ? JDA_SUCCESS : jda_set_err(ctx, e, "jda_reduce_tiles");
+}
+int jda_reduce_geometry(int32_t box_w, int32_t box_h, int32_t fx, int32_t fy, int32_t *out_w, int32_t *out_h)
+{
+    return jda_reduce_geometry_of(box_w, box_h, fx, fy, out_w, out_h);
+}
+int jda_reduce_surfaces(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *factors, const int32_t *boxes, const jda_output *dst)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n < 0 || (bytes_per_pixel != 1 && bytes_per_pixel != 4)) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    if (!src || !dst || !factors) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    reduce_plan plan;
+    const int rc = reduce_upload(ctx, n, src, bytes_per_pixel, factors, boxes, dst, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    return finish_surfaces(ctx, reduce_launch(ctx, plan), plan.block, "jda_reduce_surfaces");
+}
+int jda_thumbnail_plan(int32_t src_w, int32_t src_h, int32_t req_w, int32_t req_h, int32_t filter, double reducing_gap, jda_thumbnail_steps *plan)
+{
+    return jda_thumbnail_plan_of(src_w, src_h, req_w, req_h, filter, reducing_gap, plan);
 }
 
 int jda_decode_to_host_resized(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t options, const int32_t *rect,
@@ -2524,6 +2587,34 @@ int jda_decode_to_host_exact_rect(jda_ctx *ctx, const uint8_t *jpeg, int32_t len
 {
     return exact_to_host(ctx, jpeg, len, pixel_type, scale, flags, rect, host_pixels, pitch_bytes, rows, tiles);
 }
+// A file made a resident source of the exact road for the length of one call: a progressive file (every scan is what libjpeg decodes: no
+// option bit) or, with four, a four-component one as a coefficient image, anything else as a baseline image.  open: JDA_SUCCESS and S set,
+// or the reason; close frees whatever open made.
+struct exact_resident {
+    jda_image *img; jda_coef_image *cimg; jda_dev_image *dimg; jda_dev_coef *dcoef; jda_recode_source S;
+    exact_resident() : img(NULL), cimg(NULL), dimg(NULL), dcoef(NULL) { S.image = NULL; S.coef = NULL; }
+    int open(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, bool progressive, bool four)
+    {
+        int32_t err = JDA_SUCCESS;
+        if (progressive || four) {
+            cimg = four ? jda_coef_prepare(jpeg, len, &err) : jda_progressive_prepare(jpeg, len, &err);
+            if (cimg) dcoef = jda_coef_upload_ex(ctx, cimg, JDA_COEF_AUTO, &err);
+            S.coef = dcoef;
+        } else {
+            img = jda_prepare(jpeg, len, &err);
+            if (img) dimg = jda_upload(ctx, img, &err);
+            S.image = dimg;
+        }
+        return (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
+    }
+    void close(jda_ctx *ctx)
+    {
+        if (dimg) jda_dev_image_free(ctx, dimg);
+        if (dcoef) jda_dev_coef_free(ctx, dcoef);
+        if (img) jda_image_free(img);
+        if (cimg) jda_coef_image_free(cimg);
+    }
+};
 // rect (NULL or all zero: the whole image): the surface and the host rows hold the rectangle; tiles (may be NULL): [0] the planes-stage tiles
 // launched, [1] those of the whole image
 static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect, void *host_pixels,
@@ -2573,22 +2664,8 @@ static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t
         }
     }
     if ((int64_t)pitch_bytes < (int64_t)ow * (pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4)) return JDA_INVALID_PARAMETER;      // (a row holds the image's width, as a surface's does)
-    jda_image *img = NULL;
-    jda_coef_image *cimg = NULL;
-    jda_recode_source S = { NULL, NULL };
-    int32_t err = JDA_SUCCESS;
-    jda_dev_image *dimg = NULL;
-    jda_dev_coef *dcoef = NULL;
-    if (I.jpeg_type == 1 || four) {                        // (every scan is what libjpeg decodes: no option bit)
-        cimg = four ? jda_coef_prepare(jpeg, len, &err) : jda_progressive_prepare(jpeg, len, &err);
-        if (cimg) dcoef = jda_coef_upload_ex(ctx, cimg, JDA_COEF_AUTO, &err);
-        S.coef = dcoef;
-    } else {
-        img = jda_prepare(jpeg, len, &err);
-        if (img) dimg = jda_upload(ctx, img, &err);
-        S.image = dimg;
-    }
-    rc = (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
+    exact_resident R;
+    rc = R.open(ctx, jpeg, len, I.jpeg_type == 1, four);
     const int bpp = pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4;
     const int dpitch = (int)align16((size_t)ow * bpp), drows = rows < oh ? rows : oh;
     void *dout = NULL;
@@ -2597,17 +2674,83 @@ static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t
         jda_output O;
         O.pixels = dout; O.pitch_bytes = dpitch; O.width_px = ow; O.rows = drows;
         int32_t st = JDA_SUCCESS;
-        rc = exact_call(ctx, 1, &S, &O, &pixel_type, NULL, &st, NULL, &scale, flags, has_rect ? rect : NULL);
+        rc = exact_call(ctx, 1, &R.S, &O, &pixel_type, NULL, &st, NULL, &scale, flags, has_rect ? rect : NULL);
         if (rc == JDA_SUCCESS) rc = st;
     }
     if (rc == JDA_SUCCESS && drows > 0) {
         rc = copy_rows_back(ctx, host_pixels, (size_t)pitch_bytes, dout, (size_t)dpitch, (size_t)ow * bpp, (size_t)drows, false);
     }
     if (dout) jda_pool_free(ctx, dout);
-    if (dimg) jda_dev_image_free(ctx, dimg);
-    if (dcoef) jda_dev_coef_free(ctx, dcoef);
-    if (img) jda_image_free(img);
-    if (cimg) jda_coef_image_free(cimg);
+    R.close(ctx);
+    return rc;
+}
+
+// Pillow's Image.open(f).thumbnail((req_w, req_h), F, reducing_gap): the plan, the exact decode at its scale into a device surface, the reduce
+// and the resize behind it in the same block (each step's records wait for the host before the step is queued), the result's rows back
+int jda_decode_to_host_thumbnail(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t req_w, int32_t req_h, int32_t filter, double reducing_gap,
+                                 int32_t pixel_type, void *host_pixels, int32_t pitch_bytes, int32_t rows, int32_t *out_w, int32_t *out_h, int32_t *launches)
+{
+    if (out_w) *out_w = 0;
+    if (out_h) *out_h = 0;
+    if (launches) launches[0] = launches[1] = 0;
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (!jpeg || !host_pixels || pitch_bytes < 0 || rows < 0) return JDA_INVALID_PARAMETER;
+    if (pixel_type != JDA_RGB8888 && pixel_type != JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    jda_image_info I;
+    int rc = jda_parse(jpeg, len, &I);
+    if (rc != JDA_SUCCESS) return rc;
+    jda_thumbnail_steps T;
+    rc = jda_thumbnail_plan_of(I.width, I.height, req_w, req_h, filter, reducing_gap, &T);
+    if (rc != JDA_SUCCESS) return rc;
+    if (out_w) *out_w = T.out_w;
+    if (out_h) *out_h = T.out_h;
+    const int bpp = pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4;
+    if ((int64_t)pitch_bytes < (int64_t)T.out_w * bpp || rows < T.out_h) return JDA_INVALID_PARAMETER;
+    const bool reduces = T.fx > 1 || T.fy > 1;
+    exact_resident R;
+    rc = R.open(ctx, jpeg, len, I.jpeg_type == 1, false);
+    // one block: the draft image, behind it the reduced image and the result where the plan has those steps (each begins at a multiple of 256)
+    jda_output D[3];
+    size_t at = 0;
+    const int32_t dims[3][2] = { { T.draft_w, T.draft_h }, { T.reduced_w, T.reduced_h }, { T.out_w, T.out_h } };
+    const bool used[3] = { true, reduces, T.resize != 0 };
+    size_t offs[3];
+    for (int i = 0; i < 3; i++) {
+        D[i].pitch_bytes = (int32_t)align16((size_t)dims[i][0] * bpp); D[i].width_px = dims[i][0]; D[i].rows = dims[i][1];
+        offs[i] = at;
+        if (used[i]) at += ((size_t)D[i].pitch_bytes * (size_t)dims[i][1] + 255u) & ~(size_t)255u;
+    }
+    uint8_t *blk = NULL;
+    if (rc == JDA_SUCCESS && jda_pool_alloc(ctx, (void **)&blk, at + 16) != hipSuccess) rc = JDA_ERROR_MEMORY;
+    for (int i = 0; i < 3; i++) D[i].pixels = blk && used[i] ? blk + offs[i] : NULL;
+    if (rc == JDA_SUCCESS) {
+        int32_t st = JDA_SUCCESS;
+        rc = exact_call(ctx, 1, &R.S, &D[0], &pixel_type, NULL, &st, NULL, &T.scale);
+        if (rc == JDA_SUCCESS) rc = st;
+    }
+    const jda_output *cur = &D[0];
+    reduce_plan rd; rd.block = NULL;
+    resize_plan rs; rs.block = NULL;
+    if (rc == JDA_SUCCESS && reduces) {
+        const int32_t factors[2] = { T.fx, T.fy };
+        rc = reduce_upload(ctx, 1, cur, bpp, factors, T.reduce_box, &D[1], &rd);
+        if (rc == JDA_SUCCESS) rc = reduce_launch(ctx, rd);
+        if (rc == JDA_SUCCESS && launches) launches[0] = 1;
+        cur = &D[1];
+    }
+    if (rc == JDA_SUCCESS && T.resize) {
+        rc = resize_upload(ctx, 1, cur, bpp, NULL, &D[2], &rs, NULL, filter, T.box);
+        if (rc == JDA_SUCCESS) rc = resize_launch(ctx, rs);
+        if (rc == JDA_SUCCESS && launches) launches[1] = 1;
+        cur = &D[2];
+    }
+    if (rc == JDA_SUCCESS) rc = copy_rows_back(ctx, host_pixels, (size_t)pitch_bytes, cur->pixels, (size_t)cur->pitch_bytes, (size_t)T.out_w * bpp, (size_t)T.out_h, false);
+    else (void)hipStreamSynchronize(ctx->stream);
+    if (rd.block) jda_pool_free(ctx, rd.block);
+    if (rs.block) jda_pool_free(ctx, rs.block);
+    if (blk) jda_pool_free(ctx, blk);
+    R.close(ctx);
     return rc;
 }
 
@@ -2848,6 +2991,19 @@ int jda_internal_orient_time(jda_ctx *ctx, int32_t n, const jda_output *src, int
     const int rc = orient_upload(ctx, n, src, bytes_per_pixel, orientations, dst, &plan);
     if (rc != JDA_SUCCESS) return rc;
     return timed_launches(ctx, reps, ms, plan.block, "jda_internal_orient_time", [&]() { return orient_launch(ctx, plan); });
+}
+// Measuring hook of tools/thumbnail_bench.py (not part of the public header): the reduce launch between the context's two timer events on
+// its stream -- the job records go up before the first event.  ms[k]: repeat k.
+int jda_internal_reduce_time(jda_ctx *ctx, int32_t n, const jda_output *src, int32_t bytes_per_pixel, const int32_t *factors, const int32_t *boxes, const jda_output *dst,
+                             int32_t reps, float *ms)
+{
+    if (!ctx) return JDA_ERROR_NO_DEVICE;
+    if (n <= 0 || !src || !factors || !dst || reps <= 0 || !ms) return JDA_INVALID_PARAMETER;
+    (void)hipSetDevice(ctx->device);
+    reduce_plan plan;
+    const int rc = reduce_upload(ctx, n, src, bytes_per_pixel, factors, boxes, dst, &plan);
+    if (rc != JDA_SUCCESS) return rc;
+    return timed_launches(ctx, reps, ms, plan.block, "jda_internal_reduce_time", [&]() { return reduce_launch(ctx, plan); });
 }
 int jda_internal_copy_time(jda_ctx *ctx, void *dst, const void *src, size_t bytes, int32_t reps, float *ms)
 {

@@ -165,6 +165,9 @@ extern "C" hipError_t jda_launch_unpack(const jda_unpack_job *jobs, uint32_t n, 
 // signed_taps: the tables of a filter with negative taps (BICUBIC, LANCZOS), run by jda_resize_tiles_signed
 extern "C" hipError_t jda_launch_resize(const jda_resize_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, uint32_t signed_taps, const int32_t *tables,
                                         uint32_t lds_bytes, hipStream_t stream);
+// n jobs of one pixel size (1 or 4) shrunk by their whole factors (jda_reduce_tiles; jda_rd_* in jda_device_core.h), one workgroup a tile
+// of 256 output bytes x the job's tile rows; n_tiles: the length of the flat tile list, lds_bytes: the largest tile's LDS
+extern "C" hipError_t jda_launch_reduce(const jda_reduce_job *jobs, uint32_t n, uint32_t n_tiles, uint32_t bytes_per_pixel, uint32_t lds_bytes, hipStream_t stream);
 // one of the seven launches of jda_encode_surfaces (JDA_EN_STAGE_*; jda_en_* in jda_device_core.h); the host sizes the unstuffed scans behind stage 2
 extern "C" hipError_t jda_launch_encode_stage(const jda_en_arrays *A, uint32_t stage, uint32_t n_blocks, uint32_t n_chunks, hipStream_t stream);
 // the two more of a call with an optimised job (JDA_EN_STAGE_GATHER into the call's zeroed histograms, JDA_EN_STAGE_OPT_LENGTHS; jda_ho_*)

@@ -347,19 +347,110 @@ def decode_to_tensors(ctx, files, layout="CHW", dtype=None, table=None, options=
     return result
 
 
-def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=True, restart_interval=0, optimize=False, resample="bilinear", progressive=False):
+def _libjpeg_table_order(f):
+    """The Huffman table segments in front of a file's first scan in the order libjpeg writes them: per component of the scan its DC table,
+    then its AC table -- DC 0, AC 0, DC 1, AC 1.  jda_encode_surfaces writes a standard-table colour file's four segments as DC 0, DC 1,
+    AC 0, AC 1 (the same segments; every decoder reads either order, and its contract is the bytes behind the SOS header): a file that has
+    to be Pillow's from the first byte to the last gets them moved here, on the host, in the few hundred bytes of its header.  A file whose
+    segments already stand in that order (gray, optimised and progressive files) comes back as it is."""
+    i, first, end, segs = 2, None, 0, []
+    while i + 4 <= len(f) and f[i] == 0xFF and f[i + 1] != 0xDA:
+        length = (f[i + 2] << 8) | f[i + 3]
+        if f[i + 1] == 0xC4:
+            first = i if first is None else first
+            segs.append(f[i:i + 2 + length])
+            end = i + 2 + length
+        elif first is not None:
+            break
+        i += 2 + length
+    if first is None:
+        return f
+    return f[:first] + b"".join(sorted(segs, key=lambda s: (s[4] & 15, s[4] >> 4))) + f[end:]
+
+
+def _pillow_thumbnails(ctx, files, infos, size, filt, gap, pt, samp, quality, restart_interval, optimize, progressive):
+    """thumbnails(pillow=True): the plans, ONE exact decode at the plans' scales, one reduce launch over the files that have that step, one
+    float-box resize launch over those that are resized, one encode call over every file's final surface"""
+    n = len(files)
+    plans = [B.thumbnail_plan(i.width, i.height, size, filt, gap) for i in infos]       # (JdaError for a plan the call cannot run)
+    bpp = 1 if pt == B.GRAY8 else 4
+    total = 0
+
+    def surface(w, h):
+        nonlocal total
+        pitch = (w * bpp + 15) & ~15
+        at = total
+        total += (pitch * h + 255) & ~255
+        return [at, pitch, w, h]
+
+    draft = [surface(*p["draft"]) for p in plans]
+    reduced = [surface(*p["reduced"]) if p["factors"] != (1, 1) else None for p in plans]
+    final = [surface(*p["out"]) if p["resize"] else None for p in plans]
+    caps, foffs = [], []
+    for p in plans:
+        caps.append(B.encode_bound_progressive(p["out"][0], p["out"][1], samp) if progressive else B.encode_bound(p["out"][0], p["out"][1], samp, restart_interval))
+        foffs.append(total)
+        total += (caps[-1] + 255) & ~255
+    base = ctx.malloc(total)
+    try:
+        at = lambda q: (base + q[0], q[1], q[2], q[3])
+        status = _exact_batch(ctx, files, infos, [at(q) for q in draft], pt, [p["scale"] for p in plans])
+        for k, st in enumerate(status):
+            if st != 0:
+                raise B.JdaError(st, "file %d of the batch" % k)
+        cur = list(draft)
+        ks = [k for k in range(n) if reduced[k] is not None]
+        if ks:
+            B.reduce_surfaces(ctx, [at(cur[k]) for k in ks], bpp, [plans[k]["factors"] for k in ks], [at(reduced[k]) for k in ks], [plans[k]["reduce_box"] for k in ks])
+            for k in ks:
+                cur[k] = reduced[k]
+        ks = [k for k in range(n) if final[k] is not None]
+        if ks:
+            B.resize_surfaces_box(ctx, [at(cur[k]) for k in ks], bpp, [at(final[k]) for k in ks], [plans[k]["box"] for k in ks], filt)
+            for k in ks:
+                cur[k] = final[k]
+        jobs = [(0, 0, p["out"][0], p["out"][1], samp, quality, restart_interval) for p in plans]
+        dsts = [base + o for o in foffs]
+        if progressive:
+            nbytes, st = B.encode_surfaces_progressive(ctx, [at(q) for q in cur], bpp, jobs, dsts, caps)
+        else:
+            nbytes, st = B.encode_surfaces(ctx, [at(q) for q in cur], bpp, jobs, dsts, caps, [B.ENCODE_OPTIMIZE] * n if optimize else None)
+        if any(st):
+            raise B.JdaError(max(st), "jda_encode_surfaces")
+        return [_libjpeg_table_order(ctx.to_host(dsts[k], nbytes[k]).tobytes()) for k in range(n)]
+    finally:
+        ctx.free(base)
+
+
+def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, prescale=None, restart_interval=0, optimize=False, resample="bilinear", progressive=False,
+               pillow=False, reducing_gap=2.0):
     """files (JPEG bytes, all colour or all gray) -> list of JPEG files (bytes), each image -- or crops[k] = (x, y, w, h) of image k, in pixels
     of its visible size -- resized to size = (H, W) and encoded at `quality`; gray files take the gray sampling whatever `sampling` says.
     resample: the filter, as in decode_to_tensors (Pillow's own thumbnail() takes "bicubic").
     One Pipeline batch, one jda_resize_surfaces_ex launch and one jda_encode_surfaces call; only the files are copied back.  prescale (whole
     images only, ignored with crops): as decode_to_tensors.  optimize: every file with Huffman tables of its own (Pillow's optimize=True; a
     thumbnail loses a few hundred bytes of standard tables).  progressive: progressive files (jda_encode_surfaces_progressive: Pillow's
-    progressive=True; the tables are always the file's own, so optimize changes nothing; restart_interval must be 0).  No torch in here.  A file that fails to decode raises JdaError with its status."""
+    progressive=True; the tables are always the file's own, so optimize changes nothing; restart_interval must be 0).  No torch in here.  A file that fails to decode raises JdaError with its status.
+    prescale: None is True (what the call has always done).
+    pillow=True: Pillow's own call.  size is then Pillow's (W, H) BOUND and every file gets its own final size: the returned file k is, byte
+    for byte, im = Image.open(files[k]); im.thumbnail(size, F, reducing_gap); im.save(buf, "JPEG", quality=, subsampling=, optimize=,
+    progressive=) -- F = resample, reducing_gap as Pillow's (None, or 0 as thumbnail_plan and decode_to_host_thumbnail take it: no draft, no reduce).  The libjpeg-exact decode at the scale draft()
+    chooses, ONE jda_reduce_surfaces launch over the files that have a reduce step, ONE jda_resize_surfaces_box launch and one encode call
+    with per-file sizes; a file already within size is encoded at its own size.  (A standard-table colour file's four Huffman table
+    segments are put into libjpeg's order on the host: _libjpeg_table_order.)  crops and an explicit prescale=True are ValueErrors with
+    it, a gray / colour mix as ever; a file the plan cannot run (jda_thumbnail_plan) raises JdaError."""
     files = list(files)
     filt = B.resize_filter(resample)
+    if pillow and crops is not None:
+        raise ValueError("pillow=True: Image.thumbnail takes no crop")
+    if pillow and prescale:
+        raise ValueError("pillow=True: the decode's scale is draft()'s, not prescale's")
+    if pillow and not (reducing_gap is None or (isinstance(reducing_gap, (int, float)) and not isinstance(reducing_gap, bool) and (reducing_gap == 0 or reducing_gap >= 1.0))):
+        raise ValueError("reducing_gap: None (or 0, as thumbnail_plan takes it), or a number >= 1.0 (Pillow's rule)")
+    prescale = True if prescale is None else prescale
     size = tuple(int(v) for v in size)
     if len(size) != 2 or size[0] <= 0 or size[1] <= 0:
-        raise ValueError("size: (H, W), both positive")
+        raise ValueError("size: %s, both positive" % ("(W, H)" if pillow else "(H, W)"))
     n = len(files)
     if n == 0:
         return []
@@ -379,6 +470,8 @@ def thumbnails(ctx, files, size, quality=75, sampling="4:2:0", crops=None, presc
         raise ValueError("gray and colour files in one call: one jda_resize_surfaces launch takes one source format")
     pt = B.GRAY8 if gray[0] else B.RGB8888
     samp = B.ENCODE_GRAY if gray[0] else B.ENCODE_SAMPLINGS[sampling] if isinstance(sampling, str) else int(sampling)
+    if pillow:
+        return _pillow_thumbnails(ctx, files, infos, size, filt, reducing_gap, pt, samp, quality, restart_interval, optimize, progressive)
     opts = [prescale_option(i, pt, 0, size) if prescale and crops is None else 0 for i in infos]
     geos = [B.output_geometry(i, pt, o) for i, o in zip(infos, opts)]
     bpp = geos[0]["bpp"]
