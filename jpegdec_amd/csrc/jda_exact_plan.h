@@ -1,6 +1,6 @@
-// jda_exact_plan.h -- the host side of the libjpeg-exact decode (jda_exact_decode_surfaces / _planes): what is refused,
-// the component planes of an image in the call's scratch, and its record for the kernels.  Host work only, no HIP: the runtime and
-// tests/hostsim/exact_sim.cpp share it.
+// jda_exact_plan.h -- the host side of the libjpeg-exact decode (jda_exact_decode_* ): what is refused, the
+// component planes of an image in the call's scratch, its record for the kernels, and the plan of a whole call -- its blob, tile lists and
+// launches.  Host work only, no HIP: the runtime and the exact sims of tests/hostsim share it.
 #ifndef JDA_EXACT_PLAN_H
 #define JDA_EXACT_PLAN_H
 
@@ -256,6 +256,246 @@ inline void jda_exact_fill_rect(jda_ex_desc &X, jda_exr_rec &R, const jda_image_
     R.x = (uint32_t)rect[0]; R.y = (uint32_t)rect[1]; R.w = (uint32_t)rect[2]; R.h = (uint32_t)rect[3];
     X.out_w = out->width_px < rect[2] ? (uint32_t)(out->width_px < 0 ? 0 : out->width_px) : R.w;
     X.out_rows = out->rows < rect[3] ? (uint32_t)(out->rows < 0 ? 0 : out->rows) : R.h;
+}
+
+// ---- the plan of a call (jda_exact_decode_* in jda_runtime.cpp): everything the call decides before it has device
+// memory (jda_exact_plan_build) and what it writes once it knows where its block lies (jda_exact_plan_place).
+// The kernel family of a launch.  The first three are also the kinds of a source: the planes kernel that reads it.
+enum jda_exact_kind {
+    JDA_EXK_PLANES_DENSE = 0,        // jda_exact_planes / _planes_scaled over tiles of dense coefficient images
+    JDA_EXK_PLANES_SPARSE,           // .. of sparse ones
+    JDA_EXK_PLANES_BASELINE,         // .. of resident baseline images
+    JDA_EXK_COLOUR,                  // jda_exact_colour / _colour_scaled over tiles of gray and YCbCr images
+    JDA_EXK_COLOUR_RGB,              // jda_exact_colour_rgb / _colour_scaled_rgb over tiles of RGB-coded images
+    JDA_EXK_COLOUR4,                 // jda_exact_colour4 over tiles of four-component images (components 0..2 of the launch's layout)
+    JDA_EXK_COLOUR_RECT,             // jda_exact_colour_rect<.., false> over tile records of destination rectangles
+    JDA_EXK_COLOUR_RECT_RGB          // jda_exact_colour_rect<.., true>: the rectangles of RGB-coded images
+};
+// One resident source as the plan reads it (device pointers): a coefficient image -- tables its quantisers (and first[], sparse), scan its
+// coefficients or entries -- or a baseline image -- its tables, scan, block index and DC values.  quant: the DQT entries of its components
+// as the file lists them.  k: component 3 of a four-component image, a gray coefficient image of its own; NULL otherwise.
+struct jda_exact_source {
+    jda_exact_kind kind;
+    jda_image_info info;
+    int adobe, colour;
+    uint32_t n_mcus_ok;
+    uint16_t quant[3][64];
+    const uint8_t *tables, *scan;
+    const uint32_t *index;
+    const int16_t *dc;
+    uint32_t scan_len;
+    uint8_t ac_id[3];
+    const jda_exact_source *k;
+};
+// One launch: `n_tiles` tile records at `off` of the blob, of images of layout `mode` decoded at `scale`
+struct jda_exact_launch { jda_exact_kind kind; int mode, scale; size_t off; uint32_t n_tiles; };
+// A planned image (kind < 0: refused, nothing of it is launched): its header (a four-component image's with components 0..2 alone), its
+// planes G at plane_at of the scratch, its MCU rectangle and what jda_exact_plan_place fills its record from
+struct jda_exact_image {
+    int kind;
+    jda_image_info info;
+    uint16_t quant[3][64], quant_k[64];
+    jda_exact_geo G;
+    size_t plane_at;
+    bool luma_only, rgb, four, rect, has_out;
+    int colour, pixel_type;
+    int32_t mcu[4], rq[4];
+    jda_output out;
+};
+// The block of a call: the blob (descs | records | baseline sources, `n_rec` of each: one an image, two with flags | the tile lists, in
+// launch order | a rectangle record an image, in a call with a rectangle), the scratch at o_scratch (a multiple of 256) behind it: every
+// planned image's planes.  launches: in launch order, the planes stage's before colour_begin.
+struct jda_exact_plan {
+    std::vector<uint8_t> blob;
+    std::vector<jda_exact_launch> launches;
+    size_t colour_begin;
+    size_t o_ex, o_src, o_rect, o_scratch, scratch;
+    std::vector<jda_exact_image> images;
+    size_t n_rec;
+    int32_t n_planned;
+};
+// the tiles of an image's planes stage that hold MCUs (jda_append_strips' records without its padding); mcu: jda_exact_rect_plan's, NULL: whole
+// (what jda_decode_to_host_exact_rect reports, whether or not a plan is ever made)
+inline int32_t jda_exact_tile_count(const jda_image_info &I, const int32_t *mcu)
+{
+    const uint32_t per = jda_mcus_per_tile(jda_mode_of(I));
+    const uint32_t w = mcu ? (uint32_t)(mcu[2] - mcu[0]) : (uint32_t)I.mcus_x, h = mcu ? (uint32_t)(mcu[3] - mcu[1]) : (uint32_t)I.mcus_y;
+    return (int32_t)(h * ((w + per - 1u) / per));
+}
+// A tile list of the call.  The table of them is made in launch order -- the planes lists by (layout, scale, source); the colour stage's own
+// by (layout, scale, YCbCr or gray | RGB-coded), the four-component images' by layout, the rectangles' by (layout, YCbCr or gray | RGB-coded)
+// -- and lies in the blob in that order, so the dense, sparse and baseline lists of a (layout, scale) are one contiguous range.
+struct jda_exact_list { jda_exact_kind kind; int mode, g; std::vector<jda_strip> tiles; size_t off; };
+// where a list stands in the table (g: log2 scale; source: a planes kind; rgb: the RGB-coded images' list).  A new family gets its place
+// here and its entries in jda_exact_lists_init; placing, copying and launching follow the table.
+enum { JDA_EXACT_L_COLOUR = JDA_N_MODES * 4 * 3, JDA_EXACT_L_FOUR = JDA_EXACT_L_COLOUR + JDA_N_MODES * 4 * 2, JDA_EXACT_L_RECT = JDA_EXACT_L_FOUR + JDA_N_MODES,
+       JDA_EXACT_N_LISTS = JDA_EXACT_L_RECT + JDA_N_MODES * 2 };
+inline size_t jda_exact_l_planes(int mode, int g, int source) { return ((size_t)mode * 4 + (size_t)g) * 3 + (size_t)source; }
+inline size_t jda_exact_l_colour(int mode, int g, bool rgb) { return JDA_EXACT_L_COLOUR + ((size_t)mode * 4 + (size_t)g) * 2 + (rgb ? 1u : 0u); }
+inline size_t jda_exact_l_four(int mode) { return JDA_EXACT_L_FOUR + (size_t)mode; }
+inline size_t jda_exact_l_rect(int mode, bool rgb) { return JDA_EXACT_L_RECT + (size_t)mode * 2 + (rgb ? 1u : 0u); }
+inline void jda_exact_lists_init(jda_exact_list *L)
+{
+    for (int m = 0; m < JDA_N_MODES; m++) {
+        for (int g = 0; g < 4; g++) {
+            for (int f = 0; f < 3; f++) { jda_exact_list &l = L[jda_exact_l_planes(m, g, f)]; l.kind = (jda_exact_kind)f; l.mode = m; l.g = g; }
+            for (int f = 0; f < 2; f++) { jda_exact_list &l = L[jda_exact_l_colour(m, g, f != 0)]; l.kind = f ? JDA_EXK_COLOUR_RGB : JDA_EXK_COLOUR; l.mode = m; l.g = g; }
+        }
+        { jda_exact_list &l = L[jda_exact_l_four(m)]; l.kind = JDA_EXK_COLOUR4; l.mode = m; l.g = 0; }
+        for (int f = 0; f < 2; f++) { jda_exact_list &l = L[jda_exact_l_rect(m, f != 0)]; l.kind = f ? JDA_EXK_COLOUR_RECT_RGB : JDA_EXK_COLOUR_RECT; l.mode = m; l.g = 0; }
+    }
+}
+inline size_t jda_exact_align16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+
+// What a call does before it allocates.  sources: n views; outputs / pixel_types (NULL: RGB8888) or planes (three entries an image, four
+// with flags): the call's; scales (NULL: all 1), flags (JDA_EXACT_COLOUR_MODELS or 0), rects (NULL: none; {x, y, w, h} an image, all zero:
+// whole): the call's.  status[i]: JDA_SUCCESS, or why image i is refused -- it is left out (its records stay zero) and the call goes on.
+// Without flags and rectangles the colour stage walks the planes lists: one launch a (layout, scale) over its three lists.  Otherwise those
+// hold tiles the whole-image colour kernels must not walk (component 3's gray tiles, a rectangle's), and the colour stage has lists of its own.
+inline int jda_exact_plan_build(int32_t n, const jda_exact_source *src, const jda_output *outputs, const int32_t *pixel_types, const jda_output *planes, const int32_t *scales,
+                                uint32_t flags, const int32_t *rects, int32_t *status, jda_exact_plan *plan)
+{
+    plan->blob.clear(); plan->launches.clear(); plan->images.clear();
+    plan->colour_begin = plan->o_ex = plan->o_src = plan->o_rect = plan->o_scratch = plan->scratch = plan->n_rec = 0;
+    plan->n_planned = 0;
+    if (n < 0 || (n > 0 && (!src || !status || (!outputs && !planes)))) return JDA_INVALID_PARAMETER;
+    if (n == 0) return JDA_SUCCESS;
+    const size_t nrec = flags ? 2u * (size_t)n : (size_t)n;    // (a four-component image's component 3 is record n + i)
+    const int ps = flags ? 4 : 3;                               // entries an image in planes
+    std::vector<jda_dev_desc> descs(nrec);
+    std::vector<jda_ex_src> esrc(nrec);
+    memset(descs.data(), 0, nrec * sizeof(jda_dev_desc)); memset(esrc.data(), 0, nrec * sizeof(jda_ex_src));
+    plan->images.resize((size_t)n);
+    plan->n_rec = nrec;
+    bool any_rect = false;
+    for (int i = 0; i < n && rects && outputs; i++) any_rect = any_rect || rects[4 * i] || rects[4 * i + 1] || rects[4 * i + 2] || rects[4 * i + 3];
+    const bool own_cs = flags || any_rect;                      // the colour stage has lists of its own
+    jda_exact_list L[JDA_EXACT_N_LISTS];
+    const size_t nl = JDA_EXACT_N_LISTS;
+    jda_exact_lists_init(L);
+    for (int i = 0; i < n; i++) {
+        jda_exact_image &M = plan->images[(size_t)i];
+        jda_dev_desc &D = descs[(size_t)i];
+        const jda_exact_source &S = src[i];
+        M.kind = (int)S.kind; M.info = S.info;
+        memcpy(M.quant, S.quant, sizeof(M.quant)); memset(M.quant_k, 0, sizeof(M.quant_k));
+        const jda_image_info &I = M.info;
+        const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
+        const int scale = scales ? scales[i] : 1;
+        const bool baseline = S.kind == JDA_EXK_PLANES_BASELINE;
+        const jda_exact_source *kd = S.k;
+        int rc = (flags & JDA_EXACT_COLOUR_MODELS) ? jda_exact_check_cs(I, S.colour, pt, baseline, S.n_mcus_ok, scale, kd ? (kd->info.mcus_x == I.mcus_x && kd->info.mcus_y == I.mcus_y ? 0x11 : I.subsample) : 0)
+                                                   : jda_exact_check(I, S.adobe, pt, baseline, S.n_mcus_ok);
+        M.rgb = (flags & JDA_EXACT_COLOUR_MODELS) && S.colour == JDA_CS_RGB;
+        M.four = (flags & JDA_EXACT_COLOUR_MODELS) && I.ncomp == 4;
+        M.colour = S.colour; M.pixel_type = pt;
+        M.luma_only = outputs && pt == JDA_EIGHT_BIT_GRAYSCALE && I.ncomp == 3;
+        M.has_out = outputs != NULL;
+        if (outputs) M.out = outputs[i]; else memset(&M.out, 0, sizeof(M.out));
+        if (rc == JDA_SUCCESS && M.four && (!kd || S.kind != JDA_EXK_PLANES_DENSE)) rc = JDA_UNSUPPORTED_FEATURE;      // (dense, with component 3 beside it)
+        if (M.four) { M.info.ncomp = 3; M.info.bpp = 24; }     // (components 0..2 from here on: I is M.info)
+        if (rc == JDA_SUCCESS && !jda_exact_scale_ok(scale)) rc = JDA_INVALID_PARAMETER;
+        if (rc == JDA_SUCCESS) rc = M.four ? jda_exact_geometry4(I, kd->info.mcus_x != I.mcus_x || kd->info.mcus_y != I.mcus_y, &M.G) : jda_exact_geometry_scaled(I, M.luma_only, scale, &M.G);
+        const int32_t *rq = any_rect ? rects + 4 * i : NULL;
+        M.rect = rq && (rq[0] || rq[1] || rq[2] || rq[3]);
+        for (int k = 0; k < 4; k++) M.rq[k] = rq ? rq[k] : 0;
+        if (rc == JDA_SUCCESS && M.rect) rc = M.four ? JDA_UNSUPPORTED_FEATURE : jda_exact_rect_plan(I, M.G, M.luma_only, rq, M.mcu);
+        if (rc == JDA_SUCCESS && outputs) {
+            jda_image_info B = I;
+            B.jpeg_type = 0;
+            const uint8_t none[3] = { 0, 0, 0 };
+            jda_output O = outputs[i];                         // (a scaled image: the surface is held to the scaled size, not to the file's)
+            if (scale > 1 && O.width_px > (int32_t)M.G.w) O.width_px = (int32_t)M.G.w;
+            if (scale > 1 && O.rows > (int32_t)M.G.h) O.rows = (int32_t)M.G.h;
+            if (M.rect && O.width_px > rq[2]) O.width_px = rq[2];      // (a rectangle: the surface holds it, not the image)
+            if (M.rect && O.rows > rq[3]) O.rows = rq[3];
+            rc = jda_fill_launch_desc(D, B, none, none, none, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, O, pt == JDA_CMYK8888 ? JDA_RGB8888 : pt, 0, NULL);      // (four bytes a pixel either way)
+        } else if (rc == JDA_SUCCESS) {
+            D.mode = (uint8_t)jda_mode_of(I); D.ncomp = (uint8_t)I.ncomp; D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
+            for (int c = 0; c < (M.four ? 4 : I.ncomp == 3 ? 3 : 1) && rc == JDA_SUCCESS; c++) {
+                const jda_output &P = planes[ps * i + c];
+                const int32_t ew = c == 3 ? (int32_t)M.G.kw : c ? (int32_t)M.G.cw : (int32_t)M.G.w;
+                if (!P.pixels || P.width_px < 0 || P.rows < 0 || P.pitch_bytes < (P.width_px < ew ? P.width_px : ew)) rc = JDA_INVALID_PARAMETER;
+            }
+        }
+        if (rc != JDA_SUCCESS) { status[i] = rc; memset(&D, 0, sizeof(D)); M.kind = -1; continue; }
+        status[i] = JDA_SUCCESS;
+        plan->n_planned++;
+        M.plane_at = plan->scratch; plan->scratch += M.G.bytes;
+        if (baseline) {
+            jda_ex_src &J = esrc[(size_t)i];
+            J.S.scan = S.scan; J.S.blk_index = S.index; J.S.blk_dc = S.dc; J.S.tables = S.tables; J.S.scan_len = S.scan_len; J.S.kind = JDA_RC_IMAGE;
+            for (int c = 0; c < 3; c++) J.S.ac_id[c] = S.ac_id[c];
+            J.bpm = (uint32_t)I.blocks_per_mcu; J.nluma = I.ncomp == 3 ? J.bpm - 2u : 1u;
+        } else {
+            D.tables = S.tables; D.scan = S.scan;
+        }
+        const int g = M.G.scale == 8u ? 3 : M.G.scale == 4u ? 2 : M.G.scale == 2u ? 1 : 0;
+        jda_append_strips(L[jda_exact_l_planes(D.mode, g, M.kind)].tiles, (uint32_t)i, D.mcus_x, D.mcus_y, D.mode, 0, M.rect ? M.mcu : NULL);
+        if (M.four) {
+            jda_dev_desc &DK = descs[(size_t)n + (size_t)i];
+            memcpy(M.quant_k, kd->quant[0], sizeof(M.quant_k));
+            DK.mode = (uint8_t)JDA_MODE_GRAY; DK.ncomp = 1; DK.mcus_x = (uint32_t)kd->info.mcus_x; DK.mcus_y = (uint32_t)kd->info.mcus_y;
+            DK.tables = kd->tables; DK.scan = kd->scan;
+            jda_append_strips(L[jda_exact_l_planes(JDA_MODE_GRAY, 0, JDA_EXK_PLANES_DENSE)].tiles, (uint32_t)(n + i), DK.mcus_x, DK.mcus_y, JDA_MODE_GRAY);
+            if (outputs) jda_append_strips(L[jda_exact_l_four(D.mode)].tiles, (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        } else if (M.rect) {
+            const jda_output &O = outputs[i];
+            jda_exact_rect_tiles(L[jda_exact_l_rect(D.mode, M.rgb)].tiles, (uint32_t)i, (uint32_t)(O.width_px < rq[2] ? (O.width_px < 0 ? 0 : O.width_px) : rq[2]),
+                                 (uint32_t)(O.rows < rq[3] ? (O.rows < 0 ? 0 : O.rows) : rq[3]));
+        } else if (own_cs && outputs) jda_append_strips(L[jda_exact_l_colour(D.mode, g, M.rgb)].tiles, (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+    }
+    if (!plan->n_planned) return JDA_SUCCESS;
+    plan->o_ex = jda_exact_align16(nrec * sizeof(jda_dev_desc));
+    plan->o_src = plan->o_ex + jda_exact_align16(nrec * sizeof(jda_ex_desc));
+    size_t bytes = plan->o_src + jda_exact_align16(nrec * sizeof(jda_ex_src));
+    for (size_t k = 0; k < nl; k++) { L[k].off = bytes; bytes += L[k].tiles.size() * sizeof(jda_strip); }
+    plan->o_rect = bytes;
+    if (any_rect) bytes += (size_t)n * sizeof(jda_exr_rec);
+    plan->o_scratch = (bytes + 255u) & ~(size_t)255u;
+    plan->blob.assign(bytes, 0);
+    memcpy(plan->blob.data(), descs.data(), nrec * sizeof(jda_dev_desc));
+    memcpy(plan->blob.data() + plan->o_src, esrc.data(), nrec * sizeof(jda_ex_src));
+    for (size_t k = 0; k < nl; k++) {
+        if (k == JDA_EXACT_L_COLOUR) {
+            plan->colour_begin = plan->launches.size();
+            for (int m = 0; m < JDA_N_MODES && outputs && !own_cs; m++)      // the shared lists: dense | sparse | baseline as one range
+                for (int g = 0; g < 4; g++) {
+                    const jda_exact_list *P = &L[jda_exact_l_planes(m, g, 0)];
+                    const size_t cnt = P[0].tiles.size() + P[1].tiles.size() + P[2].tiles.size();
+                    if (cnt) plan->launches.push_back(jda_exact_launch{ JDA_EXK_COLOUR, m, 1 << g, P[0].off, (uint32_t)cnt });
+                }
+        }
+        if (L[k].tiles.empty()) continue;
+        memcpy(plan->blob.data() + L[k].off, L[k].tiles.data(), L[k].tiles.size() * sizeof(jda_strip));
+        plan->launches.push_back(jda_exact_launch{ L[k].kind, L[k].mode, 1 << L[k].g, L[k].off, (uint32_t)L[k].tiles.size() });
+    }
+    return JDA_SUCCESS;
+}
+
+// .. and once the call's block lies at `block` (device memory of o_scratch + scratch bytes; the plan never reads it): the images' records,
+// their planes at block + o_scratch + plane_at, which complete the blob
+inline void jda_exact_plan_place(jda_exact_plan *plan, uint8_t *block)
+{
+    const size_t n = plan->images.size();
+    uint8_t *ex = plan->blob.data() + plan->o_ex;
+    for (size_t i = 0; i < n; i++) {
+        const jda_exact_image &M = plan->images[i];
+        if (M.kind < 0) continue;
+        uint8_t *at = block + plan->o_scratch + M.plane_at;
+        const jda_output *O = M.has_out ? &M.out : NULL;
+        jda_ex_desc X;
+        if (M.four) {
+            jda_ex_desc XK;
+            jda_exact_fill4(X, XK, M.info, M.quant, M.quant_k, M.G, at, O, M.pixel_type, M.colour == JDA_CS_YCCK);
+            memcpy(ex + (n + i) * sizeof(jda_ex_desc), &XK, sizeof(XK));
+        } else if (M.rect) {
+            jda_exr_rec R;
+            jda_exact_fill_rect(X, R, M.info, M.quant, M.G, at, O, M.pixel_type, M.luma_only, M.rq);
+            memcpy(plan->blob.data() + plan->o_rect + i * sizeof(jda_exr_rec), &R, sizeof(R));
+        } else jda_exact_fill_scaled(X, M.info, M.quant, M.G, at, O, M.pixel_type, M.luma_only);
+        memcpy(ex + i * sizeof(jda_ex_desc), &X, sizeof(X));
+    }
 }
 
 #endif

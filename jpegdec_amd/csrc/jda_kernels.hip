@@ -86,6 +86,7 @@ __device__ unsigned long long *g_jda_wgtrace = nullptr;
 #endif
 #include "jda_device_core.h"
 #include "jda_plan.h"
+#include "jda_exact_plan.h"      // jda_exact_launch, jda_exact_kind: what jda_launch_exact is keyed on
 
 // optional phase trace (profiling aid, off unless jda_internal_set_trace() was called): per traced
 // workgroup and wave, the shader clock at each phase boundary
@@ -2943,54 +2944,20 @@ static hipError_t launch_exact_colour4(const jda_ex_desc *ex, const jda_strip *t
     JDA_LAUNCH(jda_exact_colour4<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
     return hipGetLastError();
 }
+// one of jda_exact_planes<MODE, dense | sparse | baseline> (descs as jda_launch_coef_tiles / _sparse_tiles; src: a record an image, read for
+// baseline images), else jda_exact_colour<MODE>
 template <int MODE>
-static hipError_t launch_exact(int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+static hipError_t launch_exact(jda_exact_kind kind, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
 {
     const uint32_t lds_bytes = JDA_CT_WAVES * (uint32_t)jda_ex_layout<MODE>::WAVE_BYTES;
     static_assert(JDA_CT_WAVES * jda_ex_layout<MODE>::WAVE_BYTES <= 64 * 1024, "a workgroup's LDS stays under the default limit");
     const dim3 grid((n_tiles + JDA_CT_WAVES - 1u) / JDA_CT_WAVES), block(64u * JDA_CT_WAVES);
     const auto dense = jda_exact_planes<MODE, 0>, sparse = jda_exact_planes<MODE, 1>, baseline = jda_exact_planes<MODE, 2>;
-    if (stage == 0) JDA_LAUNCH(dense, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
-    else if (stage == 1) JDA_LAUNCH(sparse, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
-    else if (stage == 2) JDA_LAUNCH(baseline, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    if (kind == JDA_EXK_PLANES_DENSE) JDA_LAUNCH(dense, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else if (kind == JDA_EXK_PLANES_SPARSE) JDA_LAUNCH(sparse, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else if (kind == JDA_EXK_PLANES_BASELINE) JDA_LAUNCH(baseline, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
     else JDA_LAUNCH(jda_exact_colour<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
     return hipGetLastError();
-}
-// stage 0 / 1 / 2: jda_exact_planes over tiles of dense coefficient images / sparse ones / resident baseline images of ONE mode (descs as
-// jda_launch_coef_tiles / _sparse_tiles; src: a record an image, read for baseline images); stage 3: jda_exact_colour over tile records of that mode;
-// stage 4: jda_exact_colour_rgb over tile records of RGB-coded images of that mode (a colour layout); stage 5: jda_exact_colour4 over tile
-// records of four-component images whose components 0..2 have that layout
-extern "C" hipError_t jda_launch_exact(int mode, int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
-                                       hipStream_t stream)
-{
-    if (n_tiles == 0) return hipSuccess;
-    if (stage < 0 || stage > 5) return hipErrorInvalidValue;
-    if (stage == 5) {
-        switch (mode) {
-        case JDA_MODE_444: return launch_exact_colour4<JDA_MODE_444>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_420: return launch_exact_colour4<JDA_MODE_420>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_422: return launch_exact_colour4<JDA_MODE_422>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_440: return launch_exact_colour4<JDA_MODE_440>(ex, tiles, n_tiles, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    if (stage == 4) {
-        switch (mode) {
-        case JDA_MODE_444: return launch_exact_rgb<JDA_MODE_444>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_420: return launch_exact_rgb<JDA_MODE_420>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_422: return launch_exact_rgb<JDA_MODE_422>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_440: return launch_exact_rgb<JDA_MODE_440>(ex, tiles, n_tiles, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    switch (mode) {
-    case JDA_MODE_GRAY: return launch_exact<JDA_MODE_GRAY>(stage, descs, ex, src, tiles, n_tiles, stream);
-    case JDA_MODE_444: return launch_exact<JDA_MODE_444>(stage, descs, ex, src, tiles, n_tiles, stream);
-    case JDA_MODE_420: return launch_exact<JDA_MODE_420>(stage, descs, ex, src, tiles, n_tiles, stream);
-    case JDA_MODE_422: return launch_exact<JDA_MODE_422>(stage, descs, ex, src, tiles, n_tiles, stream);
-    case JDA_MODE_440: return launch_exact<JDA_MODE_440>(stage, descs, ex, src, tiles, n_tiles, stream);
-    default: return hipErrorInvalidValue;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3082,52 +3049,30 @@ static hipError_t launch_exact_scaled_rgb(const jda_ex_desc *ex, const jda_strip
     JDA_LAUNCH(jda_exact_colour_scaled_rgb<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
     return hipGetLastError();
 }
+// .. and of jda_exact_planes_scaled<MODE, dense | sparse | baseline, SCALE>, else jda_exact_colour_scaled<MODE>
 template <int MODE, int SCALE>
-static hipError_t launch_exact_scaled(int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+static hipError_t launch_exact_scaled(jda_exact_kind kind, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
+                                      hipStream_t stream)
 {
     const uint32_t lds_bytes = JDA_CT_WAVES * (uint32_t)jda_ex_layout<MODE>::WAVE_BYTES;
     const dim3 grid((n_tiles + JDA_CT_WAVES - 1u) / JDA_CT_WAVES), block(64u * JDA_CT_WAVES);
     const auto dense = jda_exact_planes_scaled<MODE, 0, SCALE>, sparse = jda_exact_planes_scaled<MODE, 1, SCALE>, baseline = jda_exact_planes_scaled<MODE, 2, SCALE>;
-    if (stage == 0) JDA_LAUNCH(dense, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
-    else if (stage == 1) JDA_LAUNCH(sparse, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
-    else if (stage == 2) JDA_LAUNCH(baseline, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    if (kind == JDA_EXK_PLANES_DENSE) JDA_LAUNCH(dense, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else if (kind == JDA_EXK_PLANES_SPARSE) JDA_LAUNCH(sparse, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
+    else if (kind == JDA_EXK_PLANES_BASELINE) JDA_LAUNCH(baseline, grid, block, lds_bytes, stream, descs, ex, src, tiles, n_tiles);
     else JDA_LAUNCH(jda_exact_colour_scaled<MODE>, grid, block, 0, stream, ex, tiles, n_tiles);
     return hipGetLastError();
 }
+// the planes kernels and jda_exact_colour of MODE at `scale`: 1 the full-size kernels, 2, 4 or 8 the _scaled ones
 template <int MODE>
-static hipError_t launch_exact_scaled_mode(int stage, int scale, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
-                                           hipStream_t stream)
+static hipError_t launch_exact_mode(jda_exact_kind kind, int scale, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
+                                    hipStream_t stream)
 {
     switch (scale) {
-    case 2: return launch_exact_scaled<MODE, 2>(stage, descs, ex, src, tiles, n_tiles, stream);
-    case 4: return launch_exact_scaled<MODE, 4>(stage, descs, ex, src, tiles, n_tiles, stream);
-    case 8: return launch_exact_scaled<MODE, 8>(stage, descs, ex, src, tiles, n_tiles, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-// as jda_launch_exact, the tiles those of images decoded at `scale`: 1 -- jda_launch_exact itself, the full-size kernels --, 2, 4 or 8
-extern "C" hipError_t jda_launch_exact_scaled(int mode, int stage, int scale, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles,
-                                              uint32_t n_tiles, hipStream_t stream)
-{
-    if (scale == 1) return jda_launch_exact(mode, stage, descs, ex, src, tiles, n_tiles, stream);
-    if (n_tiles == 0) return hipSuccess;
-    if (stage < 0 || stage > 4) return hipErrorInvalidValue;
-    if (stage == 4) {                                                      // (the colour kernels take the scale from the record)
-        if (scale != 2 && scale != 4 && scale != 8) return hipErrorInvalidValue;
-        switch (mode) {
-        case JDA_MODE_444: return launch_exact_scaled_rgb<JDA_MODE_444>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_420: return launch_exact_scaled_rgb<JDA_MODE_420>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_422: return launch_exact_scaled_rgb<JDA_MODE_422>(ex, tiles, n_tiles, stream);
-        case JDA_MODE_440: return launch_exact_scaled_rgb<JDA_MODE_440>(ex, tiles, n_tiles, stream);
-        default: return hipErrorInvalidValue;
-        }
-    }
-    switch (mode) {
-    case JDA_MODE_GRAY: return launch_exact_scaled_mode<JDA_MODE_GRAY>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
-    case JDA_MODE_444: return launch_exact_scaled_mode<JDA_MODE_444>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
-    case JDA_MODE_420: return launch_exact_scaled_mode<JDA_MODE_420>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
-    case JDA_MODE_422: return launch_exact_scaled_mode<JDA_MODE_422>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
-    case JDA_MODE_440: return launch_exact_scaled_mode<JDA_MODE_440>(stage, scale, descs, ex, src, tiles, n_tiles, stream);
+    case 1: return launch_exact<MODE>(kind, descs, ex, src, tiles, n_tiles, stream);
+    case 2: return launch_exact_scaled<MODE, 2>(kind, descs, ex, src, tiles, n_tiles, stream);
+    case 4: return launch_exact_scaled<MODE, 4>(kind, descs, ex, src, tiles, n_tiles, stream);
+    case 8: return launch_exact_scaled<MODE, 8>(kind, descs, ex, src, tiles, n_tiles, stream);
     default: return hipErrorInvalidValue;
     }
 }
@@ -3160,11 +3105,53 @@ static hipError_t launch_exact_rect(const jda_ex_desc *ex, const jda_exr_rec *re
     JDA_LAUNCH((jda_exact_colour_rect<MODE, RGB>), grid, block, 0, stream, ex, rects, tiles, n_tiles);
     return hipGetLastError();
 }
-extern "C" hipError_t jda_launch_exact_rect(int mode, int rgb, const jda_ex_desc *ex, const jda_exr_rec *rects, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream)
+// One launch of a libjpeg-exact decode call (jda_exact_plan.h): the kernel of L.kind over the L.n_tiles tile records at `tiles`, all of images
+// of layout L.mode decoded at L.scale (the colour kernels take the scale from the image's record: it only picks the instance); descs, ex,
+// src: the call's records, one an image; rects: the rectangle records beside ex, read by the two rectangle kinds alone
+extern "C" hipError_t jda_launch_exact(const jda_exact_launch &L, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_exr_rec *rects,
+                                       const jda_strip *tiles, hipStream_t stream)
 {
+    const uint32_t n_tiles = L.n_tiles;
     if (n_tiles == 0) return hipSuccess;
-    if (rgb) {
-        switch (mode) {
+    if (L.scale != 1 && L.scale != 2 && L.scale != 4 && L.scale != 8) return hipErrorInvalidValue;
+    switch (L.kind) {
+    case JDA_EXK_PLANES_DENSE: case JDA_EXK_PLANES_SPARSE: case JDA_EXK_PLANES_BASELINE: case JDA_EXK_COLOUR:
+        switch (L.mode) {
+        case JDA_MODE_GRAY: return launch_exact_mode<JDA_MODE_GRAY>(L.kind, L.scale, descs, ex, src, tiles, n_tiles, stream);
+        case JDA_MODE_444: return launch_exact_mode<JDA_MODE_444>(L.kind, L.scale, descs, ex, src, tiles, n_tiles, stream);
+        case JDA_MODE_420: return launch_exact_mode<JDA_MODE_420>(L.kind, L.scale, descs, ex, src, tiles, n_tiles, stream);
+        case JDA_MODE_422: return launch_exact_mode<JDA_MODE_422>(L.kind, L.scale, descs, ex, src, tiles, n_tiles, stream);
+        case JDA_MODE_440: return launch_exact_mode<JDA_MODE_440>(L.kind, L.scale, descs, ex, src, tiles, n_tiles, stream);
+        default: return hipErrorInvalidValue;
+        }
+    case JDA_EXK_COLOUR_RGB:
+        switch (L.mode) {
+        case JDA_MODE_444: return L.scale == 1 ? launch_exact_rgb<JDA_MODE_444>(ex, tiles, n_tiles, stream) : launch_exact_scaled_rgb<JDA_MODE_444>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_420: return L.scale == 1 ? launch_exact_rgb<JDA_MODE_420>(ex, tiles, n_tiles, stream) : launch_exact_scaled_rgb<JDA_MODE_420>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_422: return L.scale == 1 ? launch_exact_rgb<JDA_MODE_422>(ex, tiles, n_tiles, stream) : launch_exact_scaled_rgb<JDA_MODE_422>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_440: return L.scale == 1 ? launch_exact_rgb<JDA_MODE_440>(ex, tiles, n_tiles, stream) : launch_exact_scaled_rgb<JDA_MODE_440>(ex, tiles, n_tiles, stream);
+        default: return hipErrorInvalidValue;
+        }
+    case JDA_EXK_COLOUR4:
+        if (L.scale != 1) return hipErrorInvalidValue;
+        switch (L.mode) {
+        case JDA_MODE_444: return launch_exact_colour4<JDA_MODE_444>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_420: return launch_exact_colour4<JDA_MODE_420>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_422: return launch_exact_colour4<JDA_MODE_422>(ex, tiles, n_tiles, stream);
+        case JDA_MODE_440: return launch_exact_colour4<JDA_MODE_440>(ex, tiles, n_tiles, stream);
+        default: return hipErrorInvalidValue;
+        }
+    case JDA_EXK_COLOUR_RECT:
+        switch (L.mode) {
+        case JDA_MODE_GRAY: return launch_exact_rect<JDA_MODE_GRAY, false>(ex, rects, tiles, n_tiles, stream);
+        case JDA_MODE_444: return launch_exact_rect<JDA_MODE_444, false>(ex, rects, tiles, n_tiles, stream);
+        case JDA_MODE_420: return launch_exact_rect<JDA_MODE_420, false>(ex, rects, tiles, n_tiles, stream);
+        case JDA_MODE_422: return launch_exact_rect<JDA_MODE_422, false>(ex, rects, tiles, n_tiles, stream);
+        case JDA_MODE_440: return launch_exact_rect<JDA_MODE_440, false>(ex, rects, tiles, n_tiles, stream);
+        default: return hipErrorInvalidValue;
+        }
+    case JDA_EXK_COLOUR_RECT_RGB:
+        switch (L.mode) {
         case JDA_MODE_444: return launch_exact_rect<JDA_MODE_444, true>(ex, rects, tiles, n_tiles, stream);
         case JDA_MODE_420: return launch_exact_rect<JDA_MODE_420, true>(ex, rects, tiles, n_tiles, stream);
         case JDA_MODE_422: return launch_exact_rect<JDA_MODE_422, true>(ex, rects, tiles, n_tiles, stream);
@@ -3172,14 +3159,7 @@ extern "C" hipError_t jda_launch_exact_rect(int mode, int rgb, const jda_ex_desc
         default: return hipErrorInvalidValue;
         }
     }
-    switch (mode) {
-    case JDA_MODE_GRAY: return launch_exact_rect<JDA_MODE_GRAY, false>(ex, rects, tiles, n_tiles, stream);
-    case JDA_MODE_444: return launch_exact_rect<JDA_MODE_444, false>(ex, rects, tiles, n_tiles, stream);
-    case JDA_MODE_420: return launch_exact_rect<JDA_MODE_420, false>(ex, rects, tiles, n_tiles, stream);
-    case JDA_MODE_422: return launch_exact_rect<JDA_MODE_422, false>(ex, rects, tiles, n_tiles, stream);
-    case JDA_MODE_440: return launch_exact_rect<JDA_MODE_440, false>(ex, rects, tiles, n_tiles, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return hipErrorInvalidValue;
 }
 
 extern "C" hipError_t jda_internal_set_wgtrace(unsigned long long *dev_buf)

@@ -3,6 +3,7 @@
 #ifndef JDA_PLAN_H
 #define JDA_PLAN_H
 
+#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
@@ -65,6 +66,41 @@ inline int jda_fill_desc(jda_dev_desc &D, const jda_image *img, int pixel_type, 
     D.out_w = (uint32_t)(out.width_px < cw ? out.width_px : cw);
     D.out_rows = (uint32_t)(out.rows < ch ? out.rows : ch);
     if (out.pitch_bytes < (int)D.out_w * bpp) return JDA_INVALID_PARAMETER;
+    return JDA_SUCCESS;
+}
+
+// Fill the descriptor of one image of a launch plan (everything but the pointers into the image's HBM block, which the
+// caller sets) and validate the output surface.  Returns JDA_SUCCESS or the error jda_batch_create reports.
+inline int jda_fill_launch_desc(jda_dev_desc &D, const jda_image_info &I, const uint8_t dc_id[3], const uint8_t ac_id[3], const uint8_t q_id[3],
+                                int fast_mul, int general_p1, uint32_t n_mcus_ok, uint32_t scan_len, const jda_output &O, int pt_req, int options,
+                                int *bpp_out)
+{
+    const int opt = jda_effective_options(&I, options);      // progressive: 1/8 thumbnail from the DC scan
+    memset(&D, 0, sizeof(D));
+    if (jda_progressive_full_requested(&I, options)) return JDA_UNSUPPORTED_FEATURE;      // every scan of a progressive file: jda_decode_to_host only
+    if (pt_req < 0 || pt_req > JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
+    int pt = pt_req;
+    if ((opt & JDA_LUMA_ONLY) && pt < JDA_EIGHT_BIT_GRAYSCALE) pt = JDA_EIGHT_BIT_GRAYSCALE;   // jpeg.inl:4991-4993
+    int bpp, ow, oh, cw, ch;
+    { const int grc = jda_output_geometry(&I, pt, opt, &bpp, &ow, &oh, &cw, &ch); if (grc != JDA_SUCCESS) return grc; }
+    D.mode = (uint8_t)jda_mode_of(I);
+    D.ncomp = (uint8_t)I.ncomp;
+    D.pixel_type = (uint8_t)((D.mode == JDA_MODE_GRAY && pt == JDA_RGB8888) ? JDA_RGB565_BIG_ENDIAN : pt);
+    D.scale_shift = (uint8_t)((opt & JDA_SCALE_HALF) ? 1 : (opt & JDA_SCALE_QUARTER) ? 2 : (opt & JDA_SCALE_EIGHTH) ? 3 : 0);
+    D.gray_from_color = (uint8_t)(D.mode != JDA_MODE_GRAY && pt == JDA_EIGHT_BIT_GRAYSCALE);
+    memcpy(D.dc_id, dc_id, 3); memcpy(D.ac_id, ac_id, 3); memcpy(D.q_id, q_id, 3);
+    D.fast_mul = (uint8_t)(fast_mul ? 1 : 0);
+    { static const char *dbg = JDA_LAB_ENV("JDA_DEBUG_SKIP"); D.pad_[0] = (uint8_t)((dbg ? (atoi(dbg) & 3) : 0) | jda_desc_stream_bits(I) | (general_p1 ? JDA_DESC_GENERAL_P1 : 0u)); }   // profiling aid: 1 = no P4, 2 = no IDCT
+    D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
+    D.n_mcus_ok = n_mcus_ok; D.scan_len = scan_len;
+    D.out = (uint8_t *)O.pixels;
+    D.out_pitch = (uint32_t)O.pitch_bytes;
+    D.out_w = (uint32_t)(O.width_px < cw ? O.width_px : cw);
+    D.out_rows = (uint32_t)(O.rows < ch ? O.rows : ch);
+    // the kernels address a surface with 32-bit byte offsets: MCU-padded rows x pitch must stay below 4 GiB
+    if (!O.pixels || ((uintptr_t)O.pixels & 15) || (O.pitch_bytes & 15) || O.width_px < 0 || O.rows < 0 || O.pitch_bytes < (int)D.out_w * bpp ||
+        (uint64_t)(ch + 16) * (uint64_t)O.pitch_bytes >= (1ull << 32) || O.pitch_bytes >= (1 << 23)) return JDA_INVALID_PARAMETER;
+    if (bpp_out) *bpp_out = bpp;
     return JDA_SUCCESS;
 }
 

@@ -29,7 +29,6 @@
 #include "jda_thumbnail_plan.h"
 #include "jda_encode_plan.h"
 #include "jda_recode_plan.h"
-#include "jda_exact_plan.h"
 #include "jda_prescan_plan.h"
 
 extern "C" uint32_t jda_image_fast_mul(const jda_image *img);
@@ -674,43 +673,6 @@ void jda_dev_image_free(jda_ctx *ctx, jda_dev_image *dimg)
 }
 
 size_t jda_dev_image_bytes(const jda_dev_image *dimg) { return dimg ? dimg->bytes : 0; }
-
-} // extern "C"
-
-int jda_fill_launch_desc(jda_dev_desc &D, const jda_image_info &I, const uint8_t dc_id[3], const uint8_t ac_id[3], const uint8_t q_id[3],
-                         int fast_mul, int general_p1, uint32_t n_mcus_ok, uint32_t scan_len, const jda_output &O, int pt_req, int options,
-                         int *bpp_out)
-{
-    const int opt = jda_effective_options(&I, options);      // progressive: 1/8 thumbnail from the DC scan
-    memset(&D, 0, sizeof(D));
-    if (jda_progressive_full_requested(&I, options)) return JDA_UNSUPPORTED_FEATURE;      // every scan of a progressive file: jda_decode_to_host only
-    if (pt_req < 0 || pt_req > JDA_EIGHT_BIT_GRAYSCALE) return JDA_INVALID_PARAMETER;
-    int pt = pt_req;
-    if ((opt & JDA_LUMA_ONLY) && pt < JDA_EIGHT_BIT_GRAYSCALE) pt = JDA_EIGHT_BIT_GRAYSCALE;   // jpeg.inl:4991-4993
-    int bpp, ow, oh, cw, ch;
-    { const int grc = jda_output_geometry(&I, pt, opt, &bpp, &ow, &oh, &cw, &ch); if (grc != JDA_SUCCESS) return grc; }
-    D.mode = (uint8_t)jda_mode_of(I);
-    D.ncomp = (uint8_t)I.ncomp;
-    D.pixel_type = (uint8_t)((D.mode == JDA_MODE_GRAY && pt == JDA_RGB8888) ? JDA_RGB565_BIG_ENDIAN : pt);
-    D.scale_shift = (uint8_t)((opt & JDA_SCALE_HALF) ? 1 : (opt & JDA_SCALE_QUARTER) ? 2 : (opt & JDA_SCALE_EIGHTH) ? 3 : 0);
-    D.gray_from_color = (uint8_t)(D.mode != JDA_MODE_GRAY && pt == JDA_EIGHT_BIT_GRAYSCALE);
-    memcpy(D.dc_id, dc_id, 3); memcpy(D.ac_id, ac_id, 3); memcpy(D.q_id, q_id, 3);
-    D.fast_mul = (uint8_t)(fast_mul ? 1 : 0);
-    { static const char *dbg = JDA_LAB_ENV("JDA_DEBUG_SKIP"); D.pad_[0] = (uint8_t)((dbg ? (atoi(dbg) & 3) : 0) | jda_desc_stream_bits(I) | (general_p1 ? JDA_DESC_GENERAL_P1 : 0u)); }   // profiling aid: 1 = no P4, 2 = no IDCT
-    D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
-    D.n_mcus_ok = n_mcus_ok; D.scan_len = scan_len;
-    D.out = (uint8_t *)O.pixels;
-    D.out_pitch = (uint32_t)O.pitch_bytes;
-    D.out_w = (uint32_t)(O.width_px < cw ? O.width_px : cw);
-    D.out_rows = (uint32_t)(O.rows < ch ? O.rows : ch);
-    // the kernels address a surface with 32-bit byte offsets: MCU-padded rows x pitch must stay below 4 GiB
-    if (!O.pixels || ((uintptr_t)O.pixels & 15) || (O.pitch_bytes & 15) || O.width_px < 0 || O.rows < 0 || O.pitch_bytes < (int)D.out_w * bpp ||
-        (uint64_t)(ch + 16) * (uint64_t)O.pitch_bytes >= (1ull << 32) || O.pitch_bytes >= (1 << 23)) return JDA_INVALID_PARAMETER;
-    if (bpp_out) *bpp_out = bpp;
-    return JDA_SUCCESS;
-}
-
-extern "C" {
 
 jda_batch *jda_batch_create(jda_ctx *ctx, int32_t n, jda_dev_image *const *images,
                             const jda_output *outputs, const int32_t *pixel_types,
@@ -2163,6 +2125,34 @@ int jda_internal_recode_time(jda_ctx *ctx, int32_t n, const jda_recode_source *s
     if (!stage_ms) return JDA_INVALID_PARAMETER;
     return recode_call(ctx, n, src, jobs, NULL, dst, dst_capacity, dst_bytes, status, stage_ms);
 }
+// A file made a resident source of the exact road or of a recode for the length of one call: a progressive file (every scan is what libjpeg
+// decodes: no option bit) or, with four, a four-component one as a coefficient image in the form `coef_form` makes resident (JDA_COEF_*),
+// anything else as a baseline image.  open: JDA_SUCCESS and S set, or the reason; close frees whatever open made.
+struct exact_resident {
+    jda_image *img; jda_coef_image *cimg; jda_dev_image *dimg; jda_dev_coef *dcoef; jda_recode_source S;
+    exact_resident() : img(NULL), cimg(NULL), dimg(NULL), dcoef(NULL) { S.image = NULL; S.coef = NULL; }
+    int open(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, bool progressive, bool four, int32_t coef_form)
+    {
+        int32_t err = JDA_SUCCESS;
+        if (progressive || four) {
+            cimg = four ? jda_coef_prepare(jpeg, len, &err) : jda_progressive_prepare(jpeg, len, &err);
+            if (cimg) dcoef = jda_coef_upload_ex(ctx, cimg, coef_form, &err);
+            S.coef = dcoef;
+        } else {
+            img = jda_prepare(jpeg, len, &err);
+            if (img) dimg = jda_upload(ctx, img, &err);
+            S.image = dimg;
+        }
+        return (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
+    }
+    void close(jda_ctx *ctx)
+    {
+        if (dimg) jda_dev_image_free(ctx, dimg);
+        if (dcoef) jda_dev_coef_free(ctx, dcoef);
+        if (img) jda_image_free(img);
+        if (cimg) jda_coef_image_free(cimg);
+    }
+};
 int jda_recode_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t form, int32_t restart_interval, void *host_file, int64_t capacity, int64_t *file_bytes)
 {
     return jda_recode_to_host_ex(ctx, jpeg, len, form, restart_interval, NULL, host_file, capacity, file_bytes);
@@ -2180,22 +2170,8 @@ int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
     int64_t bound = 0;
     rc = jda_recode_bound_bytes_ex(&I, xform, form, restart_interval, &bound);
     if (rc != JDA_SUCCESS) return rc;
-    jda_image *img = NULL;
-    jda_coef_image *cimg = NULL;
-    jda_recode_source S = { NULL, NULL };
-    int32_t err = JDA_SUCCESS;
-    jda_dev_image *dimg = NULL;
-    jda_dev_coef *dcoef = NULL;
-    if (I.jpeg_type == 1) {
-        cimg = jda_progressive_prepare(jpeg, len, &err);
-        if (cimg) dcoef = jda_coef_upload(ctx, cimg, &err);
-        S.coef = dcoef;
-    } else {
-        img = jda_prepare(jpeg, len, &err);
-        if (img) dimg = jda_upload(ctx, img, &err);
-        S.image = dimg;
-    }
-    rc = (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
+    exact_resident R;
+    rc = R.open(ctx, jpeg, len, I.jpeg_type == 1, false, JDA_COEF_DENSE);
     const int64_t fcap = std::min(capacity, bound);                                        // (no file is longer than the bound)
     void *dfile = NULL;
     if (rc == JDA_SUCCESS) {
@@ -2205,7 +2181,7 @@ int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
     if (rc == JDA_SUCCESS) {
         const jda_recode_job J = { form, restart_interval, 0, 0 };
         int32_t st = JDA_SUCCESS;
-        rc = jda_recode_images_ex(ctx, 1, &S, &J, xform, &dfile, &fcap, file_bytes, &st);
+        rc = jda_recode_images_ex(ctx, 1, &R.S, &J, xform, &dfile, &fcap, file_bytes, &st);
         if (rc == JDA_SUCCESS) rc = st;
         if (rc == JDA_SUCCESS) {
             hipError_t e = hipMemcpyAsync(host_file, dfile, (size_t)*file_bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -2214,30 +2190,35 @@ int jda_recode_to_host_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_
         }
     }
     if (dfile) jda_pool_free(ctx, dfile);
-    if (dimg) jda_dev_image_free(ctx, dimg);
-    if (dcoef) jda_dev_coef_free(ctx, dcoef);
-    if (img) jda_image_free(img);
-    if (cimg) jda_coef_image_free(cimg);
+    R.close(ctx);
     return rc;
 }
 
-// ---- libjpeg-exact decode (jda_exact_* in jda_kernels.hip, jda_ex_* in jda_device_core.h; checks, planes and records: jda_exact_plan.h;
-// DESIGN.md 5.17).  One pool block a call: the blob (descs | records | baseline sources, one of each an image | tile lists) and behind it
-// the scratch -- every planned image's component planes.  The lists of a layout lie dense, sparse, baseline, back to back, so that the
-// colour stage takes all three in one launch.  scales (NULL: all 1): the lists are then per (layout, scale), and a scale
-// above 1 launches the _scaled kernels.
-// flags (the _ex calls'; 0: the calls as they were): JDA_EXACT_COLOUR_MODELS -- the file's colour model decides (jda_exact_check_cs; DESIGN.md
-// 5.19), and the lists gain a fourth column a (layout, scale): the RGB-coded images' tiles, whatever their source, for their own colour launch
-// A four-component image (a coefficient image of jda_coef_prepare) is two images to the planes stage: its components 0..2 as a
-// three-component image of their layout (record i), component 3 as a gray image (record n + i: the records are 2 n with the flag) whose
-// tiles join the call's gray launch and write the fourth plane; jda_exact_colour4 then takes the tiles of record i.  planes: four entries
-// an image with the flag (planes[4 i + c]), three without.
-// rects (jda_exact_decode_surfaces_rect; NULL: none): {x, y, w, h} an image, all zero: that image whole.  A rectangle image's
-// planes tiles are those of its MCU rectangle (jda_exact_rect_plan) in the same lists; its colour stage is jda_exact_colour_rect over tile
-// records of its destination, a list a (layout, RGB-coded or not).  A call with a rectangle keeps colour lists of its own for its whole
-// images, as a call with flags does: the planes lists then hold tiles the whole-image colour kernels must not walk.
-struct exact_image { int kind; jda_image_info info; uint16_t quant[3][64]; jda_exact_geo G; size_t plane_at; bool luma_only; bool rgb; bool four; int colour; bool rect; int32_t mcu[4]; };
-// stage_ms (the measuring hook's, else NULL): [0] the jda_exact_planes launches, [1] the jda_exact_colour launches
+// ---- libjpeg-exact decode (jda_exact_* in jda_kernels.hip, jda_ex_* in jda_device_core.h).  Everything a call
+// decides is the plan's (jda_exact_plan.h: jda_exact_plan_build before the call has device memory, jda_exact_plan_place once it knows where
+// its block lies): what is refused, the images' planes in the scratch, their records, the tile lists and the launches over them.  Here:
+// the sources as the plan reads them, one pool block a call (the plan's blob, behind it the scratch), one copy of the blob, the plan's
+// launches in their order, the planes copied out (jda_exact_decode_planes*), the wait.
+// scales: NULL: all 1; flags: the _ex calls' (JDA_EXACT_COLOUR_MODELS; planes then has four entries an image, planes[4 i + c], else three);
+// rects: jda_exact_decode_surfaces_rect's, NULL: none.
+static void exact_view_coef(const jda_dev_coef *d, jda_exact_source *V)
+{
+    memset(V, 0, sizeof(*V));
+    V->kind = d->form == JDA_COEF_SPARSE ? JDA_EXK_PLANES_SPARSE : JDA_EXK_PLANES_DENSE;
+    V->info = d->info; V->adobe = d->adobe; V->colour = d->colour;
+    memcpy(V->quant, d->raw_quant, sizeof(V->quant));
+    V->tables = d->base; V->scan = d->base + d->off_entries;
+}
+static void exact_view_image(const jda_dev_image *d, jda_exact_source *V)
+{
+    memset(V, 0, sizeof(*V));
+    V->kind = JDA_EXK_PLANES_BASELINE;
+    V->info = d->info; V->adobe = d->adobe; V->colour = d->colour; V->n_mcus_ok = d->n_mcus_ok;
+    for (int c = 0; c < 3; c++) { memcpy(V->quant[c], d->quant_zz[d->q_id[c] & 3], sizeof(V->quant[c])); V->ac_id[c] = d->ac_id[c]; }
+    V->tables = d->base + d->off_tables; V->scan = d->base + d->off_scan; V->scan_len = d->scan_len;
+    V->index = (const uint32_t *)(d->base + d->off_index); V->dc = (const int16_t *)(d->base + d->off_dc);
+}
+// stage_ms (the measuring hook's, else NULL): [0] the planes launches, [1] the colour launches
 static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, const jda_output *outputs, const int32_t *pixel_types, const jda_output *planes,
                       int32_t *status, float *stage_ms = NULL, const int32_t *scales = NULL, uint32_t flags = 0, const int32_t *rects = NULL)
 {
@@ -2247,189 +2228,41 @@ static int exact_call(jda_ctx *ctx, int32_t n, const jda_recode_source *src, con
     if (!src || !status || (!outputs && !planes)) return JDA_INVALID_PARAMETER;
     for (int i = 0; i < n; i++) if ((src[i].image != NULL) == (src[i].coef != NULL)) return JDA_INVALID_PARAMETER;
     (void)hipSetDevice(ctx->device);
-    const size_t nrec = flags ? 2u * (size_t)n : (size_t)n;
-    const int ps = flags ? 4 : 3;                                // entries an image in planes
-    std::vector<jda_dev_desc> descs(nrec);
-    std::vector<jda_ex_desc> ex(nrec);
-    std::vector<jda_ex_src> esrc(nrec);
-    std::vector<exact_image> im((size_t)n);
-    if (flags) { memset(descs.data(), 0, nrec * sizeof(jda_dev_desc)); memset(ex.data(), 0, nrec * sizeof(jda_ex_desc)); memset(esrc.data(), 0, nrec * sizeof(jda_ex_src)); }
-    std::vector<jda_strip> c4_strips[JDA_N_MODES];              // [layout]: the four-component images' tiles for their colour stage
-    std::vector<jda_strip> strips[JDA_N_MODES][4][3];           // [layout][log2 scale][dense | sparse | baseline]
-    // with JDA_EXACT_COLOUR_MODELS the colour stage has lists of its own, [layout][log2 scale][YCbCr or gray | RGB-coded]: the images' tiles
-    // once more, by what the stage does with the planes and whatever their source
-    std::vector<jda_strip> cs_strips[JDA_N_MODES][4][2];
-    bool any_rect = false;
-    for (int i = 0; i < n && rects && outputs; i++) any_rect = any_rect || rects[4 * i] || rects[4 * i + 1] || rects[4 * i + 2] || rects[4 * i + 3];
-    const bool own_cs = flags || any_rect;                       // the colour stage has lists of its own
-    std::vector<jda_strip> rect_strips[JDA_N_MODES][2];         // [layout][YCbCr or gray | RGB-coded]: the rectangles' destination tiles
-    std::vector<jda_exr_rec> rrec(any_rect ? (size_t)n : 0u);
-    if (any_rect) memset(rrec.data(), 0, rrec.size() * sizeof(jda_exr_rec));
-    size_t scratch = 0;
-    int planned = 0;
+    std::vector<jda_exact_source> views(flags ? 2u * (size_t)n : (size_t)n);      // (image i; with flags at n + i component 3 of a four-component one)
     for (int i = 0; i < n; i++) {
-        exact_image &M = im[(size_t)i];
-        jda_dev_desc &D = descs[(size_t)i];
-        memset(&D, 0, sizeof(D)); memset(&ex[(size_t)i], 0, sizeof(jda_ex_desc)); memset(&esrc[(size_t)i], 0, sizeof(jda_ex_src));
-        int adobe = 0, colour = JDA_CS_YCBCR;
-        uint32_t n_ok = 0;
-        if (src[i].image) {
-            const jda_dev_image *d = src[i].image;
-            M.kind = 2; M.info = d->info; adobe = d->adobe; n_ok = d->n_mcus_ok; colour = d->colour;
-            for (int c = 0; c < 3; c++) memcpy(M.quant[c], d->quant_zz[d->q_id[c] & 3], sizeof(M.quant[c]));
-        } else {
-            const jda_dev_coef *d = src[i].coef;
-            M.kind = d->form == JDA_COEF_SPARSE ? 1 : 0; M.info = d->info; adobe = d->adobe; colour = d->colour;
-            memcpy(M.quant, d->raw_quant, sizeof(M.quant));
-        }
-        const jda_image_info &I = M.info;
-        const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
-        const int scale = scales ? scales[i] : 1;
-        const jda_dev_coef *kd = src[i].coef ? src[i].coef->k : NULL;
-        int rc = (flags & JDA_EXACT_COLOUR_MODELS) ? jda_exact_check_cs(I, colour, pt, M.kind == 2, n_ok, scale, kd ? (kd->info.mcus_x == I.mcus_x && kd->info.mcus_y == I.mcus_y ? 0x11 : I.subsample) : 0)
-                                                   : jda_exact_check(I, adobe, pt, M.kind == 2, n_ok);
-        M.rgb = (flags & JDA_EXACT_COLOUR_MODELS) && colour == JDA_CS_RGB;
-        M.four = (flags & JDA_EXACT_COLOUR_MODELS) && I.ncomp == 4;
-        M.colour = colour;
-        M.luma_only = outputs && pt == JDA_EIGHT_BIT_GRAYSCALE && I.ncomp == 3;
-        if (rc == JDA_SUCCESS && M.four && (!kd || M.kind != 0)) rc = JDA_UNSUPPORTED_FEATURE;      // (dense, with component 3 beside it)
-        if (M.four) { M.info.ncomp = 3; M.info.bpp = 24; }     // (components 0..2 from here on: I is M.info)
-        if (rc == JDA_SUCCESS && !jda_exact_scale_ok(scale)) rc = JDA_INVALID_PARAMETER;
-        if (rc == JDA_SUCCESS) rc = M.four ? jda_exact_geometry4(I, kd->info.mcus_x != I.mcus_x || kd->info.mcus_y != I.mcus_y, &M.G) : jda_exact_geometry_scaled(I, M.luma_only, scale, &M.G);
-        const int32_t *rq = any_rect ? rects + 4 * i : NULL;
-        M.rect = rq && (rq[0] || rq[1] || rq[2] || rq[3]);
-        if (rc == JDA_SUCCESS && M.rect) rc = M.four ? JDA_UNSUPPORTED_FEATURE : jda_exact_rect_plan(I, M.G, M.luma_only, rq, M.mcu);
-        if (rc == JDA_SUCCESS && outputs) {
-            jda_image_info B = I;
-            B.jpeg_type = 0;
-            const uint8_t none[3] = { 0, 0, 0 };
-            jda_output O = outputs[i];                         // (a scaled image: the surface is held to the scaled size, not to the file's)
-            if (scale > 1 && O.width_px > (int32_t)M.G.w) O.width_px = (int32_t)M.G.w;
-            if (scale > 1 && O.rows > (int32_t)M.G.h) O.rows = (int32_t)M.G.h;
-            if (M.rect && O.width_px > rq[2]) O.width_px = rq[2];      // (a rectangle: the surface holds it, not the image)
-            if (M.rect && O.rows > rq[3]) O.rows = rq[3];
-            rc = jda_fill_launch_desc(D, B, none, none, none, 0, 0, (uint32_t)(I.mcus_x * I.mcus_y), 0, O, pt == JDA_CMYK8888 ? JDA_RGB8888 : pt, 0, NULL);      // (four bytes a pixel either way)
-        } else if (rc == JDA_SUCCESS) {
-            D.mode = (uint8_t)jda_mode_of(I); D.ncomp = (uint8_t)I.ncomp; D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
-            for (int c = 0; c < (M.four ? 4 : I.ncomp == 3 ? 3 : 1) && rc == JDA_SUCCESS; c++) {
-                const jda_output &P = planes[ps * i + c];
-                const int32_t ew = c == 3 ? (int32_t)M.G.kw : c ? (int32_t)M.G.cw : (int32_t)M.G.w;
-                if (!P.pixels || P.width_px < 0 || P.rows < 0 || P.pitch_bytes < (P.width_px < ew ? P.width_px : ew)) rc = JDA_INVALID_PARAMETER;
-            }
-        }
-        if (rc != JDA_SUCCESS) { status[i] = rc; memset(&D, 0, sizeof(D)); M.kind = -1; continue; }
-        status[i] = JDA_SUCCESS;
-        planned++;
-        M.plane_at = scratch; scratch += M.G.bytes;
-        if (M.kind == 2) {
-            jda_ex_src &J = esrc[(size_t)i];
-            const jda_dev_image *d = src[i].image;
-            J.S.scan = d->base + d->off_scan; J.S.blk_index = (const uint32_t *)(d->base + d->off_index); J.S.blk_dc = (const int16_t *)(d->base + d->off_dc);
-            J.S.tables = d->base + d->off_tables; J.S.scan_len = d->scan_len; J.S.kind = JDA_RC_IMAGE;
-            for (int c = 0; c < 3; c++) J.S.ac_id[c] = d->ac_id[c];
-            J.bpm = (uint32_t)I.blocks_per_mcu; J.nluma = I.ncomp == 3 ? J.bpm - 2u : 1u;
-        } else {
-            D.tables = src[i].coef->base; D.scan = src[i].coef->base + src[i].coef->off_entries;
-        }
-        const int g = M.G.scale == 8u ? 3 : M.G.scale == 4u ? 2 : M.G.scale == 2u ? 1 : 0;
-        jda_append_strips(strips[D.mode][g][M.kind], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode, 0, M.rect ? M.mcu : NULL);
-        if (M.four) {
-            jda_dev_desc &DK = descs[(size_t)n + (size_t)i];
-            DK.mode = (uint8_t)JDA_MODE_GRAY; DK.ncomp = 1; DK.mcus_x = (uint32_t)kd->info.mcus_x; DK.mcus_y = (uint32_t)kd->info.mcus_y;
-            DK.tables = kd->base; DK.scan = kd->base + kd->off_entries;
-            jda_append_strips(strips[JDA_MODE_GRAY][0][0], (uint32_t)(n + i), DK.mcus_x, DK.mcus_y, JDA_MODE_GRAY);
-            if (outputs) jda_append_strips(c4_strips[D.mode], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
-        } else if (M.rect) {
-            const jda_output &O = outputs[i];
-            jda_exact_rect_tiles(rect_strips[D.mode][M.rgb ? 1 : 0], (uint32_t)i, (uint32_t)(O.width_px < rq[2] ? (O.width_px < 0 ? 0 : O.width_px) : rq[2]),
-                                 (uint32_t)(O.rows < rq[3] ? (O.rows < 0 ? 0 : O.rows) : rq[3]));
-        } else if (own_cs && outputs) jda_append_strips(cs_strips[D.mode][g][M.rgb ? 1 : 0], (uint32_t)i, D.mcus_x, D.mcus_y, D.mode);
+        jda_exact_source &V = views[(size_t)i];
+        if (src[i].image) { exact_view_image(src[i].image, &V); continue; }
+        exact_view_coef(src[i].coef, &V);
+        if (flags && src[i].coef->k) { V.k = &views[(size_t)n + (size_t)i]; exact_view_coef(src[i].coef->k, &views[(size_t)n + (size_t)i]); }
     }
-    if (!planned) return JDA_SUCCESS;
-    const size_t o_ex = align16(descs.size() * sizeof(jda_dev_desc)), o_src = o_ex + align16(ex.size() * sizeof(jda_ex_desc));
-    size_t bytes = o_src + align16(esrc.size() * sizeof(jda_ex_src));
-    size_t off[JDA_N_MODES][4][3];
-    for (int m = 0; m < JDA_N_MODES; m++)
-        for (int g = 0; g < 4; g++)
-            for (int f = 0; f < 3; f++) { off[m][g][f] = bytes; bytes += strips[m][g][f].size() * sizeof(jda_strip); }
-    size_t cs_off[JDA_N_MODES][4][2];
-    for (int m = 0; m < JDA_N_MODES; m++)
-        for (int g = 0; g < 4; g++)
-            for (int f = 0; f < 2; f++) { cs_off[m][g][f] = bytes; bytes += cs_strips[m][g][f].size() * sizeof(jda_strip); }
-    size_t c4_off[JDA_N_MODES];
-    for (int m = 0; m < JDA_N_MODES; m++) { c4_off[m] = bytes; bytes += c4_strips[m].size() * sizeof(jda_strip); }
-    size_t rect_off[JDA_N_MODES][2];
-    for (int m = 0; m < JDA_N_MODES; m++)
-        for (int f = 0; f < 2; f++) { rect_off[m][f] = bytes; bytes += rect_strips[m][f].size() * sizeof(jda_strip); }
-    const size_t o_rect = bytes;
-    bytes += rrec.size() * sizeof(jda_exr_rec);
-    const size_t o_scratch = (bytes + 255u) & ~(size_t)255u;
+    jda_exact_plan plan;
+    const int rc = jda_exact_plan_build(n, views.data(), outputs, pixel_types, planes, scales, flags, rects, status, &plan);
+    if (rc != JDA_SUCCESS || !plan.n_planned) return rc;
     uint8_t *blk = NULL;
-    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, o_scratch + scratch);
+    hipError_t e = jda_pool_alloc(ctx, (void **)&blk, plan.o_scratch + plan.scratch);
     if (e != hipSuccess) { jda_set_err(ctx, e, "hipMalloc(exact decode)"); return JDA_ERROR_MEMORY; }
-    for (int i = 0; i < n; i++) {
-        const exact_image &M = im[(size_t)i];
-        if (M.kind < 0) continue;
-        const int pt = outputs ? (pixel_types ? pixel_types[i] : JDA_RGB8888) : JDA_RGB8888;
-        if (M.four)
-            jda_exact_fill4(ex[(size_t)i], ex[(size_t)n + (size_t)i], M.info, M.quant, src[i].coef->k->raw_quant[0], M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt,
-                            M.colour == JDA_CS_YCCK);
-        else if (M.rect) jda_exact_fill_rect(ex[(size_t)i], rrec[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, &outputs[i], pt, M.luma_only, rects + 4 * i);
-        else jda_exact_fill_scaled(ex[(size_t)i], M.info, M.quant, M.G, blk + o_scratch + M.plane_at, outputs ? &outputs[i] : NULL, pt, M.luma_only);
-    }
-    std::vector<uint8_t> blob(bytes, 0);
-    memcpy(blob.data(), descs.data(), descs.size() * sizeof(jda_dev_desc));
-    memcpy(blob.data() + o_ex, ex.data(), ex.size() * sizeof(jda_ex_desc));
-    memcpy(blob.data() + o_src, esrc.data(), esrc.size() * sizeof(jda_ex_src));
-    for (int m = 0; m < JDA_N_MODES; m++)
-        for (int g = 0; g < 4; g++)
-            for (int f = 0; f < 3; f++)
-                if (!strips[m][g][f].empty()) memcpy(blob.data() + off[m][g][f], strips[m][g][f].data(), strips[m][g][f].size() * sizeof(jda_strip));
-    for (int m = 0; m < JDA_N_MODES; m++)
-        for (int g = 0; g < 4; g++)
-            for (int f = 0; f < 2; f++)
-                if (!cs_strips[m][g][f].empty()) memcpy(blob.data() + cs_off[m][g][f], cs_strips[m][g][f].data(), cs_strips[m][g][f].size() * sizeof(jda_strip));
-    for (int m = 0; m < JDA_N_MODES; m++)
-        if (!c4_strips[m].empty()) memcpy(blob.data() + c4_off[m], c4_strips[m].data(), c4_strips[m].size() * sizeof(jda_strip));
-    for (int m = 0; m < JDA_N_MODES; m++)
-        for (int f = 0; f < 2; f++)
-            if (!rect_strips[m][f].empty()) memcpy(blob.data() + rect_off[m][f], rect_strips[m][f].data(), rect_strips[m][f].size() * sizeof(jda_strip));
-    if (!rrec.empty()) memcpy(blob.data() + o_rect, rrec.data(), rrec.size() * sizeof(jda_exr_rec));
-    e = hipMemcpyAsync(blk, blob.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
-    const jda_dev_desc *d_descs = (const jda_dev_desc *)blk;
-    const jda_ex_desc *d_ex = (const jda_ex_desc *)(blk + o_ex);
-    const jda_ex_src *d_src = (const jda_ex_src *)(blk + o_src);
+    jda_exact_plan_place(&plan, blk);
+    e = hipMemcpyAsync(blk, plan.blob.data(), plan.blob.size(), hipMemcpyHostToDevice, ctx->stream);
     hipEvent_t ev[3] = { NULL, NULL, NULL };
     for (int k = 0; k < 3 && stage_ms && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess; m++)
-        for (int g = 0; g < 4 && e == hipSuccess; g++)
-            for (int f = 0; f < 3 && e == hipSuccess; f++)
-                e = jda_launch_exact_scaled(m, f, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][g][f]), (uint32_t)strips[m][g][f].size(), ctx->stream);
-    if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && !own_cs; m++)
-        for (int g = 0; g < 4 && e == hipSuccess; g++)
-            e = jda_launch_exact_scaled(m, 3, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + off[m][g][0]),
-                                        (uint32_t)(strips[m][g][0].size() + strips[m][g][1].size() + strips[m][g][2].size()), ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && own_cs; m++)
-        for (int g = 0; g < 4 && e == hipSuccess; g++)
-            for (int f = 0; f < 2 && e == hipSuccess; f++)
-                e = jda_launch_exact_scaled(m, 3 + f, 1 << g, d_descs, d_ex, d_src, (const jda_strip *)(blk + cs_off[m][g][f]), (uint32_t)cs_strips[m][g][f].size(), ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && outputs && flags; m++)
-        e = jda_launch_exact_scaled(m, 5, 1, d_descs, d_ex, d_src, (const jda_strip *)(blk + c4_off[m]), (uint32_t)c4_strips[m].size(), ctx->stream);
-    for (int m = 0; m < JDA_N_MODES && e == hipSuccess && any_rect; m++)
-        for (int f = 0; f < 2 && e == hipSuccess; f++)
-            e = jda_launch_exact_rect(m, f, d_ex, (const jda_exr_rec *)(blk + o_rect), (const jda_strip *)(blk + rect_off[m][f]), (uint32_t)rect_strips[m][f].size(), ctx->stream);
+    for (size_t k = 0; k <= plan.launches.size() && e == hipSuccess; k++) {
+        if (k == plan.colour_begin && stage_ms) e = hipEventRecord(ev[1], ctx->stream);
+        if (k < plan.launches.size() && e == hipSuccess)
+            e = jda_launch_exact(plan.launches[k], (const jda_dev_desc *)blk, (const jda_ex_desc *)(blk + plan.o_ex), (const jda_ex_src *)(blk + plan.o_src),
+                                 (const jda_exr_rec *)(blk + plan.o_rect), (const jda_strip *)(blk + plan.launches[k].off), ctx->stream);
+    }
     if (stage_ms && e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
+    const int ps = flags ? 4 : 3;                                // entries an image in planes
     for (int i = 0; i < n && e == hipSuccess && planes; i++) {
-        const exact_image &M = im[(size_t)i];
+        const jda_exact_image &M = plan.images[(size_t)i];
         if (M.kind < 0) continue;
         for (int c = 0; c < (M.four ? 4 : M.info.ncomp == 3 ? 3 : 1) && e == hipSuccess; c++) {
             const jda_output &P = planes[ps * i + c];
             const int32_t ew = c == 3 ? (int32_t)M.G.kw : c ? (int32_t)M.G.cw : (int32_t)M.G.w, eh = c == 3 ? (int32_t)M.G.kh : c ? (int32_t)M.G.ch : (int32_t)M.G.h;
             const size_t cw = (size_t)(P.width_px < ew ? P.width_px : ew), crows = (size_t)(P.rows < eh ? P.rows : eh);
             if (cw && crows)
-                e = hipMemcpy2DAsync(P.pixels, (size_t)P.pitch_bytes, blk + o_scratch + M.plane_at + (c == 3 ? M.G.off_k : M.G.off[c]), c == 3 ? M.G.pitch_k : c ? M.G.pitch_c : M.G.pitch_y, cw, crows,
+                e = hipMemcpy2DAsync(P.pixels, (size_t)P.pitch_bytes, blk + plan.o_scratch + M.plane_at + (c == 3 ? M.G.off_k : M.G.off[c]), c == 3 ? M.G.pitch_k : c ? M.G.pitch_c : M.G.pitch_y, cw, crows,
                                      hipMemcpyDeviceToDevice, ctx->stream);
         }
     }
@@ -2567,54 +2400,6 @@ int jda_internal_exact_time_scaled(jda_ctx *ctx, int32_t n, const jda_recode_sou
     stage_ms[0] = stage_ms[1] = 0.f;
     return exact_call(ctx, n, src, outputs, pixel_types, NULL, status, stage_ms, scales);
 }
-int jda_decode_to_host_exact(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, void *host_pixels, int32_t pitch_bytes, int32_t rows)
-{
-    return jda_decode_to_host_exact_scaled(ctx, jpeg, len, pixel_type, 1, host_pixels, pitch_bytes, rows);
-}
-int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, void *host_pixels, int32_t pitch_bytes, int32_t rows)
-{
-    return jda_decode_to_host_exact_ex(ctx, jpeg, len, pixel_type, scale, 0u, host_pixels, pitch_bytes, rows);
-}
-static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect, void *host_pixels,
-                         int32_t pitch_bytes, int32_t rows, int32_t *tiles);
-int jda_decode_to_host_exact_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, void *host_pixels, int32_t pitch_bytes,
-                                int32_t rows)
-{
-    return exact_to_host(ctx, jpeg, len, pixel_type, scale, flags, NULL, host_pixels, pitch_bytes, rows, NULL);
-}
-int jda_decode_to_host_exact_rect(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect, void *host_pixels,
-                                  int32_t pitch_bytes, int32_t rows, int32_t *tiles)
-{
-    return exact_to_host(ctx, jpeg, len, pixel_type, scale, flags, rect, host_pixels, pitch_bytes, rows, tiles);
-}
-// A file made a resident source of the exact road for the length of one call: a progressive file (every scan is what libjpeg decodes: no
-// option bit) or, with four, a four-component one as a coefficient image, anything else as a baseline image.  open: JDA_SUCCESS and S set,
-// or the reason; close frees whatever open made.
-struct exact_resident {
-    jda_image *img; jda_coef_image *cimg; jda_dev_image *dimg; jda_dev_coef *dcoef; jda_recode_source S;
-    exact_resident() : img(NULL), cimg(NULL), dimg(NULL), dcoef(NULL) { S.image = NULL; S.coef = NULL; }
-    int open(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, bool progressive, bool four)
-    {
-        int32_t err = JDA_SUCCESS;
-        if (progressive || four) {
-            cimg = four ? jda_coef_prepare(jpeg, len, &err) : jda_progressive_prepare(jpeg, len, &err);
-            if (cimg) dcoef = jda_coef_upload_ex(ctx, cimg, JDA_COEF_AUTO, &err);
-            S.coef = dcoef;
-        } else {
-            img = jda_prepare(jpeg, len, &err);
-            if (img) dimg = jda_upload(ctx, img, &err);
-            S.image = dimg;
-        }
-        return (S.image || S.coef) ? JDA_SUCCESS : (err != JDA_SUCCESS ? err : JDA_DECODE_ERROR);
-    }
-    void close(jda_ctx *ctx)
-    {
-        if (dimg) jda_dev_image_free(ctx, dimg);
-        if (dcoef) jda_dev_coef_free(ctx, dcoef);
-        if (img) jda_image_free(img);
-        if (cimg) jda_coef_image_free(cimg);
-    }
-};
 // rect (NULL or all zero: the whole image): the surface and the host rows hold the rectangle; tiles (may be NULL): [0] the planes-stage tiles
 // launched, [1] those of the whole image
 static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect, void *host_pixels,
@@ -2656,16 +2441,12 @@ static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t
         int32_t mcu[4];
         const bool luma_only = pixel_type == JDA_EIGHT_BIT_GRAYSCALE && I.ncomp == 3;
         if (!four && jda_exact_geometry_scaled(I, luma_only, scale, &G) == JDA_SUCCESS && (!has_rect || jda_exact_rect_plan(I, G, luma_only, rect, mcu) == JDA_SUCCESS)) {
-            std::vector<jda_strip> part, whole;
-            jda_append_strips(part, 0, (uint32_t)I.mcus_x, (uint32_t)I.mcus_y, jda_mode_of(I), 0, has_rect ? mcu : NULL);
-            jda_append_strips(whole, 0, (uint32_t)I.mcus_x, (uint32_t)I.mcus_y, jda_mode_of(I));
-            for (const jda_strip &t : part) tiles[0] += t.count ? 1 : 0;
-            for (const jda_strip &t : whole) tiles[1] += t.count ? 1 : 0;
+            tiles[0] = jda_exact_tile_count(I, has_rect ? mcu : NULL); tiles[1] = jda_exact_tile_count(I, NULL);
         }
     }
     if ((int64_t)pitch_bytes < (int64_t)ow * (pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4)) return JDA_INVALID_PARAMETER;      // (a row holds the image's width, as a surface's does)
     exact_resident R;
-    rc = R.open(ctx, jpeg, len, I.jpeg_type == 1, four);
+    rc = R.open(ctx, jpeg, len, I.jpeg_type == 1, four, JDA_COEF_AUTO);
     const int bpp = pixel_type == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4;
     const int dpitch = (int)align16((size_t)ow * bpp), drows = rows < oh ? rows : oh;
     void *dout = NULL;
@@ -2683,6 +2464,24 @@ static int exact_to_host(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t
     if (dout) jda_pool_free(ctx, dout);
     R.close(ctx);
     return rc;
+}
+int jda_decode_to_host_exact(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, void *host_pixels, int32_t pitch_bytes, int32_t rows)
+{
+    return jda_decode_to_host_exact_scaled(ctx, jpeg, len, pixel_type, 1, host_pixels, pitch_bytes, rows);
+}
+int jda_decode_to_host_exact_scaled(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, void *host_pixels, int32_t pitch_bytes, int32_t rows)
+{
+    return jda_decode_to_host_exact_ex(ctx, jpeg, len, pixel_type, scale, 0u, host_pixels, pitch_bytes, rows);
+}
+int jda_decode_to_host_exact_ex(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, void *host_pixels, int32_t pitch_bytes,
+                                int32_t rows)
+{
+    return exact_to_host(ctx, jpeg, len, pixel_type, scale, flags, NULL, host_pixels, pitch_bytes, rows, NULL);
+}
+int jda_decode_to_host_exact_rect(jda_ctx *ctx, const uint8_t *jpeg, int32_t len, int32_t pixel_type, int32_t scale, uint32_t flags, const int32_t *rect, void *host_pixels,
+                                  int32_t pitch_bytes, int32_t rows, int32_t *tiles)
+{
+    return exact_to_host(ctx, jpeg, len, pixel_type, scale, flags, rect, host_pixels, pitch_bytes, rows, tiles);
 }
 
 // Pillow's Image.open(f).thumbnail((req_w, req_h), F, reducing_gap): the plan, the exact decode at its scale into a device surface, the reduce
@@ -2709,7 +2508,7 @@ int jda_decode_to_host_thumbnail(jda_ctx *ctx, const uint8_t *jpeg, int32_t len,
     if ((int64_t)pitch_bytes < (int64_t)T.out_w * bpp || rows < T.out_h) return JDA_INVALID_PARAMETER;
     const bool reduces = T.fx > 1 || T.fy > 1;
     exact_resident R;
-    rc = R.open(ctx, jpeg, len, I.jpeg_type == 1, false);
+    rc = R.open(ctx, jpeg, len, I.jpeg_type == 1, false, JDA_COEF_AUTO);
     // one block: the draft image, behind it the reduced image and the result where the plan has those steps (each begins at a multiple of 256)
     jda_output D[3];
     size_t at = 0;

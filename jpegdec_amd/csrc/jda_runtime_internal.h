@@ -6,6 +6,7 @@
 
 #include "jda_internal.h"
 #include "jda_plan.h"
+#include "jda_exact_plan.h"
 
 // launch lists of a batch: one per (mode, fast_mul, kernel variant, window size, P1 in chunks);
 // index = (((mode * 2 + fast) * 4 + variant) * 2 + big) * 2 + cont
@@ -139,11 +140,7 @@ inline int jda_list_index(const jda_dev_desc &D, int variant, int big, int cont 
 }
 int jda_use_cont(const jda_dev_desc &D, int variant, uint32_t n_cont);
 int jda_big_window(const jda_dev_desc &D, int variant, uint32_t tiles_total = 0, uint32_t tiles_over_small = 0);
-// Fill the descriptor of one image of a launch plan (everything but the pointers into the image's HBM block, which the
-// caller sets) and validate the output surface.  Returns JDA_SUCCESS or the error jda_batch_create reports.
-int jda_fill_launch_desc(jda_dev_desc &D, const jda_image_info &I, const uint8_t dc_id[3], const uint8_t ac_id[3], const uint8_t q_id[3],
-                         int fast_mul, int general_p1, uint32_t n_mcus_ok, uint32_t scan_len, const jda_output &O, int pixel_type, int options,
-                         int *bpp_out);
+// (jda_fill_launch_desc, the descriptor of one image of a launch plan: jda_plan.h)
 
 extern "C" hipError_t jda_launch_segscan_fused(const jda_segscan_params *params, uint32_t n_images, uint32_t max_segs, uint32_t round, hipStream_t stream);
 extern "C" hipError_t jda_launch_checksum(const void *base, uint32_t pitch, uint32_t row_bytes, uint32_t rows, unsigned long long *out, hipStream_t stream);
@@ -223,18 +220,11 @@ extern "C" void jda_decode_pool_release(hipStream_t stream);
 extern "C" hipError_t jda_launch_coef_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
 // the same from the sparse form (descs[i].tables: quantisers | first[], .scan: entries): jda_sparse_tiles<mode>
 extern "C" hipError_t jda_launch_sparse_tiles(int mode, const jda_dev_desc *descs, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
-// the libjpeg-exact decode (jda_ex_* in jda_device_core.h): stage 0 / 1 / 2 jda_exact_planes<mode> over tiles of dense coefficient images /
-// sparse ones / resident baseline images (descs as for the two launches above, ex and src: a record an image), stage 3 jda_exact_colour<mode>
-// over tile records of that mode
-extern "C" hipError_t jda_launch_exact(int mode, int stage, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles, uint32_t n_tiles,
-                                       hipStream_t stream);
-// the same over tiles of images decoded at `scale`: 1 -- jda_launch_exact itself --, or 2, 4, 8: jda_exact_planes_scaled<mode,
-// stage, scale> (stage 0 / 1 / 2), jda_exact_colour_scaled<mode> (stage 3)
-extern "C" hipError_t jda_launch_exact_scaled(int mode, int stage, int scale, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_strip *tiles,
-                                              uint32_t n_tiles, hipStream_t stream);
-// the colour stage of pixel rectangles: jda_exact_colour_rect<mode, rgb> over tile records of the destination rectangles
-// (jda_exact_rect_tiles) of images of ONE layout, whatever their scales; rects: a record an image, beside ex
-extern "C" hipError_t jda_launch_exact_rect(int mode, int rgb, const jda_ex_desc *ex, const jda_exr_rec *rects, const jda_strip *tiles, uint32_t n_tiles, hipStream_t stream);
+// one launch of a libjpeg-exact decode call (jda_exact_plan.h): the kernel of L.kind for images of layout L.mode decoded
+// at L.scale over the L.n_tiles records at `tiles`; descs, ex, src: the call's records, one an image (descs as for the two launches above, src
+// read for baseline images), rects: the rectangle records beside ex (read by the two rectangle kinds alone)
+extern "C" hipError_t jda_launch_exact(const jda_exact_launch &L, const jda_dev_desc *descs, const jda_ex_desc *ex, const jda_ex_src *src, const jda_exr_rec *rects,
+                                       const jda_strip *tiles, hipStream_t stream);
 inline uint32_t jda_flat_items(const jda_dev_desc &D) { return (D.mode == JDA_MODE_GRAY ? (D.mcus_x + 3u) >> 2 : D.mcus_x) * D.mcus_y; }      // quads of blocks (gray) / MCUs
 
 #endif

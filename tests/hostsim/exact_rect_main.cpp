@@ -2,7 +2,8 @@
 // (make exactrectasan): the rectangle plan and every lane of the planes and colour stages over the files named on the command line -- a
 // baseline file as a resident baseline image, a progressive one as a dense and as a sparse coefficient image --, at every scale, RGB8888
 // and gray, whole, at every alignment and parity, at the image's edges and clipped; each rectangle's pixels are held to the crop of the
-// whole-image rectangle's.  A program: nothing is loaded into an interpreter.  Prints "exact_rect_asan ok".
+// whole-image rectangle's.  In front of the files the plan of a whole call (jda_exact_plan_build / _place) over a mixed batch made of header
+// numbers.  A program: nothing is loaded into an interpreter.  Prints "exact_rect_asan ok".
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -16,9 +17,42 @@ extern "C" int exactrectsim_plan(int width, int height, int ncomp, int subsample
 extern "C" int exactrectsim_run(const uint8_t *jpeg, int len, const int16_t *coefs, uint32_t n_blocks, int source, int pixel_type, int scale, int n_rects,
                                 const int32_t *rects, const int32_t *clips, uint8_t *out, uint8_t *twin_out, int32_t *status, int32_t *info);
 
+extern "C" int exactrectsim_call_plan(int n, const int32_t *hdr, uint32_t flags, int with_rects, int32_t *status, int64_t *launches, int cap, int32_t *n_launches,
+                                      uint8_t *blob, int64_t blob_cap, int64_t *layout, int64_t *image);
+
+// the plan of one call over every layout, source kind and scale, a rectangle, an RGB-coded and a four-component image and, in the middle, an
+// image that is refused; with the colour stage's own lists and with the shared ones; and calls with nothing to launch
+static bool call_plans()
+{
+    // width, height, ncomp, subsample, source, colour model, pixel type, scale, rectangle, surface
+    static const int32_t hdr[10][14] = {
+        { 517, 11, 1, 0x00, 0, JDA_CS_GRAY, JDA_RGB8888, 1, 0, 0, 0, 0, 517, 11 },  { 165, 11, 3, 0x11, 1, JDA_CS_YCBCR, JDA_RGB8888, 2, 0, 0, 0, 0, 83, 6 },
+        { 173, 27, 3, 0x22, 2, JDA_CS_YCBCR, JDA_RGB8888, 1, 0, 0, 0, 0, 173, 27 }, { 269, 11, 3, 0x21, 0, JDA_CS_YCBCR, JDA_RGB8888, 8, 0, 0, 0, 0, 34, 2 },
+        { 173, 27, 3, 0x22, 2, JDA_CS_YCBCR, JDA_RGB8888, 3, 0, 0, 0, 0, 173, 27 }, { 133, 27, 3, 0x12, 2, JDA_CS_YCBCR, JDA_RGB8888, 1, 0, 0, 0, 0, 133, 27 },
+        { 173, 27, 3, 0x22, 0, JDA_CS_YCBCR, JDA_RGB8888, 1, 21, 3, 97, 20, 97, 20 }, { 165, 11, 3, 0x11, 1, JDA_CS_RGB, JDA_RGB8888, 2, 0, 0, 0, 0, 83, 6 },
+        { 165, 11, 4, 0x11, 0, JDA_CS_CMYK, JDA_RGB8888, 1, 0, 0, 0, 0, 165, 11 },  { 173, 27, 3, 0x22, 1, JDA_CS_YCBCR, JDA_EIGHT_BIT_GRAYSCALE, 1, 0, 0, 0, 0, 173, 27 } };
+    std::vector<uint8_t> blob(1 << 16);
+    int64_t launches[64 * 5], layout[10], image[10 * 10];
+    int32_t status[10], nl = -1;
+    for (int own = 1; own >= 0; own--) {
+        for (int i = 0; i < 10; i++) status[i] = 99;
+        if (exactrectsim_call_plan(10, &hdr[0][0], own ? JDA_EXACT_COLOUR_MODELS : 0u, own, status, launches, 64, &nl, blob.data(), (int64_t)blob.size(), layout, image) != JDA_SUCCESS) return false;
+        // (without the flag the RGB-coded file is read as YCbCr and the four-component one refused)
+        for (int i = 0; i < 10; i++) if (status[i] != (i == 4 ? JDA_INVALID_PARAMETER : i == 8 && !own ? JDA_UNSUPPORTED_FEATURE : JDA_SUCCESS)) return false;
+        if (nl != (own ? 16 : 12) || layout[6] != (own ? 8 : 7) || layout[8] != (own ? 9 : 8)) return false;      // launches, the first colour launch, images planned
+        for (int k = 0; k < nl; k++)
+            if (launches[5 * k + 3] + 16 * launches[5 * k + 4] > layout[0] || (launches[5 * k + 3] & 15)) return false;
+    }
+    if (exactrectsim_call_plan(0, NULL, 0u, 0, status, launches, 64, &nl, blob.data(), (int64_t)blob.size(), layout, image) != JDA_SUCCESS || nl != 0) return false;
+    if (exactrectsim_call_plan(1, &hdr[4][0], 0u, 1, status, launches, 64, &nl, blob.data(), (int64_t)blob.size(), layout, image) != JDA_SUCCESS || nl != 0 || layout[0] != 0 ||
+        status[0] != JDA_INVALID_PARAMETER) return false;
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 2) { fprintf(stderr, "usage: exact_rect_asan file.jpg ..\n"); return 2; }
+    if (!call_plans()) { fprintf(stderr, "the plan of a call\n"); return 1; }
     for (int a = 1; a < argc; a++) {
         FILE *f = fopen(argv[a], "rb");
         if (!f) { fprintf(stderr, "%s: cannot open\n", argv[a]); return 2; }

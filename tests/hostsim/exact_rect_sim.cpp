@@ -1,5 +1,6 @@
 // tests/hostsim/exact_rect_sim.cpp -- TEST INFRASTRUCTURE: the libjpeg-exact decode of a pixel rectangle lane by lane on the
-// CPU: the plan (jda_exact_rect_plan, jda_exact_rect_tiles of jda_exact_plan.h), the EXISTING planes lanes (jda_ex_* at full size, jda_exs_*
+// CPU: the plan (a rectangle = a call of one image through jda_exact_plan_build / _place of jda_exact_plan.h, whose block holds the records
+// and both tile lists; exactrectsim_call_plan: the plan of a whole call from header numbers), the EXISTING planes lanes (jda_ex_* at full size, jda_exs_*
 // at 1/2, 1/4, 1/8; all three load phases) over the rectangle's tile list into a POISONED scratch, then the new colour lanes (jda_exr_* of
 // jda_device_core.h, what jda_exact_colour_rect runs) over the destination's tile list.
 //
@@ -169,6 +170,80 @@ extern "C" int exactrectsim_plan(int width, int height, int ncomp, int subsample
     return jda_exact_rect_plan(I, G, luma_only, rect, mcu);
 }
 
+// the records a workgroup of the planes kernels takes: what jda_append_strips pads an image's tiles to
+extern "C" int exactrectsim_tiles_per_wg(int mode) { return (int)jda_tiles_per_wg(mode); }
+
+// The plan of a whole call (jda_exact_plan_build + jda_exact_plan_place) from header numbers alone, nothing decoded.  hdr: n x 14 --
+// width, height, ncomp, subsample, source kind (0 dense, 1 sparse, 2 baseline), colour model (JDA_CS_*), pixel type, scale, the rectangle
+// {x, y, w, h}, the surface's width_px and rows.  A four-component image gets a component 3 of component 0's sampling.  with_rects == 0: the
+// call has no rectangles (the hdr's are ignored).  The sources' and surfaces' addresses are made up (nothing reads through them); the block
+// is real.  Out: status (n); launches: up to cap x 5 {kind, mode, scale, blob offset, tile records}, *n_launches; blob: the placed blob (up
+// to blob_cap bytes); layout[10]: blob bytes, o_ex, o_src, o_rect, o_scratch, scratch, colour_begin, n_rec, n_planned, the block's address;
+// image: n x 10 {kind or -1, plane_at, plane bytes, Y plane's offset from the block, mcu[4], jda_exact_tile_count of the MCU rectangle and
+// of the whole image}.  Returns the build's code, or -1 where cap or blob_cap is too small.
+extern "C" int exactrectsim_call_plan(int n, const int32_t *hdr, uint32_t flags, int with_rects, int32_t *status, int64_t *launches, int cap, int32_t *n_launches,
+                                      uint8_t *blob, int64_t blob_cap, int64_t *layout, int64_t *image)
+{
+    std::vector<jda_exact_source> src(2u * (size_t)(n > 0 ? n : 0));
+    std::vector<jda_output> outs((size_t)(n > 0 ? n : 0));
+    std::vector<int32_t> pts, scales, rects;
+    for (int i = 0; i < n; i++) {
+        const int32_t *h = hdr + 14 * i;
+        jda_exact_source &S = src[(size_t)i];
+        memset(&S, 0, sizeof(S));
+        S.info = info_of(h[0], h[1], h[2], h[3]);
+        const int mode = jda_mode_of(S.info);
+        const int hs = (mode == JDA_MODE_420 || mode == JDA_MODE_422) ? 2 : 1, vs = (mode == JDA_MODE_420 || mode == JDA_MODE_440) ? 2 : 1;
+        S.info.blocks_per_mcu = h[2] == 1 ? 1 : hs * vs + 2; S.info.bpp = h[2] * 8; S.info.mcu_w = 8 * hs; S.info.mcu_h = 8 * vs;
+        S.kind = (jda_exact_kind)h[4]; S.colour = h[5]; S.n_mcus_ok = (uint32_t)(S.info.mcus_x * S.info.mcus_y);
+        for (int c = 0; c < 3; c++) for (int z = 0; z < 64; z++) S.quant[c][z] = (uint16_t)(1 + c + z);
+        S.tables = (const uint8_t *)(uintptr_t)(0x10000000u + 0x100000u * (uint32_t)i); S.scan = S.tables + 0x1000;
+        S.index = (const uint32_t *)(S.tables + 0x40000); S.dc = (const int16_t *)(S.tables + 0x80000); S.scan_len = 64;
+        if (h[2] == 4) {
+            jda_exact_source &K = src[(size_t)n + (size_t)i];
+            memset(&K, 0, sizeof(K));
+            K.info = info_of(h[0], h[1], 1, 0);
+            K.info.mcus_x = S.info.mcus_x * hs; K.info.mcus_y = S.info.mcus_y * vs; K.info.blocks_per_mcu = 1; K.info.bpp = 8;
+            K.kind = JDA_EXK_PLANES_DENSE; K.colour = JDA_CS_GRAY;
+            for (int z = 0; z < 64; z++) K.quant[0][z] = (uint16_t)(7 + z);
+            K.tables = S.tables + 0xC0000; K.scan = K.tables + 0x1000;
+            S.k = &K;
+        }
+        pts.push_back(h[6]); scales.push_back(h[7]);
+        rects.insert(rects.end(), h + 8, h + 12);
+        jda_output &O = outs[(size_t)i];
+        O.pixels = (void *)(uintptr_t)(0x40000000u + 0x1000000u * (uint32_t)i);
+        O.width_px = h[12]; O.rows = h[13]; O.pitch_bytes = (h[12] * (h[6] == JDA_EIGHT_BIT_GRAYSCALE ? 1 : 4) + 15) & ~15;
+    }
+    jda_exact_plan plan;
+    const int rc = jda_exact_plan_build(n, src.data(), outs.data(), pts.data(), NULL, scales.data(), flags, with_rects ? rects.data() : NULL, status, &plan);
+    uint8_t *block = dup<uint8_t>(NULL, 0, plan.o_scratch + plan.scratch);
+    if (rc == JDA_SUCCESS) jda_exact_plan_place(&plan, block);
+    const int64_t lay[10] = { (int64_t)plan.blob.size(), (int64_t)plan.o_ex, (int64_t)plan.o_src, (int64_t)plan.o_rect, (int64_t)plan.o_scratch, (int64_t)plan.scratch,
+                              (int64_t)plan.colour_begin, (int64_t)plan.n_rec, plan.n_planned, (int64_t)(uintptr_t)block };
+    memcpy(layout, lay, sizeof(lay));
+    *n_launches = (int32_t)plan.launches.size();
+    const bool fits = plan.launches.size() <= (size_t)cap && plan.blob.size() <= (size_t)blob_cap;
+    for (size_t k = 0; fits && k < plan.launches.size(); k++) {
+        const jda_exact_launch &L = plan.launches[k];
+        const int64_t row[5] = { (int64_t)L.kind, L.mode, L.scale, (int64_t)L.off, (int64_t)L.n_tiles };
+        memcpy(launches + 5 * k, row, sizeof(row));
+    }
+    if (fits && !plan.blob.empty()) memcpy(blob, plan.blob.data(), plan.blob.size());
+    for (size_t i = 0; i < plan.images.size(); i++) {
+        const jda_exact_image &M = plan.images[i];
+        int64_t *q = image + 10 * i;
+        memset(q, 0, 10 * sizeof(int64_t));
+        q[0] = M.kind;
+        if (M.kind < 0) continue;
+        q[1] = (int64_t)M.plane_at; q[2] = (int64_t)M.G.bytes; q[3] = (int64_t)(plan.o_scratch + M.plane_at + M.G.off[0]);
+        for (int k = 0; k < 4; k++) q[4 + k] = M.rect ? M.mcu[k] : (k == 2 ? M.info.mcus_x : k == 3 ? M.info.mcus_y : 0);
+        q[8] = jda_exact_tile_count(M.info, M.rect ? M.mcu : NULL); q[9] = jda_exact_tile_count(M.info, NULL);
+    }
+    free(block);
+    return fits ? rc : -1;
+}
+
 // source: 0 a dense coefficient image, 1 a sparse one, 2 a resident baseline image; coefs == NULL with source 0 / 1: jda_progressive_prepare's.
 // rects: n_rects x {x, y, w, h}; clips: n_rects x {width_px, rows} (NULL: the rectangle's own size); out: the rectangles' clipped pixels, dense,
 // one after the other (min(w, width_px) * bpp bytes a row, min(h, rows) rows); twin_out: the WHOLE image from the row-major twin, dense.
@@ -189,10 +264,9 @@ extern "C" int exactrectsim_run(const uint8_t *jpeg, int len, const int16_t *coe
     memset(qzz, 0, sizeof(qzz));
     std::vector<int16_t> twin_coefs;
     RectIO io;
-    jda_dev_desc D;
-    memset(&D, 0, sizeof(D));
+    jda_exact_source V;                                      // the source as the plan reads it (jda_exact_plan.h)
+    memset(&V, 0, sizeof(V));
     std::vector<void *> owned;
-    jda_ex_src *esrc = NULL;
     if (source == 2) {
         bimg = jda_prepare(jpeg, len, &err);
         if (!bimg) return err;
@@ -218,10 +292,8 @@ extern "C" int exactrectsim_run(const uint8_t *jpeg, int len, const int16_t *coe
     if (rc != JDA_SUCCESS) { if (bimg) jda_image_free(bimg); if (cimg) jda_coef_image_free(cimg); return rc; }
     const int bpp = gray ? 1 : 4;
     const uint32_t nb = (uint32_t)(I.mcus_x * I.mcus_y * I.blocks_per_mcu);
-    D.mode = (uint8_t)jda_mode_of(I); D.ncomp = (uint8_t)I.ncomp; D.mcus_x = (uint32_t)I.mcus_x; D.mcus_y = (uint32_t)I.mcus_y;
-    uint8_t *scratch = dup<uint8_t>(NULL, 0, G.bytes);
-    owned.push_back(scratch);
-    io.scratch = scratch; io.scratch_bytes = G.bytes;
+    V.kind = (jda_exact_kind)source; V.info = I; V.adobe = adobe; V.colour = I.ncomp == 1 ? JDA_CS_GRAY : JDA_CS_YCBCR; V.n_mcus_ok = n_ok_all;
+    memcpy(V.quant, qzz, sizeof(V.quant));
     if (source == 2) {
         uint32_t scan_len = 0, n_ok = 0, tb = 0;
         const uint8_t *scan = jda_image_scan(bimg, &scan_len);
@@ -230,15 +302,12 @@ extern "C" int exactrectsim_run(const uint8_t *jpeg, int len, const int16_t *coe
         uint8_t *d_scan = dup(scan, scan_len, JDA_SCAN_PAD), *d_tab = dup(tables, tb);
         uint32_t *d_ix = dup(index, (size_t)nb + 1);
         int16_t *d_dc = dup(jda_image_block_dc(bimg), nb, nb & 1u);
-        esrc = dup<jda_ex_src>(NULL, 0, 1);
-        owned.insert(owned.end(), { (void *)d_scan, (void *)d_tab, (void *)d_ix, (void *)d_dc, (void *)esrc });
+        owned.insert(owned.end(), { (void *)d_scan, (void *)d_tab, (void *)d_ix, (void *)d_dc });
         io.add(d_scan, scan_len + JDA_SCAN_PAD, false); io.add(d_tab, tb, false); io.add(d_ix, ((size_t)nb + 1) * 4, false);
-        io.add(d_dc, ((size_t)nb + (nb & 1u)) * 2, false); io.add(esrc, sizeof(jda_ex_src), false);
-        uint8_t dc_id[3], ac_id[3], q_id[3];
-        jda_image_component_ids(bimg, dc_id, ac_id, q_id);
-        esrc->S.scan = d_scan; esrc->S.blk_index = d_ix; esrc->S.blk_dc = d_dc; esrc->S.tables = d_tab; esrc->S.scan_len = scan_len; esrc->S.kind = JDA_RC_IMAGE;
-        for (int c = 0; c < 3; c++) esrc->S.ac_id[c] = ac_id[c];
-        esrc->bpm = (uint32_t)I.blocks_per_mcu; esrc->nluma = I.ncomp == 3 ? esrc->bpm - 2u : 1u;
+        io.add(d_dc, ((size_t)nb + (nb & 1u)) * 2, false);
+        uint8_t dc_id[3], q_id[3];
+        jda_image_component_ids(bimg, dc_id, V.ac_id, q_id);
+        V.scan = d_scan; V.index = d_ix; V.dc = d_dc; V.tables = d_tab; V.scan_len = scan_len;
     } else {
         uint32_t nbc = 0, ne = 0;
         const int16_t *cf = jda_coef_image_coefficients(cimg, &nbc);
@@ -249,7 +318,7 @@ extern "C" int exactrectsim_run(const uint8_t *jpeg, int len, const int16_t *coe
             owned.push_back(blk);
             memcpy(blk, quant, JDA_CT_QUANT_BYTES); memcpy(blk + JDA_CT_QUANT_BYTES, cf, (size_t)nbc * 128);
             io.add(blk, JDA_CT_QUANT_BYTES + (size_t)nbc * 128, false);
-            D.tables = blk; D.scan = blk + JDA_CT_QUANT_BYTES;
+            V.tables = blk; V.scan = blk + JDA_CT_QUANT_BYTES;
         } else {
             const uint32_t *first = NULL;
             const uint32_t *entries = jda_coef_image_sparse(cimg, &first, &ne);
@@ -261,36 +330,52 @@ extern "C" int exactrectsim_run(const uint8_t *jpeg, int len, const int16_t *coe
                 memcpy(blk, quant, JDA_CT_QUANT_BYTES); memcpy(blk + JDA_CT_QUANT_BYTES, first, ((size_t)nbc + 1) * 4);
                 if (ne) memcpy(blk + JDA_CT_QUANT_BYTES + fb, entries, (size_t)ne * 4);
                 io.add(blk, JDA_CT_QUANT_BYTES + fb + eb, false);
-                D.tables = blk; D.scan = blk + JDA_CT_QUANT_BYTES + fb;
+                V.tables = blk; V.scan = blk + JDA_CT_QUANT_BYTES + fb;
             }
         }
     }
-    jda_ex_desc *X = dup<jda_ex_desc>(NULL, 0, 1);
-    jda_exr_rec *R = dup<jda_exr_rec>(NULL, 0, 1);
-    owned.push_back(X); owned.push_back(R);
-    io.add(X, sizeof(jda_ex_desc), false);
+    // a rectangle = a call of one image, as the runtime makes it: the plan, a block for the blob and the scratch behind it, the records and
+    // the two tile lists read back out of the block
     size_t at = 0;
     for (int k = 0; k < n_rects && rc == JDA_SUCCESS; k++) {
         const int32_t *rq = rects + 4 * k;
-        int32_t mcu[4];
-        status[k] = jda_exact_rect_plan(I, G, luma_only, rq, mcu);
+        int32_t inside[4];                                             // (judged before a surface is made for it; all zero is an empty rectangle here)
+        status[k] = jda_exact_rect_plan(I, G, luma_only, rq, inside);
         if (status[k] != JDA_SUCCESS) continue;
         const int width_px = clips ? clips[2 * k] : rq[2], rows = clips ? clips[2 * k + 1] : rq[3];
         const int clip_w = width_px < rq[2] ? (width_px < 0 ? 0 : width_px) : rq[2], clip_h = rows < rq[3] ? (rows < 0 ? 0 : rows) : rq[3];
         const int pitch = (rq[2] * bpp + 15) & ~15;
         uint8_t *surf = dup<uint8_t>(NULL, 0, (size_t)pitch * rq[3]);
+        jda_output O;
+        O.pixels = surf; O.pitch_bytes = pitch; O.width_px = width_px; O.rows = rows;
+        jda_exact_plan plan;
+        const int prc = jda_exact_plan_build(1, &V, &O, &pixel_type, NULL, &scale, 0u, rq, &status[k], &plan);
+        if (prc != JDA_SUCCESS) status[k] = prc;
+        // the planes launch of the source's kind and, unless the clip is empty, the rectangle's colour launch
+        const size_t nl = plan.launches.size();
+        if (status[k] != JDA_SUCCESS || nl < 1u || nl > 2u || plan.launches[0].kind != V.kind || (nl == 2u && plan.launches[1].kind != JDA_EXK_COLOUR_RECT) ||
+            (nl == 2u) != (clip_w > 0 && clip_h > 0)) {
+            if (status[k] == JDA_SUCCESS) status[k] = -30;
+            free(surf);
+            continue;
+        }
+        uint8_t *block = dup<uint8_t>(NULL, 0, plan.o_scratch + plan.scratch);
+        jda_exact_plan_place(&plan, block);
+        memcpy(block, plan.blob.data(), plan.blob.size());
         memset(surf, 0x5A, (size_t)pitch * rq[3]);
-        memset(scratch, 0xA5, G.bytes);
-        io.written.assign(G.bytes, 0);
+        memset(block + plan.o_scratch, 0xA5, plan.scratch);
+        io.scratch = block + plan.o_scratch; io.scratch_bytes = plan.scratch;
+        io.written.assign(plan.scratch, 0);
         io.surface = surf; io.surface_bytes = (size_t)pitch * (size_t)clip_h;
         io.hits.assign(io.surface_bytes, 0);
         io.err = 0;
-        jda_output O;
-        O.pixels = surf; O.pitch_bytes = pitch; O.width_px = width_px; O.rows = rows;
-        jda_exact_fill_rect(*X, *R, I, qzz, G, scratch, &O, pixel_type, luma_only, rq);
-        std::vector<jda_strip> tiles, ctiles;
-        jda_append_strips(tiles, 0, D.mcus_x, D.mcus_y, D.mode, 0, mcu);
-        jda_exact_rect_tiles(ctiles, 0, X->out_w, X->out_rows);
+        io.add(block, plan.blob.size(), false);
+        const jda_dev_desc D = *(const jda_dev_desc *)block;
+        const jda_ex_desc *X = (const jda_ex_desc *)(block + plan.o_ex);
+        const jda_exr_rec *R = (const jda_exr_rec *)(block + plan.o_rect);
+        const jda_ex_src *esrc = (const jda_ex_src *)(block + plan.o_src);
+        const jda_strip *t0 = (const jda_strip *)(block + plan.launches[0].off), *t1 = (const jda_strip *)(block + plan.launches[nl - 1u].off);
+        const std::vector<jda_strip> tiles(t0, t0 + plan.launches[0].n_tiles), ctiles(t1, t1 + (nl == 2u ? plan.launches[1].n_tiles : 0u));
         for (const jda_strip &s : ctiles) info[1] += s.count ? 1 : 0;
         switch (D.mode) {
         case JDA_MODE_GRAY: run_rect<JDA_MODE_GRAY>(scale, source, D, X, R, esrc, tiles, ctiles, io, info); break;
@@ -299,6 +384,7 @@ extern "C" int exactrectsim_run(const uint8_t *jpeg, int len, const int16_t *coe
         case JDA_MODE_422: run_rect<JDA_MODE_422>(scale, source, D, X, R, esrc, tiles, ctiles, io, info); break;
         default: run_rect<JDA_MODE_440>(scale, source, D, X, R, esrc, tiles, ctiles, io, info); break;
         }
+        io.regions.pop_back();
         int st = io.err;
         for (size_t b = 0; b < io.hits.size() && st == 0; b++) {
             const size_t x = b % (size_t)pitch;
@@ -311,8 +397,9 @@ extern "C" int exactrectsim_run(const uint8_t *jpeg, int len, const int16_t *coe
         status[k] = st;
         for (int y = 0; y < clip_h; y++) { memcpy(out + at, surf + (size_t)y * pitch, (size_t)clip_w * bpp); at += (size_t)clip_w * bpp; }
         free(surf);
+        free(block);
     }
-    io.surface = NULL; io.surface_bytes = 0;
+    io.surface = NULL; io.surface_bytes = 0; io.scratch = NULL; io.scratch_bytes = 0;
     if (rc == JDA_SUCCESS && twin_out && source != 2) {
         uint16_t qn[3][64];
         for (int c = 0; c < 3; c++) for (uint32_t z = 0; z < 64; z++) qn[c][jda_en_zigzag(z)] = qzz[c][z];

@@ -7,7 +7,9 @@ independent read set, and the kernels' lanes against the definition.
 (c) the existing planes lanes over the rectangle's tile list into a poisoned scratch, then the new colour lanes (tests/hostsim/
     exact_rect_sim.cpp): every load inside its allocation and of a plane byte this rectangle's planes stage stored, every byte of the clip
     stored exactly once and none outside = the reference = the C row-major twin's crop, for dense, sparse and baseline sources;
-(d) a rectangle equal to the image = the whole decode; (e) clipped surfaces; (f) the same as a program under ASan + UBSan."""
+(d) a rectangle equal to the image = the whole decode; (e) clipped surfaces; (f) the same as a program under ASan + UBSan;
+(g) the plan of a whole call (jda_exact_plan_build / _place) over a mixed batch of header numbers: the launch list in its order, the
+    shared planes lists of a call without flags and rectangles, coverage, the blob's layout, calls with nothing to launch."""
 import ctypes as C
 import os
 import subprocess
@@ -246,6 +248,181 @@ def test_clipped_surfaces(sim, sampling):
             got, info, _ = run(sim, f, 2, pt, s, [rect] * len(clips), clips=clips)
             for clip, g in zip(clips, got):
                 assert np.array_equal(g, Q.crop(f, s, rect, pt == GRAY8, clip)), (s, clip, pt)
+
+
+# ---- the plan of a whole call (jda_exact_plan_build / _place of jda_exact_plan.h), from header numbers alone
+MODES = ("gray", "4:4:4", "4:2:0", "4:2:2", "4:4:0")                   # JDA_MODE_*
+MCU_PX = {"gray": (8, 8), "4:4:4": (8, 8), "4:2:0": (16, 16), "4:2:2": (16, 8), "4:4:0": (8, 16)}
+DENSE, SPARSE, BASELINE, COLOUR, COLOUR_RGB, COLOUR4, COLOUR_RECT, COLOUR_RECT_RGB = range(8)      # jda_exact_kind
+CS_GRAY, CS_YCBCR, CS_RGB, CS_CMYK = 0, 1, 2, 3                         # JDA_CS_*
+COLOUR_MODELS = 1                                                       # JDA_EXACT_COLOUR_MODELS
+STRIP = np.dtype([("image", "<u4"), ("mcu_y", "<u2"), ("mcu_x0", "<u2"), ("count", "u1"), ("first", "u1"), ("pad", "<u2"), ("ord", "<u4")])
+DESC_BYTES, EX_BYTES, SRC_BYTES, RECT_BYTES = 104, 480, 72, 16
+
+
+def plan_image(sampling, source, scale=1, colour=None, ncomp=None, pt=RGB8888, rect=(0, 0, 0, 0)):
+    """an image one MCU wider than a tile and two MCU rows high, no multiple of the MCU either way (a full and a partial tile a row)"""
+    mw, mh = MCU_PX[sampling]
+    w, h = (Q.PER_TILE[sampling] + 1) * mw - 3, 2 * mh - 5
+    sub, nc = Q.SUB[sampling]
+    nc = ncomp or nc
+    colour = colour if colour is not None else (CS_GRAY if nc == 1 else CS_YCBCR)
+    sw, sh = (-(-w // scale), -(-h // scale)) if scale in SCALES else (w, h)
+    if any(rect):
+        sw, sh = rect[2], rect[3]
+    return dict(sampling=sampling, source=source, scale=scale, colour=colour, ncomp=nc, w=w, h=h, rect=rect,
+                hdr=[w, h, nc, sub, source, colour, pt, scale, *rect, sw, sh])
+
+
+def mixed_batch():
+    return [plan_image("gray", DENSE), plan_image("4:4:4", SPARSE, 2), plan_image("4:2:0", BASELINE), plan_image("4:2:2", DENSE, 8),
+            plan_image("4:2:0", BASELINE, 3),                           # refused: no such scale
+            plan_image("4:4:0", BASELINE), plan_image("4:2:0", DENSE, rect=(21, 3, 97, 20)), plan_image("4:4:4", SPARSE, 2, colour=CS_RGB),
+            plan_image("4:4:4", DENSE, colour=CS_CMYK, ncomp=4), plan_image("4:2:0", SPARSE)]
+
+
+def call_plan(sim, images, flags, with_rects):
+    n = len(images)
+    sim.exactrectsim_call_plan.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_int] + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    sim.exactrectsim_tiles_per_wg.argtypes = [C.c_int]
+    hdr = np.array([im["hdr"] for im in images], np.int32).reshape(n, 14)
+    status = np.full(max(n, 1), 99, np.int32)
+    launches, n_launches = np.zeros((160, 5), np.int64), C.c_int32(-1)
+    blob, layout, image = np.zeros(1 << 20, np.uint8), np.zeros(10, np.int64), np.zeros((max(n, 1), 10), np.int64)
+    rc = sim.exactrectsim_call_plan(n, hdr.ctypes.data, flags, with_rects, status.ctypes.data, launches.ctypes.data, 160, C.byref(n_launches), blob.ctypes.data, blob.size,
+                                    layout.ctypes.data, image.ctypes.data)
+    keys = ("blob", "o_ex", "o_src", "o_rect", "o_scratch", "scratch", "colour_begin", "n_rec", "n_planned", "block")
+    lay = dict(zip(keys, (int(v) for v in layout)))
+    L = [tuple(int(v) for v in row) for row in launches[:n_launches.value]]
+    return rc, list(status[:n]), L, blob[:lay["blob"]], lay, image[:n]
+
+
+def tiles_of(blob, launch):
+    kind, mode, scale, off, count = launch
+    return blob[off:off + 16 * count].view(STRIP)
+
+
+def padded(sim, im, mcus=None):
+    """records an image adds to a planes / colour list of its layout: a tile a run of PER_TILE MCUs a row, padded to whole workgroups"""
+    per, wg = Q.PER_TILE[im["sampling"]], sim.exactrectsim_tiles_per_wg(MODES.index(im["sampling"]))
+    mw, mh = MCU_PX[im["sampling"]]
+    x0, y0, x1, y1 = mcus or (0, 0, -(-im["w"] // mw), -(-im["h"] // mh))
+    t = (y1 - y0) * -(-(x1 - x0) // per)
+    return -(-t // wg) * wg, t
+
+
+def test_call_plan_of_a_mixed_batch(sim):
+    B = mixed_batch()
+    n = len(B)
+    rc, status, L, blob, lay, image = call_plan(sim, B, COLOUR_MODELS, 1)
+    assert rc == 0 and status == [0, 0, 0, 0, 1, 0, 0, 0, 0, 0] and lay["n_planned"] == 9 and lay["n_rec"] == 2 * n
+    assert 15 <= sim.exactrectsim_tiles_per_wg(2) <= 16 and sim.exactrectsim_tiles_per_wg(0) == 15
+    P = lambda i, mcus=None: padded(sim, B[i], mcus)[0]
+    mcu6 = tuple(int(v) for v in image[6][4:8])
+    assert mcu6 == plan(sim, B[6]["w"], B[6]["h"], "4:2:0", RGB8888, 1, B[6]["rect"])[1] == Q.mcu_rect(B[6]["w"], B[6]["h"], "4:2:0", 1, B[6]["rect"])
+    k_gray = dict(B[8], sampling="gray")                               # component 3 of the four-component image: a gray image over its blocks
+    rect_tiles = -(-(-(-20 // 32) * -(-(-(-97 // 4)) // 64)) // 4) * 4     # 64 quads x 32 rows a record, padded to the 4 of a workgroup
+    # all planes launches by (layout, scale, source); then colour: own lists by (layout, scale, YCbCr | RGB), four-component by layout, rectangles
+    want = [(DENSE, 0, 1, P(0) + padded(sim, k_gray)[0]), (DENSE, 1, 1, P(8)), (SPARSE, 1, 2, P(1) + P(7)),
+            (DENSE, 2, 1, P(6, mcu6)), (SPARSE, 2, 1, P(9)), (BASELINE, 2, 1, P(2)), (DENSE, 3, 8, P(3)), (BASELINE, 4, 1, P(5)),
+            (COLOUR, 0, 1, P(0)), (COLOUR, 1, 2, P(1)), (COLOUR_RGB, 1, 2, P(7)), (COLOUR, 2, 1, P(2) + P(9)), (COLOUR, 3, 8, P(3)), (COLOUR, 4, 1, P(5)),
+            (COLOUR4, 1, 1, P(8)), (COLOUR_RECT, 2, 1, rect_tiles)]
+    assert [(k, m, s, c) for k, m, s, off, c in L] == want
+    assert lay["colour_begin"] == 8
+    assert any(c % 4 for k, m, s, off, c in L)                          # (list lengths that are no multiple of a workgroup's 4 wavefronts)
+    # coverage: every MCU of every planned image (a rectangle image: of its MCU rectangle) in the planes lists exactly once
+    seen = {}
+    for launch in L[:lay["colour_begin"]]:
+        for t in tiles_of(blob, launch):
+            for x in range(int(t["mcu_x0"]), int(t["mcu_x0"]) + int(t["count"])):
+                key = (int(t["image"]), x, int(t["mcu_y"]))
+                assert key not in seen, key
+                seen[key] = launch[:3]
+    want_mcus = set()
+    for i, im in enumerate(B):
+        if status[i]:
+            continue
+        mw, mh = MCU_PX[im["sampling"]]
+        x0, y0, x1, y1 = mcu6 if i == 6 else (0, 0, -(-im["w"] // mw), -(-im["h"] // mh))
+        want_mcus |= {(i, x, y) for x in range(x0, x1) for y in range(y0, y1)}
+        assert all(seen[(i, x, y)] == (im["source"], MODES.index(im["sampling"]), im["scale"]) for x in range(x0, x1) for y in range(y0, y1))
+    k_mcus = {(n + 8, x, y) for x in range(-(-B[8]["w"] // 8)) for y in range(-(-B[8]["h"] // 8))}      # record n + i, in the gray dense list
+    assert set(seen) == want_mcus | k_mcus and all(seen[k] == (DENSE, 0, 1) for k in k_mcus)
+    # jda_exact_tile_count (what the one call reports) = the records of the image that hold MCUs, of its MCU rectangle and whole
+    held = {}
+    for launch in L[:lay["colour_begin"]]:
+        for t in tiles_of(blob, launch):
+            held[int(t["image"])] = held.get(int(t["image"]), 0) + (int(t["count"]) != 0)
+    for i, im in enumerate(B):
+        if not status[i]:
+            assert (int(image[i][8]), int(image[i][9])) == (held[i], padded(sim, im)[1]) and (held[i] == padded(sim, im)[1]) == (i != 6)
+    # .. and every planned image's output in exactly one colour-stage list: a whole image's MCUs there exactly once, tile by tile
+    owner, cseen = {}, set()
+    for launch in L[lay["colour_begin"]:-1]:
+        for t in tiles_of(blob, launch):
+            if t["count"]:
+                assert owner.setdefault(int(t["image"]), launch[:3]) == launch[:3]
+            for x in range(int(t["mcu_x0"]), int(t["mcu_x0"]) + int(t["count"])):
+                key = (int(t["image"]), x, int(t["mcu_y"]))
+                assert key not in cseen, key
+                cseen.add(key)
+    assert cseen == {k for k in want_mcus if k[0] != 6}                 # (K's gray tiles and the rectangle's MCUs are in no whole-image colour list)
+    assert owner == {i: ((COLOUR4 if i == 8 else COLOUR_RGB if i == 7 else COLOUR), MODES.index(B[i]["sampling"]), B[i]["scale"]) for i in (0, 1, 2, 3, 5, 7, 8, 9)}
+    rt = [t for t in tiles_of(blob, L[-1]) if t["count"]]
+    assert sorted((int(t["mcu_x0"]), int(t["mcu_y"])) for t in rt) == [(0, 0)] and all(int(t["image"]) == 6 for t in rt)
+    # the rectangle's record, and the refused image's records left zero
+    assert list(blob[lay["o_rect"] + 6 * RECT_BYTES:][:RECT_BYTES].view("<u4")) == [21, 3, 97, 20]
+    assert not blob[4 * DESC_BYTES:5 * DESC_BYTES].any() and not blob[lay["o_ex"] + 4 * EX_BYTES:lay["o_ex"] + 5 * EX_BYTES].any()
+    check_layout(L, blob, lay, image, n, True, False)
+
+
+def check_layout(L, blob, lay, image, n, with_rects, shared):
+    """16-aligned parts one behind the other inside the blob, the scratch at a multiple of 256 behind it, the planes disjoint and all of it"""
+    nrec = lay["n_rec"]
+    assert lay["o_ex"] % 16 == 0 and lay["o_src"] % 16 == 0 and lay["o_ex"] >= nrec * DESC_BYTES and lay["o_src"] >= lay["o_ex"] + nrec * EX_BYTES
+    spans = sorted((off, off + 16 * c) for k, m, s, off, c in L if k <= BASELINE or not shared)      # (shared: the colour launches walk the planes lists)
+    assert spans[0][0] >= lay["o_src"] + nrec * SRC_BYTES and spans[0][0] % 16 == 0
+    for (a0, a1), (b0, b1) in zip(spans, spans[1:]):
+        assert a1 <= b0 and b0 % 16 == 0
+    assert spans[-1][1] <= lay["o_rect"] and lay["o_rect"] + (n * RECT_BYTES if with_rects else 0) == lay["blob"] == blob.size
+    assert lay["o_scratch"] % 256 == 0 and lay["blob"] <= lay["o_scratch"] < lay["blob"] + 256 and lay["block"] % 16 == 0
+    at = 0
+    for q in image:
+        if q[0] < 0:
+            continue
+        assert q[1] == at and q[2] > 0 and q[2] % 256 == 0               # the planes one behind the other, each a multiple of 256
+        at += int(q[2])
+    assert at == lay["scratch"]
+    for i, q in enumerate(image):                                       # the record's Y plane: where the plan says, inside the block
+        if q[0] >= 0:
+            assert int(blob[lay["o_ex"] + i * EX_BYTES:][:8].view("<u8")[0]) == lay["block"] + int(q[3]) and q[3] == lay["o_scratch"] + q[1]
+
+
+def test_call_plan_shares_the_planes_lists_without_flags_and_rectangles(sim):
+    B = [im for i, im in enumerate(mixed_batch()) if i not in (6, 7, 8)]
+    n = len(B)
+    rc, status, L, blob, lay, image = call_plan(sim, B, 0, 0)
+    assert rc == 0 and status == [0, 0, 0, 0, 1, 0, 0] and lay["n_rec"] == n
+    P = lambda i: padded(sim, B[i])[0]
+    want = [(DENSE, 0, 1, P(0)), (SPARSE, 1, 2, P(1)), (SPARSE, 2, 1, P(6)), (BASELINE, 2, 1, P(2)), (DENSE, 3, 8, P(3)), (BASELINE, 4, 1, P(5)),
+            (COLOUR, 0, 1, P(0)), (COLOUR, 1, 2, P(1)), (COLOUR, 2, 1, P(6) + P(2)), (COLOUR, 3, 8, P(3)), (COLOUR, 4, 1, P(5))]
+    assert [(k, m, s, c) for k, m, s, off, c in L] == want and lay["colour_begin"] == 6
+    planes = L[:6]
+    for k, m, s, off, c in L[6:]:                                       # one colour launch a (layout, scale): from its dense list, over all three
+        group = [p for p in planes if p[1:3] == (m, s)]
+        assert off == min(p[3] for p in group) and c == sum(p[4] for p in group)
+        assert [p[3] for p in group] == [off + 16 * sum(q[4] for q in group[:j]) for j in range(len(group))]      # (dense | sparse | baseline, back to back)
+    assert max(off + 16 * c for k, m, s, off, c in planes) == lay["o_rect"] == lay["blob"]      # no list of the colour stage's own, no rectangle records
+    check_layout(L, blob, lay, image, n, False, True)
+
+
+def test_call_plan_with_nothing_to_launch(sim):
+    rc, status, L, blob, lay, image = call_plan(sim, [], COLOUR_MODELS, 1)
+    assert rc == 0 and L == [] and lay["blob"] == 0 and lay["n_planned"] == 0
+    # every image refused: a scale that is none, a pixel type the road lacks, an RGB-coded file to a gray surface
+    B = [plan_image("4:2:0", BASELINE, 3), plan_image("gray", DENSE, pt=0), plan_image("4:4:4", SPARSE, 2, colour=CS_RGB, pt=GRAY8)]
+    rc, status, L, blob, lay, image = call_plan(sim, B, COLOUR_MODELS, 0)
+    assert rc == 0 and status == [1, 1, 3] and L == [] and lay["n_planned"] == 0 and lay["scratch"] == 0 and lay["blob"] == 0
 
 
 def test_sanitizer_program(tmp_path):

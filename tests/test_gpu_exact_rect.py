@@ -5,7 +5,8 @@ tests/test_exact_rect_cpu.py holds to Pillow's crop:
     device-index, dense and sparse sources interleaved -- into guard-filled back-to-back surfaces: pixels = reference, the guard intact
     everywhere else, the launches counted per kernel instance (the planes launches present and ONE jda_exact_colour_rect), twice; RGB8888
     and gray; (b) whole images and rectangles mixed in one call; (c) RGB-coded files; (d) clipped surfaces; (e) the one call;
-(f) refusals, and calls that launch nothing; (g) decode_to_tensors with crops= against Pillow's resize(box=)."""
+(f) refusals, and calls that launch nothing; (g) decode_to_tensors with crops= against Pillow's resize(box=); (h) a mixed batch -- every
+    layout, source kind, colour model, three scales, a rectangle and a refused image -- in one call, each surface against its reference."""
 import os
 import subprocess
 import sys
@@ -291,6 +292,65 @@ def test_refusals_and_calls_that_launch_nothing(gpu_ctx):
         dev4.close()
         host4.close()
         S1.close()
+
+
+def test_mixed_batch_in_one_call(gpu_ctx):
+    """the batch whose plan tests/test_exact_rect_cpu.py takes apart, as real files in ONE jda_exact_decode_surfaces_rect call with
+    JDA_EXACT_COLOUR_MODELS: every layout, dense, sparse and baseline sources, scales 1, 2 and 8, a rectangle, an RGB-coded and a
+    four-component file, and in the middle an image that is refused -- every surface its reference, the refused one's untouched"""
+    mcu = {"gray": (8, 8), "4:4:4": (8, 8), "4:2:0": (16, 16), "4:2:2": (16, 8), "4:4:0": (8, 16)}
+    size = lambda sampling: ((Q.PER_TILE[sampling] + 1) * mcu[sampling][0] - 3, 2 * mcu[sampling][1] - 5)      # a full and a partial tile a row, two MCU rows
+    ycc = {sampling: X.written_file(*size(sampling), sampling, 90) for sampling in coef_jpeg.LAYOUTS}
+    rgb3, cmyk = A.pillow_rgb3(*size("4:4:4"), "4:4:4", 90, "ids"), A.pillow_cmyk(*size("4:4:4"), "4:4:4", 90)
+    assert A.model(rgb3) == A.RGB and A.model(cmyk) == A.CMYK
+    rect = (21, 3, 97, 20)
+    # (file, resident form, scale, rectangle or None, the reference's surface)
+    batch = [(ycc["gray"], "dense", 1, None, X.rgba(X.twin(ycc["gray"]))),
+             (ycc["4:4:4"], "sparse", 2, None, S.rgba(S.twin_scaled(ycc["4:4:4"], 2))),
+             (ycc["4:2:0"], "host", 1, None, X.rgba(X.twin(ycc["4:2:0"]))),
+             (ycc["4:2:2"], "dense", 8, None, S.rgba(S.twin_scaled(ycc["4:2:2"], 8))),
+             (ycc["4:2:0"], "host", 3, None, None),                     # refused: no such scale
+             (ycc["4:4:0"], "host", 1, None, X.rgba(X.twin(ycc["4:4:0"]))),
+             (ycc["4:2:0"], "dense", 1, rect, Q.crop(ycc["4:2:0"], 1, rect)),
+             (rgb3, "sparse", 2, None, A.surface(A.twin3(rgb3, 2))),
+             (cmyk, "dense", 1, None, A.surface(A.twin4(cmyk))),
+             (ycc["4:2:0"], "sparse", 1, None, X.rgba(X.twin(ycc["4:2:0"])))]
+    for f, s in ((ycc["gray"], 1), (ycc["4:4:4"], 2), (ycc["4:2:0"], 1), (ycc["4:2:2"], 8), (ycc["4:4:0"], 1)):
+        assert X.in_window(X.twin(f) if s == 1 else S.twin_scaled(f, s))
+    assert A.in_window(A.twin3(rgb3, 2)) and A.in_window(A.twin4(cmyk))
+    keep, items = [], []
+    try:
+        for f, form, s, r, want in batch:
+            if form == "host":
+                p = J.PreparedImage(f)
+                d = J.DeviceImage(gpu_ctx, p)
+            else:
+                p = J.CoefImage.from_file(f) if f is cmyk else J.CoefImage(f, X.natural_blocks(f))
+                d = J.DeviceCoef(gpu_ctx, p, J.COEF_SPARSE if form == "sparse" else J.COEF_DENSE)
+                assert d.form == (J.COEF_SPARSE if form == "sparse" else J.COEF_DENSE)
+            keep.append(p)
+            items.append(d)
+        n = len(batch)
+        sizes = dict([(ycc[sampling], size(sampling)) for sampling in coef_jpeg.LAYOUTS] + [(rgb3, size("4:4:4")), (cmyk, size("4:4:4"))])
+        shapes = [S.scaled_size(*sizes[f], s) if s in S.SCALES else sizes[f] for f, form, s, r, want in batch]
+        rects = [r for f, form, s, r, want in batch]
+        before = counts()
+        status, surfaces, rest = decode_into_guard(gpu_ctx, items, rects, [J.RGB8888] * n, [s for f, form, s, r, want in batch], colour_models=True, shapes=shapes)
+        d = delta(before)
+        assert status == [SUCCESS] * 4 + [INVALID_PARAMETER] + [SUCCESS] * 5
+        assert np.all(rest == FILL) and np.all(surfaces[4] == FILL)
+        for k, (f, form, s, r, want) in enumerate(batch):
+            if want is not None:
+                check_surface(surfaces[k], want, (k, form, s, r))
+        # one launch a list of the plan: the planes by (layout, scale, source), the colour stage's own lists, the four-component and the rectangle list
+        assert d == {("planes", 0, 0, 1): 1, ("planes", 1, 0, 1): 1, ("planes", 1, 1, 2): 1, ("planes", 2, 0, 1): 1, ("planes", 2, 1, 1): 1, ("planes", 2, 2, 1): 1,
+                     ("planes", 3, 0, 8): 1, ("planes", 4, 2, 1): 1, ("colour", 0): 1, ("colour_scaled", 1): 1, ("colour_scaled_rgb", 1): 1, ("colour", 2): 1,
+                     ("colour_scaled", 3): 1, ("colour", 4): 1, ("colour4", 1): 1, ("colour_rect", 2, 0): 1}
+    finally:
+        for d_ in items:
+            d_.close()
+        for p in keep:
+            p.close()
 
 
 def test_decode_to_tensors_crops_are_pillows_resize_box(gpu_ctx):
