@@ -3,6 +3,8 @@
 #   oracle/liboracle.so             the checker (CPU restatement)            -- test infrastructure
 #   oracle/_ref/*.so                the real reference, if /root/reference is present -- test infrastructure
 #   tests/hostsim/libjda_hostsim.so wave emulator for CPU-only unit tests    -- test infrastructure
+# and on request: `make devprims` (tests/devprims/libjda_devprims.so: both sides of every device-only helper branch, hipcc) and
+# `make devprimsasan` (tests/devprims/devprims_asan: their host sides as a program under ASan + UBSan) -- test infrastructure
 HIPCC ?= /opt/rocm/bin/hipcc
 CXX   ?= g++
 ARCH  ?= gfx950
@@ -179,6 +181,18 @@ recodexfasan: tests/hostsim/recode_xf_asan
 tests/hostsim/recode_xf_asan: tests/hostsim/recode_xf_main.cpp $(RECODEXFSIM_DEPS)
 	$(CXX) -O1 -g -std=c++17 -fwrapv -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/hostsim/recode_xf_main.cpp $(RECODEXFSIM_SRCS)
 
+# both sides of every `#if defined(__HIP_DEVICE_COMPILE__)` fork of jda_device_core.h behind one C interface: the helpers' host sides in a loop,
+# their device sides in a plain kernel, built with the product's HIPFLAGS flag for flag (tests/test_devprims_cpu.py, tests/test_gpu_devprims.py)
+# -- test infrastructure
+DEVPRIMS_DEPS = tests/devprims/devprims_ops.h $(CSRC)/jda_device_core.h $(CSRC)/jda_internal.h include/jpegdec_amd.h
+devprims: tests/devprims/libjda_devprims.so
+tests/devprims/libjda_devprims.so: tests/devprims/devprims.hip $(DEVPRIMS_DEPS)
+	$(HIPCC) $(HIPFLAGS) -o $@ tests/devprims/devprims.hip
+# .. and the host sides with a main of their own under AddressSanitizer + UBSan: a program, nothing loaded into an interpreter
+devprimsasan: tests/devprims/devprims_asan
+tests/devprims/devprims_asan: tests/devprims/devprims_main.cpp $(DEVPRIMS_DEPS)
+	$(CXX) -O1 -g -std=c++17 -fwrapv -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-attributes -Iinclude -pthread -o $@ tests/devprims/devprims_main.cpp
+
 # the reference-API driver (oracle/ref_shim.cpp) built against the product's JPEGDEC class -- test infrastructure
 classshim: tests/libjpegdec_class_shim.so
 tests/libjpegdec_class_shim.so: oracle/ref_shim.cpp include/JPEGDEC.h $(LIB)
@@ -241,10 +255,10 @@ tests/fuzz/frontend_tsan: tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp 
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -Wall -Iinclude -pthread -o $@ tests/fuzz/frontend_fuzz.cpp $(CSRC)/jda_frontend.cpp
 
 clean:
-	rm -f tests/hostsim/libjda_reducesim.so tests/hostsim/thumb_asan tests/hostsim/libjda_exactrectsim.so tests/hostsim/exact_rect_asan tests/hostsim/libjda_exactadobesim.so tests/hostsim/exact_adobe_asan tests/hostsim/libjda_exactscaledsim.so tests/hostsim/exact_scaled_asan tests/hostsim/libjda_exactsim.so tests/hostsim/exact_asan tests/hostsim/libjda_unpacksim.so tests/hostsim/unpack_asan tests/hostsim/libjda_recodexfsim.so tests/hostsim/recode_xf_asan tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
+	rm -f tests/devprims/libjda_devprims.so tests/devprims/devprims_asan tests/hostsim/libjda_reducesim.so tests/hostsim/thumb_asan tests/hostsim/libjda_exactrectsim.so tests/hostsim/exact_rect_asan tests/hostsim/libjda_exactadobesim.so tests/hostsim/exact_adobe_asan tests/hostsim/libjda_exactscaledsim.so tests/hostsim/exact_scaled_asan tests/hostsim/libjda_exactsim.so tests/hostsim/exact_asan tests/hostsim/libjda_unpacksim.so tests/hostsim/unpack_asan tests/hostsim/libjda_recodexfsim.so tests/hostsim/recode_xf_asan tests/hostsim/libjda_recodesim.so tests/hostsim/recode_asan tests/hostsim/libjda_encodeprogsim.so tests/hostsim/encode_prog_asan tests/fuzz/frontend_tsan $(LIB) tests/class_cpu/*.so tests/class_cpu/*.o tests/class_cpu/walks_asan tests/fuzz/frontend_fuzz tests/fuzz/chunk_equiv tests/ref_main/jpegtest_amd tests/hostsim/libjda_hostsim.so tests/hostsim/libjda_dithersim.so tests/hostsim/libjda_orientsim.so tests/hostsim/libjda_coefsim.so tests/hostsim/libjda_packsim.so tests/hostsim/libjda_resizesim.so tests/hostsim/libjda_coefsparsesim.so tests/hostsim/sparse_pack_asan tests/hostsim/libjda_encodesim.so tests/hostsim/encode_asan tests/hostsim/libjda_huffoptsim.so tests/hostsim/huffopt_asan tests/hostsim/libjda_resizefilterssim.so tests/hostsim/resize_filters_asan tests/capi_c/c_user tests/capi_c/node_user tests/capi_c/semantics_user tests/capi_c/perf_user tests/capi_c/prog_user
 	$(MAKE) -C oracle clean
 
-.PHONY: thumbasan exactrectasan exactadobeasan exactscaledasan exactasan all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan recodexfasan resizefiltersasan unpackasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
+.PHONY: devprims devprimsasan thumbasan exactrectasan exactadobeasan exactscaledasan exactasan all lib oracle hostsim classshim classcpu sparsepack encodeasan huffoptasan encodeprogasan recodeasan recodexfasan resizefiltersasan unpackasan cuser nodeuser semuser perfuser proguser fronttsan chunkequiv jpegtest frontfuzz nodestub clean
 
 # jda_node.cpp (host code above the C-ABI) over eight pretend devices -- test infrastructure, no GPU (tests/test_c_api.py)
 nodestub: tests/node_stub/node_stub_user

@@ -161,9 +161,15 @@ JDA_HD uint32_t jda_alignbyte(uint32_t hi, uint32_t lo, uint32_t byte_shift)
 #define JDA_STORE_ORDER() ((void)0)
 #endif
 
+// The host side of a fork computes what the device side's instruction gives for EVERY input (tests/devprims holds the two sides
+// together); a domain the callers keep to stands in a comment, not in a looser formula.
+// bits 23:0 of a word, sign-extended: the operand of the 24-bit multiplier (v_mul_i32_i24, v_mad_i32_i24)
+JDA_HD int32_t jda_sext24(int32_t v) { return (int32_t)((uint32_t)v << 8) >> 8; }
+
 // ---- packed 16-bit helpers (two pixels per VALU instruction in the colour stage) ---------------
 // v_perm_b32: result byte i = byte (sel >> 8i & 0xff) of the 8-byte pool {hi = bytes 4-7, lo = bytes 0-3};
-// selector 0x0c gives 0x00 and 0x0d gives 0xff.
+// selectors 8, 9, 10, 11 give the replicated bit 15 of lo, 31 of lo, 15 of hi, 31 of hi, selector 0x0c gives 0x00 and
+// 0x0d and above give 0xff.  (The callers use 0..7, 0x0c and 0x0d.)
 JDA_HD uint32_t jda_perm(uint32_t hi, uint32_t lo, uint32_t sel)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -173,7 +179,8 @@ JDA_HD uint32_t jda_perm(uint32_t hi, uint32_t lo, uint32_t sel)
     uint32_t r = 0;
     for (int i = 0; i < 4; i++) {
         const uint32_t k = (sel >> (8 * i)) & 0xffu;
-        const uint32_t b = k < 8 ? (uint32_t)(pool >> (8 * k)) & 0xffu : (k == 0x0c ? 0u : 0xffu);
+        const uint32_t b = k < 8 ? (uint32_t)(pool >> (8 * k)) & 0xffu
+                         : k < 12 ? (((pool >> (16 * (k - 8) + 15)) & 1u) ? 0xffu : 0u) : (k == 0x0c ? 0u : 0xffu);
         r |= b << (8 * i);
     }
     return r;
@@ -251,13 +258,14 @@ JDA_HD void jda_lds_bytes_apart(const uint8_t *p, uint32_t step, uint32_t delta,
     b0 = p[step]; b1 = p[step + delta];
 #endif
 }
-// a * b + c on operands that fit in 24 signed bits (v_mad_i32_i24, full rate)
+// a * b + c on operands that fit in 24 signed bits (v_mad_i32_i24, full rate: bits 23:0 of a and of b, sign-extended; the
+// low 32 bits of their product, + c)
 JDA_HD int32_t jda_mad24(int32_t a, int32_t b, int32_t c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __mul24(a, b) + c;
 #else
-    return (int32_t)((uint32_t)a * (uint32_t)b + (uint32_t)c);
+    return (int32_t)((uint32_t)jda_sext24(a) * (uint32_t)jda_sext24(b) + (uint32_t)c);
 #endif
 }
 // per 16-bit lane: the sign-extended 10-bit field at bits 14:5  (v_pk_lshlrev_b16 1, v_pk_ashrrev_i16 6)
@@ -569,16 +577,11 @@ JDA_HD uint32_t jda_decode_block(jda_bitreader &br, const jda_tables &T, int16_t
 // decode below is written without divergent branches: P1 is bound by the latency of its dependent
 // chain (stream bits -> LUT -> bit offset -> stream bits), not by instruction issue, and every
 // exec-mask region in that chain costs a VALU->SALU->branch round trip.
-// x >> n for n in 0..32 (hardware shifts take n mod 32; a result for n == 32 is never used)
-JDA_HD uint32_t jda_shr_upto32(uint32_t x, uint32_t n)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return x >> (n & 31u);
-#else
-    return n >= 32 ? 0u : x >> n;
-#endif
-}
-// EXTEND (jpeg.inl:2249-2252) of the s bits at the top of the 32-bit word t
+// x >> n for n in 0..31, as the hardware's shift takes it: n mod 32.  n == 32 gives x, not 0 -- on the host too (it used to give 0 there,
+// and a caller that used the result was right in the emulator and wrong on the GPU: jda_q4_block) -- so no caller may use that result
+JDA_HD uint32_t jda_shr_upto32(uint32_t x, uint32_t n) { return x >> (n & 31u); }
+// EXTEND (jpeg.inl:2249-2252) of the s bits at the top of the 32-bit word t, s = 1 .. 31 (s == 0: t itself, see above -- a symbol
+// without magnitude bits has no value)
 JDA_HD int32_t jda_extend_top(uint32_t t, uint32_t s)
 {
     const uint32_t v = jda_shr_upto32(t, 32u - s);
@@ -606,12 +609,14 @@ JDA_HD uint32_t jda_add_byte0(uint32_t a, uint32_t b)
     return a + (b & 0xffu);
 #endif
 }
-JDA_HD uint32_t jda_bfe(uint32_t v, uint32_t off, uint32_t width)          // v_bfe_u32: (v >> off) & ((1 << width) - 1), off + width <= 32
+// v_bfe_u32: (v >> off) & ((1 << width) - 1), off + width <= 32, width <= 31 (the instruction takes off & 31 and width & 31: a width
+// of 32 is a width of 0)
+JDA_HD uint32_t jda_bfe(uint32_t v, uint32_t off, uint32_t width)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_ubfe(v, off, width);
 #else
-    return (v >> off) & ((1u << width) - 1u);
+    return (v >> (off & 31u)) & ((1u << (width & 31u)) - 1u);
 #endif
 }
 JDA_HD uint32_t jda_alignbit(uint32_t hi, uint32_t lo, uint32_t sh)      // low 32 bits of {hi, lo} >> sh, sh = 0..31
@@ -790,7 +795,7 @@ template <bool FAST> JDA_HD int32_t jda_mulc(int32_t x, int32_t c)
     if (FAST) return __mul24(x, c);     // v_mul_i32_i24 (hip_runtime.h is included by the .hip file)
     return x * c;
 #else
-    if (FAST) return (int32_t)((uint32_t)(((int32_t)((uint32_t)x << 8)) >> 8) * (uint32_t)c);   // emulate the 24-bit operand
+    if (FAST) return (int32_t)((uint32_t)jda_sext24(x) * (uint32_t)jda_sext24(c));   // the 24-bit operands of v_mul_i32_i24
     return (int32_t)((uint32_t)x * (uint32_t)c);
 #endif
 }
@@ -3106,7 +3111,9 @@ JDA_HD uint32_t jda_q4_block(uint32_t ix, int32_t dc, jda_q4_bits B, const uint1
             if (roff > 64u && trunc) m &= ~(0xffffffffu >> ((64u + ms - roff) & 31u));      // its window ended inside the magnitude
             roff = jda_ref_refill(roff);
         }
-        const int32_t v = (int16_t)jda_extend_top(m, ms);    // (a symbol without a value is ZRL: it goes past the limit, nothing is stored)
+        // a symbol without magnitude bits stores nothing (:2246, "if (.. && usHuff)"): ZRL goes past the limit, but a run of 1 .. 14 with
+        // no value -- no encoder writes one, a table may hold one -- lands on k = 2 .. 4, and jda_extend_top(m, 0) is m, not 0
+        const int32_t v = ms ? (int32_t)(int16_t)jda_extend_top(m, ms) : 0;
         c1 = k == 1u ? v : c1; c8 = k == 2u ? v : c8; c9 = k == 4u ? v : c9;
         k++;
         if (trip < 3) {
@@ -3658,7 +3665,7 @@ JDA_HD float jda_unpack_half(uint32_t h16)
 #else
     const uint32_t sign = (h16 & 0x8000u) << 16, e = (h16 >> 10) & 31u, m = h16 & 0x3ffu;
     uint32_t bits;
-    if (e == 31u) bits = sign | 0x7f800000u | (m << 13);
+    if (e == 31u) bits = sign | 0x7f800000u | (m << 13) | (m ? 0x00400000u : 0u);      // (v_cvt_f32_f16 quiets a signalling NaN)
     else if (e) bits = sign | ((e + 112u) << 23) | (m << 13);
     else if (!m) bits = sign;
     else {
@@ -3850,7 +3857,7 @@ JDA_HD int32_t jda_rs_mul(uint32_t px, int32_t k)
 #if defined(__HIP_DEVICE_COMPILE__)
     return __mul24((int32_t)px, k);
 #else
-    return (int32_t)px * k;
+    return (int32_t)((uint32_t)jda_sext24((int32_t)px) * (uint32_t)jda_sext24(k));      // (v_mul_i32_i24: bits 23:0 of both, sign-extended)
 #endif
 }
 // the sum's and the tap's type (unsigned with the 24-bit mask as ever, or signed: the host's guard holds every tap inside 24 bits)

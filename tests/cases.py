@@ -768,5 +768,46 @@ def coef_spec(name):
 
 @functools.lru_cache(maxsize=None)
 def coef_jpeg_for(name):
+    if name in RUNONLY_CASES:
+        return _cj.write_jpeg(**runonly_spec(RUNONLY_CASES[name]))
     return _cj.write_jpeg(**coef_spec(name))
+
+
+# AC symbols with a run of 1 .. 14 and NO magnitude bits (0x10, 0x20, 0x30): no encoder writes one, but a table may hold one, and the
+# reference skips the run and stores nothing (jpeg.inl:2246, "if (.. && usHuff)"); libjpeg -- and tests/coef_jpeg.decode_coefs -- end the
+# block there, so these files are no members of COEF_CASES and its round trips.  They take the places of 0x51, 0x61 and 0x71 in the
+# Annex K tables: codes of 7 and 8 bits, so that the 32 stream bits behind such a symbol, shifted left by its length, are not zero in
+# their low half -- which is what a kernel that takes the symbol's "value" from them stores (jda_q4_block did, on the GPU alone).
+RUNONLY_CASES = {"x_runonly_gray": "gray", "x_runonly_c420": "4:2:0"}
+RUNONLY_SYMBOLS = ((0x51, 0x10), (0x61, 0x20), (0x71, 0x30))
+RUNONLY_BLOCKS = ([(1, 0), (0, 0)], [(3, 0), (0, 0)], [(2, 0), (0, 9), (0, 0)], [(1, 0), (1, 0), (0, 0)], [(0, -7), (1, 0), (0, 0)], [(2, 0), (0, 0)])
+
+
+def runonly_spec(sampling):
+    """every other block one of RUNONLY_BLOCKS (the symbols as given: a run without a value lands on zig-zag positions 2, 3 and 4 --
+    coefficients 8, 9 and beyond of the 1/4-scale decode --, before and after a real coefficient), the rest one small coefficient"""
+    hs, vs = _cj.LUMA_HV[sampling]
+    cx, cy = 6, 2
+    width, height = cx * 8 * hs, cy * 8 * vs
+    coefs = _cj.zero_coefs(width, height, sampling)
+    huff = dict(_cj.annex_k()[2])
+    for th in (0, 1):
+        bits, vals = huff[(1, th)]
+        vals = list(vals)
+        for old, new in RUNONLY_SYMBOLS:
+            vals[vals.index(old)] = new
+        huff[(1, th)] = (list(bits), vals)
+    rng = _np.random.default_rng(5)
+    pairs, k = {}, 0
+    for c, arr in enumerate(coefs):
+        flat = arr.reshape(-1, 64)
+        for i in range(flat.shape[0]):
+            flat[i, 0] = int(rng.integers(-60, 60))
+            flat[i, 1 + (i % 5)] = int(rng.integers(-40, 40)) or 3
+        for by in range(arr.shape[0]):
+            for bx in range(arr.shape[1]):
+                if (by + bx + c) % 2 == 0:
+                    pairs[(c, by, bx)] = RUNONLY_BLOCKS[k % len(RUNONLY_BLOCKS)]
+                    k += 1
+    return dict(width=width, height=height, sampling=sampling, coefs=coefs, quant={0: [3] * 64, 1: [5] * 64}, huff=huff, ac_pairs=pairs)
 

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from tests import coef_jpeg as cj
-from tests.cases import COEF_CASES, COEF_CORRUPT, FASTBOUND_Q, all_modes, coef_jpeg_for, coef_spec, custom_ac_table
+from tests.cases import COEF_CASES, COEF_CORRUPT, FASTBOUND_Q, RUNONLY_BLOCKS, RUNONLY_CASES, all_modes, coef_jpeg_for, coef_spec, custom_ac_table
 
 GOOD = sorted(k for k in COEF_CASES if k not in COEF_CORRUPT)
 FAMILIES = ("k_classes_", "k_single_", "k_fastbound_", "k_huff_", "k_dcdrift_", "k_edge_", "k_window_", "k_q4reach_")
@@ -332,3 +332,35 @@ def test_fast_path_reaches_the_range_wrap(layout, hostsim, oracle):
             elif f.max() < 128 - 640:
                 wrapped_lo += bool(np.any(px != 0))
     assert wrapped_hi > 0 and wrapped_lo > 0, (wrapped_hi, wrapped_lo)
+
+
+@pytest.mark.parametrize("name", sorted(RUNONLY_CASES))
+def test_run_symbols_without_magnitude_bits(name, hostsim, oracle):
+    """AC symbols 0x10, 0x20, 0x30 (a run of 1 .. 14, no value): the reference skips the run and stores nothing.  The file is what it
+    claims (such symbols under codes shorter than 16 bits, on zig-zag positions 2 .. 4 of the 1/4-scale decode); the oracle's frames are
+    the recorded hashes of the real reference's; the wave emulator gives the oracle's pixels in every mode.  (The 1/4-scale block
+    decoder took such a symbol's value from jda_extend_top(m, 0): 0 in the emulator as it was, the stream's bits on the GPU.)"""
+    import json
+    import os
+
+    from oracle.loader import digest
+    from tests.cases import GOLDEN_DIR, runonly_spec
+    spec = runonly_spec(RUNONLY_CASES[name])
+    jpeg, lay = cj.write_jpeg(return_layout=True, **spec)
+    assert jpeg == coef_jpeg_for(name)
+    short_runs = 0
+    for c, by, bx, dc_sym, syms in lay["blocks"]:
+        if (c, by, bx) in spec["ac_pairs"]:
+            for (run, v), (pos, ln, s) in zip(spec["ac_pairs"][(c, by, bx)], syms):
+                short_runs += run and v == 0 and ln < 16
+    assert short_runs >= len(RUNONLY_BLOCKS)
+    g = json.load(open(os.path.join(GOLDEN_DIR, "golden.json")))[name]
+    assert digest(jpeg) == g["jpeg_sha"] and len(jpeg) == g["jpeg_len"] and len(g["frames"]) >= 18
+    for key, fr in g["frames"].items():
+        pt, opt = (int(v) for v in key.split(":"))
+        rc, frame = oracle.decode_frame(jpeg, pt, opt)
+        assert fr != "fail" and rc == 1 and digest(frame) == fr.split(":")[0], (name, pt, opt)
+    for pt, opt in all_modes(name):
+        rc, want, hrc, got = _hostsim_decode(hostsim, oracle, jpeg, pt, opt)
+        assert rc == 1 and hrc == 0, (name, pt, opt, hrc, rc)
+        assert np.array_equal(got, want), (name, pt, opt, int(np.count_nonzero(got != want)))

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import jpegdec_amd as J
-from tests.cases import COEF_CASES, COEF_CORRUPT, all_modes, coef_jpeg_for, jpeg_for
+from tests.cases import COEF_CASES, COEF_CORRUPT, RUNONLY_CASES, all_modes, coef_jpeg_for, jpeg_for
 
 pytestmark = pytest.mark.gpu
 
@@ -120,3 +120,16 @@ def test_p1_in_chunks(gpu_ctx, oracle):
                 assert np.array_equal(got, want), (name, pt, opt, int(np.count_nonzero(got != want)))
         finally:
             p.close()
+
+
+@pytest.mark.parametrize("name", sorted(RUNONLY_CASES))
+def test_run_symbols_without_magnitude_bits(name, gpu_ctx, oracle):
+    """AC symbols with a run of 1 .. 14 and no value (tests/cases.py, RUNONLY_CASES): nothing is stored for them, in every pixel type and
+    scale -- the 1/4-scale kernel stored the stream's next bits as coefficients 8 and 9, which only the GPU showed"""
+    jpeg = coef_jpeg_for(name)
+    for pt, opt in all_modes(name):
+        orc, want, err = oracle.decode_canvas(jpeg, pt, opt)
+        rc, got, g = J.decode_to_host(gpu_ctx, jpeg, pt, opt)
+        assert orc == 1 and rc == 0, (name, pt, opt, rc, orc, err)
+        assert got.shape == want.shape
+        assert np.array_equal(got, want), "%s pt=%d opt=%d: %d differing bytes" % (name, pt, opt, int(np.count_nonzero(got != want)))
